@@ -9,13 +9,20 @@ torch.distributed over RCCL) every rank owns its own 2^20-term slice of one N*2^
 scaling, no data-path collective); the only exchange is an all-gather of one 64-byte partial point
 per rank, summed locally through the same library.  `python bench.py --gpus N` started plainly
 launches its N ranks itself (launch_ranks: child processes made before torch or HIP are touched);
-under `python -m torch.distributed.run` the ranks are the launcher's.  For N > 1 the line also holds
+under `python -m torch.distributed.run` the ranks are the launcher's.  For N > 1, `--full` adds
 the STRONG-scaling figures: `msm_strong_scaling` (one 2^20-term MSM over N ranks) and the verify
 legs as BASELINE.json states configs 4 / 5 (one job of proofs split over the ranks).
 
 Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel (k_acc_points) against the
 HBM roofline with the ALGORITHMIC 96 bytes per pair (32-B scalar + 64-B affine point, SURVEY.md
-§8d); `cpu_baseline` times the oracle's restatement of the reference's Straus loop on this host.
+§8d), from the stage events of the timed steps and the committed profiles/traffic.json.
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps of the headline
+MSM and prints the line; nothing else.  `--full` adds every other leg: the window cross-check, the
+live rocprofv3 traffic passes, the `valu` multiply-rate probe, `cpu_baseline` (the oracle's
+restatement of the reference's Straus loop on the host CPU), the 2^16 / registered-basis / batched /
+concurrent / host-buffer MSM legs, the prove and verify legs of every proof shape, and for N > 1
+the strong-scaling figures.  `--dump-outputs DIR` writes what the last timed step returned.
 """
 from __future__ import annotations
 
@@ -159,7 +166,7 @@ def live_msm_traffic(log2n: int, timeout_s: float = 90.0):
     vals = {}
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="bppp_pmc_", dir="/tmp")
-        cmd = [exe, "--pmc", counter, "--output-format", "csv", "-d", d, "-o", "t", "--", sys.executable, os.path.abspath(__file__), "--headline-only", "--no-cpu-baseline",
+        cmd = [exe, "--pmc", counter, "--output-format", "csv", "-d", d, "-o", "t", "--", sys.executable, os.path.abspath(__file__), "--headline-only", "--full", "--no-cpu-baseline",
                "--steps", "4", "--warmup", "2", "--log2n", str(log2n)]
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s, cwd=ROOT, env=dict(os.environ, TMPDIR="/tmp"))
@@ -182,7 +189,7 @@ def live_msm_traffic(log2n: int, timeout_s: float = 90.0):
             return None, "rocprofv3 --pmc %s: %s" % (counter, e)
         finally:
             shutil.rmtree(d, ignore_errors=True)
-    return 2.0 * vals["FETCH_SIZE"] + vals["WRITE_SIZE"], ("measured in this run: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE child passes of `bench.py --headline-only` "
+    return 2.0 * vals["FETCH_SIZE"] + vals["WRITE_SIZE"], ("measured in this run: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE child passes of `bench.py --headline-only --full` "
                                                           "(mean per k_acc_points launch; FETCH_SIZE %.0f B raw x 2 + WRITE_SIZE %.0f B)" % (vals["FETCH_SIZE"], vals["WRITE_SIZE"]))
 
 
@@ -746,7 +753,16 @@ def gpu_device(dev) -> int:
     return dev.index if getattr(dev, "index", None) is not None else 0
 
 
-def launch_ranks(n: int) -> int:
+def dump_outputs(out_dir: str, res) -> None:
+    """--dump-outputs: the point the last timed step returned (the canonical affine sum; the identity is all zeros, as the library writes it)
+    as DIR/msm_result.npy, float64 of shape (2, 8): rows x and y, columns their 32-bit limbs least significant first (exact in float64)."""
+    from bulletproofspp_amd.capi import points_to_array
+    os.makedirs(out_dir, exist_ok=True)
+    limbs = points_to_array([res])[0].view(np.uint32).reshape(2, 8)
+    np.save(os.path.join(out_dir, "msm_result.npy"), limbs.astype(np.float64))
+
+
+def launch_ranks(n: int, argv) -> int:
     """`python bench.py --gpus N` started plainly: this process — which has imported neither torch nor the library and has made no
     HIP call — starts N fresh child processes of this same script (one rank per GPU; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in
     their environment, rendezvous on 127.0.0.1), relays rank 0's JSON line and returns non-zero if any rank failed.  Nothing is
@@ -761,7 +777,7 @@ def launch_ranks(n: int) -> int:
     for r in range(n):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-        procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=env, cwd=ROOT,
+        procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + argv, env=env, cwd=ROOT,
                                       stdout=subprocess.PIPE if r == 0 else sys.stderr, text=True))
     import threading
     out0 = []
@@ -817,12 +833,22 @@ def main():
                                                                   "from their seeds) and asserts the combined point equals it")
     ap.add_argument("--launcher-selftest", action="store_true", help="no GPU: the ranks only rendezvous over gloo, all-gather their rank numbers and shard ranges, "
                                                                     "and rank 0 prints them (the CPU-tier test of the plain `--gpus N` start)")
+    ap.add_argument("--full", action="store_true", help="every leg beside the headline MSM: cross-checks, CPU baselines, other sizes, proof legs, "
+                                                        "per-kernel and roofline probes, strong scaling (off: set up, warm up, time --steps, print)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last step's result as DIR/msm_result.npy "
+                                                                        "(float64 (2, 8): x and y as 32-bit limbs, least significant first)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     global TAMPER_RANK
     TAMPER_RANK = args.tamper_rank
+    extra = args.full and not args.headline_only             # the legs beside the headline
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        raise SystemExit(launch_ranks(args.gpus))          # plain start: become the launcher BEFORE torch / HIP are touched
+        argv = sys.argv[1:]
+        if args.dump_outputs:                                # the ranks start in the repository root: hand them the directory as an absolute path
+            argv = argv + ["--dump-outputs", os.path.abspath(args.dump_outputs)]
+        raise SystemExit(launch_ranks(args.gpus, argv))    # plain start: become the launcher BEFORE torch / HIP are touched
 
     if args.launcher_selftest:
         return launcher_selftest(args)
@@ -872,10 +898,11 @@ def main():
 
     for _ in range(args.warmup):
         res = step()
-    # cross-check two different window decompositions of the same MSM (size-independent property)
-    alt = gpu.msm_device(dsc.data_ptr(), dpts.data_ptr(), n, 13 if args.window != 13 else 12)
-    ref_part = gpu.msm_device(dsc.data_ptr(), dpts.data_ptr(), n, args.window)
-    assert alt == ref_part, "MSM results differ between window widths"
+    if args.full:
+        # cross-check two different window decompositions of the same MSM (size-independent property)
+        alt = gpu.msm_device(dsc.data_ptr(), dpts.data_ptr(), n, 13 if args.window != 13 else 12)
+        ref_part = gpu.msm_device(dsc.data_ptr(), dpts.data_ptr(), n, args.window)
+        assert alt == ref_part, "MSM results differ between window widths"
 
     gpu.profile_enable(True)
     gpu.profile_read(reset=True)
@@ -900,10 +927,12 @@ def main():
     if dist is not None:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
     # STRONG scaling of the MSM metric beside the weak headline: ONE 2^log2n-term MSM, rank r owns the contiguous slice
     # shard_range(n, r, N) of it (here: the first hi - lo pairs of its own inputs), partial points all-gathered and added
     msm_strong = None
-    if world > 1:
+    if world > 1 and args.full:
         from bulletproofspp_amd.dist import shard_range
         lo_, hi_ = shard_range(n, rank, world)
         ns_ = hi_ - lo_
@@ -944,7 +973,7 @@ def main():
 
     # BASELINE config 2: the 2^16-term MSM (the first 2^16 pairs of the same synthetic inputs), same entry point
     small = None
-    if world == 1 and args.log2n > 16 and not args.headline_only:
+    if world == 1 and args.log2n > 16 and extra:
         n16 = 1 << 16
         r16 = gpu.msm_device(dsc.data_ptr(), dpts.data_ptr(), n16, 0)
         gpu.profile_read(reset=True); gpu.profile_enable(True)
@@ -964,7 +993,7 @@ def main():
     # fixed Pedersen basis: the SAME 2^log2n points registered once (bppp_basis: table 2^(c w) P_i built outside the timed region), then
     # MSMs over fresh scalars with one bucket set for all windows.  A separate leg: the headline stays the arbitrary-point MSM.
     fixed = None
-    if world == 1 and not args.headline_only:
+    if world == 1 and extra:
         tb0 = time.perf_counter()
         bas = gpu.basis(dpts.data_ptr(), device=True, n=n)
         torch.cuda.synchronize()
@@ -990,7 +1019,7 @@ def main():
     # arbitrary points (bucket method per instance), the registered basis (one bucket set per instance), and the registered basis with
     # its comb table (every multiple of every window in HBM: one mixed addition per non-zero digit, csrc/comb.hip).
     fixed_batch = None
-    if world == 1 and not args.headline_only:
+    if world == 1 and extra:
         nb, inst = 774, 4096
         rngb = np.random.default_rng(77)
         scb = rngb.integers(0, 2**64, size=(inst * nb, 4), dtype=np.uint64)
@@ -1055,7 +1084,7 @@ def main():
     # (bucket reduction, window combine, the host round trip) overlap the accumulate kernel of another.  Reported beside the
     # single-stream headline, whose per-kernel durations are what the roofline and the rocprof summaries refer to.
     concurrent = None
-    if world == 1 and args.msm_streams > 1 and not args.headline_only:
+    if world == 1 and args.msm_streams > 1 and extra:
         import threading
         ctxs = [b.Bppp(local) for _ in range(args.msm_streams)]
         for c_ in ctxs:
@@ -1082,7 +1111,7 @@ def main():
 
     # the drop-in entry point takes HOST buffers (bppp_msm, what innerProduct's FFI stub calls): PCIe-inclusive rate, never `value`
     host_call = None
-    if world == 1 and not args.headline_only:
+    if world == 1 and extra:
         sc_h = np.ascontiguousarray(dsc.cpu().numpy().view(np.uint64))
         pt_h = np.ascontiguousarray(dpts.cpu().numpy().view(np.uint64))
         assert gpu.msm(sc_h, pt_h) == res
@@ -1096,7 +1125,7 @@ def main():
         del sc_h, pt_h
 
     verify = prove = None
-    if args.verify_batch > 0 and not args.headline_only:
+    if args.verify_batch > 0 and extra:
         vsteps = max(3, args.steps // 2)
         verify, prove = bench_rangeproofs(gpu, torch, dev, rank, world, dist, combine, args.verify_batch, vsteps, 1, "64by64",
                                           cpu_baseline_leg=(world == 1 and not args.no_cpu_baseline), coll_dev=coll_dev)
@@ -1106,11 +1135,11 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             prove["cpu_baseline"] = prove_cpu_baseline("64by64")
     verify_ip = None
-    if world == 1 and args.ip_batch > 0 and not args.headline_only:
+    if world == 1 and args.ip_batch > 0 and extra:
         verify_ip = bench_ip_verify(gpu, torch, dev, args.ip_batch, max(3, args.steps // 2), cpu_baseline_leg=not args.no_cpu_baseline)
 
     verify_binary = None
-    if world == 1 and args.binary_batch > 0 and not args.headline_only:
+    if world == 1 and args.binary_batch > 0 and extra:
         verify_binary = bench_binary_verify(gpu, torch, dev, args.binary_batch, max(3, args.steps // 2), cpu_baseline_leg=not args.no_cpu_baseline)
 
     if rank == 0:
@@ -1121,7 +1150,7 @@ def main():
         acc_ms = stages["acc_points"] / launches
         achieved = BYTES_PER_PAIR * n / (acc_ms * 1e-3) / 1e9 if acc_ms > 0 else 0.0
         traffic, traffic_source = None, None
-        if world == 1 and not args.headline_only and not args.no_live_traffic:
+        if world == 1 and extra and not args.no_live_traffic:
             traffic, traffic_source = live_msm_traffic(args.log2n)
             if traffic is None:
                 traffic_source = "live passes failed (%s); " % traffic_source
@@ -1144,34 +1173,35 @@ def main():
                          "limiter": "valu",
                          "note": "`bound` names the roofline BASELINE.json's north_star asks for (fraction of HBM peak): algorithmic 96 B/pair x 2^%d pairs per launch / "
                                  "mean k_acc_points duration (HIP events).  What binds the kernel is the integer multiplier (256-bit modular multiplications): "
-                                 "`valu` below prices it against the instruction-issue bound" % args.log2n},
+                                 "`valu` (--full) prices it against the instruction-issue bound" % args.log2n},
             "stages_ms_per_step": {k: v * calls / launches for k, v in per_call.items()},
         }
         # the bound that actually binds: modular multiplications of the accumulate kernel against the
         # measured rate of a multiply-only kernel on this chip (test hook bppp_test_mulmod_rate)
-        try:
-            if args.headline_only:
-                raise RuntimeError("skipped (--headline-only)")
-            import ctypes as C
-            from bulletproofspp_amd.capi import load_test_library
-            rate = C.c_double(0.0)
-            if load_test_library().bppp_test_mulmod_rate(gpu.h, 2000, C.byref(rate)) == 0 and rate.value > 0 and acc_ms > 0:
-                c_eff = args.window or 16
-                full, r = 254 // c_eff, 255 - c_eff * (254 // c_eff)
-                adds = n * (full + 1 + (0.5 if r == c_eff else 0.0))
-                mm = adds * 10.0 / (acc_ms * 1e-3)
-                # the issue bound of the multiplier: 1024 SIMDs x 2.4 GHz / 4.8 cycles per v_mad_u64_u32 wave-instruction (benchmarks/valu_microbench.hip)
-                # x 64 lanes / 119 products per multiplication (csrc/fq26.hip.h: 100 + 19 for the 2^260 fold)
-                mad_bound = 1024 * 2.4e9 / 4.8 * 64 / 119.0
-                out["valu"] = {"kernel": "k_acc_points", "achieved": mm / 1e9, "peak": mad_bound / 1e9, "unit": "G mulmod/s", "frac": mm / mad_bound,
-                               "multiply_only_kernel": {"value": rate.value / 1e9, "frac_of_peak": rate.value / mad_bound, "frac_of_it_achieved": mm / rate.value,
-                                                        "note": "bppp_test_mulmod_rate: independent fq_mul chains, 8 waves/SIMD, measured in this run"},
-                               "note": "≈ %.1f M mixed additions per launch x 10 field multiplications (8M+2S) / mean kernel duration, against the v_mad_u64_u32 "
-                                       "issue bound (1024 SIMDs x 2.4 GHz / 4.8 cycles x 64 lanes / 119 products); a multiplication also issues ~32 other 64-bit "
-                                       "instructions at the same cost (profiles/r04_fq_mul_isa_histogram.txt), which is what the multiply-only kernel shows" % (adds / 1e6)}
-        except Exception as e:          # the hook is test-only; the headline does not depend on it
-            out["valu"] = {"error": str(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:                   # a run of the multiply-only kernel of its own
+            try:
+                if args.headline_only:
+                    raise RuntimeError("skipped (--headline-only)")
+                import ctypes as C
+                from bulletproofspp_amd.capi import load_test_library
+                rate = C.c_double(0.0)
+                if load_test_library().bppp_test_mulmod_rate(gpu.h, 2000, C.byref(rate)) == 0 and rate.value > 0 and acc_ms > 0:
+                    c_eff = args.window or 16
+                    full, r = 254 // c_eff, 255 - c_eff * (254 // c_eff)
+                    adds = n * (full + 1 + (0.5 if r == c_eff else 0.0))
+                    mm = adds * 10.0 / (acc_ms * 1e-3)
+                    # the issue bound of the multiplier: 1024 SIMDs x 2.4 GHz / 4.8 cycles per v_mad_u64_u32 wave-instruction (benchmarks/valu_microbench.hip)
+                    # x 64 lanes / 119 products per multiplication (csrc/fq26.hip.h: 100 + 19 for the 2^260 fold)
+                    mad_bound = 1024 * 2.4e9 / 4.8 * 64 / 119.0
+                    out["valu"] = {"kernel": "k_acc_points", "achieved": mm / 1e9, "peak": mad_bound / 1e9, "unit": "G mulmod/s", "frac": mm / mad_bound,
+                                   "multiply_only_kernel": {"value": rate.value / 1e9, "frac_of_peak": rate.value / mad_bound, "frac_of_it_achieved": mm / rate.value,
+                                                            "note": "bppp_test_mulmod_rate: independent fq_mul chains, 8 waves/SIMD, measured in this run"},
+                                   "note": "≈ %.1f M mixed additions per launch x 10 field multiplications (8M+2S) / mean kernel duration, against the v_mad_u64_u32 "
+                                           "issue bound (1024 SIMDs x 2.4 GHz / 4.8 cycles x 64 lanes / 119 products); a multiplication also issues ~32 other 64-bit "
+                                           "instructions at the same cost (profiles/r04_fq_mul_isa_histogram.txt), which is what the multiply-only kernel shows" % (adds / 1e6)}
+            except Exception as e:          # the hook is test-only; the headline does not depend on it
+                out["valu"] = {"error": str(e)}
+        if world == 1 and args.full and not args.no_cpu_baseline:
             sample = 1 << min(args.cpu_sample_log2, args.log2n)
             sc_np = dsc[:sample].cpu().numpy().view(np.uint64)
             pts_np = dpts[:sample].cpu().numpy().view(np.uint64)

@@ -11,7 +11,7 @@ for w in $what; do
   case $w in
     stats)
       run prof_msm   rocprofv3 --kernel-trace --stats --output-format csv -d $G/prof_msm   -o msm   -- python3 bench.py --headline-only --no-cpu-baseline
-      run prof_bench rocprofv3 --kernel-trace --stats --output-format csv -d $G/prof_bench -o bench -- python3 bench.py --no-cpu-baseline
+      run prof_bench rocprofv3 --kernel-trace --stats --output-format csv -d $G/prof_bench -o bench -- python3 bench.py --full --no-cpu-baseline
       BPPP_RP_NO_SPLIT=1 run prof_prove rocprofv3 --kernel-trace --stats --output-format csv -d $G/prof_prove -o prove -- python3 benchmarks/prove_timing.py 4096
       ;;
     msmpmc)

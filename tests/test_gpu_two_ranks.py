@@ -25,7 +25,7 @@ def _json_line(p):
 
 def test_bench_two_ranks_plain_start_both_scaling_modes():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--log2n", "17", "--verify-batch", "256", "--backend", "gloo",
-           "--same-device", "--check-combined", "--no-cpu-baseline", "--msm-streams", "1"]
+           "--same-device", "--check-combined", "--no-cpu-baseline", "--msm-streams", "1", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     out = _json_line(subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT))
@@ -44,7 +44,7 @@ def test_bench_two_ranks_plain_start_both_scaling_modes():
 
 def _plain_start(n, extra):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--log2n", "14", "--verify-batch", str(16 * n), "--ip-batch", "0",
-           "--binary-batch", "0", "--backend", "gloo", "--same-device", "--check-combined", "--no-cpu-baseline", "--msm-streams", "1"] + extra
+           "--binary-batch", "0", "--backend", "gloo", "--same-device", "--check-combined", "--no-cpu-baseline", "--msm-streams", "1", "--full"] + extra
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     return _json_line(subprocess.run(cmd, capture_output=True, text=True, timeout=1100, env=env, cwd=ROOT))
@@ -75,7 +75,7 @@ def test_bench_two_ranks_under_torch_distributed_run():
     port = 29600 + random.randrange(1500)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--log2n", "16", "--verify-batch", "0", "--backend", "gloo",
-           "--same-device", "--no-cpu-baseline", "--msm-streams", "1"]
+           "--same-device", "--no-cpu-baseline", "--msm-streams", "1", "--full"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = _json_line(subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT))
     assert out["n_gpus"] == 2 and out["msm_strong_scaling"]["pairs_per_gpu"] == (1 << 16) // 2
