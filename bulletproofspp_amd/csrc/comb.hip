@@ -17,16 +17,17 @@
 // k_comb_msm_rows (round 4): thousands of LONG rows of full-width scalars (the argument's rounds) over a table of tens of GB — lane = instance, the
 // wavefront walks (term, window) in lockstep and its 64 gathers fall into ONE table row; k_comb_join_rows adds the partial sums of an instance.
 // k_comb_msm_packed: thousands of rows of a few dozen terms (8 or 16 lanes per instance).  k_comb_lanes: one lane per three-term instance.
+//
+// Digits are read in the format of recode.hip.h; comb_gather / CombPipe / comb_walk below are the one table walk the kernels share.
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <string>
 #include "comb.hpp"
 #include "ec.hip.h"
+#include "recode.hip.h"
 
 namespace bppp {
-
-struct CombK { uint32_t k[9]; };       // sum_w 2^(c-1) 2^(c w): adding it turns signed digits into unsigned c-bit fields (as k_digits)
 
 // bases[w][i] = 2^(c w) P_i: one lane per point walks the chain (c doublings and one normalisation per window)
 __global__ void __launch_bounds__(64) k_comb_bases(const uint32_t *__restrict__ pts, uint32_t T, int c, int W, uint32_t *__restrict__ bases) {
@@ -67,11 +68,46 @@ BPPP_DI aff comb_aff(const CombRaw &r, bool neg) {
   aff p; p.x = fq_from_fe(x); p.y = fq_from_fe(y);
   return aff_cneg(p, neg);
 }
+// the entry of signed digit d in window w of a term's table slice ti = tab + i D 16 (zeros unless ok: a non-zero digit of a working lane)
+BPPP_DI CombRaw comb_gather(const uint32_t *ti, uint32_t T, uint32_t D, int w, int d, bool ok) {
+  CombRaw r; r.a = r.b = r.c = r.d = make_uint4(0, 0, 0, 0);
+  if (ok) {
+    const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
+    const uint4 *e = (const uint4 *)(ti + ((size_t)w * T * D + (mag - 1)) * 16);
+    r.a = e[0]; r.b = e[1]; r.c = e[2]; r.d = e[3];
+  }
+  return r;
+}
+// a lane's sum, one step behind its gathers: the entry of the NEXT digit is requested before the addition of the pending one is issued,
+// so a 64-B gather (random over the table: HBM, not cache) hides under one mixed addition
+struct CombPipe {
+  xyzz acc;
+  CombRaw pend;
+  bool pend_ok, pend_neg;
+  BPPP_DI CombPipe() : acc(xyzz_inf()), pend_ok(false), pend_neg(false) { pend.a = pend.b = pend.c = pend.d = make_uint4(0, 0, 0, 0); }
+  BPPP_DI void push(const CombRaw &nxt, bool ok, bool neg) {
+    if (pend_ok) xyzz_madd(acc, comb_aff(pend, pend_neg));
+    pend = nxt; pend_ok = ok; pend_neg = neg;
+  }
+  BPPP_DI void flush() { if (pend_ok) xyzz_madd(acc, comb_aff(pend, pend_neg)); }
+};
+// term i's W windows (scalar s; nz = false: an idle lane or a zero scalar, which requests nothing but keeps in step with the wavefront)
+BPPP_DI void comb_walk(CombPipe &p, const uint32_t *tab, uint32_t T, int c, int W, uint32_t D, const RecodeK &K, uint32_t i, const fe &s, bool nz) {
+  uint32_t sp[9];
+  const bool neg = recode_fold(s, K, sp);
+  const uint32_t *ti = tab + (size_t)i * D * 16;
+#pragma unroll 1
+  for (int w = 0; w < W; w++) {
+    const int d = (int)recode_next(sp, c) - (int)D;
+    const bool ok = nz && d != 0;
+    p.push(comb_gather(ti, T, D, w, d, ok), ok, (d < 0) != neg);
+  }
+}
 
 // heavy_first: the instances come as (heavy, light) pairs — the prover's X (every scalar non-zero) and R (half of them) — and the
 // launch dispatches all heavy ones first, so the light ones fill the slots that free up instead of leaving a tail of heavy ones
 template <int WPE>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) k_comb_msm(const uint32_t *__restrict__ tab, uint32_t T, int c, int W, uint32_t D, CombK K,
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) k_comb_msm(const uint32_t *__restrict__ tab, uint32_t T, int c, int W, uint32_t D, RecodeK K,
                                                  const uint32_t *__restrict__ scalars, uint32_t nterms, uint32_t ninst, int heavy_first, uint32_t parts, uint32_t tparts, int wlen,
                                                  uint32_t *__restrict__ partial, uint32_t *__restrict__ out) {
   // parts > 1 (few instances): `parts` = tparts x (window ranges of wlen windows) wavefronts share one instance — wavefront (tp, wr) takes the
@@ -80,11 +116,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
   const uint32_t lane = threadIdx.x, half = ninst >> 1, blk = blockIdx.x / parts, part = blockIdx.x % parts, tpart = part % tparts;
   const int w0 = (int)(part / tparts) * wlen, w1 = min(W, w0 + wlen);
   const uint32_t inst = !heavy_first ? blk : blk < half ? 2 * blk : 2 * (blk - half) + 1;
-  const uint32_t mask = (1u << c) - 1u;
   const uint32_t *sc = scalars + (size_t)inst * nterms * 8;       // the first nterms <= T registered points
-  xyzz acc = xyzz_inf();
-  CombRaw pend; pend.a = pend.b = pend.c = pend.d = make_uint4(0, 0, 0, 0);
-  bool pend_ok = false, pend_neg = false;
+  CombPipe p;
   // Lane l takes one term of every group of 64, rotated by 21 per group, and walks ITS terms at its own pace: a lane whose term is
   // zero moves straight on to its next non-zero one instead of idling through the other lanes' 20 digit steps.  With vectors whose
   // zeros follow a power-of-two pattern in the index (the argument's R scalars vanish on every left half) every lane then has the
@@ -102,25 +135,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
         if (i >= nterms) continue;
         const fe s = fe_load(sc + (size_t)i * 8);
         if (fe_is_zero(s)) continue;
-        fe t, tmp;
-        raw_sub(t, fr_modulus(), s);                           // n - s
-        neg = raw_sub(tmp, t, s) != 0;                         // s > n - s: take n - s and the negated point (reduceScalar, Commitment.hs:276-279)
+        fe v;
+        neg = recode_fold(s, K, sp, v);
         // a SHORT scalar (range-proof digits, bits, multiplicities) has no digit beyond window ceil(bits / c) (that one only as a carry): its lane
         // moves on after those instead of stepping through all W windows
         uint32_t hw = 1u; int top = 0;
 #pragma unroll
-        for (int q = 0; q < 8; q++) { const uint32_t v = neg ? t.v[q] : s.v[q]; if (v) { hw = v; top = q; } }
+        for (int q = 0; q < 8; q++) if (v.v[q]) { hw = v.v[q]; top = q; }
         const int nw = (32 * top + (32 - __builtin_clz(hw)) + c - 1) / c + 1;
         if (nw <= w0) continue;                                // nothing of this term in this wavefront's window range
-        uint64_t cy = 0;
-#pragma unroll
-        for (int q = 0; q < 8; q++) { cy += (uint64_t)(neg ? t.v[q] : s.v[q]) + K.k[q]; sp[q] = (uint32_t)cy; cy >>= 32; }
-        sp[8] = (uint32_t)cy + K.k[8];
-        for (int j = 0; j < w0; j++) {                          // skip the windows of the other ranges
-#pragma unroll
-          for (int q = 0; q < 8; q++) sp[q] = (sp[q] >> c) | (sp[q + 1] << (32 - c));
-          sp[8] >>= c;
-        }
+        for (int j = 0; j < w0; j++) recode_next(sp, c);       // skip the windows of the other ranges
         ti = tab + (size_t)i * D * 16;
         wend = min(w1, nw);
         w = w0; live = true;
@@ -130,22 +154,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     CombRaw nxt; nxt.a = nxt.b = nxt.c = nxt.d = make_uint4(0, 0, 0, 0);
     bool ok = false, nneg = false;
     if (live) {
-      const int d = (int)(sp[0] & mask) - (int)D;              // signed digit in [-D, D - 1]
-#pragma unroll
-      for (int q = 0; q < 8; q++) sp[q] = (sp[q] >> c) | (sp[q + 1] << (32 - c));
-      sp[8] >>= c;
+      const int d = (int)recode_next(sp, c) - (int)D;              // signed digit in [-D, D - 1]
       ok = d != 0; nneg = (d < 0) != neg;
-      if (ok) {
-        const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-        const uint4 *e = (const uint4 *)(ti + ((size_t)w * T * D + (mag - 1)) * 16);
-        nxt.a = e[0]; nxt.b = e[1]; nxt.c = e[2]; nxt.d = e[3];
-      }
+      nxt = comb_gather(ti, T, D, w, d, ok);
       w++;
     }
-    if (pend_ok) xyzz_madd(acc, comb_aff(pend, pend_neg));     // the previous digit's entry: its load was issued one step ago
-    pend = nxt; pend_ok = ok; pend_neg = nneg;
+    p.push(nxt, ok, nneg);
   }
-  if (pend_ok) xyzz_madd(acc, comb_aff(pend, pend_neg));
+  p.flush();
+  xyzz &acc = p.acc;
   for (int dd = 32; dd >= 1; dd >>= 1) {
     xyzz o = xyzz_shfl_down(acc, dd);
     if ((int)lane + dd < 64) xyzz_add(acc, o);
@@ -160,53 +177,25 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
 // serve an instance (64 / LPI instances per wavefront), each lane walks ceil(nterms / LPI) terms, a log2(LPI)-level segmented tree joins them and the
 // 64 / LPI inversions of a wavefront run side by side.
 template <int LPI>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) k_comb_msm_packed(const uint32_t *__restrict__ tab, uint32_t T, int c, int W, uint32_t D, CombK K,
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) k_comb_msm_packed(const uint32_t *__restrict__ tab, uint32_t T, int c, int W, uint32_t D, RecodeK K,
                                                                                                   const uint32_t *__restrict__ scalars, uint32_t nterms, uint32_t ninst,
                                                                                                   uint32_t *__restrict__ out) {
   const uint32_t sub = threadIdx.x % LPI, inst = blockIdx.x * (64 / LPI) + threadIdx.x / LPI;
   const bool active = inst < ninst;
-  const uint32_t mask = (1u << c) - 1u;
   const uint32_t *sc = scalars + (size_t)(active ? inst : 0) * nterms * 8;
-  xyzz acc = xyzz_inf();
-  CombRaw pend; pend.a = pend.b = pend.c = pend.d = make_uint4(0, 0, 0, 0);
-  bool pend_ok = false, pend_neg = false;
+  CombPipe p;
   for (uint32_t i = sub; i < nterms; i += LPI) {
     fe s = fe_load(sc + (size_t)i * 8);
     if (!active) s = fe_zero();
-    const bool nz = !fe_is_zero(s);
-    fe t, tmp;
-    raw_sub(t, fr_modulus(), s);
-    const bool neg = raw_sub(tmp, t, s) != 0;                    // reduceScalar (Commitment.hs:276-279)
-    uint32_t sp[9];
-    uint64_t cy = 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) { cy += (uint64_t)(neg ? t.v[q] : s.v[q]) + K.k[q]; sp[q] = (uint32_t)cy; cy >>= 32; }
-    sp[8] = (uint32_t)cy + K.k[8];
-    const uint32_t *ti = tab + (size_t)i * D * 16;
-#pragma unroll 1
-    for (int w = 0; w < W; w++) {
-      const int d = (int)(sp[0] & mask) - (int)D;
-#pragma unroll
-      for (int q = 0; q < 8; q++) sp[q] = (sp[q] >> c) | (sp[q + 1] << (32 - c));
-      sp[8] >>= c;
-      CombRaw nxt; nxt.a = nxt.b = nxt.c = nxt.d = make_uint4(0, 0, 0, 0);
-      const bool ok = nz && d != 0, nneg = (d < 0) != neg;
-      if (ok) {
-        const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-        const uint4 *e = (const uint4 *)(ti + ((size_t)w * T * D + (mag - 1)) * 16);
-        nxt.a = e[0]; nxt.b = e[1]; nxt.c = e[2]; nxt.d = e[3];
-      }
-      if (pend_ok) xyzz_madd(acc, comb_aff(pend, pend_neg));
-      pend = nxt; pend_ok = ok; pend_neg = nneg;
-    }
+    comb_walk(p, tab, T, c, W, D, K, i, s, !fe_is_zero(s));
   }
-  if (pend_ok) xyzz_madd(acc, comb_aff(pend, pend_neg));
+  p.flush();
 #pragma unroll
   for (int dd = LPI / 2; dd >= 1; dd >>= 1) {
-    xyzz o = xyzz_shfl_down(acc, dd);
-    if ((int)sub + dd < LPI) xyzz_add(acc, o);
+    xyzz o = xyzz_shfl_down(p.acc, dd);
+    if ((int)sub + dd < LPI) xyzz_add(p.acc, o);
   }
-  if (sub == 0 && active) aff_store(out + (size_t)inst * 16, xyzz_to_aff(acc));
+  if (sub == 0 && active) aff_store(out + (size_t)inst * 16, xyzz_to_aff(p.acc));
 }
 
 // LONG rows of FULL-WIDTH scalars, thousands of them (the lockstep argument's round commitments: 2 x batch rows over the whole basis): lane = INSTANCE.
@@ -216,10 +205,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 // A wavefront takes `clen` consecutive terms of 64 instances and parks the 64 partial sums for k_comb_join_rows; with `pairs` the even (heavy) instances
 // are dispatched before the odd (light) ones, whose scalars vanish on a pattern that is the same for every instance (a wave-uniform skip).
 template <int WPE>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) k_comb_msm_rows(const uint32_t *__restrict__ tab, uint32_t T, int c, int W, uint32_t D, CombK K,
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) k_comb_msm_rows(const uint32_t *__restrict__ tab, uint32_t T, int c, int W, uint32_t D, RecodeK K,
                                                  const uint32_t *__restrict__ scalars, uint32_t nterms, uint32_t ninst, int pairs, uint32_t ngroups, uint32_t chunks, uint32_t clen,
                                                  uint32_t *__restrict__ partial) {
-  const uint32_t lane = threadIdx.x, mask = (1u << c) - 1u;
+  const uint32_t lane = threadIdx.x;
   uint32_t inst, chunk;
   if (pairs) {                                                  // ngroups = groups of 64 PAIRS; blocks [0, chunks x ngroups) are the even instances
     const uint32_t par = blockIdx.x / (chunks * ngroups), rem = blockIdx.x % (chunks * ngroups);
@@ -228,42 +217,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WP
   const bool active = inst < ninst;
   const uint32_t *sc = scalars + (size_t)(active ? inst : 0) * nterms * 8;
   const uint32_t i0 = chunk * clen, i1 = min(nterms, i0 + clen);
-  xyzz acc = xyzz_inf();
-  CombRaw pend; pend.a = pend.b = pend.c = pend.d = make_uint4(0, 0, 0, 0);
-  bool pend_ok = false, pend_neg = false;
+  CombPipe p;
   for (uint32_t i = i0; i < i1; i++) {
     fe s = fe_load(sc + (size_t)i * 8);
     if (!active) s = fe_zero();
     const bool nz = !fe_is_zero(s);
     if (!__any(nz)) continue;
-    fe t, tmp;
-    raw_sub(t, fr_modulus(), s);
-    const bool neg = raw_sub(tmp, t, s) != 0;                    // reduceScalar (Commitment.hs:276-279)
-    uint32_t sp[9];
-    uint64_t cy = 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) { cy += (uint64_t)(neg ? t.v[q] : s.v[q]) + K.k[q]; sp[q] = (uint32_t)cy; cy >>= 32; }
-    sp[8] = (uint32_t)cy + K.k[8];
-    const uint32_t *ti = tab + (size_t)i * D * 16;
-#pragma unroll 1
-    for (int w = 0; w < W; w++) {
-      const int d = (int)(sp[0] & mask) - (int)D;
-#pragma unroll
-      for (int q = 0; q < 8; q++) sp[q] = (sp[q] >> c) | (sp[q + 1] << (32 - c));
-      sp[8] >>= c;
-      CombRaw nxt; nxt.a = nxt.b = nxt.c = nxt.d = make_uint4(0, 0, 0, 0);
-      const bool ok = nz && d != 0, nneg = (d < 0) != neg;
-      if (ok) {
-        const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-        const uint4 *e = (const uint4 *)(ti + ((size_t)w * T * D + (mag - 1)) * 16);
-        nxt.a = e[0]; nxt.b = e[1]; nxt.c = e[2]; nxt.d = e[3];
-      }
-      if (pend_ok) xyzz_madd(acc, comb_aff(pend, pend_neg));
-      pend = nxt; pend_ok = ok; pend_neg = nneg;
-    }
+    comb_walk(p, tab, T, c, W, D, K, i, s, nz);
   }
-  if (pend_ok) xyzz_madd(acc, comb_aff(pend, pend_neg));
-  if (active) xyzz_store(partial + ((size_t)inst * chunks + chunk) * XYZZ_WORDS, acc);
+  p.flush();
+  if (active) xyzz_store(partial + ((size_t)inst * chunks + chunk) * XYZZ_WORDS, p.acc);
 }
 // the `parts` partial sums of an instance (any count): LPI lanes serve an instance (64 / LPI instances per wavefront) — lane s adds the partials s, s + LPI, ...,
 // a log2(LPI)-level segmented shuffle tree joins the lanes, lane 0 of the segment normalises.  (With 64 lanes per instance whatever the count, the 6-level
@@ -290,86 +253,45 @@ __global__ void __launch_bounds__(64) k_comb_join_rows(const uint32_t *__restric
 // coefficients of a proof over [g | lin | norm] (g's slot unused); group q of 2^L consecutive points of the lin part, then of the norm part, is summed with
 // its coefficients into out[inst][1 + q] (canonical affine; out[inst][0] is not written).  Lane = instance as in k_comb_msm_rows: one wavefront per
 // (64 instances, group), nothing to join.
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) k_comb_msm_groups(const uint32_t *__restrict__ tab, uint32_t T, int c, int W, uint32_t D, CombK K,
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) k_comb_msm_groups(const uint32_t *__restrict__ tab, uint32_t T, int c, int W, uint32_t D, RecodeK K,
                                                  const uint32_t *__restrict__ scalars, uint32_t nterms, uint32_t ninst, uint32_t ngroups, uint32_t l0, uint32_t n0, int L, uint32_t l0r,
                                                  uint32_t out_stride, uint32_t *__restrict__ out) {
-  const uint32_t lane = threadIdx.x, mask = (1u << c) - 1u;
+  const uint32_t lane = threadIdx.x;
   const uint32_t q = blockIdx.x / ngroups, inst = (blockIdx.x % ngroups) * 64u + lane;
   const bool active = inst < ninst;
   const uint32_t *sc = scalars + (size_t)(active ? inst : 0) * nterms * 8;
   uint32_t i0, i1;
   if (q < l0r) { i0 = 1u + (q << L); i1 = min(1u + l0, i0 + (1u << L)); }
   else { i0 = 1u + l0 + ((q - l0r) << L); i1 = min(1u + l0 + n0, i0 + (1u << L)); }
-  xyzz acc = xyzz_inf();
-  CombRaw pend; pend.a = pend.b = pend.c = pend.d = make_uint4(0, 0, 0, 0);
-  bool pend_ok = false, pend_neg = false;
+  CombPipe p;
   for (uint32_t i = i0; i < i1; i++) {
     fe s = fe_load(sc + (size_t)i * 8);
     if (!active) s = fe_zero();
     const bool nz = !fe_is_zero(s);
     if (!__any(nz)) continue;
-    fe t, tmp;
-    raw_sub(t, fr_modulus(), s);
-    const bool neg = raw_sub(tmp, t, s) != 0;                    // reduceScalar (Commitment.hs:276-279)
-    uint32_t sp[9];
-    uint64_t cy = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) { cy += (uint64_t)(neg ? t.v[k] : s.v[k]) + K.k[k]; sp[k] = (uint32_t)cy; cy >>= 32; }
-    sp[8] = (uint32_t)cy + K.k[8];
-    const uint32_t *ti = tab + (size_t)i * D * 16;
-#pragma unroll 1
-    for (int w = 0; w < W; w++) {
-      const int d = (int)(sp[0] & mask) - (int)D;
-#pragma unroll
-      for (int k = 0; k < 8; k++) sp[k] = (sp[k] >> c) | (sp[k + 1] << (32 - c));
-      sp[8] >>= c;
-      CombRaw nxt; nxt.a = nxt.b = nxt.c = nxt.d = make_uint4(0, 0, 0, 0);
-      const bool ok = nz && d != 0, nneg = (d < 0) != neg;
-      if (ok) {
-        const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-        const uint4 *e = (const uint4 *)(ti + ((size_t)w * T * D + (mag - 1)) * 16);
-        nxt.a = e[0]; nxt.b = e[1]; nxt.c = e[2]; nxt.d = e[3];
-      }
-      if (pend_ok) xyzz_madd(acc, comb_aff(pend, pend_neg));
-      pend = nxt; pend_ok = ok; pend_neg = nneg;
-    }
+    comb_walk(p, tab, T, c, W, D, K, i, s, nz);
   }
-  if (pend_ok) xyzz_madd(acc, comb_aff(pend, pend_neg));
-  if (active) aff_store(out + ((size_t)inst * out_stride + 1u + q) * 16, xyzz_to_aff(acc));
+  p.flush();
+  if (active) aff_store(out + ((size_t)inst * out_stride + 1u + q) * 16, xyzz_to_aff(p.acc));
 }
 
 // MANY instances of a FEW terms each (the prover's input commitments v g + ty H0 + bl H1: batch x #values instances over the first
 // three registered points): one LANE per instance walks its terms and digits; zero scalars and zero digits cost nothing
-__global__ void __launch_bounds__(64) k_comb_lanes(const uint32_t *__restrict__ tab, uint32_t T, int c, int W, uint32_t D, CombK K,
+__global__ void __launch_bounds__(64) k_comb_lanes(const uint32_t *__restrict__ tab, uint32_t T, int c, int W, uint32_t D, RecodeK K,
                                                    const uint32_t *__restrict__ scalars, uint32_t nterms, uint64_t ninst, uint32_t *__restrict__ out) {
   const uint64_t inst = (uint64_t)blockIdx.x * 64 + threadIdx.x;
   if (inst >= ninst) return;
-  const uint32_t mask = (1u << c) - 1u;
   xyzz acc = xyzz_inf();
   for (uint32_t i = 0; i < nterms; i++) {
     const fe s = fe_load(scalars + (inst * nterms + i) * 8);
     if (fe_is_zero(s)) continue;
-    fe t, tmp;
-    raw_sub(t, fr_modulus(), s);
-    const bool neg = raw_sub(tmp, t, s) != 0;
     uint32_t sp[9];
-    uint64_t cy = 0;
-#pragma unroll
-    for (int q = 0; q < 8; q++) { cy += (uint64_t)(neg ? t.v[q] : s.v[q]) + K.k[q]; sp[q] = (uint32_t)cy; cy >>= 32; }
-    sp[8] = (uint32_t)cy + K.k[8];
+    const bool neg = recode_fold(s, K, sp);
     const uint32_t *ti = tab + (size_t)i * D * 16;
 #pragma unroll 1
     for (int w = 0; w < W; w++) {
-      const int d = (int)(sp[0] & mask) - (int)D;
-#pragma unroll
-      for (int q = 0; q < 8; q++) sp[q] = (sp[q] >> c) | (sp[q + 1] << (32 - c));
-      sp[8] >>= c;
-      if (d) {
-        const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
-        const uint4 *e = (const uint4 *)(ti + ((size_t)w * T * D + (mag - 1)) * 16);
-        CombRaw r; r.a = e[0]; r.b = e[1]; r.c = e[2]; r.d = e[3];
-        xyzz_madd(acc, comb_aff(r, (d < 0) != neg));
-      }
+      const int d = (int)recode_next(sp, c) - (int)D;
+      if (d) xyzz_madd(acc, comb_aff(comb_gather(ti, T, D, w, d, true), (d < 0) != neg));
     }
   }
   aff_store(out + inst * 16, xyzz_to_aff(acc));
@@ -426,8 +348,7 @@ int comb_create(bppp_ctx *ctx, const uint32_t *d_points, size_t T, int window_bi
 int comb_lanes(const CombTable *t, const uint32_t *d_scalars, size_t nterms, size_t ninst, uint32_t *d_out_aff, hipStream_t st) {
   if (!t || !d_scalars || !d_out_aff || !nterms || nterms > t->T) return BPPP_ERR_ARG;
   if (!ninst) return BPPP_OK;
-  CombK K; memset(&K, 0, sizeof K);
-  for (int w = 0; w < t->W; w++) { const int bit = w * t->c + t->c - 1; if (bit < 288) K.k[bit >> 5] |= 1u << (bit & 31); }
+  const RecodeK K = make_recode_k(t->c, t->W);
   k_comb_lanes<<<dim3((unsigned)((ninst + 63) / 64)), dim3(64), 0, st>>>(t->tab, (uint32_t)t->T, t->c, t->W, (uint32_t)t->D, K, d_scalars, (uint32_t)nterms, (uint64_t)ninst, d_out_aff);
   if (hipGetLastError() != hipSuccess) return fail(t->ctx, BPPP_ERR_HIP, "comb_lanes: launch failed");
   return BPPP_OK;
@@ -437,8 +358,7 @@ int comb_groups(const CombTable *t, const uint32_t *d_scalars, size_t ninst, siz
   if (!t || !d_scalars || !d_out_aff || !ninst || 1 + l0 + n0 != t->T || L < 1 || L > 20) return BPPP_ERR_ARG;
   const size_t l0r = (l0 + ((size_t)1 << L) - 1) >> L, n0r = (n0 + ((size_t)1 << L) - 1) >> L, ngroups = (ninst + 63) / 64;
   if (out_stride < 1 + l0r + n0r || ngroups * (l0r + n0r) >= (1ull << 31)) return BPPP_ERR_ARG;
-  CombK K; memset(&K, 0, sizeof K);
-  for (int w = 0; w < t->W; w++) { const int bit = w * t->c + t->c - 1; if (bit < 288) K.k[bit >> 5] |= 1u << (bit & 31); }
+  const RecodeK K = make_recode_k(t->c, t->W);
   k_comb_msm_groups<<<dim3((unsigned)(ngroups * (l0r + n0r))), dim3(64), 0, st>>>(t->tab, (uint32_t)t->T, t->c, t->W, (uint32_t)t->D, K, d_scalars, (uint32_t)t->T, (uint32_t)ninst,
                                                                                (uint32_t)ngroups, (uint32_t)l0, (uint32_t)n0, L, (uint32_t)l0r, (uint32_t)out_stride, d_out_aff);
   if (hipGetLastError() != hipSuccess) return fail(t->ctx, BPPP_ERR_HIP, "comb_groups: launch failed");
@@ -450,10 +370,9 @@ int comb_msm(const CombTable *t, const uint32_t *d_scalars, size_t ninst, uint32
   if (!t || !d_scalars || !d_out_aff || ninst >= (1u << 31) || nterms > t->T) return BPPP_ERR_ARG;
   if (!nterms) nterms = t->T;
   if (!ninst) return BPPP_OK;
-  CombK K; memset(&K, 0, sizeof K);
-  for (int w = 0; w < t->W; w++) { const int bit = w * t->c + t->c - 1; if (bit < 288) K.k[bit >> 5] |= 1u << (bit & 31); }
+  const RecodeK K = make_recode_k(t->c, t->W);
   // a few dozen terms per instance, thousands of instances: several instances per wavefront (k_comb_msm_packed)
-  if (nterms <= 48 && ninst >= 512 && !t->ctx->tune.comb_no_packed) {
+  if (nterms <= 48 && ninst >= 512) {
     const unsigned lpi = nterms <= 24 ? 8 : 16;
     const unsigned grid_p = (unsigned)((ninst * lpi + 63) / 64);
     if (lpi == 8) k_comb_msm_packed<8><<<dim3(grid_p), dim3(64), 0, st>>>(t->tab, (uint32_t)t->T, t->c, t->W, (uint32_t)t->D, K, d_scalars, (uint32_t)nterms, (uint32_t)ninst, d_out_aff);
@@ -507,7 +426,7 @@ int comb_msm(const CombTable *t, const uint32_t *d_scalars, size_t ninst, uint32
   if (d_scratch && ninst < target && groups > 1) {
     tparts = std::min<uint32_t>(std::min<uint32_t>(groups, 64u), (uint32_t)((target + ninst - 1) / ninst));
     while (tparts > 1 && (size_t)ninst * tparts * XYZZ_WORDS * 4 > scratch_bytes) tparts--;
-    if (tparts == groups && !t->ctx->tune.comb_no_wsplit) {
+    if (tparts == groups) {
       wsplit = std::min<uint32_t>(std::min<uint32_t>(64u / tparts, 4u), (uint32_t)(1024 / std::max<size_t>(1, ninst * tparts)));
       while (wsplit > 1 && (size_t)ninst * tparts * wsplit * XYZZ_WORDS * 4 > scratch_bytes) wsplit--;
       if (wsplit < 1) wsplit = 1;

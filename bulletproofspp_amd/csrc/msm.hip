@@ -5,7 +5,7 @@
 // different algorithm that yields the same group element:
 //
 //   1. k_digits      reduceScalar's sign fold (Commitment.hs:276-279, :366) + signed c-bit window
-//                    recode; coalesced 32-B scalar loads, u16 digits out.
+//                    recode (the format of recode.hip.h); coalesced 32-B scalar loads, u16 digits out.
 //   2. k_hist / k_scan* / k_scatter
 //                    counting sort of (window, |digit|) keys: the bucket histogram and cursors are
 //                    staged in LDS (<= 128 KiB per workgroup), so HBM sees only coalesced streams.
@@ -29,11 +29,10 @@
 #include "ctx.hpp"
 #include "ec.hip.h"
 #include "hostmath.hpp"
+#include "recode.hip.h"
 
 namespace bppp {
 
-
-struct RecodeK { uint32_t k[9]; };
 
 // ------------------------------------------------------------------------------------------------
 // 1. digits
@@ -46,27 +45,14 @@ __global__ void __launch_bounds__(256) k_digits(const uint32_t *__restrict__ sca
   bool valid = i < total;
   bool neg = false;
   if (valid) {
-    fe s = fe_load(scalars + 8 * i);
-    fe t, tmp;
-    raw_sub(t, fr_modulus(), s);               // n - s
-    neg = raw_sub(tmp, t, s) != 0;             // t < s  <=>  s > n - s   (reduceScalar, Commitment.hs:279)
     uint32_t sp[9];
-    uint64_t cy = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      cy += (uint64_t)(neg ? t.v[k] : s.v[k]) + K.k[k];
-      sp[k] = (uint32_t)cy; cy >>= 32;
-    }
-    sp[8] = (uint32_t)cy + K.k[8];
+    neg = recode_fold(fe_load(scalars + 8 * i), K, sp);
     uint32_t inst = (uint32_t)(i / n), j = (uint32_t)(i % n);
     size_t base = (size_t)inst * W * stride + j;
     for (int w = 0; w < W; w++) {
       const int cw = w < acnt ? c : c - 1;
-      const uint32_t mask = (1u << cw) - 1u, bias = w < acnt ? 0u : (1u << (c - 2));
-      dig[base + (size_t)w * stride] = (uint16_t)((sp[0] & mask) + bias);
-#pragma unroll
-      for (int k = 0; k < 8; k++) sp[k] = (sp[k] >> cw) | (sp[k + 1] << (32 - cw));
-      sp[8] >>= cw;
+      const uint32_t bias = w < acnt ? 0u : (1u << (c - 2));
+      dig[base + (size_t)w * stride] = (uint16_t)(recode_next(sp, cw) + bias);
     }
   }
   unsigned long long m = __ballot(valid && neg);
@@ -564,18 +550,11 @@ __global__ void __launch_bounds__(256) k_msm_small(const uint32_t *__restrict__ 
   const uint32_t bit0 = (int)w < acnt ? (uint32_t)c * w : (uint32_t)(c * acnt + (c - 1) * ((int)w - acnt)), mask = (1u << cw) - 1u;
   const int half = 1 << (cw - 1);
   for (uint32_t j = tid; j < n; j += 256) {
-    const fe s_ = fe_load(scalars + (size_t)j * 8);
-    fe t, tmp;
-    raw_sub(t, fr_modulus(), s_);
-    const bool neg = raw_sub(tmp, t, s_) != 0;                     // s > n - s (reduceScalar, Commitment.hs:279)
-    uint32_t sp[10];
-    uint64_t cy = 0;
+    uint32_t sp[9];
+    const bool neg = recode_fold(fe_load(scalars + (size_t)j * 8), K, sp);
+    uint32_t lo = 0, hi = 0;                                        // the two limbs around bit0 (above sp[8]: zero)
 #pragma unroll
-    for (int q = 0; q < 8; q++) { cy += (uint64_t)(neg ? t.v[q] : s_.v[q]) + K.k[q]; sp[q] = (uint32_t)cy; cy >>= 32; }
-    sp[8] = (uint32_t)cy + K.k[8]; sp[9] = 0;
-    uint32_t lo = 0, hi = 0;
-#pragma unroll
-    for (int q = 0; q < 9; q++) if ((bit0 >> 5) == (uint32_t)q) { lo = sp[q]; hi = sp[q + 1]; }
+    for (int q = 0; q < 9; q++) if ((bit0 >> 5) == (uint32_t)q) { lo = sp[q]; hi = q < 8 ? sp[q + 1] : 0u; }
     const uint32_t sh = bit0 & 31u;
     const uint32_t d = (uint32_t)((((uint64_t)hi << 32) | lo) >> sh) & mask;
     const int v = (int)d - half;
@@ -794,19 +773,6 @@ static MsmPlan make_plan(size_t n, size_t batch, int c, bool flat, const MsmTune
   p.G = (p.total_max + p.L - 1) / p.L; if (!p.G) p.G = 1;
   p.ntiles = (int)((p.FB + SCAN_TILE - 1) / SCAN_TILE);
   return p;
-}
-
-// sets K = sum_{w<W} 2^(c-1) * 2^(w*c) as 9 x 32-bit limbs
-static RecodeK make_recode_k(int c, int W, int acnt = -1) {
-  RecodeK K; memset(&K, 0, sizeof K);
-  if (acnt < 0) acnt = W;
-  int off = 0;
-  for (int w = 0; w < W; w++) {
-    const int cw = w < acnt ? c : c - 1, bit = off + cw - 1;
-    if (bit < 288) K.k[bit >> 5] |= 1u << (bit & 31);
-    off += cw;
-  }
-  return K;
 }
 
 int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_t n, size_t batch, int shared_points, int window_bits, uint64_t *out_xy,
