@@ -30,6 +30,7 @@ SYMBOLS = [
     "bppp_glv_decompose_device", "bppp_msm_glv_device",
     "bppp_basis_create", "bppp_basis_create_device", "bppp_basis_destroy", "bppp_basis_info", "bppp_msm_basis", "bppp_basis_enable_comb",
     "bppp_rp_create", "bppp_rp_create_binary", "bppp_rp_destroy", "bppp_rp_info", "bppp_rp_set_option", "bppp_rp_shape_of", "bppp_rp_digits", "bppp_hash_to_scalar", "bppp_rp_verify_batch", "bppp_rp_verify_batch_device", "bppp_rp_verify_shard_device", "bppp_rp_prove_batch",
+    "bppp_rp_verify_mixed", "bppp_rp_verify_mixed_device",
 ]
 
 
@@ -132,6 +133,8 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_verify_batch_device.argtypes = [vp, sz, vp, vp, vp, C.POINTER(i), vp, vp, vp]
     lib.bppp_rp_verify_shard_device.argtypes = [vp, sz, C.c_uint64, vp, vp, vp, C.POINTER(i), vp, vp, vp]
     lib.bppp_rp_prove_batch.argtypes = [vp, sz, vp, vp, vp, vp, sz, vp, vp]
+    lib.bppp_rp_verify_mixed.argtypes = [vp, sz, vp, C.POINTER(i), vp, vp]
+    lib.bppp_rp_verify_mixed_device.argtypes = [vp, sz, C.c_uint64, vp, C.POINTER(i), vp, vp]
     lib.bppp_profile_enable.argtypes = [vp, i]
     lib.bppp_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), i]
     return lib
@@ -148,6 +151,7 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_fe_op.argtypes = [vp, i, i, vp, vp, sz, vp]
     lib.bppp_test_point_op.argtypes = [vp, i, vp, vp, sz, vp]
     lib.bppp_test_mulmod_rate.argtypes = [vp, i, C.POINTER(C.c_double)]
+    lib.bppp_test_last_mixed_msm_terms.argtypes = [vp, C.POINTER(C.c_uint64)]
     return lib
 
 
@@ -159,6 +163,11 @@ class RpRange(C.Structure):
 class RpPublic(C.Structure):
     """bppp_rp_public"""
     _fields_ = [("is_output", C.c_uint32), ("reserved", C.c_uint32), ("type", C.c_uint64 * 4), ("amount", C.c_uint64 * 4)]
+
+
+class RpGroup(C.Structure):
+    """bppp_rp_group: one setup's share of a mixed batch"""
+    _fields_ = [("rp", C.c_void_p), ("batch", C.c_size_t), ("coms_files", C.c_void_p), ("proof_files", C.c_void_p)]
 
 
 class RpShape(C.Structure):

@@ -26,6 +26,7 @@ void ctx_release(bppp_ctx *ctx) {
   if (ctx->aux_stream) hipStreamSynchronize(ctx->aux_stream);
   if (ctx->ws) hipFree(ctx->ws);
   if (ctx->ws2) hipFree(ctx->ws2);
+  if (ctx->mix) hipFree(ctx->mix);
   if (ctx->pinned) hipHostFree(ctx->pinned);
   if (ctx->ev_ready) for (int i = 0; i <= BPPP_NUM_STAGES; i++) hipEventDestroy(ctx->ev[i]);
   if (ctx->aux_fork) hipEventDestroy(ctx->aux_fork);

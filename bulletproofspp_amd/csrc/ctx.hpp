@@ -49,6 +49,11 @@ struct bppp_ctx {
   uint64_t calls = 0;
   hipEvent_t ev[BPPP_NUM_STAGES + 1] = {};
   bool ev_ready = false;
+  // grow-only device buffer of the multi-setup verifier (csrc/rpmixed.hip): the one MSM's input and every group's shared scalars, which
+  // must outlive the next group's assembly in ws2
+  void *mix = nullptr;
+  size_t mix_bytes = 0;
+  uint64_t last_mixed_terms = 0;     // terms of the last multi-setup MSM (bppp_test_last_mixed_msm_terms)
 };
 
 namespace bppp {

@@ -228,22 +228,22 @@ __global__ void __launch_bounds__(256) k_vb_sum_gs(const uint32_t *__restrict__ 
   if (t == 0) { fe x; for (int i = 0; i < 8; i++) x.v[i] = lds[i]; fe_store(out, x); }
 }
 
-// the MSM's point list [G | H | g | per proof: init points, responses] in one pass (16 bytes per lane) instead of five strided copies
+// the MSM's point list [G | H | g | per proof: init points, responses] in one pass (16 bytes per lane) instead of five strided copies;
+// shared = 0: the per-proof points alone (a multi-setup batch lays the shared basis out itself, csrc/rpmixed.hip)
 __global__ void __launch_bounds__(256) k_vb_gather_points(const uint4 *__restrict__ G, uint32_t nlen, const uint4 *__restrict__ H, uint32_t llen,
                                                           const uint4 *__restrict__ g, const uint4 *__restrict__ init_pts, uint32_t ninit,
-                                                          const uint4 *__restrict__ resp, uint32_t nresp, uint64_t T, uint4 *__restrict__ out) {
+                                                          const uint4 *__restrict__ resp, uint32_t nresp, uint32_t shared, uint64_t T, uint4 *__restrict__ out) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 4 * T) return;
   const uint64_t t = i >> 2; const uint32_t part = (uint32_t)(i & 3u);
-  const uint32_t shared = nlen + llen + 1, per = ninit + nresp;
+  const uint32_t per = ninit + nresp;
   const uint4 *src;
-  if (t < nlen) src = G + t * 4;
-  else if (t < nlen + llen) src = H + (t - nlen) * 4;
-  else if (t < shared) src = g;
-  else {
+  if (t >= shared) {
     const uint64_t u = t - shared, b = u / per; const uint32_t m = (uint32_t)(u % per);
     src = m < ninit ? init_pts + (b * ninit + m) * 4 : resp + (b * nresp + (m - ninit)) * 4;
-  }
+  } else if (t < nlen) src = G + t * 4;
+  else if (t < nlen + llen) src = H + (t - nlen) * 4;
+  else src = g;
   out[i] = src[part];
 }
 
@@ -387,9 +387,79 @@ __global__ void __launch_bounds__(64) k_ipvb_proof(const uint32_t *__restrict__ 
 
 using namespace bppp;
 
+// Every batch check is two steps: the ASSEMBLY of the MSM's scalars and points (shared scalars [G | H | g], per-proof scalars and
+// points), then the one msm_run.  bppp_{nl,ip}_verify_batch_device and the range-proof verifier run both; a batch of several setups
+// (csrc/rpmixed.hip) assembles every group into its own place and runs one MSM over all of them.
 // `validate` = false: the caller made every input itself on the device (csrc/rp.hip: decoded points are on the curve or infinity and
 // decoded / derived scalars canonical by construction), so the fifteen validation launches are skipped
 namespace bppp {
+static inline size_t vb_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// bytes of ctx->ws2 the assembly carves (fac, qf2, the partial sums, gs); its caller makes sure they are there (ensure_scratch)
+size_t nl_verify_batch_scratch(size_t batch, size_t nlen, size_t llen, size_t k) {
+  const uint32_t ktile = vb_kt(batch), ntiles = (uint32_t)((batch + ktile - 1) / ktile);
+  const size_t maxlen = nlen > llen ? nlen : llen;
+  const size_t npartial = std::max((size_t)ntiles * maxlen, batch * ((llen + 3) / 4));      // the tile sums, then k_vb_lin_partial's group sums
+  return vb_round(((batch * 2 * (k ? k : 1) + batch + npartial + (size_t)SUM_GROUPS * maxlen + batch + 64) * 8) * 4);
+}
+// sc_shared [nlen + llen + 1] = [G | H | g]; sc_tail [batch][ninit + 2k]; pts = [G | H | g | per-proof points] when gather_shared, else the
+// per-proof points alone; flags: the validation word (validate), read by the caller after the MSM
+int nl_verify_batch_assemble(bppp_ctx *ctx, size_t batch, size_t nlen, size_t llen, size_t k, size_t fn, size_t fl, size_t ninit,
+                             const void *d_g_xy, const void *d_norm_g_xy, const void *d_lin_h_xy, const void *d_rho, const void *d_q,
+                             const void *d_sp, const void *d_pub_norm, const void *d_pub_lin_c, const void *d_pub_lin_x,
+                             const void *d_es, const void *d_wit_norm, const void *d_wit_lin, const void *d_init_scalars,
+                             const void *d_init_points_xy, const void *d_responses_xy, bool validate, uint32_t *sc_shared, uint32_t *sc_tail,
+                             uint32_t *pts, bool gather_shared, uint32_t *flags) {
+  hipStream_t st = ctx->stream;
+  const size_t per = ninit + 2 * k, shared = nlen + llen + 1, Tg = (gather_shared ? shared : 0) + batch * per;
+  const uint32_t ktile = vb_kt(batch), ntiles = (uint32_t)((batch + ktile - 1) / ktile);
+  const size_t maxlen = nlen > llen ? nlen : llen;
+  const size_t npartial = std::max((size_t)ntiles * maxlen, batch * ((llen + 3) / 4));
+  uint32_t *buf = (uint32_t *)ctx->ws2;
+  uint32_t *fac = buf, *qf2 = fac + batch * 2 * (k ? k : 1) * 8, *partial = qf2 + batch * 8, *partial2 = partial + npartial * 8, *gs = partial2 + (size_t)SUM_GROUPS * maxlen * 8;
+  // untrusted inputs first (asynchronous; the flag word is read after the MSM has synchronised the stream)
+  if (validate && hipMemsetAsync(flags, 0, 4, st) != hipSuccess) return fail(ctx, BPPP_ERR_HIP, "nl_verify_batch: memset");
+  auto vs = [&](const void *p, uint64_t n, int nz) {
+    if (n) k_vb_validate_scalars<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>((const uint32_t *)p, n, nz, flags);
+  };
+  auto vp = [&](const void *p, uint64_t n) {
+    if (n) k_vb_validate_points<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>((const uint32_t *)p, n, flags);
+  };
+  if (validate) {
+    vs(d_rho, batch, 1); vs(d_q, batch, 0); vs(d_sp, batch, 0); vs(d_pub_norm, batch * nlen, 0); vs(d_pub_lin_c, batch * llen, 0);
+    vs(d_pub_lin_x, batch * llen, 0); vs(d_es, batch * k, 0); vs(d_wit_norm, batch * fn, 0); vs(d_wit_lin, batch * fl, 0);
+    vs(d_init_scalars, batch * ninit, 0);
+    vp(d_g_xy, 1); vp(d_norm_g_xy, nlen); vp(d_lin_h_xy, llen); vp(d_init_points_xy, batch * ninit); vp(d_responses_xy, batch * 2 * k);
+  }
+  k_vb_factors<<<dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, st>>>((const uint32_t *)d_q, (const uint32_t *)d_es, (uint32_t)batch, (int)k, fac, qf2);
+  if (nlen) {
+    if (k >= 2) k_vb_shared4<<<dim3((unsigned)((nlen + 255) / 256), ntiles), dim3(64), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_pub_norm, (const uint32_t *)d_wit_norm, (uint32_t)fn, fac, (uint32_t)batch, (uint32_t)nlen, (int)k, 1, ktile, partial);
+    else k_vb_shared1<<<dim3((unsigned)((nlen + 255) / 256), ntiles), dim3(256), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_pub_norm, (const uint32_t *)d_wit_norm, (uint32_t)fn, fac, (uint32_t)batch, (uint32_t)nlen, (int)k, 1, ktile, partial);
+    { const uint32_t per = (ntiles + SUM_GROUPS - 1) / SUM_GROUPS, groups = (ntiles + per - 1) / per;
+      k_vb_sum_partials<<<dim3((unsigned)((nlen + 63) / 64), groups), dim3(256), 0, st>>>(partial, ntiles, per, (uint32_t)nlen, partial2);
+      k_vb_sum_partials<<<dim3((unsigned)((nlen + 63) / 64), 1), dim3(256), 0, st>>>(partial2, groups, groups, (uint32_t)nlen, sc_shared); }
+  }
+  if (llen) {
+    if (k >= 2) k_vb_shared4<<<dim3((unsigned)((llen + 255) / 256), ntiles), dim3(64), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_pub_lin_x, (const uint32_t *)d_wit_lin, (uint32_t)fl, fac, (uint32_t)batch, (uint32_t)llen, (int)k, 0, ktile, partial);
+    else k_vb_shared1<<<dim3((unsigned)((llen + 255) / 256), ntiles), dim3(256), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_pub_lin_x, (const uint32_t *)d_wit_lin, (uint32_t)fl, fac, (uint32_t)batch, (uint32_t)llen, (int)k, 0, ktile, partial);
+    { const uint32_t per = (ntiles + SUM_GROUPS - 1) / SUM_GROUPS, groups = (ntiles + per - 1) / per;
+      k_vb_sum_partials<<<dim3((unsigned)((llen + 63) / 64), groups), dim3(256), 0, st>>>(partial, ntiles, per, (uint32_t)llen, partial2);
+      k_vb_sum_partials<<<dim3((unsigned)((llen + 63) / 64), 1), dim3(256), 0, st>>>(partial2, groups, groups, (uint32_t)llen, sc_shared + nlen * 8); }
+  }
+  const uint32_t G4 = (uint32_t)((llen + 3) / 4);                 // (the partial-sum buffer is free again: at most llen / 4 of its maxlen / 2 words per proof)
+  if (G4) k_vb_lin_partial<<<dim3((unsigned)(((uint64_t)batch * G4 + 255) / 256)), dim3(256), 0, st>>>((const uint32_t *)d_wit_lin, (uint32_t)fl, (const uint32_t *)d_pub_lin_c,
+                                                                                                    (uint32_t)llen, fac, (int)k, (uint32_t)batch, G4, partial);
+  k_vb_proof<<<dim3((unsigned)batch), dim3(64), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_sp, qf2, (const uint32_t *)d_wit_norm, (uint32_t)fn, partial, G4, (int)k,
+                                                         (const uint32_t *)d_init_scalars, (uint32_t)ninit, (const uint32_t *)d_es, gs, sc_tail);
+  k_vb_sum_gs<<<dim3(1), dim3(256), 0, st>>>(gs, (uint32_t)batch, sc_shared + (nlen + llen) * 8);
+  // points: [G | H | g | per proof: init points, responses]
+  k_vb_gather_points<<<dim3((unsigned)((4 * Tg + 255) / 256)), dim3(256), 0, st>>>((const uint4 *)d_norm_g_xy, (uint32_t)nlen, (const uint4 *)d_lin_h_xy, (uint32_t)llen,
+                                                                                  (const uint4 *)d_g_xy, (const uint4 *)d_init_points_xy, (uint32_t)ninit,
+                                                                                  (const uint4 *)d_responses_xy, (uint32_t)(2 * k), gather_shared ? (uint32_t)shared : 0u,
+                                                                                  (uint64_t)Tg, (uint4 *)pts);
+  if (hipGetLastError() != hipSuccess) return fail(ctx, BPPP_ERR_HIP, "nl_verify_batch: assembling the MSM failed");
+  return BPPP_OK;
+}
+
 int nl_verify_batch_run(bppp_ctx *ctx, size_t batch, size_t nlen, size_t llen, size_t k, size_t fn, size_t fl, size_t ninit,
                         const void *d_g_xy, const void *d_norm_g_xy, const void *d_lin_h_xy, const void *d_rho, const void *d_q,
                         const void *d_sp, const void *d_pub_norm, const void *d_pub_lin_c, const void *d_pub_lin_x,
@@ -405,57 +475,15 @@ int nl_verify_batch_run(bppp_ctx *ctx, size_t batch, size_t nlen, size_t llen, s
   hipSetDevice(ctx->device);
   hipStream_t st = ctx->stream;
   const size_t per = ninit + 2 * k, shared = nlen + llen + 1, T = shared + batch * per;
-  const uint32_t ktile = vb_kt(batch), ntiles = (uint32_t)((batch + ktile - 1) / ktile);
-  const size_t maxlen = nlen > llen ? nlen : llen;
-  const size_t npartial = std::max((size_t)ntiles * maxlen, batch * ((llen + 3) / 4));      // the tile sums, then k_vb_lin_partial's group sums
-  // scratch (separate from the MSM workspace, which msm_run carves from ctx->ws)
-  size_t words = (batch * 2 * (k ? k : 1) + batch + npartial + (size_t)SUM_GROUPS * maxlen + batch + T + 64) * 8 + T * 16 + 64;
-  { int rc0 = ensure_scratch(ctx, words * 4); if (rc0) return rc0; }
-  uint32_t *buf = (uint32_t *)ctx->ws2;
-  uint32_t *fac = buf, *qf2 = fac + batch * 2 * (k ? k : 1) * 8, *partial = qf2 + batch * 8, *partial2 = partial + npartial * 8, *gs = partial2 + (size_t)SUM_GROUPS * maxlen * 8,
-           *sc = gs + batch * 8, *pts = sc + (T + 32) * 8, *flags = pts + T * 16;
-  int rc = BPPP_OK;
+  // the assembly's scratch, then the MSM's input (separate from the MSM workspace, which msm_run carves from ctx->ws)
+  const size_t sbytes = nl_verify_batch_scratch(batch, nlen, llen, k);
+  { int rc0 = ensure_scratch(ctx, sbytes + ((T + 32) * 8 + T * 16 + 64) * 4); if (rc0) return rc0; }
+  uint32_t *sc = (uint32_t *)((char *)ctx->ws2 + sbytes), *pts = sc + (T + 32) * 8, *flags = pts + T * 16;
+  int rc = nl_verify_batch_assemble(ctx, batch, nlen, llen, k, fn, fl, ninit, d_g_xy, d_norm_g_xy, d_lin_h_xy, d_rho, d_q, d_sp, d_pub_norm, d_pub_lin_c,
+                                    d_pub_lin_x, d_es, d_wit_norm, d_wit_lin, d_init_scalars, d_init_points_xy, d_responses_xy, validate, sc, sc + shared * 8,
+                                    pts, true, flags);
   do {
-    // untrusted inputs first (asynchronous; the flag word is read after the MSM has synchronised the stream)
-    if (validate && hipMemsetAsync(flags, 0, 4, st) != hipSuccess) { rc = fail(ctx, BPPP_ERR_HIP, "nl_verify_batch: memset"); break; }
-    auto vs = [&](const void *p, uint64_t n, int nz) {
-      if (n) k_vb_validate_scalars<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>((const uint32_t *)p, n, nz, flags);
-    };
-    auto vp = [&](const void *p, uint64_t n) {
-      if (n) k_vb_validate_points<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>((const uint32_t *)p, n, flags);
-    };
-    if (validate) {
-      vs(d_rho, batch, 1); vs(d_q, batch, 0); vs(d_sp, batch, 0); vs(d_pub_norm, batch * nlen, 0); vs(d_pub_lin_c, batch * llen, 0);
-      vs(d_pub_lin_x, batch * llen, 0); vs(d_es, batch * k, 0); vs(d_wit_norm, batch * fn, 0); vs(d_wit_lin, batch * fl, 0);
-      vs(d_init_scalars, batch * ninit, 0);
-      vp(d_g_xy, 1); vp(d_norm_g_xy, nlen); vp(d_lin_h_xy, llen); vp(d_init_points_xy, batch * ninit); vp(d_responses_xy, batch * 2 * k);
-    }
-    k_vb_factors<<<dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, st>>>((const uint32_t *)d_q, (const uint32_t *)d_es, (uint32_t)batch, (int)k, fac, qf2);
-    if (nlen) {
-      if (k >= 2) k_vb_shared4<<<dim3((unsigned)((nlen + 255) / 256), ntiles), dim3(64), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_pub_norm, (const uint32_t *)d_wit_norm, (uint32_t)fn, fac, (uint32_t)batch, (uint32_t)nlen, (int)k, 1, ktile, partial);
-      else k_vb_shared1<<<dim3((unsigned)((nlen + 255) / 256), ntiles), dim3(256), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_pub_norm, (const uint32_t *)d_wit_norm, (uint32_t)fn, fac, (uint32_t)batch, (uint32_t)nlen, (int)k, 1, ktile, partial);
-      { const uint32_t per = (ntiles + SUM_GROUPS - 1) / SUM_GROUPS, groups = (ntiles + per - 1) / per;
-        k_vb_sum_partials<<<dim3((unsigned)((nlen + 63) / 64), groups), dim3(256), 0, st>>>(partial, ntiles, per, (uint32_t)nlen, partial2);
-        k_vb_sum_partials<<<dim3((unsigned)((nlen + 63) / 64), 1), dim3(256), 0, st>>>(partial2, groups, groups, (uint32_t)nlen, sc); }
-    }
-    if (llen) {
-      if (k >= 2) k_vb_shared4<<<dim3((unsigned)((llen + 255) / 256), ntiles), dim3(64), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_pub_lin_x, (const uint32_t *)d_wit_lin, (uint32_t)fl, fac, (uint32_t)batch, (uint32_t)llen, (int)k, 0, ktile, partial);
-      else k_vb_shared1<<<dim3((unsigned)((llen + 255) / 256), ntiles), dim3(256), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_pub_lin_x, (const uint32_t *)d_wit_lin, (uint32_t)fl, fac, (uint32_t)batch, (uint32_t)llen, (int)k, 0, ktile, partial);
-      { const uint32_t per = (ntiles + SUM_GROUPS - 1) / SUM_GROUPS, groups = (ntiles + per - 1) / per;
-        k_vb_sum_partials<<<dim3((unsigned)((llen + 63) / 64), groups), dim3(256), 0, st>>>(partial, ntiles, per, (uint32_t)llen, partial2);
-        k_vb_sum_partials<<<dim3((unsigned)((llen + 63) / 64), 1), dim3(256), 0, st>>>(partial2, groups, groups, (uint32_t)llen, sc + nlen * 8); }
-    }
-    const uint32_t G4 = (uint32_t)((llen + 3) / 4);                 // (the partial-sum buffer is free again: at most llen / 4 of its maxlen / 2 words per proof)
-    if (G4) k_vb_lin_partial<<<dim3((unsigned)(((uint64_t)batch * G4 + 255) / 256)), dim3(256), 0, st>>>((const uint32_t *)d_wit_lin, (uint32_t)fl, (const uint32_t *)d_pub_lin_c,
-                                                                                                      (uint32_t)llen, fac, (int)k, (uint32_t)batch, G4, partial);
-    k_vb_proof<<<dim3((unsigned)batch), dim3(64), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_sp, qf2, (const uint32_t *)d_wit_norm, (uint32_t)fn, partial, G4, (int)k,
-                                                           (const uint32_t *)d_init_scalars, (uint32_t)ninit, (const uint32_t *)d_es, gs, sc + shared * 8);
-    k_vb_sum_gs<<<dim3(1), dim3(256), 0, st>>>(gs, (uint32_t)batch, sc + (nlen + llen) * 8);
-    // points: [G | H | g | per proof: init points, responses]
-    k_vb_gather_points<<<dim3((unsigned)((4 * T + 255) / 256)), dim3(256), 0, st>>>((const uint4 *)d_norm_g_xy, (uint32_t)nlen, (const uint4 *)d_lin_h_xy, (uint32_t)llen,
-                                                                                   (const uint4 *)d_g_xy, (const uint4 *)d_init_points_xy, (uint32_t)ninit,
-                                                                                   (const uint4 *)d_responses_xy, (uint32_t)(2 * k), (uint64_t)T, (uint4 *)pts);
-    if (hipGetLastError() != hipSuccess) { rc = fail(ctx, BPPP_ERR_HIP, "nl_verify_batch: assembling the MSM failed"); break; }
+    if (rc) break;
     rc = msm_run(ctx, sc, pts, T, 1, 1, 0, out_xy);
     if (rc || !validate) break;                 // (msm_run returns with the stream drained; nothing was flagged without the validation pass)
     uint32_t hflags = 0;
@@ -484,6 +512,73 @@ extern "C" int bppp_nl_verify_batch_device(bppp_ctx *ctx, size_t batch, size_t n
 // same layout and result contract as bppp_nl_verify_batch_device; d_r holds the per-proof argument of makeNorm (the range proofs'
 // challenge q, src/RangeProof/TypedReciprocal.hs:356), fn counts SCALARS of the final norm witness (even).
 namespace bppp {
+size_t ip_verify_batch_scratch(size_t batch, size_t nlen, size_t llen, size_t k, size_t fn) {
+  const size_t kk = k ? k : 1, ntiles = (batch + KT - 1) / KT, maxlen = nlen > llen ? nlen : llen;
+  return vb_round(((2 * batch * 2 * kk + batch + batch * (fn ? fn : 2) + ntiles * maxlen + (size_t)SUM_GROUPS * maxlen + batch + 64) * 8) * 4);
+}
+// outputs as nl_verify_batch_assemble; flags is always written (bit 8: a zero challenge, which makeEs cannot invert)
+int ip_verify_batch_assemble(bppp_ctx *ctx, size_t batch, size_t nlen, size_t llen, size_t k, size_t fn, size_t fl, size_t ninit,
+                             const void *d_g_xy, const void *d_norm_g_xy, const void *d_lin_h_xy, const void *d_rho, const void *d_r,
+                             const void *d_sp, const void *d_pub_norm, const void *d_pub_lin_c, const void *d_pub_lin_x,
+                             const void *d_es, const void *d_wit_norm, const void *d_wit_lin, const void *d_init_scalars,
+                             const void *d_init_points_xy, const void *d_responses_xy, bool validate, uint32_t *sc_shared, uint32_t *sc_tail,
+                             uint32_t *pts, bool gather_shared, uint32_t *flags) {
+  hipStream_t st = ctx->stream;
+  const size_t per = ninit + 2 * k, shared = nlen + llen + 1, Tg = (gather_shared ? shared : 0) + batch * per, fm = fn / 2, kk = k ? k : 1;
+  const uint32_t ktile = (uint32_t)KT, ntiles = (uint32_t)((batch + KT - 1) / KT);
+  const size_t maxlen = nlen > llen ? nlen : llen;
+  uint32_t *buf = (uint32_t *)ctx->ws2;
+  uint32_t *facx = buf, *facy = facx + batch * 2 * kk * 8, *qf = facy + batch * 2 * kk * 8, *v = qf + batch * 8, *partial = v + batch * (fn ? fn : 2) * 8,
+           *partial2 = partial + (size_t)ntiles * maxlen * 8, *gs = partial2 + (size_t)SUM_GROUPS * maxlen * 8;
+  if (hipMemsetAsync(flags, 0, 4, st) != hipSuccess) return fail(ctx, BPPP_ERR_HIP, "ip_verify_batch: memset");
+  auto vs = [&](const void *p, uint64_t n, int nz) {
+    if (n) k_vb_validate_scalars<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>((const uint32_t *)p, n, nz, flags);
+  };
+  auto vp = [&](const void *p, uint64_t n) {
+    if (n) k_vb_validate_points<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>((const uint32_t *)p, n, flags);
+  };
+  if (validate) {
+    vs(d_rho, batch, 1); vs(d_r, batch, 0); vs(d_sp, batch, 0); vs(d_pub_norm, batch * nlen, 0); vs(d_pub_lin_c, batch * llen, 0);
+    vs(d_pub_lin_x, batch * llen, 0); vs(d_es, batch * k, 0); vs(d_wit_norm, batch * fn, 0); vs(d_wit_lin, batch * fl, 0);
+    vs(d_init_scalars, batch * ninit, 0);
+    vp(d_g_xy, 1); vp(d_norm_g_xy, nlen); vp(d_lin_h_xy, llen); vp(d_init_points_xy, batch * ninit); vp(d_responses_xy, batch * 2 * k);
+  }
+  k_ipvb_factors<<<dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, st>>>((const uint32_t *)d_r, (const uint32_t *)d_es, (const uint32_t *)d_wit_norm, (uint32_t)batch,
+                                                                          (int)k, (uint32_t)fm, facx, facy, qf, v, flags);
+  const uint32_t sper = (ntiles + SUM_GROUPS - 1) / SUM_GROUPS, groups = (ntiles + sper - 1) / sper;
+  if (nlen) {
+    const uint64_t lanes = (uint64_t)ntiles * nlen;
+    k_ipvb_norm<<<dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_r, (const uint32_t *)d_pub_norm, v, (uint32_t)fm,
+                                                                             facx, facy, (uint32_t)batch, (uint32_t)nlen, (int)k, ntiles, partial);
+    k_vb_sum_partials<<<dim3((unsigned)((nlen + 63) / 64), groups), dim3(256), 0, st>>>(partial, ntiles, sper, (uint32_t)nlen, partial2);
+    k_vb_sum_partials<<<dim3((unsigned)((nlen + 63) / 64), 1), dim3(256), 0, st>>>(partial2, groups, groups, (uint32_t)nlen, sc_shared);
+  }
+  if (llen) {
+    if (k >= 2) k_vb_shared4<<<dim3((unsigned)((llen + 255) / 256), ntiles), dim3(64), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_pub_lin_x, (const uint32_t *)d_wit_lin, (uint32_t)fl, facx, (uint32_t)batch, (uint32_t)llen, (int)k, 0, ktile, partial);
+    else k_vb_shared1<<<dim3((unsigned)((llen + 255) / 256), ntiles), dim3(256), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_pub_lin_x, (const uint32_t *)d_wit_lin, (uint32_t)fl, facx, (uint32_t)batch, (uint32_t)llen, (int)k, 0, ktile, partial);
+    k_vb_sum_partials<<<dim3((unsigned)((llen + 63) / 64), groups), dim3(256), 0, st>>>(partial, ntiles, sper, (uint32_t)llen, partial2);
+    k_vb_sum_partials<<<dim3((unsigned)((llen + 63) / 64), 1), dim3(256), 0, st>>>(partial2, groups, groups, (uint32_t)llen, sc_shared + nlen * 8);
+  }
+  k_ipvb_proof<<<dim3((unsigned)batch), dim3(64), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_sp, qf, v, (uint32_t)fm, (const uint32_t *)d_wit_lin, (uint32_t)fl,
+                                                            (const uint32_t *)d_pub_lin_c, (uint32_t)llen, facx, (int)k, (const uint32_t *)d_init_scalars, (uint32_t)ninit,
+                                                            (const uint32_t *)d_es, gs, sc_tail);
+  k_vb_sum_gs<<<dim3(1), dim3(256), 0, st>>>(gs, (uint32_t)batch, sc_shared + (nlen + llen) * 8);
+  k_vb_gather_points<<<dim3((unsigned)((4 * Tg + 255) / 256)), dim3(256), 0, st>>>((const uint4 *)d_norm_g_xy, (uint32_t)nlen, (const uint4 *)d_lin_h_xy, (uint32_t)llen,
+                                                                                  (const uint4 *)d_g_xy, (const uint4 *)d_init_points_xy, (uint32_t)ninit,
+                                                                                  (const uint4 *)d_responses_xy, (uint32_t)(2 * k), gather_shared ? (uint32_t)shared : 0u,
+                                                                                  (uint64_t)Tg, (uint4 *)pts);
+  if (hipGetLastError() != hipSuccess) return fail(ctx, BPPP_ERR_HIP, "ip_verify_batch: assembling the MSM failed");
+  return BPPP_OK;
+}
+// the flag word an assembly left, after the MSM has drained the stream
+int ip_verify_batch_flags(bppp_ctx *ctx, uint32_t hflags) {
+  if (hflags & 2u) return fail(ctx, BPPP_ERR_POINT, "ip_verify_batch: a point is not on the curve");
+  if (hflags & 1u) return fail(ctx, BPPP_ERR_ARG, "ip_verify_batch: a scalar is not canonical (>= n)");
+  if (hflags & 4u) return fail(ctx, BPPP_ERR_ARG, "ip_verify_batch: a weight rho is zero (it would drop its proof from the combination)");
+  if (hflags & 8u) return fail(ctx, BPPP_ERR_ARG, "ip_verify_batch: a challenge is zero (makeEs needs its inverse)");
+  return BPPP_OK;
+}
+
 int ip_verify_batch_run(bppp_ctx *ctx, size_t batch, size_t nlen, size_t llen, size_t k, size_t fn, size_t fl, size_t ninit,
                         const void *d_g_xy, const void *d_norm_g_xy, const void *d_lin_h_xy, const void *d_rho, const void *d_r,
                         const void *d_sp, const void *d_pub_norm, const void *d_pub_lin_c, const void *d_pub_lin_x,
@@ -498,64 +593,22 @@ int ip_verify_batch_run(bppp_ctx *ctx, size_t batch, size_t nlen, size_t llen, s
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
   hipSetDevice(ctx->device);
   hipStream_t st = ctx->stream;
-  const size_t per = ninit + 2 * k, shared = nlen + llen + 1, T = shared + batch * per, fm = fn / 2, kk = k ? k : 1;
-  const uint32_t ktile = (uint32_t)KT, ntiles = (uint32_t)((batch + KT - 1) / KT);
-  const size_t maxlen = nlen > llen ? nlen : llen;
-  size_t words = (2 * batch * 2 * kk + batch + batch * (fn ? fn : 2) + (size_t)ntiles * maxlen + (size_t)SUM_GROUPS * maxlen + batch + T + 64) * 8 + T * 16 + 64;
-  { int rc0 = ensure_scratch(ctx, words * 4); if (rc0) return rc0; }
-  uint32_t *buf = (uint32_t *)ctx->ws2;
-  uint32_t *facx = buf, *facy = facx + batch * 2 * kk * 8, *qf = facy + batch * 2 * kk * 8, *v = qf + batch * 8, *partial = v + batch * (fn ? fn : 2) * 8,
-           *partial2 = partial + (size_t)ntiles * maxlen * 8, *gs = partial2 + (size_t)SUM_GROUPS * maxlen * 8, *sc = gs + batch * 8, *pts = sc + (T + 32) * 8,
-           *flags = pts + T * 16;
-  int rc = BPPP_OK;
+  const size_t per = ninit + 2 * k, shared = nlen + llen + 1, T = shared + batch * per;
+  const size_t sbytes = ip_verify_batch_scratch(batch, nlen, llen, k, fn);
+  { int rc0 = ensure_scratch(ctx, sbytes + ((T + 32) * 8 + T * 16 + 64) * 4); if (rc0) return rc0; }
+  uint32_t *sc = (uint32_t *)((char *)ctx->ws2 + sbytes), *pts = sc + (T + 32) * 8, *flags = pts + T * 16;
+  int rc = ip_verify_batch_assemble(ctx, batch, nlen, llen, k, fn, fl, ninit, d_g_xy, d_norm_g_xy, d_lin_h_xy, d_rho, d_r, d_sp, d_pub_norm, d_pub_lin_c,
+                                    d_pub_lin_x, d_es, d_wit_norm, d_wit_lin, d_init_scalars, d_init_points_xy, d_responses_xy, validate, sc, sc + shared * 8,
+                                    pts, true, flags);
   do {
-    if (hipMemsetAsync(flags, 0, 4, st) != hipSuccess) { rc = fail(ctx, BPPP_ERR_HIP, "ip_verify_batch: memset"); break; }
-    auto vs = [&](const void *p, uint64_t n, int nz) {
-      if (n) k_vb_validate_scalars<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>((const uint32_t *)p, n, nz, flags);
-    };
-    auto vp = [&](const void *p, uint64_t n) {
-      if (n) k_vb_validate_points<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>((const uint32_t *)p, n, flags);
-    };
-    if (validate) {
-      vs(d_rho, batch, 1); vs(d_r, batch, 0); vs(d_sp, batch, 0); vs(d_pub_norm, batch * nlen, 0); vs(d_pub_lin_c, batch * llen, 0);
-      vs(d_pub_lin_x, batch * llen, 0); vs(d_es, batch * k, 0); vs(d_wit_norm, batch * fn, 0); vs(d_wit_lin, batch * fl, 0);
-      vs(d_init_scalars, batch * ninit, 0);
-      vp(d_g_xy, 1); vp(d_norm_g_xy, nlen); vp(d_lin_h_xy, llen); vp(d_init_points_xy, batch * ninit); vp(d_responses_xy, batch * 2 * k);
-    }
-    k_ipvb_factors<<<dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, st>>>((const uint32_t *)d_r, (const uint32_t *)d_es, (const uint32_t *)d_wit_norm, (uint32_t)batch,
-                                                                            (int)k, (uint32_t)fm, facx, facy, qf, v, flags);
-    const uint32_t sper = (ntiles + SUM_GROUPS - 1) / SUM_GROUPS, groups = (ntiles + sper - 1) / sper;
-    if (nlen) {
-      const uint64_t lanes = (uint64_t)ntiles * nlen;
-      k_ipvb_norm<<<dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_r, (const uint32_t *)d_pub_norm, v, (uint32_t)fm,
-                                                                               facx, facy, (uint32_t)batch, (uint32_t)nlen, (int)k, ntiles, partial);
-      k_vb_sum_partials<<<dim3((unsigned)((nlen + 63) / 64), groups), dim3(256), 0, st>>>(partial, ntiles, sper, (uint32_t)nlen, partial2);
-      k_vb_sum_partials<<<dim3((unsigned)((nlen + 63) / 64), 1), dim3(256), 0, st>>>(partial2, groups, groups, (uint32_t)nlen, sc);
-    }
-    if (llen) {
-      if (k >= 2) k_vb_shared4<<<dim3((unsigned)((llen + 255) / 256), ntiles), dim3(64), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_pub_lin_x, (const uint32_t *)d_wit_lin, (uint32_t)fl, facx, (uint32_t)batch, (uint32_t)llen, (int)k, 0, ktile, partial);
-      else k_vb_shared1<<<dim3((unsigned)((llen + 255) / 256), ntiles), dim3(256), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_pub_lin_x, (const uint32_t *)d_wit_lin, (uint32_t)fl, facx, (uint32_t)batch, (uint32_t)llen, (int)k, 0, ktile, partial);
-      k_vb_sum_partials<<<dim3((unsigned)((llen + 63) / 64), groups), dim3(256), 0, st>>>(partial, ntiles, sper, (uint32_t)llen, partial2);
-      k_vb_sum_partials<<<dim3((unsigned)((llen + 63) / 64), 1), dim3(256), 0, st>>>(partial2, groups, groups, (uint32_t)llen, sc + nlen * 8);
-    }
-    k_ipvb_proof<<<dim3((unsigned)batch), dim3(64), 0, st>>>((const uint32_t *)d_rho, (const uint32_t *)d_sp, qf, v, (uint32_t)fm, (const uint32_t *)d_wit_lin, (uint32_t)fl,
-                                                              (const uint32_t *)d_pub_lin_c, (uint32_t)llen, facx, (int)k, (const uint32_t *)d_init_scalars, (uint32_t)ninit,
-                                                              (const uint32_t *)d_es, gs, sc + shared * 8);
-    k_vb_sum_gs<<<dim3(1), dim3(256), 0, st>>>(gs, (uint32_t)batch, sc + (nlen + llen) * 8);
-    k_vb_gather_points<<<dim3((unsigned)((4 * T + 255) / 256)), dim3(256), 0, st>>>((const uint4 *)d_norm_g_xy, (uint32_t)nlen, (const uint4 *)d_lin_h_xy, (uint32_t)llen,
-                                                                                   (const uint4 *)d_g_xy, (const uint4 *)d_init_points_xy, (uint32_t)ninit,
-                                                                                   (const uint4 *)d_responses_xy, (uint32_t)(2 * k), (uint64_t)T, (uint4 *)pts);
-    if (hipGetLastError() != hipSuccess) { rc = fail(ctx, BPPP_ERR_HIP, "ip_verify_batch: assembling the MSM failed"); break; }
+    if (rc) break;
     rc = msm_run(ctx, sc, pts, T, 1, 1, 0, out_xy);
     if (rc) break;
     uint32_t hflags = 0;
     if (hipMemcpyAsync(&hflags, flags, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
       rc = fail(ctx, BPPP_ERR_HIP, "ip_verify_batch: reading the validation flags failed"); break;
     }
-    if (hflags & 2u) rc = fail(ctx, BPPP_ERR_POINT, "ip_verify_batch: a point is not on the curve");
-    else if (hflags & 1u) rc = fail(ctx, BPPP_ERR_ARG, "ip_verify_batch: a scalar is not canonical (>= n)");
-    else if (hflags & 4u) rc = fail(ctx, BPPP_ERR_ARG, "ip_verify_batch: a weight rho is zero (it would drop its proof from the combination)");
-    else if (hflags & 8u) rc = fail(ctx, BPPP_ERR_ARG, "ip_verify_batch: a challenge is zero (makeEs needs its inverse)");
+    rc = ip_verify_batch_flags(ctx, hflags);
   } while (0);
   hipStreamSynchronize(st);
   return rc;

@@ -832,6 +832,51 @@ static int rp_verify_shard_run(bppp_rp *rp, size_t batch, uint64_t index_offset,
   if (combined_xy) memset(combined_xy, 0, 64);
   if (!batch) { *accept = 1; return BPPP_OK; }
   if (!d_coms_files || !d_proof_files || !seed || batch >= (1u << 22)) return fail(ctx, BPPP_ERR_ARG, "rp_verify_batch: bad arguments");
+  RpVerifyArrays A;
+  int rc = rp_verify_prepare(rp, batch, index_offset, d_coms_files, d_proof_files, seed, A);
+  if (rc) return rc;
+  hipStream_t st = ctx->stream;
+  const bppp_rps::Setup &S = rp->st;
+  const RpDims D = rp->D;
+  const size_t B = batch, k = S.rounds;
+  uint64_t out_xy[8];
+  rc = rp_verify_combine(rp, A, 0, B, out_xy);
+  if (rc) return rc;
+  // decode failures (an x with no point on the curve): Nothing in the reference (decodeCommitments, Encoding.hs:119-128).  The batch-wide
+  // flag reached pinned memory long before the MSM drained the stream; the per-proof words are fetched only when somebody needs them
+  const bool any_bad = rp->hflag[0] != 0;
+  std::vector<uint32_t> hbad(proof_status ? B : 0);
+  // async copies below target host vectors: whatever path leaves this function, the stream is drained before they are destroyed
+  struct StreamDrain { hipStream_t s; ~StreamDrain() { hipStreamSynchronize(s); } };
+  StreamDrain drain{st};
+  if (proof_status) BPPP_HIP(ctx, hipMemcpyAsync(hbad.data(), A.bad, B * 4, hipMemcpyDeviceToHost, st));
+  if (challenges_out) {                        // [batch][nch + k]: the range-proof layer's challenges (Binary: q, x, r from slots 0-2, t from slot 6), then the rounds'
+    const size_t nch = D.nch, row = (nch + k) * 32;
+    if (S.kind == 0) BPPP_HIP(ctx, hipMemcpy2DAsync(challenges_out, row, A.ch, 7 * 32, 7 * 32, B, hipMemcpyDeviceToHost, st));
+    else {
+      BPPP_HIP(ctx, hipMemcpy2DAsync(challenges_out, row, A.ch, 7 * 32, 3 * 32, B, hipMemcpyDeviceToHost, st));
+      BPPP_HIP(ctx, hipMemcpy2DAsync(challenges_out + 12, row, A.ch + 6 * 8, 7 * 32, 32, B, hipMemcpyDeviceToHost, st));
+    }
+    if (k) BPPP_HIP(ctx, hipMemcpy2DAsync(challenges_out + 4 * nch, row, A.es, k * 32, k * 32, B, hipMemcpyDeviceToHost, st));
+  }
+  if (proof_status || challenges_out) BPPP_HIP(ctx, hipStreamSynchronize(st));
+  const bool whole = rp_point_is_inf(out_xy);
+  if (combined_xy) memcpy(combined_xy, out_xy, 64);
+  *accept = (whole && !any_bad) ? 1 : 0;
+  if (!proof_status) return BPPP_OK;
+  for (size_t b = 0; b < B; b++) proof_status[b] = hbad[b] ? BPPP_RP_MALFORMED : BPPP_RP_VALID;
+  if (whole) return BPPP_OK;
+  return rp_find_culprits(rp, A, true, proof_status);
+}
+
+}  // extern "C"
+
+namespace bppp {
+// decodeProof, the transcript hashing, the public scalars and the weights rho of one batch: everything of the verification but the
+// argument's combination (see rp_internal.hpp)
+int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const uint8_t seed[32],
+                      RpVerifyArrays &A) {
+  bppp_ctx *ctx = rp->ctx;
   hipSetDevice(ctx->device);
   hipStream_t st = ctx->stream;
   const bppp_rps::Setup &S = rp->st;
@@ -895,8 +940,6 @@ static int rp_verify_shard_run(bppp_rp *rp, size_t batch, uint64_t index_offset,
   }
   BPPP_HIP(ctx, hipMemcpyAsync(rp->hflag, bad + B, 4, hipMemcpyDeviceToHost, st));     // pinned; read after the MSM has drained the stream
   const size_t host_oracle_max = rp->opt.host_oracle_verify;
-  // async copies below target host vectors: whatever path leaves this function, the stream is drained before they are destroyed
-  struct StreamDrain { hipStream_t s; ~StreamDrain() { hipStreamSynchronize(s); } };
   if (B <= host_oracle_max) {
     // the transcript text comes from the device (k_rp_text_lds: ~10 us against ~0.45 us per coordinate on a host core, 168 of them for 64by64)
     const size_t tbytes = (B * (size_t)D.text_stride + 63) & ~(size_t)63, obytes = (B * (npts + 1) * 4 + 63) & ~(size_t)63, n_hch = B * 28, n_hes = B * k * 4 + 4;
@@ -966,53 +1009,37 @@ static int rp_verify_shard_run(bppp_rp *rp, size_t batch, uint64_t index_offset,
   }
   k_rp_rho<<<dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st>>>(D, (uint32_t)B, index_offset, d_seed, ch, es, wit_norm, wit_lin, rho);
   BPPP_HIP(ctx, hipGetLastError());
-  int rc = BPPP_OK;
-  uint64_t out_xy[8];
-  // verifyBPM of the setup's argument flavour (q is makeNorm's r for the inner-product one)
-  // (every input below was made on the device by this call: canonical scalars, points on the curve or infinity — no validation pass)
-  auto verify_bp = S.flavour ? bppp::ip_verify_batch_run : bppp::nl_verify_batch_run;
-  rc = verify_bp(ctx, B, nlen, llen, k, D.fn, D.fl, ninit, rp->d_g(), rp->d_G(), rp->d_H(), rho, q, sp, pub_norm,
-                 pub_lin_c, pub_lin_x, es, wit_norm, wit_lin, init_sc, init_pts, resp_pts, out_xy, false);
-  if (rc) return rc;
-  // decode failures (an x with no point on the curve): Nothing in the reference (decodeCommitments, Encoding.hs:119-128).  The batch-wide
-  // flag reached pinned memory long before the MSM drained the stream; the per-proof words are fetched only when somebody needs them
-  const bool any_bad = rp->hflag[0] != 0;
-  std::vector<uint32_t> hbad(proof_status ? B : 0);
-  StreamDrain drain{st};
-  if (proof_status) BPPP_HIP(ctx, hipMemcpyAsync(hbad.data(), bad, B * 4, hipMemcpyDeviceToHost, st));
-  if (challenges_out) {                        // [batch][nch + k]: the range-proof layer's challenges (Binary: q, x, r from slots 0-2, t from slot 6), then the rounds'
-    const size_t nch = D.nch, row = (nch + k) * 32;
-    if (S.kind == 0) BPPP_HIP(ctx, hipMemcpy2DAsync(challenges_out, row, ch, 7 * 32, 7 * 32, B, hipMemcpyDeviceToHost, st));
-    else {
-      BPPP_HIP(ctx, hipMemcpy2DAsync(challenges_out, row, ch, 7 * 32, 3 * 32, B, hipMemcpyDeviceToHost, st));
-      BPPP_HIP(ctx, hipMemcpy2DAsync(challenges_out + 12, row, ch + 6 * 8, 7 * 32, 32, B, hipMemcpyDeviceToHost, st));
-    }
-    if (k) BPPP_HIP(ctx, hipMemcpy2DAsync(challenges_out + 4 * nch, row, es, k * 32, k * 32, B, hipMemcpyDeviceToHost, st));
-  }
-  if (proof_status || challenges_out) BPPP_HIP(ctx, hipStreamSynchronize(st));
-  auto is_inf = [](const uint64_t *p) { uint64_t o = 0; for (int i = 0; i < 8; i++) o |= p[i]; return o == 0; };
-  const bool whole = is_inf(out_xy);
-  if (combined_xy) memcpy(combined_xy, out_xy, 64);
-  *accept = (whole && !any_bad) ? 1 : 0;
-  if (!proof_status) return BPPP_OK;
-  for (size_t b = 0; b < B; b++) proof_status[b] = hbad[b] ? BPPP_RP_MALFORMED : BPPP_RP_VALID;
-  if (whole) return BPPP_OK;
-  // The combination is not the identity: find the culprits by bisection.  Every per-proof array is [batch][...], so a sub-batch
-  // [lo, hi) is the same call on offset pointers (any non-zero weights do); a malformed proof decodes to infinity points and is
-  // simply another failing member.  O(f log B) combined MSMs for f bad proofs.
+  A = RpVerifyArrays{B, init_pts, resp_pts, wit_norm, wit_lin, ch, es, rho, q, sp, pub_norm, pub_lin_c, pub_lin_x, init_sc, bad};
+  return BPPP_OK;
+}
+
+// verifyBPM of the setup's argument flavour (q is makeNorm's r for the inner-product one) over proofs [o, o + n) of a prepared batch: every
+// per-proof array is [batch][...], so a sub-batch is the same call on offset pointers (any non-zero weights do)
+// (every input was made on the device by rp_verify_prepare: canonical scalars, points on the curve or infinity — no validation pass)
+int rp_verify_combine(bppp_rp *rp, const RpVerifyArrays &A, size_t o, size_t n, uint64_t out_xy[8]) {
+  const bppp_rps::Setup &S = rp->st;
+  const RpDims &D = rp->D;
+  const size_t nlen = S.nlen, llen = S.llen, k = S.rounds, ninit = D.nrp + D.nr;
+  auto verify_bp = S.flavour ? ip_verify_batch_run : nl_verify_batch_run;
+  return verify_bp(rp->ctx, n, nlen, llen, k, D.fn, D.fl, ninit, rp->d_g(), rp->d_G(), rp->d_H(), A.rho + o * 8, A.q + o * 8, A.sp + o * 8,
+                   A.pub_norm + o * nlen * 8, A.pub_lin_c + o * llen * 8, A.pub_lin_x + o * llen * 8, A.es + o * k * 8, A.wit_norm + o * D.fn * 8,
+                   A.wit_lin + o * D.fl * 8, A.init_sc + o * ninit * 8, A.init_pts + o * ninit * 16, A.resp_pts + o * 2 * k * 16, out_xy, false);
+}
+
+// The combination is not the identity (known_bad), or may not be: find the culprits by bisection.  A malformed proof decodes to infinity
+// points and is simply another failing member.  O(f log B) combined MSMs for f bad proofs.
+int rp_find_culprits(bppp_rp *rp, const RpVerifyArrays &A, bool known_bad, uint32_t *proof_status) {
   struct Range { size_t lo, hi; bool known_bad; };
   std::vector<Range> todo;
-  todo.push_back(Range{0, B, true});
+  todo.push_back(Range{0, A.batch, known_bad});
+  uint64_t out_xy[8];
   while (!todo.empty()) {
     const Range r = todo.back(); todo.pop_back();
     bool ok = false;
     if (!r.known_bad) {
-      const size_t o = r.lo, n = r.hi - r.lo;
-      rc = verify_bp(ctx, n, nlen, llen, k, D.fn, D.fl, ninit, rp->d_g(), rp->d_G(), rp->d_H(), rho + o * 8, q + o * 8,
-                                       sp + o * 8, pub_norm + o * nlen * 8, pub_lin_c + o * llen * 8, pub_lin_x + o * llen * 8, es + o * k * 8, wit_norm + o * D.fn * 8,
-                                       wit_lin + o * D.fl * 8, init_sc + o * ninit * 8, init_pts + o * ninit * 16, resp_pts + o * 2 * k * 16, out_xy, false);
+      const int rc = rp_verify_combine(rp, A, r.lo, r.hi - r.lo, out_xy);
       if (rc) return rc;
-      ok = is_inf(out_xy);
+      ok = rp_point_is_inf(out_xy);
     }
     if (ok) continue;
     if (r.hi - r.lo == 1) { if (proof_status[r.lo] == BPPP_RP_VALID) proof_status[r.lo] = BPPP_RP_INVALID; continue; }
@@ -1021,15 +1048,11 @@ static int rp_verify_shard_run(bppp_rp *rp, size_t batch, uint64_t index_offset,
   }
   return BPPP_OK;
 }
+}  // namespace bppp
 
-int bppp_rp_verify_batch(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint8_t *proof_files, const uint8_t seed[32], int *accept,
-                         uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
-  if (!rp || !accept) return BPPP_ERR_ARG;
+// the host-buffer entry points' grow-only device staging of one handle: coms then proofs (256-byte aligned), for `batch` proofs
+int rp_ensure_stage(bppp_rp *rp, size_t batch) {
   bppp_ctx *ctx = rp->ctx;
-  if (ctx_closed(ctx)) return BPPP_ERR_ARG;
-  if (!batch) { *accept = 1; return BPPP_OK; }
-  if (!coms_files || !proof_files) return fail(ctx, BPPP_ERR_ARG, "rp_verify_batch: null input");
-  hipSetDevice(ctx->device);
   const size_t cb = batch * (size_t)rp->D.coms_bytes, pb = batch * (size_t)rp->D.proof_bytes;
   const size_t cbp = (cb + 255) & ~(size_t)255;
   if (cbp + pb + 256 > rp->stage_bytes) {      // a private grow-only buffer: the context's scratch serves bppp_nl_verify_batch_device
@@ -1039,7 +1062,22 @@ int bppp_rp_verify_batch(bppp_rp *rp, size_t batch, const uint8_t *coms_files, c
     BPPP_HIP(ctx, hipMalloc(&rp->stage, cbp + pb + 256));
     rp->stage_bytes = cbp + pb + 256;
   }
+  return BPPP_OK;
+}
+
+extern "C" {
+
+int bppp_rp_verify_batch(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint8_t *proof_files, const uint8_t seed[32], int *accept,
+                         uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
+  if (!rp || !accept) return BPPP_ERR_ARG;
+  bppp_ctx *ctx = rp->ctx;
+  if (ctx_closed(ctx)) return BPPP_ERR_ARG;
+  if (!batch) { *accept = 1; return BPPP_OK; }
+  if (!coms_files || !proof_files) return fail(ctx, BPPP_ERR_ARG, "rp_verify_batch: null input");
+  hipSetDevice(ctx->device);
+  { int rc0 = rp_ensure_stage(rp, batch); if (rc0) return rc0; }
   void *stage = rp->stage;
+  const size_t cbp = (batch * (size_t)rp->D.coms_bytes + 255) & ~(size_t)255;
   rp->host_coms = coms_files; rp->host_proofs = proof_files;          // uploaded in slices by the decode stage of the call below
   int rc = bppp_rp_verify_batch_device(rp, batch, stage, (char *)stage + cbp, seed, accept, proof_status, challenges_out, combined_xy);
   rp->host_coms = rp->host_proofs = nullptr;

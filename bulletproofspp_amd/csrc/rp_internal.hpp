@@ -49,6 +49,19 @@ int nl_verify_batch_run(bppp_ctx *, size_t, size_t, size_t, size_t, size_t, size
                         const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, uint64_t *, bool);
 int ip_verify_batch_run(bppp_ctx *, size_t, size_t, size_t, size_t, size_t, size_t, size_t, const void *, const void *, const void *, const void *, const void *, const void *,
                         const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, uint64_t *, bool);
+// ... and their first step alone, the assembly of the MSM's input (same arguments up to `validate`, then: shared scalars [G | H | g],
+// per-proof scalars [batch][ninit + 2k], points — [G | H | g | per-proof] when gather_shared, else the per-proof ones alone — and the
+// flag word read after the MSM).  Scratch: ctx->ws2 of at least {nl,ip}_verify_batch_scratch bytes, made sure of by the caller.
+int nl_verify_batch_assemble(bppp_ctx *, size_t, size_t, size_t, size_t, size_t, size_t, size_t, const void *, const void *, const void *, const void *, const void *,
+                             const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *,
+                             bool validate, uint32_t *sc_shared, uint32_t *sc_tail, uint32_t *pts, bool gather_shared, uint32_t *flags);
+int ip_verify_batch_assemble(bppp_ctx *, size_t, size_t, size_t, size_t, size_t, size_t, size_t, const void *, const void *, const void *, const void *, const void *,
+                             const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *,
+                             bool validate, uint32_t *sc_shared, uint32_t *sc_tail, uint32_t *pts, bool gather_shared, uint32_t *flags);
+size_t nl_verify_batch_scratch(size_t batch, size_t nlen, size_t llen, size_t k);
+size_t ip_verify_batch_scratch(size_t batch, size_t nlen, size_t llen, size_t k, size_t fn);
+int ip_verify_batch_flags(bppp_ctx *, uint32_t hflags);     // the inner-product assembly's flag word -> error code
+inline bool rp_point_is_inf(const uint64_t *p) { uint64_t o = 0; for (int i = 0; i < 8; i++) o |= p[i]; return o == 0; }
 
 }  // namespace bppp
 
@@ -125,4 +138,24 @@ struct bppp_rp {
 };
 
 int rp_ensure_twin(bppp_rp *rp);      // csrc/rp.hip
+int rp_ensure_stage(bppp_rp *rp, size_t batch);   // csrc/rp.hip: rp->stage holds `batch` files (coms, then proofs 256-byte aligned)
+
+namespace bppp {
+// The verifier's per-proof arrays of one prepared batch, carved from the handle's rp->work (csrc/rp.hip).  Every array is [batch][...],
+// so proofs [lo, hi) are the same arrays at offset pointers.
+struct RpVerifyArrays {
+  size_t batch;
+  uint32_t *init_pts, *resp_pts, *wit_norm, *wit_lin, *ch, *es, *rho, *q, *sp, *pub_norm, *pub_lin_c, *pub_lin_x, *init_sc, *bad;
+};
+// decodeProof, the transcript hashing (device or host oracle, as the handle chooses), the public scalars and the weights rho of the
+// proofs at job positions [index_offset, index_offset + batch): everything of the verification but the argument's combination.  Queued
+// on the context's stream; bad[b] marks a proof that did not decode and rp->hflag[0] receives "some proof did not" (read it once the
+// stream has drained).  The arrays stay valid until the handle's next verification.
+int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms, const void *d_proofs, const uint8_t seed[32], RpVerifyArrays &A);
+// verifyBPM's combination of proofs [lo, lo + n) of a prepared batch: one MSM, returns with the stream drained
+int rp_verify_combine(bppp_rp *rp, const RpVerifyArrays &A, size_t lo, size_t n, uint64_t out_xy[8]);
+// the culprits of a rejected batch by bisection: a VALID proof_status[b] whose combination fails becomes INVALID.  known_bad: the
+// whole batch's combination is already known not to be the identity (otherwise it is evaluated first)
+int rp_find_culprits(bppp_rp *rp, const RpVerifyArrays &A, bool known_bad, uint32_t *proof_status);
+}  // namespace bppp
 int rp_ensure_comb(bppp_rp *rp);      // csrc/rpprove.hip

@@ -171,3 +171,9 @@ extern "C" int bppp_test_mulmod_rate(bppp_ctx *ctx, int iters, double *mulmods_p
   hipEventDestroy(e0); hipEventDestroy(e1); hipFree(seed); hipFree(sink);
   return rc;
 }
+
+extern "C" int bppp_test_last_mixed_msm_terms(bppp_ctx *ctx, uint64_t *terms) {
+  if (!ctx || !terms) return BPPP_ERR_ARG;
+  *terms = ctx->last_mixed_terms;
+  return BPPP_OK;
+}

@@ -955,6 +955,63 @@ class NativeRangeProofs:
         return bool(acc.value), ([int(v) for v in status[:B]] if want_status else None), chs
 
 
+def _mixed_groups(files):
+    """bppp_rp_group[] for (handle, batch, coms pointer, proofs pointer) rows; every handle on one context"""
+    from .capi import RpGroup
+    arr = (RpGroup * max(len(files), 1))()
+    for g, (nat, B, pc, pp) in zip(arr, files):
+        g.rp, g.batch, g.coms_files, g.proof_files = (nat.h.value if nat.h else None), B, pc, pp
+    return arr
+
+
+def verify_mixed(gpu, groups, seed: Optional[bytes] = None, want_status: bool = False):
+    """bppp_rp_verify_mixed: proofs of SEVERAL setups in one call and one combined MSM.  groups = [(NativeRangeProofs or
+    NativeBinaryRangeProofs, commitments files, proof files)]; the job is the groups concatenated in order.  Returns accept, or
+    (accept, status list in job order) with want_status.  A file of the wrong length makes the whole job MALFORMED without a library
+    call, as NativeRangeProofs.verify_batch does for its batch.  `seed`: fresh from os.urandom unless given (fixed seeds are for tests)."""
+    import ctypes as C
+    import numpy as np
+    if seed is None:
+        seed = os.urandom(32)
+    if len(seed) != 32:
+        raise ValueError("a 32-byte seed is required")
+    groups = [(nat, list(cf), list(pf)) for nat, cf, pf in groups]
+    if any(len(cf) != len(pf) for _, cf, pf in groups):
+        raise ValueError("one commitments file per proof is required")
+    total = sum(len(pf) for _, _, pf in groups)
+    if any(len(c) != nat.shape["coms_bytes"] for nat, cf, _ in groups for c in cf) or \
+            any(len(p_) != nat.shape["proof_bytes"] for nat, _, pf in groups for p_ in pf):
+        return (False, [2] * total) if want_status else False
+    keep = [(np.frombuffer(b"".join(cf) or b"\0", dtype=np.uint8), np.frombuffer(b"".join(pf) or b"\0", dtype=np.uint8)) for _, cf, pf in groups]
+    arr = _mixed_groups([(nat, len(pf), cb.ctypes.data, pb.ctypes.data) for (nat, _, pf), (cb, pb) in zip(groups, keep)])
+    acc = C.c_int(0)
+    status = np.zeros(max(total, 1), dtype=np.uint32)
+    sd = np.frombuffer(seed, dtype=np.uint8)
+    rc = gpu.lib.bppp_rp_verify_mixed(C.cast(arr, C.c_void_p), len(groups), C.c_void_p(sd.ctypes.data), C.byref(acc),
+                                      C.c_void_p(status.ctypes.data) if want_status else None, None)
+    gpu._check(rc, "bppp_rp_verify_mixed")
+    return (bool(acc.value), [int(v) for v in status[:total]]) if want_status else bool(acc.value)
+
+
+def verify_mixed_device(gpu, groups, seed: bytes, index_offset: int = 0):
+    """bppp_rp_verify_mixed_device: groups = [(handle, batch, device pointer of the commitments files, of the proof files)], the job's
+    proofs at positions [index_offset, index_offset + total batch) (a rank's share of a sharded mixed job).  Returns (accept, status list
+    in job order, the combined point) — the combined point is the sum of every group's verify_batch_device_point at its offset."""
+    import ctypes as C
+    import numpy as np
+    from .capi import array_to_point
+    groups = list(groups)
+    total = sum(B for _, B, _, _ in groups)
+    arr = _mixed_groups([(nat, B, int(pc), int(pp)) for nat, B, pc, pp in groups])
+    acc, out = C.c_int(0), np.zeros(8, dtype=np.uint64)
+    status = np.zeros(max(total, 1), dtype=np.uint32)
+    sd = np.frombuffer(seed, dtype=np.uint8)
+    rc = gpu.lib.bppp_rp_verify_mixed_device(C.cast(arr, C.c_void_p), len(groups), index_offset, C.c_void_p(sd.ctypes.data), C.byref(acc),
+                                             C.c_void_p(status.ctypes.data), C.c_void_p(out.ctypes.data))
+    gpu._check(rc, "bppp_rp_verify_mixed_device")
+    return bool(acc.value), [int(v) for v in status[:total]], array_to_point(out)
+
+
 # ----------------------------------------------------------------------------- schema files (app/Parse.hs, app/Main.hs)
 def approx_log_w(n: int) -> int:
     """approxLogW (app/Parse.hs:202-206): the default base for a range of width n"""

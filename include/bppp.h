@@ -428,6 +428,32 @@ int bppp_rp_verify_batch_device(bppp_rp *rp, size_t batch, const void *d_coms_fi
 int bppp_rp_verify_shard_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const uint8_t seed[32],
                                 int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy);
 
+/* Batch verification of proofs of SEVERAL setups with one combined MSM: a block or a mempool holds many shapes (32 .. 128 outputs,
+ * norm-linear and inner-product argument, typed-reciprocal and binary proofs), each group below one handle of this context.  The job
+ * is the groups concatenated in the order given: proof j of group s has job position index_offset + start_s + j (start_s = the earlier
+ * groups' batches) and the weight rho bppp_rp_verify_shard_device gives that position, so combined_xy is exactly the sum over groups of
+ * bppp_rp_verify_shard_device (rp_s, batch_s, index_offset + start_s, ...)'s combined point with the same seed; a rank's share of a
+ * sharded mixed job is this call with its index_offset, the ranks' points added with bppp_sum_points as there.
+ * The shared-basis scalars are merged across setups: every setup's verification basis [g | H | G] is the prefix ps[1 : 2 + linLen +
+ * nrmLen] of the point stream its points came from (TypedReciprocal.hs:334, :348-349; Binary.hs:147-148), so handles whose bases
+ * (points 1.. of the creation's points_xy, compared point by point) extend one another share the longest one's terms; unrelated bases
+ * are concatenated.  One MSM of sum over those families of the longest basis + sum_s batch_s (ninit_s + 2 rounds_s) terms.
+ * *accept = 1 iff every proof of every group decodes and the one combination is the identity.  proof_status (may be NULL): [total
+ * batch] in job order, BPPP_RP_VALID / _INVALID / _MALFORMED; on rejection each group's own combination is evaluated and failing
+ * groups are bisected as in bppp_rp_verify_batch.  BPPP_ERR_ARG: handles on different contexts, one handle in two groups, 2^22 proofs
+ * or more, null files for a non-empty group.  Empty groups take no part; an empty job is accepted.
+ * _device: the files are in HBM; bppp_rp_verify_mixed takes host files, uploads them and runs as _device with index_offset 0. */
+typedef struct bppp_rp_group {
+  bppp_rp *rp;               /* the setup these proofs claim */
+  size_t batch;              /* proofs in this group (0 allowed) */
+  const void *coms_files;    /* [batch][coms_bytes of rp] */
+  const void *proof_files;   /* [batch][proof_bytes of rp] */
+} bppp_rp_group;
+int bppp_rp_verify_mixed_device(const bppp_rp_group *groups, size_t ngroups, uint64_t index_offset, const uint8_t seed[32], int *accept,
+                                uint32_t *proof_status, uint64_t *combined_xy);
+int bppp_rp_verify_mixed(const bppp_rp_group *groups, size_t ngroups, const uint8_t seed[32], int *accept, uint32_t *proof_status,
+                         uint64_t *combined_xy);
+
 /* Batch prover: `batch` proofs of this setup in lockstep — proveM of RangeProof (src/RangeProof.hs:93-97) = proveTRRPM
  * (src/RangeProof/TypedReciprocal.hs:399-446; blinding algebra src/RangeProof/Internal.hs:118-196) followed by proveBPM
  * (src/Bulletproof.hs:357-359), then encodeProof' (src/RangeProof.hs:60-66).  Per proof b: amounts / types / blinds are

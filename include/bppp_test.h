@@ -26,6 +26,9 @@ int bppp_test_point_op(bppp_ctx *ctx, int op, const uint64_t *p, const uint64_t 
 /* Measured ceiling of the field layer: modular multiplications per second of a kernel that does nothing but independent
  * Fq multiplications (10x26-bit limbs) at 8 wavefronts per SIMD.  bench.py quotes the MSM's multiplication rate against it. */
 int bppp_test_mulmod_rate(bppp_ctx *ctx, int iters, double *mulmods_per_sec);
+/* Terms of the one MSM the last bppp_rp_verify_mixed* call on this context ran (0 after an empty job): a test sees that the shared
+ * bases of setups from one point stream were merged. */
+int bppp_test_last_mixed_msm_terms(bppp_ctx *ctx, uint64_t *terms);
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
