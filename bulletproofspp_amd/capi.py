@@ -30,7 +30,7 @@ SYMBOLS = [
     "bppp_glv_decompose_device", "bppp_msm_glv_device",
     "bppp_basis_create", "bppp_basis_create_device", "bppp_basis_destroy", "bppp_basis_info", "bppp_msm_basis", "bppp_basis_enable_comb",
     "bppp_rp_create", "bppp_rp_create_binary", "bppp_rp_destroy", "bppp_rp_info", "bppp_rp_set_option", "bppp_rp_shape_of", "bppp_rp_digits", "bppp_hash_to_scalar", "bppp_rp_verify_batch", "bppp_rp_verify_batch_device", "bppp_rp_verify_shard_device", "bppp_rp_prove_batch",
-    "bppp_rp_verify_mixed", "bppp_rp_verify_mixed_device",
+    "bppp_rp_verify_mixed", "bppp_rp_verify_mixed_device", "bppp_rp_verify_each", "bppp_rp_verify_each_device",
 ]
 
 
@@ -135,6 +135,8 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_prove_batch.argtypes = [vp, sz, vp, vp, vp, vp, sz, vp, vp]
     lib.bppp_rp_verify_mixed.argtypes = [vp, sz, vp, C.POINTER(i), vp, vp]
     lib.bppp_rp_verify_mixed_device.argtypes = [vp, sz, C.c_uint64, vp, C.POINTER(i), vp, vp]
+    lib.bppp_rp_verify_each.argtypes = [vp, sz, vp, vp, vp, vp]
+    lib.bppp_rp_verify_each_device.argtypes = [vp, sz, vp, vp, vp, vp]
     lib.bppp_profile_enable.argtypes = [vp, i]
     lib.bppp_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), i]
     return lib
@@ -152,6 +154,8 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_point_op.argtypes = [vp, i, vp, vp, sz, vp]
     lib.bppp_test_mulmod_rate.argtypes = [vp, i, C.POINTER(C.c_double)]
     lib.bppp_test_last_mixed_msm_terms.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.bppp_test_rp_last_verify_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.bppp_test_rp_set_each_chunk.argtypes = [vp, sz]
     return lib
 
 
@@ -176,7 +180,7 @@ class RpShape(C.Structure):
                                           "challenges_per_proof")]
 
 
-RP_OPTIONS = {"comb_min": 1, "comb_budget": 2, "comb_bits": 3, "split_min": 4, "host_oracle_max": 5, "fold_points": 6, "host_algebra": 7, "timing": 8}
+RP_OPTIONS = {"comb_min": 1, "comb_budget": 2, "comb_bits": 3, "split_min": 4, "host_oracle_max": 5, "fold_points": 6, "host_algebra": 7, "timing": 8, "culprits": 9}
 RP_SHARED, RP_OUTPUT, RP_ASSUMED = 1, 2, 4
 RP_VALID, RP_INVALID, RP_MALFORMED = 0, 1, 2
 

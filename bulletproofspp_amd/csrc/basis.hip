@@ -140,6 +140,19 @@ int bppp_msm_basis(bppp_basis *h, const void *d_scalars, size_t n_terms, size_t 
   return msm_run_ex(ctx, d_scalars, h->table, n_terms, batch, 1, h->c, out_xy, h->n, nullptr);
 }
 
+}  // extern "C"
+
+namespace bppp {
+// bppp_msm_basis with the results LEFT IN HBM (d_out [batch][16], canonical affine) and nothing waited for, through the windowed table
+// (the per-proof verifier, csrc/rpeach.hip).  batch > 4.
+int basis_msm_dev(bppp_basis *h, const void *d_scalars, size_t n_terms, size_t batch, uint32_t *d_out) {
+  if (!h || !d_scalars || !d_out || batch <= 4 || !n_terms || n_terms > h->n) return BPPP_ERR_ARG;
+  uint64_t dummy[8];
+  return msm_run_ex(h->ctx, d_scalars, h->table, n_terms, batch, 1, h->c, dummy, h->n, d_out);
+}
+}  // namespace bppp
+extern "C" {
+
 // Adds the comb table tab[w][i][d-1] = d 2^(c w) P_i (csrc/comb.hip) to a registered basis: bppp_msm_basis of >= 64 instances then
 // costs one mixed addition per non-zero digit and nothing else.  window_bits = 0: the widest window (<= 18) whose table fits
 // budget_bytes.  The table stays until the handle is destroyed; *table_bytes (may be NULL) reports its size.

@@ -623,3 +623,113 @@ extern "C" int bppp_ip_verify_batch_device(bppp_ctx *ctx, size_t batch, size_t n
   return bppp::ip_verify_batch_run(ctx, batch, nlen, llen, k, fn, fl, ninit, d_g_xy, d_norm_g_xy, d_lin_h_xy, d_rho, d_r, d_sp, d_pub_norm, d_pub_lin_c, d_pub_lin_x, d_es,
                                    d_wit_norm, d_wit_lin, d_init_scalars, d_init_points_xy, d_responses_xy, out_xy, true);
 }
+
+// ------------------------------------------------------------------------------------------------ per-proof rows (csrc/rpeach.hip)
+// The term list T_b of ONE proof, unweighted and not summed over the batch (bppp_rp_verify_each): row[b] = proof b's scalars on the
+// handle's basis [g | H | G] (commitRPW's order, src/RangeProof/Internal.hs:45-50), tail[b] = its scalars on its own
+// [init points | responses], pts[b] = those points.  The g scalar and the tail are k_vb_proof's / k_ipvb_proof's with every rho = 1
+// (`ones`); the H and G columns are what k_vb_shared4 / k_ipvb_norm add up over the batch, written per proof by the kernels below.
+namespace bppp {
+// pub[i] - tensor'(vs, es, qs)[i] of one proof for the four positions i0 .. i0 + 3 (k_vb_shared4's expansion with rho = 1), stored at out[i]
+BPPP_DI void each_put4(const uint32_t *pub, const uint32_t *wit, uint32_t nvs, const uint32_t *f, uint32_t len, int k, bool use_q, uint32_t i0, uint32_t *out) {
+  if (k < 2) {                                     // the tensor index differs inside the group: position by position
+    for (uint32_t i = i0; i < min(len, i0 + 4); i++) fe_store(out + (size_t)i * 8, fe_sub<1>(fe_load(pub + (size_t)i * 8), tensor_at(wit, nvs, f, k, i, use_q)));
+    return;
+  }
+  fr t0 = fr_zero(), t1 = t0, t2 = t0, t3 = t0;
+  const uint32_t hi = i0 >> k;
+  if (hi < nvs) {                                  // zipWithDef' default 0 beyond the tensor (src/Utils.hs:182-184)
+    const fr e0 = fr_load(f + (size_t)k * 8), q0 = fr_load(f), e1 = fr_load(f + (size_t)(k + 1) * 8), q1 = fr_load(f + 8);
+    fr base = fr_load(wit + (size_t)hi * 8);
+    for (int rr = 2; rr < k; rr++) {
+      const bool bit = (i0 >> rr) & 1u;
+      if (bit || use_q) base = fr_mul(base, fr_load(f + (size_t)((bit ? k : 0) + rr) * 8));
+    }
+    t0 = base;
+    t1 = fr_mul(e0, t0); if (use_q) t0 = fr_mul(q0, t0);
+    t2 = fr_mul(e1, t0); t3 = fr_mul(e1, t1); if (use_q) { t0 = fr_mul(q1, t0); t1 = fr_mul(q1, t1); }
+  }
+#define EACH_ST(O, T) if (i0 + (O) < len) fr_store(out + (size_t)(i0 + (O)) * 8, fr_sub<1>(fr_load(pub + (size_t)(i0 + (O)) * 8), T));
+  EACH_ST(0, t0) EACH_ST(1, t1) EACH_ST(2, t2) EACH_ST(3, t3)
+#undef EACH_ST
+}
+
+// norm-linear rows: lane (b, group) fills four H (use_q = 0, pub_lin_x) or four G (use_q = 1, pub_norm) columns; group 0 also copies g
+__global__ void __launch_bounds__(256) k_each_rows_nl(const uint32_t *__restrict__ pub_norm, const uint32_t *__restrict__ wit_norm, uint32_t fn,
+                                                      const uint32_t *__restrict__ pub_lin_x, const uint32_t *__restrict__ wit_lin, uint32_t fl,
+                                                      const uint32_t *__restrict__ fac, const uint32_t *__restrict__ gs, uint32_t batch, uint32_t nlen,
+                                                      uint32_t llen, int k, uint32_t *__restrict__ rows) {
+  const uint32_t GH = (llen + 3) / 4, per = GH + (nlen + 3) / 4, T = 1 + llen + nlen;
+  const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (uint64_t)batch * per) return;
+  const uint32_t b = (uint32_t)(idx / per), g = (uint32_t)(idx % per);
+  uint32_t *row = rows + (size_t)b * T * 8;
+  const uint32_t *f = fac + (size_t)b * 2 * k * 8;
+  if (g == 0) fe_store(row, fe_load(gs + (size_t)b * 8));
+  if (g < GH) each_put4(pub_lin_x + (size_t)b * llen * 8, wit_lin + (size_t)b * fl * 8, fl, f, llen, k, false, 4 * g, row + 8);
+  else each_put4(pub_norm + (size_t)b * nlen * 8, wit_norm + (size_t)b * fn * 8, fn, f, nlen, k, true, 4 * (g - GH), row + (size_t)(1 + llen) * 8);
+}
+
+// inner-product rows: the G columns with makeNorm's basis change folded in (see k_ipvb_norm), one lane per pair (2j, 2j + 1);
+// the H columns as the norm-linear ones over 1 / e (facx, no q)
+__global__ void __launch_bounds__(256) k_each_rows_ip(const uint32_t *__restrict__ r_in, const uint32_t *__restrict__ pub_norm, const uint32_t *__restrict__ v,
+                                                      uint32_t fm, const uint32_t *__restrict__ pub_lin_x, const uint32_t *__restrict__ wit_lin, uint32_t fl,
+                                                      const uint32_t *__restrict__ facx, const uint32_t *__restrict__ facy, const uint32_t *__restrict__ gs,
+                                                      uint32_t batch, uint32_t nlen, uint32_t llen, int k, uint32_t *__restrict__ rows) {
+  const uint32_t GH = (llen + 3) / 4, per = GH + (nlen + 1) / 2, T = 1 + llen + nlen;
+  const uint64_t idx = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (uint64_t)batch * per) return;
+  const uint32_t b = (uint32_t)(idx / per), g = (uint32_t)(idx % per);
+  uint32_t *row = rows + (size_t)b * T * 8;
+  const uint32_t *fx = facx + (size_t)b * 2 * k * 8;
+  if (g == 0) fe_store(row, fe_load(gs + (size_t)b * 8));
+  if (g < GH) { each_put4(pub_lin_x + (size_t)b * llen * 8, wit_lin + (size_t)b * fl * 8, fl, fx, llen, k, false, 4 * g, row + 8); return; }
+  const uint32_t j = g - GH, i = 2 * j;
+  const fe tx = tensor_at(v + (size_t)b * 2 * fm * 8, fm, fx, k, j, true);
+  const fe ty = tensor_at(v + ((size_t)b * 2 * fm + fm) * 8, fm, facy + (size_t)b * 2 * k * 8, k, j, false);
+  const uint32_t *pub = pub_norm + (size_t)b * nlen * 8;
+  uint32_t *out = row + (size_t)(1 + llen) * 8;
+  fe_store(out + (size_t)i * 8, fe_sub<1>(fe_load(pub + (size_t)i * 8), fe_mul<1>(fe_load(r_in + (size_t)b * 8), fe_sub<1>(tx, ty))));
+  if (i + 1 < nlen) fe_store(out + (size_t)(i + 1) * 8, fe_sub<1>(fe_load(pub + (size_t)(i + 1) * 8), fe_add<1>(tx, ty)));
+}
+
+// bytes of `scratch` each_rows_assemble carves for n proofs
+size_t each_rows_scratch(int flavour, size_t n, size_t llen, size_t k, size_t fn) {
+  const size_t kk = k ? k : 1, G4 = (llen + 3) / 4;
+  if (flavour) return vb_round(((2 * n * 2 * kk + n + n * (fn ? fn : 2) + n + 8) * 8) * 4);       // facx, facy, qf, v, gs, flags
+  return vb_round(((n * 2 * kk + n + n * G4 + 8 + n) * 8) * 4);                                      // fac, qf2, lin partials, gs
+}
+// rows [n][1 + llen + nlen], tail [n][ninit + 2k], pts [n][ninit + 2k] of proofs whose arrays start at the given pointers (one chunk of a
+// prepared batch); `ones` holds n scalars 1.  Queued on the context's stream.
+int each_rows_assemble(bppp_ctx *ctx, int flavour, size_t n, size_t nlen, size_t llen, size_t k, size_t fn, size_t fl, size_t ninit, const uint32_t *ones,
+                       const uint32_t *q, const uint32_t *sp, const uint32_t *pub_norm, const uint32_t *pub_lin_c, const uint32_t *pub_lin_x,
+                       const uint32_t *es, const uint32_t *wit_norm, const uint32_t *wit_lin, const uint32_t *init_sc, const uint32_t *init_pts,
+                       const uint32_t *resp_pts, uint32_t *scratch, uint32_t *rows, uint32_t *tail, uint32_t *pts) {
+  hipStream_t st = ctx->stream;
+  const size_t kk = k ? k : 1, per = ninit + 2 * k, G4 = (llen + 3) / 4, GH = G4;
+  if (!flavour) {
+    uint32_t *fac = scratch, *qf2 = fac + n * 2 * kk * 8, *partial = qf2 + n * 8, *gs = partial + (n * G4 + 8) * 8;
+    k_vb_factors<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st>>>(q, es, (uint32_t)n, (int)k, fac, qf2);
+    if (G4) k_vb_lin_partial<<<dim3((unsigned)((n * G4 + 255) / 256)), dim3(256), 0, st>>>(wit_lin, (uint32_t)fl, pub_lin_c, (uint32_t)llen, fac, (int)k, (uint32_t)n,
+                                                                                        (uint32_t)G4, partial);
+    k_vb_proof<<<dim3((unsigned)n), dim3(64), 0, st>>>(ones, sp, qf2, wit_norm, (uint32_t)fn, partial, (uint32_t)G4, (int)k, init_sc, (uint32_t)ninit, es, gs, tail);
+    const uint64_t lanes = (uint64_t)n * (GH + (nlen + 3) / 4);
+    k_each_rows_nl<<<dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st>>>(pub_norm, wit_norm, (uint32_t)fn, pub_lin_x, wit_lin, (uint32_t)fl, fac, gs,
+                                                                               (uint32_t)n, (uint32_t)nlen, (uint32_t)llen, (int)k, rows);
+  } else {
+    const size_t fm = fn / 2;
+    uint32_t *facx = scratch, *facy = facx + n * 2 * kk * 8, *qf = facy + n * 2 * kk * 8, *v = qf + n * 8, *gs = v + n * (fn ? fn : 2) * 8, *flags = gs + n * 8;
+    k_ipvb_factors<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st>>>(q, es, wit_norm, (uint32_t)n, (int)k, (uint32_t)fm, facx, facy, qf, v, flags);
+    k_ipvb_proof<<<dim3((unsigned)n), dim3(64), 0, st>>>(ones, sp, qf, v, (uint32_t)fm, wit_lin, (uint32_t)fl, pub_lin_c, (uint32_t)llen, facx, (int)k, init_sc,
+                                                         (uint32_t)ninit, es, gs, tail);
+    const uint64_t lanes = (uint64_t)n * (GH + (nlen + 1) / 2);
+    k_each_rows_ip<<<dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st>>>(q, pub_norm, v, (uint32_t)fm, pub_lin_x, wit_lin, (uint32_t)fl, facx, facy, gs,
+                                                                               (uint32_t)n, (uint32_t)nlen, (uint32_t)llen, (int)k, rows);
+  }
+  const uint64_t Tg = (uint64_t)n * per;
+  k_vb_gather_points<<<dim3((unsigned)((4 * Tg + 255) / 256)), dim3(256), 0, st>>>(nullptr, 0, nullptr, 0, nullptr, (const uint4 *)init_pts, (uint32_t)ninit,
+                                                                                  (const uint4 *)resp_pts, (uint32_t)(2 * k), 0u, Tg, (uint4 *)pts);
+  if (hipGetLastError() != hipSuccess) return fail(ctx, BPPP_ERR_HIP, "rp_verify_each: assembling the rows failed");
+  return BPPP_OK;
+}
+}  // namespace bppp

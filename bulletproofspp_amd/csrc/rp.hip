@@ -518,6 +518,7 @@ void bppp_rp_destroy(bppp_rp *rp) {
   if (rp->d_plan) hipFree(rp->d_plan);
   if (rp->work) hipFree(rp->work);
   if (rp->stage) hipFree(rp->stage);
+  if (rp->ework) hipFree(rp->ework);
   if (rp->hflag) hipHostFree(rp->hflag);
   if (rp->hstage) hipHostFree(rp->hstage);
   for (auto &e : rp->slice_ev) if (e) hipEventDestroy(e);
@@ -659,6 +660,8 @@ int bppp_rp_set_option(bppp_rp *rp, int option, uint64_t value) {
     case BPPP_RP_OPT_FOLD_POINTS: o.fold_points = value != 0; break;
     case BPPP_RP_OPT_HOST_ALGEBRA: o.host_algebra = value != 0; break;
     case BPPP_RP_OPT_TIMING: o.timing = value != 0; break;
+    case BPPP_RP_OPT_CULPRITS: if (value > 1) return fail(rp->ctx, BPPP_ERR_ARG, "rp_set_option: culprits must be 0 (bisection) or 1 (one per-proof pass)");
+                               o.culprits = (int)value; break;
     default: return fail(rp->ctx, BPPP_ERR_ARG, "rp_set_option: unknown option");
   }
   if (rp->twin) rp->twin->opt = o;
@@ -829,6 +832,7 @@ static int rp_verify_shard_run(bppp_rp *rp, size_t batch, uint64_t index_offset,
   bppp_ctx *ctx = rp->ctx;
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
   *accept = 0;
+  rp->n_combined = rp->n_each = 0;
   if (combined_xy) memset(combined_xy, 0, 64);
   if (!batch) { *accept = 1; return BPPP_OK; }
   if (!d_coms_files || !d_proof_files || !seed || batch >= (1u << 22)) return fail(ctx, BPPP_ERR_ARG, "rp_verify_batch: bad arguments");
@@ -1021,14 +1025,30 @@ int rp_verify_combine(bppp_rp *rp, const RpVerifyArrays &A, size_t o, size_t n, 
   const RpDims &D = rp->D;
   const size_t nlen = S.nlen, llen = S.llen, k = S.rounds, ninit = D.nrp + D.nr;
   auto verify_bp = S.flavour ? ip_verify_batch_run : nl_verify_batch_run;
+  rp->n_combined++;
   return verify_bp(rp->ctx, n, nlen, llen, k, D.fn, D.fl, ninit, rp->d_g(), rp->d_G(), rp->d_H(), A.rho + o * 8, A.q + o * 8, A.sp + o * 8,
                    A.pub_norm + o * nlen * 8, A.pub_lin_c + o * llen * 8, A.pub_lin_x + o * llen * 8, A.es + o * k * 8, A.wit_norm + o * D.fn * 8,
                    A.wit_lin + o * D.fl * 8, A.init_sc + o * ninit * 8, A.init_pts + o * ninit * 16, A.resp_pts + o * 2 * k * 16, out_xy, false);
 }
 
 // The combination is not the identity (known_bad), or may not be: find the culprits by bisection.  A malformed proof decodes to infinity
-// points and is simply another failing member.  O(f log B) combined MSMs for f bad proofs.
+// points and is simply another failing member.  O(f log B) combined MSMs for f bad proofs.  With BPPP_RP_OPT_CULPRITS = 1 a rejected
+// batch is resolved by one per-proof pass over its prepared arrays instead (csrc/rpeach.hip): the same statuses at a cost that does not
+// grow with f.
 int rp_find_culprits(bppp_rp *rp, const RpVerifyArrays &A, bool known_bad, uint32_t *proof_status) {
+  if (rp->opt.culprits == 1) {
+    if (!known_bad) {
+      uint64_t xy[8];
+      const int rc = rp_verify_combine(rp, A, 0, A.batch, xy);
+      if (rc) return rc;
+      if (rp_point_is_inf(xy)) return BPPP_OK;
+    }
+    std::vector<uint32_t> each(A.batch);
+    const int rc = rp_each_pass(rp, A, each.data(), nullptr);
+    if (rc) return rc;
+    for (size_t b = 0; b < A.batch; b++) if (proof_status[b] == BPPP_RP_VALID && each[b] != BPPP_RP_VALID) proof_status[b] = BPPP_RP_INVALID;
+    return BPPP_OK;
+  }
   struct Range { size_t lo, hi; bool known_bad; };
   std::vector<Range> todo;
   todo.push_back(Range{0, A.batch, known_bad});

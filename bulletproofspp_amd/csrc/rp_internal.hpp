@@ -92,6 +92,7 @@ struct RpOptions {
   bool fold_points = false;           // BPPP_NLB_FOLD_POINTS: point-folding argument although a table exists
   bool host_algebra = false;          // BPPP_RP_HOST_ALGEBRA: field algebra and hashing of the prover on the host
   bool timing = false;                // BPPP_RP_TIMING: phase times on stderr
+  int culprits = 0;                   // BPPP_RP_OPT_CULPRITS (set_option only): 0 = bisection, 1 = one per-proof pass (csrc/rpeach.hip)
   void from_env();
 };
 struct bppp_brp_tabs;      // csrc/rp.hip: device tables of a RangeProof.Binary setup
@@ -135,6 +136,11 @@ struct bppp_rp {
   uint32_t *hflag = nullptr;                     // pinned: the verifier's "some proof did not decode" word, copied out while the batch is still in flight
   void *work = nullptr; size_t work_bytes = 0;
   void *stage = nullptr; size_t stage_bytes = 0;
+  // per-proof verifier (csrc/rpeach.hip): grow-only workspace, proofs per chunk (0 = from the row budget; a test hook may set it), and
+  // what the last verification on this handle ran (combined MSMs, per-proof passes: bppp_test_rp_last_verify_counts)
+  void *ework = nullptr; size_t ework_bytes = 0;
+  size_t each_chunk = 0;
+  uint64_t n_combined = 0, n_each = 0;
 };
 
 int rp_ensure_twin(bppp_rp *rp);      // csrc/rp.hip
@@ -157,5 +163,15 @@ int rp_verify_combine(bppp_rp *rp, const RpVerifyArrays &A, size_t lo, size_t n,
 // the culprits of a rejected batch by bisection: a VALID proof_status[b] whose combination fails becomes INVALID.  known_bad: the
 // whole batch's combination is already known not to be the identity (otherwise it is evaluated first)
 int rp_find_culprits(bppp_rp *rp, const RpVerifyArrays &A, bool known_bad, uint32_t *proof_status);
+// every proof of a prepared batch decided on its own (csrc/rpeach.hip): proof_status [A.batch] (VALID / INVALID / MALFORMED) and, when
+// proof_xy is not NULL, E_b [A.batch][8] (zeros for infinity and for a malformed proof).  Returns with the stream drained.
+int rp_each_pass(bppp_rp *rp, const RpVerifyArrays &A, uint32_t *proof_status, uint64_t *proof_xy);
+size_t each_rows_scratch(int flavour, size_t n, size_t llen, size_t k, size_t fn);     // csrc/nlbatch.hip
+int each_rows_assemble(bppp_ctx *, int flavour, size_t n, size_t nlen, size_t llen, size_t k, size_t fn, size_t fl, size_t ninit, const uint32_t *ones,
+                       const uint32_t *q, const uint32_t *sp, const uint32_t *pub_norm, const uint32_t *pub_lin_c, const uint32_t *pub_lin_x,
+                       const uint32_t *es, const uint32_t *wit_norm, const uint32_t *wit_lin, const uint32_t *init_sc, const uint32_t *init_pts,
+                       const uint32_t *resp_pts, uint32_t *scratch, uint32_t *rows, uint32_t *tail, uint32_t *pts);
+int basis_msm_dev(bppp_basis *h, const void *d_scalars, size_t n_terms, size_t batch, uint32_t *d_out);     // csrc/basis.hip
+int msm_batch_dev(bppp_ctx *, const void *, const void *, size_t, size_t, int, int, uint32_t *);           // csrc/msm.hip
 }  // namespace bppp
 int rp_ensure_comb(bppp_rp *rp);      // csrc/rpprove.hip

@@ -104,6 +104,7 @@ int mixed_run(bppp_ctx *ctx, const bppp_rp_group *groups, size_t ngroups, uint64
   for (size_t s = 0; s < ngroups; s++) {
     bppp_rp *rp = groups[s].rp;
     const size_t B = groups[s].batch;
+    rp->n_combined = rp->n_each = 0;                     // (bppp_test_rp_last_verify_counts: this call's culprit search on the handle)
     if (B) {
       MixGroup g{};
       g.rp = rp; g.coms = groups[s].coms_files; g.proofs = groups[s].proof_files; g.B = B; g.start = start;

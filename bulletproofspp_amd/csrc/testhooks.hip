@@ -5,6 +5,7 @@
 #include "ec.hip.h"
 #include "modinv.hip.h"
 #include "fr26.hip.h"
+#include "rp_internal.hpp"
 
 namespace bppp {
 template <int MOD> BPPP_DI fe apply_op(int op, const fe &a, const fe &b) {
@@ -175,5 +176,18 @@ extern "C" int bppp_test_mulmod_rate(bppp_ctx *ctx, int iters, double *mulmods_p
 extern "C" int bppp_test_last_mixed_msm_terms(bppp_ctx *ctx, uint64_t *terms) {
   if (!ctx || !terms) return BPPP_ERR_ARG;
   *terms = ctx->last_mixed_terms;
+  return BPPP_OK;
+}
+
+extern "C" int bppp_test_rp_last_verify_counts(bppp_rp *rp, uint64_t *combined_msms, uint64_t *each_passes) {
+  if (!rp || !combined_msms || !each_passes) return BPPP_ERR_ARG;
+  *combined_msms = rp->n_combined;
+  *each_passes = rp->n_each;
+  return BPPP_OK;
+}
+
+extern "C" int bppp_test_rp_set_each_chunk(bppp_rp *rp, size_t proofs) {
+  if (!rp || (proofs && proofs < 8)) return BPPP_ERR_ARG;
+  rp->each_chunk = proofs;
   return BPPP_OK;
 }

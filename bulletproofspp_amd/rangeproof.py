@@ -870,7 +870,7 @@ class NativeRangeProofs:
             pass
 
     def set_option(self, name: str, value: int):
-        """bppp_rp_set_option: comb_min, comb_budget, comb_bits, split_min, host_oracle_max, fold_points, host_algebra, timing"""
+        """bppp_rp_set_option: comb_min, comb_budget, comb_bits, split_min, host_oracle_max, fold_points, host_algebra, timing, culprits"""
         from .capi import RP_OPTIONS
         self.gpu._check(self.gpu.lib.bppp_rp_set_option(self.h, RP_OPTIONS[name], int(value)), "bppp_rp_set_option")
 
@@ -932,6 +932,37 @@ class NativeRangeProofs:
                                                       C.byref(acc), None, None, C.c_void_p(out.ctypes.data))
         self.gpu._check(rc, "bppp_rp_verify_shard_device")
         return bool(acc.value), array_to_point(out)
+
+    def verify_each(self, coms_files: Sequence[bytes], proof_files: Sequence[bytes], want_points: bool = False):
+        """bppp_rp_verify_each on host byte strings: every proof decided on its own, without weights or seed.  Returns the status list
+        (0 valid, 1 invalid, 2 malformed), or (statuses, [E_b per proof]) with want_points (None for infinity, and for a malformed
+        proof).  A file of the wrong length makes the whole batch MALFORMED without a library call, as verify_batch does."""
+        import ctypes as C
+        import numpy as np
+        B = len(proof_files)
+        if len(coms_files) != B:
+            raise ValueError("one commitments file per proof is required")
+        if any(len(c) != self.shape["coms_bytes"] for c in coms_files) or any(len(p_) != self.shape["proof_bytes"] for p_ in proof_files):
+            return ([2] * B, [None] * B) if want_points else [2] * B
+        cb = np.frombuffer(b"".join(coms_files) or b"\0", dtype=np.uint8)
+        pb = np.frombuffer(b"".join(proof_files) or b"\0", dtype=np.uint8)
+        return self._verify_each(self.gpu.lib.bppp_rp_verify_each, B, C.c_void_p(cb.ctypes.data), C.c_void_p(pb.ctypes.data), want_points)
+
+    def verify_each_device(self, batch: int, d_coms: int, d_proofs: int, want_points: bool = False):
+        """bppp_rp_verify_each_device: verify_each on files already in HBM (device pointers)"""
+        import ctypes as C
+        return self._verify_each(self.gpu.lib.bppp_rp_verify_each_device, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), want_points)
+
+    def _verify_each(self, fn, B, pc, pp, want_points):
+        import ctypes as C
+        import numpy as np
+        from .capi import array_to_point
+        status = np.zeros(max(B, 1), dtype=np.uint32)
+        xy = np.zeros((max(B, 1), 8), dtype=np.uint64) if want_points else None
+        rc = fn(self.h, B, pc, pp, C.c_void_p(status.ctypes.data), C.c_void_p(xy.ctypes.data) if want_points else None)
+        self.gpu._check(rc, "bppp_rp_verify_each")
+        st = [int(v) for v in status[:B]]
+        return (st, [array_to_point(xy[b]) for b in range(B)]) if want_points else st
 
     def _verify(self, fn, B, pc, pp, seed, want_status, want_challenges, keep):
         import ctypes as C

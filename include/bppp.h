@@ -380,7 +380,11 @@ int bppp_rp_info(const bppp_rp *rp, bppp_rp_shape *out);
  *                   restores them).  Verifying 2 .. HOST_ORACLE_MAX proofs starts, once per handle, a pool of at most 15 worker threads
  *                   that sleep between calls and end with bppp_rp_destroy.
  *   FOLD_POINTS     1 = the point-folding argument although a table exists;  HOST_ALGEBRA 1 = prover's field algebra on the host;
- *   TIMING          1 = phase times on stderr. */
+ *   TIMING          1 = phase times on stderr.
+ *   CULPRITS        how a rejected batch finds its invalid proofs (proof_status of bppp_rp_verify_batch*, the failing groups of
+ *                   bppp_rp_verify_mixed*): 0 (default) = bisection, O(f log B) combined MSMs for f bad proofs; 1 = one per-proof pass
+ *                   (bppp_rp_verify_each's) over the rejected range, whatever f.  Same statuses either way.  Set here only, no
+ *                   environment variable. */
 #define BPPP_RP_OPT_COMB_MIN 1
 #define BPPP_RP_OPT_COMB_BUDGET 2
 #define BPPP_RP_OPT_COMB_BITS 3
@@ -389,6 +393,7 @@ int bppp_rp_info(const bppp_rp *rp, bppp_rp_shape *out);
 #define BPPP_RP_OPT_FOLD_POINTS 6
 #define BPPP_RP_OPT_HOST_ALGEBRA 7
 #define BPPP_RP_OPT_TIMING 8
+#define BPPP_RP_OPT_CULPRITS 9
 int bppp_rp_set_option(bppp_rp *rp, int option, uint64_t value);
 /* Host-only helpers (no context, no GPU): the shape `setup` gives a schema (nrmLen, linLen, rounds = optimalWitnessSize, file sizes);
  * `digits` of one value in one range (src/RangeProof/TypedReciprocal.hs:125-127: greedy mixed-radix digits, the first one binary when
@@ -427,6 +432,17 @@ int bppp_rp_verify_batch_device(bppp_rp *rp, size_t batch, const void *d_coms_fi
                                 uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy);
 int bppp_rp_verify_shard_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const uint8_t seed[32],
                                 int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy);
+/* Per-proof verification without weights: the same files as bppp_rp_verify_batch, every proof decided on its own.  For proof b,
+ * E_b = MSM(T_b) over exactly the term list verifyWith builds for that proof alone (verifyM of one proof); the proof is valid iff
+ * E_b is the identity.  No seed, no random weights: the verdict is exact, and its cost does not depend on how many proofs fail
+ * (one fixed-base MSM of 1 + linLen + nrmLen terms and one of ninit + 2 rounds distinct points per proof, in chunks of bounded memory).
+ * proof_status (required, [batch]): BPPP_RP_VALID / _INVALID / _MALFORMED.  proof_xy (may be NULL, [batch][8]): E_b, infinity as all
+ * zeros; zeros for a malformed proof.  Sum_b rho_b E_b with bppp_rp_verify_batch's weights is its combined_xy.
+ * Typed-reciprocal and binary handles, both argument flavours.  BPPP_ERR_ARG as bppp_rp_verify_batch (null files with a non-empty batch,
+ * a closed context, 2^22 proofs or more); an empty batch returns BPPP_OK.  _device: the files are already in HBM. */
+int bppp_rp_verify_each(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint8_t *proof_files, uint32_t *proof_status, uint64_t *proof_xy);
+int bppp_rp_verify_each_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_proof_files, uint32_t *proof_status,
+                               uint64_t *proof_xy);
 
 /* Batch verification of proofs of SEVERAL setups with one combined MSM: a block or a mempool holds many shapes (32 .. 128 outputs,
  * norm-linear and inner-product argument, typed-reciprocal and binary proofs), each group below one handle of this context.  The job

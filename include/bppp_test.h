@@ -29,6 +29,13 @@ int bppp_test_mulmod_rate(bppp_ctx *ctx, int iters, double *mulmods_per_sec);
 /* Terms of the one MSM the last bppp_rp_verify_mixed* call on this context ran (0 after an empty job): a test sees that the shared
  * bases of setups from one point stream were merged. */
 int bppp_test_last_mixed_msm_terms(bppp_ctx *ctx, uint64_t *terms);
+/* What the last verification on this handle ran (bppp_rp_verify_batch*, _shard_device, _each*, and its group's share of
+ * bppp_rp_verify_mixed*): combined MSMs (the accept check and every bisection step) and per-proof passes.  A test sees the cost of a
+ * culprit search without timing it. */
+int bppp_test_rp_last_verify_counts(bppp_rp *rp, uint64_t *combined_msms, uint64_t *each_passes);
+/* Proofs per chunk of the per-proof pass on this handle (0 = from the row budget, the default): a test crosses a chunk boundary
+ * with a small batch. */
+int bppp_test_rp_set_each_chunk(bppp_rp *rp, size_t proofs);
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
