@@ -31,6 +31,8 @@ SYMBOLS = [
     "bppp_basis_create", "bppp_basis_create_device", "bppp_basis_destroy", "bppp_basis_info", "bppp_msm_basis", "bppp_basis_enable_comb",
     "bppp_rp_create", "bppp_rp_create_binary", "bppp_rp_destroy", "bppp_rp_info", "bppp_rp_set_option", "bppp_rp_shape_of", "bppp_rp_digits", "bppp_hash_to_scalar", "bppp_rp_verify_batch", "bppp_rp_verify_batch_device", "bppp_rp_verify_shard_device", "bppp_rp_prove_batch",
     "bppp_rp_verify_mixed", "bppp_rp_verify_mixed_device", "bppp_rp_verify_each", "bppp_rp_verify_each_device",
+    "bppp_rp_public_count", "bppp_rp_verify_batch_pub", "bppp_rp_verify_batch_pub_device", "bppp_rp_verify_shard_pub_device", "bppp_rp_verify_each_pub",
+    "bppp_rp_verify_each_pub_device", "bppp_rp_prove_batch_pub",
 ]
 
 
@@ -137,6 +139,13 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_verify_mixed_device.argtypes = [vp, sz, C.c_uint64, vp, C.POINTER(i), vp, vp]
     lib.bppp_rp_verify_each.argtypes = [vp, sz, vp, vp, vp, vp]
     lib.bppp_rp_verify_each_device.argtypes = [vp, sz, vp, vp, vp, vp]
+    lib.bppp_rp_public_count.argtypes = [vp, C.POINTER(sz)]
+    lib.bppp_rp_verify_batch_pub.argtypes = [vp, sz, vp, vp, vp, vp, C.POINTER(i), vp, vp, vp]
+    lib.bppp_rp_verify_batch_pub_device.argtypes = [vp, sz, vp, vp, vp, vp, C.POINTER(i), vp, vp, vp]
+    lib.bppp_rp_verify_shard_pub_device.argtypes = [vp, sz, C.c_uint64, vp, vp, vp, vp, C.POINTER(i), vp, vp, vp]
+    lib.bppp_rp_verify_each_pub.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    lib.bppp_rp_verify_each_pub_device.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    lib.bppp_rp_prove_batch_pub.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp, vp]
     lib.bppp_profile_enable.argtypes = [vp, i]
     lib.bppp_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), i]
     return lib

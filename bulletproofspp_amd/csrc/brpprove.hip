@@ -18,7 +18,7 @@ namespace bppp {
 // commitments of all proofs as batched MSMs over the registered basis [g | h0 h1 | G], the argument through csrc/nlb.hip — the
 // O(nrmLen) field algebra of a proof and its transcript hashing on the host cores (one proof per thread slice).
 int prove_batch_binary(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *blinds, const uint8_t *rand_prefix, size_t prefix_len,
-                              uint8_t *coms_files, uint8_t *proof_files) {
+                              uint8_t *coms_files, uint8_t *proof_files, const uint64_t *pub) {
   bppp_ctx *ctx = rp->ctx;
   hipSetDevice(ctx->device);
   hipStream_t stream = ctx->stream;
@@ -60,7 +60,7 @@ int prove_batch_binary(bppp_rp *rp, size_t batch, const uint64_t *amounts, const
       BState &p = ps[b];
       p.tr.rnd = Rnd{rand_prefix + b * prefix_len, prefix_len, 0};
       p.v.resize(nr); p.bl.resize(nr); p.ds.clear();
-      U256 vsum = st.net_public;
+      U256 vsum = pub ? U256::load(pub + 4 * b) : st.net_public;
       bool ok = true;
       for (size_t i = 0; i < nr && ok; i++) {
         const RangeData &rd = st.rds[i];
@@ -110,7 +110,7 @@ int prove_batch_binary(bppp_rp *rp, size_t batch, const uint64_t *amounts, const
       // makePublicConsts (:73-98)
       std::vector<U256> x2s(nr);
       { U256 c = xx; for (size_t j = 0; j < nr; j++) { x2s[j] = c; c = fm(c, xx); } }
-      U256 z = st.conserve ? fneg(fm(p.x, st.net_public)) : U256::zero();
+      U256 z = st.conserve ? fneg(fm(p.x, pub ? U256::load(pub + 4 * b) : st.net_public)) : U256::zero();
       for (size_t j = 0; j < nr; j++) if (!st.rds[j].assumed) z = fa(z, fm(bppp_rps::s_mod_n(st.rds[j].lo), x2s[j]));
       U256 sc = fneg(fdbl(z));
       p.pub_nrm.resize(nlive);
@@ -227,7 +227,7 @@ int prove_batch_binary(bppp_rp *rp, size_t batch, const uint64_t *amounts, const
 // The same proofs with proveBRPM's field algebra, randomness and transcript on the device (csrc/brpprove_dev.hip): the host checks the
 // witness (witnessBRP, Binary.hs:158-166), extracts the binary digits of the plain amounts (makeDigits :56-69) and writes the files.
 int prove_batch_binary_dev(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *blinds, const uint8_t *rand_prefix, size_t prefix_len,
-                                  uint8_t *coms_files, uint8_t *proof_files, size_t index_base) {
+                                  uint8_t *coms_files, uint8_t *proof_files, size_t index_base, const uint64_t *pub) {
   bppp_ctx *ctx = rp->ctx;
   hipSetDevice(ctx->device);
   const Setup &st = rp->st;
@@ -253,7 +253,7 @@ int prove_batch_binary_dev(bppp_rp *rp, size_t batch, const uint64_t *amounts, c
   rp_parallel(B, [&](size_t lo, size_t hi) {
     std::vector<uint32_t> dg;
     for (size_t b = lo; b < hi; b++) {
-      U256 vsum = st.net_public;
+      U256 vsum = pub ? U256::load(pub + 4 * b) : st.net_public;
       const char *err = nullptr;
       size_t p = 0;
       for (size_t i = 0; i < nr && !err; i++) {
@@ -277,7 +277,7 @@ int prove_batch_binary_dev(bppp_rp *rp, size_t batch, const uint64_t *amounts, c
   if (failed >= 0) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: proof " + std::to_string(index_base + (size_t)failed) + ": " + errs[failed]);
   lap("witness, digits (host)");
   std::vector<uint64_t> c_d(B * 8), c_bl(B * 8), resp(B * (k ? k : 1) * 16), wn(B * st.fn * 4 + 4), wl(B * st.fl * 4 + 4);
-  BrpHostInputs in{B, h_in_sc, bits, rand_prefix, prefix_len};
+  BrpHostInputs in{B, h_in_sc, bits, rand_prefix, prefix_len, pub};
   BrpOutputs out{h_in_pt, c_d.data(), c_bl.data(), resp.data(), wn.data(), wl.data()};
   { int rc = brp_device_prove(rp, in, out); if (rc) return rc; }
   lap("phases + argument (device)");

@@ -159,6 +159,8 @@ int brp_device_prove(bppp_rp *rp, const BrpHostInputs &in, BrpOutputs &out) {
     cscratch = cv.take<uint32_t>(comb_rows_scratch_bytes(B) / 4 + 16);
     if (!pass) { int rc = rpp_ensure_pwork(rp, cv.off); if (rc) return rc; }
   }
+  const uint32_t *d_pub = nullptr;                 // per-proof net_public (bppp_rp_prove_batch_pub)
+  if (in.pub) { int rc_ = rp_upload_public(rp, in.pub, B * 4, &d_pub); if (rc_) return rc_; }
   BPPP_HIP(ctx, hipMemcpyAsync(in_sc, in.in_sc, B * nr * 96, hipMemcpyHostToDevice, st));
   if (nlive) BPPP_HIP(ctx, hipMemcpyAsync(bits, in.bits, B * nlive, hipMemcpyHostToDevice, st));
   if (in.prefix_len) BPPP_HIP(ctx, hipMemcpyAsync(prefix, in.prefix, B * in.prefix_len, hipMemcpyHostToDevice, st));
@@ -186,7 +188,7 @@ int brp_device_prove(bppp_rp *rp, const BrpHostInputs &in, BrpOutputs &out) {
   BPPP_HIP(ctx, hipGetLastError());
   rc = comb(row_bl, c_bl, COMB_ROWS_DENSE); if (rc) return rc;
   rc = tr.call(c_bl, 1); if (rc) return rc;
-  rc = brp_public_device(rp, B, ch, a_q, p_sp, p_norm, p_cs, p_init); if (rc) return rc;
+  rc = brp_public_device(rp, B, ch, a_q, p_sp, p_norm, p_cs, p_init, d_pub); if (rc) return rc;
   { const uint64_t n = (uint64_t)B * T;
     k_brpp_combine<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(D, (uint32_t)B, (uint32_t)nd, rnd, bits, aux, in_sc, ch, p_sp, p_norm, p_init, a_s, a_lx, a_nx); }
   BPPP_HIP(ctx, hipGetLastError());

@@ -287,12 +287,13 @@ __global__ void __launch_bounds__(128) k_rp_hash(RpDims D, uint32_t batch, uint3
 // (q, x, r, t) = ch slots 0, 1, 2, 6:
 //   makePublicConsts (:73-98): bss_i = x^(2(j+1)) b_i over the positions of the ranges that are not assumed; p_i = bss_i q0^-(i+1) - 1/2;
 //                              sc = -2 (net' + sum_j min_j x^(2(j+1))) + sum_i q0^(i+1) p_i^2,  net' = -x netPublic when conserving
+//   (net_stride 8: net_public is [batch] values, one per proof — bppp_rp_*_pub; 0: the setup's one value)
 //   the argument's public opening (:215-219): scalar t^2 sc, norm vector t p_i (zero beyond the live positions), linear weights
 //   [0, r t] (setupBRP's psv, :151-152), and the initCom scalars of TranscriptBRP (:107-110) in commitment order blCom : dCom : nComs =
 //   1, t, 2 t^2 inputCoeffs (:127-129).  q0 = q^2 (NL) or -q^2 (IP) as qPowers' has it.
 __global__ void __launch_bounds__(256) k_brp_public(BrpDims D, uint32_t batch, const uint32_t *__restrict__ pos_range, const uint32_t *__restrict__ pos_coeff,
                                                    const uint32_t *__restrict__ range_min, const uint32_t *__restrict__ range_flags, const uint32_t *__restrict__ net_public,
-                                                   const uint32_t *__restrict__ ch, uint32_t *__restrict__ out_q, uint32_t *__restrict__ out_sp,
+                                                   uint32_t net_stride, const uint32_t *__restrict__ ch, uint32_t *__restrict__ out_q, uint32_t *__restrict__ out_sp,
                                                    uint32_t *__restrict__ out_norm, uint32_t *__restrict__ out_cs, uint32_t *__restrict__ out_init) {
   extern __shared__ uint32_t lds[];               // [nr] x^(2(j+1)), then [blockDim.x] partial sums
   uint32_t *x2s = lds, *part = lds + (size_t)D.nr * 8;
@@ -339,7 +340,7 @@ __global__ void __launch_bounds__(256) k_brp_public(BrpDims D, uint32_t batch, c
   fe z = fe_zero();
   for (uint32_t j = l; j < D.nr; j += NT)
     if (!(range_flags[j] & 2u)) z = fe_add<1>(z, fe_mul<1>(fe_load(range_min + (size_t)j * 8), x2(j)));
-  if (l == 0 && D.conserve) z = fe_sub<1>(z, fe_mul<1>(x, fe_load(net_public)));
+  if (l == 0 && D.conserve) z = fe_sub<1>(z, fe_mul<1>(x, fe_load(net_public + (size_t)b * net_stride)));
   acc = fe_sub<1>(acc, fe_dbl<1>(z));
   for (int k = 0; k < 8; k++) part[l * 8 + k] = acc.v[k];
   __syncthreads();
@@ -476,7 +477,8 @@ static int brp_build_tables(bppp_rp *rp) {
   return BPPP_OK;
 }
 namespace bppp {
-int brp_public_device(bppp_rp *rp, size_t batch, const uint32_t *ch, uint32_t *q, uint32_t *sp, uint32_t *pub_norm, uint32_t *pub_lin_c, uint32_t *init_sc) {
+int brp_public_device(bppp_rp *rp, size_t batch, const uint32_t *ch, uint32_t *q, uint32_t *sp, uint32_t *pub_norm, uint32_t *pub_lin_c, uint32_t *init_sc,
+                      const uint32_t *d_net) {
   bppp_ctx *ctx = rp->ctx;
   const bppp_brp_tabs *t = rp->btabs;
   // lanes per proof: a lane pays ~60 multiplications for its first powers of q0 and q0^-1 whatever its share of the positions, and 1024 proofs at one
@@ -487,7 +489,8 @@ int brp_public_device(bppp_rp *rp, size_t batch, const uint32_t *ch, uint32_t *q
   while (nt < 256 && (size_t)t->D.nlen >= (size_t)nt * 16 && batch * (nt / 64) < 2048) nt <<= 1;
   const size_t lds = ((size_t)t->D.nr + nt) * 32;
   if (lds > 64 * 1024) BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_brp_public, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  k_brp_public<<<dim3((unsigned)batch), dim3(nt), lds, ctx->stream>>>(t->D, (uint32_t)batch, t->pos_range, t->pos_coeff, t->range_min, t->range_flags, t->net_public, ch, q, sp,
+  k_brp_public<<<dim3((unsigned)batch), dim3(nt), lds, ctx->stream>>>(t->D, (uint32_t)batch, t->pos_range, t->pos_coeff, t->range_min, t->range_flags,
+                                                                     d_net ? d_net : t->net_public, d_net ? 8u : 0u, ch, q, sp,
                                                                      pub_norm, pub_lin_c, init_sc);
   BPPP_HIP(ctx, hipGetLastError());
   return BPPP_OK;
@@ -519,6 +522,7 @@ void bppp_rp_destroy(bppp_rp *rp) {
   if (rp->work) hipFree(rp->work);
   if (rp->stage) hipFree(rp->stage);
   if (rp->ework) hipFree(rp->ework);
+  if (rp->d_pub) hipFree(rp->d_pub);
   if (rp->hflag) hipHostFree(rp->hflag);
   if (rp->hstage) hipHostFree(rp->hstage);
   for (auto &e : rp->slice_ev) if (e) hipEventDestroy(e);
@@ -813,11 +817,23 @@ int bppp_rp_verify_batch_device(bppp_rp *rp, size_t batch, const void *d_coms_fi
 }
 
 static int rp_verify_shard_run(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const uint8_t seed[32],
-                               int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy);
+                               int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy, const uint32_t *d_pub);
 int bppp_rp_verify_shard_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const uint8_t seed[32],
                                 int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
+  return bppp_rp_verify_shard_pub_device(rp, batch, index_offset, d_coms_files, d_proof_files, nullptr, seed, accept, proof_status, challenges_out, combined_xy);
+}
+int bppp_rp_verify_shard_pub_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const void *d_public_amounts,
+                                    const uint8_t seed[32], int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
   if (!rp || !accept) return BPPP_ERR_ARG;
-  const int rc = rp_verify_shard_run(rp, batch, index_offset, d_coms_files, d_proof_files, seed, accept, proof_status, challenges_out, combined_xy);
+  const uint32_t *d_pub = nullptr;
+  int rc = BPPP_OK;
+  if (d_public_amounts && batch) {
+    if (ctx_closed(rp->ctx)) return BPPP_ERR_ARG;
+    *accept = 0;
+    hipSetDevice(rp->ctx->device);
+    if ((rc = rp_stage_public(rp, batch, nullptr, d_public_amounts, &d_pub))) return rc;
+  }
+  rc = rp_verify_shard_run(rp, batch, index_offset, d_coms_files, d_proof_files, seed, accept, proof_status, challenges_out, combined_xy, d_pub);
   // A failed call may leave work queued on either stream that still reads the caller's buffers (the sliced uploads from host files run on
   // the context's second stream): nothing of this call is in flight once it has returned, whatever the outcome.
   if (rc && rp->ctx && !ctx_closed(rp->ctx)) {
@@ -828,7 +844,7 @@ int bppp_rp_verify_shard_device(bppp_rp *rp, size_t batch, uint64_t index_offset
   return rc;
 }
 static int rp_verify_shard_run(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const uint8_t seed[32],
-                               int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
+                               int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy, const uint32_t *d_pub) {
   bppp_ctx *ctx = rp->ctx;
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
   *accept = 0;
@@ -837,7 +853,7 @@ static int rp_verify_shard_run(bppp_rp *rp, size_t batch, uint64_t index_offset,
   if (!batch) { *accept = 1; return BPPP_OK; }
   if (!d_coms_files || !d_proof_files || !seed || batch >= (1u << 22)) return fail(ctx, BPPP_ERR_ARG, "rp_verify_batch: bad arguments");
   RpVerifyArrays A;
-  int rc = rp_verify_prepare(rp, batch, index_offset, d_coms_files, d_proof_files, seed, A);
+  int rc = rp_verify_prepare(rp, batch, index_offset, d_coms_files, d_proof_files, seed, A, d_pub);
   if (rc) return rc;
   hipStream_t st = ctx->stream;
   const bppp_rps::Setup &S = rp->st;
@@ -879,7 +895,7 @@ namespace bppp {
 // decodeProof, the transcript hashing, the public scalars and the weights rho of one batch: everything of the verification but the
 // argument's combination (see rp_internal.hpp)
 int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const uint8_t seed[32],
-                      RpVerifyArrays &A) {
+                      RpVerifyArrays &A, const uint32_t *d_pub) {
   bppp_ctx *ctx = rp->ctx;
   hipSetDevice(ctx->device);
   hipStream_t st = ctx->stream;
@@ -976,7 +992,7 @@ int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const vo
     all(0);
     lap("host oracle, part 0");
     BPPP_HIP(ctx, hipMemcpyAsync(ch, hch, B * 7 * 32, hipMemcpyHostToDevice, st));
-    int rc0 = S.kind ? brp_public_device(rp, B, ch, q, sp, pub_norm, pub_lin_c, init_sc) : bppp_trrp_public_device(rp->tabs, B, ch, q, sp, pub_norm, pub_lin_c, init_sc);
+    int rc0 = S.kind ? brp_public_device(rp, B, ch, q, sp, pub_norm, pub_lin_c, init_sc, d_pub) : trrp_public_run(rp->tabs, B, ch, q, sp, pub_norm, pub_lin_c, init_sc, d_pub);
     if (rc0) return rc0;
     lap("launch of the scalars");
     all(1);
@@ -1007,7 +1023,7 @@ int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const vo
       BPPP_HIP(ctx, hipEventRecord(ctx->aux_join, aux));
     }
     BPPP_HIP(ctx, hipGetLastError());
-    int rc0 = S.kind ? brp_public_device(rp, B, ch, q, sp, pub_norm, pub_lin_c, init_sc) : bppp_trrp_public_device(rp->tabs, B, ch, q, sp, pub_norm, pub_lin_c, init_sc);
+    int rc0 = S.kind ? brp_public_device(rp, B, ch, q, sp, pub_norm, pub_lin_c, init_sc, d_pub) : trrp_public_run(rp->tabs, B, ch, q, sp, pub_norm, pub_lin_c, init_sc, d_pub);
     if (fork) BPPP_HIP(ctx, hipStreamWaitEvent(st, ctx->aux_join, 0));      // (joined even when the launch above failed: the second stream must not outlive the call's buffers)
     if (rc0) { hipStreamSynchronize(st); return rc0; }
   }
@@ -1085,21 +1101,95 @@ int rp_ensure_stage(bppp_rp *rp, size_t batch) {
   return BPPP_OK;
 }
 
+size_t rp_public_count(const bppp_rp *rp) {
+  if (rp->st.kind == 1) return rp->st.conserve ? 1 : 0;
+  return rp->st.has_types ? rp->st.pubs.size() : 0;
+}
+
+int rp_public_canon(bppp_rp *rp, size_t batch, const uint64_t *in, std::vector<uint64_t> &out) {
+  const size_t npub = rp_public_count(rp);
+  out.clear();
+  if (!batch) return BPPP_OK;
+  if (!npub) return fail(rp->ctx, BPPP_ERR_ARG, "rp_*_pub: this handle has no public amounts (untyped, or binary without conservation)");
+  out.resize(batch * npub * 4);
+  for (size_t b = 0; b < batch; b++)
+    for (size_t j = 0; j < npub; j++) {
+      const uint64_t *v = in + (b * npub + j) * 4;
+      if (rp->st.kind == 1) { bppp_rps::s_mod_n(U256::load(v)).store(&out[(b * npub + j) * 4]); continue; }      // as bppp_rp_create_binary's net_public
+      if (!bppp_host::scalars_canonical(v, 1))
+        return fail(rp->ctx, BPPP_ERR_ARG, "rp_*_pub: proof " + std::to_string(b) + ": public amount " + std::to_string(j) + " is not canonical");
+      memcpy(&out[(b * npub + j) * 4], v, 32);
+    }
+  return BPPP_OK;
+}
+
+int rp_upload_public(bppp_rp *rp, const uint64_t *canon, size_t words, const uint32_t **d_out) {
+  bppp_ctx *ctx = rp->ctx;
+  const size_t bytes = words * 8;
+  if (bytes > rp->d_pub_bytes) {
+    BPPP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rp->d_pub) BPPP_HIP(ctx, hipFree(rp->d_pub));
+    rp->d_pub = nullptr; rp->d_pub_bytes = 0;
+    BPPP_HIP(ctx, hipMalloc(&rp->d_pub, bytes));
+    rp->d_pub_bytes = bytes;
+  }
+  if (bytes) {
+    BPPP_HIP(ctx, hipMemcpyAsync(rp->d_pub, canon, bytes, hipMemcpyHostToDevice, ctx->stream));
+    BPPP_HIP(ctx, hipStreamSynchronize(ctx->stream));       // `canon` is the caller's
+  }
+  *d_out = rp->d_pub;
+  return BPPP_OK;
+}
+
+int rp_stage_public(bppp_rp *rp, size_t batch, const uint64_t *h_in, const void *d_in, const uint32_t **d_out) {
+  std::vector<uint64_t> raw, canon;
+  if (d_in) {                                  // device amounts come down first: 32 bytes per amount, checked on the host as the creation arguments are
+    const size_t npub = rp_public_count(rp);
+    raw.resize(batch * npub * 4);
+    if (npub) {
+      BPPP_HIP(rp->ctx, hipMemcpyAsync(raw.data(), d_in, raw.size() * 8, hipMemcpyDeviceToHost, rp->ctx->stream));
+      BPPP_HIP(rp->ctx, hipStreamSynchronize(rp->ctx->stream));
+    }
+    h_in = raw.data();
+  }
+  const int rc = rp_public_canon(rp, batch, h_in, canon);
+  return rc ? rc : rp_upload_public(rp, canon.data(), canon.size(), d_out);
+}
+
 extern "C" {
+
+int bppp_rp_public_count(const bppp_rp *rp, size_t *n) {
+  if (!rp || !n) return BPPP_ERR_ARG;
+  *n = rp_public_count(rp);
+  return BPPP_OK;
+}
 
 int bppp_rp_verify_batch(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint8_t *proof_files, const uint8_t seed[32], int *accept,
                          uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
+  return bppp_rp_verify_batch_pub(rp, batch, coms_files, proof_files, nullptr, seed, accept, proof_status, challenges_out, combined_xy);
+}
+
+int bppp_rp_verify_batch_pub_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_proof_files, const void *d_public_amounts, const uint8_t seed[32],
+                                    int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
+  return bppp_rp_verify_shard_pub_device(rp, batch, 0, d_coms_files, d_proof_files, d_public_amounts, seed, accept, proof_status, challenges_out, combined_xy);
+}
+
+int bppp_rp_verify_batch_pub(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint8_t *proof_files, const uint64_t *public_amounts, const uint8_t seed[32],
+                             int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
   if (!rp || !accept) return BPPP_ERR_ARG;
   bppp_ctx *ctx = rp->ctx;
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
   if (!batch) { *accept = 1; return BPPP_OK; }
   if (!coms_files || !proof_files) return fail(ctx, BPPP_ERR_ARG, "rp_verify_batch: null input");
   hipSetDevice(ctx->device);
+  const uint32_t *d_pub = nullptr;
+  if (public_amounts) { *accept = 0; int rc0 = rp_stage_public(rp, batch, public_amounts, nullptr, &d_pub); if (rc0) return rc0; }
   { int rc0 = rp_ensure_stage(rp, batch); if (rc0) return rc0; }
   void *stage = rp->stage;
   const size_t cbp = (batch * (size_t)rp->D.coms_bytes + 255) & ~(size_t)255;
   rp->host_coms = coms_files; rp->host_proofs = proof_files;          // uploaded in slices by the decode stage of the call below
-  int rc = bppp_rp_verify_batch_device(rp, batch, stage, (char *)stage + cbp, seed, accept, proof_status, challenges_out, combined_xy);
+  int rc = rp_verify_shard_run(rp, batch, 0, stage, (char *)stage + cbp, seed, accept, proof_status, challenges_out, combined_xy, d_pub);
+  if (rc) { hipStreamSynchronize(ctx->stream); if (ctx->aux_stream) hipStreamSynchronize(ctx->aux_stream); (void)hipGetLastError(); }
   rp->host_coms = rp->host_proofs = nullptr;
   hipStreamSynchronize(ctx->stream);
   if (ctx->aux_stream) hipStreamSynchronize(ctx->aux_stream);     // the sliced uploads read the caller's files from there

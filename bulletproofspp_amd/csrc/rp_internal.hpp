@@ -73,6 +73,10 @@ int bppp_trrp_create(bppp_ctx *ctx, int flavour, int has_types, size_t nlen, siz
 void bppp_trrp_destroy(bppp_trrp *t);
 int bppp_trrp_public_device(bppp_trrp *t, size_t batch, const void *d_challenges, void *d_q, void *d_sp, void *d_pub_norm, void *d_pub_lin_c, void *d_init_scalars);
 }
+namespace bppp {
+int trrp_public_run(bppp_trrp *t, size_t batch, const void *d_challenges, void *d_q, void *d_sp, void *d_pub_norm, void *d_pub_lin_c, void *d_init_scalars,
+                    const void *d_pub_amounts);      // csrc/trrp.hip: d_pub_amounts NULL or [batch][npub] canonical scalars
+}  // namespace bppp
 
 
 namespace bppp { struct CombTable; void comb_destroy(CombTable *); }
@@ -141,7 +145,20 @@ struct bppp_rp {
   void *ework = nullptr; size_t ework_bytes = 0;
   size_t each_chunk = 0;
   uint64_t n_combined = 0, n_each = 0;
+  // per-proof public amounts of the *_pub entry points (bppp_rp_public_count per proof): grow-only device copy of one call's canonical
+  // scalars, [batch][public_count][8] words
+  uint32_t *d_pub = nullptr; size_t d_pub_bytes = 0;
 };
+
+// public amounts per proof of the *_pub entry points: npub of a typed handle with types, 1 of a conserved binary handle, else 0
+size_t rp_public_count(const bppp_rp *rp);
+// the *_pub entry points' amounts of `batch` proofs, as the caller passes them (the creation argument's encoding), checked and made canonical
+// scalars [batch][public_count][4] (binary: net_public mod n); BPPP_ERR_ARG names the first bad proof
+int rp_public_canon(bppp_rp *rp, size_t batch, const uint64_t *in, std::vector<uint64_t> &out);
+// canonical amounts (host) -> rp->d_pub on the handle's stream; returns with the copy done
+int rp_upload_public(bppp_rp *rp, const uint64_t *canon, size_t words, const uint32_t **d_out);
+// both for a verifier entry point: the amounts from the host (h_in) or from HBM (d_in, downloaded first) into rp->d_pub
+int rp_stage_public(bppp_rp *rp, size_t batch, const uint64_t *h_in, const void *d_in, const uint32_t **d_out);
 
 int rp_ensure_twin(bppp_rp *rp);      // csrc/rp.hip
 int rp_ensure_stage(bppp_rp *rp, size_t batch);   // csrc/rp.hip: rp->stage holds `batch` files (coms, then proofs 256-byte aligned)
@@ -157,7 +174,9 @@ struct RpVerifyArrays {
 // proofs at job positions [index_offset, index_offset + batch): everything of the verification but the argument's combination.  Queued
 // on the context's stream; bad[b] marks a proof that did not decode and rp->hflag[0] receives "some proof did not" (read it once the
 // stream has drained).  The arrays stay valid until the handle's next verification.
-int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms, const void *d_proofs, const uint8_t seed[32], RpVerifyArrays &A);
+// d_pub: NULL (the handle's public amounts) or [batch][public_count] canonical scalars in HBM (rp_upload_public)
+int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms, const void *d_proofs, const uint8_t seed[32], RpVerifyArrays &A,
+                      const uint32_t *d_pub = nullptr);
 // verifyBPM's combination of proofs [lo, lo + n) of a prepared batch: one MSM, returns with the stream drained
 int rp_verify_combine(bppp_rp *rp, const RpVerifyArrays &A, size_t lo, size_t n, uint64_t out_xy[8]);
 // the culprits of a rejected batch by bisection: a VALID proof_status[b] whose combination fails becomes INVALID.  known_bad: the

@@ -85,8 +85,9 @@ void rpp_host_oracle(const std::string &tag, std::vector<std::string> &groups, s
 }
 }  // namespace bppp
 namespace {
-// witnessTRRP (TypedReciprocal.hs:372-389) + makePhase1s (:133-161) + getDsMs (:74-80): fills d, mi, pv, ms_shared
-bool make_witness(const Setup &st, PState &ps, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds) {
+// witnessTRRP (TypedReciprocal.hs:372-389) + makePhase1s (:133-161) + getDsMs (:74-80): fills d, mi, pv, ms_shared.  pub: NULL (the
+// setup's public amounts) or this proof's [npub][4] canonical amounts (bppp_rp_prove_batch_pub)
+bool make_witness(const Setup &st, PState &ps, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint64_t *pub) {
   const size_t nr = st.rds.size();
   ps.v.resize(nr); ps.ty.resize(nr); ps.bl.resize(nr);
   std::vector<U256> amt(nr);
@@ -101,7 +102,7 @@ bool make_witness(const Setup &st, PState &ps, const uint64_t *amounts, const ui
       for (auto &kv : sums) if (kv.first == ty) { kv.second = neg ? fs(kv.second, val) : fa(kv.second, val); return; }
       sums.emplace_back(ty, neg ? fneg(val) : val);
     };
-    for (const auto &pv : st.pubs) add(pv.type, pv.amount, pv.is_output);
+    for (size_t j = 0; j < st.pubs.size(); j++) add(st.pubs[j].type, pub ? U256::load(pub + 4 * j) : st.pubs[j].amount, st.pubs[j].is_output);
     for (size_t i = 0; i < nr; i++) add(ps.ty[i], ps.v[i], st.rds[i].output);
     for (auto &kv : sums) if (!kv.second.is_zero()) { ps.err = "amounts of some type do not balance"; return false; }
   }
@@ -311,8 +312,8 @@ RPW blind_blinding_term(const std::vector<U256> &bls_lin, const std::vector<U256
   return w;
 }
 
-// makePublicConsts (TypedReciprocal.hs:246-274): returns sc and the norm vector
-void make_public_consts(const Setup &st, const PState &ps, U256 &sc, std::vector<U256> &nrm) {
+// makePublicConsts (TypedReciprocal.hs:246-274): returns sc and the norm vector.  pub as for make_witness
+void make_public_consts(const Setup &st, const PState &ps, U256 &sc, std::vector<U256> &nrm, const uint64_t *pub) {
   const U256 t2 = fm(ps.t, ps.t), t3 = fm(t2, ps.t), t4 = fm(t2, t2), t5 = fm(t4, ps.t), two_t5 = fdbl(t5);
   const U256 xx = fm(ps.x, ps.x);
   U256 z = U256::zero();
@@ -324,7 +325,10 @@ void make_public_consts(const Setup &st, const PState &ps, U256 &sc, std::vector
     for (size_t j = 0; j < pr.size(); j++) pr[j] = fa(ps.e, st.pubs[j].type);
     batch_inv(pr);
     U256 sum = U256::zero();
-    for (size_t j = 0; j < pr.size(); j++) { const U256 rv = fm(pr[j], st.pubs[j].amount); sum = st.pubs[j].is_output ? fs(sum, rv) : fa(sum, rv); }
+    for (size_t j = 0; j < pr.size(); j++) {
+      const U256 rv = fm(pr[j], pub ? U256::load(pub + 4 * j) : st.pubs[j].amount);
+      sum = st.pubs[j].is_output ? fs(sum, rv) : fa(sum, rv);
+    }
     z = fs(z, fm(fm(two_t5, ps.x), sum));
   }
   nrm.resize(st.nlen);
@@ -437,7 +441,7 @@ int rp_ensure_comb(bppp_rp *rp) {
 }
 
 static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint8_t *rand_prefix,
-                            size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files, size_t index_base);
+                            size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files, size_t index_base, const uint64_t *pub);
 
 // encodeProof' (src/RangeProof.hs:60-66): commitments file = the input commitments; proof file = final witness scalars (norm, linear),
 // then blCom, rCom, dmCom, mCom and the responses
@@ -465,16 +469,33 @@ static void encode_batch(const bppp_rp *rp, size_t B, const RppOutputs &o, uint8
 
 
 static int prove_batch_one(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint8_t *rand_prefix,
-                           size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files, size_t index_base);
+                           size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files, size_t index_base, const uint64_t *pub);
+static int prove_batch_run(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint64_t *pub,
+                           const uint8_t *rand_prefix, size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files);
 
 extern "C" int bppp_rp_prove_batch(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint8_t *rand_prefix,
                                    size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files) {
+  return bppp_rp_prove_batch_pub(rp, batch, amounts, types, blinds, nullptr, rand_prefix, prefix_len, coms_files, proof_files);
+}
+
+extern "C" int bppp_rp_prove_batch_pub(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint64_t *public_amounts,
+                                       const uint8_t *rand_prefix, size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files) {
   if (!rp) return BPPP_ERR_ARG;
   bppp_ctx *ctx = rp->ctx;
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
   if (!batch) return BPPP_OK;
   if (!amounts || (!types && rp->st.kind == 0) || !blinds || (prefix_len && !rand_prefix) || !coms_files || !proof_files || batch >= (1u << 20) || prefix_len > 4096)
     return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: bad arguments");
+  std::vector<uint64_t> pub;                    // per-proof public amounts as canonical scalars: what a handle created with them holds
+  if (public_amounts) { int rc = rp_public_canon(rp, batch, public_amounts, pub); if (rc) return rc; }
+  return prove_batch_run(rp, batch, amounts, types, blinds, public_amounts ? pub.data() : nullptr, rand_prefix, prefix_len, coms_files, proof_files);
+}
+
+static int prove_batch_run(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint64_t *pub,
+                           const uint8_t *rand_prefix, size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files) {
+  bppp_ctx *ctx = rp->ctx;
+  const size_t npub = rp_public_count(rp);
+  auto pub_at = [&](size_t b0) -> const uint64_t * { return pub ? pub + 4 * npub * b0 : nullptr; };     // the amounts of the twin's half-batch
   const size_t comb_min = rp->opt.comb_min;     // default 1024: the table costs ~0.3 s and tens of GB once: worth it for a handle that proves large batches
   // ... or one that has proved that many proofs in smaller batches: with the table in place every batch size is faster (one 64by64 proof:
   // 12 ms against 22 ms; 256: 22 against 48)
@@ -489,7 +510,7 @@ extern "C" int bppp_rp_prove_batch(bppp_rp *rp, size_t batch, const uint64_t *am
       // two half-batches in flight (as below for the typed-reciprocal proofs): the transcript hashing, the phase and the round kernels of one half —
       // ~14 ms per 1024 proofs of mostly one-lane-per-proof chains — run under the comb additions of the other
       if (batch < rp->opt.split_min_binary || batch < 2 || rp->is_twin || rp->opt.no_split)
-        return prove_batch_binary_dev(rp, batch, amounts, blinds, rand_prefix, prefix_len, coms_files, proof_files);
+        return prove_batch_binary_dev(rp, batch, amounts, blinds, rand_prefix, prefix_len, coms_files, proof_files, 0, pub);
       { int rc = rp_ensure_twin(rp); if (rc) return rc; }
       if (!rp->twin->comb) rp->twin->comb = rp->comb;              // not owned by the twin
       rp->twin->opt = rp->opt;
@@ -497,26 +518,26 @@ extern "C" int bppp_rp_prove_batch(bppp_rp *rp, size_t batch, const uint64_t *am
       int rc1 = BPPP_OK;
       std::thread second([&] {
         rc1 = prove_batch_binary_dev(rp->twin, B1, amounts + 4 * nrb * B0, blinds + 4 * nrb * B0, rand_prefix ? rand_prefix + prefix_len * B0 : nullptr, prefix_len,
-                                     coms_files + (size_t)rp->D.coms_bytes * B0, proof_files + (size_t)rp->D.proof_bytes * B0, B0);
+                                     coms_files + (size_t)rp->D.coms_bytes * B0, proof_files + (size_t)rp->D.proof_bytes * B0, B0, pub_at(B0));
       });
-      const int rc0 = prove_batch_binary_dev(rp, B0, amounts, blinds, rand_prefix, prefix_len, coms_files, proof_files);
+      const int rc0 = prove_batch_binary_dev(rp, B0, amounts, blinds, rand_prefix, prefix_len, coms_files, proof_files, 0, pub);
       second.join();
       if (rc0) return rc0;
       if (rc1) return fail(ctx, rc1, bppp_last_error(rp->twin_ctx));
       return BPPP_OK;
     }
-    return prove_batch_binary(rp, batch, amounts, blinds, rand_prefix, prefix_len, coms_files, proof_files);
+    return prove_batch_binary(rp, batch, amounts, blinds, rand_prefix, prefix_len, coms_files, proof_files, pub);
   }
   // inner-product flavour without a table: the range-proof phases with their field algebra on the host cores, then the lockstep argument of
   // ip_argument_lockstep (no basis change, no point fold: every commitment an MSM over the registered original basis)
   if (rp->st.flavour != 0 && (!rp->comb || rp->opt.fold_points))
-    return prove_batch_host(rp, batch, amounts, types, blinds, rand_prefix, prefix_len, coms_files, proof_files, 0);
+    return prove_batch_host(rp, batch, amounts, types, blinds, rand_prefix, prefix_len, coms_files, proof_files, 0, pub);
   // A large batch runs as TWO half-batches in flight, the second on a twin handle with its own context (stream, workspaces, host
   // thread): the proofs are independent, and the host shares of a half (digits, the argument's half-GCDs and round bookkeeping,
   // the challenge round trips) fall under the kernels of the other.  Same bytes out as one batch (tests).
   const size_t split_min = rp->opt.split_min;   // default 4096; measured: 4096 proofs 91-93 ms split against 95-97 ms, but 2048 proofs (128by64) 109 ms split against 104 ms
   if (batch < split_min || batch < 2 || rp->is_twin || rp->opt.no_split)
-    return prove_batch_one(rp, batch, amounts, types, blinds, rand_prefix, prefix_len, coms_files, proof_files, 0);
+    return prove_batch_one(rp, batch, amounts, types, blinds, rand_prefix, prefix_len, coms_files, proof_files, 0, pub);
   { int rc = rp_ensure_twin(rp); if (rc) return rc; }
   if (rp->comb && !rp->twin->comb) rp->twin->comb = rp->comb;      // not owned by the twin
   rp->twin->opt = rp->opt;
@@ -524,9 +545,9 @@ extern "C" int bppp_rp_prove_batch(bppp_rp *rp, size_t batch, const uint64_t *am
   int rc1 = BPPP_OK;
   std::thread second([&] {
     rc1 = prove_batch_one(rp->twin, B1, amounts + 4 * nr * B0, types + 4 * nr * B0, blinds + 4 * nr * B0, rand_prefix ? rand_prefix + prefix_len * B0 : nullptr, prefix_len,
-                          coms_files + (size_t)rp->D.coms_bytes * B0, proof_files + (size_t)rp->D.proof_bytes * B0, B0);
+                          coms_files + (size_t)rp->D.coms_bytes * B0, proof_files + (size_t)rp->D.proof_bytes * B0, B0, pub_at(B0));
   });
-  const int rc0 = prove_batch_one(rp, B0, amounts, types, blinds, rand_prefix, prefix_len, coms_files, proof_files, 0);
+  const int rc0 = prove_batch_one(rp, B0, amounts, types, blinds, rand_prefix, prefix_len, coms_files, proof_files, 0, pub);
   second.join();
   if (rc0) return rc0;
   if (rc1) return fail(ctx, rc1, bppp_last_error(rp->twin_ctx));
@@ -534,16 +555,16 @@ extern "C" int bppp_rp_prove_batch(bppp_rp *rp, size_t batch, const uint64_t *am
 }
 
 static int prove_batch_one(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint8_t *rand_prefix,
-                           size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files, size_t index_base) {
+                           size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files, size_t index_base, const uint64_t *pub) {
   bppp_ctx *ctx = rp->ctx;
   const Setup &st = rp->st;
   uint32_t max_base = 0;
   for (const RangeData &rd : st.rds) max_base = std::max(max_base, rd.base);
   // the device algebra looks digits up in a per-proof table of reciprocals held in LDS (256 entries, up to 2048 for wider digit bases); bases beyond
   // that (and BPPP_RP_HOST_ALGEBRA=1, kept for comparison) take the host-algebra path: same bytes out
-  if (max_base > 2048 || (max_base > 256 && st.rds.size() > 256) || rp->opt.host_algebra || (st.flavour && !rp->comb)) return prove_batch_host(rp, batch, amounts, types, blinds, rand_prefix, prefix_len, coms_files, proof_files, index_base);
+  if (max_base > 2048 || (max_base > 256 && st.rds.size() > 256) || rp->opt.host_algebra || (st.flavour && !rp->comb)) return prove_batch_host(rp, batch, amounts, types, blinds, rand_prefix, prefix_len, coms_files, proof_files, index_base, pub);
   hipSetDevice(ctx->device);
-  const size_t B = batch, nr = st.rds.size(), nlen = st.nlen, llen = st.llen, k = st.rounds, T = 1 + llen + nlen;
+  const size_t B = batch, nr = st.rds.size(), nlen = st.nlen, llen = st.llen, k = st.rounds, T = 1 + llen + nlen, npub = rp_public_count(rp);
   if (nr >= (1u << 16)) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: too many ranges");
   { int rc = build_fixed_table(rp); if (rc) return rc; }
   if (!rp->commit_basis) { int rc = bppp_basis_create_device(ctx, rp->d_basis, T, 0, 4096, &rp->commit_basis); if (rc) return rc; }
@@ -570,7 +591,7 @@ static int prove_batch_one(bppp_rp *rp, size_t batch, const uint64_t *amounts, c
   rp_parallel(B, [&](size_t lo, size_t hi) {
     PState p;
     for (size_t b = lo; b < hi; b++) {
-      if (!make_witness(st, p, amounts + 4 * nr * b, types + 4 * nr * b, blinds + 4 * nr * b)) { failed = (int)b; errs[b] = p.err; continue; }
+      if (!make_witness(st, p, amounts + 4 * nr * b, types + 4 * nr * b, blinds + 4 * nr * b, pub ? pub + 4 * npub * b : nullptr)) { failed = (int)b; errs[b] = p.err; continue; }
       for (size_t i = 0; i < nr; i++) { p.v[i].store(&h_in_sc[(b * nr + i) * 12]); p.ty[i].store(&h_in_sc[(b * nr + i) * 12 + 4]); p.bl[i].store(&h_in_sc[(b * nr + i) * 12 + 8]); }
       for (size_t i = 0; i < nlen; i++) {
         const bool typing = (st.pos[i].kind & 0xFFu) == bppp_rps::POS_TYPING;
@@ -583,7 +604,7 @@ static int prove_batch_one(bppp_rp *rp, size_t batch, const uint64_t *amounts, c
   if (failed >= 0) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: proof " + std::to_string((size_t)failed + index_base) + ": " + errs[failed]);
   lap("witness digits (host)");
   std::vector<uint64_t> c_dm(B * 8), c_m(B * 8), c_r(B * 8), c_bl(B * 8), resp(B * k * 16), wn(B * st.fn * 4 + 4), wl(B * st.fl * 4 + 4);
-  RppHostInputs in{B, h_in_sc, dig, mul, mss, rand_prefix, prefix_len};
+  RppHostInputs in{B, h_in_sc, dig, mul, mss, rand_prefix, prefix_len, pub};
   RppOutputs out{h_in_pt, c_dm.data(), c_m.data(), c_r.data(), c_bl.data(), resp.data(), wn.data(), wl.data()};
   { int rc = rpp_device_prove(rp, in, out); if (rc) return rc; }
   lap("phases + argument (device)");
@@ -593,14 +614,14 @@ static int prove_batch_one(bppp_rp *rp, size_t batch, const uint64_t *amounts, c
 }
 
 static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint8_t *rand_prefix,
-                            size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files, size_t index_base) {
+                            size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files, size_t index_base, const uint64_t *pub) {
   if (!rp) return BPPP_ERR_ARG;
   bppp_ctx *ctx = rp->ctx;
   if (!batch) return BPPP_OK;
   hipSetDevice(ctx->device);
   hipStream_t stream = ctx->stream;
   const Setup &st = rp->st;
-  const size_t B = batch, nr = st.rds.size(), nlen = st.nlen, llen = st.llen, k = st.rounds, T = 1 + llen + nlen;
+  const size_t B = batch, nr = st.rds.size(), nlen = st.nlen, llen = st.llen, k = st.rounds, T = 1 + llen + nlen, npub = rp_public_count(rp);
   if (nr >= (1u << 16)) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: too many ranges");
   { int rc = build_fixed_table(rp); if (rc) return rc; }
   // the basis of commitRPW is fixed per setup: registered once with its fixed-base table (one bucket set for all windows)
@@ -635,7 +656,7 @@ static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
     for (size_t b = lo; b < hi; b++) {
       PState &p = ps[b];
       p.rnd = Rnd{rand_prefix + b * prefix_len, prefix_len, 0};
-      if (!make_witness(st, p, amounts + 4 * nr * b, types + 4 * nr * b, blinds + 4 * nr * b)) { failed = (int)b; continue; }
+      if (!make_witness(st, p, amounts + 4 * nr * b, types + 4 * nr * b, blinds + 4 * nr * b, pub ? pub + 4 * npub * b : nullptr)) { failed = (int)b; continue; }
       for (size_t i = 0; i < nr; i++) { p.v[i].store(&h_in_sc[(b * nr + i) * 12]); p.ty[i].store(&h_in_sc[(b * nr + i) * 12 + 4]); p.bl[i].store(&h_in_sc[(b * nr + i) * 12 + 8]); }
       p.dm = blind_witness(2, p.ms_shared, p.d, p.rnd, llen);
       p.m = blind_witness(1, std::vector<U256>(), p.mi, p.rnd, llen);
@@ -719,7 +740,7 @@ static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
       const uint64_t *pt = &c_bl[8 * b];
       oracle(rp->tag, p, &pt, 1, 1, &p.t);
       U256 psc; std::vector<U256> pn;
-      make_public_consts(st, p, psc, pn);
+      make_public_consts(st, p, psc, pn, pub ? pub + 4 * npub * b : nullptr);
       const U256 t2 = fm(p.t, p.t), t3 = fm(t2, p.t), t4 = fm(t2, t2), t5 = fm(t4, p.t), t6 = fm(t3, t3), two_t5 = fdbl(t5);
       // wit = pub + blWit + t mWit + t^2 dmWit + t^3 rWit + 2 t^5 nWitSum
       U256 sc = fa(fa(psc, p.blw.sc), fa(fa(fm(p.t, p.m.sc), fm(t2, p.dm.sc)), fa(fm(t3, p.r.sc), fm(two_t5, p.ns_sc))));

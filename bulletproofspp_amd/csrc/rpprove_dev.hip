@@ -443,7 +443,9 @@ int rpp_device_prove(bppp_rp *rp, const RppHostInputs &in, RppOutputs &out) {
     cscratch = cv.take<uint32_t>(std::max(comb_rows_scratch_bytes(B), comb_scratch_bytes(2 * B)) / 4 + 16);
     if (!pass) { int rc = rpp_ensure_pwork(rp, cv.off); if (rc) return rc; }
   }
-  // ---- uploads: inputs, digits, multiplicities, prefixes
+  // ---- uploads: per-proof public amounts (bppp_rp_prove_batch_pub), inputs, digits, multiplicities, prefixes
+  const uint32_t *d_pub = nullptr;
+  if (in.pub) { int rc_ = rp_upload_public(rp, in.pub, B * S.pubs.size() * 4, &d_pub); if (rc_) return rc_; }
   BPPP_HIP(ctx, hipMemcpyAsync(in_sc, in.in_sc, B * nr * 96, hipMemcpyHostToDevice, st));
   BPPP_HIP(ctx, hipMemcpyAsync(dig, in.dig, B * nlen * 4, hipMemcpyHostToDevice, st));
   BPPP_HIP(ctx, hipMemcpyAsync(mul, in.mul, B * nlen * 4, hipMemcpyHostToDevice, st));
@@ -494,7 +496,7 @@ int rpp_device_prove(bppp_rp *rp, const RppHostInputs &in, RppOutputs &out) {
     rc = comb(row_bl, B, c_bl, COMB_ROWS_DENSE); if (rc) return rc;
     rc = oracle_dev(c_bl, 2); if (rc) return rc;
     BPPP_HIP(ctx, hipGetLastError());
-    rc = bppp_trrp_public_device(rp->tabs, B, ch, a_q, p_sp, p_norm, p_cs, p_init); if (rc) return rc;
+    rc = trrp_public_run(rp->tabs, B, ch, a_q, p_sp, p_norm, p_cs, p_init, d_pub); if (rc) return rc;
     { const uint64_t n = (uint64_t)B * T;
       k_rpp_combine<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(D, (uint32_t)B, ch, rows_dm_m, row_r, row_bl, aux, p_sp, p_norm, a_s, a_lx, a_nx); }
     BPPP_HIP(ctx, hipGetLastError());
@@ -545,7 +547,7 @@ int rpp_device_prove(bppp_rp *rp, const RppHostInputs &in, RppOutputs &out) {
   rc = rpp_commit_rows(rp, row_bl, B, out.c_bl); if (rc) return rc;
   // ---- t <- oracle [blCom]; public constants and linear weights by the verifier's kernel; the combined witness
   rc = oracle(out.c_bl, 2); if (rc) return rc;
-  rc = bppp_trrp_public_device(rp->tabs, B, ch, a_q, p_sp, p_norm, p_cs, p_init); if (rc) return rc;
+  rc = trrp_public_run(rp->tabs, B, ch, a_q, p_sp, p_norm, p_cs, p_init, d_pub); if (rc) return rc;
   { const uint64_t n = (uint64_t)B * T;
     k_rpp_combine<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(D, (uint32_t)B, ch, rows_dm_m, row_r, row_bl, aux, p_sp, p_norm, a_s, a_lx, a_nx); }
   BPPP_HIP(ctx, hipGetLastError());

@@ -19,6 +19,7 @@ struct RppHostInputs {
   const uint32_t *mul;       // [batch][nlen]: the inline multiplicity (0 elsewhere)
   const uint32_t *mss;       // [batch][llen - 6]: the shared multiplicities
   const uint8_t *prefix; size_t prefix_len;
+  const uint64_t *pub;       // NULL (the setup's public amounts) or [batch][npub][4] canonical: bppp_rp_prove_batch_pub
 };
 struct RppOutputs {          // host arrays
   uint64_t *input_coms;      // [batch][nr][8]
@@ -35,6 +36,7 @@ struct BrpHostInputs {
   const uint64_t *in_sc;     // [batch][nr][3][4]: amount, blinding, 0 as field elements (scalarRPW', src/RangeProof/Internal.hs:56-57)
   const uint8_t *bits;       // [batch][nlive]: the binary digit of every live norm position (makeDigits, src/RangeProof/Binary.hs:56-69)
   const uint8_t *prefix; size_t prefix_len;
+  const uint64_t *pub;       // NULL (the setup's net_public) or [batch][4] canonical: bppp_rp_prove_batch_pub
 };
 struct BrpOutputs {          // host arrays
   uint64_t *input_coms;      // [batch][nr][8]
@@ -50,7 +52,9 @@ int rpp_argument_stream(bppp_rp *rp, RppTranscript &tr, size_t first_call, size_
                         const uint32_t *a_lx, uint32_t *d_resp, uint64_t *resp_out, uint64_t *wn_out, uint64_t *wl_out, const uint32_t *d_extra, size_t extra_points,
                         std::vector<uint64_t> &extra_out);
 // verifyBRPM's public scalars for a batch (k_brp_public, csrc/rp.hip): the binary prover reuses them as the TR prover reuses k_trrp_public
-int brp_public_device(bppp_rp *rp, size_t batch, const uint32_t *ch, uint32_t *q, uint32_t *sp, uint32_t *pub_norm, uint32_t *pub_lin_c, uint32_t *init_sc);
+// d_net: NULL (the setup's net_public) or [batch] canonical values, one per proof
+int brp_public_device(bppp_rp *rp, size_t batch, const uint32_t *ch, uint32_t *q, uint32_t *sp, uint32_t *pub_norm, uint32_t *pub_lin_c, uint32_t *init_sc,
+                      const uint32_t *d_net);
 
 // provided by rpprove.hip
 int rpp_ensure_pwork(bppp_rp *rp, size_t bytes);

@@ -154,10 +154,11 @@ int rpp_ensure_pwork(bppp_rp *rp, size_t bytes);       // the [3][64][15] fixed-
 int ip_argument_lockstep(bppp_rp *rp, size_t B, size_t k, const uint64_t *psv_in, const uint64_t *rr, const uint64_t *nrm, const uint64_t *lc_in, const uint64_t *lx_in,
                          const std::function<bppp_rpp::PState &(size_t)> &tr_of, uint64_t *resp, uint64_t *wn, uint64_t *wl);
 // csrc/brpprove.hip: RangeProof.Binary, host-algebra route and the wrapper of the device-resident one
+// pub: NULL (the setup's net_public) or one canonical net_public per proof, [batch][4] (bppp_rp_prove_batch_pub)
 int prove_batch_binary(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *blinds, const uint8_t *rand_prefix, size_t prefix_len, uint8_t *coms_files,
-                       uint8_t *proof_files);
+                       uint8_t *proof_files, const uint64_t *pub = nullptr);
 int prove_batch_binary_dev(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *blinds, const uint8_t *rand_prefix, size_t prefix_len, uint8_t *coms_files,
-                           uint8_t *proof_files, size_t index_base = 0);
+                           uint8_t *proof_files, size_t index_base = 0, const uint64_t *pub = nullptr);
 }  // namespace bppp
 
 extern "C" {

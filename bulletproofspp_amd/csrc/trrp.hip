@@ -43,7 +43,9 @@ BPPP_DI void lds_put(uint32_t *p, uint32_t i, const fr &a) { for (int k = 0; k <
 // (round 1) start-up was two thirds of the ~11 k multiplications per 64by64 proof.  G = 16: the chunks are four times longer, the
 // scans two steps shorter and one inversion pass serves four proofs.  (A 256-lane workgroup per proof spent three times the
 // single-wavefront figure on start-up alone.)
-template <int G>
+// PP (per-proof public amounts): pub_amount is [batch][npub] instead of the setup's [npub] (bppp_rp_*_pub); PP = false is the handle's
+// own amounts, the kernel every existing entry point runs
+template <int G, bool PP>
 __global__ void __launch_bounds__(64) k_trrp_public(TrrpDims D, uint32_t batch, uint32_t lds_words_per_proof, const uint32_t *__restrict__ pos_kind,
                                                     const uint32_t *__restrict__ pos_range,
                                                     const uint32_t *__restrict__ pos_slot, const uint32_t *__restrict__ pos_sym,
@@ -156,11 +158,13 @@ __global__ void __launch_bounds__(64) k_trrp_public(TrrpDims D, uint32_t batch, 
   // z (:254): -2 t^5 sum_j min_j x^(2(j+1))  -  [typed] 2 t^5 x pubSum
   for (uint32_t j = t; j < D.nr; j += G)
     if (!range_assumed[j]) acc = fr_subr(acc, frm(two_t5, frm(fr_load(range_min + (size_t)j * 8), lds_get(x2, j))));
-  if (D.has_types)
+  if (D.has_types) {
+    const uint32_t *amt = PP ? pub_amount + (size_t)b * D.npub * 8 : pub_amount;
     for (uint32_t j = t; j < D.npub; j += G) {
-      fr term = frm(frm(two_t5, x), frm(fr_load(pub_amount + (size_t)j * 8), lds_get(inv, 2 + pub_sym[j])));
+      fr term = frm(frm(two_t5, x), frm(fr_load(amt + (size_t)j * 8), lds_get(inv, 2 + pub_sym[j])));
       acc = pub_is_out[j] ? fr_addr(acc, term) : fr_subr(acc, term);
     }
+  }
   __syncthreads();
   lds_put(sa, t, acc);
   __syncthreads();
@@ -303,7 +307,8 @@ __global__ void __launch_bounds__(64) k_trrp_pre(TrrpDims D, uint32_t batch, con
   }
 }
 
-// one wavefront per proof; the record (written by k_trrp_pre) is only read here
+// one wavefront per proof; the record (written by k_trrp_pre) is only read here.  PP as for k_trrp_public
+template <bool PP>
 __global__ void __launch_bounds__(64, 2) k_trrp_pos(TrrpDims D, uint32_t batch, const uint32_t *__restrict__ pos_kind, const uint32_t *__restrict__ pos_range,
                                                     const uint32_t *__restrict__ pos_slot, const uint32_t *__restrict__ pos_sym, const uint32_t *__restrict__ pos_coeff,
                                                     const uint32_t *__restrict__ range_min, const uint32_t *__restrict__ range_assumed,
@@ -346,11 +351,13 @@ __global__ void __launch_bounds__(64, 2) k_trrp_pos(TrrpDims D, uint32_t batch, 
   // z (:254): -2 t^5 sum_j min_j x^(2(j+1))  -  [typed] 2 t^5 x pubSum
   for (uint32_t j = t; j < D.nr; j += 64)
     if (!range_assumed[j]) acc = fr_subr(acc, frm(rec_get(rec, TC_2T5), frm(fr_load(range_min + (size_t)j * 8), rec_get(rec + R.x2, j))));
-  if (D.has_types)
+  if (D.has_types) {
+    const uint32_t *amt = PP ? pub_amount + (size_t)b * D.npub * 8 : pub_amount;
     for (uint32_t j = t; j < D.npub; j += 64) {
-      const fr term = frm(rec_get(rec, TC_2T5X), frm(fr_load(pub_amount + (size_t)j * 8), rec_get(rec + R.inv, 2 + pub_sym[j])));
+      const fr term = frm(rec_get(rec, TC_2T5X), frm(fr_load(amt + (size_t)j * 8), rec_get(rec + R.inv, 2 + pub_sym[j])));
       acc = pub_is_out[j] ? fr_addr(acc, term) : fr_subr(acc, term);
     }
+  }
   lds_put(part, t, acc);
   __syncthreads();
   for (int d = 32; d >= 1; d >>= 1) {
@@ -450,6 +457,14 @@ int bppp_trrp_create(bppp_ctx *ctx, int flavour, int has_types, size_t nlen, siz
 
 int bppp_trrp_public_device(bppp_trrp *o, size_t batch, const void *d_challenges, void *d_q, void *d_sp, void *d_pub_norm, void *d_pub_lin_c,
                             void *d_init_scalars) {
+  return bppp::trrp_public_run(o, batch, d_challenges, d_q, d_sp, d_pub_norm, d_pub_lin_c, d_init_scalars, nullptr);
+}
+
+}  // extern "C"
+
+// d_pub_amounts: NULL (the setup's public amounts) or [batch][npub] canonical scalars, one row per proof
+int bppp::trrp_public_run(bppp_trrp *o, size_t batch, const void *d_challenges, void *d_q, void *d_sp, void *d_pub_norm, void *d_pub_lin_c, void *d_init_scalars,
+                          const void *d_pub_amounts) {
   if (!o) return BPPP_ERR_ARG;
   bppp_ctx *ctx = o->ctx;
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
@@ -465,9 +480,14 @@ int bppp_trrp_public_device(bppp_trrp *o, size_t batch, const void *d_challenges
     uint32_t *rec = (uint32_t *)ctx->ws2;
     hipStream_t st = ctx->stream;
     k_trrp_pre<16><<<dim3((unsigned)((batch + 3) / 4)), dim3(64), 0, st>>>(o->D, (uint32_t)batch, o->syms, (const uint32_t *)d_challenges, rec);
-    k_trrp_pos<<<dim3((unsigned)batch), dim3(64), 0, st>>>(o->D, (uint32_t)batch, o->pos_kind, o->pos_range, o->pos_slot, o->pos_sym, o->pos_coeff, o->range_min,
-                                                           o->range_assumed, o->pub_is_out, o->pub_amount, o->pub_sym, rec, (uint32_t *)d_q, (uint32_t *)d_sp,
-                                                           (uint32_t *)d_pub_norm);
+    if (d_pub_amounts)
+      k_trrp_pos<true><<<dim3((unsigned)batch), dim3(64), 0, st>>>(o->D, (uint32_t)batch, o->pos_kind, o->pos_range, o->pos_slot, o->pos_sym, o->pos_coeff, o->range_min,
+                                                                   o->range_assumed, o->pub_is_out, (const uint32_t *)d_pub_amounts, o->pub_sym, rec, (uint32_t *)d_q,
+                                                                   (uint32_t *)d_sp, (uint32_t *)d_pub_norm);
+    else
+      k_trrp_pos<false><<<dim3((unsigned)batch), dim3(64), 0, st>>>(o->D, (uint32_t)batch, o->pos_kind, o->pos_range, o->pos_slot, o->pos_sym, o->pos_coeff, o->range_min,
+                                                                    o->range_assumed, o->pub_is_out, o->pub_amount, o->pub_sym, rec, (uint32_t *)d_q, (uint32_t *)d_sp,
+                                                                    (uint32_t *)d_pub_norm);
     const uint64_t nl = (uint64_t)batch * (o->D.llen + 4 + o->D.nr);
     k_trrp_lin<<<dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, st>>>(o->D, (uint32_t)batch, o->range_assumed, o->cs_slot, o->cs_sym, rec, (uint32_t *)d_pub_lin_c,
                                                                        (uint32_t *)d_init_scalars);
@@ -484,19 +504,21 @@ int bppp_trrp_public_device(bppp_trrp *o, size_t batch, const void *d_challenges
   const size_t wpp = words(G), lds = wpp * 4 * (64 / G);
   if (lds > 160 * 1024) return fail(ctx, BPPP_ERR_ARG, "trrp_public: too many ranges for one workgroup's LDS");
   const unsigned grid = (unsigned)((batch + 64 / G - 1) / (64 / G));
-#define TRRP_LAUNCH(GG)                                                                                                                        \
-  k_trrp_public<GG><<<dim3(grid), dim3(64), lds, ctx->stream>>>(o->D, (uint32_t)batch, (uint32_t)wpp, o->pos_kind, o->pos_range, o->pos_slot, o->pos_sym, o->pos_coeff, \
-                                                               o->range_min, o->range_assumed, o->syms, o->cs_slot, o->cs_sym, o->pub_is_out, o->pub_amount, o->pub_sym, \
-                                                               (const uint32_t *)d_challenges, (uint32_t *)d_q, (uint32_t *)d_sp, (uint32_t *)d_pub_norm,          \
-                                                               (uint32_t *)d_pub_lin_c, (uint32_t *)d_init_scalars)
+#define TRRP_LAUNCH(GG, PP, AMT)                                                                                                               \
+  k_trrp_public<GG, PP><<<dim3(grid), dim3(64), lds, ctx->stream>>>(o->D, (uint32_t)batch, (uint32_t)wpp, o->pos_kind, o->pos_range, o->pos_slot, o->pos_sym, \
+                                                                   o->pos_coeff, o->range_min, o->range_assumed, o->syms, o->cs_slot, o->cs_sym, o->pub_is_out, \
+                                                                   (AMT), o->pub_sym, (const uint32_t *)d_challenges, (uint32_t *)d_q, (uint32_t *)d_sp,   \
+                                                                   (uint32_t *)d_pub_norm, (uint32_t *)d_pub_lin_c, (uint32_t *)d_init_scalars)
+#define TRRP_LAUNCH_G(GG) do { if (d_pub_amounts) TRRP_LAUNCH(GG, true, (const uint32_t *)d_pub_amounts); else TRRP_LAUNCH(GG, false, o->pub_amount); } while (0)
   if (G == 64) {
-    if (lds > 64 * 1024) BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_trrp_public<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    TRRP_LAUNCH(64);
-  } else if (G == 32) TRRP_LAUNCH(32);
-  else TRRP_LAUNCH(16);
+    if (lds > 64 * 1024)
+      BPPP_HIP(ctx, hipFuncSetAttribute(d_pub_amounts ? (const void *)k_trrp_public<64, true> : (const void *)k_trrp_public<64, false>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    TRRP_LAUNCH_G(64);
+  } else if (G == 32) TRRP_LAUNCH_G(32);
+  else TRRP_LAUNCH_G(16);
+#undef TRRP_LAUNCH_G
 #undef TRRP_LAUNCH
   BPPP_HIP(ctx, hipGetLastError());
   return BPPP_OK;
 }
-
-}  // extern "C"

@@ -16,3 +16,8 @@ struct bppp_trrp {
   bppp::TrrpDims D;
   uint32_t *pos_kind, *pos_range, *pos_slot, *pos_sym, *pos_coeff, *range_min, *range_assumed, *syms, *cs_slot, *cs_sym, *pub_is_out, *pub_amount, *pub_sym;
 };
+namespace bppp {
+// bppp_trrp_public_device with per-proof public amounts: d_pub_amounts NULL (the setup's) or [batch][npub] canonical scalars in HBM (csrc/trrp.hip)
+int trrp_public_run(bppp_trrp *t, size_t batch, const void *d_challenges, void *d_q, void *d_sp, void *d_pub_norm, void *d_pub_lin_c, void *d_init_scalars,
+                    const void *d_pub_amounts);
+}  // namespace bppp

@@ -874,9 +874,48 @@ class NativeRangeProofs:
         from .capi import RP_OPTIONS
         self.gpu._check(self.gpu.lib.bppp_rp_set_option(self.h, RP_OPTIONS[name], int(value)), "bppp_rp_set_option")
 
-    def prove_batch(self, inputs: Sequence[Sequence[Tuple[int, int, int]]], rand_prefixes: Sequence[bytes]) -> List[Tuple[bytes, bytes]]:
+    def public_count(self) -> int:
+        """bppp_rp_public_count: public amounts per proof the *_pub calls take (npub of a typed handle, 1 of a conserved binary one, else 0)"""
+        import ctypes as C
+        n = C.c_size_t(0)
+        self.gpu._check(self.gpu.lib.bppp_rp_public_count(self.h, C.byref(n)), "bppp_rp_public_count")
+        return int(n.value)
+
+    def _public_words(self, public_amounts, B: int):
+        """B per-proof public amount lists -> [B * npub][4] words of canonical scalars (reduced mod N, as the constructor does for pub_vt)"""
+        from .capi import scalars_to_array
+        if len(public_amounts) != B:
+            raise ValueError("one list of public amounts per proof is required")
+        return scalars_to_array([int(v) % N for row in public_amounts for v in row] or [0])
+
+    def _with_public(self, fn, public_amounts, B: int, device: bool):
+        """(entry point taking the amounts after the files, what keeps them alive): `public_amounts` is a device pointer (int) on a device
+        entry point, else per-proof values, uploaded for one"""
+        import ctypes as C
+        if isinstance(public_amounts, int):
+            return (lambda h, n, pc, pp, *rest: fn(h, n, pc, pp, C.c_void_p(public_amounts), *rest)), None
+        words = self._public_words(public_amounts, B)
+        if device:
+            d = self.gpu.to_device(words)
+            return (lambda h, n, pc, pp, *rest: fn(h, n, pc, pp, C.c_void_p(d), *rest)), d
+        return (lambda h, n, pc, pp, *rest: fn(h, n, pc, pp, C.c_void_p(words.ctypes.data), *rest)), words
+
+    def _call_public(self, fn, fn_pub, public_amounts, B: int, device: bool, run):
+        """run(fn) with the plain entry point, or with the *_pub one and these amounts (a device copy made here is freed after)"""
+        if public_amounts is None:
+            return run(fn)
+        f, keep = self._with_public(fn_pub, public_amounts, B, device)
+        try:
+            return run(f)
+        finally:
+            if device and keep is not None:
+                self.gpu.free(keep)
+
+    def prove_batch(self, inputs: Sequence[Sequence[Tuple[int, int, int]]], rand_prefixes: Sequence[bytes], public_amounts=None) -> List[Tuple[bytes, bytes]]:
         """bppp_rp_prove_batch: inputs[b] = [(amount, type, blinding) per range]; rand_prefixes[b] = the hashToScalar prefix of
-        proof b (all of one length).  Returns [(commitments file, proof file)] — the bytes encoding.encode_proof(prove(...)) gives."""
+        proof b (all of one length).  Returns [(commitments file, proof file)] — the bytes encoding.encode_proof(prove(...)) gives.
+        public_amounts (bppp_rp_prove_batch_pub): per proof, the public amounts that replace the setup's (one list per proof on a typed
+        handle, in pub_vt's order; one int per proof on a binary one); None = the setup's."""
         import ctypes as C
         import numpy as np
         from .capi import scalars_to_array
@@ -893,15 +932,20 @@ class NativeRangeProofs:
         cf = np.zeros(B * self.shape["coms_bytes"], dtype=np.uint8)
         pf = np.zeros(B * self.shape["proof_bytes"], dtype=np.uint8)
         vp = lambda a: C.c_void_p(a.ctypes.data)
-        rc = self.gpu.lib.bppp_rp_prove_batch(self.h, B, vp(amt), vp(typ), vp(bld), vp(pre), plen, vp(cf), vp(pf))
+        if public_amounts is None:
+            rc = self.gpu.lib.bppp_rp_prove_batch(self.h, B, vp(amt), vp(typ), vp(bld), vp(pre), plen, vp(cf), vp(pf))
+        else:
+            pa = self._public_words(public_amounts, B)
+            rc = self.gpu.lib.bppp_rp_prove_batch_pub(self.h, B, vp(amt), vp(typ), vp(bld), vp(pa), vp(pre), plen, vp(cf), vp(pf))
         self.gpu._check(rc, "bppp_rp_prove_batch")
         cb, pb = self.shape["coms_bytes"], self.shape["proof_bytes"]
         return [(cf[b * cb:(b + 1) * cb].tobytes(), pf[b * pb:(b + 1) * pb].tobytes()) for b in range(B)]
 
     def verify_batch(self, coms_files: Sequence[bytes], proof_files: Sequence[bytes], seed: Optional[bytes] = None, want_status: bool = False,
-                     want_challenges: bool = False):
+                     want_challenges: bool = False, public_amounts=None):
         """bppp_rp_verify_batch on host byte strings: returns accept, or (accept, status list, challenges per proof) as asked.
-        `seed` is the verifier's randomness behind the batch weights: fresh from os.urandom unless given (fixed seeds are for tests)."""
+        `seed` is the verifier's randomness behind the batch weights: fresh from os.urandom unless given (fixed seeds are for tests).
+        public_amounts: per-proof public amounts as for prove_batch (bppp_rp_verify_batch_pub), taken from the transactions."""
         import ctypes as C
         import numpy as np
         if seed is None:
@@ -912,31 +956,44 @@ class NativeRangeProofs:
         if any(len(c) != self.shape["coms_bytes"] for c in coms_files) or any(len(p_) != self.shape["proof_bytes"] for p_ in proof_files):
             return (False, [2] * B, None) if (want_status or want_challenges) else False       # wrong length: malformed, as decodeProof' returns Nothing
         cb, pb = np.frombuffer(b"".join(coms_files), dtype=np.uint8), np.frombuffer(b"".join(proof_files), dtype=np.uint8)
-        return self._verify(self.gpu.lib.bppp_rp_verify_batch, B, C.c_void_p(cb.ctypes.data), C.c_void_p(pb.ctypes.data), seed, want_status, want_challenges, (cb, pb))
+        lib = self.gpu.lib
+        return self._call_public(lib.bppp_rp_verify_batch, lib.bppp_rp_verify_batch_pub, public_amounts, B, False,
+                                 lambda fn: self._verify(fn, B, C.c_void_p(cb.ctypes.data), C.c_void_p(pb.ctypes.data), seed, want_status, want_challenges, (cb, pb)))
 
-    def verify_batch_device(self, batch: int, d_coms: int, d_proofs: int, seed: Optional[bytes] = None, want_status: bool = False, want_challenges: bool = False):
+    def verify_batch_device(self, batch: int, d_coms: int, d_proofs: int, seed: Optional[bytes] = None, want_status: bool = False, want_challenges: bool = False,
+                            public_amounts=None):
+        """bppp_rp_verify_batch_device; public_amounts: per-proof values (uploaded for the call) or a device pointer to the
+        [batch][public_count][4] words (bppp_rp_verify_batch_pub_device)"""
         import ctypes as C
         if seed is None:
             seed = os.urandom(32)
-        return self._verify(self.gpu.lib.bppp_rp_verify_batch_device, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), seed, want_status, want_challenges, None)
+        lib = self.gpu.lib
+        return self._call_public(lib.bppp_rp_verify_batch_device, lib.bppp_rp_verify_batch_pub_device, public_amounts, batch, True,
+                                 lambda fn: self._verify(fn, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), seed, want_status, want_challenges, None))
 
-    def verify_batch_device_point(self, batch: int, d_coms: int, d_proofs: int, seed: bytes, index_offset: int = 0) -> Tuple[bool, Point]:
+    def verify_batch_device_point(self, batch: int, d_coms: int, d_proofs: int, seed: bytes, index_offset: int = 0, public_amounts=None) -> Tuple[bool, Point]:
         """bppp_rp_verify_shard_device: (accept, the combined point) — the partial result of one rank when the job is sharded
-        proof-per-GPU; this rank holds proofs [index_offset, index_offset + batch) of the job, every rank passes the same seed."""
+        proof-per-GPU; this rank holds proofs [index_offset, index_offset + batch) of the job, every rank passes the same seed.
+        public_amounts as for verify_batch_device (bppp_rp_verify_shard_pub_device)."""
         import ctypes as C
         import numpy as np
         from .capi import array_to_point
         acc, out = C.c_int(0), np.zeros(8, dtype=np.uint64)
         sd = np.frombuffer(seed, dtype=np.uint8)
-        rc = self.gpu.lib.bppp_rp_verify_shard_device(self.h, batch, index_offset, C.c_void_p(d_coms), C.c_void_p(d_proofs), C.c_void_p(sd.ctypes.data),
-                                                      C.byref(acc), None, None, C.c_void_p(out.ctypes.data))
+        lib = self.gpu.lib
+        shard = lambda h, n, pc, pp, *rest: lib.bppp_rp_verify_shard_device(h, n, index_offset, pc, pp, *rest)
+        shard_pub = lambda h, n, pc, pp, pa, *rest: lib.bppp_rp_verify_shard_pub_device(h, n, index_offset, pc, pp, pa, *rest)
+        rc = self._call_public(shard, shard_pub, public_amounts, batch, True,
+                               lambda fn: fn(self.h, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), C.c_void_p(sd.ctypes.data), C.byref(acc), None, None,
+                                             C.c_void_p(out.ctypes.data)))
         self.gpu._check(rc, "bppp_rp_verify_shard_device")
         return bool(acc.value), array_to_point(out)
 
-    def verify_each(self, coms_files: Sequence[bytes], proof_files: Sequence[bytes], want_points: bool = False):
+    def verify_each(self, coms_files: Sequence[bytes], proof_files: Sequence[bytes], want_points: bool = False, public_amounts=None):
         """bppp_rp_verify_each on host byte strings: every proof decided on its own, without weights or seed.  Returns the status list
         (0 valid, 1 invalid, 2 malformed), or (statuses, [E_b per proof]) with want_points (None for infinity, and for a malformed
-        proof).  A file of the wrong length makes the whole batch MALFORMED without a library call, as verify_batch does."""
+        proof).  A file of the wrong length makes the whole batch MALFORMED without a library call, as verify_batch does.
+        public_amounts as for verify_batch (bppp_rp_verify_each_pub)."""
         import ctypes as C
         import numpy as np
         B = len(proof_files)
@@ -946,12 +1003,16 @@ class NativeRangeProofs:
             return ([2] * B, [None] * B) if want_points else [2] * B
         cb = np.frombuffer(b"".join(coms_files) or b"\0", dtype=np.uint8)
         pb = np.frombuffer(b"".join(proof_files) or b"\0", dtype=np.uint8)
-        return self._verify_each(self.gpu.lib.bppp_rp_verify_each, B, C.c_void_p(cb.ctypes.data), C.c_void_p(pb.ctypes.data), want_points)
+        lib = self.gpu.lib
+        return self._call_public(lib.bppp_rp_verify_each, lib.bppp_rp_verify_each_pub, public_amounts, B, False,
+                                 lambda fn: self._verify_each(fn, B, C.c_void_p(cb.ctypes.data), C.c_void_p(pb.ctypes.data), want_points))
 
-    def verify_each_device(self, batch: int, d_coms: int, d_proofs: int, want_points: bool = False):
-        """bppp_rp_verify_each_device: verify_each on files already in HBM (device pointers)"""
+    def verify_each_device(self, batch: int, d_coms: int, d_proofs: int, want_points: bool = False, public_amounts=None):
+        """bppp_rp_verify_each_device: verify_each on files already in HBM (device pointers); public_amounts as for verify_batch_device"""
         import ctypes as C
-        return self._verify_each(self.gpu.lib.bppp_rp_verify_each_device, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), want_points)
+        lib = self.gpu.lib
+        return self._call_public(lib.bppp_rp_verify_each_device, lib.bppp_rp_verify_each_pub_device, public_amounts, batch, True,
+                                 lambda fn: self._verify_each(fn, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), want_points))
 
     def _verify_each(self, fn, B, pc, pp, want_points):
         import ctypes as C

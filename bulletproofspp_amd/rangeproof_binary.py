@@ -233,9 +233,16 @@ class NativeBinaryRangeProofs(NativeRangeProofs):
                 (st.nrm_len, 2, st.rounds, tuple(st.final_lens)):
             raise RuntimeError("native binary setup disagrees with the host setup: %r" % (self.shape,))
 
-    def prove_batch(self, inputs: Sequence[Sequence[Tuple[int, int]]], rand_prefixes: Sequence[bytes]) -> List[Tuple[bytes, bytes]]:
-        """bppp_rp_prove_batch on a binary setup: inputs[b] = [(amount, blinding) per range]"""
-        return super().prove_batch([[(v, 0, bl) for v, bl in row] for row in inputs], rand_prefixes)
+    def prove_batch(self, inputs: Sequence[Sequence[Tuple[int, int]]], rand_prefixes: Sequence[bytes], public_amounts=None) -> List[Tuple[bytes, bytes]]:
+        """bppp_rp_prove_batch on a binary setup: inputs[b] = [(amount, blinding) per range]; public_amounts: one net_public per proof"""
+        return super().prove_batch([[(v, 0, bl) for v, bl in row] for row in inputs], rand_prefixes, public_amounts=public_amounts)
+
+    def _public_words(self, public_amounts, B: int):
+        """B per-proof net_public values -> [B][4] words (mod 2^256, as the constructor passes net_public)"""
+        from .capi import scalars_to_array
+        if len(public_amounts) != B:
+            raise ValueError("one net_public per proof is required")
+        return scalars_to_array([int(v) % 2**256 for v in public_amounts] or [0])
 
     def split_challenges(self, flat: Sequence[int]):
         return list(flat[:4]), list(flat[4:])

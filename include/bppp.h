@@ -493,6 +493,44 @@ int bppp_rp_verify_mixed(const bppp_rp_group *groups, size_t ngroups, const uint
 int bppp_rp_prove_batch(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint8_t *rand_prefix,
                         size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files);
 
+/* ---- per-proof public amounts (fees, deposits, withdrawals) --------------------------------------------------------------------
+ * A handle fixes its setup's public amounts at creation: the `amount` of every bppp_rp_public (typed reciprocal, pubSum of
+ * TypedReciprocal.hs:235-248) or `net_public` (RangeProof.Binary with conservation, netPub' of Binary.hs:72-87).  In a block of
+ * conserved transactions they are each transaction's fee or public deposit and differ from proof to proof.  The *_pub entry points
+ * below take them per proof; everything else (ranges, public types and is_output flags, basis, tag) stays the handle's.
+ *   bppp_rp_public_count: amounts per proof — npub for a typed handle created with has_types, 1 for a binary handle with `conserve`,
+ *                         0 otherwise (an untyped handle, whose public values the protocol ignores, or a binary one without conservation).
+ *   public_amounts: [batch][public_count][4] words, encoded as the creation argument is — typed: canonical scalars, in the order of the
+ *                   handle's `pubs`; binary: the plain integer in two's complement, as net_public.  NULL = the handle's own amounts:
+ *                   the call is then exactly its counterpart without _pub.  _device variants take it in HBM (d_public_amounts); it is
+ *                   read back and checked on the host (32 bytes per amount) before any work is queued.
+ * Proof b under a *_pub call behaves as proof b under a handle created with the same arguments but proof b's amounts: statuses,
+ * challenges, E_b (verify_each), the prover's files and its balance check (witnessTRRP's per-type sum, witnessBRP's netPub + sum v = 0;
+ * the first proof that does not balance is named in the BPPP_ERR_ARG message) all match that handle.  The batch weights rho_b are
+ * defined exactly as for bppp_rp_verify_shard_device — the amounts are the verifier's own inputs, fixed before it draws its seed — so
+ * combined_xy of bppp_rp_verify_shard_pub_device is the sum over b of bppp_rp_verify_shard_device (handle with amounts_b, 1,
+ * index_offset + b, ...)'s points.
+ * Fiat-Shamir: the reference does not hash the public amounts into the transcript, and neither does this library (parity): a proof
+ * made for one fee also opens against a setup whose other values agree only where the prover chose them.  The caller must take the
+ * amounts from the transaction it is validating, never from the prover.
+ * BPPP_ERR_ARG: a non-NULL public_amounts with batch > 0 on a handle whose public_count is 0; a typed amount that is not canonical;
+ * every argument error of the counterpart without _pub. */
+int bppp_rp_public_count(const bppp_rp *rp, size_t *n);
+int bppp_rp_verify_batch_pub(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint8_t *proof_files, const uint64_t *public_amounts,
+                             const uint8_t seed[32], int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy);
+int bppp_rp_verify_batch_pub_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_proof_files, const void *d_public_amounts,
+                                    const uint8_t seed[32], int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy);
+int bppp_rp_verify_shard_pub_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files,
+                                    const void *d_public_amounts, const uint8_t seed[32], int *accept, uint32_t *proof_status,
+                                    uint64_t *challenges_out, uint64_t *combined_xy);
+int bppp_rp_verify_each_pub(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint8_t *proof_files, const uint64_t *public_amounts,
+                            uint32_t *proof_status, uint64_t *proof_xy);
+int bppp_rp_verify_each_pub_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_proof_files, const void *d_public_amounts,
+                                   uint32_t *proof_status, uint64_t *proof_xy);
+int bppp_rp_prove_batch_pub(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds,
+                            const uint64_t *public_amounts, const uint8_t *rand_prefix, size_t prefix_len, uint8_t *coms_files,
+                            uint8_t *proof_files);
+
 /* ---- harness utility: pointX of getPoints (app/Main.hs:68-72) -------------------------------
  * For each candidate x (n x 4 uint64 in HBM) writes the affine point (x, y) with y the EVEN root of
  * x^3 + 7, or the infinity encoding when x^3 + 7 is a non-residue or x >= p.  (Which root
