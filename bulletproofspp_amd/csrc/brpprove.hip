@@ -1,8 +1,6 @@
 // brpprove.hip — RangeProof.Binary's lockstep prover behind bppp_rp_prove_batch: the host-algebra route (round 3) and the host wrapper of the
 // device-resident route (csrc/brpprove_dev.hip, round 4).  Both write the same bytes (tests/test_gpu_native_binary.py).
 #include <atomic>
-#include <chrono>
-#include <stdio.h>
 #include "rpprove_host.hpp"
 #include "rpprove_dev.hpp"
 
@@ -24,10 +22,7 @@ int prove_batch_binary(bppp_rp *rp, size_t batch, const uint64_t *amounts, const
   hipStream_t stream = ctx->stream;
   const Setup &st = rp->st;
   const size_t B = batch, nr = st.rds.size(), nlen = st.nlen, nlive = st.nlive, llen = 2, k = st.rounds, T = 1 + llen + nlen;
-  const bool timing = rp->opt.timing;
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t_last = timing ? now() : 0;
-  auto lap = [&](const char *what) { if (timing) { const double t = now(); fprintf(stderr, "[rp_prove binary] %-28s %8.2f ms\n", what, t - t_last); t_last = t; } };
+  LapTimer timer(rp->opt.timing, "[rp_prove binary]");
   { int rc = rpp_build_fixed_table(rp); if (rc) return rc; }
   if (!rp->commit_basis) { int rc = bppp_basis_create_device(ctx, rp->d_basis, T, 0, 4096, &rp->commit_basis); if (rc) return rc; }
   const size_t in_sc = B * nr * 3 * 32, in_pt = B * nr * 64, rows = B * T * 32;
@@ -84,7 +79,7 @@ int prove_batch_binary(bppp_rp *rp, size_t batch, const uint64_t *amounts, const
     }
   });
   if (failed >= 0) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: proof " + std::to_string((size_t)failed) + ": " + ps[failed].err);
-  lap("witness, digits (host)");
+  timer.lap("witness, digits (host)");
   BPPP_HIP(ctx, hipMemcpyAsync(d_in_sc, h_in_sc.data(), in_sc, hipMemcpyHostToDevice, stream));
   {
     int rc_ = rpp_commit_inputs(rp, d_in_sc, B * nr, d_in_pt); if (rc_) return rc_;      // the comb table when the handle has one, the fixed-base table otherwise
@@ -92,7 +87,7 @@ int prove_batch_binary(bppp_rp *rp, size_t batch, const uint64_t *amounts, const
   }
   { int rc = commit_rows(); if (rc) return rc; }            // dCom of every proof; synchronises the stream
   memcpy(c_d.data(), h_com.data(), B * 64);
-  lap("input commitments, dCom");
+  timer.lap("input commitments, dCom");
   // ---- (q, x, r), makePublicConsts, the blinding commitment (:179-189)
   const std::vector<bool> is_o = [&] { std::vector<bool> v_; for (const RangeData &rd : st.rds) v_.push_back(rd.output); return v_; }();
   rp_parallel(B, [&](size_t lo, size_t hi) {
@@ -137,10 +132,10 @@ int prove_batch_binary(bppp_rp *rp, size_t batch, const uint64_t *amounts, const
       put_row(b, p.bl0_sc, p.bl_bl, p.lin1, p.bls);
     }
   });
-  lap("q x r, public consts, bls (host)");
+  timer.lap("q x r, public consts, bls (host)");
   { int rc = commit_rows(); if (rc) return rc; }
   memcpy(c_bl.data(), h_com.data(), B * 64);
-  lap("blCom");
+  timer.lap("blCom");
   // ---- t and the argument's witness (:190-201)
   std::vector<uint64_t> a_s(B * 4), a_q(B * 4), a_nx(B * nlen * 4), a_lc(B * llen * 4), a_lx(B * llen * 4);
   rp_parallel(B, [&](size_t lo, size_t hi) {
@@ -170,57 +165,16 @@ int prove_batch_binary(bppp_rp *rp, size_t batch, const uint64_t *amounts, const
       p.bls.clear(); p.pub_nrm.clear(); p.ds.clear();
     }
   });
-  lap("t, argument witness (host)");
+  timer.lap("t, argument witness (host)");
   // ---- proveBPM in lockstep
+  // (measured and not kept for the norm-linear flavour: the fixed-basis mode over a comb table of the binary setup's 4099 points — 21.5 GB at
+  // c = 13 — takes the argument of 1024 64x64-bit proofs from 167 to 157 ms: its rounds are host round trips either way)
   std::vector<uint64_t> resp(B * (k ? k : 1) * 16), wn(B * st.fn * 4 + 4), wl(B * st.fl * 4 + 4);
-  if (st.flavour) {
-    int rc = ip_argument_lockstep(rp, B, k, a_s.data(), a_q.data(), a_nx.data(), a_lc.data(), a_lx.data(), [&](size_t b) -> PState & { return ps[b].tr; }, resp.data(),
-                                  wn.data(), wl.data());
-    if (rc) return rc;
-  } else {
-    // (measured and not kept: the fixed-basis mode over a comb table of the binary setup's 4099 points — 21.5 GB at c = 13 — takes the
-    // argument of 1024 64x64-bit proofs from 167 to 157 ms: its rounds are host round trips either way)
-    bppp_nlb *nlb = nullptr;
-    int rc = bppp_nlb_create(ctx, B, a_s.data(), rp->h_g.data(), a_q.data(), a_nx.data(), rp->h_G.data(), nlen, a_lc.data(), a_lx.data(), rp->h_H.data(), llen, &nlb);
-    if (rc) return rc;
-    std::vector<uint64_t> sX(B * 4), sR(B * 4), X(B * 8), R(B * 8), es(B * 4);
-    for (size_t round = 0; round < k && !rc; round++) {
-      rc = bppp_nlb_round_commit(nlb, sX.data(), X.data(), sR.data(), R.data());
-      if (rc) break;
-      rp_parallel(B, [&](size_t lo, size_t hi) {
-        for (size_t b = lo; b < hi; b++) {
-          const uint64_t *pts[2] = {&X[8 * b], &R[8 * b]};
-          U256 e;
-          oracle(rp->tag, ps[b].tr, pts, 2, 1, &e);
-          e.store(&es[4 * b]);
-          const size_t slot = k - 1 - round;                 // responses LAST round first (Bulletproof.hs:359)
-          memcpy(&resp[(b * k + slot) * 16], pts[0], 64); memcpy(&resp[(b * k + slot) * 16 + 8], pts[1], 64);
-        }
-      });
-      rc = bppp_nlb_round_collapse(nlb, es.data());
-    }
-    if (!rc) rc = bppp_nlb_get_witness(nlb, wn.data(), wl.data(), nullptr);
-    bppp_nlb_destroy(nlb);
-    if (rc) return rc;
-  }
-  lap("argument (lockstep)");
-  // ---- encodeProof': commitments file = the input commitments; proof file = final witness scalars, then blCom, dCom and the responses
-  const RpDims &D = rp->D;
-  rp_parallel(B, [&](size_t lo, size_t hi) {
-    std::vector<const uint64_t *> pts;
-    for (size_t b = lo; b < hi; b++) {
-      pts.assign(nr, nullptr);
-      for (size_t i = 0; i < nr; i++) pts[i] = &h_in_pt[(b * nr + i) * 8];
-      encode_points(coms_files + b * D.coms_bytes, pts.data(), nr);
-      uint8_t *pf = proof_files + b * D.proof_bytes;
-      for (size_t i = 0; i < st.fn; i++) put_field(pf + 32 * i, U256::load(&wn[(b * st.fn + i) * 4]));
-      for (size_t i = 0; i < st.fl; i++) put_field(pf + 32 * (st.fn + i), U256::load(&wl[(b * st.fl + i) * 4]));
-      pts.assign(2 + 2 * k, nullptr);
-      pts[0] = &c_bl[8 * b]; pts[1] = &c_d[8 * b];
-      for (size_t j = 0; j < 2 * k; j++) pts[2 + j] = &resp[(b * k) * 16 + 8 * j];
-      encode_points(pf + 32 * (st.fn + st.fl), pts.data(), 2 + 2 * k);
-    }
-  });
+  auto argument = st.flavour ? ip_argument_lockstep : nl_argument_lockstep;
+  { int rc = argument(rp, B, k, a_s.data(), a_q.data(), a_nx.data(), a_lc.data(), a_lx.data(), [&](size_t b) -> PState & { return ps[b].tr; }, resp.data(), wn.data(), wl.data());
+    if (rc) return rc; }
+  timer.lap("argument (lockstep)");
+  rpp_encode_files(rp, B, h_in_pt.data(), wn.data(), wl.data(), {c_bl.data(), c_d.data()}, resp.data(), coms_files, proof_files);
   return BPPP_OK;
 }
 
@@ -232,20 +186,10 @@ int prove_batch_binary_dev(bppp_rp *rp, size_t batch, const uint64_t *amounts, c
   hipSetDevice(ctx->device);
   const Setup &st = rp->st;
   const size_t B = batch, nr = st.rds.size(), nlive = st.nlive, k = st.rounds;
-  const bool timing = rp->opt.timing;
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t_last = timing ? now() : 0;
-  auto lap = [&](const char *what) { if (timing) { const double t = now(); fprintf(stderr, "[rp_prove binary] %-28s %8.2f ms\n", what, t - t_last); t_last = t; } };
+  LapTimer timer(rp->opt.timing, "[rp_prove binary]");
   // pinned staging, grow-only: [in_sc B nr 3 | input commitments B nr | bits B nlive]
   const size_t n_in_sc = B * nr * 12, n_in_pt = B * nr * 8;
-  const size_t pin_need = (n_in_sc + n_in_pt) * 8 + B * nlive + 64;
-  if (pin_need > rp->hpin_bytes) {
-    BPPP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (rp->hpin) BPPP_HIP(ctx, hipHostFree(rp->hpin));
-    rp->hpin = nullptr; rp->hpin_bytes = 0;
-    BPPP_HIP(ctx, hipHostMalloc(&rp->hpin, pin_need + pin_need / 8, hipHostMallocDefault));
-    rp->hpin_bytes = pin_need + pin_need / 8;
-  }
+  { int rc = rpp_ensure_hpin(rp, (n_in_sc + n_in_pt) * 8 + B * nlive + 64); if (rc) return rc; }
   uint64_t *h_in_sc = (uint64_t *)rp->hpin, *h_in_pt = h_in_sc + n_in_sc;
   uint8_t *bits = (uint8_t *)(h_in_pt + n_in_pt);
   std::atomic<int> failed{-1};
@@ -275,30 +219,14 @@ int prove_batch_binary_dev(bppp_rp *rp, size_t batch, const uint64_t *amounts, c
     }
   });
   if (failed >= 0) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: proof " + std::to_string(index_base + (size_t)failed) + ": " + errs[failed]);
-  lap("witness, digits (host)");
+  timer.lap("witness, digits (host)");
   std::vector<uint64_t> c_d(B * 8), c_bl(B * 8), resp(B * (k ? k : 1) * 16), wn(B * st.fn * 4 + 4), wl(B * st.fl * 4 + 4);
   BrpHostInputs in{B, h_in_sc, bits, rand_prefix, prefix_len, pub};
   BrpOutputs out{h_in_pt, c_d.data(), c_bl.data(), resp.data(), wn.data(), wl.data()};
   { int rc = brp_device_prove(rp, in, out); if (rc) return rc; }
-  lap("phases + argument (device)");
-  // encodeProof': commitments file = the input commitments; proof file = final witness scalars, then blCom, dCom and the responses
-  const RpDims &D = rp->D;
-  rp_parallel(B, [&](size_t lo, size_t hi) {
-    std::vector<const uint64_t *> pts;
-    for (size_t b = lo; b < hi; b++) {
-      pts.assign(nr, nullptr);
-      for (size_t i = 0; i < nr; i++) pts[i] = &h_in_pt[(b * nr + i) * 8];
-      encode_points(coms_files + b * D.coms_bytes, pts.data(), nr);
-      uint8_t *pf = proof_files + b * D.proof_bytes;
-      for (size_t i = 0; i < st.fn; i++) put_field(pf + 32 * i, U256::load(&wn[(b * st.fn + i) * 4]));
-      for (size_t i = 0; i < st.fl; i++) put_field(pf + 32 * (st.fn + i), U256::load(&wl[(b * st.fl + i) * 4]));
-      pts.assign(2 + 2 * k, nullptr);
-      pts[0] = &c_bl[8 * b]; pts[1] = &c_d[8 * b];
-      for (size_t j = 0; j < 2 * k; j++) pts[2 + j] = &resp[(b * k) * 16 + 8 * j];
-      encode_points(pf + 32 * (st.fn + st.fl), pts.data(), 2 + 2 * k);
-    }
-  });
-  lap("encode (host)");
+  timer.lap("phases + argument (device)");
+  rpp_encode_files(rp, B, h_in_pt, wn.data(), wl.data(), {c_bl.data(), c_d.data()}, resp.data(), coms_files, proof_files);
+  timer.lap("encode (host)");
   return BPPP_OK;
 }
 

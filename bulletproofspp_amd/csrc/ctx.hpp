@@ -85,6 +85,9 @@ void ctx_retain(bppp_ctx *ctx);
 void ctx_release(bppp_ctx *ctx);          // the last release tears the context down
 inline bool ctx_closed(const bppp_ctx *ctx) { return !ctx || ctx->closed.load(); }
 int ctx_aux(bppp_ctx *ctx);               // creates aux_stream and its two events if needed
+// nothing of a call is in flight once it has returned: both streams drained (the verifier's sliced uploads of host files run on the
+// second) and the runtime's last-error slot cleared; a no-op on a closed context
+void ctx_drain(bppp_ctx *ctx);
 int ensure_workspace(bppp_ctx *ctx, size_t bytes);
 int ensure_pinned(bppp_ctx *ctx, size_t bytes);
 int ensure_scratch(bppp_ctx *ctx, size_t bytes);

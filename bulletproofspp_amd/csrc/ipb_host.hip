@@ -148,4 +148,43 @@ int ip_argument_lockstep(bppp_rp *rp, size_t B, size_t k, const uint64_t *psv_in
   return BPPP_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ norm-linear flavour, lockstep
+// proveBPM (src/Bulletproof.hs:357-359) of the norm-linear argument for B proofs: the round commitments and collapses of csrc/nlb.hip on the
+// GPU, the oracle on the host cores.  In and out as ip_argument_lockstep (rr: makeNorm's q).  BPPP_RP_TIMING: commit / hash / collapse times.
+int nl_argument_lockstep(bppp_rp *rp, size_t B, size_t k, const uint64_t *psv_in, const uint64_t *rr, const uint64_t *nrm, const uint64_t *lc_in,
+                         const uint64_t *lx_in, const std::function<PState &(size_t)> &tr_of, uint64_t *resp, uint64_t *wn, uint64_t *wl) {
+  const Setup &st = rp->st;
+  bppp_nlb *nlb = nullptr;
+  int rc = bppp_nlb_create(rp->ctx, B, psv_in, rp->h_g.data(), rr, nrm, rp->h_G.data(), st.nlen, lc_in, lx_in, rp->h_H.data(), st.llen, &nlb);
+  if (rc) return rc;
+  double t_commit = 0, t_hash = 0, t_collapse = 0;
+  std::vector<uint64_t> sX(B * 4), sR(B * 4), X(B * 8), R(B * 8), es(B * 4);
+  for (size_t round = 0; round < k && !rc; round++) {
+    const double ta = LapTimer::ms();
+    rc = bppp_nlb_round_commit(nlb, sX.data(), X.data(), sR.data(), R.data());
+    if (rc) break;
+    const double tb = LapTimer::ms();
+    t_commit += tb - ta;
+    rp_parallel(B, [&](size_t lo, size_t hi) {
+      for (size_t b = lo; b < hi; b++) {
+        const uint64_t *pts[2] = {&X[8 * b], &R[8 * b]};
+        U256 e;
+        oracle(rp->tag, tr_of(b), pts, 2, 1, &e);
+        e.store(&es[4 * b]);
+        const size_t slot = k - 1 - round;                 // responses LAST round first (:359)
+        memcpy(&resp[(b * k + slot) * 16], pts[0], 64); memcpy(&resp[(b * k + slot) * 16 + 8], pts[1], 64);
+      }
+    });
+    const double tc = LapTimer::ms();
+    t_hash += tc - tb;
+    rc = bppp_nlb_round_collapse(nlb, es.data());
+    t_collapse += LapTimer::ms() - tc;
+  }
+  if (rp->opt.timing)
+    fprintf(stderr, "%s argument: commits %.2f ms, hashing %.2f ms, collapses %.2f ms\n", st.kind ? "[rp_prove binary]" : "[rp_prove]", t_commit, t_hash, t_collapse);
+  if (!rc) rc = bppp_nlb_get_witness(nlb, wn, wl, nullptr);
+  bppp_nlb_destroy(nlb);
+  return rc;
+}
+
 }  // namespace bppp

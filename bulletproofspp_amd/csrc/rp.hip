@@ -23,7 +23,6 @@
 // The same file holds the setup handle (`bppp_rp`: ranges, layout, basis resident in HBM) and, further down, the batch prover.
 #include <string.h>
 #include <string>
-#include <chrono>
 #include <thread>
 #include <vector>
 #include "ctx.hpp"
@@ -809,93 +808,12 @@ void host_verifier_oracle(const bppp_rp *rp, const uint8_t *text, const uint32_t
   }
 }
 }  // namespace
-extern "C" {
-
-int bppp_rp_verify_batch_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_proof_files, const uint8_t seed[32], int *accept,
-                                uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
-  return bppp_rp_verify_shard_device(rp, batch, 0, d_coms_files, d_proof_files, seed, accept, proof_status, challenges_out, combined_xy);
-}
-
-static int rp_verify_shard_run(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const uint8_t seed[32],
-                               int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy, const uint32_t *d_pub);
-int bppp_rp_verify_shard_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const uint8_t seed[32],
-                                int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
-  return bppp_rp_verify_shard_pub_device(rp, batch, index_offset, d_coms_files, d_proof_files, nullptr, seed, accept, proof_status, challenges_out, combined_xy);
-}
-int bppp_rp_verify_shard_pub_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const void *d_public_amounts,
-                                    const uint8_t seed[32], int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
-  if (!rp || !accept) return BPPP_ERR_ARG;
-  const uint32_t *d_pub = nullptr;
-  int rc = BPPP_OK;
-  if (d_public_amounts && batch) {
-    if (ctx_closed(rp->ctx)) return BPPP_ERR_ARG;
-    *accept = 0;
-    hipSetDevice(rp->ctx->device);
-    if ((rc = rp_stage_public(rp, batch, nullptr, d_public_amounts, &d_pub))) return rc;
-  }
-  rc = rp_verify_shard_run(rp, batch, index_offset, d_coms_files, d_proof_files, seed, accept, proof_status, challenges_out, combined_xy, d_pub);
-  // A failed call may leave work queued on either stream that still reads the caller's buffers (the sliced uploads from host files run on
-  // the context's second stream): nothing of this call is in flight once it has returned, whatever the outcome.
-  if (rc && rp->ctx && !ctx_closed(rp->ctx)) {
-    hipStreamSynchronize(rp->ctx->stream);
-    if (rp->ctx->aux_stream) hipStreamSynchronize(rp->ctx->aux_stream);
-    (void)hipGetLastError();
-  }
-  return rc;
-}
-static int rp_verify_shard_run(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const uint8_t seed[32],
-                               int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy, const uint32_t *d_pub) {
-  bppp_ctx *ctx = rp->ctx;
-  if (ctx_closed(ctx)) return BPPP_ERR_ARG;
-  *accept = 0;
-  rp->n_combined = rp->n_each = 0;
-  if (combined_xy) memset(combined_xy, 0, 64);
-  if (!batch) { *accept = 1; return BPPP_OK; }
-  if (!d_coms_files || !d_proof_files || !seed || batch >= (1u << 22)) return fail(ctx, BPPP_ERR_ARG, "rp_verify_batch: bad arguments");
-  RpVerifyArrays A;
-  int rc = rp_verify_prepare(rp, batch, index_offset, d_coms_files, d_proof_files, seed, A, d_pub);
-  if (rc) return rc;
-  hipStream_t st = ctx->stream;
-  const bppp_rps::Setup &S = rp->st;
-  const RpDims D = rp->D;
-  const size_t B = batch, k = S.rounds;
-  uint64_t out_xy[8];
-  rc = rp_verify_combine(rp, A, 0, B, out_xy);
-  if (rc) return rc;
-  // decode failures (an x with no point on the curve): Nothing in the reference (decodeCommitments, Encoding.hs:119-128).  The batch-wide
-  // flag reached pinned memory long before the MSM drained the stream; the per-proof words are fetched only when somebody needs them
-  const bool any_bad = rp->hflag[0] != 0;
-  std::vector<uint32_t> hbad(proof_status ? B : 0);
-  // async copies below target host vectors: whatever path leaves this function, the stream is drained before they are destroyed
-  struct StreamDrain { hipStream_t s; ~StreamDrain() { hipStreamSynchronize(s); } };
-  StreamDrain drain{st};
-  if (proof_status) BPPP_HIP(ctx, hipMemcpyAsync(hbad.data(), A.bad, B * 4, hipMemcpyDeviceToHost, st));
-  if (challenges_out) {                        // [batch][nch + k]: the range-proof layer's challenges (Binary: q, x, r from slots 0-2, t from slot 6), then the rounds'
-    const size_t nch = D.nch, row = (nch + k) * 32;
-    if (S.kind == 0) BPPP_HIP(ctx, hipMemcpy2DAsync(challenges_out, row, A.ch, 7 * 32, 7 * 32, B, hipMemcpyDeviceToHost, st));
-    else {
-      BPPP_HIP(ctx, hipMemcpy2DAsync(challenges_out, row, A.ch, 7 * 32, 3 * 32, B, hipMemcpyDeviceToHost, st));
-      BPPP_HIP(ctx, hipMemcpy2DAsync(challenges_out + 12, row, A.ch + 6 * 8, 7 * 32, 32, B, hipMemcpyDeviceToHost, st));
-    }
-    if (k) BPPP_HIP(ctx, hipMemcpy2DAsync(challenges_out + 4 * nch, row, A.es, k * 32, k * 32, B, hipMemcpyDeviceToHost, st));
-  }
-  if (proof_status || challenges_out) BPPP_HIP(ctx, hipStreamSynchronize(st));
-  const bool whole = rp_point_is_inf(out_xy);
-  if (combined_xy) memcpy(combined_xy, out_xy, 64);
-  *accept = (whole && !any_bad) ? 1 : 0;
-  if (!proof_status) return BPPP_OK;
-  for (size_t b = 0; b < B; b++) proof_status[b] = hbad[b] ? BPPP_RP_MALFORMED : BPPP_RP_VALID;
-  if (whole) return BPPP_OK;
-  return rp_find_culprits(rp, A, true, proof_status);
-}
-
-}  // extern "C"
 
 namespace bppp {
 // decodeProof, the transcript hashing, the public scalars and the weights rho of one batch: everything of the verification but the
 // argument's combination (see rp_internal.hpp)
-int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const uint8_t seed[32],
-                      RpVerifyArrays &A, const uint32_t *d_pub) {
+int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const RpFiles &files, const uint8_t seed[32], RpVerifyArrays &A,
+                      const uint32_t *d_pub) {
   bppp_ctx *ctx = rp->ctx;
   hipSetDevice(ctx->device);
   hipStream_t st = ctx->stream;
@@ -920,12 +838,11 @@ int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const vo
   BPPP_HIP(ctx, hipMemsetAsync(bad, 0, (B + 1) * 4, st));
   BPPP_HIP(ctx, hipMemsetAsync(pub_lin_x, 0, B * llen * 32, st));       // the public linear vector of these proofs is zero (TypedReciprocal.hs:466)
   BPPP_HIP(ctx, hipMemcpyAsync(d_seed, seed, 32, hipMemcpyHostToDevice, st));
-  // decodeProof.  From host buffers (bppp_rp_verify_batch left them in rp->host_*; the device pointers are then its staging area): the
-  // files go up in four slices, each followed by its decode launches, so the square roots of slice i run under the upload of slice
-  // i + 1 (a pageable copy keeps the HOST busy staging, not the stream)
+  // decodeProof.  From host files (the device pointers are then the handle's staging area, rp_stage_files): the files go up in four
+  // slices, each followed by its decode launches, so the square roots of slice i run under the upload of slice i + 1 (a pageable copy
+  // keeps the HOST busy staging, not the stream)
   {
-    const uint8_t *hc = rp->host_coms, *hp = rp->host_proofs;
-    rp->host_coms = rp->host_proofs = nullptr;
+    const uint8_t *hc = files.h_coms, *hp = files.h_proofs;
     // how many: a slice's decode launch is latency-bound (one square-root chain, ~0.18 ms for 1024 proofs against 0.53 ms for all 4096),
     // so slices cost decode time; pageable files arrive at the host's staging rate (0.7 ms per 4096 proofs) and four slices hide most of
     // it, page-locked ones (bppp_host_alloc) arrive in 0.25 ms and two are enough
@@ -938,7 +855,7 @@ int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const vo
     }
     for (size_t sl = 0; sl < nslices; sl++) {
       const size_t b0 = B * sl / nslices, b1 = B * (sl + 1) / nslices, nb = b1 - b0;
-      const uint8_t *dc = (const uint8_t *)d_coms_files + b0 * (size_t)D.coms_bytes, *dp = (const uint8_t *)d_proof_files + b0 * (size_t)D.proof_bytes;
+      const uint8_t *dc = (const uint8_t *)files.d_coms + b0 * (size_t)D.coms_bytes, *dp = (const uint8_t *)files.d_proofs + b0 * (size_t)D.proof_bytes;
       if (hc) {
         // the copies go on the context's second stream (a copy on `st` would queue behind the previous slice's kernels), the kernels wait
         // for their slice's event
@@ -972,16 +889,13 @@ int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const vo
     uint8_t *htext = (uint8_t *)rp->hstage;
     uint32_t *hoff = (uint32_t *)(htext + tbytes);
     uint64_t *hch = (uint64_t *)(htext + tbytes + obytes), *hes = hch + n_hch;
-    const bool timing = rp->opt.timing;
-    auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t_last = timing ? now() : 0;
-    auto lap = [&](const char *what) { if (timing) { const double t = now(); fprintf(stderr, "[rp_verify] %-24s %7.1f us\n", what, t - t_last); t_last = t; } };
+    LapTimer timer(rp->opt.timing, "[rp_verify]", true);
     if (rp_text_lds_bytes(D) <= 64 * 1024) k_rp_text_lds<<<dim3((unsigned)B), dim3(256), rp_text_lds_bytes(D), st>>>(D, init_pts, resp_pts, text, text_off);
     else k_rp_text<<<dim3((unsigned)B), dim3(256), (npts + 1) * 4, st>>>(D, init_pts, resp_pts, text, text_off);
     BPPP_HIP(ctx, hipMemcpyAsync(hoff, text_off, B * (npts + 1) * 4, hipMemcpyDeviceToHost, st));
     BPPP_HIP(ctx, hipMemcpyAsync(htext, text, B * (size_t)D.text_stride, hipMemcpyDeviceToHost, st));
     BPPP_HIP(ctx, hipStreamSynchronize(st));
-    lap("decode + download");
+    timer.lap("decode + download");
     // the seven challenges of verifyTRRPM first: k_trrp_public needs only those and runs while the host hashes the argument's rounds
     // one proof per item: the calling thread alone for one proof, else with the handle's pool (a std::thread per proof costs more than its 36 us of hashing)
     if (B > 1 && !rp->pool) rp->pool = new bppp::HostPool((unsigned)std::min<size_t>(host_oracle_max, 16) - 1);
@@ -990,13 +904,13 @@ int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const vo
       if (B == 1) f(0); else rp->pool->run(B, f);
     };
     all(0);
-    lap("host oracle, part 0");
+    timer.lap("host oracle, part 0");
     BPPP_HIP(ctx, hipMemcpyAsync(ch, hch, B * 7 * 32, hipMemcpyHostToDevice, st));
     int rc0 = S.kind ? brp_public_device(rp, B, ch, q, sp, pub_norm, pub_lin_c, init_sc, d_pub) : trrp_public_run(rp->tabs, B, ch, q, sp, pub_norm, pub_lin_c, init_sc, d_pub);
     if (rc0) return rc0;
-    lap("launch of the scalars");
+    timer.lap("launch of the scalars");
     all(1);
-    lap("host oracle, part 1");
+    timer.lap("host oracle, part 1");
     if (k) BPPP_HIP(ctx, hipMemcpyAsync(es, hes, B * k * 32, hipMemcpyHostToDevice, st));       // (pinned staging: the next call's downloads are ordered behind this copy on the stream)
   } else {
     // transcript text, then the hashing in two halves: the seven challenges of verifyTRRPM on the call's stream, followed there by
@@ -1084,10 +998,9 @@ int rp_find_culprits(bppp_rp *rp, const RpVerifyArrays &A, bool known_bad, uint3
   }
   return BPPP_OK;
 }
-}  // namespace bppp
 
-// the host-buffer entry points' grow-only device staging of one handle: coms then proofs (256-byte aligned), for `batch` proofs
-int rp_ensure_stage(bppp_rp *rp, size_t batch) {
+// the host-file entry points' grow-only device staging of one handle: coms then proofs (256-byte aligned), for `batch` proofs
+int rp_stage_files(bppp_rp *rp, size_t batch, const void *h_coms, const void *h_proofs, RpFiles &out) {
   bppp_ctx *ctx = rp->ctx;
   const size_t cb = batch * (size_t)rp->D.coms_bytes, pb = batch * (size_t)rp->D.proof_bytes;
   const size_t cbp = (cb + 255) & ~(size_t)255;
@@ -1098,8 +1011,77 @@ int rp_ensure_stage(bppp_rp *rp, size_t batch) {
     BPPP_HIP(ctx, hipMalloc(&rp->stage, cbp + pb + 256));
     rp->stage_bytes = cbp + pb + 256;
   }
+  out = RpFiles{rp->stage, (char *)rp->stage + cbp, (const uint8_t *)h_coms, (const uint8_t *)h_proofs};
   return BPPP_OK;
 }
+
+int rp_verify_start(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *coms, const void *proofs, const void *pub, bool host, const uint8_t seed[32],
+                    RpVerifyArrays &A) {
+  hipSetDevice(rp->ctx->device);
+  const uint32_t *d_pub = nullptr;
+  RpFiles files{coms, proofs};
+  int rc = pub ? rp_stage_public(rp, batch, host ? (const uint64_t *)pub : nullptr, host ? nullptr : pub, &d_pub) : BPPP_OK;
+  if (!rc && host) rc = rp_stage_files(rp, batch, coms, proofs, files);
+  return rc ? rc : rp_verify_prepare(rp, batch, index_offset, files, seed, A, d_pub);
+}
+
+// verifyBPM's combination of a prepared batch, the verdict and, as asked, the per-proof statuses and challenges
+static int rp_verify_decide(bppp_rp *rp, const RpVerifyArrays &A, int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
+  bppp_ctx *ctx = rp->ctx;
+  hipStream_t st = ctx->stream;
+  const bppp_rps::Setup &S = rp->st;
+  const RpDims D = rp->D;
+  const size_t B = A.batch, k = S.rounds;
+  uint64_t out_xy[8];
+  int rc = rp_verify_combine(rp, A, 0, B, out_xy);
+  if (rc) return rc;
+  // decode failures (an x with no point on the curve): Nothing in the reference (decodeCommitments, Encoding.hs:119-128).  The batch-wide
+  // flag reached pinned memory long before the MSM drained the stream; the per-proof words are fetched only when somebody needs them
+  const bool any_bad = rp->hflag[0] != 0;
+  std::vector<uint32_t> hbad(proof_status ? B : 0);
+  // async copies below target host vectors: whatever path leaves this function, the stream is drained before they are destroyed
+  struct StreamDrain { hipStream_t s; ~StreamDrain() { hipStreamSynchronize(s); } };
+  StreamDrain drain{st};
+  if (proof_status) BPPP_HIP(ctx, hipMemcpyAsync(hbad.data(), A.bad, B * 4, hipMemcpyDeviceToHost, st));
+  if (challenges_out) {                        // [batch][nch + k]: the range-proof layer's challenges (Binary: q, x, r from slots 0-2, t from slot 6), then the rounds'
+    const size_t nch = D.nch, row = (nch + k) * 32;
+    if (S.kind == 0) BPPP_HIP(ctx, hipMemcpy2DAsync(challenges_out, row, A.ch, 7 * 32, 7 * 32, B, hipMemcpyDeviceToHost, st));
+    else {
+      BPPP_HIP(ctx, hipMemcpy2DAsync(challenges_out, row, A.ch, 7 * 32, 3 * 32, B, hipMemcpyDeviceToHost, st));
+      BPPP_HIP(ctx, hipMemcpy2DAsync(challenges_out + 12, row, A.ch + 6 * 8, 7 * 32, 32, B, hipMemcpyDeviceToHost, st));
+    }
+    if (k) BPPP_HIP(ctx, hipMemcpy2DAsync(challenges_out + 4 * nch, row, A.es, k * 32, k * 32, B, hipMemcpyDeviceToHost, st));
+  }
+  if (proof_status || challenges_out) BPPP_HIP(ctx, hipStreamSynchronize(st));
+  const bool whole = rp_point_is_inf(out_xy);
+  if (combined_xy) memcpy(combined_xy, out_xy, 64);
+  *accept = (whole && !any_bad) ? 1 : 0;
+  if (!proof_status) return BPPP_OK;
+  for (size_t b = 0; b < B; b++) proof_status[b] = hbad[b] ? BPPP_RP_MALFORMED : BPPP_RP_VALID;
+  if (whole) return BPPP_OK;
+  return rp_find_culprits(rp, A, true, proof_status);
+}
+
+// the batch / shard verifier behind every bppp_rp_verify_{batch,shard}* entry point: proofs at job positions [index_offset, index_offset +
+// batch), files and public amounts (NULL: the handle's own) on the host (`host`) or in HBM; nothing of the call is in flight once it returns
+static int rp_verify_batch_impl(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *coms, const void *proofs, const void *pub, bool host,
+                                const uint8_t seed[32], int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
+  if (!rp || !accept) return BPPP_ERR_ARG;
+  bppp_ctx *ctx = rp->ctx;
+  if (ctx_closed(ctx)) return BPPP_ERR_ARG;
+  *accept = 0;
+  rp->n_combined = rp->n_each = 0;
+  if (combined_xy) memset(combined_xy, 0, 64);
+  if (!batch) { *accept = 1; return BPPP_OK; }
+  if (host && (!coms || !proofs)) return fail(ctx, BPPP_ERR_ARG, "rp_verify_batch: null input");
+  if (!coms || !proofs || !seed || batch >= (1u << 22)) return fail(ctx, BPPP_ERR_ARG, "rp_verify_batch: bad arguments");
+  RpVerifyArrays A;
+  int rc = rp_verify_start(rp, batch, index_offset, coms, proofs, pub, host, seed, A);
+  if (!rc) rc = rp_verify_decide(rp, A, accept, proof_status, challenges_out, combined_xy);
+  if (rc || host) ctx_drain(ctx);          // (host files: the sliced uploads read them from the second stream)
+  return rc;
+}
+}  // namespace bppp
 
 size_t rp_public_count(const bppp_rp *rp) {
   if (rp->st.kind == 1) return rp->st.conserve ? 1 : 0;
@@ -1166,34 +1148,27 @@ int bppp_rp_public_count(const bppp_rp *rp, size_t *n) {
 
 int bppp_rp_verify_batch(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint8_t *proof_files, const uint8_t seed[32], int *accept,
                          uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
-  return bppp_rp_verify_batch_pub(rp, batch, coms_files, proof_files, nullptr, seed, accept, proof_status, challenges_out, combined_xy);
+  return rp_verify_batch_impl(rp, batch, 0, coms_files, proof_files, nullptr, true, seed, accept, proof_status, challenges_out, combined_xy);
 }
-
-int bppp_rp_verify_batch_pub_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_proof_files, const void *d_public_amounts, const uint8_t seed[32],
-                                    int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
-  return bppp_rp_verify_shard_pub_device(rp, batch, 0, d_coms_files, d_proof_files, d_public_amounts, seed, accept, proof_status, challenges_out, combined_xy);
-}
-
 int bppp_rp_verify_batch_pub(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint8_t *proof_files, const uint64_t *public_amounts, const uint8_t seed[32],
                              int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
-  if (!rp || !accept) return BPPP_ERR_ARG;
-  bppp_ctx *ctx = rp->ctx;
-  if (ctx_closed(ctx)) return BPPP_ERR_ARG;
-  if (!batch) { *accept = 1; return BPPP_OK; }
-  if (!coms_files || !proof_files) return fail(ctx, BPPP_ERR_ARG, "rp_verify_batch: null input");
-  hipSetDevice(ctx->device);
-  const uint32_t *d_pub = nullptr;
-  if (public_amounts) { *accept = 0; int rc0 = rp_stage_public(rp, batch, public_amounts, nullptr, &d_pub); if (rc0) return rc0; }
-  { int rc0 = rp_ensure_stage(rp, batch); if (rc0) return rc0; }
-  void *stage = rp->stage;
-  const size_t cbp = (batch * (size_t)rp->D.coms_bytes + 255) & ~(size_t)255;
-  rp->host_coms = coms_files; rp->host_proofs = proof_files;          // uploaded in slices by the decode stage of the call below
-  int rc = rp_verify_shard_run(rp, batch, 0, stage, (char *)stage + cbp, seed, accept, proof_status, challenges_out, combined_xy, d_pub);
-  if (rc) { hipStreamSynchronize(ctx->stream); if (ctx->aux_stream) hipStreamSynchronize(ctx->aux_stream); (void)hipGetLastError(); }
-  rp->host_coms = rp->host_proofs = nullptr;
-  hipStreamSynchronize(ctx->stream);
-  if (ctx->aux_stream) hipStreamSynchronize(ctx->aux_stream);     // the sliced uploads read the caller's files from there
-  return rc;
+  return rp_verify_batch_impl(rp, batch, 0, coms_files, proof_files, public_amounts, true, seed, accept, proof_status, challenges_out, combined_xy);
+}
+int bppp_rp_verify_batch_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_proof_files, const uint8_t seed[32], int *accept,
+                                uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
+  return rp_verify_batch_impl(rp, batch, 0, d_coms_files, d_proof_files, nullptr, false, seed, accept, proof_status, challenges_out, combined_xy);
+}
+int bppp_rp_verify_batch_pub_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_proof_files, const void *d_public_amounts, const uint8_t seed[32],
+                                    int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
+  return rp_verify_batch_impl(rp, batch, 0, d_coms_files, d_proof_files, d_public_amounts, false, seed, accept, proof_status, challenges_out, combined_xy);
+}
+int bppp_rp_verify_shard_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const uint8_t seed[32],
+                                int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
+  return rp_verify_batch_impl(rp, batch, index_offset, d_coms_files, d_proof_files, nullptr, false, seed, accept, proof_status, challenges_out, combined_xy);
+}
+int bppp_rp_verify_shard_pub_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const void *d_public_amounts,
+                                    const uint8_t seed[32], int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
+  return rp_verify_batch_impl(rp, batch, index_offset, d_coms_files, d_proof_files, d_public_amounts, false, seed, accept, proof_status, challenges_out, combined_xy);
 }
 
 }  // extern "C"

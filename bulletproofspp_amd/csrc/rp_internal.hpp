@@ -1,6 +1,8 @@
 // rp_internal.hpp — declarations shared by the two halves of the range-proof layer (csrc/rp.hip: setup + batch verifier,
 // csrc/rpprove.hip: batch prover).
 #pragma once
+#include <stdio.h>
+#include <chrono>
 #include <string>
 #include <thread>
 #include <vector>
@@ -42,6 +44,21 @@ template <class F> static void rp_parallel(size_t n, F f) {
   for (size_t t = 0; t < nt; t++) th.emplace_back([=] { f(n * t / nt, n * (t + 1) / nt); });
   for (auto &x : th) x.join();
 }
+
+// BPPP_RP_TIMING's stderr lap timer: lap(what) prints the wall time since the previous lap (or since the timer was made) after `prefix`,
+// in milliseconds, or in microseconds with `us`
+struct LapTimer {
+  bool on; const char *prefix; bool us; double last;
+  static double ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+  LapTimer(bool on_, const char *prefix_, bool us_ = false) : on(on_), prefix(prefix_), us(us_), last(on_ ? ms() : 0) {}
+  void lap(const char *what) {
+    if (!on) return;
+    const double t = ms();
+    if (us) fprintf(stderr, "%s %-24s %7.1f us\n", prefix, what, 1000 * (t - last));
+    else fprintf(stderr, "%s %-28s %8.2f ms\n", prefix, what, t - last);
+    last = t;
+  }
+};
 
 int msm_run(bppp_ctx *, const void *, const void *, size_t, size_t, int, int, uint64_t *);
 // bppp_{nl,ip}_verify_batch_device with the validation of untrusted inputs optional (csrc/nlbatch.hip)
@@ -135,7 +152,6 @@ struct bppp_rp {
   // grow-only verifier workspace and the staging buffer of the host-buffer entry point
   bppp::HostPool *pool = nullptr;                // workers of the host oracle (batches of 2 .. host_oracle_verify proofs), made on first use
   hipEvent_t slice_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // one per upload slice of bppp_rp_verify_batch
-  const uint8_t *host_coms = nullptr, *host_proofs = nullptr;   // set by bppp_rp_verify_batch around its call of the device entry point: files still on the host
   uint64_t *hstage = nullptr; size_t hstage_bytes = 0;   // pinned, grow-only: the host oracle's downloads and uploads (a pageable target makes every async copy a blocking one)
   uint32_t *hflag = nullptr;                     // pinned: the verifier's "some proof did not decode" word, copied out while the batch is still in flight
   void *work = nullptr; size_t work_bytes = 0;
@@ -161,7 +177,6 @@ int rp_upload_public(bppp_rp *rp, const uint64_t *canon, size_t words, const uin
 int rp_stage_public(bppp_rp *rp, size_t batch, const uint64_t *h_in, const void *d_in, const uint32_t **d_out);
 
 int rp_ensure_twin(bppp_rp *rp);      // csrc/rp.hip
-int rp_ensure_stage(bppp_rp *rp, size_t batch);   // csrc/rp.hip: rp->stage holds `batch` files (coms, then proofs 256-byte aligned)
 
 namespace bppp {
 // The verifier's per-proof arrays of one prepared batch, carved from the handle's rp->work (csrc/rp.hip).  Every array is [batch][...],
@@ -170,12 +185,21 @@ struct RpVerifyArrays {
   size_t batch;
   uint32_t *init_pts, *resp_pts, *wit_norm, *wit_lin, *ch, *es, *rho, *q, *sp, *pub_norm, *pub_lin_c, *pub_lin_x, *init_sc, *bad;
 };
+// the files of one verification: in HBM, or still on the host (h_coms / h_proofs; d_coms / d_proofs are then the handle's staging buffer,
+// which the decode stage of rp_verify_prepare fills in slices)
+struct RpFiles { const void *d_coms, *d_proofs; const uint8_t *h_coms = nullptr, *h_proofs = nullptr; };
+// the host-file entry points' staging: rp->stage grown to `batch` files (coms, then proofs 256-byte aligned), `out` the host files over it
+int rp_stage_files(bppp_rp *rp, size_t batch, const void *h_coms, const void *h_proofs, RpFiles &out);
+// a single-handle verify entry point after its argument checks: the public amounts (NULL: the handle's own) and the files, both on the
+// host (`host`) or in HBM, staged, then rp_verify_prepare.  The caller drains the context (ctx_drain) on failure and after host files.
+int rp_verify_start(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *coms, const void *proofs, const void *pub, bool host, const uint8_t seed[32],
+                    RpVerifyArrays &A);
 // decodeProof, the transcript hashing (device or host oracle, as the handle chooses), the public scalars and the weights rho of the
 // proofs at job positions [index_offset, index_offset + batch): everything of the verification but the argument's combination.  Queued
 // on the context's stream; bad[b] marks a proof that did not decode and rp->hflag[0] receives "some proof did not" (read it once the
 // stream has drained).  The arrays stay valid until the handle's next verification.
 // d_pub: NULL (the handle's public amounts) or [batch][public_count] canonical scalars in HBM (rp_upload_public)
-int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms, const void *d_proofs, const uint8_t seed[32], RpVerifyArrays &A,
+int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const RpFiles &files, const uint8_t seed[32], RpVerifyArrays &A,
                       const uint32_t *d_pub = nullptr);
 // verifyBPM's combination of proofs [lo, lo + n) of a prepared batch: one MSM, returns with the stream drained
 int rp_verify_combine(bppp_rp *rp, const RpVerifyArrays &A, size_t lo, size_t n, uint64_t out_xy[8]);

@@ -112,63 +112,38 @@ using namespace bppp;
 
 extern "C" {
 
-static int rp_verify_each_run(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_proof_files, uint32_t *proof_status, uint64_t *proof_xy,
-                              const uint32_t *d_pub) {
+// the per-proof verifier behind every bppp_rp_verify_each* entry point: files and public amounts (NULL: the handle's own) on the host
+// (`host`) or in HBM; nothing of the call is in flight once it returns
+static int rp_verify_each_impl(bppp_rp *rp, size_t batch, const void *coms, const void *proofs, const void *pub, bool host, uint32_t *proof_status,
+                               uint64_t *proof_xy) {
+  if (!rp || !proof_status) return BPPP_ERR_ARG;
   bppp_ctx *ctx = rp->ctx;
+  if (ctx_closed(ctx)) return BPPP_ERR_ARG;
   rp->n_combined = rp->n_each = 0;
   if (!batch) return BPPP_OK;
-  if (!d_coms_files || !d_proof_files || batch >= (1u << 22)) return fail(ctx, BPPP_ERR_ARG, "rp_verify_each: bad arguments");
+  if (host && (!coms || !proofs)) return fail(ctx, BPPP_ERR_ARG, "rp_verify_each: null input");
+  if (!coms || !proofs || batch >= (1u << 22)) return fail(ctx, BPPP_ERR_ARG, "rp_verify_each: bad arguments");
   const uint8_t seed[32] = {0};                    // the prepared weights rho are not used
   RpVerifyArrays A;
-  int rc = rp_verify_prepare(rp, batch, 0, d_coms_files, d_proof_files, seed, A, d_pub);
-  if (rc) return rc;
-  return rp_each_pass(rp, A, proof_status, proof_xy);
-}
-
-int bppp_rp_verify_each_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_proof_files, uint32_t *proof_status, uint64_t *proof_xy) {
-  return bppp_rp_verify_each_pub_device(rp, batch, d_coms_files, d_proof_files, nullptr, proof_status, proof_xy);
-}
-
-int bppp_rp_verify_each_pub_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_proof_files, const void *d_public_amounts,
-                                   uint32_t *proof_status, uint64_t *proof_xy) {
-  if (!rp || !proof_status) return BPPP_ERR_ARG;
-  if (ctx_closed(rp->ctx)) return BPPP_ERR_ARG;
-  hipSetDevice(rp->ctx->device);
-  const uint32_t *d_pub = nullptr;
-  int rc = (d_public_amounts && batch) ? rp_stage_public(rp, batch, nullptr, d_public_amounts, &d_pub) : BPPP_OK;
-  if (!rc) rc = rp_verify_each_run(rp, batch, d_coms_files, d_proof_files, proof_status, proof_xy, d_pub);
-  if (rc && !ctx_closed(rp->ctx)) {                // nothing of a failed call stays in flight (as bppp_rp_verify_shard_device)
-    hipStreamSynchronize(rp->ctx->stream);
-    if (rp->ctx->aux_stream) hipStreamSynchronize(rp->ctx->aux_stream);
-    (void)hipGetLastError();
-  }
+  int rc = rp_verify_start(rp, batch, 0, coms, proofs, pub, host, seed, A);
+  if (!rc) rc = rp_each_pass(rp, A, proof_status, proof_xy);
+  if (rc || host) ctx_drain(ctx);
   return rc;
 }
 
 int bppp_rp_verify_each(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint8_t *proof_files, uint32_t *proof_status, uint64_t *proof_xy) {
-  return bppp_rp_verify_each_pub(rp, batch, coms_files, proof_files, nullptr, proof_status, proof_xy);
+  return rp_verify_each_impl(rp, batch, coms_files, proof_files, nullptr, true, proof_status, proof_xy);
 }
-
 int bppp_rp_verify_each_pub(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint8_t *proof_files, const uint64_t *public_amounts, uint32_t *proof_status,
                             uint64_t *proof_xy) {
-  if (!rp || !proof_status) return BPPP_ERR_ARG;
-  bppp_ctx *ctx = rp->ctx;
-  if (ctx_closed(ctx)) return BPPP_ERR_ARG;
-  if (!batch) { rp->n_combined = rp->n_each = 0; return BPPP_OK; }
-  if (!coms_files || !proof_files) return fail(ctx, BPPP_ERR_ARG, "rp_verify_each: null input");
-  hipSetDevice(ctx->device);
-  const uint32_t *d_pub = nullptr;
-  if (public_amounts) { int rc0 = rp_stage_public(rp, batch, public_amounts, nullptr, &d_pub); if (rc0) return rc0; }
-  { int rc0 = rp_ensure_stage(rp, batch); if (rc0) return rc0; }
-  void *stage = rp->stage;
-  const size_t cbp = (batch * (size_t)rp->D.coms_bytes + 255) & ~(size_t)255;
-  rp->host_coms = coms_files; rp->host_proofs = proof_files;          // uploaded in slices by the decode stage of rp_verify_prepare
-  int rc = rp_verify_each_run(rp, batch, stage, (char *)stage + cbp, proof_status, proof_xy, d_pub);
-  if (rc) { hipStreamSynchronize(ctx->stream); if (ctx->aux_stream) hipStreamSynchronize(ctx->aux_stream); (void)hipGetLastError(); }
-  rp->host_coms = rp->host_proofs = nullptr;
-  hipStreamSynchronize(ctx->stream);
-  if (ctx->aux_stream) hipStreamSynchronize(ctx->aux_stream);
-  return rc;
+  return rp_verify_each_impl(rp, batch, coms_files, proof_files, public_amounts, true, proof_status, proof_xy);
+}
+int bppp_rp_verify_each_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_proof_files, uint32_t *proof_status, uint64_t *proof_xy) {
+  return rp_verify_each_impl(rp, batch, d_coms_files, d_proof_files, nullptr, false, proof_status, proof_xy);
+}
+int bppp_rp_verify_each_pub_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_proof_files, const void *d_public_amounts,
+                                   uint32_t *proof_status, uint64_t *proof_xy) {
+  return rp_verify_each_impl(rp, batch, d_coms_files, d_proof_files, d_public_amounts, false, proof_status, proof_xy);
 }
 
 }  // extern "C"

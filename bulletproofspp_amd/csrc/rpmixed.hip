@@ -54,7 +54,7 @@ namespace {
 
 struct MixGroup {
   bppp_rp *rp;
-  const void *coms, *proofs;       // device files
+  RpFiles files;
   size_t B, start;                 // proofs, first job position (relative to index_offset)
   size_t shared, per;              // 1 + llen + nlen shared scalars; ninit + 2k terms per proof
   size_t tail_off, shared_off;     // first MSM term of its per-proof terms; its shared scalars in the mix buffer (in scalars)
@@ -93,7 +93,8 @@ int mixed_check(const bppp_rp_group *groups, size_t ngroups, const uint8_t *seed
   return BPPP_OK;
 }
 
-int mixed_run(bppp_ctx *ctx, const bppp_rp_group *groups, size_t ngroups, uint64_t index_offset, const uint8_t seed[32], int *accept,
+// host: the groups' files are on the host, each staged in its handle's buffer (rp_stage_files)
+int mixed_run(bppp_ctx *ctx, const bppp_rp_group *groups, size_t ngroups, uint64_t index_offset, bool host, const uint8_t seed[32], int *accept,
               uint32_t *proof_status, uint64_t *combined_xy) {
   hipSetDevice(ctx->device);
   hipStream_t st = ctx->stream;
@@ -107,7 +108,8 @@ int mixed_run(bppp_ctx *ctx, const bppp_rp_group *groups, size_t ngroups, uint64
     rp->n_combined = rp->n_each = 0;                     // (bppp_test_rp_last_verify_counts: this call's culprit search on the handle)
     if (B) {
       MixGroup g{};
-      g.rp = rp; g.coms = groups[s].coms_files; g.proofs = groups[s].proof_files; g.B = B; g.start = start;
+      g.rp = rp; g.files = RpFiles{groups[s].coms_files, groups[s].proof_files}; g.B = B; g.start = start;
+      if (host) { const int rc = rp_stage_files(rp, B, groups[s].coms_files, groups[s].proof_files, g.files); if (rc) return rc; }
       g.shared = 1 + rp->st.llen + rp->st.nlen; g.per = rp->D.nrp + rp->D.nr + 2 * (size_t)rp->st.rounds;
       g.family = -1;
       for (size_t f = 0; f < rep.size() && g.family < 0; f++)
@@ -141,7 +143,7 @@ int mixed_run(bppp_ctx *ctx, const bppp_rp_group *groups, size_t ngroups, uint64
   for (size_t i = 0; i < gs.size(); i++) {
     MixGroup &g = gs[i];
     bppp_rp *rp = g.rp;
-    int rc = rp_verify_prepare(rp, g.B, index_offset + g.start, g.coms, g.proofs, seed, g.A);
+    int rc = rp_verify_prepare(rp, g.B, index_offset + g.start, g.files, seed, g.A);
     if (rc) return rc;
     const bppp_rps::Setup &S = rp->st;
     const RpDims &D = rp->D;
@@ -200,20 +202,9 @@ int mixed_run(bppp_ctx *ctx, const bppp_rp_group *groups, size_t ngroups, uint64
   return BPPP_OK;
 }
 
-// nothing of a call is in flight once it has returned, whatever the outcome (the sliced uploads of host files run on the second stream)
-void mixed_drain(bppp_ctx *ctx) {
-  if (!ctx || ctx_closed(ctx)) return;
-  hipStreamSynchronize(ctx->stream);
-  if (ctx->aux_stream) hipStreamSynchronize(ctx->aux_stream);
-  (void)hipGetLastError();
-}
-
-}  // namespace
-
-extern "C" {
-
-int bppp_rp_verify_mixed_device(const bppp_rp_group *groups, size_t ngroups, uint64_t index_offset, const uint8_t seed[32], int *accept,
-                                uint32_t *proof_status, uint64_t *combined_xy) {
+// both entry points: files on the host (`host`) or in HBM; nothing of the call is in flight once it has returned
+int mixed_verify(const bppp_rp_group *groups, size_t ngroups, uint64_t index_offset, bool host, const uint8_t seed[32], int *accept, uint32_t *proof_status,
+                 uint64_t *combined_xy) {
   bppp_ctx *ctx;
   size_t total;
   int rc = mixed_check(groups, ngroups, seed, accept, &ctx, &total);
@@ -225,33 +216,22 @@ int bppp_rp_verify_mixed_device(const bppp_rp_group *groups, size_t ngroups, uin
     *accept = 1;
     return BPPP_OK;
   }
-  rc = mixed_run(ctx, groups, ngroups, index_offset, seed, accept, proof_status, combined_xy);
-  if (rc) mixed_drain(ctx);
+  rc = mixed_run(ctx, groups, ngroups, index_offset, host, seed, accept, proof_status, combined_xy);
+  if (rc || host) ctx_drain(ctx);
   return rc;
 }
 
+}  // namespace
+
+extern "C" {
+
+int bppp_rp_verify_mixed_device(const bppp_rp_group *groups, size_t ngroups, uint64_t index_offset, const uint8_t seed[32], int *accept,
+                                uint32_t *proof_status, uint64_t *combined_xy) {
+  return mixed_verify(groups, ngroups, index_offset, false, seed, accept, proof_status, combined_xy);
+}
+
 int bppp_rp_verify_mixed(const bppp_rp_group *groups, size_t ngroups, const uint8_t seed[32], int *accept, uint32_t *proof_status, uint64_t *combined_xy) {
-  bppp_ctx *ctx;
-  size_t total;
-  int rc = mixed_check(groups, ngroups, seed, accept, &ctx, &total);
-  if (rc) return rc;
-  if (!total) return bppp_rp_verify_mixed_device(groups, ngroups, 0, seed, accept, proof_status, combined_xy);
-  hipSetDevice(ctx->device);
-  // every group's files go to its handle's staging buffer, uploaded in slices by the decode stage of its rp_verify_prepare
-  std::vector<bppp_rp_group> dev(groups, groups + ngroups);
-  for (size_t s = 0; s < ngroups && !rc; s++) {
-    bppp_rp *rp = groups[s].rp;
-    if (!groups[s].batch) continue;
-    rc = rp_ensure_stage(rp, groups[s].batch);
-    if (rc) break;
-    const size_t cbp = (groups[s].batch * (size_t)rp->D.coms_bytes + 255) & ~(size_t)255;
-    dev[s].coms_files = rp->stage; dev[s].proof_files = (char *)rp->stage + cbp;
-    rp->host_coms = (const uint8_t *)groups[s].coms_files; rp->host_proofs = (const uint8_t *)groups[s].proof_files;
-  }
-  if (!rc) rc = bppp_rp_verify_mixed_device(dev.data(), ngroups, 0, seed, accept, proof_status, combined_xy);
-  for (size_t s = 0; s < ngroups; s++) groups[s].rp->host_coms = groups[s].rp->host_proofs = nullptr;
-  mixed_drain(ctx);
-  return rc;
+  return mixed_verify(groups, ngroups, 0, true, seed, accept, proof_status, combined_xy);
 }
 
 }  // extern "C"

@@ -18,7 +18,6 @@
 #include <string.h>
 #include <array>
 #include <atomic>
-#include <chrono>
 #include <stdio.h>
 #include <stdlib.h>
 #include <functional>
@@ -392,6 +391,37 @@ int ensure_pwork(bppp_rp *rp, size_t bytes) {
 
 namespace bppp {
 int rpp_ensure_pwork(bppp_rp *rp, size_t bytes) { return ensure_pwork(rp, bytes); }
+int rpp_ensure_hpin(bppp_rp *rp, size_t bytes) {
+  if (bytes <= rp->hpin_bytes) return BPPP_OK;
+  bppp_ctx *ctx = rp->ctx;
+  BPPP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (rp->hpin) BPPP_HIP(ctx, hipHostFree(rp->hpin));
+  rp->hpin = nullptr; rp->hpin_bytes = 0;
+  BPPP_HIP(ctx, hipHostMalloc(&rp->hpin, bytes + bytes / 8, hipHostMallocDefault));
+  rp->hpin_bytes = bytes + bytes / 8;
+  return BPPP_OK;
+}
+void rpp_encode_files(const bppp_rp *rp, size_t B, const uint64_t *in_pt, const uint64_t *wn, const uint64_t *wl, std::initializer_list<const uint64_t *> lead,
+                      const uint64_t *resp, uint8_t *coms_files, uint8_t *proof_files) {
+  const Setup &st = rp->st;
+  const RpDims &D = rp->D;
+  const size_t nr = st.rds.size(), k = st.rounds;
+  rp_parallel(B, [&](size_t lo, size_t hi) {
+    std::vector<const uint64_t *> pts;
+    for (size_t b = lo; b < hi; b++) {
+      pts.assign(nr, nullptr);
+      for (size_t i = 0; i < nr; i++) pts[i] = in_pt + (b * nr + i) * 8;
+      encode_points(coms_files + b * D.coms_bytes, pts.data(), nr);
+      uint8_t *pf = proof_files + b * D.proof_bytes;
+      for (size_t i = 0; i < st.fn; i++) put_field(pf + 32 * i, U256::load(wn + (b * st.fn + i) * 4));
+      for (size_t i = 0; i < st.fl; i++) put_field(pf + 32 * (st.fn + i), U256::load(wl + (b * st.fl + i) * 4));
+      pts.clear();
+      for (const uint64_t *c : lead) pts.push_back(c + 8 * b);
+      for (size_t j = 0; j < 2 * k; j++) pts.push_back(resp + (b * k) * 16 + 8 * j);
+      encode_points(pf + 32 * (st.fn + st.fl), pts.data(), pts.size());
+    }
+  });
+}
 int rpp_build_fixed_table(bppp_rp *rp) { return build_fixed_table(rp); }
 int rpp_commit_inputs(bppp_rp *rp, const uint32_t *d_in_sc, size_t n, uint32_t *d_out) {
   bppp_ctx *ctx = rp->ctx;
@@ -443,35 +473,27 @@ int rp_ensure_comb(bppp_rp *rp) {
 static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint8_t *rand_prefix,
                             size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files, size_t index_base, const uint64_t *pub);
 
-// encodeProof' (src/RangeProof.hs:60-66): commitments file = the input commitments; proof file = final witness scalars (norm, linear),
-// then blCom, rCom, dmCom, mCom and the responses
-static void encode_batch(const bppp_rp *rp, size_t B, const RppOutputs &o, uint8_t *coms_files, uint8_t *proof_files) {
-  const Setup &st = rp->st;
-  const RpDims &D = rp->D;
-  const size_t nr = st.rds.size(), k = st.rounds;
-  rp_parallel(B, [&](size_t lo, size_t hi) {
-    std::vector<const uint64_t *> pts;
-    for (size_t b = lo; b < hi; b++) {
-      pts.assign(nr, nullptr);
-      for (size_t i = 0; i < nr; i++) pts[i] = o.input_coms + (b * nr + i) * 8;
-      encode_points(coms_files + b * D.coms_bytes, pts.data(), nr);
-      uint8_t *pf = proof_files + b * D.proof_bytes;
-      for (size_t i = 0; i < st.fn; i++) put_field(pf + 32 * i, U256::load(o.wit_norm + (b * st.fn + i) * 4));
-      for (size_t i = 0; i < st.fl; i++) put_field(pf + 32 * (st.fn + i), U256::load(o.wit_lin + (b * st.fl + i) * 4));
-      pts.assign(4 + 2 * k, nullptr);
-      pts[0] = o.c_bl + 8 * b; pts[1] = o.c_r + 8 * b; pts[2] = o.c_dm + 8 * b; pts[3] = o.c_m + 8 * b;
-      for (size_t j = 0; j < 2 * k; j++) pts[4 + j] = o.resp + (b * k) * 16 + 8 * j;
-      encode_points(pf + 32 * (st.fn + st.fl), pts.data(), 4 + 2 * k);
-    }
-  });
-}
-
-
-
 static int prove_batch_one(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint8_t *rand_prefix,
                            size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files, size_t index_base, const uint64_t *pub);
-static int prove_batch_run(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint64_t *pub,
-                           const uint8_t *rand_prefix, size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files);
+
+// A large batch runs as TWO half-batches in flight, the second on a twin handle with its own context (stream, workspaces) from a host
+// thread: the proofs are independent, and the host shares of a half (digits, the argument's half-GCDs and round bookkeeping, the challenge
+// round trips) fall under the kernels of the other.  Same bytes out as one batch (tests).  half(h, b0, n) proves proofs [b0, b0 + n) of the
+// batch on handle h, naming them from b0 in its errors; a batch below split_min (or on a twin, or with no_split) is one half.
+template <class F> static int prove_halves(bppp_rp *rp, size_t batch, size_t split_min, F half) {
+  if (batch < split_min || batch < 2 || rp->is_twin || rp->opt.no_split) return half(rp, 0, batch);
+  { int rc = rp_ensure_twin(rp); if (rc) return rc; }
+  if (rp->comb && !rp->twin->comb) rp->twin->comb = rp->comb;      // not owned by the twin
+  rp->twin->opt = rp->opt;
+  const size_t B0 = (batch + 1) / 2;
+  int rc1 = BPPP_OK;
+  std::thread second([&] { rc1 = half(rp->twin, B0, batch - B0); });
+  const int rc0 = half(rp, 0, B0);
+  second.join();
+  if (rc0) return rc0;
+  if (rc1) return fail(rp->ctx, rc1, bppp_last_error(rp->twin_ctx));
+  return BPPP_OK;
+}
 
 extern "C" int bppp_rp_prove_batch(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint8_t *rand_prefix,
                                    size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files) {
@@ -486,16 +508,11 @@ extern "C" int bppp_rp_prove_batch_pub(bppp_rp *rp, size_t batch, const uint64_t
   if (!batch) return BPPP_OK;
   if (!amounts || (!types && rp->st.kind == 0) || !blinds || (prefix_len && !rand_prefix) || !coms_files || !proof_files || batch >= (1u << 20) || prefix_len > 4096)
     return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: bad arguments");
-  std::vector<uint64_t> pub;                    // per-proof public amounts as canonical scalars: what a handle created with them holds
-  if (public_amounts) { int rc = rp_public_canon(rp, batch, public_amounts, pub); if (rc) return rc; }
-  return prove_batch_run(rp, batch, amounts, types, blinds, public_amounts ? pub.data() : nullptr, rand_prefix, prefix_len, coms_files, proof_files);
-}
-
-static int prove_batch_run(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint64_t *pub,
-                           const uint8_t *rand_prefix, size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files) {
-  bppp_ctx *ctx = rp->ctx;
+  std::vector<uint64_t> canon;                  // per-proof public amounts as canonical scalars: what a handle created with them holds
+  if (public_amounts) { int rc = rp_public_canon(rp, batch, public_amounts, canon); if (rc) return rc; }
+  const uint64_t *pub = public_amounts ? canon.data() : nullptr;
   const size_t npub = rp_public_count(rp);
-  auto pub_at = [&](size_t b0) -> const uint64_t * { return pub ? pub + 4 * npub * b0 : nullptr; };     // the amounts of the twin's half-batch
+  auto pub_at = [&](size_t b0) -> const uint64_t * { return pub ? pub + 4 * npub * b0 : nullptr; };
   const size_t comb_min = rp->opt.comb_min;     // default 1024: the table costs ~0.3 s and tens of GB once: worth it for a handle that proves large batches
   // ... or one that has proved that many proofs in smaller batches: with the table in place every batch size is faster (one 64by64 proof:
   // 12 ms against 22 ms; 256: 22 against 48)
@@ -503,55 +520,30 @@ static int prove_batch_run(bppp_rp *rp, size_t batch, const uint64_t *amounts, c
     rp->proved_total += batch;
     if (batch >= comb_min || rp->proved_total >= comb_min) { int rc = rp_ensure_comb(rp); if (rc) return rc; }
   }
+  // proofs [b0, b0 + n) of the caller's arrays (prove_halves)
+  const size_t nr = rp->st.rds.size(), cb = rp->D.coms_bytes, pb = rp->D.proof_bytes;
+  auto prefix_at = [&](size_t b0) { return rand_prefix ? rand_prefix + prefix_len * b0 : nullptr; };
   // RangeProof.Binary: with the comb table in place the whole proof is a stream of kernels (csrc/brpprove_dev.hip); before that (small
   // batches) and under BPPP_RP_HOST_ALGEBRA the field algebra and the hashing run on the host cores (prove_batch_binary)
   if (rp->st.kind == 1) {
-    if (rp->comb && !rp->opt.host_algebra && !rp->opt.fold_points) {
-      // two half-batches in flight (as below for the typed-reciprocal proofs): the transcript hashing, the phase and the round kernels of one half —
-      // ~14 ms per 1024 proofs of mostly one-lane-per-proof chains — run under the comb additions of the other
-      if (batch < rp->opt.split_min_binary || batch < 2 || rp->is_twin || rp->opt.no_split)
-        return prove_batch_binary_dev(rp, batch, amounts, blinds, rand_prefix, prefix_len, coms_files, proof_files, 0, pub);
-      { int rc = rp_ensure_twin(rp); if (rc) return rc; }
-      if (!rp->twin->comb) rp->twin->comb = rp->comb;              // not owned by the twin
-      rp->twin->opt = rp->opt;
-      const size_t nrb = rp->st.rds.size(), B0 = (batch + 1) / 2, B1 = batch - B0;
-      int rc1 = BPPP_OK;
-      std::thread second([&] {
-        rc1 = prove_batch_binary_dev(rp->twin, B1, amounts + 4 * nrb * B0, blinds + 4 * nrb * B0, rand_prefix ? rand_prefix + prefix_len * B0 : nullptr, prefix_len,
-                                     coms_files + (size_t)rp->D.coms_bytes * B0, proof_files + (size_t)rp->D.proof_bytes * B0, B0, pub_at(B0));
+    // two half-batches in flight (as below for the typed-reciprocal proofs): the transcript hashing, the phase and the round kernels of one half —
+    // ~14 ms per 1024 proofs of mostly one-lane-per-proof chains — run under the comb additions of the other
+    if (rp->comb && !rp->opt.host_algebra && !rp->opt.fold_points)
+      return prove_halves(rp, batch, rp->opt.split_min_binary, [&](bppp_rp *h, size_t b0, size_t n) {
+        return prove_batch_binary_dev(h, n, amounts + 4 * nr * b0, blinds + 4 * nr * b0, prefix_at(b0), prefix_len, coms_files + cb * b0, proof_files + pb * b0, b0,
+                                      pub_at(b0));
       });
-      const int rc0 = prove_batch_binary_dev(rp, B0, amounts, blinds, rand_prefix, prefix_len, coms_files, proof_files, 0, pub);
-      second.join();
-      if (rc0) return rc0;
-      if (rc1) return fail(ctx, rc1, bppp_last_error(rp->twin_ctx));
-      return BPPP_OK;
-    }
     return prove_batch_binary(rp, batch, amounts, blinds, rand_prefix, prefix_len, coms_files, proof_files, pub);
   }
   // inner-product flavour without a table: the range-proof phases with their field algebra on the host cores, then the lockstep argument of
   // ip_argument_lockstep (no basis change, no point fold: every commitment an MSM over the registered original basis)
   if (rp->st.flavour != 0 && (!rp->comb || rp->opt.fold_points))
     return prove_batch_host(rp, batch, amounts, types, blinds, rand_prefix, prefix_len, coms_files, proof_files, 0, pub);
-  // A large batch runs as TWO half-batches in flight, the second on a twin handle with its own context (stream, workspaces, host
-  // thread): the proofs are independent, and the host shares of a half (digits, the argument's half-GCDs and round bookkeeping,
-  // the challenge round trips) fall under the kernels of the other.  Same bytes out as one batch (tests).
-  const size_t split_min = rp->opt.split_min;   // default 4096; measured: 4096 proofs 91-93 ms split against 95-97 ms, but 2048 proofs (128by64) 109 ms split against 104 ms
-  if (batch < split_min || batch < 2 || rp->is_twin || rp->opt.no_split)
-    return prove_batch_one(rp, batch, amounts, types, blinds, rand_prefix, prefix_len, coms_files, proof_files, 0, pub);
-  { int rc = rp_ensure_twin(rp); if (rc) return rc; }
-  if (rp->comb && !rp->twin->comb) rp->twin->comb = rp->comb;      // not owned by the twin
-  rp->twin->opt = rp->opt;
-  const size_t nr = rp->st.rds.size(), B0 = (batch + 1) / 2, B1 = batch - B0;
-  int rc1 = BPPP_OK;
-  std::thread second([&] {
-    rc1 = prove_batch_one(rp->twin, B1, amounts + 4 * nr * B0, types + 4 * nr * B0, blinds + 4 * nr * B0, rand_prefix ? rand_prefix + prefix_len * B0 : nullptr, prefix_len,
-                          coms_files + (size_t)rp->D.coms_bytes * B0, proof_files + (size_t)rp->D.proof_bytes * B0, B0, pub_at(B0));
+  // split_min: default 4096; measured: 4096 proofs 91-93 ms split against 95-97 ms, but 2048 proofs (128by64) 109 ms split against 104 ms
+  return prove_halves(rp, batch, rp->opt.split_min, [&](bppp_rp *h, size_t b0, size_t n) {
+    return prove_batch_one(h, n, amounts + 4 * nr * b0, types + 4 * nr * b0, blinds + 4 * nr * b0, prefix_at(b0), prefix_len, coms_files + cb * b0,
+                           proof_files + pb * b0, b0, pub_at(b0));
   });
-  const int rc0 = prove_batch_one(rp, B0, amounts, types, blinds, rand_prefix, prefix_len, coms_files, proof_files, 0, pub);
-  second.join();
-  if (rc0) return rc0;
-  if (rc1) return fail(ctx, rc1, bppp_last_error(rp->twin_ctx));
-  return BPPP_OK;
 }
 
 static int prove_batch_one(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint8_t *rand_prefix,
@@ -568,22 +560,12 @@ static int prove_batch_one(bppp_rp *rp, size_t batch, const uint64_t *amounts, c
   if (nr >= (1u << 16)) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: too many ranges");
   { int rc = build_fixed_table(rp); if (rc) return rc; }
   if (!rp->commit_basis) { int rc = bppp_basis_create_device(ctx, rp->d_basis, T, 0, 4096, &rp->commit_basis); if (rc) return rc; }
-  const bool timing = rp->opt.timing;
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t_last = now();
-  auto lap = [&](const char *what) { if (timing) { double t = now(); fprintf(stderr, "[rp_prove] %-28s %8.2f ms\n", what, t - t_last); t_last = t; } };
+  LapTimer timer(rp->opt.timing, "[rp_prove]");
   // ---- the witness on the host: digits and multiplicities are integer work on the plain amounts (TypedReciprocal.hs:125-161)
   // host staging: one pinned grow-only buffer per handle (no page faults on fresh vectors every call; the 50 MB of inputs and the
   // commitments cross PCIe at the pinned rate)
   const size_t n_in_sc = B * nr * 12, n_dig = B * nlen, n_mss = B * (llen - 6) + 1, n_in_pt = B * nr * 8;
-  const size_t pin_need = (n_in_sc + n_in_pt) * 8 + (2 * n_dig + n_mss) * 4 + 64;
-  if (pin_need > rp->hpin_bytes) {
-    BPPP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (rp->hpin) BPPP_HIP(ctx, hipHostFree(rp->hpin));
-    rp->hpin = nullptr; rp->hpin_bytes = 0;
-    BPPP_HIP(ctx, hipHostMalloc(&rp->hpin, pin_need + pin_need / 8, hipHostMallocDefault));
-    rp->hpin_bytes = pin_need + pin_need / 8;
-  }
+  { int rc = rpp_ensure_hpin(rp, (n_in_sc + n_in_pt) * 8 + (2 * n_dig + n_mss) * 4 + 64); if (rc) return rc; }
   uint64_t *h_in_sc = (uint64_t *)rp->hpin, *h_in_pt = h_in_sc + n_in_sc;
   uint32_t *dig = (uint32_t *)(h_in_pt + n_in_pt), *mul = dig + n_dig, *mss = mul + n_dig;
   std::atomic<int> failed{-1};
@@ -602,14 +584,14 @@ static int prove_batch_one(bppp_rp *rp, size_t batch, const uint64_t *amounts, c
     }
   });
   if (failed >= 0) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: proof " + std::to_string((size_t)failed + index_base) + ": " + errs[failed]);
-  lap("witness digits (host)");
+  timer.lap("witness digits (host)");
   std::vector<uint64_t> c_dm(B * 8), c_m(B * 8), c_r(B * 8), c_bl(B * 8), resp(B * k * 16), wn(B * st.fn * 4 + 4), wl(B * st.fl * 4 + 4);
   RppHostInputs in{B, h_in_sc, dig, mul, mss, rand_prefix, prefix_len, pub};
   RppOutputs out{h_in_pt, c_dm.data(), c_m.data(), c_r.data(), c_bl.data(), resp.data(), wn.data(), wl.data()};
   { int rc = rpp_device_prove(rp, in, out); if (rc) return rc; }
-  lap("phases + argument (device)");
-  encode_batch(rp, B, out, coms_files, proof_files);
-  lap("encode (host)");
+  timer.lap("phases + argument (device)");
+  rpp_encode_files(rp, B, out.input_coms, out.wit_norm, out.wit_lin, {out.c_bl, out.c_r, out.c_dm, out.c_m}, out.resp, coms_files, proof_files);
+  timer.lap("encode (host)");
   return BPPP_OK;
 }
 
@@ -632,11 +614,7 @@ static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
   uint32_t *d_in_sc = (uint32_t *)rp->pwork, *d_in_pt = (uint32_t *)((char *)rp->pwork + ((in_sc + 255) & ~(size_t)255)),
            *d_rows = (uint32_t *)((char *)d_in_pt + ((in_pt + 255) & ~(size_t)255));
 
-  // BPPP_RP_TIMING=1: wall time of each phase on stderr (tuning aid)
-  const bool timing = rp->opt.timing;
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t_last = now();
-  auto lap = [&](const char *what) { if (timing) { double t = now(); fprintf(stderr, "[rp_prove] %-28s %8.2f ms\n", what, t - t_last); t_last = t; } };
+  LapTimer timer(rp->opt.timing, "[rp_prove]");      // BPPP_RP_TIMING=1: wall time of each phase on stderr (tuning aid)
   std::vector<PState> ps(B);
   std::vector<uint64_t> h_in_sc(B * nr * 12), h_in_pt(B * nr * 8), h_rows(2 * B * T * 4), h_com(2 * B * 8);
   std::atomic<int> failed{-1};
@@ -664,7 +642,7 @@ static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
     }
   });
   if (failed >= 0) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: proof " + std::to_string((size_t)failed + index_base) + ": " + ps[failed].err);
-  lap("phase 1 host");
+  timer.lap("phase 1 host");
   BPPP_HIP(ctx, hipMemcpyAsync(d_in_sc, h_in_sc.data(), in_sc, hipMemcpyHostToDevice, stream));
   {
     const uint64_t n = (uint64_t)B * nr;
@@ -673,7 +651,7 @@ static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
     BPPP_HIP(ctx, hipMemcpyAsync(h_in_pt.data(), d_in_pt, in_pt, hipMemcpyDeviceToHost, stream));
   }
   { int rc = commit_rows(2 * B); if (rc) return rc; }       // synchronises the stream
-  lap("inputs + dm/m commits (GPU)");
+  timer.lap("inputs + dm/m commits (GPU)");
   std::vector<uint64_t> c_dm(B * 8), c_m(B * 8), c_r(B * 8), c_bl(B * 8);
   for (size_t b = 0; b < B; b++) { memcpy(&c_dm[8 * b], &h_com[16 * b], 64); memcpy(&c_m[8 * b], &h_com[16 * b + 8], 64); }
 
@@ -696,10 +674,10 @@ static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
       put_row(b, p.r);
     }
   });
-  lap("phase 2 host");
+  timer.lap("phase 2 host");
   { int rc = commit_rows(B); if (rc) return rc; }
   memcpy(c_r.data(), h_com.data(), B * 64);
-  lap("r commit (GPU)");
+  timer.lap("r commit (GPU)");
 
   // ---- phase 3: (q, x', r1), error terms, the blinding commitment (:421-437)
   rp_parallel(B, [&](size_t lo, size_t hi) {
@@ -727,10 +705,10 @@ static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
       put_row(b, p.blw);
     }
   });
-  lap("phase 3 host");
+  timer.lap("phase 3 host");
   { int rc = commit_rows(B); if (rc) return rc; }
   memcpy(c_bl.data(), h_com.data(), B * 64);
-  lap("bl commit (GPU)");
+  timer.lap("bl commit (GPU)");
 
   // ---- t, the combined witness and the argument's linear weights (:438-446)
   std::vector<uint64_t> a_s(B * 4), a_q(B * 4), a_nx(B * nlen * 4), a_lc(B * llen * 4), a_lx(B * llen * 4);
@@ -764,66 +742,15 @@ static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
     }
   });
 
-  lap("witness combination host");
+  timer.lap("witness combination host");
   // ---- proveBPM in lockstep (src/Bulletproof.hs:357-359)
   std::vector<uint64_t> resp(B * (k ? k : 1) * 16), wn(B * st.fn * 4 + 4), wl(B * st.fl * 4 + 4);
-  if (st.flavour) {
-    int rc = ip_argument_lockstep(rp, B, k, a_s.data(), a_q.data(), a_nx.data(), a_lc.data(), a_lx.data(), [&](size_t b) -> PState & { return ps[b]; }, resp.data(),
-                                  wn.data(), wl.data());
-    if (rc) return rc;
-    lap("inner-product argument");
-  } else {
-  bppp_nlb *nlb = nullptr;
-  int rc = bppp_nlb_create(ctx, B, a_s.data(), rp->h_g.data(), a_q.data(), a_nx.data(), rp->h_G.data(), nlen, a_lc.data(), a_lx.data(), rp->h_H.data(), llen, &nlb);
-  if (rc) return rc;
-  lap("nlb_create");
-  double t_commit = 0, t_hash = 0, t_collapse = 0;
-  std::vector<uint64_t> sX(B * 4), sR(B * 4), X(B * 8), R(B * 8), es(B * 4);
-  for (size_t round = 0; round < k && !rc; round++) {
-    double ta = now();
-    rc = bppp_nlb_round_commit(nlb, sX.data(), X.data(), sR.data(), R.data());
-    if (rc) break;
-    double tb = now(); t_commit += tb - ta;
-    rp_parallel(B, [&](size_t lo, size_t hi) {
-      for (size_t b = lo; b < hi; b++) {
-        const uint64_t *pts[2] = {&X[8 * b], &R[8 * b]};
-        U256 e;
-        oracle(rp->tag, ps[b], pts, 2, 1, &e);
-        e.store(&es[4 * b]);
-        const size_t slot = k - 1 - round;                 // responses LAST round first (:359)
-        memcpy(&resp[(b * k + slot) * 16], pts[0], 64); memcpy(&resp[(b * k + slot) * 16 + 8], pts[1], 64);
-      }
-    });
-    double tc = now(); t_hash += tc - tb;
-    rc = bppp_nlb_round_collapse(nlb, es.data());
-    t_collapse += now() - tc;
-  }
-  if (timing) fprintf(stderr, "[rp_prove] argument: commits %.2f ms, hashing %.2f ms, collapses %.2f ms\n", t_commit, t_hash, t_collapse);
-  t_last = now();
-  if (!rc) rc = bppp_nlb_get_witness(nlb, wn.data(), wl.data(), nullptr);
-  bppp_nlb_destroy(nlb);
-  if (rc) return rc;
-  }
-
-  // ---- encodeProof' (RangeProof.hs:60-66): commitments file = the input commitments; proof file = final witness scalars (norm, linear),
-  // then blCom, rCom, dmCom, mCom and the responses
-  const RpDims &D = rp->D;
-  rp_parallel(B, [&](size_t lo, size_t hi) {
-    std::vector<const uint64_t *> pts;
-    for (size_t b = lo; b < hi; b++) {
-      pts.assign(nr, nullptr);
-      for (size_t i = 0; i < nr; i++) pts[i] = &h_in_pt[(b * nr + i) * 8];
-      encode_points(coms_files + b * D.coms_bytes, pts.data(), nr);
-      uint8_t *pf = proof_files + b * D.proof_bytes;
-      for (size_t i = 0; i < st.fn; i++) put_field(pf + 32 * i, U256::load(&wn[(b * st.fn + i) * 4]));
-      for (size_t i = 0; i < st.fl; i++) put_field(pf + 32 * (st.fn + i), U256::load(&wl[(b * st.fl + i) * 4]));
-      pts.assign(4 + 2 * k, nullptr);
-      pts[0] = &c_bl[8 * b]; pts[1] = &c_r[8 * b]; pts[2] = &c_dm[8 * b]; pts[3] = &c_m[8 * b];
-      for (size_t j = 0; j < 2 * k; j++) pts[4 + j] = &resp[(b * k) * 16 + 8 * j];
-      encode_points(pf + 32 * (st.fn + st.fl), pts.data(), 4 + 2 * k);
-    }
-  });
-  lap("witness download + encode");
+  auto argument = st.flavour ? ip_argument_lockstep : nl_argument_lockstep;
+  { int rc = argument(rp, B, k, a_s.data(), a_q.data(), a_nx.data(), a_lc.data(), a_lx.data(), [&](size_t b) -> PState & { return ps[b]; }, resp.data(), wn.data(), wl.data());
+    if (rc) return rc; }
+  timer.lap("argument (lockstep)");
+  rpp_encode_files(rp, B, h_in_pt.data(), wn.data(), wl.data(), {c_bl.data(), c_r.data(), c_dm.data(), c_m.data()}, resp.data(), coms_files, proof_files);
+  timer.lap("witness download + encode");
   return BPPP_OK;
 }
 

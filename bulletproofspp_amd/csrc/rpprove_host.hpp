@@ -6,6 +6,7 @@
 #pragma once
 #include <string.h>
 #include <functional>
+#include <initializer_list>
 #include <string>
 #include <vector>
 #include "rp_internal.hpp"
@@ -150,8 +151,17 @@ namespace bppp {
 // csrc/rpprove.hip
 int rpp_build_fixed_table(bppp_rp *rp);
 int rpp_ensure_pwork(bppp_rp *rp, size_t bytes);       // the [3][64][15] fixed-base table of (g, H0, H1) for input commitments before a comb table exists
+int rpp_ensure_hpin(bppp_rp *rp, size_t bytes);        // rp->hpin, the batch prover's pinned host staging, holds at least `bytes` (grow-only)
+// encodeProof' (src/RangeProof.hs:60-66) of B proofs: commitments file = the input commitments in_pt [B][nr][8]; proof file = the final
+// witness scalars wn [B][fn][4], wl [B][fl][4], then the route's leading commitments ([B][8] each; typed: blCom rCom dmCom mCom, binary:
+// blCom dCom) and the responses resp [B][k][16]
+void rpp_encode_files(const bppp_rp *rp, size_t B, const uint64_t *in_pt, const uint64_t *wn, const uint64_t *wl, std::initializer_list<const uint64_t *> lead,
+                      const uint64_t *resp, uint8_t *coms_files, uint8_t *proof_files);
 // csrc/ipb_host.hip: proveBPM of the inner-product flavour with its field algebra on the host cores (the cross-check of csrc/ipb.hip)
 int ip_argument_lockstep(bppp_rp *rp, size_t B, size_t k, const uint64_t *psv_in, const uint64_t *rr, const uint64_t *nrm, const uint64_t *lc_in, const uint64_t *lx_in,
+                         const std::function<bppp_rpp::PState &(size_t)> &tr_of, uint64_t *resp, uint64_t *wn, uint64_t *wl);
+// ... and of the norm-linear flavour: the lockstep argument of csrc/nlb.hip, its oracle on the host cores (the same arguments; rr is makeNorm's q)
+int nl_argument_lockstep(bppp_rp *rp, size_t B, size_t k, const uint64_t *psv_in, const uint64_t *rr, const uint64_t *nrm, const uint64_t *lc_in, const uint64_t *lx_in,
                          const std::function<bppp_rpp::PState &(size_t)> &tr_of, uint64_t *resp, uint64_t *wn, uint64_t *wl);
 // csrc/brpprove.hip: RangeProof.Binary, host-algebra route and the wrapper of the device-resident one
 // pub: NULL (the setup's net_public) or one canonical net_public per proof, [batch][4] (bppp_rp_prove_batch_pub)

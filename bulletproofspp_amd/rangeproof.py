@@ -15,6 +15,7 @@ reference-generated vectors: parity of this layer with the Haskell implementatio
 """
 from __future__ import annotations
 
+import contextlib
 import hashlib
 import os
 from dataclasses import dataclass, field
@@ -888,28 +889,23 @@ class NativeRangeProofs:
             raise ValueError("one list of public amounts per proof is required")
         return scalars_to_array([int(v) % N for row in public_amounts for v in row] or [0])
 
-    def _with_public(self, fn, public_amounts, B: int, device: bool):
-        """(entry point taking the amounts after the files, what keeps them alive): `public_amounts` is a device pointer (int) on a device
-        entry point, else per-proof values, uploaded for one"""
+    @contextlib.contextmanager
+    def _public_arg(self, public_amounts, B: int, device: bool):
+        """the *_pub entry points' amounts argument: NULL for None (include/bppp.h: exactly the call without _pub), a device pointer (int)
+        as given, else per-proof values — uploaded for a device entry point, the copy freed after the call"""
         import ctypes as C
-        if isinstance(public_amounts, int):
-            return (lambda h, n, pc, pp, *rest: fn(h, n, pc, pp, C.c_void_p(public_amounts), *rest)), None
+        if public_amounts is None or isinstance(public_amounts, int):
+            yield C.c_void_p(public_amounts)
+            return
         words = self._public_words(public_amounts, B)
-        if device:
-            d = self.gpu.to_device(words)
-            return (lambda h, n, pc, pp, *rest: fn(h, n, pc, pp, C.c_void_p(d), *rest)), d
-        return (lambda h, n, pc, pp, *rest: fn(h, n, pc, pp, C.c_void_p(words.ctypes.data), *rest)), words
-
-    def _call_public(self, fn, fn_pub, public_amounts, B: int, device: bool, run):
-        """run(fn) with the plain entry point, or with the *_pub one and these amounts (a device copy made here is freed after)"""
-        if public_amounts is None:
-            return run(fn)
-        f, keep = self._with_public(fn_pub, public_amounts, B, device)
+        if not device:
+            yield C.c_void_p(words.ctypes.data)
+            return
+        d = self.gpu.to_device(words)
         try:
-            return run(f)
+            yield C.c_void_p(d)
         finally:
-            if device and keep is not None:
-                self.gpu.free(keep)
+            self.gpu.free(d)
 
     def prove_batch(self, inputs: Sequence[Sequence[Tuple[int, int, int]]], rand_prefixes: Sequence[bytes], public_amounts=None) -> List[Tuple[bytes, bytes]]:
         """bppp_rp_prove_batch: inputs[b] = [(amount, type, blinding) per range]; rand_prefixes[b] = the hashToScalar prefix of
@@ -932,11 +928,8 @@ class NativeRangeProofs:
         cf = np.zeros(B * self.shape["coms_bytes"], dtype=np.uint8)
         pf = np.zeros(B * self.shape["proof_bytes"], dtype=np.uint8)
         vp = lambda a: C.c_void_p(a.ctypes.data)
-        if public_amounts is None:
-            rc = self.gpu.lib.bppp_rp_prove_batch(self.h, B, vp(amt), vp(typ), vp(bld), vp(pre), plen, vp(cf), vp(pf))
-        else:
-            pa = self._public_words(public_amounts, B)
-            rc = self.gpu.lib.bppp_rp_prove_batch_pub(self.h, B, vp(amt), vp(typ), vp(bld), vp(pa), vp(pre), plen, vp(cf), vp(pf))
+        with self._public_arg(public_amounts, B, False) as pa:
+            rc = self.gpu.lib.bppp_rp_prove_batch_pub(self.h, B, vp(amt), vp(typ), vp(bld), pa, vp(pre), plen, vp(cf), vp(pf))
         self.gpu._check(rc, "bppp_rp_prove_batch")
         cb, pb = self.shape["coms_bytes"], self.shape["proof_bytes"]
         return [(cf[b * cb:(b + 1) * cb].tobytes(), pf[b * pb:(b + 1) * pb].tobytes()) for b in range(B)]
@@ -956,9 +949,8 @@ class NativeRangeProofs:
         if any(len(c) != self.shape["coms_bytes"] for c in coms_files) or any(len(p_) != self.shape["proof_bytes"] for p_ in proof_files):
             return (False, [2] * B, None) if (want_status or want_challenges) else False       # wrong length: malformed, as decodeProof' returns Nothing
         cb, pb = np.frombuffer(b"".join(coms_files), dtype=np.uint8), np.frombuffer(b"".join(proof_files), dtype=np.uint8)
-        lib = self.gpu.lib
-        return self._call_public(lib.bppp_rp_verify_batch, lib.bppp_rp_verify_batch_pub, public_amounts, B, False,
-                                 lambda fn: self._verify(fn, B, C.c_void_p(cb.ctypes.data), C.c_void_p(pb.ctypes.data), seed, want_status, want_challenges, (cb, pb)))
+        with self._public_arg(public_amounts, B, False) as pa:
+            return self._verify(self.gpu.lib.bppp_rp_verify_batch_pub, B, C.c_void_p(cb.ctypes.data), C.c_void_p(pb.ctypes.data), pa, seed, want_status, want_challenges)
 
     def verify_batch_device(self, batch: int, d_coms: int, d_proofs: int, seed: Optional[bytes] = None, want_status: bool = False, want_challenges: bool = False,
                             public_amounts=None):
@@ -967,9 +959,8 @@ class NativeRangeProofs:
         import ctypes as C
         if seed is None:
             seed = os.urandom(32)
-        lib = self.gpu.lib
-        return self._call_public(lib.bppp_rp_verify_batch_device, lib.bppp_rp_verify_batch_pub_device, public_amounts, batch, True,
-                                 lambda fn: self._verify(fn, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), seed, want_status, want_challenges, None))
+        with self._public_arg(public_amounts, batch, True) as pa:
+            return self._verify(self.gpu.lib.bppp_rp_verify_batch_pub_device, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), pa, seed, want_status, want_challenges)
 
     def verify_batch_device_point(self, batch: int, d_coms: int, d_proofs: int, seed: bytes, index_offset: int = 0, public_amounts=None) -> Tuple[bool, Point]:
         """bppp_rp_verify_shard_device: (accept, the combined point) — the partial result of one rank when the job is sharded
@@ -980,12 +971,9 @@ class NativeRangeProofs:
         from .capi import array_to_point
         acc, out = C.c_int(0), np.zeros(8, dtype=np.uint64)
         sd = np.frombuffer(seed, dtype=np.uint8)
-        lib = self.gpu.lib
-        shard = lambda h, n, pc, pp, *rest: lib.bppp_rp_verify_shard_device(h, n, index_offset, pc, pp, *rest)
-        shard_pub = lambda h, n, pc, pp, pa, *rest: lib.bppp_rp_verify_shard_pub_device(h, n, index_offset, pc, pp, pa, *rest)
-        rc = self._call_public(shard, shard_pub, public_amounts, batch, True,
-                               lambda fn: fn(self.h, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), C.c_void_p(sd.ctypes.data), C.byref(acc), None, None,
-                                             C.c_void_p(out.ctypes.data)))
+        with self._public_arg(public_amounts, batch, True) as pa:
+            rc = self.gpu.lib.bppp_rp_verify_shard_pub_device(self.h, batch, index_offset, C.c_void_p(d_coms), C.c_void_p(d_proofs), pa, C.c_void_p(sd.ctypes.data),
+                                                              C.byref(acc), None, None, C.c_void_p(out.ctypes.data))
         self.gpu._check(rc, "bppp_rp_verify_shard_device")
         return bool(acc.value), array_to_point(out)
 
@@ -1003,29 +991,27 @@ class NativeRangeProofs:
             return ([2] * B, [None] * B) if want_points else [2] * B
         cb = np.frombuffer(b"".join(coms_files) or b"\0", dtype=np.uint8)
         pb = np.frombuffer(b"".join(proof_files) or b"\0", dtype=np.uint8)
-        lib = self.gpu.lib
-        return self._call_public(lib.bppp_rp_verify_each, lib.bppp_rp_verify_each_pub, public_amounts, B, False,
-                                 lambda fn: self._verify_each(fn, B, C.c_void_p(cb.ctypes.data), C.c_void_p(pb.ctypes.data), want_points))
+        with self._public_arg(public_amounts, B, False) as pa:
+            return self._verify_each(self.gpu.lib.bppp_rp_verify_each_pub, B, C.c_void_p(cb.ctypes.data), C.c_void_p(pb.ctypes.data), pa, want_points)
 
     def verify_each_device(self, batch: int, d_coms: int, d_proofs: int, want_points: bool = False, public_amounts=None):
         """bppp_rp_verify_each_device: verify_each on files already in HBM (device pointers); public_amounts as for verify_batch_device"""
         import ctypes as C
-        lib = self.gpu.lib
-        return self._call_public(lib.bppp_rp_verify_each_device, lib.bppp_rp_verify_each_pub_device, public_amounts, batch, True,
-                                 lambda fn: self._verify_each(fn, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), want_points))
+        with self._public_arg(public_amounts, batch, True) as pa:
+            return self._verify_each(self.gpu.lib.bppp_rp_verify_each_pub_device, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), pa, want_points)
 
-    def _verify_each(self, fn, B, pc, pp, want_points):
+    def _verify_each(self, fn, B, pc, pp, pa, want_points):
         import ctypes as C
         import numpy as np
         from .capi import array_to_point
         status = np.zeros(max(B, 1), dtype=np.uint32)
         xy = np.zeros((max(B, 1), 8), dtype=np.uint64) if want_points else None
-        rc = fn(self.h, B, pc, pp, C.c_void_p(status.ctypes.data), C.c_void_p(xy.ctypes.data) if want_points else None)
+        rc = fn(self.h, B, pc, pp, pa, C.c_void_p(status.ctypes.data), C.c_void_p(xy.ctypes.data) if want_points else None)
         self.gpu._check(rc, "bppp_rp_verify_each")
         st = [int(v) for v in status[:B]]
         return (st, [array_to_point(xy[b]) for b in range(B)]) if want_points else st
 
-    def _verify(self, fn, B, pc, pp, seed, want_status, want_challenges, keep):
+    def _verify(self, fn, B, pc, pp, pa, seed, want_status, want_challenges):
         import ctypes as C
         import numpy as np
         from .capi import array_to_scalars
@@ -1034,7 +1020,7 @@ class NativeRangeProofs:
         nch = self.shape["challenges_per_proof"]
         chal = np.zeros((max(B, 1) * nch, 4), dtype=np.uint64) if want_challenges else None
         sd = np.frombuffer(seed, dtype=np.uint8)
-        rc = fn(self.h, B, pc, pp, C.c_void_p(sd.ctypes.data), C.byref(acc), C.c_void_p(status.ctypes.data) if want_status else None,
+        rc = fn(self.h, B, pc, pp, pa, C.c_void_p(sd.ctypes.data), C.byref(acc), C.c_void_p(status.ctypes.data) if want_status else None,
                 C.c_void_p(chal.ctypes.data) if want_challenges else None, None)
         self.gpu._check(rc, "bppp_rp_verify_batch")
         if not (want_status or want_challenges):

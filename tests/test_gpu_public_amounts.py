@@ -396,7 +396,9 @@ def test_null_amounts_and_argument_errors(typed, gpu):
             st_ = np.zeros(1, dtype=np.uint32)
             assert lib.bppp_rp_verify_each_pub(h.h, 1, vp(cb), vp(pb), vp(one), vp(st_), None) == ERR_ARG
             assert lib.bppp_rp_verify_batch_pub(h.h, 1, vp(cb), vp(pb), vp(one), vp(sd), C.byref(acc), None, None, None) == ERR_ARG
-            assert lib.bppp_rp_verify_batch_pub(h.h, 0, None, None, vp(one), vp(sd), C.byref(acc), None, None, None) == 0 and acc.value == 1
+            xy = np.full(8, 7, dtype=np.uint64)
+            assert lib.bppp_rp_verify_batch_pub(h.h, 0, None, None, vp(one), vp(sd), C.byref(acc), None, None, vp(xy)) == 0 and acc.value == 1
+            assert not xy.any()                     # an empty batch zeroes combined_xy, from host files as from HBM
     finally:
         untyped.close(); nb.close()
     n = C.c_size_t(9)
