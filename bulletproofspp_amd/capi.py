@@ -161,6 +161,7 @@ def load_test_library() -> C.CDLL:
     vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
     lib.bppp_test_fe_op.argtypes = [vp, i, i, vp, vp, sz, vp]
     lib.bppp_test_point_op.argtypes = [vp, i, vp, vp, sz, vp]
+    lib.bppp_test_point_quad.argtypes = [vp, i, vp, vp, sz, vp, vp]
     lib.bppp_test_mulmod_rate.argtypes = [vp, i, C.POINTER(C.c_double)]
     lib.bppp_test_last_mixed_msm_terms.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.bppp_test_rp_last_verify_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]

@@ -16,7 +16,7 @@
 //                    accumulator with mixed adds and stores complete buckets; a bucket that
 //                    straddles lanes is finished by k_merge (one lane per bucket) or, when it spans
 //                    many lanes (skewed scalars), by one wavefront in k_merge_heavy.
-//   4. k_reduce_marg / k_reduce_tail
+//   4. k_reduce_marg / k_reduce_tail_quad (k_reduce_tail: the one-lane form, MsmTune::tail_scalar)
 //                    sum_m m*B_m per window by MARGINAL SUMS (m = LO*hi + lo: plain row and column sums, every lane busy,
 //                    then two short weighted sums); k_reduce1/2 (per-lane running sums + wavefront suffix scans) for windows
 //                    under 256 buckets, k_reduce_groups for thousands of small windows.
@@ -28,6 +28,7 @@
 #include <vector>
 #include "ctx.hpp"
 #include "ec.hip.h"
+#include "ec_quad.hip.h"
 #include "hostmath.hpp"
 #include "recode.hip.h"
 
@@ -398,7 +399,8 @@ __global__ void __launch_bounds__(64) k_reduce2(const uint32_t *__restrict__ red
 // LO (<= 256) elements: k_reduce_tail, one element per lane (suffix scan + tree, ~18 chained additions).  The factor LO is not
 // applied on the device at all: the window combine, which doubles c times per window anyway, takes (W1, W2) and does
 // r = (r * 2^(c-a) + W1) * 2^a + W2.
-struct MargGeom { int a, LO, HI, PR, PC, SR, SC; uint32_t row_tiles, col_tiles; };
+// quad = 1: k_reduce_tail_quad, on TR = HI / 16 row and TC = LO / 16 column blocks of 16 elements (MsmTune::tail_scalar = 0)
+struct MargGeom { int a, LO, HI, PR, PC, SR, SC; uint32_t row_tiles, col_tiles; int quad, TR, TC; };
 
 __global__ void __launch_bounds__(64) k_reduce_marg(const uint32_t *__restrict__ buckets, int M, MargGeom Gm, uint32_t *__restrict__ R, uint32_t *__restrict__ C) {
   const uint32_t nbw = blockIdx.y, lane = threadIdx.x;
@@ -463,6 +465,68 @@ __global__ void __launch_bounds__(256) k_reduce_tail(const uint32_t *__restrict_
     for (uint32_t w = 1; w < gn; w++) { xyzz t = xyzz_load(tot + w * XYZZ_WORDS); xyzz_add(v, t); }
     xyzz_store(winsum2 + ((size_t)nbw * 2 + (isC ? 1 : 0)) * XYZZ_WORDS, v);
   }
+}
+
+// The same two weighted sums with one QUAD per element (ec_quad.hip.h): a quad addition is about a third of a lane addition's depth,
+// and the extra lanes are free where the chip is idle.  A block of 16 elements is one single-wavefront workgroup (workgroups land
+// on separate CUs, so every wavefront has a SIMD of its own; 16 wavefronts of one workgroup would share four).  The R kind reads
+// its elements shifted by one, R'_k = R_{k+1}, so that both kinds are  W = sum_i (i + 1) E_i.  With i = 16 b + j:
+//     W = sum_b A_b + 16 * sum_b b S_b,     A_b = sum_j (j + 1) E_{16b+j} = sum_j suffix_j,   S_b = sum_j E_{16b+j} = suffix_0
+// Every block writes (A_b, S_b) to part[] and draws a ticket; the last block of a (window, kind) does the second line on one quad per
+// block (suffix scan of S, four doublings, one addition, a tree).  Depth: 4 + 4 quad additions, then 2 log2(TB) + 1 additions and
+// 4 doublings.  cnt[] (one word per (window, kind)) is zero at launch.
+__global__ void __launch_bounds__(64) k_reduce_tail_quad(const uint32_t *__restrict__ R, const uint32_t *__restrict__ C, MargGeom Gm, uint32_t *__restrict__ part,
+                                                         uint32_t *__restrict__ cnt, uint32_t *__restrict__ winsum2) {
+  __shared__ uint32_t last;
+  const uint32_t nbw = blockIdx.y, lane = threadIdx.x, qd = lane >> 2;
+  const bool isC = blockIdx.x >= (uint32_t)Gm.TR;
+  const uint32_t blk = isC ? blockIdx.x - Gm.TR : blockIdx.x, nb = isC ? Gm.TC : Gm.TR, i = blk * 16 + qd;
+  xyzz suf = xyzz_inf();
+  if (isC) suf = xyzz_load(C + ((size_t)nbw * Gm.LO + i) * XYZZ_WORDS);
+  else if (i + 1 < (uint32_t)Gm.HI) suf = xyzz_load(R + ((size_t)nbw * Gm.HI + i + 1) * XYZZ_WORDS);
+  for (int d = 1; d < 16; d <<= 1) {             // inclusive suffix scan over the 16 quads
+    xyzz o = xyzz_shfl_down(suf, 4 * d);
+    xyzz_add_quad(suf, xyzz_or_inf(qd + d < 16, o));
+  }
+  xyzz v = suf;
+  for (int d = 8; d >= 1; d >>= 1) {             // tree of the suffixes: A_b in quad 0
+    xyzz o = xyzz_shfl_down(v, 4 * d);
+    xyzz_add_quad(v, xyzz_or_inf(qd + d < 16, o));
+  }
+  uint32_t *pb = part + (((size_t)nbw * 2 + (isC ? 1 : 0)) * 16 + blk) * 2 * XYZZ_WORDS;
+  if (lane == 0) xyzz_store(pb, v);
+  if (lane == 1) xyzz_store(pb + XYZZ_WORDS, suf);
+  // publish (A_b, S_b): agent-scope release before the ticket; the last arriver acquires before it reads the other blocks' pairs
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (lane == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const uint32_t t = __hip_atomic_fetch_add(cnt + (size_t)nbw * 2 + (isC ? 1 : 0), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = t == nb - 1;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+  }
+  __syncthreads();
+  if (!last) return;
+  // quad b < nb holds block b
+  const uint32_t *pr = part + ((size_t)nbw * 2 + (isC ? 1 : 0)) * 16 * 2 * XYZZ_WORDS;
+  xyzz A = xyzz_inf(), S = xyzz_inf();
+  if (qd < nb) { A = xyzz_load(pr + (size_t)qd * 2 * XYZZ_WORDS); S = xyzz_load(pr + ((size_t)qd * 2 + 1) * XYZZ_WORDS); }
+  for (uint32_t d = 1; d < nb; d <<= 1) {
+    xyzz o = xyzz_shfl_down(S, 4 * d);
+    xyzz_add_quad(S, xyzz_or_inf(qd + d < nb, o));
+  }
+  // sum_b b S_b = sum_{b >= 1} suffix_b; times 16, plus A_b, summed over the blocks
+  v = xyzz_or_inf(qd >= 1, S);
+  for (int k = 0; k < 4; k++) xyzz_dbl_quad(v);
+  xyzz_add_quad(v, A);
+  for (uint32_t d = nb >> 1; d >= 1; d >>= 1) {
+    xyzz o = xyzz_shfl_down(v, 4 * d);
+    xyzz_add_quad(v, xyzz_or_inf(qd + d < nb, o));
+  }
+  if (lane == 0) xyzz_store(winsum2 + ((size_t)nbw * 2 + (isC ? 1 : 0)) * XYZZ_WORDS, v);
 }
 
 // Many small windows (batched MSMs of a few hundred terms: M <= 256 buckets per window, thousands of windows): a whole
@@ -754,6 +818,7 @@ static MsmPlan make_plan(size_t n, size_t batch, int c, bool flat, const MsmTune
     while (g.PR > 64) { g.PR >>= 1; g.SR <<= 1; }                        // the segmented tree lives inside one wavefront
     while (g.PC > 64) { g.PC >>= 1; g.SC <<= 1; }
     g.row_tiles = (uint32_t)(((size_t)g.HI * g.PR + 63) / 64); g.col_tiles = (uint32_t)(((size_t)g.LO * g.PC + 63) / 64);
+    g.TR = g.HI / 16; g.TC = g.LO / 16; g.quad = !tune.tail_scalar && g.TR >= 1 && g.TC <= 16;     // HI, LO: powers of two in [16, 256]
   }
   // slice length: short enough to keep >= ~150K lanes (two to four wavefronts per SIMD), but at least a quarter of a bucket's
   // expected entries, so that a bucket straddles few lanes and stays on the serial merge path (sweep_window.py table)
@@ -867,7 +932,9 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
     uint2 *heavy_items = cv.take<uint2>(hmax);
     uint4 *heavy_buckets = cv.take<uint4>(hmax);
     uint32_t *chunk_sums = cv.take<uint32_t>(hmax * XYZZ_WORDS);
-    uint32_t *heavy_count = cv.take<uint32_t>(4);
+    uint32_t *heavy_count = cv.take<uint32_t>(4 + (p.marg ? 2 * (size_t)p.NS : 0));
+    uint32_t *tail_cnt = heavy_count + 4;           // k_reduce_tail_quad's tickets, zeroed with heavy_count
+    uint32_t *tail_part = cv.take<uint32_t>(p.marg && p.mg.quad ? (size_t)p.NS * 2 * 16 * 2 * XYZZ_WORDS : 0);
     uint32_t *red = cv.take<uint32_t>(p.marg ? (size_t)p.NS * (p.mg.HI + p.mg.LO) * XYZZ_WORDS : (size_t)p.NS * p.WPW * 2 * XYZZ_WORDS);
     uint32_t *winsum = cv.take<uint32_t>((size_t)p.NS * 2 * XYZZ_WORDS);
     uint32_t *out_aff = cv.take<uint32_t>((size_t)batch * 16);
@@ -895,7 +962,7 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
     k_scatter<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(dig, negmask, (uint32_t)n, stride, c, p.CH, p.W, blockhist, start, sorted,
                                                                              p.flat ? (uint32_t)table_stride : 0u);
     BPPP_HIP(ctx, hipMemsetAsync(buckets, 0, (size_t)p.FB * XYZZ_WORDS * 4, st));
-    BPPP_HIP(ctx, hipMemsetAsync(heavy_count, 0, 16, st));
+    BPPP_HIP(ctx, hipMemsetAsync(heavy_count, 0, (4 + (p.marg ? 2 * (size_t)p.NS : 0)) * 4, st));
     prof_mark(ctx, 2);
     if (ctx->pre_acc) { auto f = ctx->pre_acc; ctx->pre_acc = nullptr; int rc_ = f(ctx->pre_acc_arg); if (rc_) return rc_; }
     // 3. accumulate
@@ -912,7 +979,8 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
     } else if (p.marg) {
       uint32_t *Rm = red, *Cm = red + (size_t)p.NS * p.mg.HI * XYZZ_WORDS;
       k_reduce_marg<<<dim3(p.mg.row_tiles + p.mg.col_tiles, (unsigned)p.NS), dim3(64), 0, st>>>(buckets, p.M, p.mg, Rm, Cm);
-      k_reduce_tail<<<dim3((unsigned)p.NS, 2), dim3(64u * (unsigned)((p.mg.LO + 63) / 64)), 0, st>>>(Rm, Cm, p.mg, winsum);
+      if (p.mg.quad) k_reduce_tail_quad<<<dim3((unsigned)(p.mg.TR + p.mg.TC), (unsigned)p.NS), dim3(64), 0, st>>>(Rm, Cm, p.mg, tail_part, tail_cnt, winsum);
+      else k_reduce_tail<<<dim3((unsigned)p.NS, 2), dim3(64u * (unsigned)((p.mg.LO + 63) / 64)), 0, st>>>(Rm, Cm, p.mg, winsum);
     } else {
       k_reduce1<<<dim3((unsigned)p.NS, p.WPW), dim3(64), 0, st>>>(buckets, p.M, p.Lw, p.WPW, red);
       k_reduce2<<<dim3((unsigned)p.NS), dim3(64), 0, st>>>(red, p.Lw, p.WPW, winsum);

@@ -3,6 +3,7 @@
 #include <vector>
 #include "ctx.hpp"
 #include "ec.hip.h"
+#include "ec_quad.hip.h"
 #include "modinv.hip.h"
 #include "fr26.hip.h"
 #include "rp_internal.hpp"
@@ -88,6 +89,46 @@ __global__ void k_test_point(int op, const uint32_t *p, const uint32_t *q, uint3
   else acc = xyzz_dbl(xyzz_dbl_aff(P));  // 4P via both doubling forms
   aff_store(out + (size_t)i * 16, xyzz_to_aff(acc));
 }
+// the quad forms (ec_quad.hip.h) against the one-lane forms: one quad per element, the scalar routine on every lane beside it
+BPPP_DI xyzz test_xyzz_of(const aff &P, bool bounds) {
+  xyzz t = xyzz_dbl_aff(P);                       // 2P - P: P with ZZ != 1
+  xyzz_madd(t, aff_cneg(P, true));
+  if (bounds) {                                   // the same point with every X limb near magnitude 5 and every Y limb near 3
+    t.X = fq_sub<3>(fq_normalize(t.X), fq_zero());
+    t.Y = fq_sub<1>(fq_normalize(t.Y), fq_zero());
+  }
+  return t;
+}
+BPPP_DI uint32_t quad_or(uint32_t v) {          // OR over the quad, through the same pinned broadcasts as the point operations
+  fq t = fq_zero();
+  t.n[0] = v;
+  return fq_quad_bcast<0>(t).n[0] | fq_quad_bcast<1>(t).n[0] | fq_quad_bcast<2>(t).n[0] | fq_quad_bcast<3>(t).n[0];
+}
+__global__ void __launch_bounds__(64) k_test_point_quad(int op, const uint32_t *p, const uint32_t *q, uint32_t n, uint32_t *out, uint32_t *raw) {
+  const uint32_t i = (blockIdx.x * 64 + threadIdx.x) >> 2;
+  const bool valid = i < n, bounds = (op & 1) != 0;
+  xyzz A = xyzz_inf(), B = xyzz_inf();           // a quad past the end adds infinity: every quad takes part in the exchanges
+  if (valid) { A = test_xyzz_of(aff_load(p + (size_t)i * 16), bounds); B = test_xyzz_of(aff_load(q + (size_t)i * 16), bounds); }
+  xyzz s = A, r = A;
+  if (op < 2) { xyzz_add(s, B); xyzz_add_quad(r, B); }
+  else { s = xyzz_dbl(A); xyzz_dbl_quad(r); }
+  // do the four lanes of the quad hold the same limbs?
+  uint32_t d = 0;
+  const xyzz r0 = { fq_quad_bcast<0>(r.X), fq_quad_bcast<0>(r.Y), fq_quad_bcast<0>(r.ZZ), fq_quad_bcast<0>(r.ZZZ) };
+#pragma unroll
+  for (int k = 0; k < 10; k++) d |= (r.X.n[k] ^ r0.X.n[k]) | (r.Y.n[k] ^ r0.Y.n[k]) | (r.ZZ.n[k] ^ r0.ZZ.n[k]) | (r.ZZZ.n[k] ^ r0.ZZZ.n[k]);
+  d = quad_or(d);
+  if (valid && (threadIdx.x & 3u) == 0) {
+    uint32_t *o = raw + (size_t)i * 81;
+#pragma unroll
+    for (int k = 0; k < 10; k++) {
+      o[k] = r.X.n[k]; o[10 + k] = r.Y.n[k]; o[20 + k] = r.ZZ.n[k]; o[30 + k] = r.ZZZ.n[k];
+      o[40 + k] = s.X.n[k]; o[50 + k] = s.Y.n[k]; o[60 + k] = s.ZZ.n[k]; o[70 + k] = s.ZZZ.n[k];
+    }
+    o[80] = d == 0 ? 1u : 0u;
+    aff_store(out + (size_t)i * 16, xyzz_to_aff(r));
+  }
+}
 }  // namespace bppp
 
 using namespace bppp;
@@ -127,6 +168,23 @@ extern "C" int bppp_test_point_op(bppp_ctx *ctx, int op, const uint64_t *p, cons
       rc = bppp::fail(ctx, BPPP_ERR_HIP, "test_point_op: kernel or copy failed");
   }
   hipFree(da); hipFree(db); hipFree(dout);
+  return rc;
+}
+extern "C" int bppp_test_point_quad(bppp_ctx *ctx, int op, const uint64_t *p, const uint64_t *q, size_t n, uint64_t *out, uint32_t *raw) {
+  if (!ctx || !p || !q || !out || !raw || op < 0 || op > 3) return BPPP_ERR_ARG;
+  if (n == 0) return BPPP_OK;
+  hipSetDevice(ctx->device);
+  void *da = nullptr, *db = nullptr, *dout = nullptr, *draw = nullptr;
+  int rc = run2(ctx, p, q, n, 8, out, &da, &db, &dout);
+  if (!rc && hipMalloc(&draw, n * 81 * 4) != hipSuccess) rc = bppp::fail(ctx, BPPP_ERR_HIP, "test_point_quad: hipMalloc");
+  if (!rc) {
+    k_test_point_quad<<<dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, ctx->stream>>>(op, (const uint32_t *)da, (const uint32_t *)db, (uint32_t)n, (uint32_t *)dout,
+                                                                                        (uint32_t *)draw);
+    if (hipMemcpyAsync(out, dout, n * 64, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(raw, draw, n * 81 * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+      rc = bppp::fail(ctx, BPPP_ERR_HIP, "test_point_quad: kernel or copy failed");
+  }
+  hipFree(da); hipFree(db); hipFree(dout); hipFree(draw);
   return rc;
 }
 

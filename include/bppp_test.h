@@ -23,6 +23,12 @@ int bppp_test_fe_op(bppp_ctx *ctx, int op, int modulus, const uint64_t *a, const
 /* out[i] = p[i] + q[i] (complete group law; op 0: mixed XYZZ+affine, op 1: XYZZ+XYZZ, op 2: 2*p[i]);
  * host arrays of n x 8 uint64 affine points */
 int bppp_test_point_op(bppp_ctx *ctx, int op, const uint64_t *p, const uint64_t *q, size_t n, uint64_t *out);
+/* The quad forms of csrc/ec_quad.hip.h (four lanes share one point operation) against the one-lane forms, one quad per element:
+ * op 0: p[i] + q[i] (xyzz_add_quad vs xyzz_add), op 2: 2 * p[i] (xyzz_dbl_quad vs xyzz_dbl); op 1 / 3: the same with the XYZZ inputs
+ * pushed to the magnitude bounds (X <= 5, Y <= 3).  Inputs are affine, taken to XYZZ with ZZ != 1.  out: n x 8 uint64 affine results
+ * of the quad form; raw: n x 81 uint32, the quad form's 40 raw limbs (X, Y, ZZ, ZZZ), the scalar form's 40, and 1 iff all four
+ * lanes of the quad held the same limbs. */
+int bppp_test_point_quad(bppp_ctx *ctx, int op, const uint64_t *p, const uint64_t *q, size_t n, uint64_t *out, uint32_t *raw);
 /* Measured ceiling of the field layer: modular multiplications per second of a kernel that does nothing but independent
  * Fq multiplications (10x26-bit limbs) at 8 wavefronts per SIMD.  bench.py quotes the MSM's multiplication rate against it. */
 int bppp_test_mulmod_rate(bppp_ctx *ctx, int iters, double *mulmods_per_sec);
