@@ -33,6 +33,7 @@ SYMBOLS = [
     "bppp_rp_verify_mixed", "bppp_rp_verify_mixed_device", "bppp_rp_verify_each", "bppp_rp_verify_each_device",
     "bppp_rp_public_count", "bppp_rp_verify_batch_pub", "bppp_rp_verify_batch_pub_device", "bppp_rp_verify_shard_pub_device", "bppp_rp_verify_each_pub",
     "bppp_rp_verify_each_pub_device", "bppp_rp_prove_batch_pub",
+    "bppp_rp_share_comb", "bppp_rp_comb_info", "bppp_rp_prove_mixed",
 ]
 
 
@@ -146,6 +147,9 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_verify_each_pub.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     lib.bppp_rp_verify_each_pub_device.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     lib.bppp_rp_prove_batch_pub.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp, vp]
+    lib.bppp_rp_share_comb.argtypes = [vp, vp]
+    lib.bppp_rp_comb_info.argtypes = [vp, C.POINTER(i), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+    lib.bppp_rp_prove_mixed.argtypes = [vp, sz]
     lib.bppp_profile_enable.argtypes = [vp, i]
     lib.bppp_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), i]
     return lib
@@ -182,6 +186,13 @@ class RpPublic(C.Structure):
 class RpGroup(C.Structure):
     """bppp_rp_group: one setup's share of a mixed batch"""
     _fields_ = [("rp", C.c_void_p), ("batch", C.c_size_t), ("coms_files", C.c_void_p), ("proof_files", C.c_void_p)]
+
+
+class RpProveGroup(C.Structure):
+    """bppp_rp_prove_group: one setup's share of a mixed prove job"""
+    _fields_ = [("rp", C.c_void_p), ("batch", C.c_size_t), ("amounts", C.c_void_p), ("types", C.c_void_p), ("blinds", C.c_void_p),
+                ("public_amounts", C.c_void_p), ("rand_prefix", C.c_void_p), ("prefix_len", C.c_size_t), ("coms_files", C.c_void_p),
+                ("proof_files", C.c_void_p)]
 
 
 class RpShape(C.Structure):

@@ -141,7 +141,7 @@ int brp_device_prove(bppp_rp *rp, const BrpHostInputs &in, BrpOutputs &out) {
   if (!rp->comb || !tb) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: the device prover needs the comb table of the setup");
   const BrpDims D = tb->D;
   const size_t B = in.batch, nr = S.rds.size(), nlen = S.nlen, nlive = S.nlive, k = S.rounds, T = 3 + nlen, nd = nlen + 3;
-  if (S.llen != 2 || rp->comb->T != T) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: binary setup and comb table disagree");
+  if (S.llen != 2 || rp->comb->T < T) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: binary setup and comb table disagree");
   uint32_t *in_sc = nullptr, *in_pt = nullptr, *rnd = nullptr, *row_d = nullptr, *row_bl = nullptr, *aux = nullptr, *ch = nullptr, *es = nullptr, *tstart = nullptr,
            *ptbuf = nullptr, *a_s = nullptr, *a_q = nullptr, *a_lx = nullptr, *a_nx = nullptr, *p_sp = nullptr, *p_norm = nullptr, *p_cs = nullptr, *p_init = nullptr,
            *d_resp = nullptr, *d_com = nullptr, *cscratch = nullptr;
@@ -168,7 +168,7 @@ int brp_device_prove(bppp_rp *rp, const BrpHostInputs &in, BrpOutputs &out) {
   RppTranscript tr;
   int rc = tr.begin(rp, B, {RppCall{(uint32_t)(1 + nr), 3, 0}, RppCall{1, 1, 6}}, k, B <= rp->opt.host_oracle_prove, text, tstart, hdrs, ch, es); if (rc) return rc;
   auto comb = [&](const uint32_t *rows, uint32_t *dst, int hint) -> int {
-    int r_ = comb_msm(rp->comb, rows, B, dst, st, hint, 0, cscratch, comb_rows_scratch_bytes(B));
+    int r_ = comb_msm(rp->comb, rows, B, dst, st, hint, T, cscratch, comb_rows_scratch_bytes(B));
     return r_ ? fail(ctx, r_, bppp_last_error(rp->comb->ctx)) : BPPP_OK;
   };
   uint32_t *c_d = d_com, *c_bl = d_com + B * 16;

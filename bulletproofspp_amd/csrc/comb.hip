@@ -355,11 +355,11 @@ int comb_lanes(const CombTable *t, const uint32_t *d_scalars, size_t nterms, siz
 }
 
 int comb_groups(const CombTable *t, const uint32_t *d_scalars, size_t ninst, size_t l0, size_t n0, int L, uint32_t *d_out_aff, size_t out_stride, hipStream_t st) {
-  if (!t || !d_scalars || !d_out_aff || !ninst || 1 + l0 + n0 != t->T || L < 1 || L > 20) return BPPP_ERR_ARG;
+  if (!t || !d_scalars || !d_out_aff || !ninst || 1 + l0 + n0 > t->T || L < 1 || L > 20) return BPPP_ERR_ARG;
   const size_t l0r = (l0 + ((size_t)1 << L) - 1) >> L, n0r = (n0 + ((size_t)1 << L) - 1) >> L, ngroups = (ninst + 63) / 64;
   if (out_stride < 1 + l0r + n0r || ngroups * (l0r + n0r) >= (1ull << 31)) return BPPP_ERR_ARG;
   const RecodeK K = make_recode_k(t->c, t->W);
-  k_comb_msm_groups<<<dim3((unsigned)(ngroups * (l0r + n0r))), dim3(64), 0, st>>>(t->tab, (uint32_t)t->T, t->c, t->W, (uint32_t)t->D, K, d_scalars, (uint32_t)t->T, (uint32_t)ninst,
+  k_comb_msm_groups<<<dim3((unsigned)(ngroups * (l0r + n0r))), dim3(64), 0, st>>>(t->tab, (uint32_t)t->T, t->c, t->W, (uint32_t)t->D, K, d_scalars, (uint32_t)(1 + l0 + n0), (uint32_t)ninst,
                                                                                (uint32_t)ngroups, (uint32_t)l0, (uint32_t)n0, L, (uint32_t)l0r, (uint32_t)out_stride, d_out_aff);
   if (hipGetLastError() != hipSuccess) return fail(t->ctx, BPPP_ERR_HIP, "comb_groups: launch failed");
   return BPPP_OK;

@@ -257,7 +257,7 @@ size_t ipb_work_bytes(size_t B, size_t nlen, size_t llen) {
 int ipb_prove_stream(bppp_ctx *ctx, const CombTable *comb, RppTranscript &tr, size_t first_call, size_t B, size_t nlen, size_t llen, size_t k, size_t fn, size_t fl,
                      const uint32_t *d_psv, const uint32_t *d_rr, const uint32_t *d_nrm, const uint32_t *d_lc, const uint32_t *d_lx, void *work, size_t work_bytes,
                      uint32_t *d_resp, uint32_t *d_wn, uint32_t *d_wl, uint32_t **d_flag_out) {
-  if (!ctx || !comb || !B || nlen + llen == 0 || comb->T != 1 + llen + nlen || work_bytes < ipb_work_bytes(B, nlen, llen)) return BPPP_ERR_ARG;
+  if (!ctx || !comb || !B || nlen + llen == 0 || comb->T < 1 + llen + nlen || work_bytes < ipb_work_bytes(B, nlen, llen)) return BPPP_ERR_ARG;
   hipStream_t st = ctx->stream;
   const size_t m0 = (nlen + 1) / 2, xs = ev(m0) + 2, ls = ev(llen) + 2, T = 1 + llen + nlen;
   // lanes per proof: the smallest power of two >= the longer vector (at least 8), 256 / lp proofs per 256-lane workgroup
@@ -282,7 +282,7 @@ int ipb_prove_stream(bppp_ctx *ctx, const CombTable *comb, RppTranscript &tr, si
     k_ipb_expand<<<dim3((unsigned)((T + 255) / 256), (unsigned)(2 * B)), dim3(256), 0, st>>>(D, (uint32_t)round, (uint32_t)me, (uint32_t)le, stt, og, ol, cx, cy, cl, full);
     BPPP_HIP(ctx, hipGetLastError());
     uint32_t *lr = d_resp + round * B * 32;
-    int rc = comb_msm(comb, full, 2 * B, lr, st, false, 0, cscratch, comb_scratch_bytes(2 * B));
+    int rc = comb_msm(comb, full, 2 * B, lr, st, false, T, cscratch, comb_scratch_bytes(2 * B));
     if (rc) return fail(ctx, rc, bppp_last_error(comb->ctx));
     rc = tr.call(lr, first_call + round); if (rc) return rc;
     k_ipb_collapse<<<dim3(pgrid), dim3(256), 0, st>>>(D, (uint32_t)round, (uint32_t)mc, (uint32_t)lcn, tr.es, stt, X[cur], Y[cur], LC[cur],

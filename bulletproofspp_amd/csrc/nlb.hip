@@ -346,7 +346,7 @@ namespace bppp {
 int nlb_create_impl(bppp_ctx *ctx, size_t batch, const uint64_t *s, const uint64_t *g_xy, const uint64_t *q, const uint64_t *norm_x,
                     const uint64_t *norm_g_xy, size_t nlen, const uint64_t *lin_c, const uint64_t *lin_x, const uint64_t *lin_h_xy, size_t llen,
                     bppp_nlb **out, bool on_device, const CombTable *comb) {
-  if (comb && comb->T != 1 + llen + nlen) comb = nullptr;        // not this basis: the general route
+  if (comb && comb->T < 1 + llen + nlen) comb = nullptr;        // not (a table that covers) this basis: the general route
   const hipMemcpyKind KIND = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   if (!ctx || !out || !s || !g_xy || !q || !batch || ctx_closed(ctx)) return BPPP_ERR_ARG;
   if ((nlen && (!norm_x || !norm_g_xy)) || (llen && (!lin_c || !lin_x || !lin_h_xy)) || nlen + llen == 0 || nlen >= (1u << 24) || llen >= (1u << 24) ||
@@ -504,7 +504,7 @@ int nlb_round_commit_dev(bppp_nlb *o, uint32_t *d_XR) {
   k_nlb_expand<<<dim3((Tc + 255) / 256, (unsigned)(2 * B)), dim3(256), 0, st>>>(o->sc, (uint32_t)T, (uint32_t)ne, o->folds, o->coefn, o->coefl, (uint32_t)o->n0,
                                                                                 (uint32_t)o->l0, o->full);
   NLB_HIP(o, hipGetLastError());
-  int rc = comb_msm(o->comb, o->full, 2 * B, d_XR, st, COMB_ROWS_PAIRS, 0, o->cscratch, comb_rows_scratch_bytes(2 * B));
+  int rc = comb_msm(o->comb, o->full, 2 * B, d_XR, st, COMB_ROWS_PAIRS, Tc, o->cscratch, comb_rows_scratch_bytes(2 * B));
   if (rc) return fail(ctx, rc, bppp_last_error(o->comb->ctx));
   return BPPP_OK;
 }

@@ -531,9 +531,9 @@ void bppp_rp_destroy(bppp_rp *rp) {
   if (rp->pwork) hipFree(rp->pwork);
   if (rp->awork) hipFree(rp->awork);
   if (rp->hpin) hipHostFree(rp->hpin);
-  if (rp->twin) bppp_rp_destroy(rp->twin);
+  if (rp->twin) { bppp_rp_destroy(rp->twin); rp->twin = nullptr; }
   if (rp->d_comb_out) hipFree(rp->d_comb_out);
-  if (rp->comb && rp->comb_owned) bppp::comb_destroy(rp->comb);
+  rp_set_comb(rp, nullptr);                      // the table goes with its last holder
   if (rp->twin_ctx) bppp_ctx_destroy(rp->twin_ctx);
   delete rp;
   ctx_release(ctx);

@@ -2,6 +2,8 @@
 // csrc/rpprove.hip: batch prover).
 #pragma once
 #include <stdio.h>
+#include <string.h>
+#include <algorithm>
 #include <chrono>
 #include <string>
 #include <thread>
@@ -146,8 +148,13 @@ struct bppp_rp {
   int c_conserve = 0; uint64_t c_net_public[4] = {0, 0, 0, 0};      // bppp_rp_create_binary's arguments, for the twin handle
   bppp_rp *twin = nullptr; bppp_ctx *twin_ctx = nullptr; bool is_twin = false;
   // fixed-base comb over [g | H | G] (csrc/comb.hip): the range-proof commitments and the argument's round commitments of large
-  // batches; the twin handle uses its parent's table
-  bppp::CombTable *comb = nullptr; bool comb_owned = false, comb_failed = false; size_t proved_total = 0;
+  // batches.  The table is reference-counted (rp_set_comb): built by this handle, or the table of a LONGER basis of the same point
+  // stream that another handle built (bppp_rp_share_comb, bppp_rp_prove_mixed; csrc/rpshare.hip) — every launch passes this handle's own
+  // row length next to the table's stride; the twin handle holds its parent's table
+  bppp::CombTable *comb = nullptr; bool comb_failed = false; size_t proved_total = 0;
+  // bppp_rp_prove_mixed: the input commitments of this handle's group, already computed with its family's in one launch ([batch][nranges]
+  // affine points in HBM, complete before the group starts); rpp_commit_inputs copies them instead of launching
+  const uint32_t *pre_inputs = nullptr;
   uint32_t *d_comb_out = nullptr; size_t comb_out_rows = 0;   // fixed-base tables of the argument's first round (csrc/nlb.hip)
   // grow-only verifier workspace and the staging buffer of the host-buffer entry point
   bppp::HostPool *pool = nullptr;                // workers of the host oracle (batches of 2 .. host_oracle_verify proofs), made on first use
@@ -218,3 +225,14 @@ int basis_msm_dev(bppp_basis *h, const void *d_scalars, size_t n_terms, size_t b
 int msm_batch_dev(bppp_ctx *, const void *, const void *, size_t, size_t, int, int, uint32_t *);           // csrc/msm.hip
 }  // namespace bppp
 int rp_ensure_comb(bppp_rp *rp);      // csrc/rpprove.hip
+// the handle (and its twin) proves over table t from now on (nullptr: none): t gains a holder, the table held before loses one and is
+// freed with its last holder (csrc/rpprove.hip)
+void rp_set_comb(bppp_rp *rp, bppp::CombTable *t);
+namespace bppp {
+inline size_t rp_basis_points(const bppp_rp *rp) { return rp->c_points.size() / 8 - 1; }     // [g | H | G]: c_points without h
+// one handle's basis is a prefix of the other's (compared point by point, never by seed or tag)
+inline bool rp_same_stream(const bppp_rp *a, const bppp_rp *b) {
+  const size_t n = std::min(rp_basis_points(a), rp_basis_points(b));
+  return memcmp(a->c_points.data() + 8, b->c_points.data() + 8, n * 64) == 0;
+}
+}  // namespace bppp

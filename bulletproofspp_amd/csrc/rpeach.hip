@@ -92,7 +92,7 @@ int rp_each_pass(bppp_rp *rp, const RpVerifyArrays &A, uint32_t *proof_status, u
                                 A.init_sc + o * ninit * 8, A.init_pts + o * ninit * 16, A.resp_pts + o * 2 * k * 16, scratch, rows, tail, pts);
     if (rc) return rc;
     if (rp->comb) {
-      rc = comb_msm(rp->comb, rows, np, fixed, st, COMB_ROWS_DENSE, 0, cscratch, cbytes);
+      rc = comb_msm(rp->comb, rows, np, fixed, st, COMB_ROWS_DENSE, T, cscratch, cbytes);
       if (rc) return fail(ctx, rc, "rp_verify_each: the fixed-base MSM failed");
     } else if ((rc = basis_msm_dev(rp->commit_basis, rows, T, np, fixed))) return rc;
     if ((rc = msm_batch_dev(ctx, tail, pts, per, np, 0, 0, own))) return rc;

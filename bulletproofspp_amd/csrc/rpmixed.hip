@@ -62,13 +62,8 @@ struct MixGroup {
   RpVerifyArrays A;
 };
 
-size_t basis_points(const bppp_rp *rp) { return rp->c_points.size() / 8 - 1; }     // [g | H | G]: c_points without h
-
-// one handle's basis is a prefix of the other's (compared point by point, never by seed or tag)
-bool same_stream(const bppp_rp *a, const bppp_rp *b) {
-  const size_t n = std::min(basis_points(a), basis_points(b));
-  return memcmp(a->c_points.data() + 8, b->c_points.data() + 8, n * 64) == 0;
-}
+size_t basis_points(const bppp_rp *rp) { return rp_basis_points(rp); }
+bool same_stream(const bppp_rp *a, const bppp_rp *b) { return rp_same_stream(a, b); }      // rp_internal.hpp: shared with the prover's families (csrc/rpshare.hip)
 
 // the checks both entry points make; *ctx_out is the groups' context (null when there is none to report to)
 int mixed_check(const bppp_rp_group *groups, size_t ngroups, const uint8_t *seed, int *accept, bppp_ctx **ctx_out, size_t *total_out) {

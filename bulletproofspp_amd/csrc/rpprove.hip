@@ -425,6 +425,8 @@ void rpp_encode_files(const bppp_rp *rp, size_t B, const uint64_t *in_pt, const 
 int rpp_build_fixed_table(bppp_rp *rp) { return build_fixed_table(rp); }
 int rpp_commit_inputs(bppp_rp *rp, const uint32_t *d_in_sc, size_t n, uint32_t *d_out) {
   bppp_ctx *ctx = rp->ctx;
+  // bppp_rp_prove_mixed committed the inputs of the whole family in one launch (csrc/rpshare.hip): they are complete in HBM
+  if (rp->pre_inputs) { BPPP_HIP(ctx, hipMemcpyAsync(d_out, rp->pre_inputs, n * 64, hipMemcpyDeviceToDevice, ctx->stream)); return BPPP_OK; }
   // g, H0, H1 are the first three points of the registered basis: with its comb table a commitment is <= 3 x 17 additions, not 3 x 64
   if (rp->comb) { int rc = comb_lanes(rp->comb, d_in_sc, FB_BASES, n, d_out, ctx->stream); return rc ? fail(ctx, rc, bppp_last_error(rp->comb->ctx)) : BPPP_OK; }
   k_rp_commit_inputs<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream>>>(rp->d_fixed, d_in_sc, (uint64_t)n, d_out);
@@ -441,7 +443,7 @@ int rpp_commit_rows(bppp_rp *rp, const uint32_t *d_rows, size_t nrows, uint64_t 
     BPPP_HIP(ctx, hipMalloc(&rp->d_comb_out, nrows * 64));
     rp->comb_out_rows = nrows;
   }
-  int rc = comb_msm(rp->comb, d_rows, nrows, rp->d_comb_out, ctx->stream);      // one wavefront per instance (the fold route's small batches)
+  int rc = comb_msm(rp->comb, d_rows, nrows, rp->d_comb_out, ctx->stream, COMB_ROWS_ANY, 1 + rp->st.llen + rp->st.nlen);      // one wavefront per instance (the fold route's small batches); the handle's own row length: the table may be a longer basis's
   if (rc) return fail(ctx, rc, bppp_last_error(rp->comb->ctx));
   BPPP_HIP(ctx, hipMemcpyAsync(host_out, rp->d_comb_out, nrows * 64, hipMemcpyDeviceToHost, ctx->stream));
   BPPP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -466,8 +468,18 @@ int rp_ensure_comb(bppp_rp *rp) {
     (void)hipGetLastError();                 // a failed hipMalloc leaves its error in the runtime's last-error slot: later launch checks must not see it
     return BPPP_OK;
   }
-  rp->comb_owned = true;
+  rp_set_comb(rp->twin, rp->comb);
   return BPPP_OK;
+}
+
+void rp_set_comb(bppp_rp *rp, bppp::CombTable *t) {
+  if (!rp) return;
+  if (rp->comb != t) {
+    if (t) { bppp::comb_retain(t); if (rp->is_twin) t->twins++; }
+    if (rp->comb) { if (rp->is_twin) rp->comb->twins--; bppp::comb_release(rp->comb); }
+    rp->comb = t;
+  }
+  rp_set_comb(rp->twin, t);
 }
 
 static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint8_t *rand_prefix,
@@ -483,13 +495,15 @@ static int prove_batch_one(bppp_rp *rp, size_t batch, const uint64_t *amounts, c
 template <class F> static int prove_halves(bppp_rp *rp, size_t batch, size_t split_min, F half) {
   if (batch < split_min || batch < 2 || rp->is_twin || rp->opt.no_split) return half(rp, 0, batch);
   { int rc = rp_ensure_twin(rp); if (rc) return rc; }
-  if (rp->comb && !rp->twin->comb) rp->twin->comb = rp->comb;      // not owned by the twin
+  rp_set_comb(rp->twin, rp->comb);                                 // one more holder of the same table
   rp->twin->opt = rp->opt;
   const size_t B0 = (batch + 1) / 2;
+  rp->twin->pre_inputs = rp->pre_inputs ? rp->pre_inputs + B0 * rp->st.rds.size() * 16 : nullptr;
   int rc1 = BPPP_OK;
   std::thread second([&] { rc1 = half(rp->twin, B0, batch - B0); });
   const int rc0 = half(rp, 0, B0);
   second.join();
+  rp->twin->pre_inputs = nullptr;
   if (rc0) return rc0;
   if (rc1) return fail(rp->ctx, rc1, bppp_last_error(rp->twin_ctx));
   return BPPP_OK;

@@ -476,7 +476,7 @@ int rpp_device_prove(bppp_rp *rp, const RppHostInputs &in, RppOutputs &out) {
     if (lds2 > 64 * 1024) BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_rpp_phase2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
     if (lds3 > 64 * 1024) BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_rpp_phase3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
     auto comb = [&](const uint32_t *rows, size_t n, uint32_t *dst, int hint) -> int {
-      int r_ = comb_msm(rp->comb, rows, n, dst, st, hint, 0, cscratch, cscratch_bytes);
+      int r_ = comb_msm(rp->comb, rows, n, dst, st, hint, T, cscratch, cscratch_bytes);
       return r_ ? fail(ctx, r_, bppp_last_error(rp->comb->ctx)) : BPPP_OK;
     };
     uint32_t *c_dmm = d_com, *c_r = d_com + 2 * B * 16, *c_bl = d_com + 3 * B * 16;

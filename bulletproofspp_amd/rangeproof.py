@@ -913,26 +913,51 @@ class NativeRangeProofs:
         public_amounts (bppp_rp_prove_batch_pub): per proof, the public amounts that replace the setup's (one list per proof on a typed
         handle, in pub_vt's order; one int per proof on a binary one); None = the setup's."""
         import ctypes as C
+        B = len(inputs)
+        if B == 0:
+            return []
+        amt, typ, bld, pre, plen, cf, pf = self._prove_arrays(inputs, rand_prefixes)
+        vp = lambda a: C.c_void_p(a.ctypes.data)
+        with self._public_arg(public_amounts, B, False) as pa:
+            rc = self.gpu.lib.bppp_rp_prove_batch_pub(self.h, B, vp(amt), vp(typ), vp(bld), pa, vp(pre), plen, vp(cf), vp(pf))
+        self.gpu._check(rc, "bppp_rp_prove_batch")
+        return self._prove_files(B, cf, pf)
+
+    def _prove_rows(self, inputs):
+        """one (amount, type, blinding) per range, as this class's prove_batch takes its inputs"""
+        return inputs
+
+    def _prove_arrays(self, inputs, rand_prefixes):
+        """the prove entry points' arrays for `inputs` [(amount, type, blinding) per range] per proof: amounts, types, blindings, prefixes,
+        the prefix length and the two zeroed output buffers"""
         import numpy as np
         from .capi import scalars_to_array
         B, nr = len(inputs), len(self.st.rds)
-        if B == 0:
-            return []
         if len(rand_prefixes) != B or len({len(p_) for p_ in rand_prefixes}) != 1 or any(len(row) != nr for row in inputs):
             raise ValueError("one equal-length randomness prefix per proof and one (amount, type, blinding) per range are required")
         amt = scalars_to_array([v % 2**256 for row in inputs for v, _, _ in row])
         typ = scalars_to_array([t % N for row in inputs for _, t, _ in row])
         bld = scalars_to_array([b_ % N for row in inputs for _, _, b_ in row])
-        plen = len(rand_prefixes[0])
         pre = np.frombuffer(b"".join(rand_prefixes) or b"\0", dtype=np.uint8)
         cf = np.zeros(B * self.shape["coms_bytes"], dtype=np.uint8)
         pf = np.zeros(B * self.shape["proof_bytes"], dtype=np.uint8)
-        vp = lambda a: C.c_void_p(a.ctypes.data)
-        with self._public_arg(public_amounts, B, False) as pa:
-            rc = self.gpu.lib.bppp_rp_prove_batch_pub(self.h, B, vp(amt), vp(typ), vp(bld), pa, vp(pre), plen, vp(cf), vp(pf))
-        self.gpu._check(rc, "bppp_rp_prove_batch")
+        return amt, typ, bld, pre, len(rand_prefixes[0]), cf, pf
+
+    def _prove_files(self, B, cf, pf):
         cb, pb = self.shape["coms_bytes"], self.shape["proof_bytes"]
         return [(cf[b * cb:(b + 1) * cb].tobytes(), pf[b * pb:(b + 1) * pb].tobytes()) for b in range(B)]
+
+    def share_comb(self, donor: "NativeRangeProofs"):
+        """bppp_rp_share_comb: prove over `donor`'s comb table from now on (built now if it has none).  Same context; the donor's basis
+        must extend this handle's point by point.  The table lives until its last user is closed."""
+        self.gpu._check(self.gpu.lib.bppp_rp_share_comb(self.h, donor.h), "bppp_rp_share_comb")
+
+    def comb_info(self) -> dict:
+        """bppp_rp_comb_info: window_bits, bytes, points and users of the comb table this handle proves over (all 0 without one)"""
+        import ctypes as C
+        c, nb, npt, nu = C.c_int(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self.gpu._check(self.gpu.lib.bppp_rp_comb_info(self.h, C.byref(c), C.byref(nb), C.byref(npt), C.byref(nu)), "bppp_rp_comb_info")
+        return {"window_bits": int(c.value), "bytes": int(nb.value), "points": int(npt.value), "users": int(nu.value)}
 
     def verify_batch(self, coms_files: Sequence[bytes], proof_files: Sequence[bytes], seed: Optional[bytes] = None, want_status: bool = False,
                      want_challenges: bool = False, public_amounts=None):
@@ -1069,6 +1094,33 @@ def verify_mixed(gpu, groups, seed: Optional[bytes] = None, want_status: bool = 
                                       C.c_void_p(status.ctypes.data) if want_status else None, None)
     gpu._check(rc, "bppp_rp_verify_mixed")
     return (bool(acc.value), [int(v) for v in status[:total]]) if want_status else bool(acc.value)
+
+
+def prove_mixed(gpu, groups):
+    """bppp_rp_prove_mixed: a job of SEVERAL setups in one call.  groups = [(NativeRangeProofs or NativeBinaryRangeProofs, inputs,
+    rand_prefixes)] or, with per-proof public amounts, [(handle, inputs, rand_prefixes, public_amounts)] — each as that handle's
+    prove_batch takes them.  Returns one list of (commitments file, proof file) per group, the bytes prove_batch gives.  Handles whose
+    bases extend one another prove over one shared comb table afterwards (see NativeRangeProofs.share_comb)."""
+    import ctypes as C
+    from .capi import RpProveGroup
+    groups = [tuple(g) + (None,) * (4 - len(g)) for g in groups]
+    arr = (RpProveGroup * max(len(groups), 1))()
+    keep, outs = [], []
+    vp = lambda a: a.ctypes.data
+    for g, (nat, inputs, prefixes, pub) in zip(arr, groups):
+        B = len(inputs)
+        g.rp, g.batch = (nat.h.value if nat.h else None), B
+        if B == 0:
+            outs.append(None)
+            continue
+        amt, typ, bld, pre, plen, cf, pf = nat._prove_arrays(nat._prove_rows(inputs), prefixes)
+        words = None if pub is None else nat._public_words(pub, B)
+        keep.append((amt, typ, bld, pre, cf, pf, words))
+        g.amounts, g.types, g.blinds, g.rand_prefix, g.prefix_len, g.coms_files, g.proof_files = vp(amt), vp(typ), vp(bld), vp(pre), plen, vp(cf), vp(pf)
+        g.public_amounts = None if words is None else vp(words)
+        outs.append((cf, pf))
+    gpu._check(gpu.lib.bppp_rp_prove_mixed(C.cast(arr, C.c_void_p), len(groups)), "bppp_rp_prove_mixed")
+    return [[] if o is None else nat._prove_files(len(inputs), *o) for o, (nat, inputs, _, _) in zip(outs, groups)]
 
 
 def verify_mixed_device(gpu, groups, seed: bytes, index_offset: int = 0):

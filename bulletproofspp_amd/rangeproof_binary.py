@@ -237,6 +237,9 @@ class NativeBinaryRangeProofs(NativeRangeProofs):
         """bppp_rp_prove_batch on a binary setup: inputs[b] = [(amount, blinding) per range]; public_amounts: one net_public per proof"""
         return super().prove_batch([[(v, 0, bl) for v, bl in row] for row in inputs], rand_prefixes, public_amounts=public_amounts)
 
+    def _prove_rows(self, inputs):
+        return [[(v, 0, bl) for v, bl in row] for row in inputs]
+
     def _public_words(self, public_amounts, B: int):
         """B per-proof net_public values -> [B][4] words (mod 2^256, as the constructor passes net_public)"""
         from .capi import scalars_to_array

@@ -487,7 +487,8 @@ int bppp_rp_verify_mixed(const bppp_rp_group *groups, size_t ngroups, const uint
  * the point-folding argument, which smaller batches use anyway).  A batch of 4096 proofs or more runs as two half-batches in
  * flight, the second on a twin handle with its own context that this handle creates and owns and that shares the table
  * (BPPP_RP_SPLIT_MIN=<n> moves the threshold, BPPP_RP_NO_SPLIT=1 disables it; a RangeProof.Binary handle splits from 1024 proofs,
- * BPPP_RP_SPLIT_MIN_BINARY); a handle serves one call at a time.  Same
+ * BPPP_RP_SPLIT_MIN_BINARY); a handle serves one call at a time.  Handles whose bases extend one another can prove over ONE table
+ * instead of one each (bppp_rp_share_comb, bppp_rp_prove_mixed below); a handle never passed to those builds and keeps its own.  Same
  * randomness and inputs => byte-identical files to the host protocol code (bulletproofspp_amd/rangeproof.py: prove +
  * encoding.encode_proof), on every one of these routes, which the tests assert. */
 int bppp_rp_prove_batch(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint8_t *rand_prefix,
@@ -530,6 +531,45 @@ int bppp_rp_verify_each_pub_device(bppp_rp *rp, size_t batch, const void *d_coms
 int bppp_rp_prove_batch_pub(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds,
                             const uint64_t *public_amounts, const uint8_t *rand_prefix, size_t prefix_len, uint8_t *coms_files,
                             uint8_t *proof_files);
+
+/* ---- one comb table for the handles of a basis family --------------------------------------------------------------------------
+ * Every setup's basis [g | H | G] is a prefix of the point stream its points came from (see bppp_rp_verify_mixed), and the comb table
+ * is laid out tab[window][point][multiple]: the table of the longest basis of a stream contains the table of every shorter one (same
+ * entries, the longer table's stride).  A service that proves several shapes over one stream therefore needs ONE table, not one of
+ * tens of GB per handle.
+ * bppp_rp_share_comb: rp proves over donor's comb table from now on.  Both handles on the same context; donor's basis (points 1.. of
+ * its creation's points_xy) must extend rp's point by point — the comparison bppp_rp_verify_mixed uses for its families — else
+ * BPPP_ERR_ARG.  If donor has no table yet it is built now, under donor's COMB_BUDGET / COMB_BITS options, as donor's own prover would
+ * build it (BPPP_ERR_ARG if donor's table is switched off, BPPP_ERR_HIP if it cannot be built; rp is then unchanged).  A table rp held
+ * before is released.  The table lives until the last handle using it is destroyed, in any order.  rp == donor is a no-op that only
+ * forces the build.  The files rp proves are the same bytes as over a table of its own, on every route; the window may be narrower
+ * than rp's own table would have had (the budget is spent on the longer basis).  rp's verify_each uses the table as it uses its own.
+ * bppp_rp_comb_info: window bits, bytes and number of registered points of the table this handle proves over, and how many handles
+ * (twins not counted) use it; all zero when it has none.  Any out pointer may be NULL. */
+int bppp_rp_share_comb(bppp_rp *rp, bppp_rp *donor);
+int bppp_rp_comb_info(const bppp_rp *rp, int *window_bits, size_t *table_bytes, size_t *table_points, size_t *users);
+
+/* Proving a job of SEVERAL setups in one call: group s is bppp_rp_prove_batch_pub (rp_s, batch_s, ...) — its files are byte-identical
+ * to that call's — with the handles grouped into families as bppp_rp_verify_mixed groups them.  A family whose proofs in this job,
+ * together with what its handles proved before, reach the smallest COMB_MIN among its handles gets ONE table, built over the longest
+ * basis among the family's handles given here under that handle's COMB_BUDGET / COMB_BITS; all its handles share it afterwards, as
+ * after bppp_rp_share_comb.  A family that already has tables keeps the longest one that covers its longest basis.  A handle with the
+ * table switched off (COMB_BUDGET 0) stays without.  Families below the threshold (and those whose table cannot be built) prove as
+ * bppp_rp_prove_batch_pub does.  The input commitments of all groups of a family with a table are one launch over its first three
+ * points; the groups then run in the order given, each as its handle's prover runs it (a large group still splits in two halves).
+ * BPPP_ERR_ARG: handles on different contexts, one handle in two groups, a null buffer in a non-empty group, every argument error of
+ * bppp_rp_prove_batch_pub (the message names the group and the proof).  Empty groups take no part; an empty job returns BPPP_OK.  On
+ * an error nothing is guaranteed about ANY group's output buffers (earlier groups may be complete, later ones untouched). */
+typedef struct bppp_rp_prove_group {
+  bppp_rp *rp;
+  size_t batch;                               /* proofs in this group (0 allowed) */
+  const uint64_t *amounts, *types, *blinds;   /* as bppp_rp_prove_batch: [batch][nranges][4] */
+  const uint64_t *public_amounts;             /* as bppp_rp_prove_batch_pub, may be NULL */
+  const uint8_t *rand_prefix;
+  size_t prefix_len;
+  uint8_t *coms_files, *proof_files;          /* out: the reference's files, [batch][coms_bytes], [batch][proof_bytes] of rp */
+} bppp_rp_prove_group;
+int bppp_rp_prove_mixed(const bppp_rp_prove_group *groups, size_t ngroups);
 
 /* ---- harness utility: pointX of getPoints (app/Main.hs:68-72) -------------------------------
  * For each candidate x (n x 4 uint64 in HBM) writes the affine point (x, y) with y the EVEN root of
