@@ -41,8 +41,12 @@ namespace bppp {
 // narrow window is stored re-biased by 2^(c-2), so that every consumer reads  stored - 2^(c-1)  as the signed digit whatever the width.
 __global__ void __launch_bounds__(256) k_digits(const uint32_t *__restrict__ scalars, uint64_t total, uint32_t n, uint32_t stride, int c,
                                                 int W, int acnt, RecodeK K, uint16_t *__restrict__ dig,
-                                                unsigned long long *__restrict__ negmask) {
+                                                unsigned long long *__restrict__ negmask, uint32_t *__restrict__ zero, uint32_t nzero,
+                                                uint32_t *__restrict__ zero2, uint32_t nzero2) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  // the call's counters (heavy_count, k_reduce_tail_quad's tickets, the scan's tile sums): this is the first kernel of the call
+  for (uint64_t j = i; j < nzero; j += (uint64_t)gridDim.x * blockDim.x) zero[j] = 0u;
+  for (uint64_t j = i; j < nzero2; j += (uint64_t)gridDim.x * blockDim.x) zero2[j] = 0u;
   bool valid = i < total;
   bool neg = false;
   if (valid) {
@@ -87,58 +91,42 @@ __global__ void k_hist(const uint16_t *__restrict__ dig, uint32_t n, uint32_t st
   for (int t = threadIdx.x; t < M; t += blockDim.x) out[t] = lh[t];
 }
 
-// per flat bucket: exclusive prefix over the chunks (in place) and the bucket total
-__global__ void k_chunk_prefix(uint32_t *__restrict__ blockhist, int M, int CH, uint64_t FB, uint32_t *__restrict__ count) {
-  uint64_t fb = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (fb >= FB) return;
-  uint64_t nbw = fb / M, mb = fb % M;
-  uint32_t run = 0;
-  for (int ch = 0; ch < CH; ch++) {
-    size_t at = ((size_t)nbw * CH + ch) * M + mb;
-    uint32_t t = blockhist[at];
-    blockhist[at] = run;
-    run += t;
-  }
-  count[fb] = run;
-}
-
-// three-kernel exclusive scan over `count` (tiles of 4096)
+// Exclusive scan over the bucket totals in two launches.  k_count_tiles, one lane per flat bucket: exclusive prefix over the chunks (in
+// place) and the bucket total `count`; a workgroup adds its 256 totals to the sum of its tile of SCAN_TILE buckets (tile_sums is zero at
+// launch: k_digits).  k_scan_apply, one workgroup per tile: its offset is the sum of the tile sums before it — a few hundred words that
+// every workgroup adds up for itself, which is cheaper than a launch of one workgroup that scans them — then a block-level scan of the tile.
+// Those reads grow as ntiles^2 / 2 words: 9 K at 2^20 terms (136 tiles), 0.8 M at the largest batched shapes in use (~1300 tiles).  A plan
+// may reach 2^32 buckets only on paper — the bucket array alone is 160 B each, so 288 GB of HBM hold under 2^31 / 4096 = 2^19 tiles, and
+// anything near that is seconds of accumulation; at 2^27 buckets (21 GB, 32 K tiles) it is 2 GB of L2 reads, about a millisecond.
 static constexpr int SCAN_TILE = 4096;
-__global__ void __launch_bounds__(256) k_scan_tile_sums(const uint32_t *__restrict__ in, uint64_t n, uint32_t *__restrict__ tile_sums) {
+__global__ void __launch_bounds__(256) k_count_tiles(uint32_t *__restrict__ blockhist, int M, int CH, uint64_t FB, uint32_t *__restrict__ count,
+                                                     uint32_t *__restrict__ tile_sums) {
   __shared__ uint32_t ws[4];
-  uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE;
+  const uint64_t fb = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   uint32_t s = 0;
-  for (int k = 0; k < SCAN_TILE / 256; k++) {
-    uint64_t i = base + k * 256 + threadIdx.x;
-    if (i < n) s += in[i];
+  if (fb < FB) {
+    const uint64_t nbw = fb / M, mb = fb % M;
+    for (int ch = 0; ch < CH; ch++) {
+      const size_t at = ((size_t)nbw * CH + ch) * M + mb;
+      const uint32_t t = blockhist[at];
+      blockhist[at] = s;
+      s += t;
+    }
+    count[fb] = s;
   }
   for (int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d, 64);
   if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) tile_sums[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+  if (threadIdx.x == 0) atomicAdd(tile_sums + blockIdx.x / (SCAN_TILE / 256), ws[0] + ws[1] + ws[2] + ws[3]);
 }
-__global__ void __launch_bounds__(1024) k_scan_top(uint32_t *__restrict__ tile_sums, uint32_t ntiles, uint32_t *__restrict__ total_out) {
-  // single block: exclusive scan of tile sums in place
-  __shared__ uint32_t part[1024];
-  uint32_t per = (ntiles + 1023) / 1024, lo = threadIdx.x * per, hi = min(ntiles, lo + per);
-  uint32_t s = 0;
-  for (uint32_t i = lo; i < hi; i++) s += tile_sums[i];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {
-    uint32_t v = threadIdx.x >= (uint32_t)d ? part[threadIdx.x - d] : 0;
-    __syncthreads();
-    part[threadIdx.x] += v;
-    __syncthreads();
-  }
-  uint32_t run = part[threadIdx.x] - s;
-  for (uint32_t i = lo; i < hi; i++) { uint32_t t = tile_sums[i]; tile_sums[i] = run; run += t; }
-  if (threadIdx.x == 1023) *total_out = part[1023];
-}
-__global__ void __launch_bounds__(256) k_scan_apply(const uint32_t *__restrict__ in, uint64_t n, const uint32_t *__restrict__ tile_off,
+__global__ void __launch_bounds__(256) k_scan_apply(const uint32_t *__restrict__ in, uint64_t n, const uint32_t *__restrict__ tile_sums,
                                                     uint32_t *__restrict__ out) {
-  // block-level exclusive scan of one tile (16 per thread), plus the tile offset
-  __shared__ uint32_t wsum[4];
+  // the tile's offset, then a block-level exclusive scan of the tile (16 per thread); the last lane of the last tile writes the total out[n]
+  __shared__ uint32_t wsum[4], wpre[4];
+  uint32_t pre = 0;
+  for (uint32_t i = threadIdx.x; i < blockIdx.x; i += 256) pre += tile_sums[i];
+  for (int d = 32; d >= 1; d >>= 1) pre += __shfl_down(pre, d, 64);
+  if ((threadIdx.x & 63) == 0) wpre[threadIdx.x >> 6] = pre;
   uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * 16;
   uint32_t v[16], s = 0;
 #pragma unroll
@@ -149,9 +137,10 @@ __global__ void __launch_bounds__(256) k_scan_apply(const uint32_t *__restrict__
   __syncthreads();
   uint32_t woff = 0;
   for (int w = 0; w < (int)(threadIdx.x >> 6); w++) woff += wsum[w];
-  uint32_t run = tile_off[blockIdx.x] + woff + inc - s;
+  uint32_t run = wpre[0] + wpre[1] + wpre[2] + wpre[3] + woff + inc - s;
 #pragma unroll
   for (int k = 0; k < 16; k++) { if (base + k < n) out[base + k] = run; run += v[k]; }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) out[n] = run;
 }
 
 __global__ void k_scatter(const uint16_t *__restrict__ dig, const unsigned long long *__restrict__ negmask, uint32_t n, uint32_t stride, int c,
@@ -260,11 +249,14 @@ BPPP_DI const uint32_t *partial_ptr(const uint32_t *rec_pt, uint64_t g0, uint64_
 
 __global__ void __launch_bounds__(256) k_merge(const uint32_t *__restrict__ start, const uint32_t *__restrict__ count, uint64_t FB, int L,
                                                const uint32_t *__restrict__ rec_pt, uint32_t *__restrict__ buckets,
-                                               uint2 *__restrict__ heavy_items, uint4 *__restrict__ heavy_buckets, uint32_t *__restrict__ heavy_count) {
+                                               uint2 *__restrict__ heavy_items, uint32_t *__restrict__ heavy_slot, uint4 *__restrict__ heavy_buckets,
+                                               uint32_t *__restrict__ heavy_count) {
   uint64_t fb = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (fb >= FB) return;
   uint32_t cnt = count[fb];
-  if (!cnt) return;
+  // the bucket array is not cleared between calls: an empty bucket is marked here, every other one is written by k_acc_points, below
+  // or by k_merge_heavy before a reduction reads it
+  if (!cnt) { xyzz_store(buckets + fb * XYZZ_WORDS, xyzz_inf()); return; }
   uint32_t s = start[fb];
   uint64_t g0 = s / (uint32_t)L, g1 = (uint64_t)(s + cnt - 1) / (uint32_t)L;
   if (g0 == g1) return;                       // summed and stored by its lane
@@ -272,9 +264,9 @@ __global__ void __launch_bounds__(256) k_merge(const uint32_t *__restrict__ star
   if (np > MERGE_SERIAL_MAX + 1) {
     // skewed scalars / a narrow top window: hand the bucket to wavefronts, HEAVY_CHUNK partials each
     uint32_t nch = (np + HEAVY_CHUNK - 1) / HEAVY_CHUNK;
-    uint32_t base = atomicAdd(&heavy_count[0], nch);
-    for (uint32_t j = 0; j < nch; j++) heavy_items[base + j] = make_uint2((uint32_t)fb, j);
-    if (nch > 1) heavy_buckets[atomicAdd(&heavy_count[1], 1u)] = make_uint4((uint32_t)fb, base, nch, 0u);
+    uint32_t base = atomicAdd(&heavy_count[0], nch), hb = 0;
+    if (nch > 1) { hb = atomicAdd(&heavy_count[1], 1u); heavy_buckets[hb] = make_uint4((uint32_t)fb, base, nch, 0u); }   // .w: the chunks' ticket
+    for (uint32_t j = 0; j < nch; j++) { heavy_items[base + j] = make_uint2((uint32_t)fb, j); heavy_slot[base + j] = hb; }
     return;
   }
   xyzz acc = xyzz_load(partial_ptr(rec_pt, g0, 0));
@@ -285,11 +277,15 @@ __global__ void __launch_bounds__(256) k_merge(const uint32_t *__restrict__ star
   xyzz_store(buckets + fb * XYZZ_WORDS, acc);
 }
 
-// one wavefront per (heavy bucket, chunk): lanes stride over the chunk's partials, then a shuffle tree
+// one wavefront per (heavy bucket, chunk): lanes stride over the chunk's partials, then a shuffle tree.  A bucket of more than one chunk
+// collects its chunk sums in chunk_sums; each chunk draws a ticket on the bucket's heavy_buckets entry (.w, zero from k_merge) and the
+// wavefront that arrives last adds them up.  Launched as 2048 single-wavefront workgroups, and the shape matters beyond this kernel:
+// with 512 workgroups of four wavefronts in its place the k_reduce_marg launch that follows (69 632 single-wavefront workgroups at 2^20
+// terms) ran 0.216 ms instead of 0.158 (measured both ways, same data).
 __global__ void __launch_bounds__(64) k_merge_heavy(const uint32_t *__restrict__ start, const uint32_t *__restrict__ count, int L,
-                                                    const uint32_t *__restrict__ rec_pt, uint32_t *__restrict__ buckets,
-                                                    const uint2 *__restrict__ heavy_items, const uint32_t *__restrict__ heavy_count,
-                                                    uint32_t *__restrict__ chunk_sums) {
+                                                     const uint32_t *__restrict__ rec_pt, uint32_t *__restrict__ buckets,
+                                                     const uint2 *__restrict__ heavy_items, const uint32_t *__restrict__ heavy_slot, uint4 *heavy_buckets,
+                                                     const uint32_t *__restrict__ heavy_count, uint32_t *chunk_sums) {
   const uint32_t nitems = heavy_count[0], lane = threadIdx.x;
   for (uint32_t h = blockIdx.x; h < nitems; h += gridDim.x) {
     uint2 it = heavy_items[h];
@@ -306,28 +302,35 @@ __global__ void __launch_bounds__(64) k_merge_heavy(const uint32_t *__restrict__
       xyzz o = xyzz_shfl_down(acc, d);
       if ((int)lane + d < 64) xyzz_add(acc, o);
     }
-    if (lane == 0) {
-      if (np <= HEAVY_CHUNK) xyzz_store(buckets + (size_t)fb * XYZZ_WORDS, acc);
-      else xyzz_store(chunk_sums + (size_t)h * XYZZ_WORDS, acc);
+    if (np <= HEAVY_CHUNK) {
+      if (lane == 0) xyzz_store(buckets + (size_t)fb * XYZZ_WORDS, acc);
+      continue;
     }
-  }
-}
-// buckets with more than one chunk: one wavefront adds the chunk sums
-__global__ void __launch_bounds__(64) k_merge_heavy2(const uint4 *__restrict__ heavy_buckets, const uint32_t *__restrict__ heavy_count,
-                                                     const uint32_t *__restrict__ chunk_sums, uint32_t *__restrict__ buckets) {
-  const uint32_t nb = heavy_count[1], lane = threadIdx.x;
-  for (uint32_t h = blockIdx.x; h < nb; h += gridDim.x) {
-    uint4 hb = heavy_buckets[h];
-    xyzz acc = xyzz_inf();
-    for (uint32_t j = lane; j < hb.z; j += 64) {
-      xyzz p = xyzz_load(chunk_sums + (size_t)(hb.y + j) * XYZZ_WORDS);
+    // more than one chunk: publish this chunk's sum (agent-scope release before the ticket), the last arriver acquires and adds them
+    const uint32_t nch = (np + HEAVY_CHUNK - 1) / HEAVY_CHUNK;
+    uint32_t last = 0;
+    if (lane == 0) {
+      xyzz_store(chunk_sums + (size_t)h * XYZZ_WORDS, acc);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      last = __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(heavy_buckets + heavy_slot[h]) + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nch - 1;
+    }
+    last = (uint32_t)__shfl((int)last, 0, 64);
+    if (!last) continue;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const uint32_t base = h - it.y;                        // the bucket's chunks are consecutive items
+    acc = xyzz_inf();
+    for (uint32_t j = lane; j < nch; j += 64) {
+      xyzz p = xyzz_load(chunk_sums + (size_t)(base + j) * XYZZ_WORDS);
       xyzz_add(acc, p);
     }
     for (int d = 32; d >= 1; d >>= 1) {
       xyzz o = xyzz_shfl_down(acc, d);
       if ((int)lane + d < 64) xyzz_add(acc, o);
     }
-    if (lane == 0) xyzz_store(buckets + (size_t)hb.x * XYZZ_WORDS, acc);
+    if (lane == 0) xyzz_store(buckets + (size_t)fb * XYZZ_WORDS, acc);
   }
 }
 
@@ -711,6 +714,85 @@ __global__ void __launch_bounds__(64) k_msm_small_join(const uint32_t *__restric
   if (lane == 0) xyzz_store(winsum + (size_t)w * XYZZ_WORDS, acc);
 }
 
+// The same kernel with the point of entry p + 1 in flight while entry p is added (MsmTune::acc_lds).  The gather goes straight into LDS
+// (global_load_lds_dwordx4: per-lane source address, no VGPR destination, so the prefetch costs no occupancy): a wavefront owns two stages
+// of 4 KB laid out [piece][lane] — one instruction writes piece k of all 64 lanes contiguously, and every lane reads back only its own
+// 4 x 16 bytes, so there is no barrier.  Ordinary loads whose results are used while a direct-to-LDS load is outstanding would drain it
+// early, so everything entry p + 1 needs is read BEFORE its gather is issued: its bucket (start[] at a bucket boundary, the bisect over
+// empty buckets) and the entry after it (sorted[p + 2], first used after the next wait).  Same sums in the same order as k_acc_points.
+__global__ void __launch_bounds__(256) k_acc_points_lds(const uint32_t *__restrict__ sorted, const uint32_t *__restrict__ start, uint32_t FB,
+                                                        const uint32_t *__restrict__ points, uint32_t n, uint32_t WM, int shared_pts,
+                                                        int L, uint64_t G, uint32_t *__restrict__ buckets, uint32_t *__restrict__ rec_pt) {
+  __shared__ uint4 stage[4][2][4][64];                          // [wavefront][stage][piece][lane]
+  uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= G) return;
+  const uint32_t total = start[FB];
+  const uint64_t pos0 = g * (uint64_t)L;
+  if (pos0 >= total) return;
+  const uint32_t pos1 = (uint32_t)min((uint64_t)total, pos0 + L);
+  uint32_t lo = 0, hi = FB - 1;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo + 1) / 2;
+    if (start[mid] <= (uint32_t)pos0) lo = mid; else hi = mid - 1;
+  }
+  uint32_t cur = lo, end = start[cur + 1];
+  const bool from_prev = start[cur] < (uint32_t)pos0;
+  bool first = true;
+  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t div = shared_pts ? (uint32_t)shared_pts : 1u;
+  auto gather = [&](uint32_t st, uint32_t ent, uint32_t bucket) {
+    const uint32_t idx = ent & 0x7FFFFFFFu;
+    const size_t pidx = shared_pts == 1 ? (size_t)idx : (size_t)((bucket / WM) / div) * n + idx;
+    const uint32_t *src = points + pidx * 16;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + 4 * k),
+                                       (__attribute__((address_space(3))) void *)&stage[wv][st][k][0], 16, 0, 0);
+  };
+  uint32_t e = sorted[pos0], e1 = (pos0 + 1 < pos1) ? sorted[pos0 + 1] : 0u, st = 0;
+  gather(0, e, cur);
+  xyzz acc = xyzz_inf();
+  for (uint32_t p = (uint32_t)pos0; p < pos1; p++) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the point of entry p has landed
+    uint32_t w[16];
+#pragma unroll
+    for (int k = 0; k < 4; k++) { const uint4 v = stage[wv][st][k][lane]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
+    // the bucket of entry p + 1
+    const bool more = p + 1 < pos1, boundary = more && p + 1 == end;
+    uint32_t ncur = cur, nend = end;
+    if (boundary) {
+      ncur = cur + 1; nend = start[ncur + 1];
+      if (nend <= p + 1) {                                      // empty buckets: bisect for the one that holds p + 1 (see k_acc_points)
+        uint32_t lo2 = ncur + 1, hi2 = FB - 1;
+        while (lo2 < hi2) {
+          const uint32_t mid = lo2 + (hi2 - lo2 + 1) / 2;
+          if (start[mid] <= p + 1) lo2 = mid; else hi2 = mid - 1;
+        }
+        ncur = lo2; nend = start[ncur + 1];
+      }
+    }
+    const uint32_t e2 = (p + 2 < pos1) ? sorted[p + 2] : 0u;
+    if (more) gather(st ^ 1u, e1, ncur);
+    fe fx, fy;
+#pragma unroll
+    for (int i = 0; i < 8; i++) { fx.v[i] = w[i]; fy.v[i] = w[8 + i]; }
+    aff P; P.x = fq_from_fe(fx); P.y = fq_from_fe(fy);
+    xyzz_madd(acc, aff_cneg(P, (e >> 31) & 1u));
+    if (boundary) {
+      // the run ends inside this lane: head partial if it came from the previous lane, else complete
+      if (first && from_prev) xyzz_store(rec_pt + (2 * g) * XYZZ_WORDS, acc);
+      else xyzz_store(buckets + (size_t)cur * XYZZ_WORDS, acc);
+      first = false; acc = xyzz_inf();
+      cur = ncur; end = nend;
+    }
+    e = e1; e1 = e2; st ^= 1u;
+  }
+  const bool hi_part = first && from_prev, ti = end > pos1;
+  if (hi_part) xyzz_store(rec_pt + (2 * g) * XYZZ_WORDS, acc);
+  else if (ti) xyzz_store(rec_pt + (2 * g + 1) * XYZZ_WORDS, acc);
+  else xyzz_store(buckets + (size_t)cur * XYZZ_WORDS, acc);
+}
+
 // ------------------------------------------------------------------------------------------------
 // host orchestration
 static int choose_window(size_t n, size_t batch, const MsmTune &tune) {
@@ -932,46 +1014,46 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
     uint2 *heavy_items = cv.take<uint2>(hmax);
     uint4 *heavy_buckets = cv.take<uint4>(hmax);
     uint32_t *chunk_sums = cv.take<uint32_t>(hmax * XYZZ_WORDS);
-    uint32_t *heavy_count = cv.take<uint32_t>(4 + (p.marg ? 2 * (size_t)p.NS : 0));
-    uint32_t *tail_cnt = heavy_count + 4;           // k_reduce_tail_quad's tickets, zeroed with heavy_count
+    // counters and tickets, zeroed by k_digits (with the scan's tile sums): [0], [1] heavy items / buckets, [4..] k_reduce_tail_quad's tickets
+    const size_t nzero = 4 + (p.marg ? 2 * (size_t)p.NS : 0);
+    uint32_t *heavy_count = cv.take<uint32_t>(nzero);
+    uint32_t *tail_cnt = heavy_count + 4;
     uint32_t *tail_part = cv.take<uint32_t>(p.marg && p.mg.quad ? (size_t)p.NS * 2 * 16 * 2 * XYZZ_WORDS : 0);
     uint32_t *red = cv.take<uint32_t>(p.marg ? (size_t)p.NS * (p.mg.HI + p.mg.LO) * XYZZ_WORDS : (size_t)p.NS * p.WPW * 2 * XYZZ_WORDS);
     uint32_t *winsum = cv.take<uint32_t>((size_t)p.NS * 2 * XYZZ_WORDS);
     uint32_t *out_aff = cv.take<uint32_t>((size_t)batch * 16);
+    uint32_t *heavy_slot = cv.take<uint32_t>(hmax);     // per heavy item: its bucket's entry in heavy_buckets (the chunks' ticket)
     if (!pass) { need = cv.off; int rc = ensure_workspace(ctx, need); if (rc) return rc; continue; }
 
     hipStream_t st = ctx->stream;
     const size_t lds = (size_t)p.M * 4;
-    if (lds > 64 * 1024) {
+    if (lds > 64 * 1024 && lds > ctx->sort_lds_set) {
       BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      ctx->sort_lds_set = lds;
     }
     prof_mark(ctx, 0);
     // 1. digits
     uint64_t total_sc = (uint64_t)batch * n;
     k_digits<<<dim3((unsigned)((total_sc + 255) / 256)), dim3(256), 0, st>>>((const uint32_t *)d_scalars, total_sc, (uint32_t)n, stride, c, p.W, p.acnt,
-                                                                            make_recode_k(c, p.W, p.acnt), dig, negmask);
+                                                                            make_recode_k(c, p.W, p.acnt), dig, negmask, heavy_count, (uint32_t)nzero, tiles, (uint32_t)p.ntiles);
     prof_mark(ctx, 1);
     // 2. sort
     k_hist<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(dig, (uint32_t)n, stride, c, p.CH, blockhist);
     // flat: the (window, chunk) histograms of an instance are W * CH chunks of ONE bucket set (same memory layout)
-    k_chunk_prefix<<<dim3((unsigned)((p.FB + 255) / 256)), dim3(256), 0, st>>>(blockhist, p.M, p.flat ? p.W * p.CH : p.CH, p.FB, count);
-    k_scan_tile_sums<<<dim3(p.ntiles), dim3(256), 0, st>>>(count, p.FB, tiles);
-    k_scan_top<<<dim3(1), dim3(1024), 0, st>>>(tiles, (uint32_t)p.ntiles, start + p.FB);
+    k_count_tiles<<<dim3((unsigned)((p.FB + 255) / 256)), dim3(256), 0, st>>>(blockhist, p.M, p.flat ? p.W * p.CH : p.CH, p.FB, count, tiles);
     k_scan_apply<<<dim3(p.ntiles), dim3(256), 0, st>>>(count, p.FB, tiles, start);
     k_scatter<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(dig, negmask, (uint32_t)n, stride, c, p.CH, p.W, blockhist, start, sorted,
                                                                              p.flat ? (uint32_t)table_stride : 0u);
-    BPPP_HIP(ctx, hipMemsetAsync(buckets, 0, (size_t)p.FB * XYZZ_WORDS * 4, st));
-    BPPP_HIP(ctx, hipMemsetAsync(heavy_count, 0, (4 + (p.marg ? 2 * (size_t)p.NS : 0)) * 4, st));
     prof_mark(ctx, 2);
     if (ctx->pre_acc) { auto f = ctx->pre_acc; ctx->pre_acc = nullptr; int rc_ = f(ctx->pre_acc_arg); if (rc_) return rc_; }
     // 3. accumulate
-    k_acc_points<<<dim3((unsigned)((p.G + 255) / 256)), dim3(256), 0, st>>>(sorted, start, (uint32_t)p.FB, (const uint32_t *)d_points, (uint32_t)n,
-                                                                           (uint32_t)(p.Wc * p.M), shared_points, p.L, p.G, buckets, rec_pt);
+    ctx->last_acc_lds = ctx->tune.acc_lds ? 1 : 0;
+    (ctx->tune.acc_lds ? k_acc_points_lds : k_acc_points)<<<dim3((unsigned)((p.G + 255) / 256)), dim3(256), 0, st>>>(
+        sorted, start, (uint32_t)p.FB, (const uint32_t *)d_points, (uint32_t)n, (uint32_t)(p.Wc * p.M), shared_points, p.L, p.G, buckets, rec_pt);
     prof_mark(ctx, 3);
-    k_merge<<<dim3((unsigned)((p.FB + 255) / 256)), dim3(256), 0, st>>>(start, count, p.FB, p.L, rec_pt, buckets, heavy_items, heavy_buckets, heavy_count);
-    k_merge_heavy<<<dim3(2048), dim3(64), 0, st>>>(start, count, p.L, rec_pt, buckets, heavy_items, heavy_count, chunk_sums);
-    k_merge_heavy2<<<dim3(256), dim3(64), 0, st>>>(heavy_buckets, heavy_count, chunk_sums, buckets);
+    k_merge<<<dim3((unsigned)((p.FB + 255) / 256)), dim3(256), 0, st>>>(start, count, p.FB, p.L, rec_pt, buckets, heavy_items, heavy_slot, heavy_buckets, heavy_count);
+    k_merge_heavy<<<dim3(2048), dim3(64), 0, st>>>(start, count, p.L, rec_pt, buckets, heavy_items, heavy_slot, heavy_buckets, heavy_count, chunk_sums);
     prof_mark(ctx, 4);
     // 4. bucket reduce
     if (p.RG) {

@@ -237,6 +237,12 @@ extern "C" int bppp_test_last_mixed_msm_terms(bppp_ctx *ctx, uint64_t *terms) {
   return BPPP_OK;
 }
 
+extern "C" int bppp_test_last_acc_kernel(bppp_ctx *ctx, int *lds) {
+  if (!ctx || !lds) return BPPP_ERR_ARG;
+  *lds = ctx->last_acc_lds;
+  return BPPP_OK;
+}
+
 extern "C" int bppp_test_rp_last_verify_counts(bppp_rp *rp, uint64_t *combined_msms, uint64_t *each_passes) {
   if (!rp || !combined_msms || !each_passes) return BPPP_ERR_ARG;
   *combined_msms = rp->n_combined;

@@ -35,6 +35,9 @@ int bppp_test_mulmod_rate(bppp_ctx *ctx, int iters, double *mulmods_per_sec);
 /* Terms of the one MSM the last bppp_rp_verify_mixed* call on this context ran (0 after an empty job): a test sees that the shared
  * bases of setups from one point stream were merged. */
 int bppp_test_last_mixed_msm_terms(bppp_ctx *ctx, uint64_t *terms);
+/* The accumulate kernel the last MSM of the general pipeline on this context launched: 0 = k_acc_points, 1 = k_acc_points_lds
+ * (BPPP_ACC_LDS), -1 = none yet. */
+int bppp_test_last_acc_kernel(bppp_ctx *ctx, int *lds);
 /* What the last verification on this handle ran (bppp_rp_verify_batch*, _shard_device, _each*, and its group's share of
  * bppp_rp_verify_mixed*): combined MSMs (the accept check and every bisection step) and per-proof passes.  A test sees the cost of a
  * culprit search without timing it. */
