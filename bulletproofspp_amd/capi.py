@@ -34,6 +34,7 @@ SYMBOLS = [
     "bppp_rp_public_count", "bppp_rp_verify_batch_pub", "bppp_rp_verify_batch_pub_device", "bppp_rp_verify_shard_pub_device", "bppp_rp_verify_each_pub",
     "bppp_rp_verify_each_pub_device", "bppp_rp_prove_batch_pub",
     "bppp_rp_share_comb", "bppp_rp_comb_info", "bppp_rp_prove_mixed",
+    "bppp_rp_prove_batch_device",
 ]
 
 
@@ -150,6 +151,7 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_share_comb.argtypes = [vp, vp]
     lib.bppp_rp_comb_info.argtypes = [vp, C.POINTER(i), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     lib.bppp_rp_prove_mixed.argtypes = [vp, sz]
+    lib.bppp_rp_prove_batch_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp, vp]
     lib.bppp_profile_enable.argtypes = [vp, i]
     lib.bppp_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), i]
     return lib
@@ -171,6 +173,7 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_last_acc_kernel.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_rp_last_verify_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.bppp_test_rp_set_each_chunk.argtypes = [vp, sz]
+    lib.bppp_test_rp_witness_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     return lib
 
 
@@ -472,6 +475,13 @@ class Bppp:
         if arr.nbytes:
             self.upload(p, arr)
         return p
+
+    # ---- range proofs from HBM to HBM
+    def rp_prove_batch_device(self, rp, batch: int, d_amounts: int, d_types: int, d_blinds: int, d_public_amounts: int, d_rand_prefix: int, prefix_len: int,
+                              d_coms_files: int, d_proof_files: int):
+        """bppp_rp_prove_batch_device: `rp` a bppp_rp handle, every buffer a device pointer (0 = NULL); the files are complete in HBM on return"""
+        self._check(self.lib.bppp_rp_prove_batch_device(rp, batch, _ptr(d_amounts), _ptr(d_types), _ptr(d_blinds), _ptr(d_public_amounts), _ptr(d_rand_prefix),
+                                                        prefix_len, _ptr(d_coms_files), _ptr(d_proof_files)), "bppp_rp_prove_batch_device")
 
     # ---- profiling
     def profile_enable(self, on: bool = True):

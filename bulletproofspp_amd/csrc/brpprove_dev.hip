@@ -133,37 +133,60 @@ __global__ void __launch_bounds__(256) k_brpp_combine(BrpDims D, uint32_t batch,
   else fr_store(a_lx + (size_t)b * 16, fr_add(acc, fr_load(r + (size_t)(2 + D.nlen) * 8)));
 }
 
+int brp_carve(bppp_rp *rp, size_t B, size_t prefix_len, bool own_prefix, RppWork &W) {
+  const bppp_rps::Setup &S = rp->st;
+  const size_t nr = S.rds.size(), nlen = S.nlen, nlive = S.nlive, k = S.rounds, T = 3 + nlen, nd = nlen + 3;
+  const uint32_t stride = rp->D.text_stride;
+  W = RppWork{};
+  for (int pass = 0; pass < 2; pass++) {
+    Carver cv(pass ? rp->pwork : nullptr, rp->pwork_bytes);
+    W.in_sc = cv.take<uint32_t>(B * nr * 24); W.in_pt = cv.take<uint32_t>(B * nr * 16); W.bits = cv.take<uint8_t>(B * nlive + 16);
+    W.rnd = cv.take<uint32_t>(B * nd * 8); W.rows_dm_m = cv.take<uint32_t>(B * T * 8); W.row_bl = cv.take<uint32_t>(B * T * 8); W.aux = cv.take<uint32_t>(B * 16);
+    W.ch = cv.take<uint32_t>(B * 56); W.es = cv.take<uint32_t>(B * 8); W.tstart = cv.take<uint32_t>(B); W.ptbuf = cv.take<uint32_t>(B * (1 + nr) * 16);
+    W.a_s = cv.take<uint32_t>(B * 8); W.a_q = cv.take<uint32_t>(B * 8); W.a_lx = cv.take<uint32_t>(B * 16); W.a_nx = cv.take<uint32_t>(B * nlen * 8);
+    W.p_sp = cv.take<uint32_t>(B * 8); W.p_norm = cv.take<uint32_t>(B * nlen * 8); W.p_cs = cv.take<uint32_t>(B * 16); W.p_init = cv.take<uint32_t>(B * (2 + nr) * 8);
+    W.text = cv.take<uint8_t>(B * (size_t)stride + 64); W.prefix_own = cv.take<uint8_t>((own_prefix ? B * prefix_len : 0) + 16); W.hdrs = cv.take<uint8_t>(RppTranscript::hdr_bytes(2 + k) + 16);
+    W.d_resp = cv.take<uint32_t>(k * B * 32 + 16); W.d_com = cv.take<uint32_t>(2 * B * 16 + 16);
+    W.cscratch = cv.take<uint32_t>(comb_rows_scratch_bytes(B) / 4 + 16);
+    W.wn = cv.take<uint32_t>(B * S.fn * 8 + 8); W.wl = cv.take<uint32_t>(B * S.fl * 8 + 8); W.status = cv.take<uint32_t>(B);
+    if (!pass) { int rc = rpp_ensure_pwork(rp, cv.off); if (rc) return rc; }
+  }
+  W.prefix = W.prefix_own;
+  return BPPP_OK;
+}
+
 int brp_device_prove(bppp_rp *rp, const BrpHostInputs &in, BrpOutputs &out) {
+  bppp_ctx *ctx = rp->ctx;
+  hipStream_t st = ctx->stream;
+  const bppp_rps::Setup &S = rp->st;
+  const size_t B = in.batch, nr = S.rds.size(), nlive = S.nlive;
+  RppWork W;
+  { int rc = brp_carve(rp, B, in.prefix_len, true, W); if (rc) return rc; }
+  const uint32_t *d_pub = nullptr;                 // per-proof net_public (bppp_rp_prove_batch_pub)
+  if (in.pub) { int rc_ = rp_upload_public(rp, in.pub, B * 4, &d_pub); if (rc_) return rc_; }
+  BPPP_HIP(ctx, hipMemcpyAsync(W.in_sc, in.in_sc, B * nr * 96, hipMemcpyHostToDevice, st));
+  if (nlive) BPPP_HIP(ctx, hipMemcpyAsync(W.bits, in.bits, B * nlive, hipMemcpyHostToDevice, st));
+  if (in.prefix_len) BPPP_HIP(ctx, hipMemcpyAsync(W.prefix_own, in.prefix, B * in.prefix_len, hipMemcpyHostToDevice, st));
+  return brp_prove_body(rp, B, W, in.prefix_len, d_pub, &out, nullptr);
+}
+
+int brp_prove_body(bppp_rp *rp, size_t B, const RppWork &W, size_t prefix_len, const uint32_t *d_pub, BrpOutputs *host, RppDevResults *dev) {
   bppp_ctx *ctx = rp->ctx;
   hipStream_t st = ctx->stream;
   const bppp_rps::Setup &S = rp->st;
   const bppp_brp_tabs *tb = rp->btabs;
   if (!rp->comb || !tb) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: the device prover needs the comb table of the setup");
   const BrpDims D = tb->D;
-  const size_t B = in.batch, nr = S.rds.size(), nlen = S.nlen, nlive = S.nlive, k = S.rounds, T = 3 + nlen, nd = nlen + 3;
+  const size_t nr = S.rds.size(), nlen = S.nlen, k = S.rounds, T = 3 + nlen, nd = nlen + 3;
   if (S.llen != 2 || rp->comb->T < T) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: binary setup and comb table disagree");
-  uint32_t *in_sc = nullptr, *in_pt = nullptr, *rnd = nullptr, *row_d = nullptr, *row_bl = nullptr, *aux = nullptr, *ch = nullptr, *es = nullptr, *tstart = nullptr,
-           *ptbuf = nullptr, *a_s = nullptr, *a_q = nullptr, *a_lx = nullptr, *a_nx = nullptr, *p_sp = nullptr, *p_norm = nullptr, *p_cs = nullptr, *p_init = nullptr,
-           *d_resp = nullptr, *d_com = nullptr, *cscratch = nullptr;
-  uint8_t *bits = nullptr, *text = nullptr, *prefix = nullptr, *hdrs = nullptr;
-  const uint32_t stride = rp->D.text_stride;
-  for (int pass = 0; pass < 2; pass++) {
-    Carver cv(pass ? rp->pwork : nullptr, rp->pwork_bytes);
-    in_sc = cv.take<uint32_t>(B * nr * 24); in_pt = cv.take<uint32_t>(B * nr * 16); bits = cv.take<uint8_t>(B * nlive + 16);
-    rnd = cv.take<uint32_t>(B * nd * 8); row_d = cv.take<uint32_t>(B * T * 8); row_bl = cv.take<uint32_t>(B * T * 8); aux = cv.take<uint32_t>(B * 16);
-    ch = cv.take<uint32_t>(B * 56); es = cv.take<uint32_t>(B * 8); tstart = cv.take<uint32_t>(B); ptbuf = cv.take<uint32_t>(B * (1 + nr) * 16);
-    a_s = cv.take<uint32_t>(B * 8); a_q = cv.take<uint32_t>(B * 8); a_lx = cv.take<uint32_t>(B * 16); a_nx = cv.take<uint32_t>(B * nlen * 8);
-    p_sp = cv.take<uint32_t>(B * 8); p_norm = cv.take<uint32_t>(B * nlen * 8); p_cs = cv.take<uint32_t>(B * 16); p_init = cv.take<uint32_t>(B * (2 + nr) * 8);
-    text = cv.take<uint8_t>(B * (size_t)stride + 64); prefix = cv.take<uint8_t>(B * in.prefix_len + 16); hdrs = cv.take<uint8_t>(RppTranscript::hdr_bytes(2 + k) + 16);
-    d_resp = cv.take<uint32_t>(k * B * 32 + 16); d_com = cv.take<uint32_t>(2 * B * 16 + 16);
-    cscratch = cv.take<uint32_t>(comb_rows_scratch_bytes(B) / 4 + 16);
-    if (!pass) { int rc = rpp_ensure_pwork(rp, cv.off); if (rc) return rc; }
-  }
-  const uint32_t *d_pub = nullptr;                 // per-proof net_public (bppp_rp_prove_batch_pub)
-  if (in.pub) { int rc_ = rp_upload_public(rp, in.pub, B * 4, &d_pub); if (rc_) return rc_; }
-  BPPP_HIP(ctx, hipMemcpyAsync(in_sc, in.in_sc, B * nr * 96, hipMemcpyHostToDevice, st));
-  if (nlive) BPPP_HIP(ctx, hipMemcpyAsync(bits, in.bits, B * nlive, hipMemcpyHostToDevice, st));
-  if (in.prefix_len) BPPP_HIP(ctx, hipMemcpyAsync(prefix, in.prefix, B * in.prefix_len, hipMemcpyHostToDevice, st));
+  uint32_t *const in_sc = W.in_sc, *const in_pt = W.in_pt, *const rnd = W.rnd, *const row_d = W.rows_dm_m, *const row_bl = W.row_bl, *const aux = W.aux, *const ch = W.ch,
+           *const es = W.es, *const tstart = W.tstart, *const ptbuf = W.ptbuf, *const a_s = W.a_s, *const a_q = W.a_q, *const a_lx = W.a_lx, *const a_nx = W.a_nx,
+           *const p_sp = W.p_sp, *const p_norm = W.p_norm, *const p_cs = W.p_cs, *const p_init = W.p_init, *const d_resp = W.d_resp, *const d_com = W.d_com,
+           *const cscratch = W.cscratch;
+  uint8_t *const bits = W.bits, *const text = W.text, *const hdrs = W.hdrs;
+  const uint8_t *const prefix = W.prefix;
+  BrpOutputs none{};
+  BrpOutputs &out = host ? *host : none;
   // the oracle calls of proveBRPM: oracle' (dCom : nComs) -> q x r (:179), oracle [blCom] -> t (:189); small batches hash on the host cores
   RppTranscript tr;
   int rc = tr.begin(rp, B, {RppCall{(uint32_t)(1 + nr), 3, 0}, RppCall{1, 1, 6}}, k, B <= rp->opt.host_oracle_prove, text, tstart, hdrs, ch, es); if (rc) return rc;
@@ -172,11 +195,11 @@ int brp_device_prove(bppp_rp *rp, const BrpHostInputs &in, BrpOutputs &out) {
     return r_ ? fail(ctx, r_, bppp_last_error(rp->comb->ctx)) : BPPP_OK;
   };
   uint32_t *c_d = d_com, *c_bl = d_com + B * 16;
-  rc = rpp_draws(ctx, prefix, in.prefix_len, B, nd, rnd); if (rc) return rc;
+  rc = rpp_draws(ctx, prefix, prefix_len, B, nd, rnd); if (rc) return rc;
   { const uint64_t n = (uint64_t)B * T; k_brpp_row_d<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(D, (uint32_t)B, (uint32_t)nd, rnd, bits, row_d); }
   BPPP_HIP(ctx, hipGetLastError());
   rc = rpp_commit_inputs(rp, in_sc, B * nr, in_pt); if (rc) return rc;                 // scalarRPW' (Internal.hs:56-57): v g + bl h0
-  BPPP_HIP(ctx, hipMemcpyAsync(out.input_coms, in_pt, B * nr * 64, hipMemcpyDeviceToHost, st));
+  if (host) BPPP_HIP(ctx, hipMemcpyAsync(out.input_coms, in_pt, B * nr * 64, hipMemcpyDeviceToHost, st));
   rc = comb(row_d, c_d, COMB_ROWS_ANY); if (rc) return rc;                   // bits and a few blinders: most scalars are 0 or 1
   BPPP_HIP(ctx, hipMemcpy2DAsync(ptbuf, (1 + nr) * 64, c_d, 64, 64, B, hipMemcpyDeviceToDevice, st));
   BPPP_HIP(ctx, hipMemcpy2DAsync(ptbuf + 16, (1 + nr) * 64, in_pt, nr * 64, nr * 64, B, hipMemcpyDeviceToDevice, st));
@@ -193,7 +216,8 @@ int brp_device_prove(bppp_rp *rp, const BrpHostInputs &in, BrpOutputs &out) {
     k_brpp_combine<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(D, (uint32_t)B, (uint32_t)nd, rnd, bits, aux, in_sc, ch, p_sp, p_norm, p_init, a_s, a_lx, a_nx); }
   BPPP_HIP(ctx, hipGetLastError());
   std::vector<uint64_t> hcom;
-  rc = rpp_argument_stream(rp, tr, 2, B, a_s, a_q, a_nx, p_cs, a_lx, d_resp, out.resp, out.wit_norm, out.wit_lin, d_com, 2 * B, hcom); if (rc) return rc;
+  rc = rpp_argument_stream(rp, tr, 2, B, a_s, a_q, a_nx, p_cs, a_lx, d_resp, out.resp, out.wit_norm, out.wit_lin, d_com, 2 * B, hcom, dev, W.wn, W.wl); if (rc) return rc;
+  if (dev) { dev->input_coms = in_pt; dev->coms = d_com; dev->resp = d_resp; return BPPP_OK; }
   memcpy(out.c_d, hcom.data(), B * 64); memcpy(out.c_bl, hcom.data() + B * 8, B * 64);
   return BPPP_OK;
 }

@@ -531,6 +531,28 @@ int nlb_round_collapse_dev(bppp_nlb *o, const uint32_t *d_es) {
   o->n = o->n ? n2 : 0; o->l = o->l ? l2 : 0; o->cur = d; o->folds++;
   return BPPP_OK;
 }
+// getWitness of every proof left in HBM (fixed-basis mode): what bppp_nlb_get_witness multiplies on the host — wn [batch][n] = nn_b x_b,
+// wl [batch][l] = ln_b lx_b at the current lengths, canonical
+__global__ void __launch_bounds__(256) k_nlb_witness(const uint32_t *__restrict__ x, const uint32_t *__restrict__ lx, const uint32_t *__restrict__ stt, uint32_t batch,
+                                                     uint32_t n, uint32_t l, uint32_t xstride, uint32_t lstride, uint32_t *__restrict__ wn, uint32_t *__restrict__ wl) {
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (uint64_t)batch * (n + l)) return;
+  const uint32_t b = (uint32_t)(g / (n + l)), i = (uint32_t)(g % (n + l));
+  const uint32_t *S = stt + (size_t)b * NLB_ST * 8;
+  if (i < n) fe_store(wn + ((size_t)b * n + i) * 8, fe_mul<1>(fe_load(x + ((size_t)b * xstride + i) * 8), fe_load(S + NLB_ST_NN * 8)));
+  else fe_store(wl + ((size_t)b * l + (i - n)) * 8, fe_mul<1>(fe_load(lx + ((size_t)b * lstride + (i - n)) * 8), fe_load(S + NLB_ST_LN * 8)));
+}
+int nlb_witness_dev(bppp_nlb *o, size_t fn, size_t fl, uint32_t *d_wn, uint32_t *d_wl) {
+  if (!o || !o->comb || o->n != fn || o->l != fl || (fn && !d_wn) || (fl && !d_wl)) return BPPP_ERR_ARG;
+  bppp_ctx *ctx = o->ctx;
+  hipSetDevice(ctx->device);
+  const uint64_t tot = (uint64_t)o->batch * (fn + fl);
+  if (!tot) return BPPP_OK;
+  k_nlb_witness<<<dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream>>>(o->x[o->cur], o->lx[o->cur], o->stt, (uint32_t)o->batch, (uint32_t)fn, (uint32_t)fl,
+                                                                                  (uint32_t)o->xstride, (uint32_t)o->lstride, d_wn, d_wl);
+  NLB_HIP(o, hipGetLastError());
+  return BPPP_OK;
+}
 }  // namespace bppp
 extern "C" {
 int bppp_nlb_create(bppp_ctx *ctx, size_t batch, const uint64_t *s, const uint64_t g_xy[8], const uint64_t *q, const uint64_t *norm_x,

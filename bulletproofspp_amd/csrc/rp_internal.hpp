@@ -171,6 +171,8 @@ struct bppp_rp {
   // per-proof public amounts of the *_pub entry points (bppp_rp_public_count per proof): grow-only device copy of one call's canonical
   // scalars, [batch][public_count][8] words
   uint32_t *d_pub = nullptr; size_t d_pub_bytes = 0;
+  // bppp_rp_prove_batch_device: the per-range data of the witness kernels (csrc/rpwitness.hip.h), uploaded at the first device call
+  uint32_t *d_wit = nullptr;
 };
 
 // public amounts per proof of the *_pub entry points: npub of a typed handle with types, 1 of a conserved binary handle, else 0

@@ -514,18 +514,44 @@ extern "C" int bppp_rp_prove_batch(bppp_rp *rp, size_t batch, const uint64_t *am
   return bppp_rp_prove_batch_pub(rp, batch, amounts, types, blinds, nullptr, rand_prefix, prefix_len, coms_files, proof_files);
 }
 
-extern "C" int bppp_rp_prove_batch_pub(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint64_t *public_amounts,
-                                       const uint8_t *rand_prefix, size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files) {
+// shapes the device algebra does not serve: it looks digits up in a per-proof table of reciprocals held in LDS (256 entries, up to 2048 for wider digit
+// bases); bases beyond that take the host-algebra path (prove_batch_one)
+static bool lds_gate(const Setup &st) {
+  uint32_t max_base = 0;
+  for (const RangeData &rd : st.rds) max_base = std::max(max_base, rd.base);
+  return max_base > 2048 || (max_base > 256 && st.rds.size() > 256);
+}
+// bppp_rp_prove_batch_device: does this call run as one stream of kernels over the handle's comb table (csrc/rpprove_dev.hip, csrc/brpprove_dev.hip)?
+// Otherwise its inputs come down and the host-buffer routes below serve it.
+static bool has_device_stream(const bppp_rp *rp) {
+  return rp->comb && !rp->opt.host_algebra && !rp->opt.fold_points && (rp->st.kind == 1 || !lds_gate(rp->st));
+}
+
+// bppp_rp_prove_batch_pub (device = false: every buffer on the host) and bppp_rp_prove_batch_device (device = true: every buffer in HBM)
+static int prove_entry(bppp_rp *rp, size_t batch, const void *amounts_, const void *types_, const void *blinds_, const void *public_amounts, const void *rand_prefix_,
+                       size_t prefix_len, void *coms_files_, void *proof_files_, bool device) {
   if (!rp) return BPPP_ERR_ARG;
   bppp_ctx *ctx = rp->ctx;
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
   if (!batch) return BPPP_OK;
+  const uint64_t *amounts = (const uint64_t *)amounts_, *types = (const uint64_t *)types_, *blinds = (const uint64_t *)blinds_;
+  const uint8_t *rand_prefix = (const uint8_t *)rand_prefix_;
+  uint8_t *coms_files = (uint8_t *)coms_files_, *proof_files = (uint8_t *)proof_files_;
   if (!amounts || (!types && rp->st.kind == 0) || !blinds || (prefix_len && !rand_prefix) || !coms_files || !proof_files || batch >= (1u << 20) || prefix_len > 4096)
     return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: bad arguments");
-  std::vector<uint64_t> canon;                  // per-proof public amounts as canonical scalars: what a handle created with them holds
-  if (public_amounts) { int rc = rp_public_canon(rp, batch, public_amounts, canon); if (rc) return rc; }
-  const uint64_t *pub = public_amounts ? canon.data() : nullptr;
   const size_t npub = rp_public_count(rp);
+  std::vector<uint64_t> canon;                  // per-proof public amounts as canonical scalars: what a handle created with them holds
+  if (public_amounts) {
+    std::vector<uint64_t> raw;
+    if (device && npub) {                       // read back and checked on the host, as the verifier's *_pub_device entry points do
+      hipSetDevice(ctx->device);
+      raw.resize(batch * npub * 4);
+      BPPP_HIP(ctx, hipMemcpyAsync(raw.data(), public_amounts, raw.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+      BPPP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    int rc = rp_public_canon(rp, batch, device ? raw.data() : (const uint64_t *)public_amounts, canon); if (rc) return rc;
+  }
+  const uint64_t *pub = public_amounts ? canon.data() : nullptr;
   auto pub_at = [&](size_t b0) -> const uint64_t * { return pub ? pub + 4 * npub * b0 : nullptr; };
   const size_t comb_min = rp->opt.comb_min;     // default 1024: the table costs ~0.3 s and tens of GB once: worth it for a handle that proves large batches
   // ... or one that has proved that many proofs in smaller batches: with the table in place every batch size is faster (one 64by64 proof:
@@ -534,41 +560,80 @@ extern "C" int bppp_rp_prove_batch_pub(bppp_rp *rp, size_t batch, const uint64_t
     rp->proved_total += batch;
     if (batch >= comb_min || rp->proved_total >= comb_min) { int rc = rp_ensure_comb(rp); if (rc) return rc; }
   }
-  // proofs [b0, b0 + n) of the caller's arrays (prove_halves)
   const size_t nr = rp->st.rds.size(), cb = rp->D.coms_bytes, pb = rp->D.proof_bytes;
-  auto prefix_at = [&](size_t b0) { return rand_prefix ? rand_prefix + prefix_len * b0 : nullptr; };
-  // RangeProof.Binary: with the comb table in place the whole proof is a stream of kernels (csrc/brpprove_dev.hip); before that (small
-  // batches) and under BPPP_RP_HOST_ALGEBRA the field algebra and the hashing run on the host cores (prove_batch_binary)
-  if (rp->st.kind == 1) {
-    // two half-batches in flight (as below for the typed-reciprocal proofs): the transcript hashing, the phase and the round kernels of one half —
-    // ~14 ms per 1024 proofs of mostly one-lane-per-proof chains — run under the comb additions of the other
-    if (rp->comb && !rp->opt.host_algebra && !rp->opt.fold_points)
-      return prove_halves(rp, batch, rp->opt.split_min_binary, [&](bppp_rp *h, size_t b0, size_t n) {
-        return prove_batch_binary_dev(h, n, amounts + 4 * nr * b0, blinds + 4 * nr * b0, prefix_at(b0), prefix_len, coms_files + cb * b0, proof_files + pb * b0, b0,
-                                      pub_at(b0));
-      });
-    return prove_batch_binary(rp, batch, amounts, blinds, rand_prefix, prefix_len, coms_files, proof_files, pub);
+  // the slow path of the device entry point — a route without a device stream: the inputs come down, the host-buffer route proves, the files go up
+  std::vector<uint64_t> h_amounts, h_types, h_blinds;
+  std::vector<uint8_t> h_prefix, h_coms, h_proofs;
+  uint8_t *d_coms_out = nullptr, *d_proofs_out = nullptr;
+  if (device && !has_device_stream(rp)) {
+    hipSetDevice(ctx->device);
+    h_amounts.resize(batch * nr * 4); h_blinds.resize(batch * nr * 4); h_types.resize(types ? batch * nr * 4 : 0); h_prefix.resize(batch * prefix_len);
+    h_coms.resize(batch * cb); h_proofs.resize(batch * pb);
+    BPPP_HIP(ctx, hipMemcpyAsync(h_amounts.data(), amounts, h_amounts.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    BPPP_HIP(ctx, hipMemcpyAsync(h_blinds.data(), blinds, h_blinds.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (types) BPPP_HIP(ctx, hipMemcpyAsync(h_types.data(), types, h_types.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (prefix_len) BPPP_HIP(ctx, hipMemcpyAsync(h_prefix.data(), rand_prefix, h_prefix.size(), hipMemcpyDeviceToHost, ctx->stream));
+    BPPP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    amounts = h_amounts.data(); blinds = h_blinds.data(); types = types ? h_types.data() : nullptr; rand_prefix = prefix_len ? h_prefix.data() : nullptr;
+    d_coms_out = coms_files; d_proofs_out = proof_files;
+    coms_files = h_coms.data(); proof_files = h_proofs.data();
+    device = false;
   }
-  // inner-product flavour without a table: the range-proof phases with their field algebra on the host cores, then the lockstep argument of
-  // ip_argument_lockstep (no basis change, no point fold: every commitment an MSM over the registered original basis)
-  if (rp->st.flavour != 0 && (!rp->comb || rp->opt.fold_points))
-    return prove_batch_host(rp, batch, amounts, types, blinds, rand_prefix, prefix_len, coms_files, proof_files, 0, pub);
-  // split_min: default 4096; measured: 4096 proofs 91-93 ms split against 95-97 ms, but 2048 proofs (128by64) 109 ms split against 104 ms
-  return prove_halves(rp, batch, rp->opt.split_min, [&](bppp_rp *h, size_t b0, size_t n) {
-    return prove_batch_one(h, n, amounts + 4 * nr * b0, types + 4 * nr * b0, blinds + 4 * nr * b0, prefix_at(b0), prefix_len, coms_files + cb * b0,
-                           proof_files + pb * b0, b0, pub_at(b0));
-  });
+  // proofs [b0, b0 + n) of the caller's arrays (prove_halves)
+  auto prefix_at = [&](size_t b0) { return rand_prefix ? rand_prefix + prefix_len * b0 : nullptr; };
+  auto device_half = [&](bppp_rp *h, size_t b0, size_t n) {
+    return rp_prove_device_half(h, n, amounts + 4 * nr * b0, types ? types + 4 * nr * b0 : nullptr, blinds + 4 * nr * b0, pub_at(b0), prefix_at(b0), prefix_len,
+                                coms_files + cb * b0, proof_files + pb * b0, b0);
+  };
+  auto routes = [&]() -> int {
+    // RangeProof.Binary: with the comb table in place the whole proof is a stream of kernels (csrc/brpprove_dev.hip); before that (small
+    // batches) and under BPPP_RP_HOST_ALGEBRA the field algebra and the hashing run on the host cores (prove_batch_binary)
+    if (rp->st.kind == 1) {
+      // two half-batches in flight (as below for the typed-reciprocal proofs): the transcript hashing, the phase and the round kernels of one half —
+      // ~14 ms per 1024 proofs of mostly one-lane-per-proof chains — run under the comb additions of the other
+      if (device) return prove_halves(rp, batch, rp->opt.split_min_binary, device_half);
+      if (rp->comb && !rp->opt.host_algebra && !rp->opt.fold_points)
+        return prove_halves(rp, batch, rp->opt.split_min_binary, [&](bppp_rp *h, size_t b0, size_t n) {
+          return prove_batch_binary_dev(h, n, amounts + 4 * nr * b0, blinds + 4 * nr * b0, prefix_at(b0), prefix_len, coms_files + cb * b0, proof_files + pb * b0, b0,
+                                        pub_at(b0));
+        });
+      return prove_batch_binary(rp, batch, amounts, blinds, rand_prefix, prefix_len, coms_files, proof_files, pub);
+    }
+    // inner-product flavour without a table: the range-proof phases with their field algebra on the host cores, then the lockstep argument of
+    // ip_argument_lockstep (no basis change, no point fold: every commitment an MSM over the registered original basis)
+    if (rp->st.flavour != 0 && (!rp->comb || rp->opt.fold_points))
+      return prove_batch_host(rp, batch, amounts, types, blinds, rand_prefix, prefix_len, coms_files, proof_files, 0, pub);
+    // split_min: default 4096; measured: 4096 proofs 91-93 ms split against 95-97 ms, but 2048 proofs (128by64) 109 ms split against 104 ms
+    if (device) return prove_halves(rp, batch, rp->opt.split_min, device_half);
+    return prove_halves(rp, batch, rp->opt.split_min, [&](bppp_rp *h, size_t b0, size_t n) {
+      return prove_batch_one(h, n, amounts + 4 * nr * b0, types + 4 * nr * b0, blinds + 4 * nr * b0, prefix_at(b0), prefix_len, coms_files + cb * b0,
+                             proof_files + pb * b0, b0, pub_at(b0));
+    });
+  };
+  const int rc = routes();
+  if (rc || !d_coms_out) return rc;
+  BPPP_HIP(ctx, hipMemcpyAsync(d_coms_out, h_coms.data(), h_coms.size(), hipMemcpyHostToDevice, ctx->stream));
+  BPPP_HIP(ctx, hipMemcpyAsync(d_proofs_out, h_proofs.data(), h_proofs.size(), hipMemcpyHostToDevice, ctx->stream));
+  BPPP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return BPPP_OK;
+}
+
+extern "C" int bppp_rp_prove_batch_pub(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint64_t *public_amounts,
+                                       const uint8_t *rand_prefix, size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files) {
+  return prove_entry(rp, batch, amounts, types, blinds, public_amounts, rand_prefix, prefix_len, coms_files, proof_files, false);
+}
+
+extern "C" int bppp_rp_prove_batch_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds, const void *d_public_amounts,
+                                          const void *d_rand_prefix, size_t prefix_len, void *d_coms_files, void *d_proof_files) {
+  return prove_entry(rp, batch, d_amounts, d_types, d_blinds, d_public_amounts, d_rand_prefix, prefix_len, d_coms_files, d_proof_files, true);
 }
 
 static int prove_batch_one(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint8_t *rand_prefix,
                            size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files, size_t index_base, const uint64_t *pub) {
   bppp_ctx *ctx = rp->ctx;
   const Setup &st = rp->st;
-  uint32_t max_base = 0;
-  for (const RangeData &rd : st.rds) max_base = std::max(max_base, rd.base);
-  // the device algebra looks digits up in a per-proof table of reciprocals held in LDS (256 entries, up to 2048 for wider digit bases); bases beyond
-  // that (and BPPP_RP_HOST_ALGEBRA=1, kept for comparison) take the host-algebra path: same bytes out
-  if (max_base > 2048 || (max_base > 256 && st.rds.size() > 256) || rp->opt.host_algebra || (st.flavour && !rp->comb)) return prove_batch_host(rp, batch, amounts, types, blinds, rand_prefix, prefix_len, coms_files, proof_files, index_base, pub);
+  // shapes beyond the device algebra's LDS tables (and BPPP_RP_HOST_ALGEBRA=1, kept for comparison) take the host-algebra path: same bytes out
+  if (lds_gate(st) || rp->opt.host_algebra || (st.flavour && !rp->comb)) return prove_batch_host(rp, batch, amounts, types, blinds, rand_prefix, prefix_len, coms_files, proof_files, index_base, pub);
   hipSetDevice(ctx->device);
   const size_t B = batch, nr = st.rds.size(), nlen = st.nlen, llen = st.llen, k = st.rounds, T = 1 + llen + nlen, npub = rp_public_count(rp);
   if (nr >= (1u << 16)) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: too many ranges");

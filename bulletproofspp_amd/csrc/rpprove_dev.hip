@@ -353,16 +353,19 @@ namespace bppp {
 // table, both take their challenges from `tr` (calls first_call ...).  In (device): s [B], q [B] (makeNorm's r for the inner-product flavour),
 // nx [B][nlen], lc / lx [B][llen]; d_resp [k][B][2][16] scratch.  Out (host): resp [B][k][16] LAST round first (Bulletproof.hs:359), the final
 // witness; `d_extra` (extra_points affine points, e.g. the range-proof commitments) comes back in the same download.  Synchronises the stream.
+// With `dev` nothing is downloaded but the inner-product flag word: the responses stay in d_resp in round order, the final witness is left in
+// HBM, canonical (dev->wit_norm / wit_lin: buf_wn [B][fn][8] / buf_wl [B][fl][8], or the inner-product argument's own arrays).
 int rpp_argument_stream(bppp_rp *rp, RppTranscript &tr, size_t first_call, size_t B, const uint32_t *a_s, const uint32_t *a_q, const uint32_t *a_nx, const uint32_t *a_lc,
                         const uint32_t *a_lx, uint32_t *d_resp, uint64_t *resp_out, uint64_t *wn_out, uint64_t *wl_out, const uint32_t *d_extra, size_t extra_points,
-                        std::vector<uint64_t> &extra_out) {
+                        std::vector<uint64_t> &extra_out, RppDevResults *dev, uint32_t *buf_wn, uint32_t *buf_wl) {
   bppp_ctx *ctx = rp->ctx;
   hipStream_t st = ctx->stream;
   const bppp_rps::Setup &S = rp->st;
   const size_t nlen = S.nlen, llen = S.llen, k = S.rounds;
   int rc = BPPP_OK;
+  if (dev) extra_points = 0;
   extra_out.resize(extra_points * 8);
-  std::vector<uint64_t> hresp(k * B * 16 + 16);
+  std::vector<uint64_t> hresp(dev ? 0 : k * B * 16 + 16);
   if (S.flavour) {
     const size_t wb = ipb_work_bytes(B, nlen, llen), wit = (B * (S.fn + S.fl) * 32 + 255) & ~(size_t)255;
     if (wb + wit + 256 > rp->awork_bytes) {
@@ -377,9 +380,10 @@ int rpp_argument_stream(bppp_rp *rp, RppTranscript &tr, size_t first_call, size_
     if (rc) return rc == BPPP_ERR_ARG && !*bppp_last_error(ctx) ? fail(ctx, rc, "rp_prove_batch: inner-product argument: bad arguments") : rc;
     uint32_t hflag = 0;
     if (extra_points) BPPP_HIP(ctx, hipMemcpyAsync(extra_out.data(), d_extra, extra_points * 64, hipMemcpyDeviceToHost, st));
-    if (k) BPPP_HIP(ctx, hipMemcpyAsync(hresp.data(), d_resp, k * B * 128, hipMemcpyDeviceToHost, st));
-    if (S.fn) BPPP_HIP(ctx, hipMemcpyAsync(wn_out, d_wn, B * S.fn * 32, hipMemcpyDeviceToHost, st));
-    if (S.fl) BPPP_HIP(ctx, hipMemcpyAsync(wl_out, d_wl, B * S.fl * 32, hipMemcpyDeviceToHost, st));
+    if (k && !dev) BPPP_HIP(ctx, hipMemcpyAsync(hresp.data(), d_resp, k * B * 128, hipMemcpyDeviceToHost, st));
+    if (S.fn && !dev) BPPP_HIP(ctx, hipMemcpyAsync(wn_out, d_wn, B * S.fn * 32, hipMemcpyDeviceToHost, st));
+    if (S.fl && !dev) BPPP_HIP(ctx, hipMemcpyAsync(wl_out, d_wl, B * S.fl * 32, hipMemcpyDeviceToHost, st));
+    if (dev) { dev->wit_norm = d_wn; dev->wit_lin = d_wl; }
     BPPP_HIP(ctx, hipMemcpyAsync(&hflag, d_flag, 4, hipMemcpyDeviceToHost, st));
     BPPP_HIP(ctx, hipStreamSynchronize(st));
     if (hflag) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: a round challenge is zero");
@@ -395,6 +399,14 @@ int rpp_argument_stream(bppp_rp *rp, RppTranscript &tr, size_t first_call, size_
       if (hipGetLastError() != hipSuccess) { rc = fail(ctx, BPPP_ERR_HIP, "rp_prove_batch: round kernels"); break; }
       rc = nlb_round_collapse_dev(nlb, tr.es);
     }
+    if (dev) {
+      if (!rc) rc = nlb_witness_dev(nlb, S.fn, S.fl, buf_wn, buf_wl);
+      if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = fail(ctx, BPPP_ERR_HIP, "rp_prove_batch: argument stream");
+      bppp_nlb_destroy(nlb);
+      if (rc) return rc == BPPP_ERR_ARG && !*bppp_last_error(ctx) ? fail(ctx, rc, "rp_prove_batch: the final witness is not device-resident") : rc;
+      dev->wit_norm = buf_wn; dev->wit_lin = buf_wl;
+      return BPPP_OK;
+    }
     // everything the files need comes back now: the range-proof commitments, the 2k responses, the final witness
     if (!rc && ((extra_points && hipMemcpyAsync(extra_out.data(), d_extra, extra_points * 64, hipMemcpyDeviceToHost, st) != hipSuccess) ||
                 (k && hipMemcpyAsync(hresp.data(), d_resp, k * B * 128, hipMemcpyDeviceToHost, st) != hipSuccess)))
@@ -403,8 +415,47 @@ int rpp_argument_stream(bppp_rp *rp, RppTranscript &tr, size_t first_call, size_
     bppp_nlb_destroy(nlb);
     if (rc) return rc;
   }
+  if (dev) return BPPP_OK;
   for (size_t b = 0; b < B; b++)
     for (size_t round = 0; round < k; round++) memcpy(resp_out + (b * k + (k - 1 - round)) * 16, &hresp[(round * B + b) * 16], 128);   // responses LAST round first (:359)
+  return BPPP_OK;
+}
+
+// D.maxb: the reciprocal table covers the widest digit base only: at base 16 the phase-2 batch inversion is 18 + nr entries instead of 258 + nr
+static PDims rpp_dims(const bppp_rp *rp) {
+  const bppp_rps::Setup &S = rp->st;
+  PDims D; D.nlen = (uint32_t)S.nlen; D.llen = (uint32_t)S.llen; D.nr = (uint32_t)S.rds.size(); D.T = (uint32_t)(1 + S.llen + S.nlen); D.has_types = S.has_types ? 1u : 0u;
+  D.nd = (uint32_t)(14 + (S.llen - 5) + S.nlen);
+  D.maxb = 16;
+  for (const bppp_rps::RangeData &rd : S.rds) while (D.maxb < rd.base && D.maxb < 2048) D.maxb <<= 1;       // bases above 2048 take the host-algebra route (csrc/rpprove.hip)
+  return D;
+}
+
+int rpp_carve(bppp_rp *rp, size_t B, size_t prefix_len, bool own_prefix, RppWork &W) {
+  const bppp_rps::Setup &S = rp->st;
+  const size_t nr = S.rds.size(), nlen = S.nlen, llen = S.llen, k = S.rounds, T = 1 + llen + nlen;
+  const PDims D = rpp_dims(rp);
+  // text capacity per proof: every commitment of the final transcript (4 + nr + 2k points), right-aligned, 16 bytes of slack at the end
+  const uint32_t stride = rp->D.text_stride;
+  W = RppWork{};
+  for (int pass = 0; pass < 2; pass++) {
+    Carver cv(pass ? rp->pwork : nullptr, rp->pwork_bytes);
+    W.in_sc = cv.take<uint32_t>(B * nr * 24); W.in_pt = cv.take<uint32_t>(B * nr * 16);
+    W.dig = cv.take<uint32_t>(B * nlen); W.mul = cv.take<uint32_t>(B * nlen); W.mss = cv.take<uint32_t>(B * (llen - 6) + 1);
+    W.rnd = cv.take<uint32_t>(B * (size_t)D.nd * 8);
+    W.rows_dm_m = cv.take<uint32_t>(2 * B * T * 8); W.row_r = cv.take<uint32_t>(B * T * 8); W.row_bl = cv.take<uint32_t>(B * T * 8);
+    W.ccbuf = cv.take<uint32_t>(B * nlen * 8); W.invtab = cv.take<uint32_t>(B * (size_t)(INV_DIG + D.maxb) * 8); W.aux = cv.take<uint32_t>(B * 24);
+    W.ch = cv.take<uint32_t>(B * 56); W.es = cv.take<uint32_t>(B * 8); W.tstart = cv.take<uint32_t>(B);
+    W.ptbuf = cv.take<uint32_t>(B * (2 + nr) * 16);
+    W.a_s = cv.take<uint32_t>(B * 8); W.a_q = cv.take<uint32_t>(B * 8); W.a_lx = cv.take<uint32_t>(B * llen * 8); W.a_nx = cv.take<uint32_t>(B * nlen * 8);
+    W.p_sp = cv.take<uint32_t>(B * 8); W.p_norm = cv.take<uint32_t>(B * nlen * 8); W.p_cs = cv.take<uint32_t>(B * llen * 8); W.p_init = cv.take<uint32_t>(B * (4 + nr) * 8);
+    W.text = cv.take<uint8_t>(B * (size_t)stride + 64); W.prefix_own = cv.take<uint8_t>((own_prefix ? B * prefix_len : 0) + 16); W.hdrs = cv.take<uint8_t>(RppTranscript::hdr_bytes(3 + k) + 16);
+    W.d_resp = cv.take<uint32_t>(k * B * 32 + 16); W.d_com = cv.take<uint32_t>(4 * B * 16 + 16);
+    W.cscratch = cv.take<uint32_t>(std::max(comb_rows_scratch_bytes(B), comb_scratch_bytes(2 * B)) / 4 + 16);
+    W.wn = cv.take<uint32_t>(B * S.fn * 8 + 8); W.wl = cv.take<uint32_t>(B * S.fl * 8 + 8); W.status = cv.take<uint32_t>(B);
+    if (!pass) { int rc = rpp_ensure_pwork(rp, cv.off); if (rc) return rc; }
+  }
+  W.prefix = W.prefix_own;
   return BPPP_OK;
 }
 
@@ -412,48 +463,40 @@ int rpp_device_prove(bppp_rp *rp, const RppHostInputs &in, RppOutputs &out) {
   bppp_ctx *ctx = rp->ctx;
   hipStream_t st = ctx->stream;
   const bppp_rps::Setup &S = rp->st;
-  const size_t B = in.batch, nr = S.rds.size(), nlen = S.nlen, llen = S.llen, k = S.rounds, T = 1 + llen + nlen;
-  PDims D; D.nlen = (uint32_t)nlen; D.llen = (uint32_t)llen; D.nr = (uint32_t)nr; D.T = (uint32_t)T; D.has_types = S.has_types ? 1u : 0u;
-  D.nd = (uint32_t)(14 + (llen - 5) + nlen);
-  D.maxb = 16;       // the reciprocal table covers the widest digit base only: at base 16 the phase-2 batch inversion is 18 + nr entries instead of 258 + nr
-  for (const bppp_rps::RangeData &rd : S.rds) while (D.maxb < rd.base && D.maxb < 2048) D.maxb <<= 1;       // bases above 2048 take the host-algebra route (csrc/rpprove.hip)
-  const bppp_trrp *tb = rp->tabs;
-  const TrrpDims TD = tb->D;
-  // text capacity per proof: every commitment of the final transcript (4 + nr + 2k points), right-aligned, 16 bytes of slack at the end
-  const uint32_t stride = rp->D.text_stride;
-
-  // ---- carve the device workspace
-  uint32_t *in_sc = nullptr, *in_pt = nullptr, *dig = nullptr, *mul = nullptr, *mss = nullptr, *rnd = nullptr, *rows_dm_m = nullptr, *row_r = nullptr, *row_bl = nullptr,
-           *ccbuf = nullptr, *invtab = nullptr, *aux = nullptr, *ch = nullptr, *es = nullptr, *tstart = nullptr, *ptbuf = nullptr, *a_s = nullptr, *a_q = nullptr,
-           *a_lx = nullptr, *a_nx = nullptr, *p_sp = nullptr, *p_norm = nullptr, *p_cs = nullptr, *p_init = nullptr;
-  uint8_t *text = nullptr, *prefix = nullptr, *hdrs = nullptr; uint32_t *d_resp = nullptr, *d_com = nullptr, *cscratch = nullptr;
-  for (int pass = 0; pass < 2; pass++) {
-    Carver cv(pass ? rp->pwork : nullptr, rp->pwork_bytes);
-    in_sc = cv.take<uint32_t>(B * nr * 24); in_pt = cv.take<uint32_t>(B * nr * 16);
-    dig = cv.take<uint32_t>(B * nlen); mul = cv.take<uint32_t>(B * nlen); mss = cv.take<uint32_t>(B * (llen - 6) + 1);
-    rnd = cv.take<uint32_t>(B * (size_t)D.nd * 8);
-    rows_dm_m = cv.take<uint32_t>(2 * B * T * 8); row_r = cv.take<uint32_t>(B * T * 8); row_bl = cv.take<uint32_t>(B * T * 8);
-    ccbuf = cv.take<uint32_t>(B * nlen * 8); invtab = cv.take<uint32_t>(B * (size_t)(INV_DIG + D.maxb) * 8); aux = cv.take<uint32_t>(B * 24);
-    ch = cv.take<uint32_t>(B * 56); es = cv.take<uint32_t>(B * 8); tstart = cv.take<uint32_t>(B);
-    ptbuf = cv.take<uint32_t>(B * (2 + nr) * 16);
-    a_s = cv.take<uint32_t>(B * 8); a_q = cv.take<uint32_t>(B * 8); a_lx = cv.take<uint32_t>(B * llen * 8); a_nx = cv.take<uint32_t>(B * nlen * 8);
-    p_sp = cv.take<uint32_t>(B * 8); p_norm = cv.take<uint32_t>(B * nlen * 8); p_cs = cv.take<uint32_t>(B * llen * 8); p_init = cv.take<uint32_t>(B * (4 + nr) * 8);
-    text = cv.take<uint8_t>(B * (size_t)stride + 64); prefix = cv.take<uint8_t>(B * in.prefix_len + 16); hdrs = cv.take<uint8_t>(RppTranscript::hdr_bytes(3 + k) + 16);
-    d_resp = cv.take<uint32_t>(k * B * 32 + 16); d_com = cv.take<uint32_t>(4 * B * 16 + 16);
-    cscratch = cv.take<uint32_t>(std::max(comb_rows_scratch_bytes(B), comb_scratch_bytes(2 * B)) / 4 + 16);
-    if (!pass) { int rc = rpp_ensure_pwork(rp, cv.off); if (rc) return rc; }
-  }
+  const size_t B = in.batch, nr = S.rds.size(), nlen = S.nlen, llen = S.llen;
+  RppWork W;
+  { int rc = rpp_carve(rp, B, in.prefix_len, true, W); if (rc) return rc; }
   // ---- uploads: per-proof public amounts (bppp_rp_prove_batch_pub), inputs, digits, multiplicities, prefixes
   const uint32_t *d_pub = nullptr;
   if (in.pub) { int rc_ = rp_upload_public(rp, in.pub, B * S.pubs.size() * 4, &d_pub); if (rc_) return rc_; }
-  BPPP_HIP(ctx, hipMemcpyAsync(in_sc, in.in_sc, B * nr * 96, hipMemcpyHostToDevice, st));
-  BPPP_HIP(ctx, hipMemcpyAsync(dig, in.dig, B * nlen * 4, hipMemcpyHostToDevice, st));
-  BPPP_HIP(ctx, hipMemcpyAsync(mul, in.mul, B * nlen * 4, hipMemcpyHostToDevice, st));
-  if (llen > 6) BPPP_HIP(ctx, hipMemcpyAsync(mss, in.mss, B * (llen - 6) * 4, hipMemcpyHostToDevice, st));
-  if (in.prefix_len) BPPP_HIP(ctx, hipMemcpyAsync(prefix, in.prefix, B * in.prefix_len, hipMemcpyHostToDevice, st));
+  BPPP_HIP(ctx, hipMemcpyAsync(W.in_sc, in.in_sc, B * nr * 96, hipMemcpyHostToDevice, st));
+  BPPP_HIP(ctx, hipMemcpyAsync(W.dig, in.dig, B * nlen * 4, hipMemcpyHostToDevice, st));
+  BPPP_HIP(ctx, hipMemcpyAsync(W.mul, in.mul, B * nlen * 4, hipMemcpyHostToDevice, st));
+  if (llen > 6) BPPP_HIP(ctx, hipMemcpyAsync(W.mss, in.mss, B * (llen - 6) * 4, hipMemcpyHostToDevice, st));
+  if (in.prefix_len) BPPP_HIP(ctx, hipMemcpyAsync(W.prefix_own, in.prefix, B * in.prefix_len, hipMemcpyHostToDevice, st));
+  return rpp_prove_body(rp, B, W, in.prefix_len, d_pub, &out, nullptr);
+}
+
+int rpp_prove_body(bppp_rp *rp, size_t B, const RppWork &W, size_t prefix_len, const uint32_t *d_pub, RppOutputs *host, RppDevResults *dev) {
+  bppp_ctx *ctx = rp->ctx;
+  hipStream_t st = ctx->stream;
+  const bppp_rps::Setup &S = rp->st;
+  const size_t nr = S.rds.size(), nlen = S.nlen, llen = S.llen, k = S.rounds, T = 1 + llen + nlen;
+  const PDims D = rpp_dims(rp);
+  const bppp_trrp *tb = rp->tabs;
+  const TrrpDims TD = tb->D;
+  uint32_t *const in_sc = W.in_sc, *const in_pt = W.in_pt, *const dig = W.dig, *const mul = W.mul, *const mss = W.mss, *const rnd = W.rnd, *const rows_dm_m = W.rows_dm_m,
+           *const row_r = W.row_r, *const row_bl = W.row_bl, *const ccbuf = W.ccbuf, *const invtab = W.invtab, *const aux = W.aux, *const ch = W.ch, *const es = W.es,
+           *const tstart = W.tstart, *const ptbuf = W.ptbuf, *const a_s = W.a_s, *const a_q = W.a_q, *const a_lx = W.a_lx, *const a_nx = W.a_nx, *const p_sp = W.p_sp,
+           *const p_norm = W.p_norm, *const p_cs = W.p_cs, *const p_init = W.p_init, *const d_resp = W.d_resp, *const d_com = W.d_com, *const cscratch = W.cscratch;
+  uint8_t *const text = W.text, *const hdrs = W.hdrs;
+  const uint8_t *const prefix = W.prefix;
+  RppOutputs none{};
+  RppOutputs &out = host ? *host : none;
   // fixed-basis mode (comb table in place): the whole proof is ONE stream of kernels — commitments stay on the device until the end,
   // every oracle call reads its points where they lie, and the headers of all 3 + k oracle calls go up here
   const bool stream_mode = rp->comb != nullptr && !rp->opt.fold_points;
+  if (dev && !stream_mode) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch_device: no device stream on this route");
   const size_t cscratch_bytes = std::max(comb_rows_scratch_bytes(B), comb_scratch_bytes(2 * B));
   // A handful of proofs: the oracle moves to the host.  One GPU lane walks the ~160 SHA-256 blocks of a 64by64 transcript in ~0.6 ms
   // (11 times per proof); a host core needs ~50 us, which pays for the round trip of the new points and the challenges as long as
@@ -464,12 +507,12 @@ int rpp_device_prove(bppp_rp *rp, const RppHostInputs &in, RppOutputs &out) {
   RppTranscript tr;
   { int rc_ = tr.begin(rp, B, {RppCall{(uint32_t)(2 + nr), 3, 0}, RppCall{1, 3, 3}, RppCall{1, 1, 6}}, k, host_oracle, text, tstart, hdrs, ch, es); if (rc_) return rc_; }
   auto oracle_dev = [&](const uint32_t *pts_dev, size_t call) -> int { return tr.call(pts_dev, call); };
-  { int rc_ = rpp_draws(ctx, prefix, in.prefix_len, B, D.nd, rnd); if (rc_) return rc_; }
+  { int rc_ = rpp_draws(ctx, prefix, prefix_len, B, D.nd, rnd); if (rc_) return rc_; }
   { const uint64_t n = (uint64_t)B * T;
     k_rpp_rows_dm_m<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(D, tb->pos_kind, tb->pos_range, in_sc, dig, mul, mss, rnd, (uint32_t)B, rows_dm_m); }
   BPPP_HIP(ctx, hipGetLastError());
   int rc = rpp_commit_inputs(rp, in_sc, B * nr, in_pt); if (rc) return rc;
-  BPPP_HIP(ctx, hipMemcpyAsync(out.input_coms, in_pt, B * nr * 64, hipMemcpyDeviceToHost, st));
+  if (host) BPPP_HIP(ctx, hipMemcpyAsync(out.input_coms, in_pt, B * nr * 64, hipMemcpyDeviceToHost, st));
   if (stream_mode) {
     const size_t lds2 = (2 * (INV_DIG + D.maxb + nr) + 128 + TRRP_MAX_SLOTS) * 32, lds3 = ((size_t)6 * 64 + nr + TRRP_MAX_SLOTS + 4) * 32;
     if (lds2 > 160 * 1024) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: too many ranges for the device prover");
@@ -501,7 +544,8 @@ int rpp_device_prove(bppp_rp *rp, const RppHostInputs &in, RppOutputs &out) {
       k_rpp_combine<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(D, (uint32_t)B, ch, rows_dm_m, row_r, row_bl, aux, p_sp, p_norm, a_s, a_lx, a_nx); }
     BPPP_HIP(ctx, hipGetLastError());
     // proveBPM in lockstep (src/Bulletproof.hs:357-359): the start state taken where it lies in HBM, k rounds queued back to back
-    rc = rpp_argument_stream(rp, tr, 3, B, a_s, a_q, a_nx, p_cs, a_lx, d_resp, out.resp, out.wit_norm, out.wit_lin, d_com, 4 * B, hcom_host); if (rc) return rc;
+    rc = rpp_argument_stream(rp, tr, 3, B, a_s, a_q, a_nx, p_cs, a_lx, d_resp, out.resp, out.wit_norm, out.wit_lin, d_com, 4 * B, hcom_host, dev, W.wn, W.wl); if (rc) return rc;
+    if (dev) { dev->input_coms = in_pt; dev->coms = d_com; dev->resp = d_resp; return BPPP_OK; }
     for (size_t b = 0; b < B; b++) {
       memcpy(out.c_dm + 8 * b, &hcom_host[16 * b], 64); memcpy(out.c_m + 8 * b, &hcom_host[16 * b + 8], 64);
       memcpy(out.c_r + 8 * b, &hcom_host[(2 * B + b) * 8], 64); memcpy(out.c_bl + 8 * b, &hcom_host[(3 * B + b) * 8], 64);

@@ -46,11 +46,36 @@ struct BrpOutputs {          // host arrays
 };
 int brp_device_prove(bppp_rp *rp, const BrpHostInputs &in, BrpOutputs &out);
 
+// The device workspace of one batch of either prover, carved from rp->pwork (rpp_carve / brp_carve): the inputs of the stream of kernels — in_sc,
+// dig, mul, mss (typed) or bits (binary), prefix — are filled by an upload (the host entry points) or by the witness kernel
+// (bppp_rp_prove_batch_device, csrc/rpwitness.hip); the rest is the stream's own
+struct RppWork {
+  uint32_t *in_sc, *in_pt, *dig, *mul, *mss, *rnd, *rows_dm_m, *row_r, *row_bl, *ccbuf, *invtab, *aux, *ch, *es, *tstart, *ptbuf, *a_s, *a_q, *a_lx, *a_nx, *p_sp,
+           *p_norm, *p_cs, *p_init, *d_resp, *d_com, *cscratch, *wn, *wl, *status;
+  uint8_t *bits, *text, *hdrs;
+  const uint8_t *prefix;     // [batch][prefix_len] in HBM: carved (prefix_own), or the caller's buffer
+  uint8_t *prefix_own;
+};
+// what a stream leaves in HBM for k_rp_encode_files: input commitments [batch][nr][16], the range-proof commitments (typed: [dm m] x batch, r x batch,
+// bl x batch; binary: d x batch, bl x batch), responses [rounds][batch][2][16] in round order, the final witness [batch][fn][8], [batch][fl][8]
+struct RppDevResults { const uint32_t *input_coms, *coms, *resp, *wit_norm, *wit_lin; };
+int rpp_carve(bppp_rp *rp, size_t batch, size_t prefix_len, bool own_prefix, RppWork &W);
+int brp_carve(bppp_rp *rp, size_t batch, size_t prefix_len, bool own_prefix, RppWork &W);
+// the provers' kernels from the randomness to the end of the argument over inputs that lie in W; d_pub: NULL or the batch's canonical public
+// amounts in HBM.  Exactly one of `host` (results downloaded, as rpp_device_prove / brp_device_prove return them) and `dev` (results stay in
+// HBM; needs the handle's comb table) is given.  Returns with the stream drained.
+int rpp_prove_body(bppp_rp *rp, size_t batch, const RppWork &W, size_t prefix_len, const uint32_t *d_pub, RppOutputs *host, RppDevResults *dev);
+int brp_prove_body(bppp_rp *rp, size_t batch, const RppWork &W, size_t prefix_len, const uint32_t *d_pub, BrpOutputs *host, RppDevResults *dev);
+// proofs [index_base, index_base + batch) of a bppp_rp_prove_batch_device call on a route with a device stream (csrc/rpwitness.hip): every
+// buffer in HBM but `pub` (NULL or the half's canonical public amounts, on the host as bppp_rp_prove_batch_pub's halves take them)
+int rp_prove_device_half(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds, const uint64_t *pub, const uint8_t *d_prefix,
+                         size_t prefix_len, uint8_t *d_coms_files, uint8_t *d_proof_files, size_t index_base);
+
 struct RppTranscript;
 // proveBPM of the setup's flavour behind the range-proof phases, device-resident (csrc/rpprove_dev.hip)
 int rpp_argument_stream(bppp_rp *rp, RppTranscript &tr, size_t first_call, size_t B, const uint32_t *a_s, const uint32_t *a_q, const uint32_t *a_nx, const uint32_t *a_lc,
                         const uint32_t *a_lx, uint32_t *d_resp, uint64_t *resp_out, uint64_t *wn_out, uint64_t *wl_out, const uint32_t *d_extra, size_t extra_points,
-                        std::vector<uint64_t> &extra_out);
+                        std::vector<uint64_t> &extra_out, RppDevResults *dev = nullptr, uint32_t *buf_wn = nullptr, uint32_t *buf_wl = nullptr);
 // verifyBRPM's public scalars for a batch (k_brp_public, csrc/rp.hip): the binary prover reuses them as the TR prover reuses k_trrp_public
 // d_net: NULL (the setup's net_public) or [batch] canonical values, one per proof
 int brp_public_device(bppp_rp *rp, size_t batch, const uint32_t *ch, uint32_t *q, uint32_t *sp, uint32_t *pub_norm, uint32_t *pub_lin_c, uint32_t *init_sc,
@@ -68,6 +93,7 @@ void rpp_host_oracle(const std::string &tag, std::vector<std::string> &groups, s
 bool nlb_fixed_basis(const bppp_nlb *o);
 int nlb_round_commit_dev(bppp_nlb *o, uint32_t *d_XR);
 int nlb_round_collapse_dev(bppp_nlb *o, const uint32_t *d_es);
+int nlb_witness_dev(bppp_nlb *o, size_t fn, size_t fl, uint32_t *d_wn, uint32_t *d_wl);     // the final witness, canonical, into HBM; asynchronous
 
 }  // namespace bppp
 

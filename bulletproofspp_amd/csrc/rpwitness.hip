@@ -1,0 +1,55 @@
+// rpwitness.hip — one half-batch of bppp_rp_prove_batch_device on a route with a device stream: the witness kernel on the caller's HBM buffers,
+// the status words read back (batch x 4 bytes; a refused proof fails the call before anything else is queued), the provers' stream of kernels
+// (rpp_prove_body / brp_prove_body, the same body the host entry points run behind their uploads) and the encoding kernel into the caller's
+// file buffers.  The kernels: csrc/rpwitness.hip.h.
+#include <string>
+#include <vector>
+#include "rpwitness.hip.h"
+#include "rpprove_dev.hpp"
+
+namespace bppp {
+
+int rp_prove_device_half(bppp_rp *rp, size_t B, const void *d_amounts, const void *d_types, const void *d_blinds, const uint64_t *pub, const uint8_t *d_prefix,
+                         size_t prefix_len, uint8_t *d_coms_files, uint8_t *d_proof_files, size_t index_base) {
+  bppp_ctx *ctx = rp->ctx;
+  hipSetDevice(ctx->device);
+  hipStream_t st = ctx->stream;
+  const bppp_rps::Setup &S = rp->st;
+  const bool binary = S.kind == 1;
+  const size_t nr = S.rds.size();
+  if (!binary && nr >= (1u << 16)) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: too many ranges");
+  LapTimer timer(rp->opt.timing, binary ? "[rp_prove binary]" : "[rp_prove]");
+  RppWork W;
+  { int rc = binary ? brp_carve(rp, B, prefix_len, false, W) : rpp_carve(rp, B, prefix_len, false, W); if (rc) return rc; }
+  W.prefix = d_prefix;
+  const uint32_t *d_pub = nullptr;
+  if (pub) { int rc = rp_upload_public(rp, pub, B * rp_public_count(rp) * 4, &d_pub); if (rc) return rc; }
+  { int rc = wit_launch(rp, B, d_amounts, d_types, d_blinds, d_pub, W.in_sc, W.dig, W.mul, W.mss, W.bits, W.status); if (rc) return rc; }
+  std::vector<uint32_t> status(B);
+  BPPP_HIP(ctx, hipMemcpyAsync(status.data(), W.status, B * 4, hipMemcpyDeviceToHost, st));
+  BPPP_HIP(ctx, hipStreamSynchronize(st));
+  for (size_t b = 0; b < B; b++)
+    if (status[b] != WIT_OK) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: proof " + std::to_string(index_base + b) + ": " + wit_status_text(status[b]));
+  timer.lap("witness (device)");
+  RppDevResults R{};
+  { int rc = binary ? brp_prove_body(rp, B, W, prefix_len, d_pub, nullptr, &R) : rpp_prove_body(rp, B, W, prefix_len, d_pub, nullptr, &R); if (rc) return rc; }
+  timer.lap("phases + argument (device)");
+  EncDims E{};
+  E.nr = (uint32_t)nr; E.k = (uint32_t)S.rounds; E.fn = (uint32_t)S.fn; E.fl = (uint32_t)S.fl; E.coms_bytes = rp->D.coms_bytes; E.proof_bytes = rp->D.proof_bytes;
+  E.batch = (uint32_t)B;
+  const uint32_t Bw = (uint32_t)B;
+  if (binary) {                     // blCom dCom (rpp_encode_files' lead of prove_batch_binary_dev)
+    E.nlead = 2;
+    E.lead_off[0] = Bw; E.lead_stride[0] = 1; E.lead_off[1] = 0; E.lead_stride[1] = 1;
+  } else {                          // blCom rCom dmCom mCom (prove_batch_one)
+    E.nlead = 4;
+    E.lead_off[0] = 3 * Bw; E.lead_stride[0] = 1; E.lead_off[1] = 2 * Bw; E.lead_stride[1] = 1; E.lead_off[2] = 0; E.lead_stride[2] = 2; E.lead_off[3] = 1; E.lead_stride[3] = 2;
+  }
+  k_rp_encode_files<<<dim3((unsigned)B), dim3(256), 0, st>>>(E, R.input_coms, R.coms, R.resp, R.wit_norm, R.wit_lin, d_coms_files, d_proof_files);
+  BPPP_HIP(ctx, hipGetLastError());
+  BPPP_HIP(ctx, hipStreamSynchronize(st));
+  timer.lap("encode (device)");
+  return BPPP_OK;
+}
+
+}  // namespace bppp

@@ -7,6 +7,7 @@
 #include "modinv.hip.h"
 #include "fr26.hip.h"
 #include "rp_internal.hpp"
+#include "rpwitness.hip.h"
 
 namespace bppp {
 template <int MOD> BPPP_DI fe apply_op(int op, const fe &a, const fe &b) {
@@ -254,4 +255,32 @@ extern "C" int bppp_test_rp_set_each_chunk(bppp_rp *rp, size_t proofs) {
   if (!rp || (proofs && proofs < 8)) return BPPP_ERR_ARG;
   rp->each_chunk = proofs;
   return BPPP_OK;
+}
+
+extern "C" int bppp_test_rp_witness_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds, const void *d_public_amounts,
+                                           uint64_t *in_sc, uint32_t *dig, uint32_t *mul, uint32_t *mss, uint32_t *status) {
+  if (!rp || !batch || !d_amounts || !d_blinds || !in_sc || !dig || !status) return BPPP_ERR_ARG;
+  const bool binary = rp->st.kind == 1;
+  if (!binary && (!d_types || !mul || !mss)) return BPPP_ERR_ARG;
+  bppp_ctx *ctx = rp->ctx;
+  hipSetDevice(ctx->device);
+  const size_t nr = rp->st.rds.size(), nlen = rp->st.nlen, nmss = binary ? 0 : rp->st.llen - 6, nlive = rp->st.nlive;
+  const size_t w_sc = batch * nr * 24, w_dig = batch * nlen, w_mss = batch * nmss + 1, b_bits = batch * nlive + 16;
+  uint32_t *d = nullptr;
+  BPPP_HIP(ctx, hipMalloc(&d, (w_sc + 2 * w_dig + w_mss + batch) * 4 + b_bits));
+  uint32_t *d_sc = d, *d_dig = d_sc + w_sc, *d_mul = d_dig + w_dig, *d_mss = d_mul + w_dig, *d_st = d_mss + w_mss;
+  uint8_t *d_bits = (uint8_t *)(d_st + batch);
+  std::vector<uint8_t> bits(batch * nlive);
+  int rc = wit_launch(rp, batch, d_amounts, d_types, d_blinds, (const uint32_t *)d_public_amounts, d_sc, d_dig, d_mul, d_mss, d_bits, d_st);
+  hipStream_t st = ctx->stream;
+  bool ok = !rc && hipMemcpyAsync(in_sc, d_sc, w_sc * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+            hipMemcpyAsync(status, d_st, batch * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+  if (ok && binary) ok = !bits.size() || hipMemcpyAsync(bits.data(), d_bits, bits.size(), hipMemcpyDeviceToHost, st) == hipSuccess;
+  else if (ok) ok = hipMemcpyAsync(dig, d_dig, w_dig * 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipMemcpyAsync(mul, d_mul, w_dig * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+                    (!nmss || hipMemcpyAsync(mss, d_mss, batch * nmss * 4, hipMemcpyDeviceToHost, st) == hipSuccess);
+  if (hipStreamSynchronize(st) != hipSuccess) ok = false;
+  if (!rc && !ok) rc = bppp::fail(ctx, BPPP_ERR_HIP, "test_rp_witness_device: kernel or copy failed");
+  if (!rc && binary) for (size_t i = 0; i < bits.size(); i++) dig[i] = bits[i];
+  hipFree(d);
+  return rc;
 }

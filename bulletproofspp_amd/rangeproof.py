@@ -923,6 +923,12 @@ class NativeRangeProofs:
         self.gpu._check(rc, "bppp_rp_prove_batch")
         return self._prove_files(B, cf, pf)
 
+    def prove_batch_device(self, batch: int, d_amounts: int, d_types: int, d_blinds: int, d_prefix: int, prefix_len: int, d_coms: int, d_proofs: int,
+                           d_public_amounts: int = 0):
+        """bppp_rp_prove_batch_device: prove_batch with every buffer in HBM (device pointers, the layouts of _prove_arrays; d_types is 0 on a
+        binary handle, d_public_amounts 0 = the setup's amounts).  On return d_coms / d_proofs hold the files prove_batch returns."""
+        self.gpu.rp_prove_batch_device(self.h, batch, d_amounts, d_types, d_blinds, d_public_amounts, d_prefix, prefix_len, d_coms, d_proofs)
+
     def _prove_rows(self, inputs):
         """one (amount, type, blinding) per range, as this class's prove_batch takes its inputs"""
         return inputs

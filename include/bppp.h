@@ -532,6 +532,27 @@ int bppp_rp_prove_batch_pub(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
                             const uint64_t *public_amounts, const uint8_t *rand_prefix, size_t prefix_len, uint8_t *coms_files,
                             uint8_t *proof_files);
 
+/* ---- proving from HBM to HBM -------------------------------------------------------------------------------------------------------
+ * bppp_rp_prove_batch_device is bppp_rp_prove_batch_pub with every buffer in HBM (16-byte aligned): d_amounts, d_types, d_blinds
+ * [batch][nranges][4] words (amounts as plain integers in two's complement; d_types is ignored and may be NULL on a binary handle),
+ * d_public_amounts NULL or [batch][public_count][4], d_rand_prefix [batch][prefix_len] bytes (NULL iff prefix_len == 0); out:
+ * d_coms_files [batch][coms_bytes], d_proof_files [batch][proof_bytes].  Synchronous: on return the files are complete in HBM.  The
+ * two output buffers hold, byte for byte, what bppp_rp_prove_batch_pub writes for the same inputs on the same handle, and the call
+ * does the same bookkeeping (the comb table is built at the same point, the options, a shared table and the two half-batches of a
+ * large batch apply as they do there; d_public_amounts is read back and checked on the host as the verifier's _pub_device calls do).
+ * With the handle's comb table in place (and neither HOST_ALGEBRA nor FOLD_POINTS set, no digit base above 2048) nothing of a proof
+ * crosses to the host but one status word per proof: a kernel checks the witness (canonical types and blindings, balance, ranges) and
+ * extracts digits and multiplicities, the prover's stream of kernels runs on its output, a kernel encodes the files.  Internal
+ * thresholds stay (at most HOST_ORACLE_MAX proofs still hash their transcripts on the host cores).  Every other route is the SLOW PATH
+ * of this entry point: the inputs are downloaded, the host-buffer route proves, the files are uploaded.
+ * Errors: return code and bppp_last_error text of bppp_rp_prove_batch_pub on the same inputs (bad arguments, a public amount that is
+ * not canonical, "proof N: value outside its range" ...).  When SEVERAL proofs of a batch are refused the device stream names the
+ * LOWEST-numbered one, with the reason the host entry point gives for that proof alone; the host entry point names whichever its
+ * worker threads reported last. */
+int bppp_rp_prove_batch_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds,
+                               const void *d_public_amounts, const void *d_rand_prefix, size_t prefix_len, void *d_coms_files,
+                               void *d_proof_files);
+
 /* ---- one comb table for the handles of a basis family --------------------------------------------------------------------------
  * Every setup's basis [g | H | G] is a prefix of the point stream its points came from (see bppp_rp_verify_mixed), and the comb table
  * is laid out tab[window][point][multiple]: the table of the longest basis of a stream contains the table of every shorter one (same

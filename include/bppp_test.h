@@ -45,6 +45,13 @@ int bppp_test_rp_last_verify_counts(bppp_rp *rp, uint64_t *combined_msms, uint64
 /* Proofs per chunk of the per-proof pass on this handle (0 = from the row budget, the default): a test crosses a chunk boundary
  * with a small batch. */
 int bppp_test_rp_set_each_chunk(bppp_rp *rp, size_t proofs);
+/* The witness kernel of bppp_rp_prove_batch_device alone (csrc/rpwitness.hip.h): inputs in HBM as that entry point takes them
+ * (d_types ignored on a binary handle, d_public_amounts NULL or CANONICAL scalars [batch][public_count][4]); its arrays copied to the
+ * host: in_sc [batch][nranges][3][4] words, status [batch] (0 = a witness; the arrays of a refused proof are unspecified) and, typed:
+ * dig, mul [batch][norm_len], mss [batch][lin_len - 6] as rpp_device_prove takes them; binary: dig [batch][live positions] holds the
+ * bits, mul and mss are not written (may be NULL). */
+int bppp_test_rp_witness_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds,
+                                const void *d_public_amounts, uint64_t *in_sc, uint32_t *dig, uint32_t *mul, uint32_t *mss, uint32_t *status);
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
