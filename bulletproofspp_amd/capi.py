@@ -35,6 +35,7 @@ SYMBOLS = [
     "bppp_rp_verify_each_pub_device", "bppp_rp_prove_batch_pub",
     "bppp_rp_share_comb", "bppp_rp_comb_info", "bppp_rp_prove_mixed",
     "bppp_rp_prove_batch_device",
+    "bppp_rp_prove_batch_status", "bppp_rp_prove_batch_status_device", "bppp_rp_witness_status_text",
 ]
 
 
@@ -152,6 +153,10 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_comb_info.argtypes = [vp, C.POINTER(i), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
     lib.bppp_rp_prove_mixed.argtypes = [vp, sz]
     lib.bppp_rp_prove_batch_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp, vp]
+    lib.bppp_rp_prove_batch_status.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp, vp, vp]
+    lib.bppp_rp_prove_batch_status_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp, vp, vp]
+    lib.bppp_rp_witness_status_text.argtypes = [C.c_uint32]
+    lib.bppp_rp_witness_status_text.restype = C.c_char_p
     lib.bppp_profile_enable.argtypes = [vp, i]
     lib.bppp_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), i]
     return lib
@@ -208,6 +213,8 @@ class RpShape(C.Structure):
 RP_OPTIONS = {"comb_min": 1, "comb_budget": 2, "comb_bits": 3, "split_min": 4, "host_oracle_max": 5, "fold_points": 6, "host_algebra": 7, "timing": 8, "culprits": 9}
 RP_SHARED, RP_OUTPUT, RP_ASSUMED = 1, 2, 4
 RP_VALID, RP_INVALID, RP_MALFORMED = 0, 1, 2
+# BPPP_RP_WIT_*: a proof's verdict from bppp_rp_prove_batch_status{,_device}
+RP_WIT_OK, RP_WIT_NOT_CANONICAL, RP_WIT_UNBALANCED, RP_WIT_OUT_OF_RANGE, RP_WIT_BIN_NOT_CANONICAL, RP_WIT_BIN_UNBALANCED = 0, 1, 2, 3, 4, 5
 
 
 # ---- integer <-> limb helpers (host-side glue for tests / bench)
@@ -482,6 +489,16 @@ class Bppp:
         """bppp_rp_prove_batch_device: `rp` a bppp_rp handle, every buffer a device pointer (0 = NULL); the files are complete in HBM on return"""
         self._check(self.lib.bppp_rp_prove_batch_device(rp, batch, _ptr(d_amounts), _ptr(d_types), _ptr(d_blinds), _ptr(d_public_amounts), _ptr(d_rand_prefix),
                                                         prefix_len, _ptr(d_coms_files), _ptr(d_proof_files)), "bppp_rp_prove_batch_device")
+
+    def rp_prove_batch_status_device(self, rp, batch: int, d_amounts: int, d_types: int, d_blinds: int, d_public_amounts: int, d_rand_prefix: int, prefix_len: int,
+                                     d_coms_files: int, d_proof_files: int) -> np.ndarray:
+        """bppp_rp_prove_batch_status_device: rp_prove_batch_device that refuses proof by proof; returns the RP_WIT_* verdicts (uint32 [batch]).  A
+        refused proof's two files are zero bytes in HBM"""
+        status = np.zeros(max(batch, 1), dtype=np.uint32)
+        self._check(self.lib.bppp_rp_prove_batch_status_device(rp, batch, _ptr(d_amounts), _ptr(d_types), _ptr(d_blinds), _ptr(d_public_amounts), _ptr(d_rand_prefix),
+                                                               prefix_len, _ptr(d_coms_files), _ptr(d_proof_files), C.c_void_p(status.ctypes.data)),
+                    "bppp_rp_prove_batch_status_device")
+        return status[:batch]
 
     # ---- profiling
     def profile_enable(self, on: bool = True):

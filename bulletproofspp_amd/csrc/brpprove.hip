@@ -55,22 +55,19 @@ int prove_batch_binary(bppp_rp *rp, size_t batch, const uint64_t *amounts, const
       BState &p = ps[b];
       p.tr.rnd = Rnd{rand_prefix + b * prefix_len, prefix_len, 0};
       p.v.resize(nr); p.bl.resize(nr); p.ds.clear();
-      U256 vsum = pub ? U256::load(pub + 4 * b) : st.net_public;
-      bool ok = true;
-      for (size_t i = 0; i < nr && ok; i++) {
+      // canonical blindings, amounts in their ranges, a conserved schema that balances: one verdict (witness_status, csrc/rpsetup.hpp)
+      if (const uint32_t refusal = bppp_rps::witness_status(st, amounts + 4 * b * nr, nullptr, blinds + 4 * b * nr, pub ? pub + 4 * b : nullptr)) {
+        p.err = bppp_rps::wit_status_text(refusal); failed = (int)b; continue;
+      }
+      for (size_t i = 0; i < nr; i++) {
         const RangeData &rd = st.rds[i];
         const U256 amt = U256::load(amounts + 4 * (b * nr + i));
         p.bl[i] = U256::load(blinds + 4 * (b * nr + i));
-        if (!scalars_canonical(blinds + 4 * (b * nr + i), 1)) { p.err = "blinding is not canonical"; ok = false; break; }
         p.v[i] = bppp_rps::s_mod_n(amt);
-        vsum = rd.output ? fs(vsum, p.v[i]) : fa(vsum, p.v[i]);
         if (rd.assumed) continue;
-        if (bppp_rps::s_lt(amt, rd.lo) || !bppp_rps::s_lt(amt, rd.hi)) { p.err = "value outside its range"; ok = false; break; }
         bppp_rps::digits_binary_into(rd, bppp_rps::u_sub(amt, rd.lo), dg);
         for (uint32_t d : dg) p.ds.push_back(small(d));
       }
-      if (ok && !(st.conserve && vsum.is_zero())) { p.err = "a binary witness needs a conserved schema whose amounts balance (Binary.hs:162-164)"; ok = false; }
-      if (!ok) { failed = (int)b; continue; }
       for (size_t i = 0; i < nr; i++) {                     // scalarRPW' (Internal.hs:56-57): v g + bl h0
         p.v[i].store(&h_in_sc[(b * nr + i) * 12]); p.bl[i].store(&h_in_sc[(b * nr + i) * 12 + 4]); U256::zero().store(&h_in_sc[(b * nr + i) * 12 + 8]);
       }
@@ -197,23 +194,18 @@ int prove_batch_binary_dev(bppp_rp *rp, size_t batch, const uint64_t *amounts, c
   rp_parallel(B, [&](size_t lo, size_t hi) {
     std::vector<uint32_t> dg;
     for (size_t b = lo; b < hi; b++) {
-      U256 vsum = pub ? U256::load(pub + 4 * b) : st.net_public;
-      const char *err = nullptr;
+      const uint32_t refusal = bppp_rps::witness_status(st, amounts + 4 * b * nr, nullptr, blinds + 4 * b * nr, pub ? pub + 4 * b : nullptr);
+      const char *err = refusal ? bppp_rps::wit_status_text(refusal) : nullptr;
       size_t p = 0;
       for (size_t i = 0; i < nr && !err; i++) {
         const RangeData &rd = st.rds[i];
         const U256 amt = U256::load(amounts + 4 * (b * nr + i));
-        if (!scalars_canonical(blinds + 4 * (b * nr + i), 1)) { err = "blinding is not canonical"; break; }
-        const U256 v = bppp_rps::s_mod_n(amt);
-        vsum = rd.output ? fs(vsum, v) : fa(vsum, v);
         uint64_t *row = &h_in_sc[(b * nr + i) * 12];          // scalarRPW' (Internal.hs:56-57): v g + bl h0
-        v.store(row); memcpy(row + 4, blinds + 4 * (b * nr + i), 32); memset(row + 8, 0, 32);
+        bppp_rps::s_mod_n(amt).store(row); memcpy(row + 4, blinds + 4 * (b * nr + i), 32); memset(row + 8, 0, 32);
         if (rd.assumed) continue;
-        if (bppp_rps::s_lt(amt, rd.lo) || !bppp_rps::s_lt(amt, rd.hi)) { err = "value outside its range"; break; }
         bppp_rps::digits_binary_into(rd, bppp_rps::u_sub(amt, rd.lo), dg);
         for (uint32_t d : dg) bits[b * nlive + p++] = (uint8_t)d;
       }
-      if (!err && !(st.conserve && vsum.is_zero())) err = "a binary witness needs a conserved schema whose amounts balance (Binary.hs:162-164)";
       if (!err && p != nlive) err = "digit count disagrees with the setup";
       if (err) { failed = (int)b; errs[b] = err; }
     }

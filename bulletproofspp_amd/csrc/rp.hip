@@ -523,6 +523,7 @@ void bppp_rp_destroy(bppp_rp *rp) {
   if (rp->ework) hipFree(rp->ework);
   if (rp->d_pub) hipFree(rp->d_pub);
   if (rp->d_wit) hipFree(rp->d_wit);
+  if (rp->d_sel) hipFree(rp->d_sel);
   if (rp->hflag) hipHostFree(rp->hflag);
   if (rp->hstage) hipHostFree(rp->hstage);
   for (auto &e : rp->slice_ev) if (e) hipEventDestroy(e);

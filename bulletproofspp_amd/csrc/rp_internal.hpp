@@ -173,6 +173,9 @@ struct bppp_rp {
   uint32_t *d_pub = nullptr; size_t d_pub_bytes = 0;
   // bppp_rp_prove_batch_device: the per-range data of the witness kernels (csrc/rpwitness.hip.h), uploaded at the first device call
   uint32_t *d_wit = nullptr;
+  // bppp_rp_prove_batch_status_device, a batch with refused proofs: the accepted and the refused proofs' indices and the accepted proofs' public
+  // words in compact order (csrc/rpwitness.hip), grow-only
+  uint32_t *d_sel = nullptr; size_t d_sel_bytes = 0;
 };
 
 // public amounts per proof of the *_pub entry points: npub of a typed handle with types, 1 of a conserved binary handle, else 0

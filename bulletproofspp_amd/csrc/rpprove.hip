@@ -88,22 +88,13 @@ namespace {
 // setup's public amounts) or this proof's [npub][4] canonical amounts (bppp_rp_prove_batch_pub)
 bool make_witness(const Setup &st, PState &ps, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint64_t *pub) {
   const size_t nr = st.rds.size();
+  // canonical types and blindings, balancing types, amounts in their ranges: one verdict (witness_status, csrc/rpsetup.hpp)
+  if (const uint32_t refusal = bppp_rps::witness_status(st, amounts, types, blinds, pub)) { ps.err = bppp_rps::wit_status_text(refusal); return false; }
   ps.v.resize(nr); ps.ty.resize(nr); ps.bl.resize(nr);
   std::vector<U256> amt(nr);
   for (size_t i = 0; i < nr; i++) {
     amt[i] = U256::load(amounts + 4 * i);
-    if (!scalars_canonical(types + 4 * i, 1) || !scalars_canonical(blinds + 4 * i, 1)) { ps.err = "type / blinding not canonical"; return false; }
     ps.v[i] = bppp_rps::s_mod_n(amt[i]); ps.ty[i] = U256::load(types + 4 * i); ps.bl[i] = U256::load(blinds + 4 * i);
-  }
-  if (st.has_types) {                                     // amounts of every type must balance (:376-381)
-    std::vector<std::pair<U256, U256>> sums;
-    auto add = [&](const U256 &ty, const U256 &val, bool neg) {
-      for (auto &kv : sums) if (kv.first == ty) { kv.second = neg ? fs(kv.second, val) : fa(kv.second, val); return; }
-      sums.emplace_back(ty, neg ? fneg(val) : val);
-    };
-    for (size_t j = 0; j < st.pubs.size(); j++) add(st.pubs[j].type, pub ? U256::load(pub + 4 * j) : st.pubs[j].amount, st.pubs[j].is_output);
-    for (size_t i = 0; i < nr; i++) add(ps.ty[i], ps.v[i], st.rds[i].output);
-    for (auto &kv : sums) if (!kv.second.is_zero()) { ps.err = "amounts of some type do not balance"; return false; }
   }
   ps.d.assign(st.nlen, U256::zero()); ps.mi.assign(st.nlen, U256::zero()); ps.pv.assign(st.nlen, U256::one());
   // the shared multiplicities are counts of digits: summed as integers (64 ranges x 255 digit values of modular additions per proof were most of
@@ -119,7 +110,6 @@ bool make_witness(const Setup &st, PState &ps, const uint64_t *amounts, const ui
   for (size_t i = 0; i < nr; i++) {
     const RangeData &rd = st.rds[i];
     if (rd.assumed) continue;
-    if (bppp_rps::s_lt(amt[i], rd.lo) || !bppp_rps::s_lt(amt[i], rd.hi)) { ps.err = "value outside its range"; return false; }
     std::vector<uint32_t> &ds = ps.tmp_ds, &cnt = ps.tmp_cnt, &ms = ps.tmp_ms;       // reused across ranges and proofs
     bppp_rps::digits_into(rd, bppp_rps::u_sub(amt[i], rd.lo), ds);
     const uint32_t b = rd.base;
@@ -527,13 +517,17 @@ static bool has_device_stream(const bppp_rp *rp) {
   return rp->comb && !rp->opt.host_algebra && !rp->opt.fold_points && (rp->st.kind == 1 || !lds_gate(rp->st));
 }
 
-// bppp_rp_prove_batch_pub (device = false: every buffer on the host) and bppp_rp_prove_batch_device (device = true: every buffer in HBM)
+// bppp_rp_prove_batch_pub (device = false: every buffer on the host) and bppp_rp_prove_batch_device (device = true: every buffer in HBM); with
+// per_proof, their *_status forms: proof_status [batch] on the host takes every proof's verdict, a refused proof's files are zeroed and the rest is
+// proved — on a route with a device stream inside each half (csrc/rpwitness.hip), elsewhere here: the accepted proofs' rows are compacted on the
+// host, the route below proves them as a batch of its own, and their files are scattered back
 static int prove_entry(bppp_rp *rp, size_t batch, const void *amounts_, const void *types_, const void *blinds_, const void *public_amounts, const void *rand_prefix_,
-                       size_t prefix_len, void *coms_files_, void *proof_files_, bool device) {
+                       size_t prefix_len, void *coms_files_, void *proof_files_, bool device, bool per_proof = false, uint32_t *proof_status = nullptr) {
   if (!rp) return BPPP_ERR_ARG;
   bppp_ctx *ctx = rp->ctx;
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
   if (!batch) return BPPP_OK;
+  if (per_proof && !proof_status) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch_status: proof_status is NULL");
   const uint64_t *amounts = (const uint64_t *)amounts_, *types = (const uint64_t *)types_, *blinds = (const uint64_t *)blinds_;
   const uint8_t *rand_prefix = (const uint8_t *)rand_prefix_;
   uint8_t *coms_files = (uint8_t *)coms_files_, *proof_files = (uint8_t *)proof_files_;
@@ -583,7 +577,7 @@ static int prove_entry(bppp_rp *rp, size_t batch, const void *amounts_, const vo
   auto prefix_at = [&](size_t b0) { return rand_prefix ? rand_prefix + prefix_len * b0 : nullptr; };
   auto device_half = [&](bppp_rp *h, size_t b0, size_t n) {
     return rp_prove_device_half(h, n, amounts + 4 * nr * b0, types ? types + 4 * nr * b0 : nullptr, blinds + 4 * nr * b0, pub_at(b0), prefix_at(b0), prefix_len,
-                                coms_files + cb * b0, proof_files + pb * b0, b0);
+                                coms_files + cb * b0, proof_files + pb * b0, b0, proof_status ? proof_status + b0 : nullptr);
   };
   auto routes = [&]() -> int {
     // RangeProof.Binary: with the comb table in place the whole proof is a stream of kernels (csrc/brpprove_dev.hip); before that (small
@@ -610,7 +604,39 @@ static int prove_entry(bppp_rp *rp, size_t batch, const void *amounts_, const vo
                              proof_files + pb * b0, b0, pub_at(b0));
     });
   };
-  const int rc = routes();
+  // per-proof verdicts on host buffers (a device stream takes them from its witness kernel): the refused proofs leave the batch before its route sees it
+  std::vector<uint64_t> a_amounts, a_types, a_blinds, a_pub;
+  std::vector<uint8_t> a_prefix, a_coms, a_proofs;
+  std::vector<size_t> accepted;
+  const size_t submitted = batch;
+  uint8_t *const all_coms = coms_files, *const all_proofs = proof_files;
+  if (proof_status && !device) {
+    rp_parallel(batch, [&](size_t lo, size_t hi) {
+      for (size_t b = lo; b < hi; b++) proof_status[b] = bppp_rps::witness_status(rp->st, amounts + 4 * nr * b, types ? types + 4 * nr * b : nullptr, blinds + 4 * nr * b, pub_at(b));
+    });
+    for (size_t b = 0; b < batch; b++) if (proof_status[b] == bppp_rps::WIT_OK) accepted.push_back(b);
+    if (accepted.size() < batch) {
+      const size_t G = accepted.size();
+      a_amounts.resize(G * nr * 4); a_blinds.resize(G * nr * 4); a_types.resize(types ? G * nr * 4 : 0); a_pub.resize(pub ? G * npub * 4 : 0);
+      a_prefix.resize(G * prefix_len); a_coms.resize(G * cb); a_proofs.resize(G * pb);
+      for (size_t s = 0; s < G; s++) {
+        const size_t b = accepted[s];
+        memcpy(&a_amounts[s * nr * 4], amounts + 4 * nr * b, nr * 32); memcpy(&a_blinds[s * nr * 4], blinds + 4 * nr * b, nr * 32);
+        if (types) memcpy(&a_types[s * nr * 4], types + 4 * nr * b, nr * 32);
+        if (pub && npub) memcpy(&a_pub[s * npub * 4], pub + 4 * npub * b, npub * 32);
+        if (prefix_len) memcpy(&a_prefix[s * prefix_len], rand_prefix + prefix_len * b, prefix_len);
+      }
+      amounts = a_amounts.data(); blinds = a_blinds.data(); types = types ? a_types.data() : nullptr; rand_prefix = prefix_len ? a_prefix.data() : nullptr;
+      if (pub) pub = a_pub.data();
+      coms_files = a_coms.data(); proof_files = a_proofs.data();
+      batch = G;
+    }
+  }
+  const int rc = batch ? routes() : BPPP_OK;
+  if (!rc && batch < submitted) {
+    memset(all_coms, 0, submitted * cb); memset(all_proofs, 0, submitted * pb);
+    for (size_t s = 0; s < batch; s++) { memcpy(all_coms + accepted[s] * cb, &a_coms[s * cb], cb); memcpy(all_proofs + accepted[s] * pb, &a_proofs[s * pb], pb); }
+  }
   if (rc || !d_coms_out) return rc;
   BPPP_HIP(ctx, hipMemcpyAsync(d_coms_out, h_coms.data(), h_coms.size(), hipMemcpyHostToDevice, ctx->stream));
   BPPP_HIP(ctx, hipMemcpyAsync(d_proofs_out, h_proofs.data(), h_proofs.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -627,6 +653,18 @@ extern "C" int bppp_rp_prove_batch_device(bppp_rp *rp, size_t batch, const void 
                                           const void *d_rand_prefix, size_t prefix_len, void *d_coms_files, void *d_proof_files) {
   return prove_entry(rp, batch, d_amounts, d_types, d_blinds, d_public_amounts, d_rand_prefix, prefix_len, d_coms_files, d_proof_files, true);
 }
+
+extern "C" int bppp_rp_prove_batch_status(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint64_t *public_amounts,
+                                          const uint8_t *rand_prefix, size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files, uint32_t *proof_status) {
+  return prove_entry(rp, batch, amounts, types, blinds, public_amounts, rand_prefix, prefix_len, coms_files, proof_files, false, true, proof_status);
+}
+
+extern "C" int bppp_rp_prove_batch_status_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds, const void *d_public_amounts,
+                                                 const void *d_rand_prefix, size_t prefix_len, void *d_coms_files, void *d_proof_files, uint32_t *proof_status) {
+  return prove_entry(rp, batch, d_amounts, d_types, d_blinds, d_public_amounts, d_rand_prefix, prefix_len, d_coms_files, d_proof_files, true, true, proof_status);
+}
+
+extern "C" const char *bppp_rp_witness_status_text(uint32_t status) { return bppp_rps::wit_status_text(status); }
 
 static int prove_batch_one(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint8_t *rand_prefix,
                            size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files, size_t index_base, const uint64_t *pub) {

@@ -67,9 +67,11 @@ int brp_carve(bppp_rp *rp, size_t batch, size_t prefix_len, bool own_prefix, Rpp
 int rpp_prove_body(bppp_rp *rp, size_t batch, const RppWork &W, size_t prefix_len, const uint32_t *d_pub, RppOutputs *host, RppDevResults *dev);
 int brp_prove_body(bppp_rp *rp, size_t batch, const RppWork &W, size_t prefix_len, const uint32_t *d_pub, BrpOutputs *host, RppDevResults *dev);
 // proofs [index_base, index_base + batch) of a bppp_rp_prove_batch_device call on a route with a device stream (csrc/rpwitness.hip): every
-// buffer in HBM but `pub` (NULL or the half's canonical public amounts, on the host as bppp_rp_prove_batch_pub's halves take them)
+// buffer in HBM but `pub` (NULL or the half's canonical public amounts, on the host as bppp_rp_prove_batch_pub's halves take them).
+// proof_status: NULL (a refused witness fails the call) or the half's [batch] verdicts on the host (bppp_rp_prove_batch_status_device: the refused
+// proofs' files are zeroed, the others proved)
 int rp_prove_device_half(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds, const uint64_t *pub, const uint8_t *d_prefix,
-                         size_t prefix_len, uint8_t *d_coms_files, uint8_t *d_proof_files, size_t index_base);
+                         size_t prefix_len, uint8_t *d_coms_files, uint8_t *d_proof_files, size_t index_base, uint32_t *proof_status);
 
 struct RppTranscript;
 // proveBPM of the setup's flavour behind the range-proof phases, device-resident (csrc/rpprove_dev.hip)

@@ -318,4 +318,53 @@ inline bool make_setup_binary(bool conserve, const std::vector<RangeData> &rds, 
   return true;
 }
 
+// ---- the verdict on one proof's witness: 0 = a witness, else why the prover refuses it.  The witness kernels (csrc/rpwitness.hip.h) write these
+// words, the host routes get them from witness_status below; include/bppp.h publishes them as BPPP_RP_WIT_* with the same numbers
+enum : uint32_t { WIT_OK = 0, WIT_NOT_CANONICAL = 1, WIT_UNBALANCED = 2, WIT_OUT_OF_RANGE = 3, WIT_BIN_NOT_CANONICAL = 4, WIT_BIN_UNBALANCED = 5 };
+inline const char *wit_status_text(uint32_t s) {
+  switch (s) {
+    case WIT_NOT_CANONICAL: return "type / blinding not canonical";
+    case WIT_UNBALANCED: return "amounts of some type do not balance";
+    case WIT_OUT_OF_RANGE: return "value outside its range";
+    case WIT_BIN_NOT_CANONICAL: return "blinding is not canonical";
+    case WIT_BIN_UNBALANCED: return "a binary witness needs a conserved schema whose amounts balance (Binary.hs:162-164)";
+    default: return "unknown witness status";
+  }
+}
+// witnessTRRP's checks (TypedReciprocal.hs:372-389) resp. witnessBRP's (Binary.hs:158-166) on one proof: amounts / types / blinds [nr][4] as the
+// caller gave them (types unused on a binary setup); pub NULL (the setup's public amounts) or this proof's canonical ones ([npub][4]; binary: [4]).
+// Typed: the lowest code that applies (canonical, then balance, then range); binary: the first offending range, then the balance.
+inline uint32_t witness_status(const Setup &st, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint64_t *pub) {
+  const bppp_host::Mod &R = bppp_host::FR();
+  const size_t nr = st.rds.size();
+  auto canonical = [&](const uint64_t *w) { return bppp_host::cmp(U256::load(w), R.m) < 0; };
+  auto in_range = [](const RangeData &rd, const U256 &amt) { return !s_lt(amt, rd.lo) && s_lt(amt, rd.hi); };
+  if (st.kind == 1) {
+    U256 vsum = pub ? U256::load(pub) : st.net_public;
+    for (size_t i = 0; i < nr; i++) {
+      const RangeData &rd = st.rds[i];
+      if (!canonical(blinds + 4 * i)) return WIT_BIN_NOT_CANONICAL;
+      const U256 amt = U256::load(amounts + 4 * i), v = s_mod_n(amt);
+      vsum = rd.output ? bppp_host::msub(vsum, v, R) : bppp_host::madd(vsum, v, R);
+      if (!rd.assumed && !in_range(rd, amt)) return WIT_OUT_OF_RANGE;
+    }
+    return st.conserve && vsum.is_zero() ? WIT_OK : WIT_BIN_UNBALANCED;
+  }
+  for (size_t i = 0; i < nr; i++)
+    if (!canonical(types + 4 * i) || !canonical(blinds + 4 * i)) return WIT_NOT_CANONICAL;
+  if (st.has_types) {                                     // amounts of every type must balance (:376-381)
+    std::vector<std::pair<U256, U256>> sums;
+    auto add = [&](const U256 &ty, const U256 &val, bool neg) {
+      for (auto &kv : sums) if (kv.first == ty) { kv.second = neg ? bppp_host::msub(kv.second, val, R) : bppp_host::madd(kv.second, val, R); return; }
+      sums.emplace_back(ty, neg ? bppp_host::mneg(val, R) : val);
+    };
+    for (size_t j = 0; j < st.pubs.size(); j++) add(st.pubs[j].type, pub ? U256::load(pub + 4 * j) : st.pubs[j].amount, st.pubs[j].is_output);
+    for (size_t i = 0; i < nr; i++) add(U256::load(types + 4 * i), s_mod_n(U256::load(amounts + 4 * i)), st.rds[i].output);
+    for (auto &kv : sums) if (!kv.second.is_zero()) return WIT_UNBALANCED;
+  }
+  for (size_t i = 0; i < nr; i++)
+    if (!st.rds[i].assumed && !in_range(st.rds[i], U256::load(amounts + 4 * i))) return WIT_OUT_OF_RANGE;
+  return WIT_OK;
+}
+
 }  // namespace bppp_rps

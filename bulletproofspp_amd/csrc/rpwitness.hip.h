@@ -18,17 +18,9 @@
 namespace bppp {
 
 // status word of one proof: 0 = a witness, else the host's refusal (same order of precedence as make_witness / prove_batch_binary_dev)
-enum : uint32_t { WIT_OK = 0, WIT_NOT_CANONICAL = 1, WIT_UNBALANCED = 2, WIT_OUT_OF_RANGE = 3, WIT_BIN_NOT_CANONICAL = 4, WIT_BIN_UNBALANCED = 5 };
-inline const char *wit_status_text(uint32_t s) {
-  switch (s) {
-    case WIT_NOT_CANONICAL: return "type / blinding not canonical";
-    case WIT_UNBALANCED: return "amounts of some type do not balance";
-    case WIT_OUT_OF_RANGE: return "value outside its range";
-    case WIT_BIN_NOT_CANONICAL: return "blinding is not canonical";
-    case WIT_BIN_UNBALANCED: return "a binary witness needs a conserved schema whose amounts balance (Binary.hs:162-164)";
-    default: return "unknown witness status";
-  }
-}
+// — the words and their texts: csrc/rpsetup.hpp, next to the host's witness_status
+using bppp_rps::WIT_OK; using bppp_rps::WIT_NOT_CANONICAL; using bppp_rps::WIT_UNBALANCED; using bppp_rps::WIT_OUT_OF_RANGE; using bppp_rps::WIT_BIN_NOT_CANONICAL;
+using bppp_rps::WIT_BIN_UNBALANCED; using bppp_rps::wit_status_text;
 
 struct WitDims { uint32_t nr, nlen, nmss, npub, has_types, nlive, conserve, coef_words, pub_words; };
 // rp->d_wit: [nr][WR_WORDS] range records | coefficients [..][8] (plain integers) | typed: [npub][WP_WORDS] public (type, amount, is_output);
@@ -70,12 +62,14 @@ BPPP_DI uint32_t wi_digit(fe &n, const fe &cf, uint32_t radix) {
 
 // amounts / types / blinds [B][nr][8] words as the caller gave them; d_pub NULL or [B][npub][8] canonical.  Out: in_sc [B][nr][3][8] (amount mod n,
 // type, blinding), dig / mul [B][nlen], mss [B][nmss], status [B].  The arrays of a proof whose status is not WIT_OK are unspecified.
+// src_index: NULL, or slot b (the block) reads proof src_index[b] of amounts / types / blinds / d_pub and writes slot b of every output — the
+// accepted proofs of a batch compacted (bppp_rp_prove_batch_status_device, csrc/rpwitness.hip)
 __global__ void __launch_bounds__(64) k_rpp_witness(WitDims D, const uint32_t *__restrict__ tab, const uint32_t *__restrict__ amounts, const uint32_t *__restrict__ types,
                                                     const uint32_t *__restrict__ blinds, const uint32_t *__restrict__ d_pub, uint32_t *in_sc, uint32_t *dig, uint32_t *mul,
-                                                    uint32_t *mss, uint32_t *__restrict__ status) {
+                                                    uint32_t *mss, uint32_t *__restrict__ status, const uint32_t *__restrict__ src_index) {
   __shared__ uint32_t bad;
   const uint32_t t = threadIdx.x;
-  const size_t b = blockIdx.x;
+  const size_t b = blockIdx.x, src = src_index ? src_index[b] : b;
   const uint32_t *coefs = tab + (size_t)D.nr * WR_WORDS, *pubs = coefs + D.coef_words;
   if (t == 0) bad = 0;
   for (uint32_t i = t; i < D.nlen; i += 64) { dig[b * D.nlen + i] = 0; mul[b * D.nlen + i] = 0; }
@@ -83,8 +77,8 @@ __global__ void __launch_bounds__(64) k_rpp_witness(WitDims D, const uint32_t *_
   __syncthreads();
   for (uint32_t i = t; i < D.nr; i += 64) {
     const uint32_t *R = tab + (size_t)i * WR_WORDS;
-    const size_t e = b * D.nr + i;
-    const fe amt = fe_load(amounts + e * 8), ty = fe_load(types + e * 8), bl = fe_load(blinds + e * 8);
+    const size_t e = b * D.nr + i, se = src * D.nr + i;
+    const fe amt = fe_load(amounts + se * 8), ty = fe_load(types + se * 8), bl = fe_load(blinds + se * 8);
     if (!wi_canonical(ty) || !wi_canonical(bl)) atomicOr(&bad, 1u << WIT_NOT_CANONICAL);
     fe_store(in_sc + e * 24, wi_smod_n(amt)); fe_store(in_sc + e * 24 + 8, ty); fe_store(in_sc + e * 24 + 16, bl);
     const uint32_t fl = R[WR_FLAGS];
@@ -119,7 +113,7 @@ __global__ void __launch_bounds__(64) k_rpp_witness(WitDims D, const uint32_t *_
         bool out;
         if (f < D.npub) {
           const uint32_t *P = pubs + (size_t)f * WP_WORDS;
-          tf = fe_load(P); v = d_pub ? fe_load(d_pub + (b * D.npub + f) * 8) : fe_load(P + 8); out = P[16] != 0;
+          tf = fe_load(P); v = d_pub ? fe_load(d_pub + (src * D.npub + f) * 8) : fe_load(P + 8); out = P[16] != 0;
         } else {
           const uint32_t *I = in_sc + (b * D.nr + (f - D.npub)) * 24;
           tf = fe_load(I + 8); v = fe_load(I); out = (tab[(size_t)(f - D.npub) * WR_WORDS + WR_FLAGS] & WF_OUTPUT) != 0;
@@ -135,22 +129,22 @@ __global__ void __launch_bounds__(64) k_rpp_witness(WitDims D, const uint32_t *_
 }
 
 // RangeProof.Binary: amounts / blinds [B][nr][8]; d_pub NULL or [B][8] canonical net_public.  Out: in_sc [B][nr][3][8] (amount mod n, blinding, 0),
-// bits [B][nlive] (one byte per live position), status [B]
+// bits [B][nlive] (one byte per live position), status [B]; src_index as for k_rpp_witness
 __global__ void __launch_bounds__(64) k_brp_witness(WitDims D, const uint32_t *__restrict__ tab, const uint32_t *__restrict__ amounts, const uint32_t *__restrict__ blinds,
                                                     const uint32_t *__restrict__ d_pub, uint32_t *__restrict__ in_sc, uint8_t *__restrict__ bits,
-                                                    uint32_t *__restrict__ status) {
+                                                    uint32_t *__restrict__ status, const uint32_t *__restrict__ src_index) {
   __shared__ uint32_t first_bad;             // (range << 3 | reason) of the lowest-numbered range the host's loop would stop at
   __shared__ uint32_t part[64 * 8];
   const uint32_t t = threadIdx.x;
-  const size_t b = blockIdx.x;
+  const size_t b = blockIdx.x, src = src_index ? src_index[b] : b;
   const uint32_t *coefs = tab + (size_t)D.nr * WR_WORDS, *netp = coefs + D.coef_words;
   if (t == 0) first_bad = 0xFFFFFFFFu;
   __syncthreads();
   fe vsum = fe_zero();
   for (uint32_t i = t; i < D.nr; i += 64) {
     const uint32_t *R = tab + (size_t)i * WR_WORDS;
-    const size_t e = b * D.nr + i;
-    const fe amt = fe_load(amounts + e * 8), bl = fe_load(blinds + e * 8), v = wi_smod_n(amt);
+    const size_t e = b * D.nr + i, se = src * D.nr + i;
+    const fe amt = fe_load(amounts + se * 8), bl = fe_load(blinds + se * 8), v = wi_smod_n(amt);
     const uint32_t fl = R[WR_FLAGS];
     vsum = (fl & WF_OUTPUT) ? fe_sub<1>(vsum, v) : fe_add<1>(vsum, v);
     fe_store(in_sc + e * 24, v); fe_store(in_sc + e * 24 + 8, bl); fe_store(in_sc + e * 24 + 16, fe_zero());      // scalarRPW' (Internal.hs:56-57): v g + bl h0
@@ -178,7 +172,7 @@ __global__ void __launch_bounds__(64) k_brp_witness(WitDims D, const uint32_t *_
   for (int k = 0; k < 8; k++) part[t * 8 + k] = vsum.v[k];
   __syncthreads();
   if (t == 0) {
-    fe s = d_pub ? fe_load(d_pub + b * 8) : fe_load(netp);
+    fe s = d_pub ? fe_load(d_pub + src * 8) : fe_load(netp);
     for (uint32_t l = 0; l < 64; l++) { fe p; for (int k = 0; k < 8; k++) p.v[k] = part[l * 8 + k]; s = fe_add<1>(s, p); }
     status[b] = first_bad != 0xFFFFFFFFu ? (first_bad & 7u) : (D.conserve && fe_is_zero(s)) ? WIT_OK : WIT_BIN_UNBALANCED;
   }
@@ -205,14 +199,15 @@ BPPP_DI uint32_t enc_sign(const uint32_t *pt) {
 }
 // in_pt [B][nr][16]; com: the range-proof commitments (EncDims::lead_*); resp [k][B][2][16] in round order (the file lists the LAST round
 // first, Bulletproof.hs:359); wn [B][fn][8], wl [B][fl][8] canonical.  coms_files [B][coms_bytes], proof_files [B][proof_bytes]
+// dst_index: NULL, or the files of slot b (the block) are those of proof dst_index[b] in the two file buffers
 __global__ void __launch_bounds__(256) k_rp_encode_files(EncDims D, const uint32_t *__restrict__ in_pt, const uint32_t *__restrict__ com, const uint32_t *__restrict__ resp,
                                                          const uint32_t *__restrict__ wn, const uint32_t *__restrict__ wl, uint8_t *__restrict__ coms_files,
-                                                         uint8_t *__restrict__ proof_files) {
-  const size_t b = blockIdx.x;
+                                                         uint8_t *__restrict__ proof_files, const uint32_t *__restrict__ dst_index) {
+  const size_t b = blockIdx.x, dst = dst_index ? dst_index[b] : b;
   const uint32_t t = threadIdx.x;
   {
     const uint32_t ns = (D.nr + 7) / 8;
-    uint8_t *f = coms_files + b * D.coms_bytes;
+    uint8_t *f = coms_files + dst * D.coms_bytes;
     const uint32_t *pts = in_pt + b * D.nr * 16;
     for (uint32_t o = t; o < D.coms_bytes; o += 256) {
       uint8_t v = 0;
@@ -227,7 +222,7 @@ __global__ void __launch_bounds__(256) k_rp_encode_files(EncDims D, const uint32
     const uint32_t r = j - D.nlead, round = D.k - 1 - (r >> 1);
     return resp + (((size_t)round * D.batch + b) * 2 + (r & 1)) * 16;
   };
-  uint8_t *f = proof_files + b * D.proof_bytes;
+  uint8_t *f = proof_files + dst * D.proof_bytes;
   for (uint32_t o = t; o < D.proof_bytes; o += 256) {
     uint8_t v = 0;
     if (o < 32 * nsc) {
@@ -242,6 +237,25 @@ __global__ void __launch_bounds__(256) k_rp_encode_files(EncDims D, const uint32
     }
     f[o] = v;
   }
+}
+
+// ---- a batch with refused proofs (bppp_rp_prove_batch_status_device): the accepted ones are proved in compact order
+// slot s (one workgroup) takes the randomness prefix and the canonical public words of proof index[s]: prefix_out [n][prefix_len] bytes, pub_out
+// [n][pub_words] (pub NULL or pub_words 0: none)
+__global__ void __launch_bounds__(256) k_rp_gather_accepted(const uint32_t *__restrict__ index, const uint8_t *__restrict__ prefix, uint32_t prefix_len,
+                                                            const uint32_t *__restrict__ pub, uint32_t pub_words, uint8_t *__restrict__ prefix_out,
+                                                            uint32_t *__restrict__ pub_out) {
+  const size_t s = blockIdx.x, src = index[s];
+  for (uint32_t o = threadIdx.x; o < prefix_len; o += 256) prefix_out[s * prefix_len + o] = prefix[src * prefix_len + o];
+  if (pub)
+    for (uint32_t o = threadIdx.x; o < pub_words; o += 256) pub_out[s * pub_words + o] = pub[src * pub_words + o];
+}
+// the two files of every refused proof (one workgroup each, consecutive lanes on consecutive bytes) become zero bytes
+__global__ void __launch_bounds__(256) k_rp_zero_files(const uint32_t *__restrict__ index, uint32_t coms_bytes, uint32_t proof_bytes, uint8_t *__restrict__ coms_files,
+                                                       uint8_t *__restrict__ proof_files) {
+  const size_t dst = index[blockIdx.x];
+  for (uint32_t o = threadIdx.x; o < coms_bytes; o += 256) coms_files[dst * coms_bytes + o] = 0;
+  for (uint32_t o = threadIdx.x; o < proof_bytes; o += 256) proof_files[dst * proof_bytes + o] = 0;
 }
 
 // ---- host side: the per-range data of a setup, uploaded once per handle
@@ -294,17 +308,17 @@ inline int wit_ensure_tables(bppp_rp *rp) {
 }
 
 // the witness kernel of the handle's kind, queued on its stream.  Typed: dig / mul / mss as rpp_device_prove takes them; binary: `bits` [B][nlive]
-// bytes (dig / mul / mss unused)
+// bytes (dig / mul / mss unused).  src_index: NULL, or B slots that read the proofs it lists (the kernels' comment)
 inline int wit_launch(bppp_rp *rp, size_t B, const void *d_amounts, const void *d_types, const void *d_blinds, const uint32_t *d_pub, uint32_t *in_sc, uint32_t *dig,
-                      uint32_t *mul, uint32_t *mss, uint8_t *bits, uint32_t *status) {
+                      uint32_t *mul, uint32_t *mss, uint8_t *bits, uint32_t *status, const uint32_t *src_index = nullptr) {
   bppp_ctx *ctx = rp->ctx;
   { int rc = wit_ensure_tables(rp); if (rc) return rc; }
   const WitDims D = wit_dims(rp);
   if (rp->st.kind == 1)
-    k_brp_witness<<<dim3((unsigned)B), dim3(64), 0, ctx->stream>>>(D, rp->d_wit, (const uint32_t *)d_amounts, (const uint32_t *)d_blinds, d_pub, in_sc, bits, status);
+    k_brp_witness<<<dim3((unsigned)B), dim3(64), 0, ctx->stream>>>(D, rp->d_wit, (const uint32_t *)d_amounts, (const uint32_t *)d_blinds, d_pub, in_sc, bits, status, src_index);
   else
     k_rpp_witness<<<dim3((unsigned)B), dim3(64), 0, ctx->stream>>>(D, rp->d_wit, (const uint32_t *)d_amounts, (const uint32_t *)d_types, (const uint32_t *)d_blinds, d_pub,
-                                                                  in_sc, dig, mul, mss, status);
+                                                                  in_sc, dig, mul, mss, status, src_index);
   BPPP_HIP(ctx, hipGetLastError());
   return BPPP_OK;
 }

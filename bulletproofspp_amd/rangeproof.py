@@ -929,6 +929,30 @@ class NativeRangeProofs:
         binary handle, d_public_amounts 0 = the setup's amounts).  On return d_coms / d_proofs hold the files prove_batch returns."""
         self.gpu.rp_prove_batch_device(self.h, batch, d_amounts, d_types, d_blinds, d_public_amounts, d_prefix, prefix_len, d_coms, d_proofs)
 
+    def prove_batch_status(self, inputs, rand_prefixes: Sequence[bytes], public_amounts=None):
+        """bppp_rp_prove_batch_status: prove_batch that refuses proof by proof.  Returns (files, statuses): files[b] is (commitments file, proof
+        file) — the bytes prove_batch gives for proof b alone — or None for a refused proof; statuses[b] is its capi.RP_WIT_* verdict (0 =
+        accepted)."""
+        import ctypes as C
+        import numpy as np
+        B = len(inputs)
+        if B == 0:
+            return [], []
+        amt, typ, bld, pre, plen, cf, pf = self._prove_arrays(self._prove_rows(inputs), rand_prefixes)
+        status = np.zeros(B, dtype=np.uint32)
+        vp = lambda a: C.c_void_p(a.ctypes.data)
+        with self._public_arg(public_amounts, B, False) as pa:
+            rc = self.gpu.lib.bppp_rp_prove_batch_status(self.h, B, vp(amt), vp(typ), vp(bld), pa, vp(pre), plen, vp(cf), vp(pf), vp(status))
+        self.gpu._check(rc, "bppp_rp_prove_batch_status")
+        files = self._prove_files(B, cf, pf)
+        return [f if s == 0 else None for f, s in zip(files, status)], [int(s) for s in status]
+
+    def prove_batch_status_device(self, batch: int, d_amounts: int, d_types: int, d_blinds: int, d_prefix: int, prefix_len: int, d_coms: int, d_proofs: int,
+                                  d_public_amounts: int = 0):
+        """bppp_rp_prove_batch_status_device: prove_batch_device that refuses proof by proof.  Returns the verdicts (numpy uint32 [batch], capi.RP_WIT_*); on
+        return d_coms / d_proofs hold the accepted proofs' files and zero bytes for the refused ones."""
+        return self.gpu.rp_prove_batch_status_device(self.h, batch, d_amounts, d_types, d_blinds, d_public_amounts, d_prefix, prefix_len, d_coms, d_proofs)
+
     def _prove_rows(self, inputs):
         """one (amount, type, blinding) per range, as this class's prove_batch takes its inputs"""
         return inputs

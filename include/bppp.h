@@ -553,6 +553,45 @@ int bppp_rp_prove_batch_device(bppp_rp *rp, size_t batch, const void *d_amounts,
                                const void *d_public_amounts, const void *d_rand_prefix, size_t prefix_len, void *d_coms_files,
                                void *d_proof_files);
 
+/* ---- per-proof witness verdicts: skip the refused proofs, prove the rest ---------------------------------------------------------------
+ * bppp_rp_prove_batch_status is bppp_rp_prove_batch_pub, and bppp_rp_prove_batch_status_device is bppp_rp_prove_batch_device, with one
+ * more argument: proof_status [batch], in HOST memory on both (as for bppp_rp_verify_each_device), required.  A witness the counterpart
+ * would refuse no longer fails the call: proof_status[b] says why (BPPP_RP_WIT_*), the other proofs are proved in the same single
+ * lockstep pass.
+ * Return code: BPPP_OK whenever the call itself was well formed, however many proofs were refused — all of them included.  The
+ * counterpart's call-level errors stay, with its code and message: NULL buffers, batch >= 2^20, prefix_len > 4096, a public amount that
+ * is not canonical (or given to a handle whose public_count is 0), a closed context.  A NULL proof_status with batch > 0 is BPPP_ERR_ARG;
+ * an empty batch is BPPP_OK.
+ * Accepted proofs (proof_status[b] == BPPP_RP_WIT_OK): the two files of proof b are, byte for byte, what bppp_rp_prove_batch_pub writes
+ * when given proof b's inputs alone, on every route — a proof's randomness comes from its own prefix and its transcript is its own, so
+ * neither its position in the batch nor its neighbours matter.
+ * Refused proofs: both files of proof b are all zero bytes (on the host, and in HBM), and proof_status[b] is the reason
+ * bppp_rp_prove_batch_pub gives for proof b alone — a typed handle reports the lowest code that applies (canonical types and blindings
+ * are checked first, then the balance, then the ranges), a binary handle the first offending range (its blinding, then its bounds) and,
+ * if there is none, the balance.  Host and _device variants report identical statuses.  bppp_rp_witness_status_text is the text after
+ * "proof N: " in the counterpart's message (a static string; "unknown witness status" for any other value).
+ * Bookkeeping: the decision to build the comb table counts the submitted batch, as the counterpart does, before any witness is looked
+ * at.  The accepted proofs are proved as a batch of their own: HOST_ORACLE_MAX applies to their number, and so does SPLIT_MIN /
+ * SPLIT_MIN_BINARY on the host-buffer routes; on the device stream the submitted batch is split (each half checks and compacts its own
+ * proofs in HBM; statuses sit at their indices in the whole batch).  None of this changes a byte.
+ * Device stream (bppp_rp_prove_batch_device's conditions): nothing of a proof crosses to the host but its status word; a batch without a
+ * refusal queues exactly the kernels of bppp_rp_prove_batch_device.  Otherwise the accepted proofs' indices go up, the witness kernel
+ * runs again over them in compact order, and one kernel zeroes the refused proofs' files.
+ * Not covered: bppp_rp_prove_mixed; verdicts on public amounts (the caller's own inputs). */
+#define BPPP_RP_WIT_OK 0u
+#define BPPP_RP_WIT_NOT_CANONICAL 1u      /* typed: a type or blinding >= n */
+#define BPPP_RP_WIT_UNBALANCED 2u         /* typed: amounts of some type do not balance */
+#define BPPP_RP_WIT_OUT_OF_RANGE 3u       /* either kind */
+#define BPPP_RP_WIT_BIN_NOT_CANONICAL 4u  /* binary: a blinding >= n */
+#define BPPP_RP_WIT_BIN_UNBALANCED 5u     /* binary: no conserved, balancing schema */
+const char *bppp_rp_witness_status_text(uint32_t status);
+int bppp_rp_prove_batch_status(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds,
+                               const uint64_t *public_amounts, const uint8_t *rand_prefix, size_t prefix_len, uint8_t *coms_files,
+                               uint8_t *proof_files, uint32_t *proof_status);
+int bppp_rp_prove_batch_status_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds,
+                                      const void *d_public_amounts, const void *d_rand_prefix, size_t prefix_len, void *d_coms_files,
+                                      void *d_proof_files, uint32_t *proof_status /* host, [batch] */);
+
 /* ---- one comb table for the handles of a basis family --------------------------------------------------------------------------
  * Every setup's basis [g | H | G] is a prefix of the point stream its points came from (see bppp_rp_verify_mixed), and the comb table
  * is laid out tab[window][point][multiple]: the table of the longest basis of a stream contains the table of every shorter one (same
