@@ -36,6 +36,7 @@ SYMBOLS = [
     "bppp_rp_share_comb", "bppp_rp_comb_info", "bppp_rp_prove_mixed",
     "bppp_rp_prove_batch_device",
     "bppp_rp_prove_batch_status", "bppp_rp_prove_batch_status_device", "bppp_rp_witness_status_text",
+    "bppp_seed_candidate_x", "bppp_points_from_seed", "bppp_points_from_seed_device", "bppp_rp_create_seeded", "bppp_rp_create_binary_seeded",
 ]
 
 
@@ -157,6 +158,11 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_prove_batch_status_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp, vp, vp]
     lib.bppp_rp_witness_status_text.argtypes = [C.c_uint32]
     lib.bppp_rp_witness_status_text.restype = C.c_char_p
+    lib.bppp_seed_candidate_x.argtypes = [C.c_char_p, sz, C.c_uint64, vp]
+    lib.bppp_points_from_seed.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
+    lib.bppp_points_from_seed_device.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
+    lib.bppp_rp_create_seeded.argtypes = [vp, i, i, vp, sz, vp, sz, C.c_char_p, sz, C.c_char_p, C.POINTER(vp)]
+    lib.bppp_rp_create_binary_seeded.argtypes = [vp, i, i, vp, sz, vp, C.c_char_p, sz, C.c_char_p, C.POINTER(vp)]
     lib.bppp_profile_enable.argtypes = [vp, i]
     lib.bppp_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64), i]
     return lib
@@ -179,6 +185,8 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_rp_last_verify_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.bppp_test_rp_set_each_chunk.argtypes = [vp, sz]
     lib.bppp_test_rp_witness_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.bppp_test_points_from_seed_chunked.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, sz, vp, C.POINTER(C.c_uint64)]
+    lib.bppp_test_seed_lift_digests.argtypes = [vp, C.c_char_p, sz, vp, vp, vp]
     return lib
 
 
@@ -441,6 +449,31 @@ class Bppp:
 
     def lift_x(self, d_x: int, n: int, d_points: int):
         self._check(self.lib.bppp_lift_x_device(self.h, _ptr(d_x), n, _ptr(d_points)), "bppp_lift_x_device")
+
+    # ---- a setup's basis from its seed (getPoints)
+    def seed_candidate_x(self, seed: bytes, n: int) -> int:
+        """bppp_seed_candidate_x (host only): x of candidate n of the seed's stream, before the curve test"""
+        out = np.zeros(4, dtype=np.uint64)
+        rc = self.lib.bppp_seed_candidate_x(bytes(seed), len(seed), n, _ptr(out))
+        if rc != 0:
+            raise BpppError(f"bppp_seed_candidate_x failed ({rc})")
+        return limbs_to_int(out)
+
+    def points_from_seed(self, seed: bytes, count: int, first_candidate: int = 0, device: bool = False):
+        """`count` consecutive points of getPoints(seed), the search starting at candidate first_candidate: ((count, 8) uint64 array,
+        next_candidate) — or, with device=True, (device pointer, next_candidate): the points stay in HBM (release with free())."""
+        nxt = C.c_uint64(0)
+        if device:
+            d = self.alloc(max(count, 1) * 64)
+            rc = self.lib.bppp_points_from_seed_device(self.h, bytes(seed), len(seed), first_candidate, count, _ptr(d), C.byref(nxt))
+            if rc != 0:
+                self.free(d)
+            self._check(rc, "bppp_points_from_seed_device")
+            return d, int(nxt.value)
+        out = np.zeros((count, 8), dtype=np.uint64)
+        self._check(self.lib.bppp_points_from_seed(self.h, bytes(seed), len(seed), first_candidate, count, C.c_void_p(out.ctypes.data), C.byref(nxt)),
+                    "bppp_points_from_seed")
+        return out, int(nxt.value)
 
     # ---- device memory
     def alloc(self, nbytes: int) -> int:

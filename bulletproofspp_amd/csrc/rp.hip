@@ -541,11 +541,13 @@ void bppp_rp_destroy(bppp_rp *rp) {
   ctx_release(ctx);
 }
 
-int bppp_rp_create(bppp_ctx *ctx, int flavour, int has_types, const bppp_rp_range *ranges, size_t nranges, const bppp_rp_public *pubs, size_t npub,
-                   const uint64_t *points_xy, size_t npoints, const char *oracle_tag, bppp_rp **out) {
+// bppp_rp_create and bppp_rp_create_seeded: `seeded` takes the basis from getPoints (seed) once the setup's lengths are known
+// (csrc/seedpoints.hip) instead of points_xy, and is bppp_rp_create on those points from there
+static int rp_create_common(bppp_ctx *ctx, int flavour, int has_types, const bppp_rp_range *ranges, size_t nranges, const bppp_rp_public *pubs, size_t npub,
+                            const uint64_t *points_xy, size_t npoints, bool seeded, const uint8_t *seed, size_t seed_len, const char *oracle_tag, bppp_rp **out) {
   if (!ctx || !out || ctx_closed(ctx)) return BPPP_ERR_ARG;
   *out = nullptr;
-  if (!ranges || !nranges || (npub && !pubs) || !points_xy) return fail(ctx, BPPP_ERR_ARG, "rp_create: null argument");
+  if (!ranges || !nranges || (npub && !pubs) || (!seeded && !points_xy)) return fail(ctx, BPPP_ERR_ARG, "rp_create: null argument");
   if (flavour != 0 && flavour != 1) return fail(ctx, BPPP_ERR_ARG, "rp_create: flavour must be 0 (norm-linear argument) or 1 (inner-product argument)");
   if (nranges >= (1u << 20) || npub >= (1u << 20)) return fail(ctx, BPPP_ERR_ARG, "rp_create: too many ranges");
   std::vector<bppp_rps::RangeData> rds(nranges);
@@ -569,6 +571,13 @@ int bppp_rp_create(bppp_ctx *ctx, int flavour, int has_types, const bppp_rp_rang
     if (!bppp_rps::make_setup(has_types != 0, rds, pv, rp->st, err, flavour)) return fail(ctx, BPPP_ERR_ARG, "rp_create: " + err);
     const bppp_rps::Setup &st = rp->st;
     // points = h : g : hs (linLen) ++ gs (nrmLen)   (TypedReciprocal.hs:334, :348-349); h is not used by the proof
+    std::vector<uint64_t> seed_points;
+    if (seeded) {
+      npoints = 2 + st.llen + st.nlen;
+      seed_points.resize(npoints * 8);
+      int rc = bppp_points_from_seed(ctx, seed, seed_len, 0, npoints, seed_points.data(), nullptr); if (rc) return rc;
+      points_xy = seed_points.data();
+    }
     if (npoints < 2 + st.llen + st.nlen) return fail(ctx, BPPP_ERR_ARG, "rp_create: not enough basis points (need 2 + linLen + nrmLen)");
     if (!bppp_host::points_on_curve(points_xy, 2 + st.llen + st.nlen)) return fail(ctx, BPPP_ERR_POINT, "rp_create: a basis point is not on the curve");
     rp->h_g.assign(points_xy + 8, points_xy + 16);
@@ -595,6 +604,14 @@ int bppp_rp_create(bppp_ctx *ctx, int flavour, int has_types, const bppp_rp_rang
   if (int rc = fill()) { bppp_rp_destroy(rp); return rc; }
   *out = rp;
   return BPPP_OK;
+}
+int bppp_rp_create(bppp_ctx *ctx, int flavour, int has_types, const bppp_rp_range *ranges, size_t nranges, const bppp_rp_public *pubs, size_t npub,
+                   const uint64_t *points_xy, size_t npoints, const char *oracle_tag, bppp_rp **out) {
+  return rp_create_common(ctx, flavour, has_types, ranges, nranges, pubs, npub, points_xy, npoints, false, nullptr, 0, oracle_tag, out);
+}
+int bppp_rp_create_seeded(bppp_ctx *ctx, int flavour, int has_types, const bppp_rp_range *ranges, size_t nranges, const bppp_rp_public *pubs, size_t npub,
+                          const uint8_t *seed, size_t seed_len, const char *oracle_tag, bppp_rp **out) {
+  return rp_create_common(ctx, flavour, has_types, ranges, nranges, pubs, npub, nullptr, 0, true, seed, seed_len, oracle_tag, out);
 }
 
 // host-only: the shape a setup would have (no context, no GPU) — setup's arithmetic of TypedReciprocal.hs:332-359 alone
@@ -683,11 +700,11 @@ int bppp_rp_info(const bppp_rp *rp, bppp_rp_shape *out) {
 }
 
 // RangeProof.Binary behind the same handle: setupBRP (src/RangeProof/Binary.hs:143-156).  points = [h, g, h0, h1] ++ gs (:147-148)
-int bppp_rp_create_binary(bppp_ctx *ctx, int flavour, int conserve, const bppp_rp_range *ranges, size_t nranges, const uint64_t net_public[4],
-                          const uint64_t *points_xy, size_t npoints, const char *oracle_tag, bppp_rp **out) {
+static int rp_create_binary_common(bppp_ctx *ctx, int flavour, int conserve, const bppp_rp_range *ranges, size_t nranges, const uint64_t net_public[4],
+                                   const uint64_t *points_xy, size_t npoints, bool seeded, const uint8_t *seed, size_t seed_len, const char *oracle_tag, bppp_rp **out) {
   if (!ctx || !out || ctx_closed(ctx)) return BPPP_ERR_ARG;
   *out = nullptr;
-  if (!ranges || !nranges || !net_public || !points_xy) return fail(ctx, BPPP_ERR_ARG, "rp_create_binary: null argument");
+  if (!ranges || !nranges || !net_public || (!seeded && !points_xy)) return fail(ctx, BPPP_ERR_ARG, "rp_create_binary: null argument");
   if (flavour != 0 && flavour != 1) return fail(ctx, BPPP_ERR_ARG, "rp_create_binary: flavour must be 0 (norm-linear argument) or 1 (inner-product argument)");
   if (nranges > 1024) return fail(ctx, BPPP_ERR_ARG, "rp_create_binary: at most 1024 ranges");
   std::vector<bppp_rps::RangeData> rds(nranges);
@@ -704,6 +721,13 @@ int bppp_rp_create_binary(bppp_ctx *ctx, int flavour, int conserve, const bppp_r
   auto fill = [&]() -> int {
     if (!bppp_rps::make_setup_binary(conserve != 0, rds, bppp_rps::s_mod_n(U256::load(net_public)), flavour, rp->st, err)) return fail(ctx, BPPP_ERR_ARG, "rp_create_binary: " + err);
     const bppp_rps::Setup &st = rp->st;
+    std::vector<uint64_t> seed_points;
+    if (seeded) {
+      npoints = 4 + st.nlen;
+      seed_points.resize(npoints * 8);
+      int rc = bppp_points_from_seed(ctx, seed, seed_len, 0, npoints, seed_points.data(), nullptr); if (rc) return rc;
+      points_xy = seed_points.data();
+    }
     if (npoints < 4 + st.nlen) return fail(ctx, BPPP_ERR_ARG, "rp_create_binary: not enough basis points (need 4 + nrmLen)");
     if (!bppp_host::points_on_curve(points_xy, 4 + st.nlen)) return fail(ctx, BPPP_ERR_POINT, "rp_create_binary: a basis point is not on the curve");
     rp->h_g.assign(points_xy + 8, points_xy + 16);
@@ -728,6 +752,14 @@ int bppp_rp_create_binary(bppp_ctx *ctx, int flavour, int conserve, const bppp_r
   if (int rc = fill()) { bppp_rp_destroy(rp); return rc; }
   *out = rp;
   return BPPP_OK;
+}
+int bppp_rp_create_binary(bppp_ctx *ctx, int flavour, int conserve, const bppp_rp_range *ranges, size_t nranges, const uint64_t net_public[4],
+                          const uint64_t *points_xy, size_t npoints, const char *oracle_tag, bppp_rp **out) {
+  return rp_create_binary_common(ctx, flavour, conserve, ranges, nranges, net_public, points_xy, npoints, false, nullptr, 0, oracle_tag, out);
+}
+int bppp_rp_create_binary_seeded(bppp_ctx *ctx, int flavour, int conserve, const bppp_rp_range *ranges, size_t nranges, const uint64_t net_public[4],
+                                 const uint8_t *seed, size_t seed_len, const char *oracle_tag, bppp_rp **out) {
+  return rp_create_binary_common(ctx, flavour, conserve, ranges, nranges, net_public, nullptr, 0, true, seed, seed_len, oracle_tag, out);
 }
 
 // grow-only device workspace of the verifier; returns the carved pointers through `cv`

@@ -8,6 +8,7 @@
 #include "fr26.hip.h"
 #include "rp_internal.hpp"
 #include "rpwitness.hip.h"
+#include "seedpoints.hip.h"
 
 namespace bppp {
 template <int MOD> BPPP_DI fe apply_op(int op, const fe &a, const fe &b) {
@@ -283,4 +284,51 @@ extern "C" int bppp_test_rp_witness_device(bppp_rp *rp, size_t batch, const void
   if (!rc && binary) for (size_t i = 0; i < bits.size(); i++) dig[i] = bits[i];
   hipFree(d);
   return rc;
+}
+
+extern "C" int bppp_test_points_from_seed_chunked(bppp_ctx *ctx, const uint8_t *seed, size_t seed_len, uint64_t first_candidate, size_t count, size_t chunk,
+                                                  uint64_t *points_xy, uint64_t *next_candidate) {
+  if (!ctx || (seed_len && !seed) || seed_len > SEED_MAX_LEN || !count || !points_xy || !chunk || chunk > SEED_CHUNK_MAX || count >= (1u << 24)) return BPPP_ERR_ARG;
+  hipSetDevice(ctx->device);
+  SeedMsg M;
+  seed_msg_init(M, seed, seed_len);
+  void *scratch = nullptr, *d_out = nullptr;
+  if (hipMalloc(&scratch, seed_scratch_bytes(chunk)) != hipSuccess || hipMalloc(&d_out, count * 64) != hipSuccess) { hipFree(scratch); return bppp::fail(ctx, BPPP_ERR_HIP, "test_points_from_seed_chunked: hipMalloc"); }
+  int rc = seed_points_run(ctx, M, first_candidate, count, chunk, scratch, d_out, next_candidate);
+  if (!rc && (hipMemcpyAsync(points_xy, d_out, count * 64, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess))
+    rc = bppp::fail(ctx, BPPP_ERR_HIP, "test_points_from_seed_chunked: copy failed");
+  hipFree(scratch); hipFree(d_out);
+  return rc;
+}
+
+namespace bppp {
+__global__ void __launch_bounds__(64) k_test_seed_lift(const uint32_t *__restrict__ h, uint32_t n, uint32_t *__restrict__ x, uint32_t *__restrict__ is_point, uint32_t *__restrict__ pts) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t d[8];
+  for (int k = 0; k < 8; k++) d[k] = h[(size_t)i * 8 + k];
+  fe xe; aff pt;
+  const bool ok = seed_lift_digest(d, xe, pt);
+  if (!ok) pt = aff_inf();
+  fe_store(x + (size_t)i * 8, xe);
+  is_point[i] = ok ? 1u : 0u;
+  aff_store(pts + (size_t)i * 16, pt);
+}
+}  // namespace bppp
+extern "C" int bppp_test_seed_lift_digests(bppp_ctx *ctx, const uint8_t *digests, size_t n, uint64_t *x, uint32_t *is_point, uint64_t *points_xy) {
+  if (!ctx || !digests || !n || !x || !is_point || !points_xy || n >= (1u << 20)) return BPPP_ERR_ARG;
+  hipSetDevice(ctx->device);
+  std::vector<uint32_t> h(n * 8);
+  for (size_t i = 0; i < n * 8; i++) h[i] = ((uint32_t)digests[4 * i] << 24) | ((uint32_t)digests[4 * i + 1] << 16) | ((uint32_t)digests[4 * i + 2] << 8) | digests[4 * i + 3];
+  uint32_t *d = nullptr;                     // digests | x | points | flags
+  BPPP_HIP(ctx, hipMalloc(&d, n * (32 + 32 + 64 + 4)));
+  uint32_t *d_x = d + n * 8, *d_p = d_x + n * 8, *d_f = d_p + n * 16;
+  hipStream_t st = ctx->stream;
+  bool ok = hipMemcpyAsync(d, h.data(), n * 32, hipMemcpyHostToDevice, st) == hipSuccess;
+  if (ok) bppp::k_test_seed_lift<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st>>>(d, (uint32_t)n, d_x, d_f, d_p);
+  ok = ok && hipMemcpyAsync(x, d_x, n * 32, hipMemcpyDeviceToHost, st) == hipSuccess && hipMemcpyAsync(points_xy, d_p, n * 64, hipMemcpyDeviceToHost, st) == hipSuccess &&
+       hipMemcpyAsync(is_point, d_f, n * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+  if (hipStreamSynchronize(st) != hipSuccess) ok = false;
+  hipFree(d);
+  return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_seed_lift_digests: kernel or copy failed");
 }

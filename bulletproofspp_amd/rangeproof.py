@@ -830,7 +830,9 @@ class NativeRangeProofs:
     Both argument flavours verify and prove (bppp_rp_prove_batch: the norm-linear argument through csrc/nlb.hip, the inner-product one
     through csrc/ipb.hip once the handle has its comb table, csrc/rpprove.hip's host-algebra ip_argument_lockstep before that)."""
 
-    def __init__(self, gpu, st: SetupTRRP, oracle_tag: bytes = b"", h: Point = None):
+    def __init__(self, gpu, st: SetupTRRP, oracle_tag: bytes = b"", h: Point = None, basis_seed: Optional[bytes] = None):
+        """basis_seed: the schema's "basisSeed" as bytes — the library derives the basis from it on the GPU (bppp_rp_create_seeded:
+        getPoints from candidate 0) instead of taking st's points; `st` must be the setup over that same stream (setup_from_schema)."""
         import ctypes as C
         from .capi import RP_ASSUMED, RP_OUTPUT, RP_SHARED, RpPublic, RpRange, RpShape, int_to_limbs, points_to_array
         self.gpu, self.st, self.h = gpu, st, None
@@ -845,11 +847,16 @@ class NativeRangeProofs:
             p_.is_output = 1 if io else 0
             p_.type[:] = [int(x) for x in int_to_limbs(ty % N)]
             p_.amount[:] = [int(x) for x in int_to_limbs(v % N)]
-        pts = points_to_array([h if h is not None else st.g, st.g] + list(st.hs) + list(st.gs))
         hnd = C.c_void_p()
-        rc = gpu.lib.bppp_rp_create(gpu.h, 0 if st.flavour == "NL" else 1, int(st.has_types), C.cast(rng, C.c_void_p), len(st.rds), C.cast(pubs, C.c_void_p), len(st.pub_vt),
-                                    C.c_void_p(pts.ctypes.data), pts.shape[0], oracle_tag if oracle_tag else None, C.byref(hnd))
-        gpu._check(rc, "bppp_rp_create")
+        if basis_seed is not None:
+            rc = gpu.lib.bppp_rp_create_seeded(gpu.h, 0 if st.flavour == "NL" else 1, int(st.has_types), C.cast(rng, C.c_void_p), len(st.rds), C.cast(pubs, C.c_void_p),
+                                               len(st.pub_vt), bytes(basis_seed), len(basis_seed), oracle_tag if oracle_tag else None, C.byref(hnd))
+            gpu._check(rc, "bppp_rp_create_seeded")
+        else:
+            pts = points_to_array([h if h is not None else st.g, st.g] + list(st.hs) + list(st.gs))
+            rc = gpu.lib.bppp_rp_create(gpu.h, 0 if st.flavour == "NL" else 1, int(st.has_types), C.cast(rng, C.c_void_p), len(st.rds), C.cast(pubs, C.c_void_p), len(st.pub_vt),
+                                        C.c_void_p(pts.ctypes.data), pts.shape[0], oracle_tag if oracle_tag else None, C.byref(hnd))
+            gpu._check(rc, "bppp_rp_create")
         self.h = hnd
         gpu._adopt(self)
         shp = RpShape()

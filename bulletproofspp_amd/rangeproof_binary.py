@@ -208,7 +208,8 @@ class NativeBinaryRangeProofs(NativeRangeProofs):
     reciprocal proofs — verify_batch* decode the reference's files, hash every transcript and decide the batch with one MSM
     (verifyBRPM + verifyBPM); prove_batch is proveBRPM + proveBPM in lockstep (norm-linear argument)."""
 
-    def __init__(self, gpu, st: SetupBRP, oracle_tag: bytes = b"", h: Point = None):
+    def __init__(self, gpu, st: SetupBRP, oracle_tag: bytes = b"", h: Point = None, basis_seed: Optional[bytes] = None):
+        """basis_seed: as NativeRangeProofs — the basis comes from the schema's "basisSeed" on the GPU (bppp_rp_create_binary_seeded)"""
         import ctypes as C
         from .capi import RP_ASSUMED, RP_OUTPUT, RpRange, RpShape, int_to_limbs, points_to_array
         self.gpu, self.st, self.h = gpu, st, None
@@ -218,12 +219,17 @@ class NativeBinaryRangeProofs(NativeRangeProofs):
             r.flags = (RP_OUTPUT if rd.is_output else 0) | (RP_ASSUMED if rd.is_assumed else 0)
             r.min[:] = [int(v) for v in int_to_limbs(rd.lo % 2**256)]
             r.max[:] = [int(v) for v in int_to_limbs(rd.hi % 2**256)]
-        pts = points_to_array([h if h is not None else st.g, st.g] + list(st.hs) + list(st.gs))
         net = int_to_limbs(st.net_public % 2**256)
         hnd = C.c_void_p()
-        rc = gpu.lib.bppp_rp_create_binary(gpu.h, 0 if st.flavour == "NL" else 1, int(st.conserve), C.cast(rng, C.c_void_p), len(st.rds), C.c_void_p(net.ctypes.data),
-                                           C.c_void_p(pts.ctypes.data), pts.shape[0], oracle_tag if oracle_tag else None, C.byref(hnd))
-        gpu._check(rc, "bppp_rp_create_binary")
+        if basis_seed is not None:
+            rc = gpu.lib.bppp_rp_create_binary_seeded(gpu.h, 0 if st.flavour == "NL" else 1, int(st.conserve), C.cast(rng, C.c_void_p), len(st.rds), C.c_void_p(net.ctypes.data),
+                                                      bytes(basis_seed), len(basis_seed), oracle_tag if oracle_tag else None, C.byref(hnd))
+            gpu._check(rc, "bppp_rp_create_binary_seeded")
+        else:
+            pts = points_to_array([h if h is not None else st.g, st.g] + list(st.hs) + list(st.gs))
+            rc = gpu.lib.bppp_rp_create_binary(gpu.h, 0 if st.flavour == "NL" else 1, int(st.conserve), C.cast(rng, C.c_void_p), len(st.rds), C.c_void_p(net.ctypes.data),
+                                               C.c_void_p(pts.ctypes.data), pts.shape[0], oracle_tag if oracle_tag else None, C.byref(hnd))
+            gpu._check(rc, "bppp_rp_create_binary")
         self.h = hnd
         gpu._adopt(self)
         shp = RpShape()

@@ -365,6 +365,15 @@ int bppp_rp_create(bppp_ctx *ctx, int flavour, int has_types, const bppp_rp_rang
  * agrees wherever its own proofs verify — SURVEY.md App. D-1). */
 int bppp_rp_create_binary(bppp_ctx *ctx, int flavour, int conserve, const bppp_rp_range *ranges, size_t nranges, const uint64_t net_public[4],
                           const uint64_t *points_xy, size_t npoints, const char *oracle_tag, bppp_rp **out);
+/* The two constructors with the basis named as the schema names it, by its "basisSeed": each generates the points its counterpart
+ * requires for the shape (2 + lin_len + norm_len; 4 + nrmLen) with bppp_points_from_seed from candidate 0 and is the counterpart
+ * called with them from there — same handle, same bytes, every argument error of the counterpart with its message, and those of
+ * bppp_points_from_seed for the seed.  Handles seeded alike hold prefixes of one stream: bppp_rp_share_comb and the merging of
+ * bppp_rp_verify_mixed work on them as on any handles of one basis. */
+int bppp_rp_create_seeded(bppp_ctx *ctx, int flavour, int has_types, const bppp_rp_range *ranges, size_t nranges, const bppp_rp_public *pubs,
+                          size_t npub, const uint8_t *seed, size_t seed_len, const char *oracle_tag, bppp_rp **out);
+int bppp_rp_create_binary_seeded(bppp_ctx *ctx, int flavour, int conserve, const bppp_rp_range *ranges, size_t nranges,
+                                 const uint64_t net_public[4], const uint8_t *seed, size_t seed_len, const char *oracle_tag, bppp_rp **out);
 void bppp_rp_destroy(bppp_rp *rp);
 int bppp_rp_info(const bppp_rp *rp, bppp_rp_shape *out);
 /* Tuning knobs of one handle.  Every knob has a measured default; the BPPP_RP_* environment variables of the
@@ -637,6 +646,28 @@ int bppp_rp_prove_mixed(const bppp_rp_prove_group *groups, size_t ngroups);
  * galois-field's `sr` returns cannot be confirmed offline — SURVEY.md 8c; even-y is this build's
  * documented choice.)  Used to make synthetic bases on the GPU. */
 int bppp_lift_x_device(bppp_ctx *ctx, const void *d_x, size_t n, void *d_points_xy);
+
+/* ---- a setup's basis from its seed: getPoints (app/Main.hs:68-72), the stream h : g : hs ++ gs the CLI hands to setup (:260) -------
+ * Candidate n of `seed` is x = decode (SHA-256 (seed <> decimal ASCII of n)) mod p, decode = Binary (Prime p) (src/Encoding.hs:75-79:
+ * four big-endian 64-bit words, least significant first); it is a point iff x^3 + 7 is a square, with the EVEN root as y (the choice
+ * of bppp_lift_x_device).  The stream is the accepted candidates in increasing n, so every basis of one seed is a prefix of every
+ * longer one — what bppp_rp_share_comb and the basis merging of bppp_rp_verify_mixed compare.  The work runs on the GPU in ordered
+ * passes (csrc/seedpoints.hip.h: one lane per candidate, ballot / LDS / one scan for the slots, no atomics): the same call writes the
+ * same bytes every time.
+ *
+ * bppp_seed_candidate_x: host only, no context, no GPU: x of candidate n (before the curve test).
+ * bppp_points_from_seed{,_device}: `count` consecutive points of the stream, the search starting at candidate `first_candidate`;
+ * *next_candidate (may be NULL) = the index after the last accepted candidate, so a later call with it continues the same stream.
+ * points_xy: [count][8] words on the host; _device: the same in HBM, ready for bppp_basis_create_device.
+ * `seed` may be NULL iff seed_len == 0; seed_len <= 4096.  count == 0 returns BPPP_OK, writes nothing and sets *next_candidate =
+ * first_candidate.  BPPP_ERR_ARG: a seed outside those rules, a NULL output with count > 0, a closed context, or a search that would
+ * run past the last candidate (the stream ends with candidate 2^64 - 2, so that *next_candidate always names a candidate; nothing is
+ * promised about the output then). */
+int bppp_seed_candidate_x(const uint8_t *seed, size_t seed_len, uint64_t n, uint64_t out_x[4]);
+int bppp_points_from_seed_device(bppp_ctx *ctx, const uint8_t *seed, size_t seed_len, uint64_t first_candidate, size_t count, void *d_points_xy,
+                                 uint64_t *next_candidate);
+int bppp_points_from_seed(bppp_ctx *ctx, const uint8_t *seed, size_t seed_len, uint64_t first_candidate, size_t count, uint64_t *points_xy,
+                          uint64_t *next_candidate);
 
 /* ---- device memory helpers (so a non-HIP host language can keep vectors resident) ---------- */
 int bppp_device_alloc(bppp_ctx *ctx, size_t bytes, void **d_ptr);

@@ -52,6 +52,13 @@ int bppp_test_rp_set_each_chunk(bppp_rp *rp, size_t proofs);
  * bits, mul and mss are not written (may be NULL). */
 int bppp_test_rp_witness_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds,
                                 const void *d_public_amounts, uint64_t *in_sc, uint32_t *dig, uint32_t *mul, uint32_t *mss, uint32_t *status);
+/* bppp_points_from_seed with every pass forced to `chunk` candidates (1 .. 2^20; csrc/seedpoints.hip.h): a small request crosses pass
+ * and workgroup boundaries.  points_xy: host, [count][8] words. */
+int bppp_test_points_from_seed_chunked(bppp_ctx *ctx, const uint8_t *seed, size_t seed_len, uint64_t first_candidate, size_t count, size_t chunk,
+                                       uint64_t *points_xy, uint64_t *next_candidate);
+/* The decode-and-lift step of the candidate kernel on caller-given digests ([n][32] bytes as SHA-256 writes them) — a digest that
+ * decodes to p or more is out of any hash's reach: x [n][4] = decode mod p, is_point [n], points_xy [n][8] (zero where not a point). */
+int bppp_test_seed_lift_digests(bppp_ctx *ctx, const uint8_t *digests, size_t n, uint64_t *x, uint32_t *is_point, uint64_t *points_xy);
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
