@@ -43,6 +43,7 @@ void MsmTune::from_env() {
   window_batched = geti("BPPP_WINDOW_BATCHED"); comb_wpe = geti("BPPP_COMB_WPE"); comb_rows_waves = geti("BPPP_COMB_ROWS_WAVES"); reduce_old = getenv("BPPP_REDUCE_OLD") != nullptr;
   small_c = geti("BPPP_MSM_SMALL_C"); small_len = geti("BPPP_MSM_SMALL_LEN"); small_max = geti("BPPP_MSM_SMALL_MAX"); hist_ch = geti("BPPP_HIST_CH"); no_small = getenv("BPPP_MSM_NO_SMALL") != nullptr; if (getenv("BPPP_COMB_ROWS_MIN_MB")) comb_rows_min_bytes = (size_t)strtoull(getenv("BPPP_COMB_ROWS_MIN_MB"), nullptr, 10) << 20; no_balance = getenv("BPPP_MSM_NO_BALANCE") != nullptr;
   tail_scalar = getenv("BPPP_REDUCE_TAIL_SCALAR") != nullptr;     // k_reduce_tail (one lane per element) instead of k_reduce_tail_quad
+  if (const char *e = getenv("BPPP_SORT_RANGES")) sort_ranges = atoi(e);   // 0 k_scatter, 2 / 4 k_scatter_ranges with that many bucket ranges per window
   if (const char *e = getenv("BPPP_ACC_LDS")) acc_lds = atoi(e) != 0;   // k_acc_points_lds (next point prefetched into LDS) instead of k_acc_points
 }
 namespace bppp {

@@ -180,6 +180,46 @@ __global__ void k_scatter(const uint16_t *__restrict__ dig, const unsigned long 
   }
 }
 
+// The scatter of ONE MSM with wide windows (M * 4 > 80 KiB; make_plan, MsmPlan::Q), by bucket range.  k_scatter's stores are its whole cost:
+// a bucket's ~n / M entries (one 128-byte line at 2^20 terms) arrive from CH workgroups that sit on all 8 XCDs, so every 4-byte store leaves an
+// L2 as a request of its own.  Here a workgroup is (window w, range q of Q, chunk ch): it reads its chunk of the window's digit row as
+// k_scatter does, keeps only the cursors of the M / Q buckets of its range in LDS and places only their entries, at the positions k_scatter
+// would use (the order inside a (bucket, chunk) may differ).  The 1-D grid puts the chunks of one (w, q) unit on blocks b = s (mod 8), the
+// observed XCD affinity: an XCD works through its units one after another and the unit's slice of `sorted` (n * 4 / Q bytes) can stay in its
+// 4-MiB L2 until the lines are full.  That is placement for speed only — any dispatch order and any block -> XCD map give the same `sorted`
+// positions; no workgroup waits for another.  The digit row is re-read Q times (non-temporal: it should not push the output lines out).
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__global__ void k_scatter_ranges(const uint16_t *__restrict__ dig, const unsigned long long *__restrict__ negmask, uint32_t n, uint32_t stride,
+                                 int c, int CH, int Q, uint32_t U, const uint32_t *__restrict__ blockhist, const uint32_t *__restrict__ start,
+                                 uint32_t *__restrict__ sorted) {
+  extern __shared__ uint32_t lh[];
+  const uint32_t M = 1u << (c - 1), Mq = M / (uint32_t)Q;
+  const uint32_t s = blockIdx.x & 7u, k = blockIdx.x >> 3, u = (k / (uint32_t)CH) * 8u + s, ch = k % (uint32_t)CH;
+  if (u >= U) return;                                       // the grid is padded to 8 slots x whole units
+  const uint32_t nbw = u / (uint32_t)Q, r0 = (u % (uint32_t)Q) * Mq;   // the (nearly empty) carry window's units come last
+  const uint32_t *bh = blockhist + ((size_t)nbw * CH + ch) * M + r0;
+  const uint32_t *st = start + (size_t)nbw * M + r0;
+  for (uint32_t t = threadIdx.x; t < Mq; t += blockDim.x) lh[t] = st[t] + bh[t];
+  __syncthreads();
+  uint32_t per = (((n + CH - 1) / CH) + 7u) & ~7u, lo = ch * per, hi = min(n, lo + per);
+  const uint16_t *d = dig + (size_t)nbw * stride;
+  for (uint32_t j0 = lo + threadIdx.x * 8; j0 < hi; j0 += blockDim.x * 8) {
+    u32x4 pk = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(d + j0));
+    uint32_t w[4] = {pk.x, pk.y, pk.z, pk.w};
+    const uint32_t sneg8 = (uint32_t)(negmask[j0 >> 6] >> (j0 & 63u));   // one instance, j0 a multiple of 8: the 8 sign bits share a word
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+      int v = (int)((w[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu) - (int)M;
+      uint32_t mb = (uint32_t)(v < 0 ? -v : v) - 1u - r0;   // v == 0: wraps past Mq
+      if (j0 + e < hi && v && mb < Mq) {
+        uint32_t sg = (v < 0 ? 1u : 0u) ^ ((sneg8 >> e) & 1u);
+        uint32_t pos = atomicAdd(&lh[mb], 1u);
+        sorted[pos] = (sg << 31) | (j0 + e);
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // 3. load-balanced accumulation
 // Lane g owns sorted positions [g*L, (g+1)*L).  A bucket b = [start[b], start[b]+count[b]) that lies
@@ -833,6 +873,7 @@ struct MsmPlan {
   int RG;                      // k_reduce_groups lanes per window (0 = wave-per-window path)
   bool marg; MargGeom mg;      // marginal-sum reduction (M >= 256, not the grouped path)
   int ntiles;
+  int Q;                       // bucket ranges per window of the ranged scatter (k_scatter_ranges); 0 = k_scatter
 };
 
 static MsmPlan make_plan(size_t n, size_t batch, int c, bool flat, const MsmTune &tune) {
@@ -856,7 +897,19 @@ static MsmPlan make_plan(size_t n, size_t batch, int c, bool flat, const MsmTune
   // the histogram of a wide window (>= 80 KB of LDS) leaves room for ONE k_hist / k_scatter workgroup per CU: a grid a few workgroups
   // over a whole number of rounds (17 windows x 16 chunks on 256 CUs) runs a nearly empty extra round — take the chunk count that fills
   // the rounds instead (15: sort stage 0.301 -> 0.277 ms at 2^20)
-  if ((size_t)p.M * 4 > 80 * 1024 && tune.num_cus > 0) {
+  // ranged scatter (k_scatter_ranges): a (window, range) unit has as many chunks as an XCD has CUs (num_cus / 8: 32).  Two of its workgroups
+  // fit on a CU, so two units are live on an XCD: 2 MiB of `sorted` slices (n * 4 / Q bytes each for evenly spread digits) at 2^20 terms and
+  // Q = 4, half of the L2.  Measured there, sort stage: Q = 4 0.229 / 0.212 / 0.277 ms at 16 / 32 / 64 chunks, Q = 2 0.299 / 0.218 / 0.287
+  // (k_scatter, 15 chunks: 0.260).  A shorter input takes fewer chunks — more units are then live, still about 2 MiB of slices in all — but
+  // never fewer than the rule above gives.
+  // k_hist, k_count_tiles and the blockhist layout use the same chunk count.
+  p.Q = 0;
+  if (batch == 1 && !flat && (size_t)p.M * 4 > 80 * 1024 && tune.num_cus >= 8 && (tune.sort_ranges == 2 || tune.sort_ranges == 4)) {
+    p.Q = tune.sort_ranges;
+    const uint64_t cus = (uint64_t)tune.num_cus / 8, unit_bytes = (uint64_t)n * 4 / p.Q;
+    const uint64_t ch = (cus * unit_bytes + (1u << 20) - 1) >> 20;
+    p.CH = (int)std::min<uint64_t>(std::min<uint64_t>(cus, 64), std::max<uint64_t>((uint64_t)p.CH, ch));
+  } else if ((size_t)p.M * 4 > 80 * 1024 && tune.num_cus > 0) {
     const double rounds = (double)p.NB * p.CH / tune.num_cus;
     if (rounds >= 0.75) {
       const uint64_t r = (uint64_t)(rounds + 0.5) ? (uint64_t)(rounds + 0.5) : 1;
@@ -1030,6 +1083,7 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
     if (lds > 64 * 1024 && lds > ctx->sort_lds_set) {
       BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter_ranges, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       ctx->sort_lds_set = lds;
     }
     prof_mark(ctx, 0);
@@ -1043,8 +1097,14 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
     // flat: the (window, chunk) histograms of an instance are W * CH chunks of ONE bucket set (same memory layout)
     k_count_tiles<<<dim3((unsigned)((p.FB + 255) / 256)), dim3(256), 0, st>>>(blockhist, p.M, p.flat ? p.W * p.CH : p.CH, p.FB, count, tiles);
     k_scan_apply<<<dim3(p.ntiles), dim3(256), 0, st>>>(count, p.FB, tiles, start);
-    k_scatter<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(dig, negmask, (uint32_t)n, stride, c, p.CH, p.W, blockhist, start, sorted,
-                                                                             p.flat ? (uint32_t)table_stride : 0u);
+    ctx->last_sort_ranges = p.Q;
+    if (p.Q) {
+      const uint32_t U = (uint32_t)p.W * p.Q;                // units (window, range); 8 slots x ceil(U / 8) units x CH chunks
+      k_scatter_ranges<<<dim3(8u * ((U + 7) / 8) * p.CH), dim3(p.hist_threads), lds / p.Q, st>>>(dig, negmask, (uint32_t)n, stride, c, p.CH, p.Q, U,
+                                                                                                 blockhist, start, sorted);
+    } else
+      k_scatter<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(dig, negmask, (uint32_t)n, stride, c, p.CH, p.W, blockhist, start, sorted,
+                                                                               p.flat ? (uint32_t)table_stride : 0u);
     prof_mark(ctx, 2);
     if (ctx->pre_acc) { auto f = ctx->pre_acc; ctx->pre_acc = nullptr; int rc_ = f(ctx->pre_acc_arg); if (rc_) return rc_; }
     // 3. accumulate
