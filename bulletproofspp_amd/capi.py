@@ -188,6 +188,7 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_rp_witness_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.bppp_test_points_from_seed_chunked.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, sz, vp, C.POINTER(C.c_uint64)]
     lib.bppp_test_seed_lift_digests.argtypes = [vp, C.c_char_p, sz, vp, vp, vp]
+    lib.bppp_test_rp_decode_device.argtypes = [vp, sz, C.c_char_p, C.c_char_p, vp, vp, vp, vp, vp, vp]
     return lib
 
 

@@ -31,84 +31,14 @@
 #include "rpsetup.hpp"
 #include "sha256.hip.h"
 #include "rp_internal.hpp"
+#include "rpdecode.hip.h"
 #include "brp.hpp"
 #include "rphash.hip.h"
 #include "fr26.hip.h"
 
 namespace bppp {
 
-// ------------------------------------------------------------------------------------------------ decode
-// Binary (Prime p) get (Encoding.hs:76-80): limb i = big-endian 64-bit word at bytes 8i..8i+7, least-significant limb first;
-// toP reduces (one conditional subtraction: the value is < 2^256 < 2m)
-template <int MOD> BPPP_DI fe load_field_be(const uint8_t *p) {
-  fe v;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const uint8_t *q = p + 8 * i;
-    v.v[2 * i + 1] = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3];
-    v.v[2 * i] = ((uint32_t)q[4] << 24) | ((uint32_t)q[5] << 16) | ((uint32_t)q[6] << 8) | q[7];
-  }
-  fe t;
-  uint32_t br = raw_sub(t, v, modulus<MOD>());
-#pragma unroll
-  for (int i = 0; i < 8; i++) v.v[i] = br ? v.v[i] : t.v[i];
-  return v;
-}
-
-// Point t of a proof IN TRANSCRIPT ORDER (newest first, the order shaOracle's final call sees, src/ZKP.hs:98):
-//   t < 2k            the argument's responses, last round first  = bpComs of the proof file (RangeProof.hs:60-66)
-//   2k <= t < 2k + 4  blCom, rCom, dmCom, mCom  (Binary: blCom, dCom) = rpComs of the proof file
-//   else              the input commitments                         = the commitments file
-// Output: responses to resp[b][t], the rest to init[b][...] in the order blCom : rCom : dmCom : mCom : nComs.
-__global__ void __launch_bounds__(64) k_rp_decode_points(RpDims D, uint32_t batch, const uint8_t *__restrict__ coms, const uint8_t *__restrict__ proofs,
-                                                         uint32_t *__restrict__ init_pts, uint32_t *__restrict__ resp_pts, uint32_t *__restrict__ bad,
-                                                         uint32_t *__restrict__ any_bad) {   // bad[b] per proof of this launch, *any_bad for the call
-  const uint32_t npts = rp_npts(D);
-  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= (uint64_t)batch * npts) return;
-  const uint32_t b = (uint32_t)(g / npts), t = (uint32_t)(g % npts);
-  const uint8_t *signs, *xs;
-  uint32_t idx;
-  const uint32_t nproof_pts = D.nrp + 2 * D.k;
-  if (t < 2 * D.k + D.nrp) {
-    const uint8_t *pf = proofs + (size_t)b * D.proof_bytes + (size_t)(D.fn + D.fl) * 32;
-    signs = pf; xs = pf + (nproof_pts + 7) / 8;
-    idx = t < 2 * D.k ? D.nrp + t : t - 2 * D.k;
-  } else {
-    const uint8_t *cf = coms + (size_t)b * D.coms_bytes;
-    signs = cf; xs = cf + (D.nr + 7) / 8;
-    idx = t - 2 * D.k - D.nrp;
-  }
-  const bool want_big = (signs[idx >> 3] >> (idx & 7)) & 1;
-  const fe xe = load_field_be<0>(xs + (size_t)idx * 32);
-  const fq x = fq_from_fe(xe);
-  fq seven = fq_zero(); seven.n[0] = 7;
-  const fq rhs = fq_add(fq_mul(fq_sqr(x), x), seven);         // magnitude 2
-  fq y = fq_sqrt_candidate(rhs);
-  const bool ok = fq_normalizes_to_zero(fq_sub<2>(fq_sqr(y), rhs));
-  y = fq_normalize(y);
-  // fromXWithSign (Encoding.hs:97-103): keep the root whose (y > p - y) equals the sign bit
-  const fe ye = fq_to_fe(y), yn = fe_neg<0>(ye);
-  fe d;
-  const bool y_big = raw_sub(d, yn, ye) != 0;                  // -y < y
-  aff r; r.x = x; r.y = (y_big != want_big) ? fq_from_fe(yn) : y;
-  if (!ok) { r = aff_inf(); atomicOr(bad + b, 1u); atomicOr(any_bad, 1u); }
-  uint32_t *out = t < 2 * D.k ? resp_pts + ((size_t)b * 2 * D.k + t) * 16
-                              : init_pts + ((size_t)b * (D.nrp + D.nr) + (t - 2 * D.k)) * 16;
-  aff_store(out, r);
-}
-
-// final witness scalars: norm part then linear part (encodeProof', RangeProof.hs:60-66)
-__global__ void __launch_bounds__(64) k_rp_decode_scalars(RpDims D, uint32_t batch, const uint8_t *__restrict__ proofs, uint32_t *__restrict__ wit_norm,
-                                                          uint32_t *__restrict__ wit_lin) {
-  const uint32_t ns = D.fn + D.fl;
-  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= (uint64_t)batch * ns) return;
-  const uint32_t b = (uint32_t)(g / ns), i = (uint32_t)(g % ns);
-  const fe v = load_field_be<1>(proofs + (size_t)b * D.proof_bytes + (size_t)i * 32);
-  if (i < D.fn) fe_store(wit_norm + ((size_t)b * D.fn + i) * 8, v);
-  else fe_store(wit_lin + ((size_t)b * D.fl + (i - D.fn)) * 8, v);
-}
+// ------------------------------------------------------------------------------------------------ decode: csrc/rpdecode.hip.h
 
 // ------------------------------------------------------------------------------------------------ transcript text (helpers: rphash.hip.h)
 BPPP_DI const uint32_t *rp_point_ptr(const RpDims &D, const uint32_t *init_pts, const uint32_t *resp_pts, uint32_t b, uint32_t t) {
@@ -904,9 +834,7 @@ int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const Rp
         BPPP_HIP(ctx, hipMemcpyAsync((void *)dp, hp + b0 * (size_t)D.proof_bytes, nb * (size_t)D.proof_bytes, hipMemcpyHostToDevice, up));
         if (nslices > 1) { BPPP_HIP(ctx, hipEventRecord(rp->slice_ev[sl], up)); BPPP_HIP(ctx, hipStreamWaitEvent(st, rp->slice_ev[sl], 0)); }
       }
-      const uint64_t np = (uint64_t)nb * npts, ns = (uint64_t)nb * (D.fn + D.fl);
-      k_rp_decode_points<<<dim3((unsigned)((np + 63) / 64)), dim3(64), 0, st>>>(D, (uint32_t)nb, dc, dp, init_pts + b0 * ninit * 16, resp_pts + b0 * 2 * k * 16, bad + b0, bad + B);
-      if (ns) k_rp_decode_scalars<<<dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, st>>>(D, (uint32_t)nb, dp, wit_norm + b0 * D.fn * 8, wit_lin + b0 * D.fl * 8);
+      rp_decode_launch(D, nb, dc, dp, init_pts + b0 * ninit * 16, resp_pts + b0 * 2 * k * 16, wit_norm + b0 * D.fn * 8, wit_lin + b0 * D.fl * 8, bad + b0, bad + B, st);
     }
   }
   BPPP_HIP(ctx, hipMemcpyAsync(rp->hflag, bad + B, 4, hipMemcpyDeviceToHost, st));     // pinned; read after the MSM has drained the stream

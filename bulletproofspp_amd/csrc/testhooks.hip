@@ -8,6 +8,7 @@
 #include "fr26.hip.h"
 #include "rp_internal.hpp"
 #include "rpwitness.hip.h"
+#include "rpdecode.hip.h"
 #include "seedpoints.hip.h"
 
 namespace bppp {
@@ -290,6 +291,34 @@ extern "C" int bppp_test_rp_witness_device(bppp_rp *rp, size_t batch, const void
   if (!rc && binary) for (size_t i = 0; i < bits.size(); i++) dig[i] = bits[i];
   hipFree(d);
   return rc;
+}
+
+extern "C" int bppp_test_rp_decode_device(bppp_rp *rp, size_t batch, const uint8_t *coms, const uint8_t *proofs, uint64_t *init_pts, uint64_t *resp_pts, uint64_t *wit_norm,
+                                          uint64_t *wit_lin, uint32_t *bad, uint32_t *any_bad) {
+  if (!rp || !batch || batch >= (1u << 20) || !coms || !proofs || !init_pts || !resp_pts || !wit_norm || !wit_lin || !bad || !any_bad) return BPPP_ERR_ARG;
+  bppp_ctx *ctx = rp->ctx;
+  hipSetDevice(ctx->device);
+  hipStream_t st = ctx->stream;
+  const RpDims D = rp->D;
+  const size_t B = batch, b_coms = B * D.coms_bytes, b_prf = B * D.proof_bytes, b_init = B * (D.nrp + D.nr) * 64, b_resp = B * 2 * D.k * 64, b_wn = B * D.fn * 32,
+               b_wl = B * D.fl * 32, b_bad = (B + 1) * 4;
+  auto up256 = [](size_t n) { return (n + 255) & ~(size_t)255; };
+  uint8_t *d = nullptr;                      // coms | proofs | init | resp | wit_norm | wit_lin | bad, any_bad  (each 256-byte aligned)
+  BPPP_HIP(ctx, hipMalloc(&d, up256(b_coms) + up256(b_prf) + up256(b_init) + up256(b_resp) + up256(b_wn) + up256(b_wl) + up256(b_bad) + 256));
+  uint8_t *d_coms = d, *d_prf = d_coms + up256(b_coms), *d_init = d_prf + up256(b_prf), *d_resp = d_init + up256(b_init), *d_wn = d_resp + up256(b_resp),
+          *d_wl = d_wn + up256(b_wn), *d_bad = d_wl + up256(b_wl);
+  bool ok = hipMemcpyAsync(d_coms, coms, b_coms, hipMemcpyHostToDevice, st) == hipSuccess && hipMemcpyAsync(d_prf, proofs, b_prf, hipMemcpyHostToDevice, st) == hipSuccess &&
+            hipMemsetAsync(d_init, 0xA5, (size_t)(d_bad - d_init), st) == hipSuccess && hipMemsetAsync(d_bad, 0, b_bad, st) == hipSuccess;
+  if (ok) {
+    rp_decode_launch(D, B, d_coms, d_prf, (uint32_t *)d_init, (uint32_t *)d_resp, (uint32_t *)d_wn, (uint32_t *)d_wl, (uint32_t *)d_bad, (uint32_t *)d_bad + B, st);
+    ok = hipGetLastError() == hipSuccess;
+  }
+  auto down = [&](void *h, const void *dv, size_t n) { return !n || hipMemcpyAsync(h, dv, n, hipMemcpyDeviceToHost, st) == hipSuccess; };
+  ok = ok && down(init_pts, d_init, b_init) && down(resp_pts, d_resp, b_resp) && down(wit_norm, d_wn, b_wn) && down(wit_lin, d_wl, b_wl) && down(bad, d_bad, B * 4) &&
+       down(any_bad, d_bad + B * 4, 4);
+  if (hipStreamSynchronize(st) != hipSuccess) ok = false;
+  hipFree(d);
+  return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_rp_decode_device: kernel or copy failed");
 }
 
 extern "C" int bppp_test_points_from_seed_chunked(bppp_ctx *ctx, const uint8_t *seed, size_t seed_len, uint64_t first_candidate, size_t count, size_t chunk,

@@ -644,7 +644,9 @@ int bppp_rp_prove_mixed(const bppp_rp_prove_group *groups, size_t ngroups);
  * For each candidate x (n x 4 uint64 in HBM) writes the affine point (x, y) with y the EVEN root of
  * x^3 + 7, or the infinity encoding when x^3 + 7 is a non-residue or x >= p.  (Which root
  * galois-field's `sr` returns cannot be confirmed offline — SURVEY.md 8c; even-y is this build's
- * documented choice.)  Used to make synthetic bases on the GPU. */
+ * documented choice.)  An x >= p is NOT reduced: it is "not a point" here, while the decoder of proof and
+ * commitments files (Binary (Prime p), src/Encoding.hs:76-80) and the seed stream below reduce mod p first.
+ * Used to make synthetic bases on the GPU. */
 int bppp_lift_x_device(bppp_ctx *ctx, const void *d_x, size_t n, void *d_points_xy);
 
 /* ---- a setup's basis from its seed: getPoints (app/Main.hs:68-72), the stream h : g : hs ++ gs the CLI hands to setup (:260) -------

@@ -62,6 +62,19 @@ int bppp_test_points_from_seed_chunked(bppp_ctx *ctx, const uint8_t *seed, size_
 /* The decode-and-lift step of the candidate kernel on caller-given digests ([n][32] bytes as SHA-256 writes them) — a digest that
  * decodes to p or more is out of any hash's reach: x [n][4] = decode mod p, is_point [n], points_xy [n][8] (zero where not a point). */
 int bppp_test_seed_lift_digests(bppp_ctx *ctx, const uint8_t *digests, size_t n, uint64_t *x, uint32_t *is_point, uint64_t *points_xy);
+/* The decode stage of the verifier alone (csrc/rpdecode.hip.h: k_rp_decode_points + k_rp_decode_scalars through rp_decode_launch, the launch
+ * bppp_rp_verify_batch* makes per upload slice) on `batch` host files of the handle's coms_bytes / proof_bytes each — any bytes of
+ * that length, they need not be proofs.  Everything it wrote, copied to the host (k = rounds, nrp = 4 range-proof commitments, 2 on a
+ * binary handle; points as 8 words x | y, all zero = "not a point"; scalars as 4 words, canonical):
+ *   resp_pts [batch][2k][8]          resp[b][t] = point nrp + t of proof file b (the argument's responses, last round first)
+ *   init_pts [batch][nrp + nranges][8]   init[b] = the nrp range-proof commitments (points 0 .. nrp-1 of proof file b), then the nranges
+ *                                    input commitments (commitments file b)
+ *   wit_norm [batch][final_norm][4], wit_lin [batch][final_lin][4]   the proof file's scalars, norm part then linear part
+ *   bad [batch]                      non-zero iff some x of proof b is not on the curve;  any_bad [1]: their OR
+ * bad and any_bad are zeroed before the launch as the verifier does; the point and scalar arrays are pre-filled with 0xA5 bytes, so a
+ * slot the kernels did not write shows. */
+int bppp_test_rp_decode_device(bppp_rp *rp, size_t batch, const uint8_t *coms, const uint8_t *proofs, uint64_t *init_pts, uint64_t *resp_pts, uint64_t *wit_norm,
+                               uint64_t *wit_lin, uint32_t *bad, uint32_t *any_bad);
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
