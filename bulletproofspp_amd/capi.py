@@ -183,6 +183,7 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_last_mixed_msm_terms.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.bppp_test_last_acc_kernel.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_last_sort_ranges.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.bppp_test_last_acc_sized.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_rp_last_verify_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.bppp_test_rp_set_each_chunk.argtypes = [vp, sz]
     lib.bppp_test_rp_witness_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]

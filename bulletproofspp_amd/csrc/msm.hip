@@ -6,7 +6,7 @@
 //
 //   1. k_digits      reduceScalar's sign fold (Commitment.hs:276-279, :366) + signed c-bit window
 //                    recode (the format of recode.hip.h); coalesced 32-B scalar loads, u16 digits out.
-//   2. k_hist / k_scan* / k_scatter
+//   2. k_hist / k_count_tiles / k_scan_apply / k_scatter, k_scatter_ranges
 //                    counting sort of (window, |digit|) keys: the bucket histogram and cursors are
 //                    staged in LDS (<= 128 KiB per workgroup), so HBM sees only coalesced streams.
 //   3. k_acc_points / k_merge / k_merge_heavy
@@ -15,7 +15,13 @@
 //                    bucket offsets start[], it is not stored), sums runs of one bucket in an XYZZ register
 //                    accumulator with mixed adds and stores complete buckets; a bucket that
 //                    straddles lanes is finished by k_merge (one lane per bucket) or, when it spans
-//                    many lanes (skewed scalars), by one wavefront in k_merge_heavy.
+//                    many lanes (skewed scalars), by one wavefront in k_merge_heavy.  Batches, registered bases and one
+//                    MSM with windows under 16 bits.
+//   3'. k_order / k_acc_points_sized / k_merge_heavy<true>
+//                    one MSM over arbitrary points with 16-bit windows (MsmTune::acc_sized): a lane sums one whole
+//                    bucket (or a piece of <= 128 entries of a larger one), the buckets dispatched in descending order
+//                    of size so that the lanes of a wavefront run equally long: no boundary logic in the loop, no
+//                    partial sums unless the scalars are skewed.
 //   4. k_reduce_marg / k_reduce_tail_quad (k_reduce_tail: the one-lane form, MsmTune::tail_scalar)
 //                    sum_m m*B_m per window by MARGINAL SUMS (m = LO*hi + lo: plain row and column sums, every lane busy,
 //                    then two short weighted sums); k_reduce1/2 (per-lane running sums + wavefront suffix scans) for windows
@@ -119,10 +125,17 @@ __global__ void __launch_bounds__(256) k_count_tiles(uint32_t *__restrict__ bloc
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(tile_sums + blockIdx.x / (SCAN_TILE / 256), ws[0] + ws[1] + ws[2] + ws[3]);
 }
+// An ITEM of the sized accumulation (section 3'): a bucket of at most ACC_CAP entries, or a piece of ACC_CAP entries (the last one: the rest) of
+// a larger one.  size_hist (the sized route only, else null; zero at launch: k_digits) counts the items by size: the tile's histogram in LDS,
+// then one global atomic per non-empty bin.  Bin size - 1 is the word (size - 1) * ACC_LINE: a bin has a 128-byte line to itself, so that the
+// atomics of different bins do not queue on one line.
+static constexpr uint32_t ACC_CAP = 128, ACC_LINE = 32;
 __global__ void __launch_bounds__(256) k_scan_apply(const uint32_t *__restrict__ in, uint64_t n, const uint32_t *__restrict__ tile_sums,
-                                                    uint32_t *__restrict__ out) {
+                                                    uint32_t *__restrict__ out, uint32_t *__restrict__ size_hist) {
   // the tile's offset, then a block-level exclusive scan of the tile (16 per thread); the last lane of the last tile writes the total out[n]
   __shared__ uint32_t wsum[4], wpre[4];
+  __shared__ uint32_t lh[ACC_CAP];
+  if (size_hist && threadIdx.x < ACC_CAP) lh[threadIdx.x] = 0;
   uint32_t pre = 0;
   for (uint32_t i = threadIdx.x; i < blockIdx.x; i += 256) pre += tile_sums[i];
   for (int d = 32; d >= 1; d >>= 1) pre += __shfl_down(pre, d, 64);
@@ -135,6 +148,15 @@ __global__ void __launch_bounds__(256) k_scan_apply(const uint32_t *__restrict__
   for (int d = 1; d < 64; d <<= 1) { uint32_t t = __shfl_up(inc, d, 64); if ((int)(threadIdx.x & 63) >= d) inc += t; }
   if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = inc;
   __syncthreads();
+  if (size_hist) {
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+      if (v[k] >= ACC_CAP) atomicAdd(&lh[ACC_CAP - 1], v[k] / ACC_CAP);
+      if (v[k] % ACC_CAP) atomicAdd(&lh[v[k] % ACC_CAP - 1], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < ACC_CAP && lh[threadIdx.x]) atomicAdd(size_hist + threadIdx.x * ACC_LINE, lh[threadIdx.x]);
+  }
   uint32_t woff = 0;
   for (int w = 0; w < (int)(threadIdx.x >> 6); w++) woff += wsum[w];
   uint32_t run = wpre[0] + wpre[1] + wpre[2] + wpre[3] + woff + inc - s;
@@ -322,20 +344,29 @@ __global__ void __launch_bounds__(256) k_merge(const uint32_t *__restrict__ star
 // wavefront that arrives last adds them up.  Launched as 2048 single-wavefront workgroups, and the shape matters beyond this kernel:
 // with 512 workgroups of four wavefronts in its place the k_reduce_marg launch that follows (69 632 single-wavefront workgroups at 2^20
 // terms) ran 0.216 ms instead of 0.158 (measured both ways, same data).
+// SIZED (the join of k_acc_points_sized's pieces, section 3'): the partials of bucket fb are its ceil(count / ACC_CAP) piece sums, consecutive in
+// rec_pt from slot piece_base[fb] on.
+template <bool SIZED>
 __global__ void __launch_bounds__(64) k_merge_heavy(const uint32_t *__restrict__ start, const uint32_t *__restrict__ count, int L,
-                                                     const uint32_t *__restrict__ rec_pt, uint32_t *__restrict__ buckets,
+                                                     const uint32_t *__restrict__ rec_pt, const uint32_t *__restrict__ piece_base, uint32_t *__restrict__ buckets,
                                                      const uint2 *__restrict__ heavy_items, const uint32_t *__restrict__ heavy_slot, uint4 *heavy_buckets,
                                                      const uint32_t *__restrict__ heavy_count, uint32_t *chunk_sums) {
   const uint32_t nitems = heavy_count[0], lane = threadIdx.x;
   for (uint32_t h = blockIdx.x; h < nitems; h += gridDim.x) {
     uint2 it = heavy_items[h];
-    uint32_t fb = it.x, s = start[fb], cnt = count[fb];
-    uint64_t g0 = s / (uint32_t)L, g1 = (uint64_t)(s + cnt - 1) / (uint32_t)L;
-    uint32_t np = (uint32_t)(g1 - g0 + 1);
+    uint32_t fb = it.x, cnt = count[fb], np;
+    uint64_t g0 = 0;
+    const uint32_t *pieces = nullptr;
+    if (SIZED) { np = (cnt + ACC_CAP - 1) / ACC_CAP; pieces = rec_pt + (size_t)piece_base[fb] * XYZZ_WORDS; }
+    else {
+      const uint32_t s = start[fb];
+      g0 = s / (uint32_t)L;
+      np = (uint32_t)((uint64_t)(s + cnt - 1) / (uint32_t)L - g0 + 1);
+    }
     uint32_t t0 = it.y * HEAVY_CHUNK, t1 = min(np, t0 + HEAVY_CHUNK);
     xyzz acc = xyzz_inf();
     for (uint32_t t = t0 + lane; t < t1; t += 64) {
-      xyzz p = xyzz_load(partial_ptr(rec_pt, g0, t));
+      xyzz p = xyzz_load(SIZED ? pieces + (size_t)t * XYZZ_WORDS : partial_ptr(rec_pt, g0, t));
       xyzz_add(acc, p);
     }
     for (int d = 32; d >= 1; d >>= 1) {
@@ -372,6 +403,87 @@ __global__ void __launch_bounds__(64) k_merge_heavy(const uint32_t *__restrict__
     }
     if (lane == 0) xyzz_store(buckets + (size_t)fb * XYZZ_WORDS, acc);
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// 3'. accumulation by whole buckets, ordered by size (one MSM over arbitrary points; MsmTune::acc_sized)
+// The slices of section 3 cross a bucket boundary in nearly every iteration of some lane of a wavefront (store, clear, next bucket: executed by
+// all under divergence), spend a whole addition slot on the copy that starts each run and leave half of the buckets in two partial sums.
+// Here a lane takes one ITEM (k_count_tiles) and the items are dispatched in descending order of size, so the lanes of a wavefront run the
+// same number of additions: the loop has no boundary, the first entry is loaded into the accumulator (one addition less per item), and a
+// bucket that is one item — every bucket unless the scalars are skewed — is stored once and finished.
+//
+// k_order, one workgroup per tile of SCAN_TILE buckets (16 per lane): every workgroup derives the class offsets (largest size first) from the
+// size histogram, counts its own items per class in LDS, draws its share of each class with one global atomic (cursors, laid out like the
+// histogram, zero at launch: k_digits) and writes items[] = (bucket, piece).  The order inside a class is arbitrary: the sums are group
+// elements.  It also marks the empty buckets (the bucket array is not cleared between calls) and lists the buckets of several pieces for
+// k_merge_heavy<true>, which adds their piece sums: the pieces' slots (piece_base[bucket], drawn from ctr[2]) and the (bucket, chunk) items
+// of that kernel.  ctr[3]: the number of items.
+__global__ void __launch_bounds__(256) k_order(const uint32_t *__restrict__ count, uint64_t FB, const uint32_t *__restrict__ size_hist,
+                                               uint32_t *__restrict__ cursors, uint2 *__restrict__ items, uint32_t *__restrict__ piece_base,
+                                               uint32_t *__restrict__ buckets, uint2 *__restrict__ heavy_items, uint32_t *__restrict__ heavy_slot,
+                                               uint4 *__restrict__ heavy_buckets, uint32_t *__restrict__ ctr) {
+  __shared__ uint32_t off[ACC_CAP], lc[ACC_CAP], lb[ACC_CAP];
+  const uint32_t t = threadIdx.x;
+  if (t < ACC_CAP) { lc[t] = 0; lb[t] = size_hist[t * ACC_LINE]; }
+  __syncthreads();
+  if (t < ACC_CAP) {
+    uint32_t s = 0;
+    for (uint32_t u = t + 1; u < ACC_CAP; u++) s += lb[u];
+    off[t] = s;                                               // items of a larger size
+    if (t == 0 && blockIdx.x == 0) ctr[3] = s + lb[0];
+  }
+  const uint64_t fb0 = (uint64_t)blockIdx.x * SCAN_TILE + t;
+  uint32_t cnt[16], rr[16], rf[16];                           // the ranks of the bucket's short item (bin rem - 1) and of its full pieces (the last bin)
+#pragma unroll
+  for (int k = 0; k < 16; k++) {
+    const uint64_t fb = fb0 + (uint64_t)k * 256;
+    cnt[k] = fb < FB ? count[fb] : 0u;
+    rr[k] = cnt[k] % ACC_CAP ? atomicAdd(&lc[cnt[k] % ACC_CAP - 1], 1u) : 0u;
+    rf[k] = cnt[k] >= ACC_CAP ? atomicAdd(&lc[ACC_CAP - 1], cnt[k] / ACC_CAP) : 0u;
+  }
+  __syncthreads();                                            // lc complete, lb read by all
+  if (t < ACC_CAP) lb[t] = lc[t] ? atomicAdd(cursors + t * ACC_LINE, lc[t]) : 0u;
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 16; k++) {
+    const uint64_t fb = fb0 + (uint64_t)k * 256;
+    if (fb >= FB) continue;
+    const uint32_t full = cnt[k] / ACC_CAP, rem = cnt[k] % ACC_CAP;
+    if (!cnt[k]) { xyzz_store(buckets + fb * XYZZ_WORDS, xyzz_inf()); continue; }
+    for (uint32_t j = 0; j < full; j++) items[off[ACC_CAP - 1] + lb[ACC_CAP - 1] + rf[k] + j] = make_uint2((uint32_t)fb, j);
+    if (rem) items[off[rem - 1] + lb[rem - 1] + rr[k]] = make_uint2((uint32_t)fb, full);
+    if (cnt[k] <= ACC_CAP) continue;
+    const uint32_t np = full + (rem ? 1u : 0u), nch = (np + HEAVY_CHUNK - 1) / HEAVY_CHUNK;
+    piece_base[fb] = atomicAdd(&ctr[2], np);
+    uint32_t base = atomicAdd(&ctr[0], nch), hb = 0;
+    if (nch > 1) { hb = atomicAdd(&ctr[1], 1u); heavy_buckets[hb] = make_uint4((uint32_t)fb, base, nch, 0u); }   // .w: the chunks' ticket
+    for (uint32_t j = 0; j < nch; j++) { heavy_items[base + j] = make_uint2((uint32_t)fb, j); heavy_slot[base + j] = hb; }
+  }
+}
+
+// one item per lane: the same 4-byte entries, sign fold and complete mixed addition as k_acc_points.  A lane whose item is shorter than the
+// wavefront's longest leaves the loop early (execution mask); a whole bucket goes to `buckets`, a piece to its slot of `pieces`.
+__global__ void __launch_bounds__(256) k_acc_points_sized(const uint32_t *__restrict__ sorted, const uint32_t *__restrict__ start,
+                                                          const uint32_t *__restrict__ count, const uint2 *__restrict__ items,
+                                                          const uint32_t *__restrict__ ctr, const uint32_t *__restrict__ piece_base,
+                                                          const uint32_t *__restrict__ points, uint32_t *__restrict__ buckets,
+                                                          uint32_t *__restrict__ pieces) {
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= ctr[3]) return;
+  const uint2 it = items[g];
+  const uint32_t fb = it.x, cnt = count[fb], first = it.y * ACC_CAP, len = min(ACC_CAP, cnt - first);
+  const uint32_t *ent = sorted + start[fb] + first;
+  uint32_t e = ent[0];
+  xyzz acc = xyzz_from_aff(aff_cneg(aff_load(points + (size_t)(e & 0x7FFFFFFFu) * 16), (e >> 31) & 1u));
+  e = len > 1 ? ent[1] : 0u;
+  for (uint32_t k = 1; k < len; k++) {
+    const uint32_t e_next = (k + 1 < len) ? ent[k + 1] : 0u;
+    aff P = aff_cneg(aff_load(points + (size_t)(e & 0x7FFFFFFFu) * 16), (e >> 31) & 1u);
+    xyzz_madd(acc, P);
+    e = e_next;
+  }
+  xyzz_store(cnt > ACC_CAP ? pieces + ((size_t)piece_base[fb] + it.y) * XYZZ_WORDS : buckets + (size_t)fb * XYZZ_WORDS, acc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -874,6 +986,7 @@ struct MsmPlan {
   bool marg; MargGeom mg;      // marginal-sum reduction (M >= 256, not the grouped path)
   int ntiles;
   int Q;                       // bucket ranges per window of the ranged scatter (k_scatter_ranges); 0 = k_scatter
+  bool sized;                  // accumulate whole buckets in order of size (k_order, k_acc_points_sized) instead of slices of L entries
 };
 
 static MsmPlan make_plan(size_t n, size_t batch, int c, bool flat, const MsmTune &tune) {
@@ -972,6 +1085,10 @@ static MsmPlan make_plan(size_t n, size_t batch, int c, bool flat, const MsmTune
   if (tune.lacc >= 1 && tune.lacc <= 4096) p.L = tune.lacc;
   p.G = (p.total_max + p.L - 1) / p.L; if (!p.G) p.G = 1;
   p.ntiles = (int)((p.FB + SCAN_TILE - 1) / SCAN_TILE);
+  // sized accumulation: one MSM over arbitrary points.  The default is by measurement ("whole buckets by size"): at 2^20 terms
+  // and c = 16 the accumulation stage falls 1.113 -> 1.010 ms; at 2^16 and c = 13 it has 86 K items of 16 entries, a third of the chip's wave
+  // slots on chains twice as long as the slices', and rises 0.186 -> 0.311 ms
+  p.sized = batch == 1 && !flat && !tune.acc_lds && (tune.acc_sized > 0 || (tune.acc_sized < 0 && c == 16));
   return p;
 }
 
@@ -1061,16 +1178,25 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
     uint32_t *tiles = cv.take<uint32_t>(p.ntiles + 1);
     uint32_t *sorted = cv.take<uint32_t>(p.total_max + 4);
     uint32_t *buckets = cv.take<uint32_t>((size_t)p.FB * XYZZ_WORDS);
-    uint32_t *rec_pt = cv.take<uint32_t>((size_t)p.G * 2 * XYZZ_WORDS);
+    // sized: a bucket of several pieces has more than ACC_CAP entries and ceil(count / ACC_CAP) <= 2 count / ACC_CAP pieces, so there are at
+    // most total / ACC_CAP such buckets, 2 total / ACC_CAP piece sums (they take rec_pt's place) and total / ACC_CAP + 2 total / (ACC_CAP *
+    // HEAVY_CHUNK) (bucket, chunk) items; every non-empty bucket adds at most one item to the total / ACC_CAP full pieces
+    const size_t tcap = (size_t)(p.total_max / ACC_CAP);
+    const size_t items_max = std::min<size_t>((size_t)p.total_max, (size_t)p.FB + tcap);
+    uint32_t *rec_pt = cv.take<uint32_t>((p.sized ? 2 * tcap + 2 : (size_t)p.G * 2) * XYZZ_WORDS);
+    uint2 *items = cv.take<uint2>(p.sized ? items_max + 1 : 0);
+    uint32_t *piece_base = cv.take<uint32_t>(p.sized ? (size_t)p.FB : 0);
     // heavy buckets span > 9 lanes: at most G/9 of them, and at most G/256 + G/9 (bucket, chunk) items
-    size_t hmax = (size_t)(p.G / 8 + 2);
+    size_t hmax = p.sized ? tcap + 2 * tcap / HEAVY_CHUNK + 4 : (size_t)(p.G / 8 + 2);
     uint2 *heavy_items = cv.take<uint2>(hmax);
     uint4 *heavy_buckets = cv.take<uint4>(hmax);
     uint32_t *chunk_sums = cv.take<uint32_t>(hmax * XYZZ_WORDS);
-    // counters and tickets, zeroed by k_digits (with the scan's tile sums): [0], [1] heavy items / buckets, [4..] k_reduce_tail_quad's tickets
-    const size_t nzero = 4 + (p.marg ? 2 * (size_t)p.NS : 0);
+    // counters and tickets, zeroed by k_digits (with the scan's tile sums): [0], [1] heavy items / buckets, [2], [3] the sized route's piece
+    // slots / items, [4..] k_reduce_tail_quad's tickets, then the sized route's size histogram and class cursors
+    const size_t ntail = p.marg ? 2 * (size_t)p.NS : 0, nzero = 4 + ntail + (p.sized ? 2 * ACC_CAP * ACC_LINE : 0);
     uint32_t *heavy_count = cv.take<uint32_t>(nzero);
     uint32_t *tail_cnt = heavy_count + 4;
+    uint32_t *size_hist = p.sized ? tail_cnt + ntail : nullptr, *cursors = p.sized ? size_hist + ACC_CAP * ACC_LINE : nullptr;
     uint32_t *tail_part = cv.take<uint32_t>(p.marg && p.mg.quad ? (size_t)p.NS * 2 * 16 * 2 * XYZZ_WORDS : 0);
     uint32_t *red = cv.take<uint32_t>(p.marg ? (size_t)p.NS * (p.mg.HI + p.mg.LO) * XYZZ_WORDS : (size_t)p.NS * p.WPW * 2 * XYZZ_WORDS);
     uint32_t *winsum = cv.take<uint32_t>((size_t)p.NS * 2 * XYZZ_WORDS);
@@ -1096,7 +1222,7 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
     k_hist<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(dig, (uint32_t)n, stride, c, p.CH, blockhist);
     // flat: the (window, chunk) histograms of an instance are W * CH chunks of ONE bucket set (same memory layout)
     k_count_tiles<<<dim3((unsigned)((p.FB + 255) / 256)), dim3(256), 0, st>>>(blockhist, p.M, p.flat ? p.W * p.CH : p.CH, p.FB, count, tiles);
-    k_scan_apply<<<dim3(p.ntiles), dim3(256), 0, st>>>(count, p.FB, tiles, start);
+    k_scan_apply<<<dim3(p.ntiles), dim3(256), 0, st>>>(count, p.FB, tiles, start, size_hist);
     ctx->last_sort_ranges = p.Q;
     if (p.Q) {
       const uint32_t U = (uint32_t)p.W * p.Q;                // units (window, range); 8 slots x ceil(U / 8) units x CH chunks
@@ -1106,14 +1232,27 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
       k_scatter<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(dig, negmask, (uint32_t)n, stride, c, p.CH, p.W, blockhist, start, sorted,
                                                                                p.flat ? (uint32_t)table_stride : 0u);
     prof_mark(ctx, 2);
-    if (ctx->pre_acc) { auto f = ctx->pre_acc; ctx->pre_acc = nullptr; int rc_ = f(ctx->pre_acc_arg); if (rc_) return rc_; }
     // 3. accumulate
     ctx->last_acc_lds = ctx->tune.acc_lds ? 1 : 0;
-    (ctx->tune.acc_lds ? k_acc_points_lds : k_acc_points)<<<dim3((unsigned)((p.G + 255) / 256)), dim3(256), 0, st>>>(
-        sorted, start, (uint32_t)p.FB, (const uint32_t *)d_points, (uint32_t)n, (uint32_t)(p.Wc * p.M), shared_points, p.L, p.G, buckets, rec_pt);
-    prof_mark(ctx, 3);
-    k_merge<<<dim3((unsigned)((p.FB + 255) / 256)), dim3(256), 0, st>>>(start, count, p.FB, p.L, rec_pt, buckets, heavy_items, heavy_slot, heavy_buckets, heavy_count);
-    k_merge_heavy<<<dim3(2048), dim3(64), 0, st>>>(start, count, p.L, rec_pt, buckets, heavy_items, heavy_slot, heavy_buckets, heavy_count, chunk_sums);
+    ctx->last_acc_sized = p.sized ? 1 : 0;
+    // the ordering pass has to precede the accumulation, so its time is booked with acc_points; acc_points + acc_records is the accumulation
+    // on either route
+    if (p.sized)
+      k_order<<<dim3(p.ntiles), dim3(256), 0, st>>>(count, p.FB, size_hist, cursors, items, piece_base, buckets, heavy_items, heavy_slot,
+                                                                          heavy_buckets, heavy_count);
+    if (ctx->pre_acc) { auto f = ctx->pre_acc; ctx->pre_acc = nullptr; int rc_ = f(ctx->pre_acc_arg); if (rc_) return rc_; }
+    if (p.sized) {
+      k_acc_points_sized<<<dim3((unsigned)((items_max + 255) / 256)), dim3(256), 0, st>>>(sorted, start, count, items, heavy_count, piece_base,
+                                                                                          (const uint32_t *)d_points, buckets, rec_pt);
+      prof_mark(ctx, 3);
+      k_merge_heavy<true><<<dim3(2048), dim3(64), 0, st>>>(start, count, 0, rec_pt, piece_base, buckets, heavy_items, heavy_slot, heavy_buckets, heavy_count, chunk_sums);
+    } else {
+      (ctx->tune.acc_lds ? k_acc_points_lds : k_acc_points)<<<dim3((unsigned)((p.G + 255) / 256)), dim3(256), 0, st>>>(
+          sorted, start, (uint32_t)p.FB, (const uint32_t *)d_points, (uint32_t)n, (uint32_t)(p.Wc * p.M), shared_points, p.L, p.G, buckets, rec_pt);
+      prof_mark(ctx, 3);
+      k_merge<<<dim3((unsigned)((p.FB + 255) / 256)), dim3(256), 0, st>>>(start, count, p.FB, p.L, rec_pt, buckets, heavy_items, heavy_slot, heavy_buckets, heavy_count);
+      k_merge_heavy<false><<<dim3(2048), dim3(64), 0, st>>>(start, count, p.L, rec_pt, nullptr, buckets, heavy_items, heavy_slot, heavy_buckets, heavy_count, chunk_sums);
+    }
     prof_mark(ctx, 4);
     // 4. bucket reduce
     if (p.RG) {

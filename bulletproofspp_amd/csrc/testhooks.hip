@@ -252,6 +252,12 @@ extern "C" int bppp_test_last_sort_ranges(bppp_ctx *ctx, int *q) {
   return BPPP_OK;
 }
 
+extern "C" int bppp_test_last_acc_sized(bppp_ctx *ctx, int *sized) {
+  if (!ctx || !sized) return BPPP_ERR_ARG;
+  *sized = ctx->last_acc_sized;
+  return BPPP_OK;
+}
+
 extern "C" int bppp_test_rp_last_verify_counts(bppp_rp *rp, uint64_t *combined_msms, uint64_t *each_passes) {
   if (!rp || !combined_msms || !each_passes) return BPPP_ERR_ARG;
   *combined_msms = rp->n_combined;

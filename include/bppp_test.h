@@ -41,6 +41,10 @@ int bppp_test_last_acc_kernel(bppp_ctx *ctx, int *lds);
 /* The scatter the last MSM of the general pipeline on this context launched: 0 = k_scatter, 2 or 4 = k_scatter_ranges with that many
  * bucket ranges per window (BPPP_SORT_RANGES; one MSM over arbitrary points with 16-bit windows only), -1 = none yet. */
 int bppp_test_last_sort_ranges(bppp_ctx *ctx, int *q);
+/* How the last MSM of the general pipeline on this context accumulated its buckets: 1 = whole buckets in order of size (k_order,
+ * k_acc_points_sized; BPPP_ACC_SIZED, one MSM over arbitrary points only), 0 = slices of the sorted entries (k_acc_points, k_merge),
+ * -1 = none yet. */
+int bppp_test_last_acc_sized(bppp_ctx *ctx, int *sized);
 /* What the last verification on this handle ran (bppp_rp_verify_batch*, _shard_device, _each*, and its group's share of
  * bppp_rp_verify_mixed*): combined MSMs (the accept check and every bisection step) and per-proof passes.  A test sees the cost of a
  * culprit search without timing it. */
