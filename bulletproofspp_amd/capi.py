@@ -36,6 +36,7 @@ SYMBOLS = [
     "bppp_rp_share_comb", "bppp_rp_comb_info", "bppp_rp_prove_mixed",
     "bppp_rp_prove_batch_device",
     "bppp_rp_prove_batch_status", "bppp_rp_prove_batch_status_device", "bppp_rp_witness_status_text",
+    "bppp_rp_commit_batch", "bppp_rp_commit_batch_device", "bppp_rp_open_each", "bppp_rp_open_each_device", "bppp_rp_open_batch", "bppp_rp_open_batch_device",
     "bppp_seed_candidate_x", "bppp_points_from_seed", "bppp_points_from_seed_device", "bppp_rp_create_seeded", "bppp_rp_create_binary_seeded",
 ]
 
@@ -158,6 +159,12 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_prove_batch_status_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp, vp, vp]
     lib.bppp_rp_witness_status_text.argtypes = [C.c_uint32]
     lib.bppp_rp_witness_status_text.restype = C.c_char_p
+    lib.bppp_rp_commit_batch.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    lib.bppp_rp_commit_batch_device.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    lib.bppp_rp_open_each.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    lib.bppp_rp_open_each_device.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    lib.bppp_rp_open_batch.argtypes = [vp, sz, vp, vp, vp, vp, vp, C.POINTER(i), vp, vp]
+    lib.bppp_rp_open_batch_device.argtypes = [vp, sz, C.c_uint64, vp, vp, vp, vp, vp, C.POINTER(i), vp, vp]
     lib.bppp_seed_candidate_x.argtypes = [C.c_char_p, sz, C.c_uint64, vp]
     lib.bppp_points_from_seed.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
     lib.bppp_points_from_seed_device.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
@@ -226,6 +233,9 @@ RP_SHARED, RP_OUTPUT, RP_ASSUMED = 1, 2, 4
 RP_VALID, RP_INVALID, RP_MALFORMED = 0, 1, 2
 # BPPP_RP_WIT_*: a proof's verdict from bppp_rp_prove_batch_status{,_device}
 RP_WIT_OK, RP_WIT_NOT_CANONICAL, RP_WIT_UNBALANCED, RP_WIT_OUT_OF_RANGE, RP_WIT_BIN_NOT_CANONICAL, RP_WIT_BIN_UNBALANCED = 0, 1, 2, 3, 4, 5
+# bppp_rp_commit_batch's own row verdict next to RP_WIT_OK / _NOT_CANONICAL / _BIN_NOT_CANONICAL, and BPPP_RP_OPEN_*: one opening's verdict
+RP_COMMIT_INFINITY = 16
+RP_OPEN_OK, RP_OPEN_MISMATCH, RP_OPEN_MALFORMED, RP_OPEN_NOT_CANONICAL = 0, 1, 2, 3
 
 
 # ---- integer <-> limb helpers (host-side glue for tests / bench)

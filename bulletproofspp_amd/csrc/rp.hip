@@ -909,6 +909,13 @@ int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const Rp
   return BPPP_OK;
 }
 
+// the commitments files alone (bppp_rp_open_*, csrc/rpcommit.hip): the same two kernels' launcher over a shape without a proof file
+void rp_decode_coms(bppp_rp *rp, size_t nb, const uint8_t *d_coms, uint32_t *pts, uint32_t *bad, uint32_t *any_bad) {
+  RpDims D{};
+  D.nr = rp->D.nr; D.coms_bytes = rp->D.coms_bytes;
+  rp_decode_launch(D, nb, d_coms, nullptr, pts, nullptr, nullptr, nullptr, bad, any_bad, rp->ctx->stream);
+}
+
 // verifyBPM of the setup's argument flavour (q is makeNorm's r for the inner-product one) over proofs [o, o + n) of a prepared batch: every
 // per-proof array is [batch][...], so a sub-batch is the same call on offset pointers (any non-zero weights do)
 // (every input was made on the device by rp_verify_prepare: canonical scalars, points on the curve or infinity — no validation pass)

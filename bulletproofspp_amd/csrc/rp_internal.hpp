@@ -136,7 +136,8 @@ struct bppp_rp {
   bppp::HashPlan *d_plan = nullptr;
   uint32_t nhash = 0;
   bppp::RpDims D{};
-  // prover side (csrc/rpprove.hip): fixed-base window table of g, H[0], H[1] for the input commitments, prover workspace
+  // fixed-base window table of g, H[0], H[1] for the input commitments (csrc/rpcommit.hip: the provers and the commit / open entry points);
+  // prover workspace (csrc/rpprove.hip), also the commit / open entry points' — a handle serves one call at a time
   uint32_t *d_fixed = nullptr;
   bppp_basis *commit_basis = nullptr;           // [g | H | G] registered with its fixed-base table: the range-proof commitments
   void *pwork = nullptr; size_t pwork_bytes = 0;
@@ -228,6 +229,20 @@ int each_rows_assemble(bppp_ctx *, int flavour, size_t n, size_t nlen, size_t ll
                        const uint32_t *resp_pts, uint32_t *scratch, uint32_t *rows, uint32_t *tail, uint32_t *pts);
 int basis_msm_dev(bppp_basis *h, const void *d_scalars, size_t n_terms, size_t batch, uint32_t *d_out);     // csrc/basis.hip
 int msm_batch_dev(bppp_ctx *, const void *, const void *, size_t, size_t, int, int, uint32_t *);           // csrc/msm.hip
+}  // namespace bppp
+namespace bppp {
+// ---- input commitments v g + ty H0 + bl H1 (csrc/rpcommit.hip), shared by the provers and by bppp_rp_commit_batch / bppp_rp_open_*
+// the [3][64][15] fixed-base window table of (g, H0, H1), rp->d_fixed: built once per handle, by whichever side needs it first
+int rpp_build_fixed_table(bppp_rp *rp);
+// d_out[i] = sum_j d_in_sc[i][j] * (g, H0, H1)[j] for n commitments (canonical scalars [n][3][8], affine points [n][16]); asynchronous on the
+// context's stream.  rpp_commit_inputs takes the handle's comb table when it has one (and the inputs bppp_rp_prove_mixed already committed),
+// else the window table, which the caller has made sure of; rpp_commit_inputs_fixed always takes the window table.  Same points either way.
+int rpp_commit_inputs(bppp_rp *rp, const uint32_t *d_in_sc, size_t n, uint32_t *d_out);
+int rpp_commit_inputs_fixed(bppp_rp *rp, const uint32_t *d_in_sc, size_t n, uint32_t *d_out);
+// decodeCommitments (Encoding.hs:119-128) alone, by the verifier's decoders (csrc/rpdecode.hip.h, launched from csrc/rp.hip): the commitments
+// files of nb rows in HBM -> pts [nb][nr][16]; an x without a curve point decodes to the infinity encoding and sets bad[row] and any_bad[0]
+// (both OR-ed into: the caller zeroes them).  Queued on the context's stream.
+void rp_decode_coms(bppp_rp *rp, size_t nb, const uint8_t *d_coms, uint32_t *pts, uint32_t *bad, uint32_t *any_bad);
 }  // namespace bppp
 int rp_ensure_comb(bppp_rp *rp);      // csrc/rpprove.hip
 // the handle (and its twin) proves over table t from now on (nullptr: none): t gains a holder, the table held before loses one and is

@@ -9,7 +9,7 @@
 //   proveBPM                        src/Bulletproof.hs:357-359 (the lockstep argument of csrc/nlb.hip)
 //   encodeProof'                    src/RangeProof.hs:60-66, src/Encoding.hs:130-134
 // Work split: every group operation is on the device — the input commitments through a fixed-base window table of (g, H0, H1)
-// (k_rp_commit_inputs: B x #ranges three-term commitments in one launch), the four range-proof commitments of all proofs as
+// (k_rp_commit_inputs, csrc/rpcommit.hip: B x #ranges three-term commitments in one launch), the four range-proof commitments of all proofs as
 // batched MSMs over the registered basis (2B, B, B instances of 1 + linLen + nrmLen terms; comb MSMs once the handle has its comb
 // table, csrc/comb.hip), the argument through csrc/nlb.hip.  The per-proof field algebra (O(nrmLen) multiplications per phase) and
 // the transcript hashing (the CLI's shaOracle and hashToScalar, app/Main.hs:64-87) run on the device (csrc/rpprove_dev.hip;
@@ -30,33 +30,6 @@
 #include "rpprove_dev.hpp"
 #include "rpprove_host.hpp"
 #include "sha256.hip.h"
-
-namespace bppp {
-
-// ---- input commitments  v g + ty H0 + bl H1  (scalarPairRPW', src/RangeProof/Internal.hs:59-60) by fixed-base windows:
-// table[base][w][d - 1] = d 16^w P_base (affine), 3 x 64 x 15 points; a commitment is at most 192 mixed additions, no doubling.
-static constexpr int FB_BASES = 3, FB_WIN = 64, FB_DIG = 15;
-__global__ void __launch_bounds__(64) k_rp_commit_inputs(const uint32_t *__restrict__ table, const uint32_t *__restrict__ sc, uint64_t n,
-                                                         uint32_t *__restrict__ out) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  xyzz acc = xyzz_inf();
-  for (int base = 0; base < FB_BASES; base++) {
-    const fe s = fe_load(sc + (i * FB_BASES + base) * 8);
-    if (fe_is_zero(s)) continue;
-#pragma unroll 1
-    for (int w = 0; w < FB_WIN; w++) {
-      uint32_t limb = 0;
-#pragma unroll
-      for (int k = 0; k < 8; k++) if ((w >> 3) == k) limb = s.v[k];
-      const uint32_t d = (limb >> (4 * (w & 7))) & 15u;
-      if (d) xyzz_madd(acc, aff_load(table + ((size_t)(base * FB_WIN + w) * FB_DIG + (d - 1)) * 16));
-    }
-  }
-  aff_store(out + i * 16, xyzz_to_aff(acc));
-}
-
-}  // namespace bppp
 
 using namespace bppp;
 using namespace bppp_host;
@@ -335,37 +308,6 @@ void make_public_consts(const Setup &st, const PState &ps, U256 &sc, std::vector
   sc = fa(z, acc);
 }
 
-// the fixed-base table of (g, H0, H1): [3][64][15] affine points, built once per setup on the host (2880 additions, one batch inversion)
-int build_fixed_table(bppp_rp *rp) {
-  if (rp->d_fixed) return BPPP_OK;
-  bppp_ctx *ctx = rp->ctx;
-  const Mod &Q = FQ();
-  std::vector<HJac> jac;
-  jac.reserve(FB_BASES * FB_WIN * FB_DIG);
-  const uint64_t *bases[3] = {rp->h_g.data(), rp->h_H.data(), rp->h_H.data() + 8};
-  for (int b = 0; b < FB_BASES; b++) {
-    HJac cur = hj_from_aff(HAff{U256::load(bases[b]), U256::load(bases[b] + 4)});
-    for (int w = 0; w < FB_WIN; w++) {
-      HJac acc = cur;
-      for (int d = 1; d <= FB_DIG; d++) { jac.push_back(acc); acc = hj_add(acc, cur); }
-      cur = acc;                                   // 16 * cur
-    }
-  }
-  std::vector<U256> zs(jac.size());
-  for (size_t i = 0; i < jac.size(); i++) zs[i] = jac[i].Z;
-  batch_minv(zs.data(), zs.size(), Q);
-  std::vector<uint64_t> host(jac.size() * 8, 0);
-  for (size_t i = 0; i < jac.size(); i++) {
-    if (jac[i].inf()) continue;                    // cannot happen for points of prime order; kept as the infinity encoding
-    const U256 zi2 = fqmul(zs[i], zs[i]);
-    fqmul(jac[i].X, zi2).store(&host[8 * i]);
-    fqmul(jac[i].Y, fqmul(zi2, zs[i])).store(&host[8 * i + 4]);
-  }
-  BPPP_HIP(ctx, hipMalloc(&rp->d_fixed, host.size() * 8));
-  BPPP_HIP(ctx, hipMemcpy(rp->d_fixed, host.data(), host.size() * 8, hipMemcpyHostToDevice));
-  return BPPP_OK;
-}
-
 int ensure_pwork(bppp_rp *rp, size_t bytes) {
   if (bytes <= rp->pwork_bytes) return BPPP_OK;
   bppp_ctx *ctx = rp->ctx;
@@ -411,17 +353,6 @@ void rpp_encode_files(const bppp_rp *rp, size_t B, const uint64_t *in_pt, const 
       encode_points(pf + 32 * (st.fn + st.fl), pts.data(), pts.size());
     }
   });
-}
-int rpp_build_fixed_table(bppp_rp *rp) { return build_fixed_table(rp); }
-int rpp_commit_inputs(bppp_rp *rp, const uint32_t *d_in_sc, size_t n, uint32_t *d_out) {
-  bppp_ctx *ctx = rp->ctx;
-  // bppp_rp_prove_mixed committed the inputs of the whole family in one launch (csrc/rpshare.hip): they are complete in HBM
-  if (rp->pre_inputs) { BPPP_HIP(ctx, hipMemcpyAsync(d_out, rp->pre_inputs, n * 64, hipMemcpyDeviceToDevice, ctx->stream)); return BPPP_OK; }
-  // g, H0, H1 are the first three points of the registered basis: with its comb table a commitment is <= 3 x 17 additions, not 3 x 64
-  if (rp->comb) { int rc = comb_lanes(rp->comb, d_in_sc, FB_BASES, n, d_out, ctx->stream); return rc ? fail(ctx, rc, bppp_last_error(rp->comb->ctx)) : BPPP_OK; }
-  k_rp_commit_inputs<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream>>>(rp->d_fixed, d_in_sc, (uint64_t)n, d_out);
-  BPPP_HIP(ctx, hipGetLastError());
-  return BPPP_OK;
 }
 int rpp_commit_rows(bppp_rp *rp, const uint32_t *d_rows, size_t nrows, uint64_t *host_out) {
   if (!rp->comb) return bppp_msm_basis(rp->commit_basis, d_rows, 1 + rp->st.llen + rp->st.nlen, nrows, host_out);
@@ -675,7 +606,7 @@ static int prove_batch_one(bppp_rp *rp, size_t batch, const uint64_t *amounts, c
   hipSetDevice(ctx->device);
   const size_t B = batch, nr = st.rds.size(), nlen = st.nlen, llen = st.llen, k = st.rounds, T = 1 + llen + nlen, npub = rp_public_count(rp);
   if (nr >= (1u << 16)) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: too many ranges");
-  { int rc = build_fixed_table(rp); if (rc) return rc; }
+  { int rc = rpp_build_fixed_table(rp); if (rc) return rc; }
   if (!rp->commit_basis) { int rc = bppp_basis_create_device(ctx, rp->d_basis, T, 0, 4096, &rp->commit_basis); if (rc) return rc; }
   LapTimer timer(rp->opt.timing, "[rp_prove]");
   // ---- the witness on the host: digits and multiplicities are integer work on the plain amounts (TypedReciprocal.hs:125-161)
@@ -722,7 +653,7 @@ static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
   const Setup &st = rp->st;
   const size_t B = batch, nr = st.rds.size(), nlen = st.nlen, llen = st.llen, k = st.rounds, T = 1 + llen + nlen, npub = rp_public_count(rp);
   if (nr >= (1u << 16)) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: too many ranges");
-  { int rc = build_fixed_table(rp); if (rc) return rc; }
+  { int rc = rpp_build_fixed_table(rp); if (rc) return rc; }
   // the basis of commitRPW is fixed per setup: registered once with its fixed-base table (one bucket set for all windows)
   if (!rp->commit_basis) { int rc = bppp_basis_create_device(ctx, rp->d_basis, T, 0, 4096, &rp->commit_basis); if (rc) return rc; }
   // device workspace: [input scalars B nr 3 | input commitments B nr | commitment rows 2B T]
@@ -762,9 +693,7 @@ static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
   timer.lap("phase 1 host");
   BPPP_HIP(ctx, hipMemcpyAsync(d_in_sc, h_in_sc.data(), in_sc, hipMemcpyHostToDevice, stream));
   {
-    const uint64_t n = (uint64_t)B * nr;
-    k_rp_commit_inputs<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream>>>(rp->d_fixed, d_in_sc, n, d_in_pt);
-    BPPP_HIP(ctx, hipGetLastError());
+    { int rc = rpp_commit_inputs_fixed(rp, d_in_sc, B * nr, d_in_pt); if (rc) return rc; }      // this route keeps the 4-bit window table (csrc/rpcommit.hip)
     BPPP_HIP(ctx, hipMemcpyAsync(h_in_pt.data(), d_in_pt, in_pt, hipMemcpyDeviceToHost, stream));
   }
   { int rc = commit_rows(2 * B); if (rc) return rc; }       // synchronises the stream

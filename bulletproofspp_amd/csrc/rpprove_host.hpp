@@ -149,8 +149,7 @@ inline void encode_points(uint8_t *dst, const uint64_t *const *pts, size_t n) {
 
 namespace bppp {
 // csrc/rpprove.hip
-int rpp_build_fixed_table(bppp_rp *rp);
-int rpp_ensure_pwork(bppp_rp *rp, size_t bytes);       // the [3][64][15] fixed-base table of (g, H0, H1) for input commitments before a comb table exists
+int rpp_ensure_pwork(bppp_rp *rp, size_t bytes);       // rp->pwork, the prover's device workspace, holds at least `bytes` (grow-only)
 int rpp_ensure_hpin(bppp_rp *rp, size_t bytes);        // rp->hpin, the batch prover's pinned host staging, holds at least `bytes` (grow-only)
 // encodeProof' (src/RangeProof.hs:60-66) of B proofs: commitments file = the input commitments in_pt [B][nr][8]; proof file = the final
 // witness scalars wn [B][fn][4], wl [B][fl][4], then the route's leading commitments ([B][8] each; typed: blCom rCom dmCom mCom, binary:

@@ -6,7 +6,7 @@
 //   k_brp_witness      witnessBRP (src/RangeProof/Binary.hs:158-166) + makeDigits (:56-69): prove_batch_binary_dev's host loop (csrc/brpprove.hip)
 //   k_rp_encode_files  encodeProof' (src/RangeProof.hs:60-66, src/Encoding.hs:81-86, :130-134): rpp_encode_files (csrc/rpprove.hip)
 // One workgroup (one wavefront) per proof.  Ranges of a proof are independent (one lane each), the digits of a range are a dependent chain.
-// Range arithmetic is on 256-bit INTEGERS in two's complement (csrc/rpsetup.hpp), not on field elements.  A digit is found by bisection over a
+// Range arithmetic is on 256-bit INTEGERS in two's complement (csrc/rpsetup.hpp; wi_*, csrc/rpwords.hip.h), not on field elements.  A digit is found by bisection over a
 // 256 x 32-bit product for every input: the host's 64-bit fast path (digits_into, csrc/rpsetup.hpp) returns the same digit where it applies
 // (a coefficient that does not fit: 0; a zero coefficient: radix - 1).
 // The kernels and their launchers live in a header because the test library (csrc/testhooks.hip) runs the witness kernel alone.
@@ -14,6 +14,7 @@
 #include <vector>
 #include "fe.hip.h"
 #include "rp_internal.hpp"
+#include "rpwords.hip.h"
 
 namespace bppp {
 
@@ -28,18 +29,6 @@ struct WitDims { uint32_t nr, nlen, nmss, npub, has_types, nlive, conserve, coef
 enum : uint32_t { WR_LO = 0, WR_HI = 8, WR_BASE = 16, WR_FLAGS = 17, WR_NCOEF = 18, WR_COEF = 19, WR_POS = 20, WR_MOFF = 21, WR_MOFF2 = 22, WR_WORDS = 24,
                   WF_SHARED = 1, WF_OUTPUT = 2, WF_ASSUMED = 4, WF_BIT = 8, WP_WORDS = 17 };
 
-// ---- 256-bit integers in two's complement (csrc/rpsetup.hpp: s_neg, s_lt, s_mod_n)
-BPPP_DI bool wi_neg(const fe &a) { return (a.v[7] >> 31) != 0; }
-BPPP_DI bool wi_ult(const fe &a, const fe &b) { fe t; return raw_sub(t, a, b) != 0; }
-BPPP_DI bool wi_slt(const fe &a, const fe &b) { return wi_neg(a) != wi_neg(b) ? wi_neg(a) : wi_ult(a, b); }
-BPPP_DI fe wi_umod_n(const fe &a) { fe t; return raw_sub(t, a, fr_modulus()) ? a : t; }
-BPPP_DI fe wi_smod_n(const fe &a) {
-  if (!wi_neg(a)) return wi_umod_n(a);
-  fe m;
-  raw_sub(m, fe_zero(), a);
-  return fe_neg<1>(wi_umod_n(m));
-}
-BPPP_DI bool wi_canonical(const fe &a) { return wi_ult(a, fr_modulus()); }
 // a * m for a 32-bit m; true when the product does not fit 256 bits
 BPPP_DI bool wi_mul32(fe &r, const fe &a, uint32_t m) {
   uint64_t c = 0;
@@ -183,20 +172,6 @@ struct EncDims {
   uint32_t nr, k, fn, fl, nlead, coms_bytes, proof_bytes, batch;
   uint32_t lead_off[4], lead_stride[4];       // leading commitment j of proof b: com + (lead_off[j] + b * lead_stride[j]) * 16 words
 };
-// Binary (Prime p) put (Encoding.hs:81-86) as put_field (csrc/rpprove_host.hpp) writes it: the four 64-bit limbs least significant first,
-// each big-endian; byte o (< 32) from 8 little-endian 32-bit words
-BPPP_DI uint8_t enc_be_byte(const uint32_t *w, uint32_t o) {
-  const uint32_t j = 8 * (o >> 3) + 7 - (o & 7);       // index of the byte in the little-endian image
-  return (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
-}
-// the sign bit of encodeCommitments (Encoding.hs:130-134): y > p - y
-BPPP_DI uint32_t enc_sign(const uint32_t *pt) {
-  const fe y = fe_load(pt + 8);
-  if (fe_is_zero(y)) return 0;
-  fe ny;
-  raw_sub(ny, fp_modulus(), y);
-  return wi_ult(ny, y) ? 1u : 0u;
-}
 // in_pt [B][nr][16]; com: the range-proof commitments (EncDims::lead_*); resp [k][B][2][16] in round order (the file lists the LAST round
 // first, Bulletproof.hs:359); wn [B][fn][8], wl [B][fl][8] canonical.  coms_files [B][coms_bytes], proof_files [B][proof_bytes]
 // dst_index: NULL, or the files of slot b (the block) are those of proof dst_index[b] in the two file buffers

@@ -984,6 +984,113 @@ class NativeRangeProofs:
         cb, pb = self.shape["coms_bytes"], self.shape["proof_bytes"]
         return [(cf[b * cb:(b + 1) * cb].tobytes(), pf[b * pb:(b + 1) * pb].tobytes()) for b in range(B)]
 
+    # ---- commitments without a proof, and their openings (bppp_rp_commit_batch / bppp_rp_open_each / bppp_rp_open_batch)
+    def _claim_arrays(self, inputs):
+        """amounts, types, blindings of `inputs` (the shape prove_batch takes) as the entry points' [B * nranges][4] word arrays"""
+        from .capi import scalars_to_array
+        rows, nr = self._prove_rows(inputs), len(self.st.rds)
+        if any(len(row) != nr for row in rows):
+            raise ValueError("one (amount, type, blinding) per range is required")
+        return (scalars_to_array([v % 2**256 for row in rows for v, _, _ in row] or [0]), scalars_to_array([t for row in rows for _, t, _ in row] or [0]),
+                scalars_to_array([b_ for row in rows for _, _, b_ in row] or [0]))
+
+    def _coms_array(self, coms_files, B):
+        import numpy as np
+        if len(coms_files) != B or any(len(c) != self.shape["coms_bytes"] for c in coms_files):
+            raise ValueError("one commitments file of coms_bytes per row of inputs is required")
+        return np.frombuffer(b"".join(coms_files) or b"\0", dtype=np.uint8)
+
+    def commit_batch(self, inputs, want_status: bool = False):
+        """bppp_rp_commit_batch: the commitments file of every row of `inputs` (prove_batch's shape; types and blindings are passed as given,
+        so a value >= N is the library's to refuse) — no witness is judged.  Returns the files, or (files, statuses) with want_status: a refused
+        row (capi.RP_WIT_NOT_CANONICAL / RP_WIT_BIN_NOT_CANONICAL / RP_COMMIT_INFINITY) has None for its file.  Without want_status a refused
+        row raises BpppError."""
+        import ctypes as C
+        import numpy as np
+        B, cb = len(inputs), self.shape["coms_bytes"]
+        if B == 0:
+            return ([], []) if want_status else []
+        amt, typ, bld = self._claim_arrays(inputs)
+        cf, status = np.zeros(B * cb, dtype=np.uint8), np.zeros(B, dtype=np.uint32)
+        vp = lambda a: C.c_void_p(a.ctypes.data)
+        rc = self.gpu.lib.bppp_rp_commit_batch(self.h, B, vp(amt), vp(typ), vp(bld), vp(status) if want_status else None, vp(cf))
+        self.gpu._check(rc, "bppp_rp_commit_batch")
+        files = [cf[b * cb:(b + 1) * cb].tobytes() for b in range(B)]
+        return ([f if s == 0 else None for f, s in zip(files, status)], [int(s) for s in status]) if want_status else files
+
+    def commit_batch_device(self, batch: int, d_amounts: int, d_types: int, d_blinds: int, d_coms: int, want_status: bool = False):
+        """bppp_rp_commit_batch_device: commit_batch with every buffer in HBM (device pointers; d_types is 0 on a binary handle).  On return
+        d_coms holds the files; returns the verdicts (numpy uint32 [batch]) with want_status, else None (a refused row raises)."""
+        import ctypes as C
+        import numpy as np
+        status = np.zeros(max(batch, 1), dtype=np.uint32)
+        rc = self.gpu.lib.bppp_rp_commit_batch_device(self.h, batch, C.c_void_p(d_amounts), C.c_void_p(d_types), C.c_void_p(d_blinds),
+                                                      C.c_void_p(status.ctypes.data) if want_status else None, C.c_void_p(d_coms))
+        self.gpu._check(rc, "bppp_rp_commit_batch_device")
+        return status[:batch] if want_status else None
+
+    def open_each(self, coms_files: Sequence[bytes], inputs):
+        """bppp_rp_open_each: does commitment i of file b open to inputs[b][i]?  Returns [batch][nranges] ints (capi.RP_OPEN_*): exact, no weights."""
+        import ctypes as C
+        B = len(inputs)
+        if B == 0:
+            return []
+        amt, typ, bld = self._claim_arrays(inputs)
+        cf = self._coms_array(coms_files, B)
+        vp = lambda a: C.c_void_p(a.ctypes.data)
+        return self._open_each(self.gpu.lib.bppp_rp_open_each, B, vp(cf), vp(amt), vp(typ), vp(bld))
+
+    def open_each_device(self, batch: int, d_coms: int, d_amounts: int, d_types: int, d_blinds: int):
+        """bppp_rp_open_each_device: open_each on buffers already in HBM (device pointers; d_types is 0 on a binary handle)"""
+        import ctypes as C
+        return self._open_each(self.gpu.lib.bppp_rp_open_each_device, batch, C.c_void_p(d_coms), C.c_void_p(d_amounts), C.c_void_p(d_types), C.c_void_p(d_blinds))
+
+    def _open_each(self, fn, B, pc, pa, pt, pb):
+        import ctypes as C
+        import numpy as np
+        nr = len(self.st.rds)
+        status = np.zeros(max(B, 1) * nr, dtype=np.uint32)
+        self.gpu._check(fn(self.h, B, pc, pa, pt, pb, C.c_void_p(status.ctypes.data)), "bppp_rp_open_each")
+        return [[int(v) for v in status[b * nr:(b + 1) * nr]] for b in range(B)]
+
+    def open_batch(self, coms_files: Sequence[bytes], inputs, seed: Optional[bytes] = None, want_status: bool = False, want_point: bool = False):
+        """bppp_rp_open_batch: every opening checked with one weighted combination (weights: open_weight below).  `seed` is the checker's
+        randomness, fresh from os.urandom unless given.  Returns accept, or (accept, statuses or None, combined point or None) when
+        want_status / want_point is set: statuses as open_each returns them, the point None for the identity."""
+        import ctypes as C
+        B = len(inputs)
+        amt, typ, bld = self._claim_arrays(inputs)
+        cf = self._coms_array(coms_files, B)
+        vp = lambda a: C.c_void_p(a.ctypes.data)
+        return self._open_batch(lambda *a: self.gpu.lib.bppp_rp_open_batch(self.h, B, vp(cf), vp(amt), vp(typ), vp(bld), *a), B, seed, want_status, want_point)
+
+    def open_batch_device(self, batch: int, d_coms: int, d_amounts: int, d_types: int, d_blinds: int, seed: Optional[bytes] = None, index_offset: int = 0,
+                          want_status: bool = False, want_point: bool = False):
+        """bppp_rp_open_batch_device: open_batch on buffers in HBM; this call holds rows [index_offset, index_offset + batch) of a sharded job
+        whose ranks all pass the same seed (their combined points add up to the one-call point)"""
+        import ctypes as C
+        fn = lambda *a: self.gpu.lib.bppp_rp_open_batch_device(self.h, batch, index_offset, C.c_void_p(d_coms), C.c_void_p(d_amounts), C.c_void_p(d_types),
+                                                               C.c_void_p(d_blinds), *a)
+        return self._open_batch(fn, batch, seed, want_status, want_point)
+
+    def _open_batch(self, fn, B, seed, want_status, want_point):
+        import ctypes as C
+        import numpy as np
+        from .capi import array_to_point
+        if seed is None:
+            seed = os.urandom(32)
+        if len(seed) != 32:
+            raise ValueError("a 32-byte seed is required")
+        nr = len(self.st.rds)
+        acc, sd = C.c_int(0), np.frombuffer(seed, dtype=np.uint8)
+        status, xy = np.zeros(max(B, 1) * nr, dtype=np.uint32), np.zeros(8, dtype=np.uint64)
+        rc = fn(C.c_void_p(sd.ctypes.data), C.byref(acc), C.c_void_p(status.ctypes.data) if want_status else None, C.c_void_p(xy.ctypes.data) if want_point else None)
+        self.gpu._check(rc, "bppp_rp_open_batch")
+        if not (want_status or want_point):
+            return bool(acc.value)
+        return (bool(acc.value), [[int(v) for v in status[b * nr:(b + 1) * nr]] for b in range(B)] if want_status else None,
+                array_to_point(xy) if want_point else None)
+
     def share_comb(self, donor: "NativeRangeProofs"):
         """bppp_rp_share_comb: prove over `donor`'s comb table from now on (built now if it has none).  Same context; the donor's basis
         must extend this handle's point by point.  The table lives until its last user is closed."""
@@ -1093,6 +1200,14 @@ class NativeRangeProofs:
             lead = nch - self.shape["rounds"]               # 7 range-proof challenges (typed reciprocal) or 4 (binary), then one per round
             chs = [(flat[b * nch:b * nch + lead], flat[b * nch + lead:(b + 1) * nch]) for b in range(B)]
         return bool(acc.value), ([int(v) for v in status[:B]] if want_status else None), chs
+
+
+def open_weight(seed: bytes, j: int, x: bytes, sign: int, v: int, ty: int, bl: int) -> int:
+    """The weight rho_j bppp_rp_open_batch gives the opening at job position j (include/bppp.h states the message): x = the commitment's 32
+    x bytes as they stand in the file, sign = its sign bit, (v, ty, bl) the claimed scalars (v already reduced mod N; ty = 0 on a binary handle)."""
+    put = lambda s: b"".join(((s >> (64 * i)) & (2**64 - 1)).to_bytes(8, "big") for i in range(4))      # Binary (Prime p) put (Encoding.hs:81-86)
+    msg = seed + (j % 2**64).to_bytes(8, "little") + x + bytes([sign]) + put(v) + put(ty) + put(bl)
+    return decode_field(hashlib.sha256(msg).digest(), N) or 1
 
 
 def _mixed_groups(files):

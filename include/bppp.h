@@ -601,6 +601,69 @@ int bppp_rp_prove_batch_status_device(bppp_rp *rp, size_t batch, const void *d_a
                                       const void *d_public_amounts, const void *d_rand_prefix, size_t prefix_len, void *d_coms_files,
                                       void *d_proof_files, uint32_t *proof_status /* host, [batch] */);
 
+/* ---- commitments without a proof, and checking their openings ---------------------------------------------------------------------------
+ * The input commitments of a transaction exist before its proof does (a receiver makes them, a builder lays out a transaction with them)
+ * and are checked after it (an auditor, a receiving wallet, a service re-checking its book of openings).  These entry points are
+ * scalarPairRPW' / com (src/RangeProof/Internal.hs:59-60) and encodeCommitments / decodeCommitments (src/Encoding.hs:119-134) on their own:
+ *   C = v g + ty H0 + bl H1      (a RangeProof.Binary handle: C = v g + bl h0, scalarRPW' Internal.hs:56-57; it has no types)
+ * over the first three points [g | H0 | H1] of the handle's registered basis.  Every call takes a bppp_rp of either kind and either
+ * argument flavour (the flavour plays no part).  amounts / types / blinds are laid out as for bppp_rp_prove_batch, [batch][nranges][4]
+ * words: an amount is a plain integer in two's complement, reduced mod n as the prover reduces it (so v and v + n name one commitment);
+ * a type and a blinding are canonical scalars; `types` is ignored on a binary handle and may be NULL there.  NO WITNESS IS JUDGED: no
+ * range check, no balance check, no public amount — any amount has a commitment; bppp_rp_prove_batch_status judges witnesses.
+ * The host variants upload, call the _device variant and download; d_* buffers are in HBM, 16-byte aligned; status arrays are host memory.
+ *
+ * bppp_rp_commit_batch{,_device}: coms_files [batch][coms_bytes], the commitments file of every row.  For every row bppp_rp_prove_batch_pub
+ * accepts, the file equals that call's coms_files row byte for byte.  commit_status ([batch], host, may be NULL): BPPP_RP_WIT_OK,
+ * BPPP_RP_WIT_NOT_CANONICAL (typed: a type or blinding >= n), BPPP_RP_WIT_BIN_NOT_CANONICAL (binary: a blinding >= n) or
+ * BPPP_RP_COMMIT_INFINITY — some commitment of the row is the point at infinity (amount, type and blinding all zero mod n), which has no
+ * encoding (encodeCommitments takes affine coordinates).  NOT_CANONICAL is reported before INFINITY.  The file of a refused row is all
+ * zero bytes, the others are written.  With commit_status == NULL a refused row is BPPP_ERR_ARG and bppp_last_error names the
+ * lowest-numbered one ("proof N: ...") — the files are then as they would be with commit_status given.
+ *
+ * bppp_rp_open_each{,_device}: open_status [batch][nranges] (required), one exact verdict per commitment, no randomness:
+ *   BPPP_RP_OPEN_OK             the decoded point, with its sign applied, equals the recomputed commitment
+ *   BPPP_RP_OPEN_MISMATCH       it does not
+ *   BPPP_RP_OPEN_MALFORMED      the x has no curve point (decodeCommitments' Nothing; an x >= p is reduced first, as the verifier does)
+ *   BPPP_RP_OPEN_NOT_CANONICAL  the claimed type or blinding is >= n (binary: the blinding)
+ * The file is judged before the claim: MALFORMED wins over NOT_CANONICAL.
+ *
+ * bppp_rp_open_batch{,_device}: all openings checked by ONE weighted combination, as bppp_rp_verify_shard_device checks proofs.  The
+ * commitment i of row b has job position j = (index_offset + b) * nranges + i (mod 2^64), error term E_j = C_j - v_j g - ty_j H0 - bl_j H1
+ * and weight
+ *   rho_j = decode (SHA-256 (M_j)) mod n, with 1 in place of 0;  decode = Binary (Prime p): four big-endian 64-bit words, least significant first
+ *   M_j   = seed[32] || le64 (j) || the 32 x bytes of the commitment AS THEY STAND IN THE FILE || one byte holding its sign bit (0 or 1)
+ *           || put (v_j mod n) || put (ty_j) || put (bl_j)          — 169 bytes;  ty_j = 0 on a binary handle;
+ *   put   = Binary (Prime p) put (Encoding.hs:81-86): 32 bytes, the four 64-bit limbs least significant first, each big-endian.
+ * combined = sum_j rho_j E_j = sum_j rho_j C_j - (sum rho_j v_j) g - (sum rho_j ty_j) H0 - (sum rho_j bl_j) H1 (binary: bl on H0): one MSM
+ * over the decoded points plus three reduced scalars.  *accept = 1 iff no x is malformed, no claimed scalar is non-canonical and
+ * combined is the identity.  `seed` is the checker's fresh secret randomness (never a constant outside tests); every rank of a sharded job
+ * passes the same seed and its own index_offset, and the ranks' combined points add up (bppp_sum_points) to the one-call point.
+ * open_status (may be NULL, [batch][nranges]): all BPPP_RP_OPEN_OK when accepted; on rejection exactly bppp_rp_open_each's verdicts over
+ * the same inputs, from one such pass (no bisection).  combined_xy (may be NULL): the combined point, infinity as all zeros; it is defined
+ * by the formula above only when nothing is malformed or non-canonical.  bppp_rp_open_batch is the _device call with index_offset 0.
+ *
+ * Errors, as for the verify entry points: NULL buffers with a non-empty batch, a closed context and batch * nranges >= 2^31 are
+ * BPPP_ERR_ARG; an empty batch returns BPPP_OK (bppp_rp_open_batch* with *accept = 1).  A large batch is worked through in chunks of
+ * 2^22 commitments of bounded memory. */
+#define BPPP_RP_COMMIT_INFINITY 16u
+#define BPPP_RP_OPEN_OK 0u
+#define BPPP_RP_OPEN_MISMATCH 1u
+#define BPPP_RP_OPEN_MALFORMED 2u
+#define BPPP_RP_OPEN_NOT_CANONICAL 3u
+int bppp_rp_commit_batch(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, uint32_t *commit_status,
+                         uint8_t *coms_files);
+int bppp_rp_commit_batch_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds,
+                                uint32_t *commit_status /* host, [batch], may be NULL */, void *d_coms_files);
+int bppp_rp_open_each(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds,
+                      uint32_t *open_status);
+int bppp_rp_open_each_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_amounts, const void *d_types, const void *d_blinds,
+                             uint32_t *open_status /* host, [batch][nranges], required */);
+int bppp_rp_open_batch(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds,
+                       const uint8_t seed[32], int *accept, uint32_t *open_status, uint64_t *combined_xy);
+int bppp_rp_open_batch_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_amounts, const void *d_types,
+                              const void *d_blinds, const uint8_t seed[32], int *accept, uint32_t *open_status, uint64_t *combined_xy);
+
 /* ---- one comb table for the handles of a basis family --------------------------------------------------------------------------
  * Every setup's basis [g | H | G] is a prefix of the point stream its points came from (see bppp_rp_verify_mixed), and the comb table
  * is laid out tab[window][point][multiple]: the table of the longest basis of a stream contains the table of every shorter one (same
