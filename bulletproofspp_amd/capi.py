@@ -36,6 +36,7 @@ SYMBOLS = [
     "bppp_rp_share_comb", "bppp_rp_comb_info", "bppp_rp_prove_mixed",
     "bppp_rp_prove_batch_device",
     "bppp_rp_prove_batch_status", "bppp_rp_prove_batch_status_device", "bppp_rp_witness_status_text",
+    "bppp_rp_verify_bound", "bppp_rp_verify_bound_device", "bppp_rp_verify_each_bound", "bppp_rp_verify_each_bound_device", "bppp_rp_prove_bound", "bppp_rp_prove_bound_device",
     "bppp_rp_commit_batch", "bppp_rp_commit_batch_device", "bppp_rp_open_each", "bppp_rp_open_each_device", "bppp_rp_open_batch", "bppp_rp_open_batch_device",
     "bppp_seed_candidate_x", "bppp_points_from_seed", "bppp_points_from_seed_device", "bppp_rp_create_seeded", "bppp_rp_create_binary_seeded",
 ]
@@ -159,6 +160,12 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_prove_batch_status_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, sz, vp, vp, vp]
     lib.bppp_rp_witness_status_text.argtypes = [C.c_uint32]
     lib.bppp_rp_witness_status_text.restype = C.c_char_p
+    lib.bppp_rp_verify_bound.argtypes = [vp, sz, vp, vp, vp, vp, vp, C.POINTER(i), vp, vp, vp]
+    lib.bppp_rp_verify_bound_device.argtypes = [vp, sz, C.c_uint64, vp, vp, vp, vp, vp, C.POINTER(i), vp, vp, vp]
+    lib.bppp_rp_verify_each_bound.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
+    lib.bppp_rp_verify_each_bound_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
+    lib.bppp_rp_prove_bound.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]
+    lib.bppp_rp_prove_bound_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]
     lib.bppp_rp_commit_batch.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     lib.bppp_rp_commit_batch_device.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     lib.bppp_rp_open_each.argtypes = [vp, sz, vp, vp, vp, vp, vp]
@@ -236,6 +243,26 @@ RP_WIT_OK, RP_WIT_NOT_CANONICAL, RP_WIT_UNBALANCED, RP_WIT_OUT_OF_RANGE, RP_WIT_
 # bppp_rp_commit_batch's own row verdict next to RP_WIT_OK / _NOT_CANONICAL / _BIN_NOT_CANONICAL, and BPPP_RP_OPEN_*: one opening's verdict
 RP_COMMIT_INFINITY = 16
 RP_OPEN_OK, RP_OPEN_MISMATCH, RP_OPEN_MALFORMED, RP_OPEN_NOT_CANONICAL = 0, 1, 2, 3
+# BPPP_RP_BINDING_BYTES: one proof's transcript binding of the bppp_rp_*_bound* entry points
+RP_BINDING_BYTES = 32
+
+
+def bindings_array(bindings, batch: int):
+    """The `bindings` argument of the bound range-proof calls as a contiguous [batch, 32] uint8 array: a sequence of 32-byte bytes objects or an
+    array of that shape.  None stays None (the unbound call).  A wrong length or shape is a ValueError, raised before any library call."""
+    if bindings is None:
+        return None
+    if isinstance(bindings, np.ndarray):
+        if bindings.dtype != np.uint8 or bindings.shape != (batch, RP_BINDING_BYTES):
+            raise ValueError(f"bindings: expected a uint8 array of shape ({batch}, {RP_BINDING_BYTES}), got {bindings.dtype} {bindings.shape}")
+        return np.ascontiguousarray(bindings)
+    rows = list(bindings)
+    if len(rows) != batch:
+        raise ValueError(f"bindings: {len(rows)} bindings for {batch} proofs")
+    for k, r in enumerate(rows):
+        if not isinstance(r, (bytes, bytearray)) or len(r) != RP_BINDING_BYTES:
+            raise ValueError(f"bindings: binding {k} is not {RP_BINDING_BYTES} bytes")
+    return np.frombuffer(b"".join(bytes(r) for r in rows), dtype=np.uint8).reshape(batch, RP_BINDING_BYTES).copy()
 
 
 # ---- integer <-> limb helpers (host-side glue for tests / bench)

@@ -23,6 +23,7 @@ int prove_batch_binary(bppp_rp *rp, size_t batch, const uint64_t *amounts, const
   const Setup &st = rp->st;
   const size_t B = batch, nr = st.rds.size(), nlen = st.nlen, nlive = st.nlive, llen = 2, k = st.rounds, T = 1 + llen + nlen;
   LapTimer timer(rp->opt.timing, "[rp_prove binary]");
+  { int rc = rp_bind_host(rp); if (rc) return rc; }     // a bound call: the oracles below hash under tag <> binding_b
   { int rc = rpp_build_fixed_table(rp); if (rc) return rc; }
   if (!rp->commit_basis) { int rc = bppp_basis_create_device(ctx, rp->d_basis, T, 0, 4096, &rp->commit_basis); if (rc) return rc; }
   const size_t in_sc = B * nr * 3 * 32, in_pt = B * nr * 64, rows = B * T * 32;
@@ -94,7 +95,7 @@ int prove_batch_binary(bppp_rp *rp, size_t batch, const uint64_t *amounts, const
       pts[0] = &c_d[8 * b];
       for (size_t i = 0; i < nr; i++) pts[1 + i] = &h_in_pt[(b * nr + i) * 8];
       U256 ch[3];
-      oracle(rp->tag, p.tr, pts.data(), pts.size(), 3, ch);
+      oracle(rp_tag_at(rp, b), p.tr, pts.data(), pts.size(), 3, ch);
       p.q = ch[0]; p.x = ch[1]; p.r = ch[2];
       p.q0 = fm(p.q, p.q);                                  // qPowers': powers' (q^2) for the norm-linear argument (NormArgument.hs:148),
       if (st.flavour) p.q0 = fneg(p.q0);                    // powers' (-q^2) for the inner-product one (InnerProductArgument.hs:231)
@@ -139,7 +140,7 @@ int prove_batch_binary(bppp_rp *rp, size_t batch, const uint64_t *amounts, const
     for (size_t b = lo; b < hi; b++) {
       BState &p = ps[b];
       const uint64_t *pt = &c_bl[8 * b];
-      oracle(rp->tag, p.tr, &pt, 1, 1, &p.t);
+      oracle(rp_tag_at(rp, b), p.tr, &pt, 1, 1, &p.t);
       const U256 xx = fm(p.x, p.x), two_t = fdbl(p.t);
       U256 x2 = xx, icv = U256::zero(), icb = U256::zero();
       for (size_t j = 0; j < nr; j++) {                     // inputCoeffs (:127-129)

@@ -101,7 +101,7 @@ int ip_argument_lockstep(bppp_rp *rp, size_t B, size_t k, const uint64_t *psv_in
         IpState &p = sts[b];
         const uint64_t *pts[2] = {&h_com[16 * b], &h_com[16 * b + 8]};
         U256 e;
-        oracle(rp->tag, tr_of(b), pts, 2, 1, &e);
+        oracle(rp_tag_at(rp, b), tr_of(b), pts, 2, 1, &e);
         if (e.is_zero()) { bad = 1; continue; }
         const U256 ei = finv(e);
         const size_t slot = k - 1 - round;                     // responses LAST round first (Bulletproof.hs:359)
@@ -169,7 +169,7 @@ int nl_argument_lockstep(bppp_rp *rp, size_t B, size_t k, const uint64_t *psv_in
       for (size_t b = lo; b < hi; b++) {
         const uint64_t *pts[2] = {&X[8 * b], &R[8 * b]};
         U256 e;
-        oracle(rp->tag, tr_of(b), pts, 2, 1, &e);
+        oracle(rp_tag_at(rp, b), tr_of(b), pts, 2, 1, &e);
         e.store(&es[4 * b]);
         const size_t slot = k - 1 - round;                 // responses LAST round first (:359)
         memcpy(&resp[(b * k + slot) * 16], pts[0], 64); memcpy(&resp[(b * k + slot) * 16 + 8], pts[1], 64);

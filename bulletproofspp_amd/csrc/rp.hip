@@ -193,9 +193,10 @@ __global__ void __launch_bounds__(64) k_rp_rho(RpDims D, uint32_t batch, uint64_
 }
 // 64 hashes per workgroup of two wavefronts (producer / consumer, rphash.hip.h); hashes of one KIND sit in one workgroup (equal
 // lengths, the same header): g = h * batch + b
-__global__ void __launch_bounds__(128) k_rp_hash(RpDims D, uint32_t batch, uint32_t nhash, const HashPlan *__restrict__ plan, const uint8_t *__restrict__ text,
-                                                 const uint32_t *__restrict__ text_off, uint32_t *__restrict__ ch, uint32_t *__restrict__ es) {
-  __shared__ uint32_t lds[RP_HASH_PC_LDS_WORDS];
+// (bhdr: NULL, a constant of k_rp_hash — the header of hash kind h, the same for every proof — or, on a bound call, the headers of every
+// (kind, proof) as k_rp_bound_headers wrote them, 32 binding bytes longer: k_rp_hash_bound)
+BPPP_DI void rp_hash_lane(const RpDims &D, uint32_t batch, uint32_t nhash, const HashPlan *__restrict__ plan, const uint32_t *__restrict__ bhdr,
+                          const uint8_t *__restrict__ text, const uint32_t *__restrict__ text_off, uint32_t *__restrict__ ch, uint32_t *__restrict__ es, uint32_t *lds) {
   const uint64_t g = (uint64_t)blockIdx.x * 64 + (threadIdx.x & 63u);
   const bool active = g < (uint64_t)batch * nhash;
   const uint32_t h = active ? (uint32_t)(g / batch) : 0u, b = active ? (uint32_t)(g % batch) : 0u;
@@ -203,11 +204,24 @@ __global__ void __launch_bounds__(128) k_rp_hash(RpDims D, uint32_t batch, uint3
   const uint32_t npts = rp_npts(D);
   const uint32_t *off = text_off + (size_t)b * (npts + 1);
   const uint32_t t0 = off[pl->start_pt], t1 = off[npts];
-  const fe v = rp_hash_to_fr_pc(active, pl->hdr_be, pl->hlen, text + (size_t)b * D.text_stride + t0, t1 - t0, lds);   // the suffix of the proof's text this call hashes
+  const uint32_t *hdr = bhdr ? bhdr + ((size_t)h * batch + b) * 16 : pl->hdr_be;
+  const uint32_t hlen = bhdr ? pl->hlen + (uint32_t)RP_BINDING_BYTES : pl->hlen;
+  const fe v = rp_hash_to_fr_pc(active, hdr, hlen, text + (size_t)b * D.text_stride + t0, t1 - t0, lds);   // the suffix of the proof's text this call hashes
   if (!active || threadIdx.x < 64) return;                  // the consumer wavefront holds the digests
   const uint32_t slot = pl->out_slot;                      // < 7: a challenge of the range-proof layer (ch rows are 7 wide for both kinds), else 7 + round slot
   if (slot < 7) fe_store(ch + ((size_t)b * 7 + slot) * 8, v);
   else fe_store(es + ((size_t)b * D.k + (slot - 7)) * 8, v);
+}
+__global__ void __launch_bounds__(128) k_rp_hash(RpDims D, uint32_t batch, uint32_t nhash, const HashPlan *__restrict__ plan, const uint8_t *__restrict__ text,
+                                                 const uint32_t *__restrict__ text_off, uint32_t *__restrict__ ch, uint32_t *__restrict__ es) {
+  __shared__ uint32_t lds[RP_HASH_PC_LDS_WORDS];
+  rp_hash_lane(D, batch, nhash, plan, nullptr, text, text_off, ch, es, lds);
+}
+__global__ void __launch_bounds__(128) k_rp_hash_bound(RpDims D, uint32_t batch, uint32_t nhash, const HashPlan *__restrict__ plan, const uint32_t *__restrict__ bhdr,
+                                                       const uint8_t *__restrict__ text, const uint32_t *__restrict__ text_off, uint32_t *__restrict__ ch,
+                                                       uint32_t *__restrict__ es) {
+  __shared__ uint32_t lds[RP_HASH_PC_LDS_WORDS];
+  rp_hash_lane(D, batch, nhash, plan, bhdr, text, text_off, ch, es, lds);
 }
 
 
@@ -350,6 +364,7 @@ int rp_build_plan(bppp_rp *rp) {
     if (h.size() > RP_HDR_MAX) return false;
     rp_pack_header(h, p.hdr_be);
     p.hlen = (uint32_t)h.size(); p.start_pt = start; p.out_slot = slot;
+    rp->hdr_max = std::max(rp->hdr_max, p.hlen);
     plan.push_back(p);
     return true;
   };
@@ -454,6 +469,8 @@ void bppp_rp_destroy(bppp_rp *rp) {
   if (rp->d_pub) hipFree(rp->d_pub);
   if (rp->d_wit) hipFree(rp->d_wit);
   if (rp->d_sel) hipFree(rp->d_sel);
+  if (rp->d_bind) hipFree(rp->d_bind);
+  if (rp->d_bhdr) hipFree(rp->d_bhdr);
   if (rp->hflag) hipHostFree(rp->hflag);
   if (rp->hstage) hipHostFree(rp->hstage);
   for (auto &e : rp->slice_ev) if (e) hipEventDestroy(e);
@@ -749,11 +766,11 @@ U256 host_digest_to_fr(const uint32_t h[8]) {
 }
 // text / off: the proof's transcript text and the offsets of its points as k_rp_text_lds wrote them (downloaded); ch_out [7][4], es_out [k][4]
 // (the weight rho_b is k_rp_rho's on both routes).  part 0: the seven challenges of verifyTRRPM; part 1: the k round challenges of verifyBPM
-void host_verifier_oracle(const bppp_rp *rp, const uint8_t *text, const uint32_t *off, uint64_t *ch_out, uint64_t *es_out, int part) {
+void host_verifier_oracle(const bppp_rp *rp, const std::string &tag, const uint8_t *text, const uint32_t *off, uint64_t *ch_out, uint64_t *es_out, int part) {
   const uint32_t k = rp->D.k, nr = rp->D.nr, nrp = rp->D.nrp, npts = 2 * k + nrp + nr;
   auto one = [&](uint32_t n, uint32_t count, uint32_t start, uint64_t *out) {
     Sha256 h;
-    const std::string hdr = rp->tag + std::to_string(n) + std::to_string(count);
+    const std::string hdr = tag + std::to_string(n) + std::to_string(count);
     h.update(hdr.data(), hdr.size());
     h.update(text + off[start], off[npts] - off[start]);
     uint32_t d[8];
@@ -851,6 +868,7 @@ int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const Rp
     uint8_t *htext = (uint8_t *)rp->hstage;
     uint32_t *hoff = (uint32_t *)(htext + tbytes);
     uint64_t *hch = (uint64_t *)(htext + tbytes + obytes), *hes = hch + n_hch;
+    { int rcb = rp_bind_host(rp); if (rcb) return rcb; }      // a bound call: every proof's oracle takes tag <> binding_b
     LapTimer timer(rp->opt.timing, "[rp_verify]", true);
     if (rp_text_lds_bytes(D) <= 64 * 1024) k_rp_text_lds<<<dim3((unsigned)B), dim3(256), rp_text_lds_bytes(D), st>>>(D, init_pts, resp_pts, text, text_off);
     else k_rp_text<<<dim3((unsigned)B), dim3(256), (npts + 1) * 4, st>>>(D, init_pts, resp_pts, text, text_off);
@@ -862,7 +880,7 @@ int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const Rp
     // one proof per item: the calling thread alone for one proof, else with the handle's pool (a std::thread per proof costs more than its 36 us of hashing)
     if (B > 1 && !rp->pool) rp->pool = new bppp::HostPool((unsigned)std::min<size_t>(host_oracle_max, 16) - 1);
     auto all = [&](int part) {
-      const std::function<void(size_t)> f = [&](size_t b) { host_verifier_oracle(rp, htext + b * (size_t)D.text_stride, hoff + b * (npts + 1), &hch[b * 28], &hes[b * k * 4], part); };
+      const std::function<void(size_t)> f = [&](size_t b) { host_verifier_oracle(rp, rp_tag_at(rp, b), htext + b * (size_t)D.text_stride, hoff + b * (npts + 1), &hch[b * 28], &hes[b * k * 4], part); };
       if (B == 1) f(0); else rp->pool->run(B, f);
     };
     all(0);
@@ -883,6 +901,9 @@ int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const Rp
     // each only stretches: hash 0.65 -> 0.55 + 0.87, scalars 0.84 -> 1.04 ms: measured, not kept.)
     if (rp_text_lds_bytes(D) <= 64 * 1024) k_rp_text_lds<<<dim3((unsigned)B), dim3(256), rp_text_lds_bytes(D), st>>>(D, init_pts, resp_pts, text, text_off);
     else k_rp_text<<<dim3((unsigned)B), dim3(256), (npts + 1) * 4, st>>>(D, init_pts, resp_pts, text, text_off);
+    // a bound call: the headers of every (hash kind, proof) first, on `st` ahead of the fork, so both hashing halves find them written
+    const uint32_t *bhdr = nullptr;
+    if (rp->bind.on()) { int rcb = rp_bound_headers(rp, B, (const uint32_t *)rp->d_plan, RpHdrLayout{1, (uint32_t)(sizeof(HashPlan) / 4), RP_HDR_MAX / 4}, rp->nhash, &bhdr); if (rcb) return rcb; }
     const uint32_t nch = D.nch, nes = rp->nhash - D.nch;
     hipStream_t aux = st;
     const bool fork = nes && B <= rp->opt.hash_fork_max;
@@ -893,9 +914,11 @@ int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const Rp
       BPPP_HIP(ctx, hipStreamWaitEvent(aux, ctx->aux_fork, 0));
     }
     const uint32_t nfirst = fork ? nch : rp->nhash;            // one launch over every hash unless the halves run side by side
-    k_rp_hash<<<dim3((unsigned)(((uint64_t)B * nfirst + 63) / 64)), dim3(128), 0, st>>>(D, (uint32_t)B, nfirst, rp->d_plan, text, text_off, ch, es);
+    if (bhdr) k_rp_hash_bound<<<dim3((unsigned)(((uint64_t)B * nfirst + 63) / 64)), dim3(128), 0, st>>>(D, (uint32_t)B, nfirst, rp->d_plan, bhdr, text, text_off, ch, es);
+    else k_rp_hash<<<dim3((unsigned)(((uint64_t)B * nfirst + 63) / 64)), dim3(128), 0, st>>>(D, (uint32_t)B, nfirst, rp->d_plan, text, text_off, ch, es);
     if (fork) {
-      k_rp_hash<<<dim3((unsigned)(((uint64_t)B * nes + 63) / 64)), dim3(128), 0, aux>>>(D, (uint32_t)B, nes, rp->d_plan + nch, text, text_off, ch, es);
+      if (bhdr) k_rp_hash_bound<<<dim3((unsigned)(((uint64_t)B * nes + 63) / 64)), dim3(128), 0, aux>>>(D, (uint32_t)B, nes, rp->d_plan + nch, bhdr + (size_t)nch * B * 16, text, text_off, ch, es);
+      else k_rp_hash<<<dim3((unsigned)(((uint64_t)B * nes + 63) / 64)), dim3(128), 0, aux>>>(D, (uint32_t)B, nes, rp->d_plan + nch, text, text_off, ch, es);
       BPPP_HIP(ctx, hipEventRecord(ctx->aux_join, aux));
     }
     BPPP_HIP(ctx, hipGetLastError());
@@ -1032,9 +1055,11 @@ static int rp_verify_decide(bppp_rp *rp, const RpVerifyArrays &A, int *accept, u
 }
 
 // the batch / shard verifier behind every bppp_rp_verify_{batch,shard}* entry point: proofs at job positions [index_offset, index_offset +
-// batch), files and public amounts (NULL: the handle's own) on the host (`host`) or in HBM; nothing of the call is in flight once it returns
+// batch), files, public amounts (NULL: the handle's own) and bindings (NULL: an unbound call) on the host (`host`) or in HBM; nothing of the
+// call is in flight once it returns
 static int rp_verify_batch_impl(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *coms, const void *proofs, const void *pub, bool host,
-                                const uint8_t seed[32], int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
+                                const uint8_t seed[32], int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy,
+                                const void *bindings = nullptr) {
   if (!rp || !accept) return BPPP_ERR_ARG;
   bppp_ctx *ctx = rp->ctx;
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
@@ -1045,7 +1070,9 @@ static int rp_verify_batch_impl(bppp_rp *rp, size_t batch, uint64_t index_offset
   if (host && (!coms || !proofs)) return fail(ctx, BPPP_ERR_ARG, "rp_verify_batch: null input");
   if (!coms || !proofs || !seed || batch >= (1u << 22)) return fail(ctx, BPPP_ERR_ARG, "rp_verify_batch: bad arguments");
   RpVerifyArrays A;
-  int rc = rp_verify_start(rp, batch, index_offset, coms, proofs, pub, host, seed, A);
+  RpBindGuard guard{rp};
+  int rc = rp_bind_begin(rp, bindings, !host, batch, "rp_verify_bound");
+  if (!rc) rc = rp_verify_start(rp, batch, index_offset, coms, proofs, pub, host, seed, A);
   if (!rc) rc = rp_verify_decide(rp, A, accept, proof_status, challenges_out, combined_xy);
   if (rc || host) ctx_drain(ctx);          // (host files: the sliced uploads read them from the second stream)
   return rc;
@@ -1138,6 +1165,16 @@ int bppp_rp_verify_shard_device(bppp_rp *rp, size_t batch, uint64_t index_offset
 int bppp_rp_verify_shard_pub_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const void *d_public_amounts,
                                     const uint8_t seed[32], int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
   return rp_verify_batch_impl(rp, batch, index_offset, d_coms_files, d_proof_files, d_public_amounts, false, seed, accept, proof_status, challenges_out, combined_xy);
+}
+int bppp_rp_verify_bound(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint8_t *proof_files, const uint64_t *public_amounts, const uint8_t *bindings,
+                         const uint8_t seed[32], int *accept, uint32_t *proof_status, uint64_t *challenges_out, uint64_t *combined_xy) {
+  return rp_verify_batch_impl(rp, batch, 0, coms_files, proof_files, public_amounts, true, seed, accept, proof_status, challenges_out, combined_xy, bindings);
+}
+int bppp_rp_verify_bound_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files, const void *d_public_amounts,
+                                const void *d_bindings, const uint8_t seed[32], int *accept, uint32_t *proof_status, uint64_t *challenges_out,
+                                uint64_t *combined_xy) {
+  return rp_verify_batch_impl(rp, batch, index_offset, d_coms_files, d_proof_files, d_public_amounts, false, seed, accept, proof_status, challenges_out, combined_xy,
+                              d_bindings);
 }
 
 }  // extern "C"

@@ -36,6 +36,22 @@ inline void rp_pack_header(const std::string &h, uint32_t be[RP_HDR_MAX / 4]) {
   for (size_t i = 0; i < h.size() && i < (size_t)RP_HDR_MAX; i++) be[i >> 2] |= (uint32_t)(uint8_t)h[i] << (24 - 8 * (i & 3));
 }   // out_slot: index into ch[7] (< 7) or 7 + index into es[k]
 
+// ---- per-proof transcript bindings (the bppp_rp_*_bound* entry points, include/bppp.h; csrc/rpbind.hip)
+// Proof b of a bound call hashes under the tag  oracle_tag <> binding_b[32].  The bindings of one call hang on the handle while the call
+// runs (a handle serves one call at a time): every oracle of every route reads them there, so a route that never hears of bindings
+// cannot drop them.  h / d: [n][32] bytes as the caller passed them, on the host or in HBM (rp_bind_host / rp_bind_device fetch the
+// other copy); both NULL: an unbound call.  sel_h / sel_d: NULL (slot s of the batch in flight is proof s) or the proofs of the slots,
+// after the refused proofs of a status call were compacted away (csrc/rpwitness.hip).
+static constexpr size_t RP_BINDING_BYTES = 32;
+struct RpBind {
+  const uint8_t *h = nullptr, *d = nullptr; size_t n = 0;
+  const uint32_t *sel_h = nullptr, *sel_d = nullptr;
+  bool on() const { return h || d; }
+  RpBind from(size_t b0, size_t count) const { RpBind r = *this; if (r.h) r.h += RP_BINDING_BYTES * b0; if (r.d) r.d += RP_BINDING_BYTES * b0; r.n = count; return r; }
+};
+// where the unbound headers of a kernel's header table lie, in 32-bit words: header i is the 16 words at (i / per) * group + (i % per) * 16, its
+// length the word at (i / per) * group + hlen + i % per  (HashPlan: {1, 19, 16}; RppHdrs, csrc/rpp_transcript.hip: {3, 54, 48})
+struct RpHdrLayout { uint32_t per, group, hlen; };
 
 // f(lo, hi) on disjoint ranges covering [0, n), one host thread each (at most 16: the GPU box's CPU share per GPU)
 template <class F> static void rp_parallel(size_t n, F f) {
@@ -177,7 +193,30 @@ struct bppp_rp {
   // bppp_rp_prove_batch_status_device, a batch with refused proofs: the accepted and the refused proofs' indices and the accepted proofs' public
   // words in compact order (csrc/rpwitness.hip), grow-only
   uint32_t *d_sel = nullptr; size_t d_sel_bytes = 0;
+  // the bound entry points: the bindings of the call in flight, the copy of them this handle fetched (host: bind_hbuf, HBM: d_bind) and the
+  // per-(oracle output, proof) headers the bound hash kernels read (d_bhdr, [headers][batch][16] big-endian words); grow-only.
+  // hdr_max: the longest unbound header of this setup (rp_build_plan): a bound call needs hdr_max + 32 <= RP_HDR_MAX
+  bppp::RpBind bind;
+  std::vector<uint8_t> bind_hbuf;
+  uint8_t *d_bind = nullptr; size_t d_bind_bytes = 0;
+  uint32_t *d_bhdr = nullptr; size_t d_bhdr_bytes = 0;
+  uint32_t hdr_max = 0;
 };
+namespace bppp {
+// a bound entry point's bindings (NULL: nothing to do) on the handle until the guard goes; `who` names the entry point in the tag-length
+// error, which rp_bind_begin returns (BPPP_ERR_ARG) when the handle's tag leaves no room for 32 more bytes in a header
+int rp_bind_begin(bppp_rp *rp, const void *bindings, bool device, size_t batch, const char *who);
+struct RpBindGuard { bppp_rp *rp; ~RpBindGuard() { if (rp) rp->bind = RpBind(); } };
+// the bindings of the call in flight where a route needs them: on the host (host oracles) or in HBM (the header kernel); no-ops on an
+// unbound call and when that copy is already there
+int rp_bind_host(bppp_rp *rp);
+int rp_bind_device(bppp_rp *rp);
+// the tag slot s of the batch in flight hashes under: oracle_tag, with its binding behind it on a bound call (after rp_bind_host)
+std::string rp_tag_at(const bppp_rp *rp, size_t s);
+// k_rp_bound_headers: out[(i * slots + s) * 16 ..] = the 16 big-endian words of  tag <> binding of slot s <> the rest of unbound header i, for the
+// `nh` headers of a table in HBM (d_table, laid out as L says) — rp->d_bhdr, grown as needed.  Queued on the context's stream.
+int rp_bound_headers(bppp_rp *rp, size_t slots, const uint32_t *d_table, RpHdrLayout L, size_t nh, const uint32_t **out);
+}  // namespace bppp
 
 // public amounts per proof of the *_pub entry points: npub of a typed handle with types, 1 of a conserved binary handle, else 0
 size_t rp_public_count(const bppp_rp *rp);

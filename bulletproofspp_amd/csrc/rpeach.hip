@@ -115,7 +115,7 @@ extern "C" {
 // the per-proof verifier behind every bppp_rp_verify_each* entry point: files and public amounts (NULL: the handle's own) on the host
 // (`host`) or in HBM; nothing of the call is in flight once it returns
 static int rp_verify_each_impl(bppp_rp *rp, size_t batch, const void *coms, const void *proofs, const void *pub, bool host, uint32_t *proof_status,
-                               uint64_t *proof_xy) {
+                               uint64_t *proof_xy, const void *bindings = nullptr) {
   if (!rp || !proof_status) return BPPP_ERR_ARG;
   bppp_ctx *ctx = rp->ctx;
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
@@ -125,7 +125,9 @@ static int rp_verify_each_impl(bppp_rp *rp, size_t batch, const void *coms, cons
   if (!coms || !proofs || batch >= (1u << 22)) return fail(ctx, BPPP_ERR_ARG, "rp_verify_each: bad arguments");
   const uint8_t seed[32] = {0};                    // the prepared weights rho are not used
   RpVerifyArrays A;
-  int rc = rp_verify_start(rp, batch, 0, coms, proofs, pub, host, seed, A);
+  RpBindGuard guard{rp};
+  int rc = rp_bind_begin(rp, bindings, !host, batch, "rp_verify_each_bound");
+  if (!rc) rc = rp_verify_start(rp, batch, 0, coms, proofs, pub, host, seed, A);
   if (!rc) rc = rp_each_pass(rp, A, proof_status, proof_xy);
   if (rc || host) ctx_drain(ctx);
   return rc;
@@ -144,6 +146,14 @@ int bppp_rp_verify_each_device(bppp_rp *rp, size_t batch, const void *d_coms_fil
 int bppp_rp_verify_each_pub_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_proof_files, const void *d_public_amounts,
                                    uint32_t *proof_status, uint64_t *proof_xy) {
   return rp_verify_each_impl(rp, batch, d_coms_files, d_proof_files, d_public_amounts, false, proof_status, proof_xy);
+}
+int bppp_rp_verify_each_bound(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint8_t *proof_files, const uint64_t *public_amounts, const uint8_t *bindings,
+                              uint32_t *proof_status, uint64_t *proof_xy) {
+  return rp_verify_each_impl(rp, batch, coms_files, proof_files, public_amounts, true, proof_status, proof_xy, bindings);
+}
+int bppp_rp_verify_each_bound_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_proof_files, const void *d_public_amounts,
+                                     const void *d_bindings, uint32_t *proof_status, uint64_t *proof_xy) {
+  return rp_verify_each_impl(rp, batch, d_coms_files, d_proof_files, d_public_amounts, false, proof_status, proof_xy, d_bindings);
 }
 
 }  // extern "C"

@@ -129,18 +129,32 @@ __global__ void __launch_bounds__(256) k_rpp_text_prepend_small(const uint32_t *
 // into ch[b][7] (slot < 7) or es[b] (slot = 7)
 struct RppHdrs { uint32_t hdr_be[3][RP_HDR_MAX / 4]; uint32_t hlen[3]; uint32_t slot[3]; };
 // 64 hashes per workgroup of two wavefronts (producer / consumer, rphash.hip.h): g = n * batch + b
-__global__ void __launch_bounds__(128) k_rpp_hash(const RppHdrs *__restrict__ H, uint32_t count, uint32_t batch, const uint8_t *__restrict__ text, uint32_t stride,
-                                                  const uint32_t *__restrict__ tstart, uint32_t tend, uint32_t *__restrict__ ch, uint32_t *__restrict__ es) {
-  __shared__ uint32_t lds[RP_HASH_PC_LDS_WORDS];
+// (bhdr: NULL, a constant of k_rpp_hash — header n of this call, the same for every proof — or, on a bound call, this call's headers of every
+// (n, proof) as k_rp_bound_headers wrote them, [3][batch][16] words, 32 binding bytes longer: k_rpp_hash_bound)
+BPPP_DI void rpp_hash_lane(const RppHdrs *__restrict__ H, const uint32_t *__restrict__ bhdr, uint32_t count, uint32_t batch, const uint8_t *__restrict__ text,
+                           uint32_t stride, const uint32_t *__restrict__ tstart, uint32_t tend, uint32_t *__restrict__ ch, uint32_t *__restrict__ es, uint32_t *lds) {
   const uint64_t g = (uint64_t)blockIdx.x * 64 + (threadIdx.x & 63u);
   const bool active = g < (uint64_t)batch * count;
   const uint32_t n = active ? (uint32_t)(g / batch) : 0u, b = active ? (uint32_t)(g % batch) : 0u;
   const uint32_t s = tstart[b];
-  const fe v = rp_hash_to_fr_pc(active, H->hdr_be[n], H->hlen[n], text + (size_t)b * stride + s, tend - s, lds);
+  const uint32_t *hdr = bhdr ? bhdr + ((size_t)n * batch + b) * 16 : H->hdr_be[n];
+  const uint32_t hlen = bhdr ? H->hlen[n] + (uint32_t)RP_BINDING_BYTES : H->hlen[n];
+  const fe v = rp_hash_to_fr_pc(active, hdr, hlen, text + (size_t)b * stride + s, tend - s, lds);
   if (!active || threadIdx.x < 64) return;
   const uint32_t slot = H->slot[n];
   if (slot < 7) fe_store(ch + ((size_t)b * 7 + slot) * 8, v);
   else fe_store(es + (size_t)b * 8, v);
+}
+__global__ void __launch_bounds__(128) k_rpp_hash(const RppHdrs *__restrict__ H, uint32_t count, uint32_t batch, const uint8_t *__restrict__ text, uint32_t stride,
+                                                  const uint32_t *__restrict__ tstart, uint32_t tend, uint32_t *__restrict__ ch, uint32_t *__restrict__ es) {
+  __shared__ uint32_t lds[RP_HASH_PC_LDS_WORDS];
+  rpp_hash_lane(H, nullptr, count, batch, text, stride, tstart, tend, ch, es, lds);
+}
+__global__ void __launch_bounds__(128) k_rpp_hash_bound(const RppHdrs *__restrict__ H, const uint32_t *__restrict__ bhdr, uint32_t count, uint32_t batch,
+                                                        const uint8_t *__restrict__ text, uint32_t stride, const uint32_t *__restrict__ tstart, uint32_t tend,
+                                                        uint32_t *__restrict__ ch, uint32_t *__restrict__ es) {
+  __shared__ uint32_t lds[RP_HASH_PC_LDS_WORDS];
+  rpp_hash_lane(H, bhdr, count, batch, text, stride, tstart, tend, ch, es, lds);
 }
 
 }  // namespace bppp
@@ -183,6 +197,14 @@ int RppTranscript::begin(bppp_rp *rp_, size_t batch, const std::vector<RppCall> 
     }
   }
   BPPP_HIP(ctx, hipMemcpyAsync(hdrs, hh.data(), hh.size() * sizeof(RppHdrs), hipMemcpyHostToDevice, st));
+  // a bound call (bppp_rp_prove_bound*): every proof hashes under tag <> binding_b — on the host oracle the bindings come to the host, else one kernel
+  // writes the headers of every (call, n, proof) behind the upload above
+  bhdr = nullptr;
+  if (rp->bind.on() && host) { int rc = rp_bind_host(rp); if (rc) return rc; }
+  else if (rp->bind.on()) {
+    static_assert(sizeof(RppHdrs) == 216, "RpHdrLayout below");
+    int rc = rp_bound_headers(rp, B, (const uint32_t *)hdrs, RpHdrLayout{3, (uint32_t)(sizeof(RppHdrs) / 4), 3 * RP_HDR_MAX / 4}, 3 * calls.size(), &bhdr); if (rc) return rc;
+  }
   BPPP_HIP(ctx, hipStreamSynchronize(st));          // ts, hh go out of scope
   groups.assign(host ? B : 0, std::vector<std::string>());
   np.assign(host ? B : 0, 0);
@@ -198,7 +220,9 @@ int RppTranscript::call(const uint32_t *pts_dev, size_t call_index) {
     if (m <= 8 && B >= 256) k_rpp_text_prepend_small<<<dim3((unsigned)((B + 31) / 32)), dim3(256), 0, st>>>(pts_dev, (uint32_t)m, (uint32_t)B, text, stride, tstart);
     else k_rpp_text_prepend<<<dim3((unsigned)B), dim3(256), (m + 1) * 4, st>>>(pts_dev, (uint32_t)m, text, stride, tstart);
     const uint64_t n = (uint64_t)B * count;
-    k_rpp_hash<<<dim3((unsigned)((n + 63) / 64)), dim3(128), 0, st>>>((const RppHdrs *)hdrs + call_index, (uint32_t)count, (uint32_t)B, text, stride, tstart, tend, ch, es);
+    if (bhdr) k_rpp_hash_bound<<<dim3((unsigned)((n + 63) / 64)), dim3(128), 0, st>>>((const RppHdrs *)hdrs + call_index, bhdr + call_index * 3 * B * 16, (uint32_t)count, (uint32_t)B, text,
+                                                                                       stride, tstart, tend, ch, es);
+    else k_rpp_hash<<<dim3((unsigned)((n + 63) / 64)), dim3(128), 0, st>>>((const RppHdrs *)hdrs + call_index, (uint32_t)count, (uint32_t)B, text, stride, tstart, tend, ch, es);
     BPPP_HIP(ctx, hipGetLastError());
     return BPPP_OK;
   }
@@ -206,7 +230,7 @@ int RppTranscript::call(const uint32_t *pts_dev, size_t call_index) {
   BPPP_HIP(ctx, hipMemcpyAsync(hp.data(), pts_dev, B * m * 64, hipMemcpyDeviceToHost, st));
   BPPP_HIP(ctx, hipStreamSynchronize(st));
   {
-    auto work = [&](size_t lo, size_t hi) { for (size_t b = lo; b < hi; b++) rpp_host_oracle(rp->tag, groups[b], np[b], &hp[b * m * 8], m, count, &ho[b * 12]); };
+    auto work = [&](size_t lo, size_t hi) { for (size_t b = lo; b < hi; b++) rpp_host_oracle(rp_tag_at(rp, b), groups[b], np[b], &hp[b * m * 8], m, count, &ho[b * 12]); };
     const size_t nt = std::min<size_t>(B / 16, 16);          // a proof's call is ~10 us of hashing and text: threads only pay from a few dozen proofs
     if (nt <= 1) work(0, B);
     else {

@@ -18,6 +18,7 @@ struct RppTranscript {
   std::vector<RppCall> calls;            // the range-proof layer's calls, then one (2, 1, 7) per round of the argument
   bool host = false;                     // a handful of proofs: the hashing runs on the host cores, the new points and the challenges cross PCIe
   uint8_t *text = nullptr; uint32_t *tstart = nullptr; void *hdrs = nullptr; uint32_t *ch = nullptr, *es = nullptr;     // device; ch [B][7][8], es [B][8]
+  const uint32_t *bhdr = nullptr;        // a bound call in device mode: the headers of every (call, n, proof), [calls][3][B][16] words (csrc/rpbind.hip)
   uint32_t stride = 0, tend = 0;         // text capacity per proof (rp->D.text_stride), right-aligned with 16 bytes of slack at the end
   std::vector<std::vector<std::string>> groups; std::vector<size_t> np;      // host mode: every proof's transcript so far
   static size_t hdr_bytes(size_t ncalls);                                    // device bytes `d_hdrs` needs

@@ -420,11 +420,14 @@ template <class F> static int prove_halves(bppp_rp *rp, size_t batch, size_t spl
   rp->twin->opt = rp->opt;
   const size_t B0 = (batch + 1) / 2;
   rp->twin->pre_inputs = rp->pre_inputs ? rp->pre_inputs + B0 * rp->st.rds.size() * 16 : nullptr;
+  const RpBind whole = rp->bind;                                   // a bound call: the second half starts at its own binding
+  rp->twin->bind = whole.from(B0, batch - B0); rp->bind = whole.from(0, B0);
   int rc1 = BPPP_OK;
   std::thread second([&] { rc1 = half(rp->twin, B0, batch - B0); });
   const int rc0 = half(rp, 0, B0);
   second.join();
   rp->twin->pre_inputs = nullptr;
+  rp->twin->bind = RpBind(); rp->bind = whole;
   if (rc0) return rc0;
   if (rc1) return fail(rp->ctx, rc1, bppp_last_error(rp->twin_ctx));
   return BPPP_OK;
@@ -452,8 +455,10 @@ static bool has_device_stream(const bppp_rp *rp) {
 // per_proof, their *_status forms: proof_status [batch] on the host takes every proof's verdict, a refused proof's files are zeroed and the rest is
 // proved — on a route with a device stream inside each half (csrc/rpwitness.hip), elsewhere here: the accepted proofs' rows are compacted on the
 // host, the route below proves them as a batch of its own, and their files are scattered back
+// bindings: NULL, or the bppp_rp_prove_bound* entry points' [batch][32] bytes (host / HBM as the other buffers): proof b hashes under tag <> binding_b
 static int prove_entry(bppp_rp *rp, size_t batch, const void *amounts_, const void *types_, const void *blinds_, const void *public_amounts, const void *rand_prefix_,
-                       size_t prefix_len, void *coms_files_, void *proof_files_, bool device, bool per_proof = false, uint32_t *proof_status = nullptr) {
+                       size_t prefix_len, void *coms_files_, void *proof_files_, bool device, bool per_proof = false, uint32_t *proof_status = nullptr,
+                       const void *bindings = nullptr) {
   if (!rp) return BPPP_ERR_ARG;
   bppp_ctx *ctx = rp->ctx;
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
@@ -464,6 +469,8 @@ static int prove_entry(bppp_rp *rp, size_t batch, const void *amounts_, const vo
   uint8_t *coms_files = (uint8_t *)coms_files_, *proof_files = (uint8_t *)proof_files_;
   if (!amounts || (!types && rp->st.kind == 0) || !blinds || (prefix_len && !rand_prefix) || !coms_files || !proof_files || batch >= (1u << 20) || prefix_len > 4096)
     return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: bad arguments");
+  RpBindGuard guard{rp};
+  { int rc = rp_bind_begin(rp, bindings, device, batch, "rp_prove_bound"); if (rc) return rc; }
   const size_t npub = rp_public_count(rp);
   std::vector<uint64_t> canon;                  // per-proof public amounts as canonical scalars: what a handle created with them holds
   if (public_amounts) {
@@ -537,7 +544,7 @@ static int prove_entry(bppp_rp *rp, size_t batch, const void *amounts_, const vo
   };
   // per-proof verdicts on host buffers (a device stream takes them from its witness kernel): the refused proofs leave the batch before its route sees it
   std::vector<uint64_t> a_amounts, a_types, a_blinds, a_pub;
-  std::vector<uint8_t> a_prefix, a_coms, a_proofs;
+  std::vector<uint8_t> a_prefix, a_coms, a_proofs, a_bind;
   std::vector<size_t> accepted;
   const size_t submitted = batch;
   uint8_t *const all_coms = coms_files, *const all_proofs = proof_files;
@@ -550,8 +557,10 @@ static int prove_entry(bppp_rp *rp, size_t batch, const void *amounts_, const vo
       const size_t G = accepted.size();
       a_amounts.resize(G * nr * 4); a_blinds.resize(G * nr * 4); a_types.resize(types ? G * nr * 4 : 0); a_pub.resize(pub ? G * npub * 4 : 0);
       a_prefix.resize(G * prefix_len); a_coms.resize(G * cb); a_proofs.resize(G * pb);
+      if (rp->bind.on()) { int rcb = rp_bind_host(rp); if (rcb) return rcb; a_bind.resize(G * RP_BINDING_BYTES); }      // the accepted proofs' bindings move with them
       for (size_t s = 0; s < G; s++) {
         const size_t b = accepted[s];
+        if (!a_bind.empty()) memcpy(&a_bind[s * RP_BINDING_BYTES], rp->bind.h + b * RP_BINDING_BYTES, RP_BINDING_BYTES);
         memcpy(&a_amounts[s * nr * 4], amounts + 4 * nr * b, nr * 32); memcpy(&a_blinds[s * nr * 4], blinds + 4 * nr * b, nr * 32);
         if (types) memcpy(&a_types[s * nr * 4], types + 4 * nr * b, nr * 32);
         if (pub && npub) memcpy(&a_pub[s * npub * 4], pub + 4 * npub * b, npub * 32);
@@ -560,6 +569,7 @@ static int prove_entry(bppp_rp *rp, size_t batch, const void *amounts_, const vo
       amounts = a_amounts.data(); blinds = a_blinds.data(); types = types ? a_types.data() : nullptr; rand_prefix = prefix_len ? a_prefix.data() : nullptr;
       if (pub) pub = a_pub.data();
       coms_files = a_coms.data(); proof_files = a_proofs.data();
+      if (!a_bind.empty()) { rp->bind = RpBind(); rp->bind.h = a_bind.data(); rp->bind.n = G; }
       batch = G;
     }
   }
@@ -593,6 +603,18 @@ extern "C" int bppp_rp_prove_batch_status(bppp_rp *rp, size_t batch, const uint6
 extern "C" int bppp_rp_prove_batch_status_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds, const void *d_public_amounts,
                                                  const void *d_rand_prefix, size_t prefix_len, void *d_coms_files, void *d_proof_files, uint32_t *proof_status) {
   return prove_entry(rp, batch, d_amounts, d_types, d_blinds, d_public_amounts, d_rand_prefix, prefix_len, d_coms_files, d_proof_files, true, true, proof_status);
+}
+
+extern "C" int bppp_rp_prove_bound(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, const uint64_t *public_amounts,
+                                   const uint8_t *bindings, const uint8_t *rand_prefix, size_t prefix_len, uint8_t *coms_files, uint8_t *proof_files,
+                                   uint32_t *proof_status) {
+  return prove_entry(rp, batch, amounts, types, blinds, public_amounts, rand_prefix, prefix_len, coms_files, proof_files, false, false, proof_status, bindings);
+}
+
+extern "C" int bppp_rp_prove_bound_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds, const void *d_public_amounts,
+                                          const void *d_bindings, const void *d_rand_prefix, size_t prefix_len, void *d_coms_files, void *d_proof_files,
+                                          uint32_t *proof_status) {
+  return prove_entry(rp, batch, d_amounts, d_types, d_blinds, d_public_amounts, d_rand_prefix, prefix_len, d_coms_files, d_proof_files, true, false, proof_status, d_bindings);
 }
 
 extern "C" const char *bppp_rp_witness_status_text(uint32_t status) { return bppp_rps::wit_status_text(status); }
@@ -662,6 +684,7 @@ static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
   uint32_t *d_in_sc = (uint32_t *)rp->pwork, *d_in_pt = (uint32_t *)((char *)rp->pwork + ((in_sc + 255) & ~(size_t)255)),
            *d_rows = (uint32_t *)((char *)d_in_pt + ((in_pt + 255) & ~(size_t)255));
 
+  { int rc = rp_bind_host(rp); if (rc) return rc; }     // a bound call: the oracles below hash under tag <> binding_b
   LapTimer timer(rp->opt.timing, "[rp_prove]");      // BPPP_RP_TIMING=1: wall time of each phase on stderr (tuning aid)
   std::vector<PState> ps(B);
   std::vector<uint64_t> h_in_sc(B * nr * 12), h_in_pt(B * nr * 8), h_rows(2 * B * T * 4), h_com(2 * B * 8);
@@ -709,7 +732,7 @@ static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
       pts[0] = &c_dm[8 * b]; pts[1] = &c_m[8 * b];
       for (size_t i = 0; i < nr; i++) pts[2 + i] = &h_in_pt[(b * nr + i) * 8];
       U256 ch[3];
-      oracle(rp->tag, p, pts.data(), pts.size(), 3, ch);
+      oracle(rp_tag_at(rp, b), p, pts.data(), pts.size(), 3, ch);
       p.e = ch[0]; p.x = ch[1]; p.r0 = ch[2];
       p.e_inv = finv(p.e); p.r0_inv = finv(p.r0);
       make_phase2(st, p);
@@ -731,7 +754,7 @@ static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
       PState &p = ps[b];
       const uint64_t *pt = &c_r[8 * b];
       U256 ch[3];
-      oracle(rp->tag, p, &pt, 1, 3, ch);
+      oracle(rp_tag_at(rp, b), p, &pt, 1, 3, ch);
       p.q = ch[0]; p.xp = ch[1]; p.r1 = ch[2];
       p.q0 = fm(p.q, p.q);                                  // qPowers': powers' (q^2) for the NL norm (NormArgument.hs:148),
       if (st.flavour) p.q0 = fneg(p.q0);                    // powers' (-q^2) for the IP one (InnerProductArgument.hs:231)
@@ -762,7 +785,7 @@ static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
     for (size_t b = lo; b < hi; b++) {
       PState &p = ps[b];
       const uint64_t *pt = &c_bl[8 * b];
-      oracle(rp->tag, p, &pt, 1, 1, &p.t);
+      oracle(rp_tag_at(rp, b), p, &pt, 1, 1, &p.t);
       U256 psc; std::vector<U256> pn;
       make_public_consts(st, p, psc, pn, pub ? pub + 4 * npub * b : nullptr);
       const U256 t2 = fm(p.t, p.t), t3 = fm(t2, p.t), t4 = fm(t2, t2), t5 = fm(t4, p.t), t6 = fm(t3, t3), two_t5 = fdbl(t5);

@@ -44,6 +44,8 @@ int rp_prove_device_half(bppp_rp *rp, size_t B, const void *d_amounts, const voi
   const size_t all = B;
   const uint32_t *d_accepted = nullptr;        // NULL (slot b is proof b) or the proofs of the B slots proved below
   std::vector<uint32_t> sel;                   // the accepted proofs, then the refused ones
+  // a bound call: the bindings stay where they are, [all][32] in the caller's order; the oracles reach them through the index lists from here on
+  struct SelGuard { bppp_rp *rp; ~SelGuard() { rp->bind.sel_h = rp->bind.sel_d = nullptr; } } sel_guard{rp};
   if (refused) {
     B = all - refused;
     for (size_t b = 0; b < all; b++) if (status[b] == WIT_OK) sel.push_back((uint32_t)b);
@@ -60,6 +62,7 @@ int rp_prove_device_half(bppp_rp *rp, size_t B, const void *d_amounts, const voi
     BPPP_HIP(ctx, hipGetLastError());
     if (!B) { BPPP_HIP(ctx, hipStreamSynchronize(st)); timer.lap("refused files (device)"); return BPPP_OK; }
     d_accepted = rp->d_sel;
+    if (rp->bind.on()) { rp->bind.sel_h = sel.data(); rp->bind.sel_d = d_accepted; }
     { int rc = binary ? brp_carve(rp, B, prefix_len, true, W) : rpp_carve(rp, B, prefix_len, true, W); if (rc) return rc; }
     { int rc = wit_launch(rp, B, d_amounts, d_types, d_blinds, d_pub, W.in_sc, W.dig, W.mul, W.mss, W.bits, W.status, d_accepted); if (rc) return rc; }
     uint32_t *d_pub_own = rp->d_sel + lists;

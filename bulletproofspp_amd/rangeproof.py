@@ -914,51 +914,105 @@ class NativeRangeProofs:
         finally:
             self.gpu.free(d)
 
-    def prove_batch(self, inputs: Sequence[Sequence[Tuple[int, int, int]]], rand_prefixes: Sequence[bytes], public_amounts=None) -> List[Tuple[bytes, bytes]]:
+    @contextlib.contextmanager
+    def _bindings_arg(self, bindings, B: int, device: bool):
+        """the *_bound entry points' bindings argument: per-proof 32-byte values (capi.bindings_array: a sequence of bytes or a [B, 32] uint8
+        array; ValueError for anything else, before any library call) — uploaded for a device entry point, the copy freed after the call — or,
+        for a device entry point, a device pointer (int) to the [B][32] bytes as given"""
+        import ctypes as C
+        from .capi import bindings_array
+        if device and isinstance(bindings, int):
+            yield C.c_void_p(bindings)
+            return
+        arr = bindings_array(bindings, B)
+        if not device:
+            yield C.c_void_p(arr.ctypes.data)
+            return
+        d = self.gpu.to_device(arr)
+        try:
+            yield C.c_void_p(d)
+        finally:
+            self.gpu.free(d)
+
+    def prove_batch(self, inputs: Sequence[Sequence[Tuple[int, int, int]]], rand_prefixes: Sequence[bytes], public_amounts=None, bindings=None) -> List[Tuple[bytes, bytes]]:
         """bppp_rp_prove_batch: inputs[b] = [(amount, type, blinding) per range]; rand_prefixes[b] = the hashToScalar prefix of
         proof b (all of one length).  Returns [(commitments file, proof file)] — the bytes encoding.encode_proof(prove(...)) gives.
         public_amounts (bppp_rp_prove_batch_pub): per proof, the public amounts that replace the setup's (one list per proof on a typed
-        handle, in pub_vt's order; one int per proof on a binary one); None = the setup's."""
+        handle, in pub_vt's order; one int per proof on a binary one); None = the setup's.
+        bindings (bppp_rp_prove_bound): per proof, 32 bytes that tie the proof to its transaction — proof b is the proof of a handle whose
+        oracle tag is tag + bindings[b]; None = the unbound call."""
         import ctypes as C
+        from .capi import bindings_array
         B = len(inputs)
+        bindings_array(bindings, B)
         if B == 0:
             return []
         amt, typ, bld, pre, plen, cf, pf = self._prove_arrays(inputs, rand_prefixes)
         vp = lambda a: C.c_void_p(a.ctypes.data)
         with self._public_arg(public_amounts, B, False) as pa:
-            rc = self.gpu.lib.bppp_rp_prove_batch_pub(self.h, B, vp(amt), vp(typ), vp(bld), pa, vp(pre), plen, vp(cf), vp(pf))
-        self.gpu._check(rc, "bppp_rp_prove_batch")
+            if bindings is None:
+                rc = self.gpu.lib.bppp_rp_prove_batch_pub(self.h, B, vp(amt), vp(typ), vp(bld), pa, vp(pre), plen, vp(cf), vp(pf))
+            else:
+                with self._bindings_arg(bindings, B, False) as ba:
+                    rc = self.gpu.lib.bppp_rp_prove_bound(self.h, B, vp(amt), vp(typ), vp(bld), pa, ba, vp(pre), plen, vp(cf), vp(pf), None)
+        self.gpu._check(rc, "bppp_rp_prove_batch" if bindings is None else "bppp_rp_prove_bound")
         return self._prove_files(B, cf, pf)
 
     def prove_batch_device(self, batch: int, d_amounts: int, d_types: int, d_blinds: int, d_prefix: int, prefix_len: int, d_coms: int, d_proofs: int,
-                           d_public_amounts: int = 0):
+                           d_public_amounts: int = 0, bindings=None):
         """bppp_rp_prove_batch_device: prove_batch with every buffer in HBM (device pointers, the layouts of _prove_arrays; d_types is 0 on a
-        binary handle, d_public_amounts 0 = the setup's amounts).  On return d_coms / d_proofs hold the files prove_batch returns."""
-        self.gpu.rp_prove_batch_device(self.h, batch, d_amounts, d_types, d_blinds, d_public_amounts, d_prefix, prefix_len, d_coms, d_proofs)
+        binary handle, d_public_amounts 0 = the setup's amounts).  On return d_coms / d_proofs hold the files prove_batch returns.
+        bindings (bppp_rp_prove_bound_device): as for prove_batch (uploaded for the call), or a device pointer to the [batch][32] bytes."""
+        import ctypes as C
+        if bindings is None:
+            self.gpu.rp_prove_batch_device(self.h, batch, d_amounts, d_types, d_blinds, d_public_amounts, d_prefix, prefix_len, d_coms, d_proofs)
+            return
+        p = lambda v: C.c_void_p(v or None)
+        with self._bindings_arg(bindings, batch, True) as ba:
+            rc = self.gpu.lib.bppp_rp_prove_bound_device(self.h, batch, p(d_amounts), p(d_types), p(d_blinds), p(d_public_amounts), ba, p(d_prefix), prefix_len, p(d_coms),
+                                                         p(d_proofs), None)
+        self.gpu._check(rc, "bppp_rp_prove_bound_device")
 
-    def prove_batch_status(self, inputs, rand_prefixes: Sequence[bytes], public_amounts=None):
+    def prove_batch_status(self, inputs, rand_prefixes: Sequence[bytes], public_amounts=None, bindings=None):
         """bppp_rp_prove_batch_status: prove_batch that refuses proof by proof.  Returns (files, statuses): files[b] is (commitments file, proof
         file) — the bytes prove_batch gives for proof b alone — or None for a refused proof; statuses[b] is its capi.RP_WIT_* verdict (0 =
-        accepted)."""
+        accepted).  bindings as for prove_batch (bppp_rp_prove_bound with proof_status)."""
         import ctypes as C
         import numpy as np
+        from .capi import bindings_array
         B = len(inputs)
+        bindings_array(bindings, B)
         if B == 0:
             return [], []
         amt, typ, bld, pre, plen, cf, pf = self._prove_arrays(self._prove_rows(inputs), rand_prefixes)
         status = np.zeros(B, dtype=np.uint32)
         vp = lambda a: C.c_void_p(a.ctypes.data)
         with self._public_arg(public_amounts, B, False) as pa:
-            rc = self.gpu.lib.bppp_rp_prove_batch_status(self.h, B, vp(amt), vp(typ), vp(bld), pa, vp(pre), plen, vp(cf), vp(pf), vp(status))
-        self.gpu._check(rc, "bppp_rp_prove_batch_status")
+            if bindings is None:
+                rc = self.gpu.lib.bppp_rp_prove_batch_status(self.h, B, vp(amt), vp(typ), vp(bld), pa, vp(pre), plen, vp(cf), vp(pf), vp(status))
+            else:
+                with self._bindings_arg(bindings, B, False) as ba:
+                    rc = self.gpu.lib.bppp_rp_prove_bound(self.h, B, vp(amt), vp(typ), vp(bld), pa, ba, vp(pre), plen, vp(cf), vp(pf), vp(status))
+        self.gpu._check(rc, "bppp_rp_prove_batch_status" if bindings is None else "bppp_rp_prove_bound")
         files = self._prove_files(B, cf, pf)
         return [f if s == 0 else None for f, s in zip(files, status)], [int(s) for s in status]
 
     def prove_batch_status_device(self, batch: int, d_amounts: int, d_types: int, d_blinds: int, d_prefix: int, prefix_len: int, d_coms: int, d_proofs: int,
-                                  d_public_amounts: int = 0):
+                                  d_public_amounts: int = 0, bindings=None):
         """bppp_rp_prove_batch_status_device: prove_batch_device that refuses proof by proof.  Returns the verdicts (numpy uint32 [batch], capi.RP_WIT_*); on
-        return d_coms / d_proofs hold the accepted proofs' files and zero bytes for the refused ones."""
-        return self.gpu.rp_prove_batch_status_device(self.h, batch, d_amounts, d_types, d_blinds, d_public_amounts, d_prefix, prefix_len, d_coms, d_proofs)
+        return d_coms / d_proofs hold the accepted proofs' files and zero bytes for the refused ones.  bindings as for prove_batch_device
+        (bppp_rp_prove_bound_device with proof_status)."""
+        import ctypes as C
+        import numpy as np
+        if bindings is None:
+            return self.gpu.rp_prove_batch_status_device(self.h, batch, d_amounts, d_types, d_blinds, d_public_amounts, d_prefix, prefix_len, d_coms, d_proofs)
+        status = np.zeros(max(batch, 1), dtype=np.uint32)
+        p = lambda v: C.c_void_p(v or None)
+        with self._bindings_arg(bindings, batch, True) as ba:
+            rc = self.gpu.lib.bppp_rp_prove_bound_device(self.h, batch, p(d_amounts), p(d_types), p(d_blinds), p(d_public_amounts), ba, p(d_prefix), prefix_len, p(d_coms),
+                                                         p(d_proofs), C.c_void_p(status.ctypes.data))
+        self.gpu._check(rc, "bppp_rp_prove_bound_device")
+        return status[:batch]
 
     def _prove_rows(self, inputs):
         """one (amount, type, blinding) per range, as this class's prove_batch takes its inputs"""
@@ -1104,56 +1158,76 @@ class NativeRangeProofs:
         return {"window_bits": int(c.value), "bytes": int(nb.value), "points": int(npt.value), "users": int(nu.value)}
 
     def verify_batch(self, coms_files: Sequence[bytes], proof_files: Sequence[bytes], seed: Optional[bytes] = None, want_status: bool = False,
-                     want_challenges: bool = False, public_amounts=None):
+                     want_challenges: bool = False, public_amounts=None, bindings=None):
         """bppp_rp_verify_batch on host byte strings: returns accept, or (accept, status list, challenges per proof) as asked.
         `seed` is the verifier's randomness behind the batch weights: fresh from os.urandom unless given (fixed seeds are for tests).
-        public_amounts: per-proof public amounts as for prove_batch (bppp_rp_verify_batch_pub), taken from the transactions."""
+        public_amounts: per-proof public amounts as for prove_batch (bppp_rp_verify_batch_pub), taken from the transactions.
+        bindings: per-proof 32-byte bindings as for prove_batch (bppp_rp_verify_bound), derived from the transactions, never taken from the prover."""
         import ctypes as C
         import numpy as np
+        from .capi import bindings_array
         if seed is None:
             seed = os.urandom(32)
         B = len(proof_files)
+        bindings_array(bindings, B)
         if len(coms_files) != B or len(seed) != 32:
             raise ValueError("one commitments file per proof and a 32-byte seed are required")
         if any(len(c) != self.shape["coms_bytes"] for c in coms_files) or any(len(p_) != self.shape["proof_bytes"] for p_ in proof_files):
             return (False, [2] * B, None) if (want_status or want_challenges) else False       # wrong length: malformed, as decodeProof' returns Nothing
         cb, pb = np.frombuffer(b"".join(coms_files), dtype=np.uint8), np.frombuffer(b"".join(proof_files), dtype=np.uint8)
         with self._public_arg(public_amounts, B, False) as pa:
-            return self._verify(self.gpu.lib.bppp_rp_verify_batch_pub, B, C.c_void_p(cb.ctypes.data), C.c_void_p(pb.ctypes.data), pa, seed, want_status, want_challenges)
+            if bindings is None:
+                return self._verify(self.gpu.lib.bppp_rp_verify_batch_pub, B, C.c_void_p(cb.ctypes.data), C.c_void_p(pb.ctypes.data), pa, seed, want_status, want_challenges)
+            with self._bindings_arg(bindings, B, False) as ba:
+                fn = lambda h, n, pc, pp, pa_, *rest: self.gpu.lib.bppp_rp_verify_bound(h, n, pc, pp, pa_, ba, *rest)
+                return self._verify(fn, B, C.c_void_p(cb.ctypes.data), C.c_void_p(pb.ctypes.data), pa, seed, want_status, want_challenges)
 
     def verify_batch_device(self, batch: int, d_coms: int, d_proofs: int, seed: Optional[bytes] = None, want_status: bool = False, want_challenges: bool = False,
-                            public_amounts=None):
+                            public_amounts=None, bindings=None):
         """bppp_rp_verify_batch_device; public_amounts: per-proof values (uploaded for the call) or a device pointer to the
-        [batch][public_count][4] words (bppp_rp_verify_batch_pub_device)"""
+        [batch][public_count][4] words (bppp_rp_verify_batch_pub_device); bindings: per-proof values (uploaded for the call) or a device
+        pointer to the [batch][32] bytes (bppp_rp_verify_bound_device)"""
         import ctypes as C
         if seed is None:
             seed = os.urandom(32)
         with self._public_arg(public_amounts, batch, True) as pa:
-            return self._verify(self.gpu.lib.bppp_rp_verify_batch_pub_device, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), pa, seed, want_status, want_challenges)
+            if bindings is None:
+                return self._verify(self.gpu.lib.bppp_rp_verify_batch_pub_device, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), pa, seed, want_status, want_challenges)
+            with self._bindings_arg(bindings, batch, True) as ba:
+                fn = lambda h, n, pc, pp, pa_, *rest: self.gpu.lib.bppp_rp_verify_bound_device(h, n, 0, pc, pp, pa_, ba, *rest)
+                return self._verify(fn, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), pa, seed, want_status, want_challenges)
 
-    def verify_batch_device_point(self, batch: int, d_coms: int, d_proofs: int, seed: bytes, index_offset: int = 0, public_amounts=None) -> Tuple[bool, Point]:
+    def verify_batch_device_point(self, batch: int, d_coms: int, d_proofs: int, seed: bytes, index_offset: int = 0, public_amounts=None, bindings=None) -> Tuple[bool, Point]:
         """bppp_rp_verify_shard_device: (accept, the combined point) — the partial result of one rank when the job is sharded
         proof-per-GPU; this rank holds proofs [index_offset, index_offset + batch) of the job, every rank passes the same seed.
-        public_amounts as for verify_batch_device (bppp_rp_verify_shard_pub_device)."""
+        public_amounts as for verify_batch_device (bppp_rp_verify_shard_pub_device); bindings as there, those of this rank's own proofs
+        (bppp_rp_verify_bound_device)."""
         import ctypes as C
         import numpy as np
         from .capi import array_to_point
         acc, out = C.c_int(0), np.zeros(8, dtype=np.uint64)
         sd = np.frombuffer(seed, dtype=np.uint8)
         with self._public_arg(public_amounts, batch, True) as pa:
-            rc = self.gpu.lib.bppp_rp_verify_shard_pub_device(self.h, batch, index_offset, C.c_void_p(d_coms), C.c_void_p(d_proofs), pa, C.c_void_p(sd.ctypes.data),
-                                                              C.byref(acc), None, None, C.c_void_p(out.ctypes.data))
+            if bindings is None:
+                rc = self.gpu.lib.bppp_rp_verify_shard_pub_device(self.h, batch, index_offset, C.c_void_p(d_coms), C.c_void_p(d_proofs), pa, C.c_void_p(sd.ctypes.data),
+                                                                  C.byref(acc), None, None, C.c_void_p(out.ctypes.data))
+            else:
+                with self._bindings_arg(bindings, batch, True) as ba:
+                    rc = self.gpu.lib.bppp_rp_verify_bound_device(self.h, batch, index_offset, C.c_void_p(d_coms), C.c_void_p(d_proofs), pa, ba, C.c_void_p(sd.ctypes.data),
+                                                                  C.byref(acc), None, None, C.c_void_p(out.ctypes.data))
         self.gpu._check(rc, "bppp_rp_verify_shard_device")
         return bool(acc.value), array_to_point(out)
 
-    def verify_each(self, coms_files: Sequence[bytes], proof_files: Sequence[bytes], want_points: bool = False, public_amounts=None):
+    def verify_each(self, coms_files: Sequence[bytes], proof_files: Sequence[bytes], want_points: bool = False, public_amounts=None, bindings=None):
         """bppp_rp_verify_each on host byte strings: every proof decided on its own, without weights or seed.  Returns the status list
         (0 valid, 1 invalid, 2 malformed), or (statuses, [E_b per proof]) with want_points (None for infinity, and for a malformed
         proof).  A file of the wrong length makes the whole batch MALFORMED without a library call, as verify_batch does.
-        public_amounts as for verify_batch (bppp_rp_verify_each_pub)."""
+        public_amounts and bindings as for verify_batch (bppp_rp_verify_each_pub, bppp_rp_verify_each_bound)."""
         import ctypes as C
         import numpy as np
+        from .capi import bindings_array
         B = len(proof_files)
+        bindings_array(bindings, B)
         if len(coms_files) != B:
             raise ValueError("one commitments file per proof is required")
         if any(len(c) != self.shape["coms_bytes"] for c in coms_files) or any(len(p_) != self.shape["proof_bytes"] for p_ in proof_files):
@@ -1161,13 +1235,21 @@ class NativeRangeProofs:
         cb = np.frombuffer(b"".join(coms_files) or b"\0", dtype=np.uint8)
         pb = np.frombuffer(b"".join(proof_files) or b"\0", dtype=np.uint8)
         with self._public_arg(public_amounts, B, False) as pa:
-            return self._verify_each(self.gpu.lib.bppp_rp_verify_each_pub, B, C.c_void_p(cb.ctypes.data), C.c_void_p(pb.ctypes.data), pa, want_points)
+            if bindings is None:
+                return self._verify_each(self.gpu.lib.bppp_rp_verify_each_pub, B, C.c_void_p(cb.ctypes.data), C.c_void_p(pb.ctypes.data), pa, want_points)
+            with self._bindings_arg(bindings, B, False) as ba:
+                fn = lambda h, n, pc, pp, pa_, *rest: self.gpu.lib.bppp_rp_verify_each_bound(h, n, pc, pp, pa_, ba, *rest)
+                return self._verify_each(fn, B, C.c_void_p(cb.ctypes.data), C.c_void_p(pb.ctypes.data), pa, want_points)
 
-    def verify_each_device(self, batch: int, d_coms: int, d_proofs: int, want_points: bool = False, public_amounts=None):
-        """bppp_rp_verify_each_device: verify_each on files already in HBM (device pointers); public_amounts as for verify_batch_device"""
+    def verify_each_device(self, batch: int, d_coms: int, d_proofs: int, want_points: bool = False, public_amounts=None, bindings=None):
+        """bppp_rp_verify_each_device: verify_each on files already in HBM (device pointers); public_amounts and bindings as for verify_batch_device"""
         import ctypes as C
         with self._public_arg(public_amounts, batch, True) as pa:
-            return self._verify_each(self.gpu.lib.bppp_rp_verify_each_pub_device, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), pa, want_points)
+            if bindings is None:
+                return self._verify_each(self.gpu.lib.bppp_rp_verify_each_pub_device, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), pa, want_points)
+            with self._bindings_arg(bindings, batch, True) as ba:
+                fn = lambda h, n, pc, pp, pa_, *rest: self.gpu.lib.bppp_rp_verify_each_bound_device(h, n, pc, pp, pa_, ba, *rest)
+                return self._verify_each(fn, batch, C.c_void_p(d_coms), C.c_void_p(d_proofs), pa, want_points)
 
     def _verify_each(self, fn, B, pc, pp, pa, want_points):
         import ctypes as C

@@ -239,9 +239,10 @@ class NativeBinaryRangeProofs(NativeRangeProofs):
                 (st.nrm_len, 2, st.rounds, tuple(st.final_lens)):
             raise RuntimeError("native binary setup disagrees with the host setup: %r" % (self.shape,))
 
-    def prove_batch(self, inputs: Sequence[Sequence[Tuple[int, int]]], rand_prefixes: Sequence[bytes], public_amounts=None) -> List[Tuple[bytes, bytes]]:
-        """bppp_rp_prove_batch on a binary setup: inputs[b] = [(amount, blinding) per range]; public_amounts: one net_public per proof"""
-        return super().prove_batch([[(v, 0, bl) for v, bl in row] for row in inputs], rand_prefixes, public_amounts=public_amounts)
+    def prove_batch(self, inputs: Sequence[Sequence[Tuple[int, int]]], rand_prefixes: Sequence[bytes], public_amounts=None, bindings=None) -> List[Tuple[bytes, bytes]]:
+        """bppp_rp_prove_batch on a binary setup: inputs[b] = [(amount, blinding) per range]; public_amounts: one net_public per proof;
+        bindings: 32 bytes per proof (bppp_rp_prove_bound), as NativeRangeProofs.prove_batch takes them"""
+        return super().prove_batch([[(v, 0, bl) for v, bl in row] for row in inputs], rand_prefixes, public_amounts=public_amounts, bindings=bindings)
 
     def _prove_rows(self, inputs):
         return [[(v, 0, bl) for v, bl in row] for row in inputs]

@@ -520,9 +520,11 @@ int bppp_rp_prove_batch(bppp_rp *rp, size_t batch, const uint64_t *amounts, cons
  * defined exactly as for bppp_rp_verify_shard_device — the amounts are the verifier's own inputs, fixed before it draws its seed — so
  * combined_xy of bppp_rp_verify_shard_pub_device is the sum over b of bppp_rp_verify_shard_device (handle with amounts_b, 1,
  * index_offset + b, ...)'s points.
- * Fiat-Shamir: the reference does not hash the public amounts into the transcript, and neither does this library (parity): a proof
+ * Fiat-Shamir: the reference does not hash the public amounts into the transcript, and neither do these entry points (parity): a proof
  * made for one fee also opens against a setup whose other values agree only where the prover chose them.  The caller must take the
- * amounts from the transaction it is validating, never from the prover.
+ * amounts from the transaction it is validating, never from the prover — and a caller that wants the proof TIED to that transaction
+ * (its fee, recipients, memo, chain id) passes a hash of them as the proof's binding to the bppp_rp_*_bound* entry points below, which
+ * put it into every oracle message of that proof.
  * BPPP_ERR_ARG: a non-NULL public_amounts with batch > 0 on a handle whose public_count is 0; a typed amount that is not canonical;
  * every argument error of the counterpart without _pub. */
 int bppp_rp_public_count(const bppp_rp *rp, size_t *n);
@@ -600,6 +602,59 @@ int bppp_rp_prove_batch_status(bppp_rp *rp, size_t batch, const uint64_t *amount
 int bppp_rp_prove_batch_status_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds,
                                       const void *d_public_amounts, const void *d_rand_prefix, size_t prefix_len, void *d_coms_files,
                                       void *d_proof_files, uint32_t *proof_status /* host, [batch] */);
+
+/* ---- per-proof transcript bindings: tie each proof to its transaction ------------------------------------------------------------------
+ * The oracle of the range-proof entry points is the CLI's shaOracle (app/Main.hs:75-80) over ZKPT's transcript (src/ZKP.hs:96-101): every
+ * message is  tag <> show n <> show (length ps) <> text,  and the tag is the handle's oracle_tag, fixed at creation — the only domain
+ * separation.  The *_bound* entry points take one more array, bindings: [batch][BPPP_RP_BINDING_BYTES] opaque bytes, which the caller derives
+ * from what each proof belongs to (typically SHA-256 of the transaction's public data).  Proof b of a bound call behaves in every respect as
+ * a proof under a handle whose oracle tag is  oracle_tag <> binding_b:  every oracle message of that proof is
+ *   oracle_tag <> binding_b[32] <> show n <> show (length ps) <> text
+ * so a proof lifted from one transaction does not verify inside another.  Nothing else changes: the prover's randomness (rand_prefix), the
+ * wire format, the file sizes and the commitments are as before, and the batch weights rho_b keep their formula (they hash t and e_last,
+ * which now depend on the binding).  Bindings are raw bytes — 0x00 and bytes >= 0x80 are ordinary values — and two proofs may carry the
+ * same one.  bindings == NULL: the call is exactly its unbound counterpart (the same kernels queued, the same bytes, challenges_out and
+ * combined_xy).  _device variants take d_bindings in HBM; it stays there whenever the batch hashes its transcripts on the GPU, and is read
+ * back (32 bytes per proof) on the routes that hash on host cores (at most HOST_ORACLE_MAX proofs, HOST_ALGEBRA, FOLD_POINTS, a prover
+ * without its comb table).  The host variants upload it where the GPU hashes.
+ *   bppp_rp_verify_bound         bppp_rp_verify_batch_pub plus bindings
+ *   bppp_rp_verify_bound_device  bppp_rp_verify_shard_pub_device plus d_bindings.  index_offset moves the weights only, never the bindings:
+ *                                a rank passes the bindings of its own proofs, and the ranks' combined_xy add up as before
+ *   bppp_rp_verify_each_bound{,_device}   bppp_rp_verify_each_pub{,_device} plus bindings
+ *   bppp_rp_prove_bound{,_device}         with proof_status == NULL: bppp_rp_prove_batch_pub / bppp_rp_prove_batch_device plus bindings (a
+ *                                refused witness fails the call); with proof_status ([batch], host memory on both): bppp_rp_prove_batch_status
+ *                                {,_device} plus bindings (refused proofs get their BPPP_RP_WIT_* code and zeroed files, the rest are proved,
+ *                                each under its own binding wherever it lands in the compacted batch)
+ * public_amounts / d_public_amounts may be NULL as in the counterparts.  Typed-reciprocal and binary handles, both argument flavours.
+ * The culprit search of a rejected batch (bisection or CULPRITS = 1), the two half-batches of a large prove call and verify_each's chunks
+ * all work on each proof's own binding.
+ * Tag limit: a header (tag, binding, the decimal digits of n and of the point count) is at most 64 bytes, so a bound call needs
+ *   strlen (oracle_tag) <= 64 - 32 - 1 - digits (nranges + 2 rounds + 4)       (binary: nranges + 2 rounds + 2)
+ * — 29 bytes while the transcript has fewer than 100 points, 28 below 1000.  On a handle with a longer tag a bound call with bindings
+ * returns BPPP_ERR_ARG and bppp_last_error says so; unbound calls on that handle (bindings == NULL included) keep working.
+ * Errors otherwise: those of the counterpart, with its codes and texts (NULL files with a non-empty batch, ...); an empty batch is BPPP_OK.
+ * What a binding protects: the TRANSCRIPT — a proof verifies only under the binding it was made with.  It does not make the encodings
+ * unique (the malleability of the files is as documented for the unbound calls), and it protects nothing if the verifier takes the
+ * binding from the prover: derive it from the transaction being validated.
+ * Not covered: bppp_rp_verify_mixed*, bppp_rp_prove_mixed (one handle per group there: give each its own tag), and the commit / open entry
+ * points, which hash no transcript and so have nothing to bind. */
+#define BPPP_RP_BINDING_BYTES 32
+int bppp_rp_verify_bound(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint8_t *proof_files, const uint64_t *public_amounts /* NULL ok */,
+                         const uint8_t *bindings /* [batch][32], NULL ok */, const uint8_t seed[32], int *accept, uint32_t *proof_status,
+                         uint64_t *challenges_out, uint64_t *combined_xy);
+int bppp_rp_verify_bound_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_proof_files,
+                                const void *d_public_amounts, const void *d_bindings, const uint8_t seed[32], int *accept, uint32_t *proof_status,
+                                uint64_t *challenges_out, uint64_t *combined_xy);
+int bppp_rp_verify_each_bound(bppp_rp *rp, size_t batch, const uint8_t *coms_files, const uint8_t *proof_files, const uint64_t *public_amounts,
+                              const uint8_t *bindings, uint32_t *proof_status, uint64_t *proof_xy);
+int bppp_rp_verify_each_bound_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_proof_files, const void *d_public_amounts,
+                                     const void *d_bindings, uint32_t *proof_status, uint64_t *proof_xy);
+int bppp_rp_prove_bound(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds,
+                        const uint64_t *public_amounts, const uint8_t *bindings, const uint8_t *rand_prefix, size_t prefix_len, uint8_t *coms_files,
+                        uint8_t *proof_files, uint32_t *proof_status /* may be NULL */);
+int bppp_rp_prove_bound_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds,
+                               const void *d_public_amounts, const void *d_bindings, const void *d_rand_prefix, size_t prefix_len,
+                               void *d_coms_files, void *d_proof_files, uint32_t *proof_status /* host, [batch], may be NULL */);
 
 /* ---- commitments without a proof, and checking their openings ---------------------------------------------------------------------------
  * The input commitments of a transaction exist before its proof does (a receiver makes them, a builder lays out a transaction with them)
