@@ -38,6 +38,7 @@ SYMBOLS = [
     "bppp_rp_prove_batch_status", "bppp_rp_prove_batch_status_device", "bppp_rp_witness_status_text",
     "bppp_rp_verify_bound", "bppp_rp_verify_bound_device", "bppp_rp_verify_each_bound", "bppp_rp_verify_each_bound_device", "bppp_rp_prove_bound", "bppp_rp_prove_bound_device",
     "bppp_rp_commit_batch", "bppp_rp_commit_batch_device", "bppp_rp_open_each", "bppp_rp_open_each_device", "bppp_rp_open_batch", "bppp_rp_open_batch_device",
+    "bppp_rp_tally_each", "bppp_rp_tally_each_device", "bppp_rp_tally_batch", "bppp_rp_tally_batch_device", "bppp_rp_tally_claims", "bppp_rp_tally_claims_device",
     "bppp_seed_candidate_x", "bppp_points_from_seed", "bppp_points_from_seed_device", "bppp_rp_create_seeded", "bppp_rp_create_binary_seeded",
 ]
 
@@ -172,6 +173,12 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_open_each_device.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     lib.bppp_rp_open_batch.argtypes = [vp, sz, vp, vp, vp, vp, vp, C.POINTER(i), vp, vp]
     lib.bppp_rp_open_batch_device.argtypes = [vp, sz, C.c_uint64, vp, vp, vp, vp, vp, C.POINTER(i), vp, vp]
+    lib.bppp_rp_tally_each.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp]
+    lib.bppp_rp_tally_each_device.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp]
+    lib.bppp_rp_tally_batch.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, C.POINTER(i), vp, vp]
+    lib.bppp_rp_tally_batch_device.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, C.c_uint64, vp, C.POINTER(i), vp, vp]
+    lib.bppp_rp_tally_claims.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, sz, vp, vp, vp]
+    lib.bppp_rp_tally_claims_device.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, sz, vp, vp, vp]
     lib.bppp_seed_candidate_x.argtypes = [C.c_char_p, sz, C.c_uint64, vp]
     lib.bppp_points_from_seed.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
     lib.bppp_points_from_seed_device.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
@@ -200,6 +207,9 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_last_acc_sized.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_rp_last_verify_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.bppp_test_rp_set_each_chunk.argtypes = [vp, sz]
+    lib.bppp_test_rp_set_tally_short_max.argtypes = [vp, sz]
+    lib.bppp_test_rp_set_tally_piece.argtypes = [vp, sz]
+    lib.bppp_test_rp_set_tally_chunk.argtypes = [vp, sz]
     lib.bppp_test_rp_witness_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.bppp_test_points_from_seed_chunked.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, sz, vp, C.POINTER(C.c_uint64)]
     lib.bppp_test_seed_lift_digests.argtypes = [vp, C.c_char_p, sz, vp, vp, vp]

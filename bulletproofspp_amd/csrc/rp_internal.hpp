@@ -185,6 +185,9 @@ struct bppp_rp {
   void *ework = nullptr; size_t ework_bytes = 0;
   size_t each_chunk = 0;
   uint64_t n_combined = 0, n_each = 0;
+  // the tally entry points (csrc/rptally.hip): the longest sum one lane walks alone, the entries of one workgroup's piece of a longer sum, and
+  // the entries (and sums) of one pass over the workspace; test hooks lower them so that small jobs straddle them (include/bppp_test.h)
+  size_t tally_short_max = 16, tally_piece = 4096, tally_chunk = (size_t)1 << 22;
   // per-proof public amounts of the *_pub entry points (bppp_rp_public_count per proof): grow-only device copy of one call's canonical
   // scalars, [batch][public_count][8] words
   uint32_t *d_pub = nullptr; size_t d_pub_bytes = 0;
@@ -282,6 +285,12 @@ int rpp_commit_inputs_fixed(bppp_rp *rp, const uint32_t *d_in_sc, size_t n, uint
 // files of nb rows in HBM -> pts [nb][nr][16]; an x without a curve point decodes to the infinity encoding and sets bad[row] and any_bad[0]
 // (both OR-ed into: the caller zeroes them).  Queued on the context's stream.
 void rp_decode_coms(bppp_rp *rp, size_t nb, const uint8_t *d_coms, uint32_t *pts, uint32_t *bad, uint32_t *any_bad);
+// the launches of two of the commit / open kernels (csrc/rpcommit.hip) for the tally entry points (csrc/rptally.hip), queued on the context's stream:
+// k_rp_claim_scalars — n claimed (amount, type, blinding) -> in_sc [n][3][8] in base order, flag [n] and any[0] for a type or blinding >= n;
+// k_rp_open_reduce twice — the three columns of prods [n][3][8] summed mod n and negated into out [3][8]; part: RPP_REDUCE_BLOCKS * 24 words
+static constexpr unsigned RPP_REDUCE_BLOCKS = 1024;
+int rpp_claim_scalars(bppp_rp *rp, uint64_t n, const uint32_t *amounts, const uint32_t *types, const uint32_t *blinds, uint32_t *in_sc, uint32_t *flag, uint32_t *any);
+int rpp_negated_column_sums(bppp_rp *rp, uint64_t n, const uint32_t *prods, uint32_t *part, uint32_t *out);
 }  // namespace bppp
 int rp_ensure_comb(bppp_rp *rp);      // csrc/rpprove.hip
 // the handle (and its twin) proves over table t from now on (nullptr: none): t gains a holder, the table held before loses one and is

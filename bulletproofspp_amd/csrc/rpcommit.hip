@@ -221,6 +221,20 @@ int rpp_commit_inputs(bppp_rp *rp, const uint32_t *d_in_sc, size_t n, uint32_t *
   if (rp->comb) { int rc = comb_lanes(rp->comb, d_in_sc, FB_BASES, n, d_out, ctx->stream); return rc ? fail(ctx, rc, bppp_last_error(rp->comb->ctx)) : BPPP_OK; }
   return rpp_commit_inputs_fixed(rp, d_in_sc, n, d_out);
 }
+int rpp_claim_scalars(bppp_rp *rp, uint64_t n, const uint32_t *amounts, const uint32_t *types, const uint32_t *blinds, uint32_t *in_sc, uint32_t *flag, uint32_t *any) {
+  bppp_ctx *ctx = rp->ctx;
+  k_rp_claim_scalars<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream>>>(n, rp->st.kind == 1, amounts, types, blinds, in_sc, flag, any);
+  BPPP_HIP(ctx, hipGetLastError());
+  return BPPP_OK;
+}
+int rpp_negated_column_sums(bppp_rp *rp, uint64_t n, const uint32_t *prods, uint32_t *part, uint32_t *out) {
+  bppp_ctx *ctx = rp->ctx;
+  const unsigned G = (unsigned)std::min<uint64_t>((n + 255) / 256, RPP_REDUCE_BLOCKS);
+  k_rp_open_reduce<<<dim3(G), dim3(256), 0, ctx->stream>>>(n, prods, part, 0u);
+  k_rp_open_reduce<<<dim3(1), dim3(256), 0, ctx->stream>>>(G, part, out, 1u);
+  BPPP_HIP(ctx, hipGetLastError());
+  return BPPP_OK;
+}
 
 }  // namespace bppp
 

@@ -271,6 +271,22 @@ extern "C" int bppp_test_rp_set_each_chunk(bppp_rp *rp, size_t proofs) {
   return BPPP_OK;
 }
 
+extern "C" int bppp_test_rp_set_tally_short_max(bppp_rp *rp, size_t entries) {
+  if (!rp) return BPPP_ERR_ARG;
+  rp->tally_short_max = entries ? entries : bppp_rp().tally_short_max;
+  return BPPP_OK;
+}
+extern "C" int bppp_test_rp_set_tally_piece(bppp_rp *rp, size_t entries) {
+  if (!rp || entries == 1) return BPPP_ERR_ARG;
+  rp->tally_piece = entries ? entries : bppp_rp().tally_piece;
+  return BPPP_OK;
+}
+extern "C" int bppp_test_rp_set_tally_chunk(bppp_rp *rp, size_t entries) {
+  if (!rp) return BPPP_ERR_ARG;
+  rp->tally_chunk = entries ? entries : bppp_rp().tally_chunk;
+  return BPPP_OK;
+}
+
 extern "C" int bppp_test_rp_witness_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds, const void *d_public_amounts,
                                            uint64_t *in_sc, uint32_t *dig, uint32_t *mul, uint32_t *mss, uint32_t *status) {
   if (!rp || !batch || !d_amounts || !d_blinds || !in_sc || !dig || !status) return BPPP_ERR_ARG;

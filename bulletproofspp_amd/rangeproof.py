@@ -1145,6 +1145,124 @@ class NativeRangeProofs:
         return (bool(acc.value), [[int(v) for v in status[b * nr:(b + 1) * nr]] for b in range(B)] if want_status else None,
                 array_to_point(xy) if want_point else None)
 
+    # ---- tallies: signed sums of commitments against claimed openings (bppp_rp_tally_each / bppp_rp_tally_batch / bppp_rp_tally_claims)
+    @staticmethod
+    def _tally_csr(sum_start, entries):
+        """the CSR arrays as the entry points take them: sum_start [nsums + 1], entries [nnz] (bit 31 = subtract), both uint32"""
+        import numpy as np
+        if len(sum_start) < 1:
+            raise ValueError("sum_start holds nsums + 1 offsets")
+        return np.array(list(sum_start), dtype=np.uint32), np.array(list(entries) or [0], dtype=np.uint32), len(sum_start) - 1, len(entries)
+
+    def _tally_claim_arrays(self, claims, nsums):
+        """one (amount, type, blinding) per sum ((amount, blinding) on a binary handle) as three [nsums][4] word arrays; None: no arrays, every
+        claim is zero.  Amounts are reduced mod N here (any integer names its residue); types and blindings are passed as given."""
+        from .capi import scalars_to_array
+        if claims is None:
+            return None, None, None
+        if len(claims) != nsums:
+            raise ValueError("one claim per sum is required")
+        rows = self._prove_rows([list(claims)])[0]
+        return (scalars_to_array([tally_amount_word(a) for a, _, _ in rows] or [0]), scalars_to_array([t for _, t, _ in rows] or [0]),
+                scalars_to_array([e for _, _, e in rows] or [0]))
+
+    def tally_each(self, coms_files: Sequence[bytes], sum_start, entries, claims=None, want_points: bool = False):
+        """bppp_rp_tally_each: does sum t of the commitments gathered from `coms_files` (entry = flat index row * nranges + i, bit 31 set to
+        subtract: tally_entry) equal claims[t]?  Returns one capi.RP_OPEN_* per sum, or (statuses, points) with want_points: the signed sums
+        themselves, None for the identity and for a MALFORMED sum.  claims None: every claim is zero."""
+        import ctypes as C
+        ss, en, nsums, nnz = self._tally_csr(sum_start, entries)
+        amt, typ, bld = self._tally_claim_arrays(claims, nsums)
+        cf = self._coms_array(coms_files, len(coms_files))
+        vp = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+        return self._tally_each(self.gpu.lib.bppp_rp_tally_each, len(coms_files), vp(cf), nsums, vp(ss), vp(en), nnz, vp(amt), vp(typ), vp(bld), want_points)
+
+    def tally_each_device(self, rows: int, d_coms: int, nsums: int, d_sum_start: int, d_entries: int, nnz: int, d_amounts: int, d_types: int, d_blinds: int,
+                          want_points: bool = False):
+        """bppp_rp_tally_each_device: tally_each on buffers already in HBM (device pointers; 0 for all three claim arrays: zero claims)"""
+        import ctypes as C
+        p = C.c_void_p
+        return self._tally_each(self.gpu.lib.bppp_rp_tally_each_device, rows, p(d_coms), nsums, p(d_sum_start), p(d_entries), nnz, p(d_amounts), p(d_types), p(d_blinds),
+                                want_points)
+
+    def _tally_each(self, fn, rows, pc, nsums, ps, pe, nnz, pa, pt, pb, want_points):
+        import ctypes as C
+        import numpy as np
+        from .capi import array_to_point
+        status, xy = np.zeros(max(nsums, 1), dtype=np.uint32), np.zeros((max(nsums, 1), 8), dtype=np.uint64)
+        self.gpu._check(fn(self.h, rows, pc, nsums, ps, pe, nnz, pa, pt, pb, C.c_void_p(status.ctypes.data), C.c_void_p(xy.ctypes.data) if want_points else None),
+                        "bppp_rp_tally_each")
+        out = [int(v) for v in status[:nsums]]
+        return (out, [array_to_point(xy[t]) for t in range(nsums)]) if want_points else out
+
+    def tally_batch(self, coms_files: Sequence[bytes], sum_start, entries, claims=None, seed: Optional[bytes] = None, want_status: bool = False,
+                    want_point: bool = False):
+        """bppp_rp_tally_batch: every sum checked with one weighted combination (weights: tally_weight below).  `seed` is the checker's
+        randomness, fresh from os.urandom unless given; the pool and the entries are the checker's own, fixed before the seed is drawn.
+        Returns accept, or (accept, statuses or None, combined point or None) when want_status / want_point is set."""
+        import ctypes as C
+        ss, en, nsums, nnz = self._tally_csr(sum_start, entries)
+        amt, typ, bld = self._tally_claim_arrays(claims, nsums)
+        cf = self._coms_array(coms_files, len(coms_files))
+        vp = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+        fn = lambda *a: self.gpu.lib.bppp_rp_tally_batch(self.h, len(coms_files), vp(cf), nsums, vp(ss), vp(en), nnz, vp(amt), vp(typ), vp(bld), *a)
+        return self._tally_batch(fn, nsums, seed, want_status, want_point)
+
+    def tally_batch_device(self, rows: int, d_coms: int, nsums: int, d_sum_start: int, d_entries: int, nnz: int, d_amounts: int, d_types: int, d_blinds: int,
+                           seed: Optional[bytes] = None, index_offset: int = 0, want_status: bool = False, want_point: bool = False):
+        """bppp_rp_tally_batch_device: tally_batch on buffers in HBM; this call holds sums [index_offset, index_offset + nsums) of a sharded job
+        whose ranks all pass the same seed (their combined points add up to the one-call point)"""
+        import ctypes as C
+        p = C.c_void_p
+        fn = lambda *a: self.gpu.lib.bppp_rp_tally_batch_device(self.h, rows, p(d_coms), nsums, p(d_sum_start), p(d_entries), nnz, p(d_amounts), p(d_types), p(d_blinds),
+                                                                index_offset, *a)
+        return self._tally_batch(fn, nsums, seed, want_status, want_point)
+
+    def _tally_batch(self, fn, nsums, seed, want_status, want_point):
+        import ctypes as C
+        import numpy as np
+        from .capi import array_to_point
+        if seed is None:
+            seed = os.urandom(32)
+        if len(seed) != 32:
+            raise ValueError("a 32-byte seed is required")
+        acc, sd = C.c_int(0), np.frombuffer(seed, dtype=np.uint8)
+        status, xy = np.zeros(max(nsums, 1), dtype=np.uint32), np.zeros(8, dtype=np.uint64)
+        rc = fn(C.c_void_p(sd.ctypes.data), C.byref(acc), C.c_void_p(status.ctypes.data) if want_status else None, C.c_void_p(xy.ctypes.data) if want_point else None)
+        self.gpu._check(rc, "bppp_rp_tally_batch")
+        if not (want_status or want_point):
+            return bool(acc.value)
+        return bool(acc.value), ([int(v) for v in status[:nsums]] if want_status else None), (array_to_point(xy) if want_point else None)
+
+    def tally_claims(self, inputs, sum_start, entries):
+        """bppp_rp_tally_claims: the claims of the signed sums over the witness rows `inputs` (commit_batch's shape): one (amount, type,
+        blinding) per sum ((amount, blinding) on a binary handle), every value in [0, N).  tally_each over commit_batch(inputs) with them
+        is all RP_OPEN_OK."""
+        import ctypes as C
+        import numpy as np
+        from .capi import array_to_scalars
+        ss, en, nsums, nnz = self._tally_csr(sum_start, entries)
+        amt, typ, bld = self._claim_arrays(inputs)
+        out = [np.zeros((max(nsums, 1), 4), dtype=np.uint64) for _ in range(3)]
+        vp = lambda a: C.c_void_p(a.ctypes.data)
+        rc = self.gpu.lib.bppp_rp_tally_claims(self.h, len(inputs), vp(amt), vp(typ), vp(bld), nsums, vp(ss), vp(en), nnz, vp(out[0]), vp(out[1]), vp(out[2]))
+        self.gpu._check(rc, "bppp_rp_tally_claims")
+        a, ty, e = (array_to_scalars(o)[:nsums] for o in out)
+        return self._tally_claims_shape([((v - 2**256 if v >= 2**255 else v) % N, t, b) for v, t, b in zip(a, ty, e)])
+
+    def _tally_claims_shape(self, triples):
+        return triples
+
+    def tally_claims_device(self, rows: int, d_amounts: int, d_types: int, d_blinds: int, nsums: int, d_sum_start: int, d_entries: int, nnz: int,
+                            d_claim_amounts: int, d_claim_types: int, d_claim_blinds: int):
+        """bppp_rp_tally_claims_device: tally_claims with every buffer in HBM; the three claim arrays [nsums][4] are written as the other tally
+        entry points take them (d_types and d_claim_types are 0 on a binary handle)"""
+        import ctypes as C
+        p = C.c_void_p
+        rc = self.gpu.lib.bppp_rp_tally_claims_device(self.h, rows, p(d_amounts), p(d_types), p(d_blinds), nsums, p(d_sum_start), p(d_entries), nnz, p(d_claim_amounts),
+                                                      p(d_claim_types), p(d_claim_blinds))
+        self.gpu._check(rc, "bppp_rp_tally_claims_device")
+
     def share_comb(self, donor: "NativeRangeProofs"):
         """bppp_rp_share_comb: prove over `donor`'s comb table from now on (built now if it has none).  Same context; the donor's basis
         must extend this handle's point by point.  The table lives until its last user is closed."""
@@ -1290,6 +1408,54 @@ def open_weight(seed: bytes, j: int, x: bytes, sign: int, v: int, ty: int, bl: i
     put = lambda s: b"".join(((s >> (64 * i)) & (2**64 - 1)).to_bytes(8, "big") for i in range(4))      # Binary (Prime p) put (Encoding.hs:81-86)
     msg = seed + (j % 2**64).to_bytes(8, "little") + x + bytes([sign]) + put(v) + put(ty) + put(bl)
     return decode_field(hashlib.sha256(msg).digest(), N) or 1
+
+
+TALLY_SUBTRACT = 1 << 31
+
+
+def tally_entry(j: int, subtract: bool = False) -> int:
+    """one entry of a tally's CSR: the flat index j = row * nranges + i of a commitment, bit 31 set when it is subtracted"""
+    if not 0 <= j < TALLY_SUBTRACT:
+        raise ValueError("a flat index is below 2^31")
+    return j | (TALLY_SUBTRACT if subtract else 0)
+
+
+def tally_amount_word(a: int) -> int:
+    """the 256-bit two's-complement word that names the amount a mod N to the entry points: the residue when it is below 2^255, else the residue - N"""
+    r = a % N
+    return r if r < 2**255 else (r - N) % 2**256
+
+
+def tally_weight(seed: bytes, t: int, a: int, ty: int, e: int) -> int:
+    """The weight rho_t bppp_rp_tally_batch gives the sum at job position t (include/bppp.h states the message): (a, ty, e) the claim, a
+    already reduced mod N; ty = 0 on a binary handle.  The pool and the entries are not in the message: they are the checker's own inputs."""
+    put = lambda s: b"".join(((s >> (64 * i)) & (2**64 - 1)).to_bytes(8, "big") for i in range(4))      # Binary (Prime p) put (Encoding.hs:81-86)
+    msg = seed + (t % 2**64).to_bytes(8, "little") + put(a) + put(ty) + put(e)
+    return decode_field(hashlib.sha256(msg).digest(), N) or 1
+
+
+def tally_sums(backend: "Backend", points: Sequence[Point], sum_start: Sequence[int], entries: Sequence[int]) -> List[Point]:
+    """Host restatement of the segmented signed sum over the Backend group operations: S_t = sum over entries [sum_start[t], sum_start[t + 1])
+    of +-points[index]; None is the identity (an empty sum, or one that cancels)."""
+    out = []
+    for t in range(len(sum_start) - 1):
+        es = entries[sum_start[t]:sum_start[t + 1]]
+        out.append(backend.commit([N - 1 if e & TALLY_SUBTRACT else 1 for e in es], [points[e & (TALLY_SUBTRACT - 1)] for e in es]) if es else None)
+    return out
+
+
+def tally_claims_host(triples: Sequence[Tuple[int, int, int]], sum_start: Sequence[int], entries: Sequence[int]) -> List[Tuple[int, int, int]]:
+    """Host restatement of bppp_rp_tally_claims: triples[j] = (amount, type, blinding) of the commitment with flat index j (amounts any
+    integers, negative ones too); one (a, ty, e) mod N per sum."""
+    out = []
+    for t in range(len(sum_start) - 1):
+        acc = [0, 0, 0]
+        for e in entries[sum_start[t]:sum_start[t + 1]]:
+            sign = -1 if e & TALLY_SUBTRACT else 1
+            for k in range(3):
+                acc[k] += sign * triples[e & (TALLY_SUBTRACT - 1)][k]
+        out.append(tuple(v % N for v in acc))
+    return out
 
 
 def _mixed_groups(files):

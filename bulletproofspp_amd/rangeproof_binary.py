@@ -247,6 +247,10 @@ class NativeBinaryRangeProofs(NativeRangeProofs):
     def _prove_rows(self, inputs):
         return [[(v, 0, bl) for v, bl in row] for row in inputs]
 
+    def _tally_claims_shape(self, triples):
+        """tally_claims on a binary setup: one (amount, blinding) per sum, as tally_each / tally_batch take their claims here"""
+        return [(a, e) for a, _, e in triples]
+
     def _public_words(self, public_amounts, B: int):
         """B per-proof net_public values -> [B][4] words (mod 2^256, as the constructor passes net_public)"""
         from .capi import scalars_to_array

@@ -719,6 +719,80 @@ int bppp_rp_open_batch(bppp_rp *rp, size_t batch, const uint8_t *coms_files, con
 int bppp_rp_open_batch_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_amounts, const void *d_types,
                               const void *d_blinds, const uint8_t seed[32], int *accept, uint32_t *open_status, uint64_t *combined_xy);
 
+/* ---- tallies: signed sums of commitments against claimed openings --------------------------------------------------------------------
+ * The homomorphic check next to commit / open: a set of commitments adds up.  A validator checks that inputs - outputs - fee g is a commitment
+ * to zero with a known excess blinding; an auditor checks that a book of commitments sums to a stated total.  The shapes that prove balance
+ * inside the proof (conserved typed-reciprocal and conserved binary) do not need it; every other shape, and any untyped handle, does.
+ *
+ * POOL.  coms_files [rows][coms_bytes] of handle rp, exactly as bppp_rp_open_each takes it.  Commitment i of row r has the flat index
+ * j = r * nranges + i; rows * nranges < 2^31, so bit 31 of an index is free.  The pool is decoded once per call (64 bytes a commitment in
+ * HBM; a pool whose decoded form cannot be allocated is BPPP_ERR_HIP).
+ * SUMS.  nsums sums in CSR form: sum_start [nsums + 1] (uint32, non-decreasing, sum_start[0] = 0, sum_start[nsums] = nnz) and entries [nnz]
+ * (uint32: bits 0..30 a flat index, bit 31 set = the commitment is subtracted); nnz < 2^31 and nsums < 2^31.  A commitment may appear in any
+ * number of sums and more than once in one sum; an empty sum is the identity.  nnz is passed next to entries: it is the length the caller
+ * vouches for, and sum_start is checked against it.
+ * CLAIM.  Sum t must equal a_t g + ty_t H0 + e_t H1 (a binary handle: a_t g + e_t h0; ty is ignored there and may be NULL).  claim_amounts,
+ * claim_types, claim_blinds are [nsums][4] words, encoded as for bppp_rp_open_each: the amount a plain integer in two's complement, reduced
+ * mod n; the type and the blinding canonical scalars.  All three NULL: every claim is zero, the pure "these balance to nothing" tally.
+ * The host variants upload, call the _device variant and download; d_* buffers are in HBM, 16-byte aligned; status and point arrays are host
+ * memory.
+ *
+ * bppp_rp_tally_each{,_device}: tally_status [nsums] (required), one exact verdict per sum, no randomness — the BPPP_RP_OPEN_* codes:
+ *   BPPP_RP_OPEN_OK             the signed sum equals the recomputed claim
+ *   BPPP_RP_OPEN_MISMATCH       it does not
+ *   BPPP_RP_OPEN_MALFORMED      the x of some commitment the sum references has no curve point
+ *   BPPP_RP_OPEN_NOT_CANONICAL  the claimed type or blinding is >= n (binary: the blinding)
+ * The file is judged before the claim, as in bppp_rp_open_each: MALFORMED wins over NOT_CANONICAL.  A commitment that no sum references is
+ * never judged.  sums_xy (may be NULL, [nsums][8]): the signed sum itself, infinity as all zeros, and zeros for a MALFORMED sum.
+ *
+ * bppp_rp_tally_batch{,_device}: all sums checked by ONE weighted combination,
+ *   combined = sum_t rho_t (S_t - a_t g - ty_t H0 - e_t H1)
+ * computed as one MSM over nnz + 3 terms: every entry contributes its decoded point with the scalar +-rho_t, and three reduced scalars go on
+ * the first three points of the registered basis (more than 2^22 entries: one such MSM per 2^22, added with bppp_sum_points).  Sum t of this
+ * call has job position index_offset + t (mod 2^64) and weight
+ *   rho_t = decode (SHA-256 (M_t)) mod n, with 1 in place of 0
+ *   M_t   = seed[32] || le64 (index_offset + t) || put (a_t mod n) || put (ty_t) || put (e_t)      — 136 bytes;  ty_t = 0 on a binary handle
+ * with decode and put as defined for bppp_rp_open_batch.  The message does not name the pool or the entries: they are the checker's OWN
+ * inputs, fixed before it draws the seed — as the public amounts of the *_pub calls are.  `seed` is the checker's fresh secret randomness
+ * (never a constant outside tests); a checker that lets another party choose entries after seeing the seed has no guarantee.
+ * *accept = 1 iff nothing referenced is malformed, no claim is non-canonical and combined is the identity.  tally_status (may be NULL,
+ * [nsums]): all BPPP_RP_OPEN_OK when accepted; on rejection exactly bppp_rp_tally_each's verdicts over the same inputs, from one such pass.
+ * combined_xy (may be NULL): the combined point, infinity as all zeros, defined by the formula only when nothing is malformed or
+ * non-canonical.  Every rank of a sharded job passes the same seed, its own sums and its own index_offset; the ranks' points add up
+ * (bppp_sum_points) to the one-call point.  bppp_rp_tally_batch is the _device call with index_offset 0.
+ *
+ * bppp_rp_tally_claims{,_device}: the builder's side (pedersen_blind_sum's counterpart).  amounts / types / blinds are the witness rows
+ * [rows][nranges][4] in bppp_rp_commit_batch's layout, the CSR arrays as above; claim_amounts, claim_types, claim_blinds [nsums][4] receive
+ * the signed sums mod n of the referenced (amount mod n, type, blinding).  The amount is written as the integer the other entry points read
+ * back as itself: a when a < 2^255, else a - n in two's complement.  On a binary handle types is ignored and claim_types may be NULL (zeros
+ * are written when it is not).  A referenced type or blinding >= n is BPPP_ERR_ARG naming the lowest such sum.  By construction
+ * bppp_rp_tally_each over bppp_rp_commit_batch's files of these rows with these claims is all BPPP_RP_OPEN_OK.
+ *
+ * Errors (BPPP_ERR_ARG, bppp_last_error names the first offender): NULL buffers with a non-empty job; a closed context; rows * nranges,
+ * nnz or nsums >= 2^31; a sum_start that is not non-decreasing from 0 to nnz ("sum_start[i] = ..."); an entry whose index is >= rows * nranges
+ * ("entries[i]: index ..."); only some of the claim arrays NULL (a binary handle's types do not count).  nsums == 0 is BPPP_OK (tally_batch
+ * with *accept = 1).  The CSR conditions are established by a kernel of their own whose verdict is read back BEFORE anything reads through
+ * entries, on the host variants too: a bad array is an error code, never an out-of-bounds read, and no output buffer is written.  The
+ * sums are worked through in passes of at most 2^22 entries of bounded workspace. */
+int bppp_rp_tally_each(bppp_rp *rp, size_t rows, const uint8_t *coms_files, size_t nsums, const uint32_t *sum_start, const uint32_t *entries, size_t nnz,
+                       const uint64_t *claim_amounts, const uint64_t *claim_types, const uint64_t *claim_blinds, uint32_t *tally_status,
+                       uint64_t *sums_xy /* may be NULL */);
+int bppp_rp_tally_each_device(bppp_rp *rp, size_t rows, const void *d_coms_files, size_t nsums, const void *d_sum_start, const void *d_entries, size_t nnz,
+                              const void *d_claim_amounts, const void *d_claim_types, const void *d_claim_blinds,
+                              uint32_t *tally_status /* host, [nsums], required */, uint64_t *sums_xy /* host, [nsums][8], may be NULL */);
+int bppp_rp_tally_batch(bppp_rp *rp, size_t rows, const uint8_t *coms_files, size_t nsums, const uint32_t *sum_start, const uint32_t *entries, size_t nnz,
+                        const uint64_t *claim_amounts, const uint64_t *claim_types, const uint64_t *claim_blinds, const uint8_t seed[32], int *accept,
+                        uint32_t *tally_status, uint64_t *combined_xy);
+int bppp_rp_tally_batch_device(bppp_rp *rp, size_t rows, const void *d_coms_files, size_t nsums, const void *d_sum_start, const void *d_entries, size_t nnz,
+                               const void *d_claim_amounts, const void *d_claim_types, const void *d_claim_blinds, uint64_t index_offset,
+                               const uint8_t seed[32], int *accept, uint32_t *tally_status, uint64_t *combined_xy);
+int bppp_rp_tally_claims(bppp_rp *rp, size_t rows, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds, size_t nsums,
+                         const uint32_t *sum_start, const uint32_t *entries, size_t nnz, uint64_t *claim_amounts, uint64_t *claim_types,
+                         uint64_t *claim_blinds);
+int bppp_rp_tally_claims_device(bppp_rp *rp, size_t rows, const void *d_amounts, const void *d_types, const void *d_blinds, size_t nsums,
+                                const void *d_sum_start, const void *d_entries, size_t nnz, void *d_claim_amounts, void *d_claim_types,
+                                void *d_claim_blinds);
+
 /* ---- one comb table for the handles of a basis family --------------------------------------------------------------------------
  * Every setup's basis [g | H | G] is a prefix of the point stream its points came from (see bppp_rp_verify_mixed), and the comb table
  * is laid out tab[window][point][multiple]: the table of the longest basis of a stream contains the table of every shorter one (same
