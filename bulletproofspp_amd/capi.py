@@ -205,6 +205,7 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_last_acc_kernel.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_last_sort_ranges.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_last_acc_sized.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.bppp_test_last_windows.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_rp_last_verify_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.bppp_test_rp_set_each_chunk.argtypes = [vp, sz]
     lib.bppp_test_rp_set_tally_short_max.argtypes = [vp, sz]

@@ -57,6 +57,7 @@ struct bppp_ctx {
   int last_acc_lds = -1;             // accumulate kernel of the last general-pipeline MSM: 0 k_acc_points, 1 k_acc_points_lds (bppp_test_last_acc_kernel)
   int last_sort_ranges = -1;         // bucket ranges Q of the last general-pipeline MSM's scatter: 0 k_scatter, 2 / 4 k_scatter_ranges (bppp_test_last_sort_ranges)
   int last_acc_sized = -1;           // 1: the last general-pipeline MSM accumulated whole buckets by size (k_order, k_acc_points_sized), 0: slices (bppp_test_last_acc_sized)
+  int last_windows = -1;             // digit rows W per scalar of the last MSM's plan, either route (bppp_test_last_windows)
   size_t sort_lds_set = 0;           // largest dynamic-LDS size set on the MSM's sort kernels (hipFuncSetAttribute once, not per call)
 };
 

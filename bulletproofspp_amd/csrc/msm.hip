@@ -45,8 +45,10 @@ namespace bppp {
 // 1. digits
 // Window widths: the first `acnt` windows are c bits wide, the others c - 1 (balanced windows, make_plan; acnt = W: all c).  A digit of a
 // narrow window is stored re-biased by 2^(c-2), so that every consumer reads  stored - 2^(c-1)  as the signed digit whatever the width.
+// top >= 0 (a plan without carry window, window_layout): K leaves row `top`, the last one, unbiased and its digit d in [0, 2^(cw-1)] is stored
+// NEGATED, as 2^(c-1) - d: magnitude, bucket and zero test are those of every other row, and the scatter flips the sign of that row's entries.
 __global__ void __launch_bounds__(256) k_digits(const uint32_t *__restrict__ scalars, uint64_t total, uint32_t n, uint32_t stride, int c,
-                                                int W, int acnt, RecodeK K, uint16_t *__restrict__ dig,
+                                                int W, int acnt, int top, RecodeK K, uint16_t *__restrict__ dig,
                                                 unsigned long long *__restrict__ negmask, uint32_t *__restrict__ zero, uint32_t nzero,
                                                 uint32_t *__restrict__ zero2, uint32_t nzero2) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -63,7 +65,8 @@ __global__ void __launch_bounds__(256) k_digits(const uint32_t *__restrict__ sca
     for (int w = 0; w < W; w++) {
       const int cw = w < acnt ? c : c - 1;
       const uint32_t bias = w < acnt ? 0u : (1u << (c - 2));
-      dig[base + (size_t)w * stride] = (uint16_t)(recode_next(sp, cw) + bias);
+      const uint32_t f = recode_next(sp, cw);
+      dig[base + (size_t)w * stride] = (uint16_t)(w == top ? (1u << (c - 1)) - f : f + bias);
     }
   }
   unsigned long long m = __ballot(valid && neg);
@@ -167,10 +170,11 @@ __global__ void __launch_bounds__(256) k_scan_apply(const uint32_t *__restrict__
 
 __global__ void k_scatter(const uint16_t *__restrict__ dig, const unsigned long long *__restrict__ negmask, uint32_t n, uint32_t stride, int c,
                           int CH, int W, const uint32_t *__restrict__ blockhist, const uint32_t *__restrict__ start,
-                          uint32_t *__restrict__ sorted, uint32_t flat_stride) {
+                          uint32_t *__restrict__ sorted, uint32_t flat_stride, int top) {
   extern __shared__ uint32_t lh[];
   const int M = 1 << (c - 1);
   const uint32_t nbw = blockIdx.x, ch = blockIdx.y;
+  const uint32_t flip = (int)(nbw % W) == top ? 1u : 0u;     // row `top` holds its digits negated (k_digits)
   const uint32_t *bh = blockhist + ((size_t)nbw * CH + ch) * M;
   // flat_stride != 0: the windows of an instance share one bucket set and the entry indexes the table row of its window
   const uint32_t *st = start + (size_t)(flat_stride ? nbw / W : nbw) * M;
@@ -194,7 +198,7 @@ __global__ void k_scatter(const uint16_t *__restrict__ dig, const unsigned long 
         uint64_t flat = flat0 + k;
         unsigned long long mw = ((flat >> 6) == (flat0 >> 6)) ? m0 : m1;
         uint32_t sneg = (uint32_t)((mw >> (flat & 63)) & 1ull);
-        uint32_t sg = (v < 0 ? 1u : 0u) ^ sneg;
+        uint32_t sg = (v < 0 ? 1u : 0u) ^ sneg ^ flip;
         uint32_t pos = atomicAdd(&lh[mb], 1u);
         sorted[pos] = (sg << 31) | (idx_base + j0 + k);   // 4 bytes: the bucket is implied by start[] (position -> bucket), not stored
       }
@@ -212,13 +216,14 @@ __global__ void k_scatter(const uint16_t *__restrict__ dig, const unsigned long 
 // positions; no workgroup waits for another.  The digit row is re-read Q times (non-temporal: it should not push the output lines out).
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 __global__ void k_scatter_ranges(const uint16_t *__restrict__ dig, const unsigned long long *__restrict__ negmask, uint32_t n, uint32_t stride,
-                                 int c, int CH, int Q, uint32_t U, const uint32_t *__restrict__ blockhist, const uint32_t *__restrict__ start,
-                                 uint32_t *__restrict__ sorted) {
+                                 int c, int CH, int Q, uint32_t U, int top, const uint32_t *__restrict__ blockhist,
+                                 const uint32_t *__restrict__ start, uint32_t *__restrict__ sorted) {
   extern __shared__ uint32_t lh[];
   const uint32_t M = 1u << (c - 1), Mq = M / (uint32_t)Q;
   const uint32_t s = blockIdx.x & 7u, k = blockIdx.x >> 3, u = (k / (uint32_t)CH) * 8u + s, ch = k % (uint32_t)CH;
   if (u >= U) return;                                       // the grid is padded to 8 slots x whole units
-  const uint32_t nbw = u / (uint32_t)Q, r0 = (u % (uint32_t)Q) * Mq;   // the (nearly empty) carry window's units come last
+  const uint32_t nbw = u / (uint32_t)Q, r0 = (u % (uint32_t)Q) * Mq;
+  const uint32_t flip = (int)nbw == top ? 1u : 0u;          // row `top` holds its digits negated (k_digits)
   const uint32_t *bh = blockhist + ((size_t)nbw * CH + ch) * M + r0;
   const uint32_t *st = start + (size_t)nbw * M + r0;
   for (uint32_t t = threadIdx.x; t < Mq; t += blockDim.x) lh[t] = st[t] + bh[t];
@@ -234,7 +239,7 @@ __global__ void k_scatter_ranges(const uint16_t *__restrict__ dig, const unsigne
       int v = (int)((w[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu) - (int)M;
       uint32_t mb = (uint32_t)(v < 0 ? -v : v) - 1u - r0;   // v == 0: wraps past Mq
       if (j0 + e < hi && v && mb < Mq) {
-        uint32_t sg = (v < 0 ? 1u : 0u) ^ ((sneg8 >> e) & 1u);
+        uint32_t sg = (v < 0 ? 1u : 0u) ^ ((sneg8 >> e) & 1u) ^ flip;
         uint32_t pos = atomicAdd(&lh[mb], 1u);
         sorted[pos] = (sg << 31) | (j0 + e);
       }
@@ -751,7 +756,7 @@ static constexpr size_t MSM_SMALL_DEFAULT_MAX = 8192;      // terms per MSM on t
                                                            // pays the ~17-operation reduction chain with most lanes idle, so the general pipeline wins from ~2^14 terms
                                                            // (benchmarks/sweep_small_msm.py: 858 terms 0.36 -> 0.21 ms, 4096 0.38 -> 0.27, 8192 0.40 -> 0.33, 22016 0.45 -> 0.43, 65536 0.52 -> 0.78)
 __global__ void __launch_bounds__(256) k_msm_small(const uint32_t *__restrict__ scalars_all, const uint32_t *__restrict__ points_all, uint32_t n_all, uint32_t slice_len,
-                                                   int c, int acnt, RecodeK K, uint32_t *__restrict__ winsum) {
+                                                   int c, int acnt, int top, RecodeK K, uint32_t *__restrict__ winsum) {
   // slice blockIdx.y of the terms: its own bucket set, its own partial window sum (k_msm_small_join adds the slices of a window)
   const uint32_t j0 = blockIdx.y * slice_len, n = min(slice_len, n_all - j0);
   const uint32_t *scalars = scalars_all + (size_t)j0 * 8, *points = points_all + (size_t)j0 * 16;
@@ -768,6 +773,7 @@ __global__ void __launch_bounds__(256) k_msm_small(const uint32_t *__restrict__ 
   const int cw = (int)w < acnt ? c : c - 1;
   const uint32_t bit0 = (int)w < acnt ? (uint32_t)c * w : (uint32_t)(c * acnt + (c - 1) * ((int)w - acnt)), mask = (1u << cw) - 1u;
   const int half = 1 << (cw - 1);
+  const uint32_t flip = (int)w == top ? 1u : 0u;                    // window `top` is unbiased: read negated with the sign flipped, as k_digits stores it
   for (uint32_t j = tid; j < n; j += 256) {
     uint32_t sp[9];
     const bool neg = recode_fold(fe_load(scalars + (size_t)j * 8), K, sp);
@@ -776,11 +782,11 @@ __global__ void __launch_bounds__(256) k_msm_small(const uint32_t *__restrict__ 
     for (int q = 0; q < 9; q++) if ((bit0 >> 5) == (uint32_t)q) { lo = sp[q]; hi = q < 8 ? sp[q + 1] : 0u; }
     const uint32_t sh = bit0 & 31u;
     const uint32_t d = (uint32_t)((((uint64_t)hi << 32) | lo) >> sh) & mask;
-    const int v = (int)d - half;
+    const int v = flip ? -(int)d : (int)d - half;
     uint16_t kx = 0xFFFFu;
     if (v) {
       const uint32_t mb = (uint32_t)(v < 0 ? -v : v) - 1u;
-      kx = (uint16_t)((mb << 1) | (((v < 0) != neg) ? 1u : 0u));
+      kx = (uint16_t)((mb << 1) | ((((v < 0) != neg) ? 1u : 0u) ^ flip));
       atomicAdd(&hist[mb], 1u);
     }
     key[j] = kx;
@@ -950,14 +956,15 @@ __global__ void __launch_bounds__(256) k_acc_points_lds(const uint32_t *__restri
 static int choose_window(size_t n, size_t batch, const MsmTune &tune) {
   // Cost model in units of one mixed addition (~68 ps chip-wide, measured at 2^20; profiles/):
   //   accumulate: one addition per (scalar, window that holds real bits): ceil(255/c) windows (+ half a window when
-  //               c divides 255: the top digit then wraps for half the scalars and a carry window appears);
+  //               c divides 255: the top digit then wraps for half the scalars and a carry window appears — the only widths
+  //               that still have one, window_layout);
   //   reduce:     ~10 per bucket (the wave-prefix bucket reduction is latency-bound; fitted at c = 13..16); ~3.5 per
   //               bucket for a large batch of small MSMs, which goes through k_reduce_groups (throughput-bound);
   //   heavy top:  when the top window has few real bits its buckets hold n / 2^r entries each and go through the
   //               wave-cooperative merge tree: a flat ~1.5e6 (0.1 ms) once they span many lanes.
   // One large MSM: the reduction is latency-bound and nearly flat in the bucket count (0.12 ms at c = 11 .. 0.26 ms at c = 16),
   // so the model above overprices wide windows; thresholds read off the (n, c, L) table of benchmarks/sweep_window.py
-  // (profiles/r02_window_sweep.txt): c = 16 has 17 windows against 20 at c = 13 and no heavy top window.
+  // (profiles/r02_window_sweep.txt): c = 16 has 16 windows (17 when that table was read, window_layout) against 20 at c = 13 and no heavy top window.
   // (re-read after the balanced windows of make_plan, which removed the heavy top window of every width that does not divide 256:
   // 9000-12000 terms 0.47 ms at c = 8 against 0.33 at c = 11; 22 016 terms 0.376 at c = 12; 43 782 terms 0.423 at c = 13)
   if (batch == 1 && n >= 4096) return n < 20000 ? 11 : n < 30000 ? 12 : n < 200000 ? 13 : 16;
@@ -965,7 +972,7 @@ static int choose_window(size_t n, size_t batch, const MsmTune &tune) {
   const int cmin = tune.cmin ? std::max(2, tune.cmin) : 4;
   double best = 1e300; int bc = 8;
   for (int c = cmin; c <= 16; c++) {
-    int W = 256 / c + 1, full = 254 / c, r = 255 - c * full;       // r = real bits in the top window (1..c)
+    int full = 254 / c, r = 255 - c * full, W = full + 1 + (r == c ? 1 : 0);   // r = real bits in the top window (1..c); W as window_layout's
     double weff = full + 1 + (r == c ? 0.5 : 0.0);
     const bool groups = c <= 9 && (double)batch * W >= 4096.0;
     double cost = weff * (double)n + (groups ? gcost : 10.0) * W * (double)(1u << (c - 1));
@@ -976,8 +983,29 @@ static int choose_window(size_t n, size_t batch, const MsmTune &tune) {
   return bc;
 }
 
+// The windows of a scalar over arbitrary points.  A folded scalar has 255 bits (recode.hip.h) and the signed digits carry upwards, so the top
+// window holds d in [0, 2^r] for its r real bits.  r <= cw - 2: d + 2^(cw-1) fits the window's cw bits as every other digit does.
+// r = cw - 1: only d = 2^(cw-1) does not, and rather than a further window for that one carry the top window is left unbiased and stored
+// negated (top = its index; k_digits, k_msm_small) — its largest magnitude is then the bucket of -2^(cw-1) that every window has.
+// r = cw (uniform widths, c divides 255): half of the scalars carry, the window above stays.
+//   balanced (one MSM, c does not divide 256): ceil(256 / c) windows, the first acnt c bits wide, the others c - 1; r = cw - 1 always;
+//   uniform: ceil(255 / c) windows, r = cw - 1 exactly when c divides 256 (16 windows at c = 16, 32 at c = 8), + 1 when c divides 255.
+// A registered basis (flat plans, basis.hip, comb.hip) keeps 256 / c + 1 biased rows: its tables are laid out by them.
+struct WindowLayout { int W, acnt, top; };
+static WindowLayout window_layout(int c, bool balanced) {
+  WindowLayout l;
+  if (balanced) {
+    l.W = (256 + c - 1) / c; l.acnt = 256 - l.W * (c - 1); l.top = l.W - 1;
+  } else {
+    const int T = (255 + c - 1) / c, r = 255 - c * (T - 1);
+    l.W = T + (r == c ? 1 : 0); l.acnt = l.W; l.top = r == c - 1 ? l.W - 1 : -1;
+  }
+  return l;
+}
+
 struct MsmPlan {
   size_t n, batch; int c, W, acnt, M, CH, hist_threads, Lw, WPW;   // acnt: windows [0, acnt) are c bits wide, the others c - 1
+  int top;                     // the digit row stored negated (window_layout), -1: none
   bool flat;                   // precomputed table 2^(c w) P_i: all windows of an instance share ONE bucket set
   int Wc;                      // windows left for the window combine (1 when flat)
   uint64_t NB, NS, FB, total_max;   // digit rows (batch * W), bucket sets (batch * W, or batch when flat), buckets, sorted entries
@@ -992,15 +1020,14 @@ struct MsmPlan {
 static MsmPlan make_plan(size_t n, size_t batch, int c, bool flat, const MsmTune &tune) {
   MsmPlan p;
   p.n = n; p.batch = batch; p.c = c; p.W = 256 / c + 1; p.M = 1 << (c - 1);
-  p.acnt = p.W;
+  p.acnt = p.W; p.top = -1;
   // Balanced windows (one MSM over arbitrary points, c not a divisor of 256): with uniform widths the top window holds only
   // 256 - c floor(256 / c) real bits, i.e. a few buckets with n / 2^r entries each — the "heavy" merges (0.05 ms at 2^16 terms, c = 13:
   // 256 buckets of 256 entries).  Instead ceil(256 / c) windows of widths c (the low ones) and c - 1 share the 256 bits, so every
-  // window's buckets are evenly filled; the extra top window only catches the carry of the rare scalars within 2^-(c-2) of 2^255.
-  if (batch == 1 && !flat && c >= 3 && 256 % c != 0 && !tune.no_balance) {
-    const int Wr = (256 + c - 1) / c;
-    p.acnt = 256 - Wr * (c - 1);
-    p.W = Wr + 1;
+  // window's buckets are evenly filled.
+  if (!flat) {
+    const WindowLayout l = window_layout(c, batch == 1 && c >= 3 && 256 % c != 0 && !tune.no_balance);
+    p.W = l.W; p.acnt = l.acnt; p.top = l.top;
   }
   p.flat = flat; p.Wc = flat ? 1 : p.W;
   p.NB = (uint64_t)batch * p.W; p.NS = flat ? batch : p.NB; p.FB = p.NS * p.M; p.total_max = p.NB * n;
@@ -1119,8 +1146,8 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
   const size_t small_max = ctx->tune.small_max ? (size_t)ctx->tune.small_max : MSM_SMALL_DEFAULT_MAX;
   if (batch == 1 && !table_stride && !window_bits && n <= small_max && !ctx->tune.no_small && !d_out_dev) {
     const int c = ctx->tune.small_c >= 5 && ctx->tune.small_c <= 8 ? ctx->tune.small_c : 6, M = 1 << (c - 1);
-    const bool bal = 256 % c != 0 && !ctx->tune.no_balance;
-    const int Wr = (256 + c - 1) / c, acnt = bal ? 256 - Wr * (c - 1) : 256 / c + 1, W = bal ? Wr + 1 : 256 / c + 1;
+    const WindowLayout wl = window_layout(c, 256 % c != 0 && !ctx->tune.no_balance);
+    const int W = wl.W, acnt = wl.acnt;
     size_t len = ctx->tune.small_len >= 64 && ctx->tune.small_len <= (int)MSM_SMALL_MAX ? (size_t)ctx->tune.small_len : (n <= 2048 ? 512 : 1024);
     if (n <= len + len / 2) len = n;                                  // a second slice has to pay for the join launch
     const size_t S = (n + len - 1) / len;
@@ -1132,11 +1159,12 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
     const size_t bytes = (size_t)W * XYZZ_WORDS * 4;
     rc = ensure_pinned(ctx, bytes); if (rc) return rc;
     hipStream_t st = ctx->stream;
+    ctx->last_windows = W;
     for (int i = 0; i <= 2; i++) prof_mark(ctx, i);
     if (ctx->pre_acc) { auto f = ctx->pre_acc; ctx->pre_acc = nullptr; int rc_ = f(ctx->pre_acc_arg); if (rc_) return rc_; }
     const size_t lds = (((size_t)(2 * M + 1) + len + (len + 1) / 2 + 3) & ~(size_t)3) * 4 + (size_t)(M + 4) * XYZZ_WORDS * 4;
     k_msm_small<<<dim3((unsigned)W, (unsigned)S), dim3(256), lds, st>>>((const uint32_t *)d_scalars, (const uint32_t *)d_points, (uint32_t)n, (uint32_t)len, c,
-                                                                       acnt, make_recode_k(c, W, acnt), S > 1 ? partials : winsum);
+                                                                       acnt, wl.top, make_recode_k(c, W, acnt, wl.top >= 0), S > 1 ? partials : winsum);
     if (S > 1) k_msm_small_join<<<dim3((unsigned)W), dim3(64), 0, st>>>(partials, (uint32_t)S, winsum);
     for (int i = 3; i <= 5; i++) prof_mark(ctx, i);
     BPPP_HIP(ctx, hipMemcpyAsync(ctx->pinned, winsum, bytes, hipMemcpyDeviceToHost, st));
@@ -1215,8 +1243,8 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
     prof_mark(ctx, 0);
     // 1. digits
     uint64_t total_sc = (uint64_t)batch * n;
-    k_digits<<<dim3((unsigned)((total_sc + 255) / 256)), dim3(256), 0, st>>>((const uint32_t *)d_scalars, total_sc, (uint32_t)n, stride, c, p.W, p.acnt,
-                                                                            make_recode_k(c, p.W, p.acnt), dig, negmask, heavy_count, (uint32_t)nzero, tiles, (uint32_t)p.ntiles);
+    k_digits<<<dim3((unsigned)((total_sc + 255) / 256)), dim3(256), 0, st>>>((const uint32_t *)d_scalars, total_sc, (uint32_t)n, stride, c, p.W, p.acnt, p.top,
+                                                                            make_recode_k(c, p.W, p.acnt, p.top >= 0), dig, negmask, heavy_count, (uint32_t)nzero, tiles, (uint32_t)p.ntiles);
     prof_mark(ctx, 1);
     // 2. sort
     k_hist<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(dig, (uint32_t)n, stride, c, p.CH, blockhist);
@@ -1224,13 +1252,14 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
     k_count_tiles<<<dim3((unsigned)((p.FB + 255) / 256)), dim3(256), 0, st>>>(blockhist, p.M, p.flat ? p.W * p.CH : p.CH, p.FB, count, tiles);
     k_scan_apply<<<dim3(p.ntiles), dim3(256), 0, st>>>(count, p.FB, tiles, start, size_hist);
     ctx->last_sort_ranges = p.Q;
+    ctx->last_windows = p.W;
     if (p.Q) {
       const uint32_t U = (uint32_t)p.W * p.Q;                // units (window, range); 8 slots x ceil(U / 8) units x CH chunks
       k_scatter_ranges<<<dim3(8u * ((U + 7) / 8) * p.CH), dim3(p.hist_threads), lds / p.Q, st>>>(dig, negmask, (uint32_t)n, stride, c, p.CH, p.Q, U,
-                                                                                                 blockhist, start, sorted);
+                                                                                                 p.top, blockhist, start, sorted);
     } else
       k_scatter<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(dig, negmask, (uint32_t)n, stride, c, p.CH, p.W, blockhist, start, sorted,
-                                                                               p.flat ? (uint32_t)table_stride : 0u);
+                                                                               p.flat ? (uint32_t)table_stride : 0u, p.top);
     prof_mark(ctx, 2);
     // 3. accumulate
     ctx->last_acc_lds = ctx->tune.acc_lds ? 1 : 0;

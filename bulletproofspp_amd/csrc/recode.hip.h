@@ -3,6 +3,13 @@
 // A scalar s is folded as reduceScalar does (Commitment.hs:276-279): s > n - s takes n - s and the negated point.  Adding the bias
 // K = sum_w 2^(cw-1) 2^(off_w) to the folded value turns every signed window digit into an unsigned cw-bit field f of the 9-limb sum
 // sp: the digit is f - 2^(cw-1), and the windows are peeled off from the bottom (recode_next).
+//
+// The top window may be left unbiased (make_recode_k's top_unbiased).  The folded value is v <= (n - 1) / 2 < 2^255, and the biases below the
+// top window, which starts at bit off, sum to less than 2^off: what is left for the top window is d = (v + K) >> off <= 2^(255 - off), never
+// negative.  With the bias a top window of cw = 255 - off + 1 bits overflows in the one case d = 2^(cw-1) and needs a further window for
+// the carry; without it d itself is the digit, fits the cw bits, and its largest magnitude 2^(cw-1) is that of the digit -2^(cw-1) of any
+// other window.  The windows then cover 256 bits or more and v + K < 2^255 + 2^off <= 2^256: after the last recode_next sp is zero, sp[8]
+// included.
 #pragma once
 #include <string.h>
 #include "fe.hip.h"
@@ -11,12 +18,13 @@ namespace bppp {
 
 struct RecodeK { uint32_t k[9]; };
 
-// K = sum_{w<W} 2^(cw-1) 2^(off_w) as 9 x 32-bit limbs: the first `acnt` windows are c bits wide, the others c - 1 (balanced widths; acnt < 0: all c)
-inline RecodeK make_recode_k(int c, int W, int acnt = -1) {
+// K = sum_{w<W} 2^(cw-1) 2^(off_w) as 9 x 32-bit limbs: the first `acnt` windows are c bits wide, the others c - 1 (balanced widths; acnt < 0: all c);
+// top_unbiased: the sum stops before window W - 1, whose field is then the (non-negative) digit itself
+inline RecodeK make_recode_k(int c, int W, int acnt = -1, bool top_unbiased = false) {
   RecodeK K; memset(&K, 0, sizeof K);
   if (acnt < 0) acnt = W;
   int off = 0;
-  for (int w = 0; w < W; w++) {
+  for (int w = 0; w < W - (top_unbiased ? 1 : 0); w++) {
     const int cw = w < acnt ? c : c - 1, bit = off + cw - 1;
     if (bit < 288) K.k[bit >> 5] |= 1u << (bit & 31);
     off += cw;

@@ -258,6 +258,12 @@ extern "C" int bppp_test_last_acc_sized(bppp_ctx *ctx, int *sized) {
   return BPPP_OK;
 }
 
+extern "C" int bppp_test_last_windows(bppp_ctx *ctx, int *windows) {
+  if (!ctx || !windows) return BPPP_ERR_ARG;
+  *windows = ctx->last_windows;
+  return BPPP_OK;
+}
+
 extern "C" int bppp_test_rp_last_verify_counts(bppp_rp *rp, uint64_t *combined_msms, uint64_t *each_passes) {
   if (!rp || !combined_msms || !each_passes) return BPPP_ERR_ARG;
   *combined_msms = rp->n_combined;

@@ -45,6 +45,9 @@ int bppp_test_last_sort_ranges(bppp_ctx *ctx, int *q);
  * k_acc_points_sized; BPPP_ACC_SIZED, one MSM over arbitrary points only), 0 = slices of the sorted entries (k_acc_points, k_merge),
  * -1 = none yet. */
 int bppp_test_last_acc_sized(bppp_ctx *ctx, int *sized);
+/* The windows (digit rows per scalar) of the plan of the last MSM on this context, the small route included: 16 with 16-bit windows, where
+ * the top window is stored negated instead of carrying into a 17th; 256 / c + 1 for a registered basis; -1 = none yet. */
+int bppp_test_last_windows(bppp_ctx *ctx, int *windows);
 /* What the last verification on this handle ran (bppp_rp_verify_batch*, _shard_device, _each*, and its group's share of
  * bppp_rp_verify_mixed*): combined MSMs (the accept check and every bisection step) and per-proof passes.  A test sees the cost of a
  * culprit search without timing it. */
