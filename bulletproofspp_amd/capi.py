@@ -215,7 +215,20 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_points_from_seed_chunked.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, sz, vp, C.POINTER(C.c_uint64)]
     lib.bppp_test_seed_lift_digests.argtypes = [vp, C.c_char_p, sz, vp, vp, vp]
     lib.bppp_test_rp_decode_device.argtypes = [vp, sz, C.c_char_p, C.c_char_p, vp, vp, vp, vp, vp, vp]
+    lib.bppp_test_comb_create.argtypes = [vp, vp, sz, i, C.POINTER(vp)]
+    lib.bppp_test_comb_destroy.argtypes = [vp]
+    lib.bppp_test_comb_destroy.restype = None
+    lib.bppp_test_comb_msm.argtypes = [vp, vp, sz, sz, i, sz, vp]
+    lib.bppp_test_comb_groups.argtypes = [vp, vp, sz, sz, sz, i, sz, vp]
+    lib.bppp_test_comb_lanes.argtypes = [vp, vp, sz, sz, vp]
+    lib.bppp_test_last_comb_msm.argtypes = [vp, C.POINTER(TestCombReport)]
     return lib
+
+
+class TestCombReport(C.Structure):
+    """bppp_test_comb_report (include/bppp_test.h): what the last comb_msm launch on a context did"""
+    __test__ = False                      # not a pytest class
+    _fields_ = [("route", C.c_int32), ("heavy_first", C.c_int32)] + [(n, C.c_uint32) for n in ("parts", "tparts", "wsplit", "chunks", "clen", "join_lanes")]
 
 
 class RpRange(C.Structure):

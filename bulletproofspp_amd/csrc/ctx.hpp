@@ -14,6 +14,14 @@ struct MsmTune {
   void from_env();
 };
 
+// What the last comb_msm launch on a context did (csrc/comb.hip.h; read by bppp_test_last_comb_msm): the kernel it took and how it split the work
+struct CombLast {
+  int route = -1;                    // -1 none yet, 0 k_comb_msm (wavefront per instance), 1 / 2 k_comb_msm_packed<8 / 16>, 3 k_comb_msm_rows, 4 the same with pairs
+  int heavy_first = 0;               // k_comb_msm: the heavy instances of the pairs dispatched first
+  uint32_t parts = 0, tparts = 0, wsplit = 0;         // k_comb_msm: wavefronts per instance = term parts x window ranges
+  uint32_t chunks = 0, clen = 0, join_lanes = 0;      // rows: partial sums per instance, terms of each, lanes per instance of k_comb_join_rows
+};
+
 struct bppp_ctx {
   MsmTune tune;
   // Lifetime: the caller's handle holds one reference, every child handle (bppp_nl, bppp_nlb, bppp_ip, bppp_trrp, bppp_basis,
@@ -58,6 +66,7 @@ struct bppp_ctx {
   int last_sort_ranges = -1;         // bucket ranges Q of the last general-pipeline MSM's scatter: 0 k_scatter, 2 / 4 k_scatter_ranges (bppp_test_last_sort_ranges)
   int last_acc_sized = -1;           // 1: the last general-pipeline MSM accumulated whole buckets by size (k_order, k_acc_points_sized), 0: slices (bppp_test_last_acc_sized)
   int last_windows = -1;             // digit rows W per scalar of the last MSM's plan, either route (bppp_test_last_windows)
+  CombLast last_comb;                // the last comb_msm launch (bppp_test_last_comb_msm)
   size_t sort_lds_set = 0;           // largest dynamic-LDS size set on the MSM's sort kernels (hipFuncSetAttribute once, not per call)
 };
 

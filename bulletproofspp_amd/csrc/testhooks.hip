@@ -10,6 +10,7 @@
 #include "rpwitness.hip.h"
 #include "rpdecode.hip.h"
 #include "seedpoints.hip.h"
+#include "comb.hip.h"
 
 namespace bppp {
 template <int MOD> BPPP_DI fe apply_op(int op, const fe &a, const fe &b) {
@@ -394,4 +395,69 @@ extern "C" int bppp_test_seed_lift_digests(bppp_ctx *ctx, const uint8_t *digests
   if (hipStreamSynchronize(st) != hipSuccess) ok = false;
   hipFree(d);
   return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_seed_lift_digests: kernel or copy failed");
+}
+
+// ---- the fixed-base comb's launchers (csrc/comb.hip.h) on a table of the test's own: every route of comb_msm, comb_groups, comb_lanes
+struct bppp_test_comb { bppp::CombTable t; };
+
+extern "C" int bppp_test_comb_create(bppp_ctx *ctx, const void *d_points, size_t T, int window_bits, bppp_test_comb **out) {
+  if (!ctx || !d_points || !T || !out || T >= (1u << 24)) return BPPP_ERR_ARG;
+  if (window_bits < 4 || window_bits > 18) return bppp::fail(ctx, BPPP_ERR_ARG, "test_comb_create: window_bits must be in [4,18]");
+  hipSetDevice(ctx->device);
+  bppp_test_comb *h = new bppp_test_comb();
+  CombTable &t = h->t;
+  const int c = window_bits;
+  t.ctx = ctx; t.T = T; t.c = c; t.W = (257 + c - 1) / c; t.D = 1 << (c - 1); t.tab = nullptr; t.bytes = comb_table_bytes(c, T);
+  const std::string err = comb_fill(&t, (const uint32_t *)d_points);
+  if (!err.empty()) { (void)hipGetLastError(); delete h; return bppp::fail(ctx, BPPP_ERR_HIP, err); }
+  *out = h;
+  return BPPP_OK;
+}
+extern "C" void bppp_test_comb_destroy(bppp_test_comb *h) {
+  if (!h) return;
+  hipSetDevice(h->t.ctx->device);
+  hipStreamSynchronize(h->t.ctx->stream);
+  if (h->t.tab) hipFree(h->t.tab);
+  delete h;
+}
+// out (host, `words` uint64): uploaded, handed to `launch` as the device result array, downloaded again
+template <typename F> static int comb_hook_run(bppp_ctx *ctx, uint64_t *out, size_t words, size_t scratch_bytes, const char *what, F launch) {
+  hipSetDevice(ctx->device);
+  hipStream_t st = ctx->stream;
+  uint32_t *d_out = nullptr, *d_scratch = nullptr;
+  if (hipMalloc(&d_out, words * 8) != hipSuccess || (scratch_bytes && hipMalloc(&d_scratch, scratch_bytes) != hipSuccess)) {
+    (void)hipGetLastError(); hipFree(d_out);
+    return bppp::fail(ctx, BPPP_ERR_HIP, std::string(what) + ": hipMalloc failed");
+  }
+  int rc = hipMemcpyAsync(d_out, out, words * 8, hipMemcpyHostToDevice, st) == hipSuccess ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, std::string(what) + ": upload failed");
+  if (!rc) rc = launch(d_out, d_scratch, st);
+  if (!rc && hipMemcpyAsync(out, d_out, words * 8, hipMemcpyDeviceToHost, st) != hipSuccess) rc = bppp::fail(ctx, BPPP_ERR_HIP, std::string(what) + ": download failed");
+  if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = bppp::fail(ctx, BPPP_ERR_HIP, std::string(what) + ": kernel or copy failed");
+  hipFree(d_out); hipFree(d_scratch);
+  return rc;
+}
+extern "C" int bppp_test_comb_msm(bppp_test_comb *h, const void *d_scalars, size_t ninst, size_t nterms, int rows_hint, size_t scratch_bytes, uint64_t *out) {
+  if (!h || !d_scalars || !out || !ninst || ninst >= (1u << 31) || nterms > h->t.T || rows_hint < COMB_ROWS_ANY || rows_hint > COMB_ROWS_DENSE) return BPPP_ERR_ARG;
+  return comb_hook_run(h->t.ctx, out, ninst * 8, scratch_bytes, "test_comb_msm", [&](uint32_t *d_out, uint32_t *d_scratch, hipStream_t st) {
+    return comb_msm_launch(&h->t, (const uint32_t *)d_scalars, ninst, d_out, st, rows_hint, nterms, d_scratch, scratch_bytes);
+  });
+}
+extern "C" int bppp_test_comb_groups(bppp_test_comb *h, const void *d_scalars, size_t ninst, size_t l0, size_t n0, int L, size_t out_stride, uint64_t *out) {
+  if (!h || !d_scalars || !out || !ninst || ninst >= (1u << 24) || !out_stride || out_stride >= (1u << 24)) return BPPP_ERR_ARG;
+  return comb_hook_run(h->t.ctx, out, ninst * out_stride * 8, 0, "test_comb_groups", [&](uint32_t *d_out, uint32_t *, hipStream_t st) {
+    return comb_groups_launch(&h->t, (const uint32_t *)d_scalars, ninst, l0, n0, L, d_out, out_stride, st);
+  });
+}
+extern "C" int bppp_test_comb_lanes(bppp_test_comb *h, const void *d_scalars, size_t nterms, size_t ninst, uint64_t *out) {
+  if (!h || !d_scalars || !out || !ninst || ninst >= (1u << 31) || !nterms || nterms > h->t.T) return BPPP_ERR_ARG;
+  return comb_hook_run(h->t.ctx, out, ninst * 8, 0, "test_comb_lanes", [&](uint32_t *d_out, uint32_t *, hipStream_t st) {
+    return comb_lanes_launch(&h->t, (const uint32_t *)d_scalars, nterms, ninst, d_out, st);
+  });
+}
+extern "C" int bppp_test_last_comb_msm(bppp_ctx *ctx, bppp_test_comb_report *r) {
+  if (!ctx || !r) return BPPP_ERR_ARG;
+  const CombLast &l = ctx->last_comb;
+  r->route = l.route; r->heavy_first = l.heavy_first; r->parts = l.parts; r->tparts = l.tparts; r->wsplit = l.wsplit;
+  r->chunks = l.chunks; r->clen = l.clen; r->join_lanes = l.join_lanes;
+  return BPPP_OK;
 }

@@ -89,6 +89,30 @@ int bppp_test_seed_lift_digests(bppp_ctx *ctx, const uint8_t *digests, size_t n,
  * slot the kernels did not write shows. */
 int bppp_test_rp_decode_device(bppp_rp *rp, size_t batch, const uint8_t *coms, const uint8_t *proofs, uint64_t *init_pts, uint64_t *resp_pts, uint64_t *wit_norm,
                                uint64_t *wit_lin, uint32_t *bad, uint32_t *any_bad);
+/* The fixed-base comb (csrc/comb.hip.h) on a table of the test's own, so that every route of its launchers runs at small shapes.
+ * bppp_test_comb_create: the table of T affine points in HBM ([T][8] words, all zero = infinity) at window_bits in [4, 18], as the product's
+ * comb_create builds it; it borrows ctx (destroy the table first).  The tuning is the context's (BPPP_COMB_ROWS_MIN_MB, BPPP_COMB_ROWS_WAVES
+ * when the context was created).  d_scalars: canonical scalars in HBM.  out: HOST words, uploaded before the launch and downloaded after it,
+ * so a slot the kernels did not write keeps what the caller put there.
+ *   _msm     comb_msm: d_scalars [ninst][nterms] over the first nterms <= T points (0 = T), rows_hint 0 any / 1 pairs / 2 dense, a scratch of
+ *            exactly scratch_bytes (0: none); out [ninst][8]
+ *   _groups  comb_groups: d_scalars [ninst][1 + l0 + n0], out [ninst][out_stride][8] (slot 1 + q = group q of 2^L points; slot 0 and the slots past
+ *            the groups are not written)
+ *   _lanes   comb_lanes: d_scalars [ninst][nterms], out [ninst][8]
+ * What the launchers refuse (nterms > T, 1 + l0 + n0 > T, L outside [1, 20], a stride below 1 + the groups) comes back as their BPPP_ERR_ARG: nothing
+ * was launched and out is left as it was. */
+typedef struct bppp_test_comb bppp_test_comb;
+int bppp_test_comb_create(bppp_ctx *ctx, const void *d_points, size_t T, int window_bits, bppp_test_comb **out);
+void bppp_test_comb_destroy(bppp_test_comb *tab);
+int bppp_test_comb_msm(bppp_test_comb *tab, const void *d_scalars, size_t ninst, size_t nterms, int rows_hint, size_t scratch_bytes, uint64_t *out);
+int bppp_test_comb_groups(bppp_test_comb *tab, const void *d_scalars, size_t ninst, size_t l0, size_t n0, int L, size_t out_stride, uint64_t *out);
+int bppp_test_comb_lanes(bppp_test_comb *tab, const void *d_scalars, size_t nterms, size_t ninst, uint64_t *out);
+/* What the last comb_msm launch on this context did, the product's own calls included.  route: -1 none yet, 0 k_comb_msm (a wavefront, or
+ * parts = tparts x wsplit of them, per instance; heavy_first: the even instances dispatched first), 1 / 2 k_comb_msm_packed with 8 / 16 lanes
+ * per instance, 3 k_comb_msm_rows (lane = instance: chunks partial sums of clen terms per instance, k_comb_join_rows with join_lanes lanes per
+ * instance), 4 the same with the instances dispatched as pairs.  Fields of the other routes are 0. */
+typedef struct bppp_test_comb_report { int32_t route, heavy_first; uint32_t parts, tparts, wsplit, chunks, clen, join_lanes; } bppp_test_comb_report;
+int bppp_test_last_comb_msm(bppp_ctx *ctx, bppp_test_comb_report *report);
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -114,7 +114,8 @@ def test_lane_per_instance_comb_rows_write_the_same_files(monkeypatch, oracle_li
     """round 4: >= 1024 long rows of full-width scalars (the argument's X / R rows, the blinded phase rows) over a large comb table run with one LANE
     per instance (k_comb_msm_rows + k_comb_join_rows, csrc/comb.hip) — another schedule of the same sums.  examples/64by64, 1030 proofs (2060 round
     rows in heavy / light pairs, 1030 dense phase rows: neither a multiple of 64), on a context where every table qualifies (BPPP_COMB_ROWS_MIN_MB=0):
-    proof 0 is the oracle backend's byte for byte, and the batch equals the one a context with the route switched off writes."""
+    proof 0 is the oracle backend's byte for byte, and the batch equals the one a context with the route switched off writes.
+    (Route by route, every instance against an independent reference: tests/test_gpu_comb_routes.py.)"""
     import bulletproofspp_amd as b
     schema = _schema("64by64", False)
     st_o = RP.setup_from_schema(OracleBackend(oracle_lib), schema)
@@ -139,7 +140,8 @@ def test_lane_per_instance_comb_rows_write_the_same_files(monkeypatch, oracle_li
 
 
 def test_lane_per_instance_comb_rows_binary_shape(monkeypatch):
-    """the same at the 64 x 64-bit BINARY shape (rows of 4099 terms; 1027 proofs: 2054 round rows, 1027 dense rows of the blinding commitment)"""
+    """the same at the 64 x 64-bit BINARY shape (rows of 4099 terms; 1027 proofs: 2054 round rows, 1027 dense rows of the blinding commitment).
+    (The rows route and comb_groups on their own, every instance against an independent reference: tests/test_gpu_comb_routes.py.)"""
     import bulletproofspp_amd as b
     from bulletproofspp_amd import rangeproof_binary as BRP
     count, amount, B = 64, 10000, 1027
