@@ -16,6 +16,9 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib")
 HIP_SOURCES = ["msm.hip", "basis.hip", "comb.hip", "fold.hip", "rounds.hip", "nl.hip", "nlb.hip", "nlbatch.hip", "ip.hip", "trrp.hip", "rp.hip", "rpmixed.hip", "rpshare.hip", "rpeach.hip", "rpbind.hip", "rpcommit.hip", "rptally.hip", "rpprove.hip", "rpprove_dev.hip", "rpwitness.hip", "rpp_transcript.hip", "ipb.hip", "ipb_host.hip", "brpprove.hip", "brpprove_dev.hip", "glv.hip", "seedpoints.hip", "capi.hip"]
 TEST_SOURCES = ["testhooks.hip"]
+# product objects linked into the test library a second time: the hooks that drive RppTranscript and rpp_draws (csrc/rpp_transcript.hip, with the
+# bound headers of csrc/rpbind.hip) need the code itself, and the product library exports nothing but its C ABI
+TEST_SHARED_SOURCES = ["rpp_transcript.hip", "rpbind.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"] + os.environ.get("BPPP_EXTRA_FLAGS", "").split()
 
@@ -55,7 +58,7 @@ def build_hip(force: bool = False, verbose: bool = True) -> str:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
     tout = os.path.join(LIB, "libbppp_hip_test.so")
-    tobjs = [os.path.join(LIB, "obj", s.replace(".hip", ".o")) for s in TEST_SOURCES]
+    tobjs = [os.path.join(LIB, "obj", s.replace(".hip", ".o")) for s in TEST_SOURCES + TEST_SHARED_SOURCES]
     if force or jobs or _newer(tout, tobjs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(CSRC, "exports.map"), "-o", tout] + tobjs
         if verbose:

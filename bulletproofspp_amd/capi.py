@@ -222,6 +222,9 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_comb_groups.argtypes = [vp, vp, sz, sz, sz, i, sz, vp]
     lib.bppp_test_comb_lanes.argtypes = [vp, vp, sz, sz, vp]
     lib.bppp_test_last_comb_msm.argtypes = [vp, C.POINTER(TestCombReport)]
+    lib.bppp_test_rp_last_text_kernel.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.bppp_test_rpp_transcript.argtypes = [vp, sz, vp, sz, vp, vp, vp]
+    lib.bppp_test_rpp_draws.argtypes = [vp, C.c_char_p, sz, sz, sz, vp]
     return lib
 
 
@@ -229,6 +232,12 @@ class TestCombReport(C.Structure):
     """bppp_test_comb_report (include/bppp_test.h): what the last comb_msm launch on a context did"""
     __test__ = False                      # not a pytest class
     _fields_ = [("route", C.c_int32), ("heavy_first", C.c_int32)] + [(n, C.c_uint32) for n in ("parts", "tparts", "wsplit", "chunks", "clen", "join_lanes")]
+
+
+class TestRppCall(C.Structure):
+    """bppp_test_rpp_call (include/bppp_test.h): one oracle call of bppp_test_rpp_transcript"""
+    __test__ = False
+    _fields_ = [("points", C.c_uint32), ("count", C.c_uint32), ("first_slot", C.c_uint32)]
 
 
 class RpRange(C.Structure):

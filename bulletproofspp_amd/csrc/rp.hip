@@ -136,6 +136,16 @@ __global__ void __launch_bounds__(256) k_rp_text_lds(RpDims D, const uint32_t *_
   for (uint32_t i = tid; i < n16; i += 256) dst[i] = src[i];
 }
 
+// the text of B proofs on the context's stream: through LDS while the image fits the 64 KiB a workgroup may ask for (npts <= 272)
+static void rp_text_launch(bppp_rp *rp, size_t B, const uint32_t *init_pts, const uint32_t *resp_pts, uint8_t *text, uint32_t *text_off) {
+  const RpDims &D = rp->D;
+  hipStream_t st = rp->ctx->stream;
+  const bool lds = rp_text_lds_bytes(D) <= 64 * 1024;
+  rp->last_text_kernel = lds ? 1 : 0;
+  if (lds) k_rp_text_lds<<<dim3((unsigned)B), dim3(256), rp_text_lds_bytes(D), st>>>(D, init_pts, resp_pts, text, text_off);
+  else k_rp_text<<<dim3((unsigned)B), dim3(256), (rp_npts(D) + 1) * 4, st>>>(D, init_pts, resp_pts, text, text_off);
+}
+
 // ------------------------------------------------------------------------------------------------ hashing
 // Hash h of a proof (h < 7 + k):  0,1,2 -> e, x, r0   first oracle call  [dmCom, mCom] ++ nComs      (TypedReciprocal.hs:459)
 //                                 3,4,5 -> q, x', r1  second call, rCom prepended                    (:460)
@@ -870,8 +880,7 @@ int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const Rp
     uint64_t *hch = (uint64_t *)(htext + tbytes + obytes), *hes = hch + n_hch;
     { int rcb = rp_bind_host(rp); if (rcb) return rcb; }      // a bound call: every proof's oracle takes tag <> binding_b
     LapTimer timer(rp->opt.timing, "[rp_verify]", true);
-    if (rp_text_lds_bytes(D) <= 64 * 1024) k_rp_text_lds<<<dim3((unsigned)B), dim3(256), rp_text_lds_bytes(D), st>>>(D, init_pts, resp_pts, text, text_off);
-    else k_rp_text<<<dim3((unsigned)B), dim3(256), (npts + 1) * 4, st>>>(D, init_pts, resp_pts, text, text_off);
+    rp_text_launch(rp, B, init_pts, resp_pts, text, text_off);
     BPPP_HIP(ctx, hipMemcpyAsync(hoff, text_off, B * (npts + 1) * 4, hipMemcpyDeviceToHost, st));
     BPPP_HIP(ctx, hipMemcpyAsync(htext, text, B * (size_t)D.text_stride, hipMemcpyDeviceToHost, st));
     BPPP_HIP(ctx, hipStreamSynchronize(st));
@@ -899,8 +908,7 @@ int rp_verify_prepare(bppp_rp *rp, size_t batch, uint64_t index_offset, const Rp
     // (Round-2 measurement with the 8 x 32-limb scalar kernels had the fork ahead up to 1024 proofs, 256 proofs 1.65 -> 1.38 ms; with the
     // 10 x 26 kernels of round 3 the crossover fell to ~64.  At 4096 proofs the three kernels already fill the VALU and side by side
     // each only stretches: hash 0.65 -> 0.55 + 0.87, scalars 0.84 -> 1.04 ms: measured, not kept.)
-    if (rp_text_lds_bytes(D) <= 64 * 1024) k_rp_text_lds<<<dim3((unsigned)B), dim3(256), rp_text_lds_bytes(D), st>>>(D, init_pts, resp_pts, text, text_off);
-    else k_rp_text<<<dim3((unsigned)B), dim3(256), (npts + 1) * 4, st>>>(D, init_pts, resp_pts, text, text_off);
+    rp_text_launch(rp, B, init_pts, resp_pts, text, text_off);
     // a bound call: the headers of every (hash kind, proof) first, on `st` ahead of the fork, so both hashing halves find them written
     const uint32_t *bhdr = nullptr;
     if (rp->bind.on()) { int rcb = rp_bound_headers(rp, B, (const uint32_t *)rp->d_plan, RpHdrLayout{1, (uint32_t)(sizeof(HashPlan) / 4), RP_HDR_MAX / 4}, rp->nhash, &bhdr); if (rcb) return rcb; }

@@ -185,6 +185,7 @@ struct bppp_rp {
   void *ework = nullptr; size_t ework_bytes = 0;
   size_t each_chunk = 0;
   uint64_t n_combined = 0, n_each = 0;
+  int last_text_kernel = -1;         // transcript text kernel of the last verification on this handle: 0 k_rp_text, 1 k_rp_text_lds (bppp_test_rp_last_text_kernel)
   // the tally entry points (csrc/rptally.hip): the longest sum one lane walks alone, the entries of one workgroup's piece of a longer sum, and
   // the entries (and sums) of one pass over the workspace; test hooks lower them so that small jobs straddle them (include/bppp_test.h)
   size_t tally_short_max = 16, tally_piece = 4096, tally_chunk = (size_t)1 << 22;

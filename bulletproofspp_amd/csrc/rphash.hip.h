@@ -74,51 +74,15 @@ BPPP_DI uint32_t rp_msg_word(const uint32_t *hdr_be, uint32_t hlen, const uint8_
 }
 
 // SHA-256 (hdr <> tx[0 .. tlen)), digest -> Fr by Binary (Prime p) (src/Encoding.hs:75-79), toP.  hdr_be: the header (<= 64 bytes) as 16
-// big-endian words, zero-padded, in global memory; tx: any alignment, readable from 4 bytes before it to 8 bytes past its end
-// (the callers' buffers have that slack).
-BPPP_DI fe rp_hash_to_fr(const uint32_t *hdr_be, uint32_t hlen, const uint8_t *tx, uint32_t tlen) {
-  uint32_t st[8];
-  sha256_init(st);
-  uint32_t w[16];
-  const uint32_t mlen = hlen + tlen;
-  const uint32_t nblk = (mlen + 9 + 63) / 64;
-  // Interior blocks (all 64 bytes inside the text) are read as 17 aligned dwords and shifted into place.  One wavefront per
-  // SIMD is all this kernel gets at batch sizes of a few thousand (15 hashes per proof), so nothing else hides the load latency:
-  // the dwords of block k + 1 are requested BEFORE block k is compressed.
-  const uint32_t first_fast = (hlen + 63) / 64, last_fast = mlen / 64;            // fast blocks: [first_fast, last_fast)
-  const uintptr_t a0 = (uintptr_t)(tx + ((size_t)first_fast * 64 - hlen));
-  const uint32_t sh = (uint32_t)(a0 & 3) * 8;
-  const uint32_t *q = (const uint32_t *)(a0 & ~(uintptr_t)3);                       // dword holding the first byte of block first_fast
-  uint32_t nx[17];
-  if (first_fast < last_fast) {
-#pragma unroll
-    for (int i = 0; i < 17; i++) nx[i] = q[i];
-  }
-  for (uint32_t blk = 0; blk < nblk; blk++) {
-    const uint32_t p0 = blk * 64;
-    if (blk >= first_fast && blk < last_fast) {
-#pragma unroll
-      for (int i = 0; i < 16; i++) w[i] = __builtin_bswap32((uint32_t)((((uint64_t)nx[i + 1] << 32) | nx[i]) >> sh));
-      if (blk + 1 < last_fast) {
-        const uint32_t *qn = q + (size_t)(blk + 1 - first_fast) * 16;
-#pragma unroll
-        for (int i = 0; i < 17; i++) nx[i] = qn[i];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 16; i++) w[i] = rp_msg_word(hdr_be, hlen, tx, mlen, p0 + 4 * i);
-      if (blk == nblk - 1) { w[14] = 0; w[15] = mlen * 8; }     // mlen < 2^29 bytes
-    }
-    sha256_compress(st, w);
-  }
-  fe v; sha256_digest_to_limbs(st, v.v);
-  fe t; const uint32_t br = raw_sub(t, v, fr_modulus());
-#pragma unroll
-  for (int i = 0; i < 8; i++) v.v[i] = br ? v.v[i] : t.v[i];
-  return v;
-}
-
-// The same hash by a PAIR of wavefronts (workgroup of 128 threads, 64 hashes): threads 0..63 PRODUCE — they fetch the message words of
+// big-endian words, zero-padded, in global memory; tx: any alignment.  Reads around the text: rp_msg_word fetches the two aligned dwords
+// that hold bytes off .. off + 3 for every word of a block that is not interior, header and padding words included (masked afterwards),
+// with off clamped to -4 below and reaching  64 * nblk - 4 - hlen <= tlen + 68  in the padding block: the bytes from 4 before the text
+// (7 with the alignment) to 76 past its end must be READABLE; nothing is written there and nothing read there reaches the digest.
+// The callers' buffers have that slack: a proof's text ends at least 16 bytes before the end of its text_stride and every text buffer is
+// carved 64 bytes longer than batch * text_stride (16 + 64 >= 76 for the last proof; every other proof over-reads into its
+// neighbour's stride), and no text buffer is the first carving of its workspace.
+//
+// By a PAIR of wavefronts (workgroup of 128 threads, 64 hashes): threads 0..63 PRODUCE — they fetch the message words of
 // block k + 1, expand its schedule and leave W[t] + K[t] in LDS — while threads 64..127 CONSUME block k (the 64 dependent rounds).  A lane
 // of one wavefront issues ~1700 dependent-ish instructions per block at one wavefront's rate; split this way the critical path is the
 // ~900 instructions of the rounds, and the two wavefronts sit on different SIMDs.  `lds`: 2 x 64 x 64 + 1 words.  Every thread of the
@@ -137,7 +101,8 @@ BPPP_DI fe rp_hash_to_fr_pc(bool active, const uint32_t *hdr_be, uint32_t hlen, 
   const uint32_t maxblk = *maxp;
   uint32_t st[8];
   sha256_init(st);
-  // producer state: as in rp_hash_to_fr, interior blocks come as 17 aligned dwords requested one block ahead
+  // producer state.  Interior blocks (all 64 bytes inside the text) are read as 17 aligned dwords and shifted into place; nothing else
+  // hides the load latency, so the dwords of block k + 1 are requested BEFORE block k is scheduled.  fast blocks: [first_fast, last_fast)
   const uint32_t first_fast = (hlen + 63) / 64, last_fast = mlen / 64;
   const uintptr_t a0 = (uintptr_t)(tx + ((size_t)first_fast * 64 - hlen));
   const uint32_t sh = (uint32_t)(a0 & 3) * 8;

@@ -11,6 +11,7 @@
 #include "rpdecode.hip.h"
 #include "seedpoints.hip.h"
 #include "comb.hip.h"
+#include "rpp_transcript.hpp"
 
 namespace bppp {
 template <int MOD> BPPP_DI fe apply_op(int op, const fe &a, const fe &b) {
@@ -460,4 +461,85 @@ extern "C" int bppp_test_last_comb_msm(bppp_ctx *ctx, bppp_test_comb_report *r) 
   r->route = l.route; r->heavy_first = l.heavy_first; r->parts = l.parts; r->tparts = l.tparts; r->wsplit = l.wsplit;
   r->chunks = l.chunks; r->clen = l.clen; r->join_lanes = l.join_lanes;
   return BPPP_OK;
+}
+
+extern "C" int bppp_test_rp_last_text_kernel(bppp_rp *rp, int *lds) {
+  if (!rp || !lds) return BPPP_ERR_ARG;
+  *lds = rp->last_text_kernel;
+  return BPPP_OK;
+}
+
+// ---- the provers' transcript and randomness (csrc/rpp_transcript.hip) alone.  That file and csrc/rpbind.hip are linked into this library as they
+// are (bulletproofspp_amd/_build.py); of what they call, only the host oracle of RppTranscript::call lives elsewhere (csrc/rpprove.hip), and the
+// hook runs device mode alone: it is never reached.
+namespace bppp {
+void rpp_host_oracle(const std::string &, std::vector<std::string> &, size_t &, const uint64_t *, size_t, int, uint64_t *) { abort(); }
+}  // namespace bppp
+
+extern "C" int bppp_test_rpp_transcript(bppp_rp *rp, size_t batch, const bppp_test_rpp_call *calls, size_t ncalls, const uint64_t *points, const uint8_t *bindings,
+                                        uint64_t *challenges) {
+  if (!rp || !batch || batch >= (1u << 16) || !calls || !ncalls || ncalls > 64 || !points || !challenges) return BPPP_ERR_ARG;
+  bppp_ctx *ctx = rp->ctx;
+  hipSetDevice(ctx->device);
+  hipStream_t st = ctx->stream;
+  const size_t B = batch, stride = rp->D.text_stride;
+  std::vector<RppCall> plan;
+  size_t total = 0, mmax = 0;
+  for (size_t c = 0; c < ncalls; c++) {
+    const bppp_test_rpp_call &k = calls[c];
+    if (!k.points || k.count < 1 || k.count > 3 || (k.first_slot < 7 ? k.first_slot + k.count > 7 : (k.first_slot != 7 || k.count != 1)))
+      return bppp::fail(ctx, BPPP_ERR_ARG, "test_rpp_transcript: a call has points, 1 .. 3 outputs in slots 0 .. 6, or one output in slot 7");
+    plan.push_back(RppCall{k.points, k.count, k.first_slot});
+    total += k.points; mmax = std::max<size_t>(mmax, k.points);
+  }
+  // the text buffer of a proof holds the handle's own transcript: npts points of 2 x 78 digits
+  if (total > rp_npts(rp->D)) return bppp::fail(ctx, BPPP_ERR_ARG, "test_rpp_transcript: more points than the handle's text buffer holds");
+  auto up256 = [](size_t n) { return (n + 255) & ~(size_t)255; };
+  const size_t b_ts = up256(B * 4), b_ch = up256(B * 7 * 32), b_es = up256(B * 32), b_hdr = up256(RppTranscript::hdr_bytes(ncalls) + 16), b_pts = up256(B * mmax * 64),
+               b_text = up256(B * stride + 64);                 // the text last and 64 bytes longer, as the provers carve it; never first
+  uint8_t *d = nullptr;
+  BPPP_HIP(ctx, hipMalloc(&d, b_ts + b_ch + b_es + b_hdr + b_pts + b_text));
+  uint32_t *d_ts = (uint32_t *)d, *d_ch = (uint32_t *)(d + b_ts), *d_es = (uint32_t *)(d + b_ts + b_ch);
+  uint8_t *d_hdr = d + b_ts + b_ch + b_es, *d_pts = d_hdr + b_hdr, *d_text = d_pts + b_pts;
+  int rc = rp_bind_begin(rp, bindings, false, B, "test_rpp_transcript");
+  RpBindGuard guard{rp};
+  if (!rc && hipMemsetAsync(d_ch, 0xA5, b_ch + b_es, st) != hipSuccess) rc = bppp::fail(ctx, BPPP_ERR_HIP, "test_rpp_transcript: memset");
+  RppTranscript tr;
+  if (!rc) rc = tr.begin(rp, B, plan, 0, false, d_text, d_ts, d_hdr, d_ch, d_es);
+  std::vector<uint64_t> hch(B * 28), hes(B * 4);
+  for (size_t c = 0; c < ncalls && !rc; c++) {
+    const size_t m = calls[c].points;
+    if (hipMemcpyAsync(d_pts, points, B * m * 64, hipMemcpyHostToDevice, st) != hipSuccess) { rc = bppp::fail(ctx, BPPP_ERR_HIP, "test_rpp_transcript: upload"); break; }
+    points += B * m * 8;
+    rc = tr.call((const uint32_t *)d_pts, c);
+    if (rc) break;
+    if (hipMemcpyAsync(hch.data(), d_ch, B * 7 * 32, hipMemcpyDeviceToHost, st) != hipSuccess || hipMemcpyAsync(hes.data(), d_es, B * 32, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) { rc = bppp::fail(ctx, BPPP_ERR_HIP, "test_rpp_transcript: kernel or copy failed"); break; }
+    for (size_t b = 0; b < B; b++) {
+      uint64_t *out = challenges + (c * B + b) * 12;
+      memset(out, 0, 12 * 8);
+      if (calls[c].first_slot == 7) memcpy(out, &hes[b * 4], 32);
+      else memcpy(out, &hch[b * 28 + calls[c].first_slot * 4], (size_t)calls[c].count * 32);
+    }
+  }
+  hipStreamSynchronize(st);
+  hipFree(d);
+  return rc;
+}
+
+extern "C" int bppp_test_rpp_draws(bppp_ctx *ctx, const uint8_t *prefixes, size_t prefix_len, size_t batch, size_t nd, uint64_t *out) {
+  if (!ctx || (prefix_len && !prefixes) || !batch || !nd || !out || prefix_len >= (1u << 20) || (uint64_t)batch * nd >= (1u << 24)) return BPPP_ERR_ARG;
+  hipSetDevice(ctx->device);
+  hipStream_t st = ctx->stream;
+  const size_t b_pre = (batch * prefix_len + 16 + 255) & ~(size_t)255, n = batch * nd;
+  uint8_t *d = nullptr;
+  BPPP_HIP(ctx, hipMalloc(&d, b_pre + n * 32));
+  uint32_t *d_rnd = (uint32_t *)(d + b_pre);
+  bool ok = hipMemsetAsync(d_rnd, 0xA5, n * 32, st) == hipSuccess && (!prefix_len || hipMemcpyAsync(d, prefixes, batch * prefix_len, hipMemcpyHostToDevice, st) == hipSuccess);
+  int rc = ok ? rpp_draws(ctx, d, prefix_len, batch, nd, d_rnd) : bppp::fail(ctx, BPPP_ERR_HIP, "test_rpp_draws: upload failed");
+  if (!rc && (hipMemcpyAsync(out, d_rnd, n * 32, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
+    rc = bppp::fail(ctx, BPPP_ERR_HIP, "test_rpp_draws: kernel or copy failed");
+  hipStreamSynchronize(st);
+  hipFree(d);
+  return rc;
 }

@@ -113,6 +113,22 @@ int bppp_test_comb_lanes(bppp_test_comb *tab, const void *d_scalars, size_t nter
  * instance), 4 the same with the instances dispatched as pairs.  Fields of the other routes are 0. */
 typedef struct bppp_test_comb_report { int32_t route, heavy_first; uint32_t parts, tparts, wsplit, chunks, clen, join_lanes; } bppp_test_comb_report;
 int bppp_test_last_comb_msm(bppp_ctx *ctx, bppp_test_comb_report *report);
+/* The transcript text kernel of the last verification on this handle (bppp_rp_verify_batch*, _each*, its share of _mixed*): 0 = k_rp_text,
+ * 1 = k_rp_text_lds (while the text image of a proof fits 64 KiB of LDS: up to 272 transcript points), -1 = none yet. */
+int bppp_test_rp_last_text_kernel(bppp_rp *rp, int *lds);
+/* The provers' transcript (RppTranscript of csrc/rpp_transcript.hip) alone, in device mode whatever the batch size: begin with the `ncalls` oracle
+ * calls given, no argument rounds, then call 0, 1, ... in turn.  Call c puts calls[c].points new points in front of every proof's text and draws
+ * calls[c].count (1 .. 3) challenges, into slots first_slot .. of ch (first_slot + count <= 7) or, first_slot = 7 and count = 1, into es.
+ * points: host words, for call 0, then call 1, ...: [batch][calls[c].points][8] affine x | y, any values below 2^256 — they are text, not checked
+ * to be on the curve; the calls' points together may not exceed the handle's own transcript (nrp + nranges + 2 rounds), which sizes the text
+ * buffer.  bindings: NULL or [batch][32] bytes (the tag of proof b is then oracle_tag <> bindings[b]).  challenges: host, [ncalls][batch][3][4]
+ * words, the outputs of call c as read back after it (zero beyond count). */
+typedef struct bppp_test_rpp_call { uint32_t points, count, first_slot; } bppp_test_rpp_call;
+int bppp_test_rpp_transcript(bppp_rp *rp, size_t batch, const bppp_test_rpp_call *calls, size_t ncalls, const uint64_t *points, const uint8_t *bindings,
+                             uint64_t *challenges);
+/* rpp_draws: out[b][c] = hashToScalar (prefix_b <> show c), c < nd; prefixes host [batch][prefix_len] (prefix_len 0: NULL will do), out host
+ * [batch][nd][4] words. */
+int bppp_test_rpp_draws(bppp_ctx *ctx, const uint8_t *prefixes, size_t prefix_len, size_t batch, size_t nd, uint64_t *out);
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
