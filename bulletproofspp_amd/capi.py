@@ -200,6 +200,8 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_fe_op.argtypes = [vp, i, i, vp, vp, sz, vp]
     lib.bppp_test_point_op.argtypes = [vp, i, vp, vp, sz, vp]
     lib.bppp_test_point_quad.argtypes = [vp, i, vp, vp, sz, vp, vp]
+    lib.bppp_test_fq_pair.argtypes = [vp, i, vp, vp, vp, vp, sz, vp]
+    lib.bppp_test_point_chain.argtypes = [vp, i, vp, vp, sz, vp, vp]
     lib.bppp_test_mulmod_rate.argtypes = [vp, i, C.POINTER(C.c_double)]
     lib.bppp_test_last_mixed_msm_terms.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.bppp_test_last_acc_kernel.argtypes = [vp, C.POINTER(C.c_int)]

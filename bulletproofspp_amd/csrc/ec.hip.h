@@ -106,6 +106,46 @@ BPPP_DI void xyzz_add(xyzz &acc, const xyzz &q) {
   acc.X = X3; acc.Y = Y3;
 }
 
+// ---- the same two routines for dependent chains on a lone wavefront (fq26.hip.h, pair forms): the same formulas, branches and fq_sub
+// bounds, the products issued two at a time.  Outputs equal xyzz_dbl's / xyzz_add's limb for limb.
+BPPP_DI xyzz xyzz_dbl_chain(const xyzz &p) {
+  if (xyzz_is_inf(p) || fq_normalizes_to_zero(p.Y)) return xyzz_inf();
+  const fq U = fq_mul_int(p.Y, 2);                  // <= 6
+  fq V, XX, W, S, MM, Ya, Yb;
+  fq_sqr2(U, p.X, V, XX);
+  fq_mul2(U, V, p.X, V, W, S);
+  const fq M = fq_mul_int(XX, 3);
+  xyzz r;
+  fq_mul_sqr(V, p.ZZ, M, r.ZZ, MM);
+  r.X = fq_sub<2>(MM, fq_mul_int(S, 2));            // 4
+  fq_mul2(M, fq_sub<4>(S, r.X), W, p.Y, Ya, Yb);
+  r.Y = fq_sub<1>(Ya, Yb);                          // 3
+  r.ZZZ = fq_mul(W, p.ZZZ);
+  return r;
+}
+BPPP_DI void xyzz_add_chain(xyzz &acc, const xyzz &q) {
+  if (xyzz_is_inf(q)) return;
+  if (xyzz_is_inf(acc)) { acc = q; return; }
+  fq U1, U2, S1, S2;
+  fq_mul2(acc.X, q.ZZ, q.X, acc.ZZ, U1, U2);
+  fq_mul2(acc.Y, q.ZZZ, q.Y, acc.ZZZ, S1, S2);
+  const fq Pd = fq_sub<1>(U2, U1), R = fq_sub<1>(S2, S1);      // 3, 3
+  if (fq_normalizes_to_zero(Pd)) {
+    if (fq_normalizes_to_zero(R)) acc = xyzz_dbl_chain(acc); else acc = xyzz_inf();
+    return;
+  }
+  fq PP, RR, Z12, Z123, PPP, Q, Ya, Yb;
+  fq_sqr2(Pd, R, PP, RR);
+  fq_mul2(acc.ZZ, q.ZZ, acc.ZZZ, q.ZZZ, Z12, Z123);
+  fq_mul2(Pd, PP, U1, PP, PPP, Q);
+  xyzz r;
+  r.X = fq_sub<3>(RR, fq_add(PPP, fq_mul_int(Q, 2)));          // 5
+  fq_mul2(Z12, PP, Z123, PPP, r.ZZ, r.ZZZ);
+  fq_mul2(R, fq_sub<5>(Q, r.X), S1, PPP, Ya, Yb);
+  r.Y = fq_sub<1>(Ya, Yb);                                     // 3
+  acc = r;
+}
+
 // normalize / jacToAff (Commitment.hs:121, :172-173): one inversion per point; canonical output.
 BPPP_DI aff xyzz_to_aff(const xyzz &p) {
   if (xyzz_is_inf(p)) return aff_inf();

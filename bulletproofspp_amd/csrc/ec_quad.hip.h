@@ -8,6 +8,9 @@
 // result, limb for limb equal to xyzz_add / xyzz_dbl (ec.hip.h): the squares are fq_mul(x, x), whose column sums are the same
 // integers as fq_sqr's, and every other product keeps the scalar routine's operand order and fq_sub bounds.
 //
+// The multiplier is a template argument: fq_mul by default, fq_mul_lone (fq26.hip.h: no stall slots when nothing else runs on the SIMD) for
+// k_reduce_tail_quad, whose wavefronts have a SIMD each.  A lane has ONE product per stage, so the pair forms have nothing to pair here.
+//
 // Rules for callers:
 //  - all four lanes of a quad are active at every call (DPP reads across the quad): a quad with nothing to add adds infinity; never
 //    branch around a call on anything that is not uniform within the quad;
@@ -50,18 +53,21 @@ BPPP_DI xyzz xyzz_sel(bool c, const xyzz &a, const xyzz &b) {     // c ? a : b, 
 }
 BPPP_DI xyzz xyzz_or_inf(bool keep, const xyzz &p) { return xyzz_sel(keep, p, xyzz_inf()); }
 
+// LONE: the multiplier is fq_mul_lone (fq26.hip.h) — for kernels whose wavefronts have a SIMD to themselves; same limbs either way
+template <bool LONE> BPPP_DI fq fq_mul_q(const fq &a, const fq &b) { return LONE ? fq_mul_lone(a, b) : fq_mul(a, b); }
+
 // dbl-2008-s-1 (a = 0) on a quad, three stages:  V = U^2, XX = X^2  |  W = U V, S = X V, ZZ3 = V ZZ, M^2  |  M (S - X3), W Y, ZZZ3 = W ZZZ
-BPPP_DI void xyzz_dbl_quad(xyzz &p) {
+template <bool LONE = false> BPPP_DI void xyzz_dbl_quad(xyzz &p) {
   const uint32_t s = quad_lane();
   const bool inf = xyzz_is_inf(p) || fq_normalizes_to_zero(p.Y);
   const fq U = fq_mul_int(p.Y, 2);                                 // <= 6
   const fq a1 = fq_sel4(s, U, p.X, U, p.X);
-  const fq m1 = fq_mul(a1, a1);
+  const fq m1 = fq_mul_q<LONE>(a1, a1);
   const fq V = fq_quad_bcast<0>(m1), M = fq_mul_int(fq_quad_bcast<1>(m1), 3);
-  const fq m2 = fq_mul(fq_sel4(s, U, p.X, V, M), fq_sel4(s, V, V, p.ZZ, M));
+  const fq m2 = fq_mul_q<LONE>(fq_sel4(s, U, p.X, V, M), fq_sel4(s, V, V, p.ZZ, M));
   const fq W = fq_quad_bcast<0>(m2), S = fq_quad_bcast<1>(m2), ZZ3 = fq_quad_bcast<2>(m2);
   const fq X3 = fq_sub<2>(fq_quad_bcast<3>(m2), fq_mul_int(S, 2));                  // 4
-  const fq m3 = fq_mul(fq_sel4(s, M, W, W, W), fq_sel4(s, fq_sub<4>(S, X3), p.Y, p.ZZZ, p.ZZZ));
+  const fq m3 = fq_mul_q<LONE>(fq_sel4(s, M, W, W, W), fq_sel4(s, fq_sub<4>(S, X3), p.Y, p.ZZZ, p.ZZZ));
   xyzz r;
   r.X = X3;
   r.Y = fq_sub<1>(fq_quad_bcast<0>(m3), fq_quad_bcast<1>(m3));                       // 3
@@ -74,24 +80,24 @@ BPPP_DI void xyzz_dbl_quad(xyzz &p) {
 //   2. PP = Pd^2, RR = R^2, Z12 = ZZ1 ZZ2, Z123 = ZZZ1 ZZZ2          (Z12 and Z123 stay in lanes 2 and 3)
 //   3. PPP = Pd PP, Q = U1 PP, ZZ3 = Z12 PP, -                       -> X3
 //   4. R (Q - X3), S1 PPP, -, ZZZ3 = Z123 PPP                        -> Y3
-BPPP_DI void xyzz_add_quad(xyzz &acc, const xyzz &q) {
+template <bool LONE = false> BPPP_DI void xyzz_add_quad(xyzz &acc, const xyzz &q) {
   const uint32_t s = quad_lane();
   const bool ia = xyzz_is_inf(acc), iq = xyzz_is_inf(q);
-  const fq m1 = fq_mul(fq_sel4(s, acc.X, q.X, acc.Y, q.Y), fq_sel4(s, q.ZZ, acc.ZZ, q.ZZZ, acc.ZZZ));
+  const fq m1 = fq_mul_q<LONE>(fq_sel4(s, acc.X, q.X, acc.Y, q.Y), fq_sel4(s, q.ZZ, acc.ZZ, q.ZZZ, acc.ZZZ));
   const fq U1 = fq_quad_bcast<0>(m1), S1 = fq_quad_bcast<2>(m1);
   const fq Pd = fq_sub<1>(fq_quad_bcast<1>(m1), U1), R = fq_sub<1>(fq_quad_bcast<3>(m1), S1);     // 3, 3
   if (!ia && !iq && fq_normalizes_to_zero(Pd)) {                  // same x: uniform within the quad
-    if (fq_normalizes_to_zero(R)) xyzz_dbl_quad(acc); else acc = xyzz_inf();
+    if (fq_normalizes_to_zero(R)) xyzz_dbl_quad<LONE>(acc); else acc = xyzz_inf();
     return;
   }
-  const fq m2 = fq_mul(fq_sel4(s, Pd, R, acc.ZZ, acc.ZZZ), fq_sel4(s, Pd, R, q.ZZ, q.ZZZ));
+  const fq m2 = fq_mul_q<LONE>(fq_sel4(s, Pd, R, acc.ZZ, acc.ZZZ), fq_sel4(s, Pd, R, q.ZZ, q.ZZZ));
   const fq PP = fq_quad_bcast<0>(m2), RR = fq_quad_bcast<1>(m2);
-  const fq m3 = fq_mul(fq_sel4(s, Pd, U1, m2, m2), PP);
+  const fq m3 = fq_mul_q<LONE>(fq_sel4(s, Pd, U1, m2, m2), PP);
   const fq PPP = fq_quad_bcast<0>(m3), Q = fq_quad_bcast<1>(m3);
   xyzz r;
   r.ZZ = fq_quad_bcast<2>(m3);
   r.X = fq_sub<3>(RR, fq_add(PPP, fq_mul_int(Q, 2)));                                 // 5
-  const fq m4 = fq_mul(fq_sel4(s, R, S1, m2, m2), s == 0 ? fq_sub<5>(Q, r.X) : PPP);
+  const fq m4 = fq_mul_q<LONE>(fq_sel4(s, R, S1, m2, m2), s == 0 ? fq_sub<5>(Q, r.X) : PPP);
   r.Y = fq_sub<1>(fq_quad_bcast<0>(m4), fq_quad_bcast<1>(m4));                       // 3
   r.ZZZ = fq_quad_bcast<3>(m4);
   acc = xyzz_sel(iq, acc, xyzz_sel(ia, q, r));

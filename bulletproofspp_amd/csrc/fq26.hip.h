@@ -46,8 +46,10 @@ BPPP_DI bool fq_all_zero(const fq &a) {        // exact all-limbs-zero test (the
 // Round 4 form: TWO carry chains — H = columns 9 .. 18, L = columns 0 .. 8 with the fold of H's limbs — in which the carry of a column is
 // the ADDEND of the next column's first product (no 64-bit add), pinned product by product (an empty asm after each), with R0 / R1 held in
 // scalar registers so that u * R1 stays one v_mad_u64_u32: 119 v_mad_u64_u32 + 7 v_lshl_add_u64 + 22 v_lshrrev_b64 + 3 v_lshlrev_b64 +
-// 6 v_mov + 23 v_and (+ 42 s_nop 0 the compiler puts between back-to-back dependent products: hidden by the other wavefronts of the
-// SIMD) — 203 G/s in the same microbenchmark, bit-identical results (also at the magnitude-8 bounds); k_acc_points 1.106 -> 1.04 ms.
+// 6 v_mov + 23 v_and (+ the s_nop 0 the compiler puts between back-to-back dependent products: 42 in the round-4 loop of four independent
+// chains per lane, profiles/r04_fq_mul_isa_histogram.txt, 61 in a loop
+// r = fq_mul(r, b) of one chain, profiles/r11_fq_pair_isa_histogram.txt; hidden by the other wavefronts of the SIMD where there are any,
+// paid in full by a lone wavefront: the pair forms below) — 203 G/s in the same microbenchmark, bit-identical results (also at the magnitude-8 bounds); k_acc_points 1.106 -> 1.04 ms.
 // A third form that fills those slots with the 45 low products as free column sums (benchmarks/fqmul_variants.h v3: no s_nop, 15
 // v_lshl_add_u64) measures 196 G/s there and the same in the kernels: not kept.  ISA histograms: profiles/r04_fq_mul_isa_histogram.txt.
 BPPP_DI uint64_t fq_madc(uint32_t x, uint32_t y, uint64_t acc) { uint64_t r = (uint64_t)x * y + acc; asm("" : "+v"(r)); return r; }
@@ -123,6 +125,69 @@ BPPP_DI fq fq_sqr(const fq &a) {
   return r;
 }
 
+// ---- pair forms for dependent chains at ONE wavefront per SIMD (the bucket reduction's kernels, msm.hip section 4')
+// fq_mul / fq_sqr are tuned for throughput: every product of a chain takes the one before it as its addend, an s_nop stands behind each pin
+// where the next instruction reads the pinned sum (61 per multiplication in a loop  r = fq_mul(r, b)), and the other wavefronts of the
+// SIMD fill those slots.  A kernel that walks a chain of point additions on a lone wavefront has nothing to fill them with.  Measured
+// (benchmarks/fqmul_variants.hip, argument `chain`; profiles/r11_fqmul_chain_rates.txt), ns per product of a dependent chain at 1 / 8
+// wavefronts per SIMD:  fq_mul 531 / 2686 (336 per product of SIMD time: the throughput cost), fq_sqr 349 / 1970.
+// The pair forms compute TWO independent products (a point addition has them in every step) as four chains, issued product by product:
+// H of the first, H of the second, ..., then L of the first, L of the second, ...: no s_nop is left (profiles/r11_fq_pair_isa_histogram.txt)
+// and a lone wavefront pays 378-395 ns per product with fq_mul2, 296 with fq_sqr2; a whole xyzz_add 428 -> 378 per product (ec.hip.h,
+// xyzz_add_chain).  Every product keeps its own chains, its column order, its fold (fq_mul_tail) and its magnitude contract, so the
+// outputs equal fq_mul's / fq_sqr's limb for limb (tests/test_gpu_fq_pair.py).
+// Throughput kernels (k_acc_points*, the comb kernels, the verifier) stay on fq_mul / fq_sqr.
+template <bool SQ> BPPP_DI constexpr int fq_col_n(int k) {          // products in column k
+  return SQ ? ((k + 1) / 2 - (k > 9 ? k - 9 : 0)) + ((k & 1) == 0 ? 1 : 0) : (k < 9 ? k : 9) - (k > 9 ? k - 9 : 0) + 1;
+}
+// product j of column k in fq_mul's (a, b) or fq_sqr's (a, doubled a in b) order
+template <bool SQ> BPPP_DI uint64_t fq_col_step(const fq &a, const fq &b, int k, int j, uint64_t acc) {
+  const int i = (k > 9 ? k - 9 : 0) + j;
+  if (SQ) return 2 * i < k ? fq_madc(b.n[i], a.n[k - i], acc) : fq_madc(a.n[k / 2], a.n[k / 2], acc);
+  return fq_madc(a.n[i], b.n[k - i], acc);
+}
+// keeps the products in the order written: left to itself the compiler's scheduler sorts them back into one chain after the other (the
+// pin of fq_madc orders only its own chain)
+BPPP_DI void fq_fence() { __builtin_amdgcn_sched_barrier(0); }
+template <bool SQ1, bool SQ2> BPPP_DI void fq_pair(const fq a, const fq b_, const fq c, const fq d_, fq &r1, fq &r2) {     // inputs by value: an output may be an input
+  const uint32_t R0 = fq_sreg(FQ_R0), R1 = fq_sreg(FQ_R1);
+  fq b = b_, d = d_;
+#pragma unroll
+  for (int i = 0; i < 10; i++) { if (SQ1) b.n[i] = a.n[i] << 1; if (SQ2) d.n[i] = c.n[i] << 1; }     // < 2^31 for magnitude <= 8
+  uint64_t h1 = 0, h2 = 0;
+  uint32_t t9a = 0, t9b = 0, u1[9], u2[9];
+#pragma unroll
+  for (int k = 9; k <= 18; k++) {
+#pragma unroll
+    for (int j = 0; j < 10; j++) {
+      if (j < fq_col_n<SQ1>(k)) { h1 = fq_col_step<SQ1>(a, b, k, j, h1); fq_fence(); }
+      if (j < fq_col_n<SQ2>(k)) { h2 = fq_col_step<SQ2>(c, d, k, j, h2); fq_fence(); }
+    }
+    if (k == 9) { t9a = (uint32_t)h1 & FQ_M26; t9b = (uint32_t)h2 & FQ_M26; }
+    else { u1[k - 10] = (uint32_t)h1 & FQ_M26; u2[k - 10] = (uint32_t)h2 & FQ_M26; }
+    h1 >>= 26; h2 >>= 26;
+  }
+  uint64_t l1 = 0, l2 = 0;
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+#pragma unroll
+    for (int j = 0; j < 9; j++) {
+      if (j < fq_col_n<SQ1>(k)) { l1 = fq_col_step<SQ1>(a, b, k, j, l1); fq_fence(); }
+      if (j < fq_col_n<SQ2>(k)) { l2 = fq_col_step<SQ2>(c, d, k, j, l2); fq_fence(); }
+    }
+    l1 = fq_madc(u1[k], R0, l1); fq_fence(); l2 = fq_madc(u2[k], R0, l2); fq_fence();
+    if (k) { l1 = fq_madc(u1[k - 1], R1, l1); fq_fence(); l2 = fq_madc(u2[k - 1], R1, l2); fq_fence(); }
+    r1.n[k] = (uint32_t)l1 & FQ_M26; l1 >>= 26;
+    r2.n[k] = (uint32_t)l2 & FQ_M26; l2 >>= 26;
+  }
+  fq_mul_tail(r1, l1, t9a, h1, u1[8]);
+  fq_mul_tail(r2, l2, t9b, h2, u2[8]);
+}
+// (r1, r2) = (a b, c d);  (a b, c^2);  (a^2, c^2)
+BPPP_DI void fq_mul2(const fq &a, const fq &b, const fq &c, const fq &d, fq &r1, fq &r2) { fq_pair<false, false>(a, b, c, d, r1, r2); }
+BPPP_DI void fq_mul_sqr(const fq &a, const fq &b, const fq &c, fq &r1, fq &r2) { fq_pair<false, true>(a, b, c, c, r1, r2); }
+BPPP_DI void fq_sqr2(const fq &a, const fq &c, fq &r1, fq &r2) { fq_pair<true, true>(a, a, c, c, r1, r2); }
+
 // the round 1-3 form of the multiplication (plain columns, the compiler's own order): a cross-check for tests and benchmarks
 #define FQ_COL(acc, k)                                                                 \
   _Pragma("unroll") for (int i = ((k) > 9 ? (k)-9 : 0); i <= ((k) < 9 ? (k) : 9); i++) \
@@ -145,6 +210,41 @@ BPPP_DI fq fq_mul_cols(const fq &a, const fq &b) {
     FQ_COL(c, k)
     c += (uint64_t)u[k] * FQ_R0;
     if (k) c += (uint64_t)u[k - 1] * FQ_R1;
+    r.n[k] = (uint32_t)c & FQ_M26; c >>= 26;
+  }
+  fq_mul_tail(r, c, t9, u9, u[8]);
+  return r;
+}
+
+// ONE product on a lone wavefront (the quad forms of ec_quad.hip.h: a lane has one product per stage, nothing to pair it with): the H chain
+// pinned as in fq_mul, the 45 low products as free, unpinned column sums that the compiler's scheduler puts between H's dependent products,
+// then a pinned fold chain  c = u_k R0 + carry; c += u_(k-1) R1; c += P_k  (one 64-bit add per low column).  The column sums are the
+// same integers as fq_mul's, so the limbs are equal.  With the SIMD full it is the slower form (the third form of the comment above fq_madc);
+// alone on a SIMD a chain  r = fq_mul_lone(r, b)  costs 417 ns per product against fq_mul's 531.
+BPPP_DI fq fq_mul_lone(const fq &a, const fq &b) {
+  const uint32_t R0 = fq_sreg(FQ_R0), R1 = fq_sreg(FQ_R1);
+  uint64_t P[9];
+#pragma unroll
+  for (int k = 0; k < 9; k++) { uint64_t c = 0; FQ_COL(c, k) P[k] = c; }
+  uint64_t d = 0;
+#pragma unroll
+  for (int i = 0; i <= 9; i++) d = fq_madc(a.n[i], b.n[9 - i], d);
+  const uint32_t t9 = (uint32_t)d & FQ_M26; d >>= 26;
+  uint32_t u[9];
+#pragma unroll
+  for (int k = 10; k <= 18; k++) {
+#pragma unroll
+    for (int i = k - 9; i <= 9; i++) d = fq_madc(a.n[i], b.n[k - i], d);
+    u[k - 10] = (uint32_t)d & FQ_M26; d >>= 26;
+  }
+  const uint64_t u9 = d;
+  fq r;
+  uint64_t c = 0;
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+    c = fq_madc(u[k], R0, c);
+    if (k) c = fq_madc(u[k - 1], R1, c);
+    c += P[k];
     r.n[k] = (uint32_t)c & FQ_M26; c >>= 26;
   }
   fq_mul_tail(r, c, t9, u9, u[8]);

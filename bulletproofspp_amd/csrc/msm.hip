@@ -372,11 +372,11 @@ __global__ void __launch_bounds__(64) k_merge_heavy(const uint32_t *__restrict__
     xyzz acc = xyzz_inf();
     for (uint32_t t = t0 + lane; t < t1; t += 64) {
       xyzz p = xyzz_load(SIZED ? pieces + (size_t)t * XYZZ_WORDS : partial_ptr(rec_pt, g0, t));
-      xyzz_add(acc, p);
+      xyzz_add_chain(acc, p);
     }
     for (int d = 32; d >= 1; d >>= 1) {
       xyzz o = xyzz_shfl_down(acc, d);
-      if ((int)lane + d < 64) xyzz_add(acc, o);
+      if ((int)lane + d < 64) xyzz_add_chain(acc, o);
     }
     if (np <= HEAVY_CHUNK) {
       if (lane == 0) xyzz_store(buckets + (size_t)fb * XYZZ_WORDS, acc);
@@ -400,11 +400,11 @@ __global__ void __launch_bounds__(64) k_merge_heavy(const uint32_t *__restrict__
     acc = xyzz_inf();
     for (uint32_t j = lane; j < nch; j += 64) {
       xyzz p = xyzz_load(chunk_sums + (size_t)(base + j) * XYZZ_WORDS);
-      xyzz_add(acc, p);
+      xyzz_add_chain(acc, p);
     }
     for (int d = 32; d >= 1; d >>= 1) {
       xyzz o = xyzz_shfl_down(acc, d);
-      if ((int)lane + d < 64) xyzz_add(acc, o);
+      if ((int)lane + d < 64) xyzz_add_chain(acc, o);
     }
     if (lane == 0) xyzz_store(buckets + (size_t)fb * XYZZ_WORDS, acc);
   }
@@ -555,12 +555,29 @@ __global__ void __launch_bounds__(64) k_reduce2(const uint32_t *__restrict__ red
 // Here the bucket index splits as i = hi * LO + lo (weight i + 1 = LO * hi + (lo + 1)):
 //     sum_i (i + 1) B_i  =  LO * sum_hi hi * R_hi  +  sum_lo (lo + 1) * C_lo,     R_hi = sum_lo B,   C_lo = sum_hi B
 // R and C are PLAIN sums: k_reduce_marg gives every lane S consecutive (rows) or strided (columns) buckets — no scan, every
-// lane busy, one wavefront per SIMD — and finishes them with a short segmented tree.  The two weighted sums left are over HI and
+// lane busy, one wavefront per SIMD — and finishes them with a short segmented tree.  With the SIMD to itself the wavefront adds with
+// xyzz_add_chain (ec.hip.h: the products of an addition issued in pairs, so that one fills the other's stall slots) and loads the
+// next bucket while it adds the current one; so do k_reduce_tail and the trees of k_merge_heavy.  The two weighted sums left are over HI and
 // LO (<= 256) elements: k_reduce_tail, one element per lane (suffix scan + tree, ~18 chained additions).  The factor LO is not
 // applied on the device at all: the window combine, which doubles c times per window anyway, takes (W1, W2) and does
 // r = (r * 2^(c-a) + W1) * 2^a + W2.
 // quad = 1: k_reduce_tail_quad, on TR = HI / 16 row and TC = LO / 16 column blocks of 16 elements (MsmTune::tail_scalar = 0)
 struct MargGeom { int a, LO, HI, PR, PC, SR, SC; uint32_t row_tiles, col_tiles; int quad, TR, TC; };
+
+// the serial part of a lane: b[0] + b[stride] + ... (S terms).  Bucket k + 1 is loaded (ten 16-byte loads into a second set of registers)
+// before bucket k is added, so the wavefront — alone on its SIMD, nothing else to hide a load behind — waits for memory once, not S times.
+BPPP_DI xyzz marg_serial_sum(const uint32_t *b, int S, size_t stride) {
+  xyzz acc = xyzz_load(b);
+  if (S < 2) return acc;
+  xyzz B = xyzz_load(b + stride);
+  for (int k = 2; k < S; k++) {
+    const xyzz Bn = xyzz_load(b + (size_t)k * stride);
+    xyzz_add_chain(acc, B);
+    B = Bn;
+  }
+  xyzz_add_chain(acc, B);
+  return acc;
+}
 
 __global__ void __launch_bounds__(64) k_reduce_marg(const uint32_t *__restrict__ buckets, int M, MargGeom Gm, uint32_t *__restrict__ R, uint32_t *__restrict__ C) {
   const uint32_t nbw = blockIdx.y, lane = threadIdx.x;
@@ -571,12 +588,11 @@ __global__ void __launch_bounds__(64) k_reduce_marg(const uint32_t *__restrict__
     const bool act = hi < (uint32_t)Gm.HI;
     if (act) {
       const uint32_t *b = wb + ((size_t)hi * Gm.LO + (size_t)part * Gm.SR) * XYZZ_WORDS;
-      acc = xyzz_load(b);
-      for (int k = 1; k < Gm.SR; k++) { xyzz B = xyzz_load(b + (size_t)k * XYZZ_WORDS); xyzz_add(acc, B); }
+      acc = marg_serial_sum(b, Gm.SR, XYZZ_WORDS);
     }
     for (int d = Gm.PR >> 1; d >= 1; d >>= 1) {
       xyzz o = xyzz_shfl_down(acc, d);
-      if ((int)part + d < Gm.PR) xyzz_add(acc, o);
+      if ((int)part + d < Gm.PR) xyzz_add_chain(acc, o);
     }
     if (act && part == 0) xyzz_store(R + ((size_t)nbw * Gm.HI + hi) * XYZZ_WORDS, acc);
   } else {
@@ -584,12 +600,11 @@ __global__ void __launch_bounds__(64) k_reduce_marg(const uint32_t *__restrict__
     const bool act = lo < (uint32_t)Gm.LO;
     if (act) {
       const uint32_t *b = wb + ((size_t)part * Gm.SC * Gm.LO + lo) * XYZZ_WORDS;
-      acc = xyzz_load(b);
-      for (int k = 1; k < Gm.SC; k++) { xyzz B = xyzz_load(b + (size_t)k * Gm.LO * XYZZ_WORDS); xyzz_add(acc, B); }
+      acc = marg_serial_sum(b, Gm.SC, (size_t)Gm.LO * XYZZ_WORDS);
     }
     for (int d = Gm.PC >> 1; d >= 1; d >>= 1) {
       xyzz o = xyzz_shfl_down(acc, d);
-      if ((int)part + d < Gm.PC) xyzz_add(acc, o);
+      if ((int)part + d < Gm.PC) xyzz_add_chain(acc, o);
     }
     if (act && part == 0) xyzz_store(C + ((size_t)nbw * Gm.LO + lo) * XYZZ_WORDS, acc);
   }
@@ -607,22 +622,22 @@ __global__ void __launch_bounds__(256) k_reduce_tail(const uint32_t *__restrict_
   if (idx < n) suf = xyzz_load((isC ? C + ((size_t)nbw * Gm.LO + idx) * XYZZ_WORDS : R + ((size_t)nbw * Gm.HI + idx) * XYZZ_WORDS));
   for (int d = 1; d < 64; d <<= 1) {             // inclusive suffix scan inside the wavefront
     xyzz o = xyzz_shfl_down(suf, d);
-    if ((int)lane + d < 64) xyzz_add(suf, o);
+    if ((int)lane + d < 64) xyzz_add_chain(suf, o);
   }
   if (lane == 0) xyzz_store(tot + gw * XYZZ_WORDS, suf);
   __syncthreads();
-  for (uint32_t w = gw + 1; w < gn; w++) { xyzz t = xyzz_load(tot + w * XYZZ_WORDS); xyzz_add(suf, t); }     // later wavefronts of the group
+  for (uint32_t w = gw + 1; w < gn; w++) { xyzz t = xyzz_load(tot + w * XYZZ_WORDS); xyzz_add_chain(suf, t); }     // later wavefronts of the group
   // R: sum_hi hi * R_hi = sum_{hi >= 1} suffix(hi);   C: sum_lo (lo + 1) * C_lo = sum_{lo >= 0} suffix(lo)
   xyzz v = (!isC && idx == 0) ? xyzz_inf() : suf;
   for (int d = 32; d >= 1; d >>= 1) {
     xyzz o = xyzz_shfl_down(v, d);
-    if ((int)lane + d < 64) xyzz_add(v, o);
+    if ((int)lane + d < 64) xyzz_add_chain(v, o);
   }
   __syncthreads();
   if (lane == 0) xyzz_store(tot + gw * XYZZ_WORDS, v);
   __syncthreads();
   if (lane == 0 && gw == 0) {
-    for (uint32_t w = 1; w < gn; w++) { xyzz t = xyzz_load(tot + w * XYZZ_WORDS); xyzz_add(v, t); }
+    for (uint32_t w = 1; w < gn; w++) { xyzz t = xyzz_load(tot + w * XYZZ_WORDS); xyzz_add_chain(v, t); }
     xyzz_store(winsum2 + ((size_t)nbw * 2 + (isC ? 1 : 0)) * XYZZ_WORDS, v);
   }
 }
@@ -646,12 +661,12 @@ __global__ void __launch_bounds__(64) k_reduce_tail_quad(const uint32_t *__restr
   else if (i + 1 < (uint32_t)Gm.HI) suf = xyzz_load(R + ((size_t)nbw * Gm.HI + i + 1) * XYZZ_WORDS);
   for (int d = 1; d < 16; d <<= 1) {             // inclusive suffix scan over the 16 quads
     xyzz o = xyzz_shfl_down(suf, 4 * d);
-    xyzz_add_quad(suf, xyzz_or_inf(qd + d < 16, o));
+    xyzz_add_quad<true>(suf, xyzz_or_inf(qd + d < 16, o));
   }
   xyzz v = suf;
   for (int d = 8; d >= 1; d >>= 1) {             // tree of the suffixes: A_b in quad 0
     xyzz o = xyzz_shfl_down(v, 4 * d);
-    xyzz_add_quad(v, xyzz_or_inf(qd + d < 16, o));
+    xyzz_add_quad<true>(v, xyzz_or_inf(qd + d < 16, o));
   }
   uint32_t *pb = part + (((size_t)nbw * 2 + (isC ? 1 : 0)) * 16 + blk) * 2 * XYZZ_WORDS;
   if (lane == 0) xyzz_store(pb, v);
@@ -676,15 +691,15 @@ __global__ void __launch_bounds__(64) k_reduce_tail_quad(const uint32_t *__restr
   if (qd < nb) { A = xyzz_load(pr + (size_t)qd * 2 * XYZZ_WORDS); S = xyzz_load(pr + ((size_t)qd * 2 + 1) * XYZZ_WORDS); }
   for (uint32_t d = 1; d < nb; d <<= 1) {
     xyzz o = xyzz_shfl_down(S, 4 * d);
-    xyzz_add_quad(S, xyzz_or_inf(qd + d < nb, o));
+    xyzz_add_quad<true>(S, xyzz_or_inf(qd + d < nb, o));
   }
   // sum_b b S_b = sum_{b >= 1} suffix_b; times 16, plus A_b, summed over the blocks
   v = xyzz_or_inf(qd >= 1, S);
-  for (int k = 0; k < 4; k++) xyzz_dbl_quad(v);
-  xyzz_add_quad(v, A);
+  for (int k = 0; k < 4; k++) xyzz_dbl_quad<true>(v);
+  xyzz_add_quad<true>(v, A);
   for (uint32_t d = nb >> 1; d >= 1; d >>= 1) {
     xyzz o = xyzz_shfl_down(v, 4 * d);
-    xyzz_add_quad(v, xyzz_or_inf(qd + d < nb, o));
+    xyzz_add_quad<true>(v, xyzz_or_inf(qd + d < nb, o));
   }
   if (lane == 0) xyzz_store(winsum2 + ((size_t)nbw * 2 + (isC ? 1 : 0)) * XYZZ_WORDS, v);
 }

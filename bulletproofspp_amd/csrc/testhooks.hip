@@ -115,7 +115,10 @@ __global__ void __launch_bounds__(64) k_test_point_quad(int op, const uint32_t *
   xyzz A = xyzz_inf(), B = xyzz_inf();           // a quad past the end adds infinity: every quad takes part in the exchanges
   if (valid) { A = test_xyzz_of(aff_load(p + (size_t)i * 16), bounds); B = test_xyzz_of(aff_load(q + (size_t)i * 16), bounds); }
   xyzz s = A, r = A;
-  if (op < 2) { xyzz_add(s, B); xyzz_add_quad(r, B); }
+  if (op & 4) {                                    // the forms on fq_mul_lone (k_reduce_tail_quad's)
+    if ((op & 3) < 2) { xyzz_add(s, B); xyzz_add_quad<true>(r, B); }
+    else { s = xyzz_dbl(A); xyzz_dbl_quad<true>(r); }
+  } else if (op < 2) { xyzz_add(s, B); xyzz_add_quad(r, B); }
   else { s = xyzz_dbl(A); xyzz_dbl_quad(r); }
   // do the four lanes of the quad hold the same limbs?
   uint32_t d = 0;
@@ -133,6 +136,35 @@ __global__ void __launch_bounds__(64) k_test_point_quad(int op, const uint32_t *
     o[80] = d == 0 ? 1u : 0u;
     aff_store(out + (size_t)i * 16, xyzz_to_aff(r));
   }
+}
+// the pair forms of fq26.hip.h against fq_mul / fq_sqr on raw limbs (any magnitude <= 8 the caller builds): per element 40 words,
+// pair r1, pair r2, one-product r1, one-product r2.  kind 0: (a b, c d)  1: (a b, c^2)  2: (a^2, c^2)
+__global__ void __launch_bounds__(64) k_test_fq_pair(int kind, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d, uint32_t n, uint32_t *raw) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const fq A = fq_load10(a + (size_t)i * 10), B = fq_load10(b + (size_t)i * 10), Cc = fq_load10(c + (size_t)i * 10), D = fq_load10(d + (size_t)i * 10);
+  fq r1, r2, s1, s2;
+  if (kind == 0) { fq_mul2(A, B, Cc, D, r1, r2); s1 = fq_mul(A, B); s2 = fq_mul(Cc, D); }
+  else if (kind == 1) { fq_mul_sqr(A, B, Cc, r1, r2); s1 = fq_mul(A, B); s2 = fq_sqr(Cc); }
+  else { fq_sqr2(A, Cc, r1, r2); s1 = fq_sqr(A); s2 = fq_sqr(Cc); }
+  uint32_t *o = raw + (size_t)i * 40;
+  fq_store10(o, r1); fq_store10(o + 10, r2); fq_store10(o + 20, s1); fq_store10(o + 30, s2);
+}
+// xyzz_add_chain / xyzz_dbl_chain against xyzz_add / xyzz_dbl, one lane per element.  op bit 0: the left operand is 3 p[i] built as a sum
+// of three points (ZZ != 1) instead of p[i] with ZZ = 1; bit 1: the same for the right operand; bit 2: doubling of the left operand
+__global__ void __launch_bounds__(64) k_test_point_chain(int op, const uint32_t *p, const uint32_t *q, uint32_t n, uint32_t *out, uint32_t *raw) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const aff P = aff_load(p + (size_t)i * 16), Q = aff_load(q + (size_t)i * 16);
+  xyzz A = xyzz_from_aff(P), B = xyzz_from_aff(Q);
+  if (op & 1) { A = xyzz_dbl_aff(P); xyzz_madd(A, P); }
+  if (op & 2) { B = xyzz_dbl_aff(Q); xyzz_madd(B, Q); }
+  xyzz r = A, s = A;
+  if (op & 4) { r = xyzz_dbl_chain(A); s = xyzz_dbl(A); }
+  else { xyzz_add_chain(r, B); xyzz_add(s, B); }
+  uint32_t *o = raw + (size_t)i * 80;
+  xyzz_store(o, r); xyzz_store(o + 40, s);
+  aff_store(out + (size_t)i * 16, xyzz_to_aff(r));
 }
 }  // namespace bppp
 
@@ -176,7 +208,7 @@ extern "C" int bppp_test_point_op(bppp_ctx *ctx, int op, const uint64_t *p, cons
   return rc;
 }
 extern "C" int bppp_test_point_quad(bppp_ctx *ctx, int op, const uint64_t *p, const uint64_t *q, size_t n, uint64_t *out, uint32_t *raw) {
-  if (!ctx || !p || !q || !out || !raw || op < 0 || op > 3) return BPPP_ERR_ARG;
+  if (!ctx || !p || !q || !out || !raw || op < 0 || op > 7) return BPPP_ERR_ARG;
   if (n == 0) return BPPP_OK;
   hipSetDevice(ctx->device);
   void *da = nullptr, *db = nullptr, *dout = nullptr, *draw = nullptr;
@@ -188,6 +220,41 @@ extern "C" int bppp_test_point_quad(bppp_ctx *ctx, int op, const uint64_t *p, co
     if (hipMemcpyAsync(out, dout, n * 64, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
         hipMemcpyAsync(raw, draw, n * 81 * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
       rc = bppp::fail(ctx, BPPP_ERR_HIP, "test_point_quad: kernel or copy failed");
+  }
+  hipFree(da); hipFree(db); hipFree(dout); hipFree(draw);
+  return rc;
+}
+extern "C" int bppp_test_fq_pair(bppp_ctx *ctx, int kind, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d, size_t n, uint32_t *raw) {
+  if (!ctx || !a || !b || !c || !d || !raw || kind < 0 || kind > 2) return BPPP_ERR_ARG;
+  if (n == 0) return BPPP_OK;
+  hipSetDevice(ctx->device);
+  uint32_t *din = nullptr, *draw = nullptr;
+  const size_t words = n * 10;
+  if (hipMalloc(&din, 4 * words * 4) != hipSuccess || hipMalloc(&draw, n * 40 * 4) != hipSuccess) { hipFree(din); return bppp::fail(ctx, BPPP_ERR_HIP, "test_fq_pair: hipMalloc"); }
+  const uint32_t *src[4] = {a, b, c, d};
+  int rc = BPPP_OK;
+  for (int k = 0; k < 4 && !rc; k++)
+    if (hipMemcpyAsync(din + k * words, src[k], words * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = bppp::fail(ctx, BPPP_ERR_HIP, "test_fq_pair: copy failed");
+  if (!rc) {
+    k_test_fq_pair<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream>>>(kind, din, din + words, din + 2 * words, din + 3 * words, (uint32_t)n, draw);
+    if (hipMemcpyAsync(raw, draw, n * 40 * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+      rc = bppp::fail(ctx, BPPP_ERR_HIP, "test_fq_pair: kernel or copy failed");
+  }
+  hipFree(din); hipFree(draw);
+  return rc;
+}
+extern "C" int bppp_test_point_chain(bppp_ctx *ctx, int op, const uint64_t *p, const uint64_t *q, size_t n, uint64_t *out, uint32_t *raw) {
+  if (!ctx || !p || !q || !out || !raw || op < 0 || op > 7) return BPPP_ERR_ARG;
+  if (n == 0) return BPPP_OK;
+  hipSetDevice(ctx->device);
+  void *da = nullptr, *db = nullptr, *dout = nullptr, *draw = nullptr;
+  int rc = run2(ctx, p, q, n, 8, out, &da, &db, &dout);
+  if (!rc && hipMalloc(&draw, n * 80 * 4) != hipSuccess) rc = bppp::fail(ctx, BPPP_ERR_HIP, "test_point_chain: hipMalloc");
+  if (!rc) {
+    k_test_point_chain<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream>>>(op, (const uint32_t *)da, (const uint32_t *)db, (uint32_t)n, (uint32_t *)dout, (uint32_t *)draw);
+    if (hipMemcpyAsync(out, dout, n * 64, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(raw, draw, n * 80 * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+      rc = bppp::fail(ctx, BPPP_ERR_HIP, "test_point_chain: kernel or copy failed");
   }
   hipFree(da); hipFree(db); hipFree(dout); hipFree(draw);
   return rc;

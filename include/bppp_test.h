@@ -25,10 +25,20 @@ int bppp_test_fe_op(bppp_ctx *ctx, int op, int modulus, const uint64_t *a, const
 int bppp_test_point_op(bppp_ctx *ctx, int op, const uint64_t *p, const uint64_t *q, size_t n, uint64_t *out);
 /* The quad forms of csrc/ec_quad.hip.h (four lanes share one point operation) against the one-lane forms, one quad per element:
  * op 0: p[i] + q[i] (xyzz_add_quad vs xyzz_add), op 2: 2 * p[i] (xyzz_dbl_quad vs xyzz_dbl); op 1 / 3: the same with the XYZZ inputs
- * pushed to the magnitude bounds (X <= 5, Y <= 3).  Inputs are affine, taken to XYZZ with ZZ != 1.  out: n x 8 uint64 affine results
+ * pushed to the magnitude bounds (X <= 5, Y <= 3); op 4 .. 7: ops 0 .. 3 with the quad forms on fq_mul_lone (csrc/fq26.hip.h), as the
+ * bucket reduction's tail runs them.  Inputs are affine, taken to XYZZ with ZZ != 1.  out: n x 8 uint64 affine results
  * of the quad form; raw: n x 81 uint32, the quad form's 40 raw limbs (X, Y, ZZ, ZZZ), the scalar form's 40, and 1 iff all four
  * lanes of the quad held the same limbs. */
 int bppp_test_point_quad(bppp_ctx *ctx, int op, const uint64_t *p, const uint64_t *q, size_t n, uint64_t *out, uint32_t *raw);
+/* The pair forms of csrc/fq26.hip.h against the one-product forms on caller-built RAW limbs (n x 10 uint32 each, any magnitude <= 8):
+ * kind 0: fq_mul2 (a b, c d), 1: fq_mul_sqr (a b, c^2; d is read but unused), 2: fq_sqr2 (a^2, c^2; b and d unused).  raw: n x 40 uint32, the pair
+ * form's two results, then fq_mul's / fq_sqr's for the same operands. */
+int bppp_test_fq_pair(bppp_ctx *ctx, int kind, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d, size_t n, uint32_t *raw);
+/* xyzz_add_chain / xyzz_dbl_chain (csrc/ec.hip.h) against xyzz_add / xyzz_dbl, one lane per element.  op bit 0: the left operand is
+ * 3 p[i], built as a sum of three points so that ZZ != 1 (else p[i] with ZZ = 1); bit 1: the right operand is 3 q[i] likewise; bit 2:
+ * double the left operand instead of adding.  out: n x 8 uint64 affine results of the chain form; raw: n x 80 uint32, the chain form's 40
+ * raw limbs (X, Y, ZZ, ZZZ), then the plain form's 40. */
+int bppp_test_point_chain(bppp_ctx *ctx, int op, const uint64_t *p, const uint64_t *q, size_t n, uint64_t *out, uint32_t *raw);
 /* Measured ceiling of the field layer: modular multiplications per second of a kernel that does nothing but independent
  * Fq multiplications (10x26-bit limbs) at 8 wavefronts per SIMD.  bench.py quotes the MSM's multiplication rate against it. */
 int bppp_test_mulmod_rate(bppp_ctx *ctx, int iters, double *mulmods_per_sec);
