@@ -39,6 +39,8 @@ SYMBOLS = [
     "bppp_rp_verify_bound", "bppp_rp_verify_bound_device", "bppp_rp_verify_each_bound", "bppp_rp_verify_each_bound_device", "bppp_rp_prove_bound", "bppp_rp_prove_bound_device",
     "bppp_rp_commit_batch", "bppp_rp_commit_batch_device", "bppp_rp_open_each", "bppp_rp_open_each_device", "bppp_rp_open_batch", "bppp_rp_open_batch_device",
     "bppp_rp_tally_each", "bppp_rp_tally_each_device", "bppp_rp_tally_batch", "bppp_rp_tally_batch_device", "bppp_rp_tally_claims", "bppp_rp_tally_claims_device",
+    "bppp_rp_excess_sign", "bppp_rp_excess_sign_device", "bppp_rp_excess_verify_each", "bppp_rp_excess_verify_each_device", "bppp_rp_excess_verify_batch",
+    "bppp_rp_excess_verify_batch_device",
     "bppp_seed_candidate_x", "bppp_points_from_seed", "bppp_points_from_seed_device", "bppp_rp_create_seeded", "bppp_rp_create_binary_seeded",
 ]
 
@@ -179,6 +181,12 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_tally_batch_device.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, C.c_uint64, vp, C.POINTER(i), vp, vp]
     lib.bppp_rp_tally_claims.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, sz, vp, vp, vp]
     lib.bppp_rp_tally_claims_device.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, sz, vp, vp, vp]
+    lib.bppp_rp_excess_sign.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
+    lib.bppp_rp_excess_sign_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
+    lib.bppp_rp_excess_verify_each.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]
+    lib.bppp_rp_excess_verify_each_device.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]
+    lib.bppp_rp_excess_verify_batch.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, C.POINTER(i), vp, vp]
+    lib.bppp_rp_excess_verify_batch_device.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, C.c_uint64, vp, C.POINTER(i), vp, vp]
     lib.bppp_seed_candidate_x.argtypes = [C.c_char_p, sz, C.c_uint64, vp]
     lib.bppp_points_from_seed.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
     lib.bppp_points_from_seed_device.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
@@ -213,6 +221,7 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_rp_set_tally_short_max.argtypes = [vp, sz]
     lib.bppp_test_rp_set_tally_piece.argtypes = [vp, sz]
     lib.bppp_test_rp_set_tally_chunk.argtypes = [vp, sz]
+    lib.bppp_test_rp_excess_mul.argtypes = [vp, sz, vp, vp, vp]
     lib.bppp_test_rp_witness_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.bppp_test_points_from_seed_chunked.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, sz, vp, C.POINTER(C.c_uint64)]
     lib.bppp_test_seed_lift_digests.argtypes = [vp, C.c_char_p, sz, vp, vp, vp]
@@ -278,6 +287,10 @@ RP_WIT_OK, RP_WIT_NOT_CANONICAL, RP_WIT_UNBALANCED, RP_WIT_OUT_OF_RANGE, RP_WIT_
 # bppp_rp_commit_batch's own row verdict next to RP_WIT_OK / _NOT_CANONICAL / _BIN_NOT_CANONICAL, and BPPP_RP_OPEN_*: one opening's verdict
 RP_COMMIT_INFINITY = 16
 RP_OPEN_OK, RP_OPEN_MISMATCH, RP_OPEN_MALFORMED, RP_OPEN_NOT_CANONICAL = 0, 1, 2, 3
+# BPPP_RP_EXCESS_*: bppp_rp_excess_sign's verdicts, and the two bppp_rp_excess_verify_* add to RP_OPEN_*
+RP_EXCESS_OK, RP_EXCESS_NOT_CANONICAL, RP_EXCESS_ZERO, RP_EXCESS_NONCE = 0, 1, 2, 3
+RP_EXCESS_BAD_R, RP_EXCESS_NO_KEY = 4, 5
+RP_EXCESS_SIG_BYTES = 65
 # BPPP_RP_BINDING_BYTES: one proof's transcript binding of the bppp_rp_*_bound* entry points
 RP_BINDING_BYTES = 32
 

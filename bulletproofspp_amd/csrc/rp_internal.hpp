@@ -12,6 +12,7 @@
 #include "hostmath.hpp"
 #include "rpsetup.hpp"
 #include "hostpool.hpp"
+#include "rptally_plan.hpp"
 
 struct bppp_trrp;
 struct bppp_nlb;
@@ -292,6 +293,37 @@ void rp_decode_coms(bppp_rp *rp, size_t nb, const uint8_t *d_coms, uint32_t *pts
 static constexpr unsigned RPP_REDUCE_BLOCKS = 1024;
 int rpp_claim_scalars(bppp_rp *rp, uint64_t n, const uint32_t *amounts, const uint32_t *types, const uint32_t *blinds, uint32_t *in_sc, uint32_t *flag, uint32_t *any);
 int rpp_negated_column_sums(bppp_rp *rp, uint64_t n, const uint32_t *prods, uint32_t *part, uint32_t *out);
+}  // namespace bppp
+namespace bppp {
+// ---- the stage the tally entry points (csrc/rptally.hip, which defines it) and the excess signatures (csrc/rpexcess.hip) share: the job's
+// checks, the pool decoded once, the plan of a pass and the segmented signed sums of its sums
+namespace tally {
+using bppp_tally::Levels;
+// one call's arguments, all in HBM, and what the checks established
+struct Job {
+  bppp_rp *rp; const char *who;
+  size_t rows, nsums, nnz;
+  const uint8_t *coms; const uint32_t *start, *entries, *amt, *ty, *bl;
+  std::vector<uint32_t> h_start;               // sum_start on the host, after validation
+  bool zero_claims = false;
+};
+struct Work {
+  uint32_t *pool, *bad, *any, *sums, *malformed, *in_sc, *flag, *rec, *status, *zz, *zinv, *xy, *zero, *part[2];
+  uint4 *items;
+  uint32_t *rho, *prods, *red, *sc3, *msm_sc, *msm_pt;
+  uint8_t *seed, *extra;
+};
+// claims: the three claim arrays of a tally are judged too (all given or all NULL)
+int tally_checks(Job &J, bool null_args, bool claims);
+std::vector<size_t> chunk_bounds(const Job &J);
+Levels plan_levels(const Job &J, size_t t0, size_t t1);
+int carve(const Job &J, size_t ns, bool each, size_t ni, const size_t np[2], bool batch, size_t ne, Work &W, size_t extra = 0);
+int decode_pool(const Job &J, const Work &W);
+// W.sums [ns][XYZZ_WORDS] and W.malformed [ns] of the sums [t0, t0 + ns), planned as L; zeroes W.any[0..1]
+int sum_launches(const Job &J, const Work &W, size_t t0, size_t ns, const Levels &L);
+// k_rp_tally_affine: n XYZZ points and the inverses of their ZZ ZZZ (zero: the all-zero point) -> affine
+int affine_launch(bppp_ctx *ctx, size_t n, const uint32_t *sums, const uint32_t *zinv, uint32_t *out);
+}  // namespace tally
 }  // namespace bppp
 int rp_ensure_comb(bppp_rp *rp);      // csrc/rpprove.hip
 // the handle (and its twin) proves over table t from now on (nullptr: none): t gains a holder, the table held before loses one and is

@@ -7,25 +7,9 @@
 #pragma once
 #include "ec.hip.h"
 #include "rp_internal.hpp"
+#include "rplift.hip.h"
 
 namespace bppp {
-
-// Binary (Prime p) get (Encoding.hs:76-80): limb i = big-endian 64-bit word at bytes 8i..8i+7, least-significant limb first;
-// toP reduces (one conditional subtraction: the value is < 2^256 < 2m)
-template <int MOD> BPPP_DI fe load_field_be(const uint8_t *p) {
-  fe v;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const uint8_t *q = p + 8 * i;
-    v.v[2 * i + 1] = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3];
-    v.v[2 * i] = ((uint32_t)q[4] << 24) | ((uint32_t)q[5] << 16) | ((uint32_t)q[6] << 8) | q[7];
-  }
-  fe t;
-  uint32_t br = raw_sub(t, v, modulus<MOD>());
-#pragma unroll
-  for (int i = 0; i < 8; i++) v.v[i] = br ? v.v[i] : t.v[i];
-  return v;
-}
 
 // Point t of a proof IN TRANSCRIPT ORDER (newest first, the order shaOracle's final call sees, src/ZKP.hs:98):
 //   t < 2k            the argument's responses, last round first  = bpComs of the proof file (RangeProof.hs:60-66)
@@ -52,18 +36,8 @@ __global__ void __launch_bounds__(64) k_rp_decode_points(RpDims D, uint32_t batc
     idx = t - 2 * D.k - D.nrp;
   }
   const bool want_big = (signs[idx >> 3] >> (idx & 7)) & 1;
-  const fe xe = load_field_be<0>(xs + (size_t)idx * 32);
-  const fq x = fq_from_fe(xe);
-  fq seven = fq_zero(); seven.n[0] = 7;
-  const fq rhs = fq_add(fq_mul(fq_sqr(x), x), seven);         // magnitude 2
-  fq y = fq_sqrt_candidate(rhs);
-  const bool ok = fq_normalizes_to_zero(fq_sub<2>(fq_sqr(y), rhs));
-  y = fq_normalize(y);
-  // fromXWithSign (Encoding.hs:97-103): keep the root whose (y > p - y) equals the sign bit
-  const fe ye = fq_to_fe(y), yn = fe_neg<0>(ye);
-  fe d;
-  const bool y_big = raw_sub(d, yn, ye) != 0;                  // -y < y
-  aff r; r.x = x; r.y = (y_big != want_big) ? fq_from_fe(yn) : y;
+  bool ok;
+  aff r = rp_lift_x(load_field_be<0>(xs + (size_t)idx * 32), want_big, ok);
   if (!ok) { r = aff_inf(); atomicOr(bad + b, 1u); atomicOr(any_bad, 1u); }
   uint32_t *out = t < 2 * D.k ? resp_pts + ((size_t)b * 2 * D.k + t) * 16
                               : init_pts + ((size_t)b * (D.nrp + D.nr) + (t - 2 * D.k)) * 16;

@@ -14,6 +14,8 @@
 //   k_rp_tally_terms     per entry: scalar +-rho_t and the gathered point, the MSM's input
 //   k_rp_tally_claims    the builder's side: signed sums mod n of the referenced (amount, type, blinding), one wavefront per sum
 // Every kernel is bounds-checked on its own index, takes its loop bounds from validated arrays only, and writes with ordinary vector stores.
+// The job's checks, the decoded pool, the plan of a pass and the k_rp_tally_sum launches are declared in rp_internal.hpp (bppp::tally): the excess
+// signatures (csrc/rpexcess.hip) run the same stage.
 #include <string.h>
 #include <algorithm>
 #include <string>
@@ -235,18 +237,8 @@ __global__ void __launch_bounds__(256) k_rp_tally_claims(uint32_t nsums, uint32_
 
 }  // namespace bppp
 
-using namespace bppp;
-
-namespace {
-
-// one call's arguments, all in HBM, and what the checks established
-struct Job {
-  bppp_rp *rp; const char *who;
-  size_t rows, nsums, nnz;
-  const uint8_t *coms; const uint32_t *start, *entries, *amt, *ty, *bl;
-  std::vector<uint32_t> h_start;               // sum_start on the host, after validation
-  bool zero_claims = false;
-};
+namespace bppp {
+namespace tally {
 
 // the call-level checks of a non-empty job; then the CSR conditions by k_rp_tally_validate, its flag read back before anything gathers
 int tally_checks(Job &J, bool null_args, bool claims) {
@@ -288,21 +280,15 @@ int tally_checks(Job &J, bool null_args, bool claims) {
   return BPPP_OK;
 }
 
-using bppp_tally::Levels;
 static_assert(sizeof(bppp_tally::Item) == sizeof(uint4), "an item is the kernel's uint4");
 std::vector<size_t> chunk_bounds(const Job &J) { return bppp_tally::chunk_bounds(J.h_start.data(), J.nsums, J.rp->tally_chunk); }
 Levels plan_levels(const Job &J, size_t t0, size_t t1) {
   return bppp_tally::plan_levels(J.h_start.data(), t0, t1, (uint32_t)std::min<size_t>(J.rp->tally_short_max, 0xFFFFFFFFu), (uint32_t)std::min<size_t>(J.rp->tally_piece, 0x7FFFFFFFu));
 }
 
-struct Work {
-  uint32_t *pool, *bad, *any, *sums, *malformed, *in_sc, *flag, *rec, *status, *zz, *zinv, *xy, *zero, *part[2];
-  uint4 *items;
-  uint32_t *rho, *prods, *red, *sc3, *msm_sc, *msm_pt;
-  uint8_t *seed;
-};
-// ns: the sums of the largest chunk; each: the per-sum pass (ni items, np[2] partial points); batch: the weighted combination (ne entries a MSM)
-int carve(const Job &J, size_t ns, bool each, size_t ni, const size_t np[2], bool batch, size_t ne, Work &W) {
+// ns: the sums of the largest chunk; each: the per-sum pass (ni items, np[2] partial points); batch: the weighted combination (ne entries a MSM);
+// extra: bytes behind everything else for the caller's own arrays (csrc/rpexcess.hip), so that the arrays above lie where they lay without them
+int carve(const Job &J, size_t ns, bool each, size_t ni, const size_t np[2], bool batch, size_t ne, Work &W, size_t extra) {
   bppp_rp *rp = J.rp;
   const size_t total = J.rows * rp->D.nr, R = std::max<size_t>(1, std::min<size_t>(J.rows, ((size_t)1 << 22) / rp->D.nr));
   for (int pass = 0; pass < 2; pass++) {
@@ -315,7 +301,7 @@ int carve(const Job &J, size_t ns, bool each, size_t ni, const size_t np[2], boo
     for (int k = 0; k < 2; k++) W.part[k] = cv.take<uint32_t>(each ? np[k] * XYZZ_WORDS : 0);
     W.rho = cv.take<uint32_t>(batch ? ns * 8 : 0); W.prods = cv.take<uint32_t>(batch ? ns * 24 : 0); W.red = cv.take<uint32_t>(batch ? (size_t)RPP_REDUCE_BLOCKS * 24 : 0);
     W.sc3 = cv.take<uint32_t>(24); W.msm_sc = cv.take<uint32_t>(batch ? (ne + 3) * 8 : 0); W.msm_pt = cv.take<uint32_t>(batch ? (ne + 3) * 16 : 0);
-    W.seed = cv.take<uint8_t>(32);
+    W.seed = cv.take<uint8_t>(32); W.extra = cv.take<uint8_t>(extra);
     if (!pass) { int rc = rpp_ensure_pwork(rp, cv.off); if (rc) return rc; }
   }
   return BPPP_OK;
@@ -334,6 +320,42 @@ int decode_pool(const Job &J, const Work &W) {
   }
   return BPPP_OK;
 }
+
+// the signed sums of [t0, t0 + ns) into W.sums, their malformed flags into W.malformed: one lane a short sum, then the plan's levels
+int sum_launches(const Job &J, const Work &W, size_t t0, size_t ns, const Levels &L) {
+  bppp_rp *rp = J.rp;
+  bppp_ctx *ctx = rp->ctx;
+  hipStream_t st = ctx->stream;
+  const uint32_t smax = (uint32_t)rp->tally_short_max;
+  BPPP_HIP(ctx, hipMemsetAsync(W.malformed, 0, ns * 4, st));
+  BPPP_HIP(ctx, hipMemsetAsync(W.any, 0, 8, st));
+  k_rp_tally_sum<<<dim3((unsigned)((ns + TALLY_LANES - 1) / TALLY_LANES)), dim3(TALLY_LANES), 0, st>>>(0u, (uint32_t)ns, smax, J.start + t0, J.entries, W.pool, nullptr, nullptr, nullptr,
+                                                                                                    W.sums, W.malformed);
+  size_t io = 0;
+  for (size_t k = 0; k < L.lv.size(); k++) {
+    const std::vector<bppp_tally::Item> &items = L.lv[k];
+    BPPP_HIP(ctx, hipMemcpyAsync(W.items + io, items.data(), items.size() * sizeof(uint4), hipMemcpyHostToDevice, st));
+    k_rp_tally_sum<<<dim3((unsigned)items.size()), dim3(TALLY_LANES), 0, st>>>(k ? 2u : 1u, (uint32_t)items.size(), smax, J.start + t0, J.entries, W.pool, W.items + io,
+                                                                             W.part[(k + 1) & 1], W.part[k & 1], W.sums, W.malformed);
+    io += items.size();
+  }
+  BPPP_HIP(ctx, hipGetLastError());
+  return BPPP_OK;
+}
+
+int affine_launch(bppp_ctx *ctx, size_t n, const uint32_t *sums, const uint32_t *zinv, uint32_t *out) {
+  k_rp_tally_affine<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream>>>((uint32_t)n, sums, zinv, out);
+  BPPP_HIP(ctx, hipGetLastError());
+  return BPPP_OK;
+}
+
+}  // namespace tally
+}  // namespace bppp
+
+using namespace bppp;
+using namespace bppp::tally;
+
+namespace {
 
 // sums [t0, t0 + ns): the claimed scalars in W.in_sc / W.flag, W.any[1] raised by a non-canonical one
 int claim_scalars(const Job &J, const Work &W, size_t t0, size_t ns) {
@@ -362,31 +384,16 @@ int each_pass(const Job &J, uint32_t *status, uint64_t *sums_xy) {
   }
   Work W;
   if ((rc = carve(J, ns_max, true, ni, np, false, 0, W)) || (rc = decode_pool(J, W))) return rc;
-  const uint32_t smax = (uint32_t)rp->tally_short_max;
   for (size_t c = 0; c + 1 < cb.size(); c++) {
     const size_t t0 = cb[c], ns = cb[c + 1] - t0;
-    const Levels &L = plans[c];
-    BPPP_HIP(ctx, hipMemsetAsync(W.malformed, 0, ns * 4, st));
-    BPPP_HIP(ctx, hipMemsetAsync(W.any, 0, 8, st));
-    k_rp_tally_sum<<<dim3((unsigned)((ns + TALLY_LANES - 1) / TALLY_LANES)), dim3(TALLY_LANES), 0, st>>>(0u, (uint32_t)ns, smax, J.start + t0, J.entries, W.pool, nullptr, nullptr, nullptr,
-                                                                                                      W.sums, W.malformed);
-    size_t io = 0;
-    for (size_t k = 0; k < L.lv.size(); k++) {
-      const std::vector<bppp_tally::Item> &items = L.lv[k];
-      BPPP_HIP(ctx, hipMemcpyAsync(W.items + io, items.data(), items.size() * sizeof(uint4), hipMemcpyHostToDevice, st));
-      k_rp_tally_sum<<<dim3((unsigned)items.size()), dim3(TALLY_LANES), 0, st>>>(k ? 2u : 1u, (uint32_t)items.size(), smax, J.start + t0, J.entries, W.pool, W.items + io,
-                                                                               W.part[(k + 1) & 1], W.part[k & 1], W.sums, W.malformed);
-      io += items.size();
-    }
-    BPPP_HIP(ctx, hipGetLastError());
+    if ((rc = sum_launches(J, W, t0, ns, plans[c]))) return rc;
     if ((rc = claim_scalars(J, W, t0, ns)) || (rc = rpp_commit_inputs(rp, W.in_sc, ns, W.rec))) return rc;
     k_rp_tally_compare<<<dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st>>>((uint32_t)ns, W.sums, W.rec, W.flag, W.malformed, W.status, sums_xy ? W.zz : nullptr);
     BPPP_HIP(ctx, hipGetLastError());
     BPPP_HIP(ctx, hipMemcpyAsync(status + t0, W.status, ns * 4, hipMemcpyDeviceToHost, st));
     if (sums_xy) {
       if ((rc = batch_inverse_run(ctx, W.zz, ns, 0, W.zinv))) return rc;
-      k_rp_tally_affine<<<dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st>>>((uint32_t)ns, W.sums, W.zinv, W.xy);
-      BPPP_HIP(ctx, hipGetLastError());
+      if ((rc = affine_launch(ctx, ns, W.sums, W.zinv, W.xy))) return rc;
       BPPP_HIP(ctx, hipMemcpyAsync(sums_xy + t0 * 8, W.xy, ns * 64, hipMemcpyDeviceToHost, st));
     }
     BPPP_HIP(ctx, hipStreamSynchronize(st));

@@ -9,6 +9,7 @@
 #include "rp_internal.hpp"
 #include "rpwitness.hip.h"
 #include "rpdecode.hip.h"
+#include "rpexcess.hip.h"
 #include "seedpoints.hip.h"
 #include "comb.hip.h"
 #include "rpp_transcript.hpp"
@@ -360,6 +361,24 @@ extern "C" int bppp_test_rp_set_tally_chunk(bppp_rp *rp, size_t entries) {
   if (!rp) return BPPP_ERR_ARG;
   rp->tally_chunk = entries ? entries : bppp_rp().tally_chunk;
   return BPPP_OK;
+}
+
+// one quad per instance; all four lanes hold the product, lane 0 of the quad inverts and stores
+namespace bppp {
+__global__ void __launch_bounds__(64) k_test_excess_mul(uint32_t n, const uint32_t *__restrict__ sc, const uint32_t *__restrict__ pts, uint32_t *__restrict__ out) {
+  const uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) >> 2;
+  if (i >= n) return;
+  const xyzz r = excess_mul_quad(fe_load(sc + (size_t)i * 8), aff_load(pts + (size_t)i * 16));
+  if (quad_lane() == 0) aff_store(out + (size_t)i * 16, xyzz_to_aff(r));
+}
+}  // namespace bppp
+extern "C" int bppp_test_rp_excess_mul(bppp_rp *rp, size_t n, const void *d_scalars, const void *d_points_xy, void *d_out_xy) {
+  if (!rp || !n || n >= (1u << 24) || !d_scalars || !d_points_xy || !d_out_xy) return BPPP_ERR_ARG;
+  bppp_ctx *ctx = rp->ctx;
+  hipSetDevice(ctx->device);
+  k_test_excess_mul<<<dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, ctx->stream>>>((uint32_t)n, (const uint32_t *)d_scalars, (const uint32_t *)d_points_xy, (uint32_t *)d_out_xy);
+  const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
+  return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_rp_excess_mul: kernel failed");
 }
 
 extern "C" int bppp_test_rp_witness_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds, const void *d_public_amounts,

@@ -1263,6 +1263,113 @@ class NativeRangeProofs:
                                                       p(d_claim_types), p(d_claim_blinds))
         self.gpu._check(rc, "bppp_rp_tally_claims_device")
 
+    # ---- excess signatures: a tally checked without revealing the blinding sum (bppp_rp_excess_sign / _verify_each / _verify_batch)
+    @staticmethod
+    def _excess_bytes(rows, width, what):
+        import numpy as np
+        if any(len(r) != width for r in rows):
+            raise ValueError("%s of %d bytes each are required" % (what, width))
+        return np.frombuffer(b"".join(rows) or b"\0", dtype=np.uint8)
+
+    def _excess_claim_arrays(self, claims, nsums):
+        """the public claims, one (amount, type) per sum ((amount,) or a plain amount on a binary handle; longer tuples are cut), as two
+        [nsums][4] word arrays; None: no arrays, every claim is zero"""
+        from .capi import scalars_to_array
+        if claims is None:
+            return None, None
+        if len(claims) != nsums:
+            raise ValueError("one claim per sum is required")
+        rows = [c if isinstance(c, (tuple, list)) else (c,) for c in claims]
+        typed = isinstance(self.st, SetupTRRP)
+        return (scalars_to_array([tally_amount_word(c[0]) for c in rows] or [0]), scalars_to_array([c[1] for c in rows] or [0]) if typed else None)
+
+    def excess_sign(self, blinds: Sequence[int], msgs: Sequence[bytes], aux: bytes = bytes(32), want_status: bool = False, want_points: bool = False):
+        """bppp_rp_excess_sign: one signature per sum over msgs[t] with the blinding sum blinds[t] (tally_claims' last component).  Returns the
+        65-byte signatures, or (signatures, statuses or None, excess points or None) as asked; without want_status a refused sum raises BpppError."""
+        import ctypes as C
+        import numpy as np
+        from .capi import scalars_to_array
+        n = len(blinds)
+        if len(msgs) != n or len(aux) != 32:
+            raise ValueError("one 32-byte message per sum and 32 bytes of aux are required")
+        bl, mg = scalars_to_array(list(blinds) or [0]), self._excess_bytes(msgs, 32, "messages")
+        sg = np.zeros(max(n, 1) * EXCESS_SIG_BYTES, dtype=np.uint8)
+        vp = lambda a: C.c_void_p(a.ctypes.data)
+        return self._excess_sign(self.gpu.lib.bppp_rp_excess_sign, n, vp(bl), vp(mg), aux, vp(sg), want_status, want_points, lambda: sg)
+
+    def excess_sign_device(self, nsums: int, d_blinds: int, d_msgs: int, d_sigs: int, aux: bytes = bytes(32), want_status: bool = False, want_points: bool = False):
+        """bppp_rp_excess_sign_device: excess_sign on buffers in HBM (d_sigs receives [nsums][65] bytes); returns (statuses or None, points or None)"""
+        import ctypes as C
+        p = C.c_void_p
+        return self._excess_sign(self.gpu.lib.bppp_rp_excess_sign_device, nsums, p(d_blinds), p(d_msgs), aux, p(d_sigs), want_status, want_points, None)
+
+    def _excess_sign(self, fn, n, pb, pm, aux, ps, want_status, want_points, sigs):
+        import ctypes as C
+        import numpy as np
+        from .capi import array_to_point
+        status, xy, ax = np.zeros(max(n, 1), dtype=np.uint32), np.zeros((max(n, 1), 8), dtype=np.uint64), np.frombuffer(aux, dtype=np.uint8)
+        rc = fn(self.h, n, pb, pm, C.c_void_p(ax.ctypes.data), ps, C.c_void_p(xy.ctypes.data) if want_points else None, C.c_void_p(status.ctypes.data) if want_status else None)
+        self.gpu._check(rc, "bppp_rp_excess_sign")
+        st = [int(v) for v in status[:n]] if want_status else None
+        pts = [array_to_point(xy[t]) for t in range(n)] if want_points else None
+        if sigs is None:
+            return st, pts
+        raw = sigs().tobytes()
+        out = [raw[t * EXCESS_SIG_BYTES:(t + 1) * EXCESS_SIG_BYTES] for t in range(n)]
+        return (out, st, pts) if (want_status or want_points) else out
+
+    def _excess_host_args(self, coms_files, sum_start, entries, claims, msgs, sigs):
+        import ctypes as C
+        ss, en, nsums, nnz = self._tally_csr(sum_start, entries)
+        if len(msgs) != nsums or len(sigs) != nsums:
+            raise ValueError("one message and one signature per sum are required")
+        amt, typ = self._excess_claim_arrays(claims, nsums)
+        keep = [self._coms_array(coms_files, len(coms_files)), ss, en, amt, typ, self._excess_bytes(msgs, 32, "messages"), self._excess_bytes(sigs, EXCESS_SIG_BYTES, "signatures")]
+        vp = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+        cf, ss, en, amt, typ, mg, sg = keep
+        return keep, nsums, (len(coms_files), vp(cf), nsums, vp(ss), vp(en), nnz, vp(amt), vp(typ), vp(mg), vp(sg))
+
+    def excess_verify_each(self, coms_files: Sequence[bytes], sum_start, entries, claims, msgs: Sequence[bytes], sigs: Sequence[bytes], want_points: bool = False):
+        """bppp_rp_excess_verify_each: does sigs[t] sign msgs[t] under the excess of sum t over the public claims[t] ((amount, type); a binary
+        handle: the amount)?  Returns one verdict per sum (capi.RP_OPEN_* / RP_EXCESS_BAD_R / RP_EXCESS_NO_KEY), or (verdicts, excess points)."""
+        keep, nsums, args = self._excess_host_args(coms_files, sum_start, entries, claims, msgs, sigs)
+        return self._excess_each(self.gpu.lib.bppp_rp_excess_verify_each, nsums, args, want_points)
+
+    def excess_verify_each_device(self, rows: int, d_coms: int, nsums: int, d_sum_start: int, d_entries: int, nnz: int, d_amounts: int, d_types: int, d_msgs: int,
+                                  d_sigs: int, want_points: bool = False):
+        """bppp_rp_excess_verify_each_device: excess_verify_each on buffers in HBM (0 for both claim arrays: zero claims)"""
+        import ctypes as C
+        p = C.c_void_p
+        return self._excess_each(self.gpu.lib.bppp_rp_excess_verify_each_device, nsums,
+                                 (rows, p(d_coms), nsums, p(d_sum_start), p(d_entries), nnz, p(d_amounts), p(d_types), p(d_msgs), p(d_sigs)), want_points)
+
+    def _excess_each(self, fn, nsums, args, want_points):
+        import ctypes as C
+        import numpy as np
+        from .capi import array_to_point
+        status, xy = np.zeros(max(nsums, 1), dtype=np.uint32), np.zeros((max(nsums, 1), 8), dtype=np.uint64)
+        self.gpu._check(fn(self.h, *args, C.c_void_p(status.ctypes.data), C.c_void_p(xy.ctypes.data) if want_points else None), "bppp_rp_excess_verify_each")
+        out = [int(v) for v in status[:nsums]]
+        return (out, [array_to_point(xy[t]) for t in range(nsums)]) if want_points else out
+
+    def excess_verify_batch(self, coms_files: Sequence[bytes], sum_start, entries, claims, msgs: Sequence[bytes], sigs: Sequence[bytes], seed: Optional[bytes] = None,
+                            want_status: bool = False, want_point: bool = False):
+        """bppp_rp_excess_verify_batch: every signature checked with one weighted combination (weights: excess_weight below).  Returns accept, or
+        (accept, verdicts or None, combined point or None) when want_status / want_point is set."""
+        keep, nsums, args = self._excess_host_args(coms_files, sum_start, entries, claims, msgs, sigs)
+        fn = lambda *a: self.gpu.lib.bppp_rp_excess_verify_batch(self.h, *args, *a)
+        return self._tally_batch(fn, nsums, seed, want_status, want_point)
+
+    def excess_verify_batch_device(self, rows: int, d_coms: int, nsums: int, d_sum_start: int, d_entries: int, nnz: int, d_amounts: int, d_types: int, d_msgs: int,
+                                   d_sigs: int, seed: Optional[bytes] = None, index_offset: int = 0, want_status: bool = False, want_point: bool = False):
+        """bppp_rp_excess_verify_batch_device: excess_verify_batch on buffers in HBM; this call holds sums [index_offset, index_offset + nsums) of a
+        sharded job whose ranks all pass the same seed (their combined points add up to the one-call point)"""
+        import ctypes as C
+        p = C.c_void_p
+        fn = lambda *a: self.gpu.lib.bppp_rp_excess_verify_batch_device(self.h, rows, p(d_coms), nsums, p(d_sum_start), p(d_entries), nnz, p(d_amounts), p(d_types),
+                                                                        p(d_msgs), p(d_sigs), index_offset, *a)
+        return self._tally_batch(fn, nsums, seed, want_status, want_point)
+
     def share_comb(self, donor: "NativeRangeProofs"):
         """bppp_rp_share_comb: prove over `donor`'s comb table from now on (built now if it has none).  Same context; the donor's basis
         must extend this handle's point by point.  The table lives until its last user is closed."""
@@ -1456,6 +1563,90 @@ def tally_claims_host(triples: Sequence[Tuple[int, int, int]], sum_start: Sequen
                 acc[k] += sign * triples[e & (TALLY_SUBTRACT - 1)][k]
         out.append(tuple(v % N for v in acc))
     return out
+
+
+# ----------------------------------------------------------------------------- excess signatures (bppp_rp_excess_*; include/bppp.h states every message)
+FIELD_P = 2**256 - 2**32 - 977
+EXCESS_SIG_BYTES = 65
+EXCESS_OK, EXCESS_NOT_CANONICAL, EXCESS_ZERO, EXCESS_NONCE, EXCESS_BAD_R, EXCESS_NO_KEY = 0, 1, 2, 3, 4, 5
+
+
+def _put(s: int) -> bytes:
+    """Binary (Prime p) put (Encoding.hs:81-86): the four 64-bit limbs least significant first, each big-endian"""
+    return b"".join(((s >> (64 * i)) & (2**64 - 1)).to_bytes(8, "big") for i in range(4))
+
+
+def _point33(p: Tuple[int, int]) -> bytes:
+    """put (x) and the sign byte (y > p - y) of an affine point"""
+    return _put(p[0]) + bytes([1 if p[1] > FIELD_P - p[1] else 0])
+
+
+def excess_nonce(tag: bytes, e: int, msg: bytes, aux: bytes) -> int:
+    """k = decode (SHA-256 (Dn || put (e) || msg || aux)) mod n, Dn = SHA-256 ("bppp/excess/nonce/v1" || tag): 128 bytes"""
+    return decode_field(hashlib.sha256(hashlib.sha256(b"bppp/excess/nonce/v1" + tag).digest() + _put(e) + msg + aux).digest(), N)
+
+
+def excess_challenge(tag: bytes, r33: bytes, X: Tuple[int, int], msg: bytes) -> int:
+    """c = decode (SHA-256 (Dc || the 33 bytes of R as the signature holds them || put (X.x) || sign (X) || msg)) mod n,
+    Dc = SHA-256 ("bppp/excess/challenge/v1" || tag): 130 bytes"""
+    return decode_field(hashlib.sha256(hashlib.sha256(b"bppp/excess/challenge/v1" + tag).digest() + r33 + _point33(X) + msg).digest(), N)
+
+
+def excess_weight(seed: bytes, t: int, sig: bytes, X: Tuple[int, int], msg: bytes) -> int:
+    """rho_t of bppp_rp_excess_verify_batch: decode (SHA-256 (seed || le64 (t) || sig[65] || put (X.x) || sign (X) || msg)) mod n, 1 for 0: 170 bytes"""
+    return decode_field(hashlib.sha256(seed + (t % 2**64).to_bytes(8, "little") + sig + _point33(X) + msg).digest(), N) or 1
+
+
+def _excess_bases(setup):
+    """(g, H0 or None, B): B = H1 of a typed setup, h0 of a binary one (which has no type base)"""
+    return (setup.g, setup.hs[0], setup.hs[1]) if isinstance(setup, SetupTRRP) else (setup.g, None, setup.hs[0])
+
+
+def _commit_terms(backend: "Backend", terms) -> Point:
+    terms = [(s % N, p) for s, p in terms if p is not None and s % N]
+    return backend.commit([s for s, _ in terms], [p for _, p in terms]) if terms else None
+
+
+def excess_sign_host(backend: "Backend", setup, e: int, msg: bytes, aux: bytes, tag: bytes = b""):
+    """Host restatement of bppp_rp_excess_sign for one sum: (status, the 65 signature bytes, X = e B); a refused sum has zero bytes and no point"""
+    _, _, B = _excess_bases(setup)
+    status = EXCESS_NOT_CANONICAL if not 0 <= e < N else EXCESS_ZERO if e == 0 else EXCESS_OK
+    k = excess_nonce(tag, e, msg, aux) if status == EXCESS_OK else 0
+    if status == EXCESS_OK and k == 0:
+        status = EXCESS_NONCE
+    if status != EXCESS_OK:
+        return status, bytes(EXCESS_SIG_BYTES), None
+    R, X = backend.commit([k], [B]), backend.commit([e], [B])
+    r33 = _point33(R)
+    return status, r33 + _put((k + excess_challenge(tag, r33, X, msg) * e) % N), X
+
+
+def excess_key_host(backend: "Backend", setup, S: Point, claim) -> Point:
+    """X = S - a g - ty H0 (a binary setup: S - a g); claim = (a, ty, ...) typed, (a, ...) binary"""
+    g, H0, _ = _excess_bases(setup)
+    return _commit_terms(backend, [(1, S), (-claim[0], g)] + ([(-claim[1], H0)] if H0 is not None else []))
+
+
+def excess_verify_host(backend: "Backend", setup, S: Point, claim, msg: bytes, sig: bytes, tag: bytes = b"", malformed: bool = False) -> int:
+    """Host restatement of bppp_rp_excess_verify_each for one sum S (None: the identity; malformed: some referenced x has no curve point):
+    the first verdict that applies, in the header's order"""
+    _, H0, B = _excess_bases(setup)
+    if malformed:
+        return 2
+    s = sum(int.from_bytes(sig[33 + 8 * i:41 + 8 * i], "big") << (64 * i) for i in range(4))
+    if (H0 is not None and not 0 <= claim[1] < N) or s >= N:
+        return 3
+    x = decode_field(sig[:32], FIELD_P)
+    y = pow((x * x * x + 7) % FIELD_P, (FIELD_P + 1) // 4, FIELD_P)
+    if sig[32] > 1 or (y * y - x * x * x - 7) % FIELD_P:
+        return EXCESS_BAD_R
+    if (y > FIELD_P - y) != bool(sig[32]):
+        y = FIELD_P - y
+    X = excess_key_host(backend, setup, S, claim)
+    if X is None:
+        return EXCESS_NO_KEY
+    c = excess_challenge(tag, sig[:33], X, msg)
+    return 0 if _commit_terms(backend, [(s, B), (-c, X)]) == (x, y) else 1
 
 
 def _mixed_groups(files):

@@ -723,6 +723,9 @@ int bppp_rp_open_batch_device(bppp_rp *rp, size_t batch, uint64_t index_offset, 
  * The homomorphic check next to commit / open: a set of commitments adds up.  A validator checks that inputs - outputs - fee g is a commitment
  * to zero with a known excess blinding; an auditor checks that a book of commitments sums to a stated total.  The shapes that prove balance
  * inside the proof (conserved typed-reciprocal and conserved binary) do not need it; every other shape, and any untyped handle, does.
+ * "Known" means TOLD: the claim of a tally includes e_t, the signed sum of the blindings, so these calls serve a checker who is shown the
+ * books.  A checker who is not told e_t (a public validator) takes the excess signatures below, bppp_rp_excess_verify_*, over the same pool
+ * and the same sums: the builder proves that it knows e_t instead of revealing it.
  *
  * POOL.  coms_files [rows][coms_bytes] of handle rp, exactly as bppp_rp_open_each takes it.  Commitment i of row r has the flat index
  * j = r * nranges + i; rows * nranges < 2^31, so bit 31 of an index is free.  The pool is decoded once per call (64 bytes a commitment in
@@ -792,6 +795,86 @@ int bppp_rp_tally_claims(bppp_rp *rp, size_t rows, const uint64_t *amounts, cons
 int bppp_rp_tally_claims_device(bppp_rp *rp, size_t rows, const void *d_amounts, const void *d_types, const void *d_blinds, size_t nsums,
                                 const void *d_sum_start, const void *d_entries, size_t nnz, void *d_claim_amounts, void *d_claim_types,
                                 void *d_claim_blinds);
+
+/* ---- excess signatures: a tally checked without revealing the blinding sum -----------------------------------------------------------
+ * pedersen_blind_sum's other use: the excess of sum t over its PUBLIC claim,
+ *   X_t = S_t - a_t g - ty_t H0 = e_t B            (a binary handle: X_t = S_t - a_t g)
+ * is published as a public key and the builder signs the transaction with e_t (Schnorr).  B is the blinding generator: H1 on a typed
+ * handle (point 2 of [g | H0 | H1]), h0 on a RangeProof.Binary handle (point 1).  A valid signature shows that X_t has no g (and no H0)
+ * component, i.e. that the sum carries exactly the claimed amount and type — without anyone learning e_t.
+ *
+ * POOL, SUMS, entries: exactly as for bppp_rp_tally_each, the same arrays and the same validation before anything reads through them.
+ * PUBLIC CLAIM.  claim_amounts, claim_types [nsums][4], encoded as for the tally; claim_types is ignored on a binary handle and may be NULL
+ * there; both NULL: every claim is zero.  There is no claim_blinds.
+ * MESSAGE.  msgs [nsums][32], opaque bytes: typically the transaction's binding, the same 32 bytes a *_bound call takes.
+ * SIGNATURE.  sigs [nsums][BPPP_RP_EXCESS_SIG_BYTES = 65]: put (R.x), then one sign byte of R (0 or 1: y > p - y, as encodeCommitments
+ * defines the sign), then put (s); put and decode as defined for bppp_rp_open_batch.
+ * DOMAINS, computed once per call on the host; tag = the handle's oracle tag bytes:
+ *   Dc = SHA-256 ("bppp/excess/challenge/v1" || tag)        Dn = SHA-256 ("bppp/excess/nonce/v1" || tag)
+ * NONCE (signer).  k_t = decode (SHA-256 (Dn || put (e_t) || msg_t || aux[32])) mod n      — 128 bytes.  aux is the signer's 32 bytes of
+ * randomness; it may be constant, the derivation is deterministic in the secret: equal (e, msg, aux) give an equal signature.
+ * CHALLENGE.  c_t = decode (SHA-256 (Dc || put (R.x) || sign (R) || put (X_t.x) || sign (X_t) || msg_t)) mod n      — 130 bytes.  The 33 bytes
+ * of R are hashed as they stand in the signature, those of X_t are the canonical affine point's.  THE CHALLENGE HASHES X_t: over (R, msg)
+ * alone a forger could choose R = r B + d g, compute c, and solve  s B - c X = R  for X = (s - r) / c B - d / c g — an "excess" with a non-zero
+ * g component, i.e. an unbalanced sum that verifies.  With X_t under the hash, c is fixed only after X_t is, and the equation then proves
+ * knowledge of log_B X_t.
+ * RESPONSE.  s_t = k_t + c_t e_t mod n;  the verifier checks  s_t B - c_t X_t = R_t.
+ *
+ * bppp_rp_excess_sign{,_device}: the builder's side; it takes no pool — claim_blinds [nsums][4] are the e_t bppp_rp_tally_claims returned.
+ * sigs receives the signatures, excess_xy (host, may be NULL, [nsums][8]) the points X_t = e_t B.  sign_status (host, may be NULL, [nsums]):
+ *   BPPP_RP_EXCESS_OK             signed
+ *   BPPP_RP_EXCESS_NOT_CANONICAL  e >= n
+ *   BPPP_RP_EXCESS_ZERO           e = 0: the excess is infinity and has no encoding; the plain tally with e = 0 serves this case
+ *   BPPP_RP_EXCESS_NONCE          k = 0
+ * A refused sum gets 65 zero bytes (and a zero excess_xy row).  With sign_status == NULL a refusal is BPPP_ERR_ARG and bppp_last_error names
+ * the lowest such sum ("sum N: ..."), as bppp_rp_commit_batch does; the signatures are then as they would be with sign_status given.
+ * No side-channel hardening, as everywhere in this library.
+ *
+ * bppp_rp_excess_verify_each{,_device}: status [nsums] (required), one exact verdict per sum — the first that applies of
+ *   BPPP_RP_OPEN_MALFORMED (2)      an x in a referenced commitment has no curve point
+ *   BPPP_RP_OPEN_NOT_CANONICAL (3)  the claimed type is >= n, or s >= n
+ *   BPPP_RP_EXCESS_BAD_R (4)        the sign byte is not 0 or 1, or R.x has no curve point
+ *   BPPP_RP_EXCESS_NO_KEY (5)       X_t is infinity
+ *   BPPP_RP_OPEN_MISMATCH (1) or BPPP_RP_OPEN_OK (0), from the equation.
+ * excess_xy (host, may be NULL, [nsums][8]): X_t, zeros for infinity and for a MALFORMED sum.  c_t X_t is a scalar multiplication of a point
+ * of its own per sum: four lanes share each (256 doublings and the additions of the set bits, on the complete law).
+ *
+ * bppp_rp_excess_verify_batch{,_device}: all sums by ONE weighted combination per pass,
+ *   combined = sum_t rho_t (s_t B - c_t X_t - R_t)        over the sums whose verdict the equation has to give,
+ *   rho_t = decode (SHA-256 (seed[32] || le64 (index_offset + t) || sig_t[65] || put (X_t.x) || sign (X_t) || msg_t)) mod n, 1 in place of 0
+ *                                                                                                                      — 170 bytes,
+ * as one MSM over 2 ns + 1 terms: (sum rho_t s_t) on B, n - rho_t c_t on X_t, n - rho_t on R_t.  *accept = 1 iff no sum has one of the
+ * verdicts 2 .. 5 and combined is the identity.  status (may be NULL): all BPPP_RP_OPEN_OK when accepted; on rejection exactly
+ * bppp_rp_excess_verify_each's verdicts, from one such pass (no bisection).  combined_xy (may be NULL): the combined point, infinity as all
+ * zeros.  seed, index_offset, shards adding up with bppp_sum_points and the passes of bounded workspace are as in bppp_rp_tally_batch_device;
+ * bppp_rp_excess_verify_batch is the _device call with index_offset 0.
+ *
+ * The host variants upload, call the _device variant and download; status and point arrays are host memory; aux and seed are host memory.
+ * nsums == 0 is BPPP_OK (verify_batch with *accept = 1).  Argument errors, CSR errors and their texts are as for bppp_rp_tally_each (only one
+ * of claim_amounts / claim_types NULL on a typed handle is BPPP_ERR_ARG); the CSR verdict is read back before anything gathers. */
+#define BPPP_RP_EXCESS_SIG_BYTES 65
+#define BPPP_RP_EXCESS_OK 0u
+#define BPPP_RP_EXCESS_NOT_CANONICAL 1u
+#define BPPP_RP_EXCESS_ZERO 2u
+#define BPPP_RP_EXCESS_NONCE 3u
+#define BPPP_RP_EXCESS_BAD_R 4u
+#define BPPP_RP_EXCESS_NO_KEY 5u
+int bppp_rp_excess_sign(bppp_rp *rp, size_t nsums, const uint64_t *claim_blinds, const uint8_t *msgs, const uint8_t aux[32], uint8_t *sigs,
+                        uint64_t *excess_xy /* may be NULL */, uint32_t *sign_status /* may be NULL */);
+int bppp_rp_excess_sign_device(bppp_rp *rp, size_t nsums, const void *d_claim_blinds, const void *d_msgs, const uint8_t aux[32], void *d_sigs,
+                               uint64_t *excess_xy /* host, [nsums][8], may be NULL */, uint32_t *sign_status /* host, [nsums], may be NULL */);
+int bppp_rp_excess_verify_each(bppp_rp *rp, size_t rows, const uint8_t *coms_files, size_t nsums, const uint32_t *sum_start, const uint32_t *entries,
+                               size_t nnz, const uint64_t *claim_amounts, const uint64_t *claim_types, const uint8_t *msgs, const uint8_t *sigs,
+                               uint32_t *status, uint64_t *excess_xy /* may be NULL */);
+int bppp_rp_excess_verify_each_device(bppp_rp *rp, size_t rows, const void *d_coms_files, size_t nsums, const void *d_sum_start, const void *d_entries,
+                                      size_t nnz, const void *d_claim_amounts, const void *d_claim_types, const void *d_msgs, const void *d_sigs,
+                                      uint32_t *status /* host, [nsums], required */, uint64_t *excess_xy /* host, [nsums][8], may be NULL */);
+int bppp_rp_excess_verify_batch(bppp_rp *rp, size_t rows, const uint8_t *coms_files, size_t nsums, const uint32_t *sum_start, const uint32_t *entries,
+                                size_t nnz, const uint64_t *claim_amounts, const uint64_t *claim_types, const uint8_t *msgs, const uint8_t *sigs,
+                                const uint8_t seed[32], int *accept, uint32_t *status, uint64_t *combined_xy);
+int bppp_rp_excess_verify_batch_device(bppp_rp *rp, size_t rows, const void *d_coms_files, size_t nsums, const void *d_sum_start, const void *d_entries,
+                                       size_t nnz, const void *d_claim_amounts, const void *d_claim_types, const void *d_msgs, const void *d_sigs,
+                                       uint64_t index_offset, const uint8_t seed[32], int *accept, uint32_t *status, uint64_t *combined_xy);
 
 /* ---- one comb table for the handles of a basis family --------------------------------------------------------------------------
  * Every setup's basis [g | H | G] is a prefix of the point stream its points came from (see bppp_rp_verify_mixed), and the comb table

@@ -65,13 +65,18 @@ int bppp_test_rp_last_verify_counts(bppp_rp *rp, uint64_t *combined_msms, uint64
 /* Proofs per chunk of the per-proof pass on this handle (0 = from the row budget, the default): a test crosses a chunk boundary
  * with a small batch. */
 int bppp_test_rp_set_each_chunk(bppp_rp *rp, size_t proofs);
-/* The thresholds of the tally entry points on this handle (csrc/rptally.hip; 0 restores the default): the longest sum one lane walks alone
+/* The thresholds of the tally entry points on this handle, and of bppp_rp_excess_verify_*, which run the same sum stage (csrc/rptally.hip; 0
+ * restores the default): the longest sum one lane walks alone
  * (default 16), the entries of one workgroup's piece of a longer sum (default 4096, at least 2: longer sums are split and their partial
  * points summed by further launches) and the entries, and sums, of one pass over the workspace (default 2^22).  A test straddles each with a
  * small job. */
 int bppp_test_rp_set_tally_short_max(bppp_rp *rp, size_t entries);
 int bppp_test_rp_set_tally_piece(bppp_rp *rp, size_t entries);
 int bppp_test_rp_set_tally_chunk(bppp_rp *rp, size_t entries);
+/* The quad walk of k_rp_excess_mulcheck alone (csrc/rpexcess.hip.h): out_i = c_i X_i in affine form, infinity as all zeros, for n instances
+ * of four lanes each.  d_scalars [n][4] words (walked as the 256-bit integers they are, reduced or not), d_points_xy and d_out_xy [n][8]
+ * words, all in HBM.  The real entry points derive the challenge from a hash; here a test chooses it. */
+int bppp_test_rp_excess_mul(bppp_rp *rp, size_t n, const void *d_scalars, const void *d_points_xy, void *d_out_xy);
 /* The witness kernel of bppp_rp_prove_batch_device alone (csrc/rpwitness.hip.h): inputs in HBM as that entry point takes them
  * (d_types ignored on a binary handle, d_public_amounts NULL or CANONICAL scalars [batch][public_count][4]); its arrays copied to the
  * host: in_sc [batch][nranges][3][4] words, status [batch] (0 = a witness; the arrays of a refused proof are unspecified) and, typed:
