@@ -1,12 +1,14 @@
 // fqmul_variants.hip — the forms of the Fq multiplication (csrc/fq26.hip.h, benchmarks/fqmul_variants.h) against each other: same results on
 // random and worst-case-magnitude inputs, multiplications per second at 8 wavefronts per SIMD (the bppp_test_mulmod_rate shape: four
-// independent chains per lane); with the argument `chain`, dependent chains at 1 .. 8 wavefronts per SIMD.   hipcc -O3 --offload-arch=gfx950 -std=c++17 -o benchmarks/fqmul_variants benchmarks/fqmul_variants.hip
+// independent chains per lane), and the 9 x 29-bit multiplication of csrc/fq29.hip.h in the same run; with the argument `chain`, dependent chains
+// at 1 .. 8 wavefronts per SIMD.   hipcc -O3 --offload-arch=gfx950 -std=c++17 -o benchmarks/fqmul_variants benchmarks/fqmul_variants.hip
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string>
 #include <vector>
 #include "fqmul_variants.h"
 #include "../bulletproofspp_amd/csrc/ec_quad.hip.h"
+#include "../bulletproofspp_amd/csrc/fq29.hip.h"
 using namespace bppp;
 
 template <int V> BPPP_DI fq mulv(const fq &a, const fq &b) {
@@ -45,6 +47,55 @@ template <int V> double run(const uint32_t *seed, uint32_t *out, std::vector<uin
   k_mag<V><<<64, 256>>>(seed, out);
   mag.resize(64 * 256 * 8); hipMemcpy(mag.data(), out, mag.size() * 4, hipMemcpyDeviceToHost);
   return (double)blocks * 256.0 * 4.0 * iters / (ms * 1e-3);
+}
+// the same four chains per lane on 9 x 29-bit limbs (fq29_mul): same operands, so the canonical results equal k_rate's
+__global__ void __launch_bounds__(256) k_rate29(const uint32_t *__restrict__ seed, int iters, uint32_t *__restrict__ out) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  fq29 a[4], b;
+  for (int k = 0; k < 4; k++) a[k] = fq29_from_fe(fe_load(seed + (size_t)((t + 17 * k) & 1023) * 8));
+  b = fq29_from_fe(fe_load(seed + (size_t)((t * 7 + 3) & 1023) * 8));
+  for (int i = 0; i < iters; i++) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) a[k] = fq29_mul(a[k], b);
+  }
+  const fq29 r = fq29_add(fq29_add(a[0], a[1]), fq29_add(a[2], a[3]));       // magnitude 4
+  fe_store(out + (size_t)t * 8, fq_to_fe(fq29_to_fq26(r)));
+}
+static double run29(const uint32_t *seed, uint32_t *out, std::vector<uint32_t> &res) {
+  const int blocks = 256 * 4 * 8 / 4 * 2, iters = 2000;
+  hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+  k_rate29<<<blocks, 256>>>(seed, 8, out);
+  hipEventRecord(e0);
+  k_rate29<<<blocks, 256>>>(seed, iters, out);
+  hipEventRecord(e1); hipEventSynchronize(e1);
+  float ms = 0; hipEventElapsedTime(&ms, e0, e1);
+  res.resize((size_t)blocks * 256 * 8); hipMemcpy(res.data(), out, res.size() * 4, hipMemcpyDeviceToHost);
+  hipEventDestroy(e0); hipEventDestroy(e1);
+  return (double)blocks * 256.0 * 4.0 * iters / (ms * 1e-3);
+}
+// dependent chains on 9 x 29-bit limbs.  MODE 0: r = fq29_mul(r, b)   1: r = fq29_sqr(r)
+template <int MODE> __global__ void __launch_bounds__(256) k_chain29(const uint32_t *__restrict__ seed, int iters, uint32_t *__restrict__ out) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  fq29 r = fq29_from_fe(fe_load(seed + (size_t)((t + 40) & 1023) * 8));
+  const fq29 b = fq29_from_fe(fe_load(seed + (size_t)((t * 7 + 3) & 1023) * 8));
+  for (int i = 0; i < iters; i++) r = MODE == 0 ? fq29_mul(r, b) : fq29_sqr(r);
+  fe_store(out + (size_t)t * 8, fq_to_fe(fq29_to_fq26(r)));
+}
+template <int MODE> void chain29_row(const char *name, const uint32_t *seed, uint32_t *out) {
+  const int iters = 4000;
+  printf("%-34s", name);
+  for (int w = 1; w <= 8; w *= 2) {
+    const int blocks = 256 * w;
+    hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+    k_chain29<MODE><<<blocks, 256>>>(seed, 8, out);
+    hipEventRecord(e0);
+    k_chain29<MODE><<<blocks, 256>>>(seed, iters, out);
+    hipEventRecord(e1); hipEventSynchronize(e1);
+    float ms = 0; hipEventElapsedTime(&ms, e0, e1);
+    printf("  %7.1f", (double)ms * 1e6 / (double)iters);
+    hipEventDestroy(e0); hipEventDestroy(e1);
+  }
+  printf("\n");
 }
 // ---- dependent-chain mode: what ONE chain per lane costs when 1, 2, 4 or 8 wavefronts share a SIMD (the bucket reduction's kernels run at 1).
 // MODE 0: r = fq_mul(r, b)   1: (r, s) = fq_mul2(r, b, s, b): two chains per lane   2: r = fq_sqr(r)   3: (r, s) = fq_sqr2(r, s)
@@ -103,6 +154,8 @@ static int chain_mode(const uint32_t *seed, uint32_t *out) {
   chain_row<6>("fq_mul_lone  one chain per lane", seed, out, 1, nullptr);
   chain_row<7>("xyzz_add_quad on fq_mul  (4 deep)", seed, out, 4, &a7);
   chain_row<8>("xyzz_add_quad on fq_mul_lone", seed, out, 4, &a8);
+  chain29_row<0>("fq29_mul one chain per lane", seed, out);
+  chain29_row<1>("fq29_sqr one chain per lane", seed, out);
   printf("xyzz_add_chain results %s, xyzz_add_quad on fq_mul_lone %s\n", a4 == a5 ? "equal" : "DIFFER", a7 == a8 ? "equal" : "DIFFER");
   return a4 == a5 && a7 == a8 ? 0 : 1;
 }
@@ -123,5 +176,9 @@ int main(int argc, char **argv) {
   printf("fq_mul (two chains)      %.1f G mulmod/s  results %s, magnitude-8 %s\n", g1 / 1e9, r1 == r0 ? "equal" : "DIFFER", m1 == m0 ? "equal" : "DIFFER");
   printf("v2 (register R0, R1)     %.1f G mulmod/s  results %s, magnitude-8 %s\n", g2 / 1e9, r2 == r0 ? "equal" : "DIFFER", m2 == m0 ? "equal" : "DIFFER");
   printf("v3 (H chain + free low)   %.1f G mulmod/s  results %s, magnitude-8 %s\n", g3 / 1e9, r3 == r0 ? "equal" : "DIFFER", m3 == m0 ? "equal" : "DIFFER");
+  std::vector<uint32_t> r29;
+  const double g29 = run29(seed, out, r29);
+  printf("fq29_mul (9 x 29 limbs)  %.1f G mulmod/s  results %s\n", g29 / 1e9, r29 == r0 ? "equal" : "DIFFER");
+  if (r29 != r0) return 1;
   return (r3 == r0 && m3 == m0 && r1 == r0 && r2 == r0 && m1 == m0 && m2 == m0) ? 0 : 1;
 }

@@ -215,6 +215,9 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_last_acc_kernel.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_last_sort_ranges.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_last_acc_sized.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.bppp_test_last_acc_fq29.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.bppp_test_fq29_op.argtypes = [vp, i, vp, vp, sz, vp, vp]
+    lib.bppp_test_madd29_chain.argtypes = [vp, vp, vp, sz, sz, vp, vp]
     lib.bppp_test_last_windows.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_rp_last_verify_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.bppp_test_rp_set_each_chunk.argtypes = [vp, sz]

@@ -45,6 +45,7 @@ void MsmTune::from_env() {
   tail_scalar = getenv("BPPP_REDUCE_TAIL_SCALAR") != nullptr;     // k_reduce_tail (one lane per element) instead of k_reduce_tail_quad
   if (const char *e = getenv("BPPP_SORT_RANGES")) sort_ranges = atoi(e);   // 0 k_scatter, 2 / 4 k_scatter_ranges with that many bucket ranges per window
   if (const char *e = getenv("BPPP_ACC_SIZED")) acc_sized = atoi(e) != 0;   // 1 / 0: k_acc_points_sized for every / no MSM over arbitrary points; unset: make_plan's default
+  if (const char *e = getenv("BPPP_ACC_FQ29")) acc_fq29 = atoi(e) != 0;   // 1 / 0: k_acc_points_sized29 (9 x 29-bit limbs) for every / no sized accumulation
   if (const char *e = getenv("BPPP_ACC_LDS")) acc_lds = atoi(e) != 0;   // k_acc_points_lds (next point prefetched into LDS) instead of k_acc_points
 }
 namespace bppp {

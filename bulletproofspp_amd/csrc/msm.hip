@@ -21,7 +21,8 @@
 //                    one MSM over arbitrary points with 16-bit windows (MsmTune::acc_sized): a lane sums one whole
 //                    bucket (or a piece of <= 128 entries of a larger one), the buckets dispatched in descending order
 //                    of size so that the lanes of a wavefront run equally long: no boundary logic in the loop, no
-//                    partial sums unless the scalars are skewed.
+//                    partial sums unless the scalars are skewed.  k_acc_points_sized29 (MsmTune::acc_fq29, the default) is the same
+//                    kernel with the accumulator in 9 x 29-bit limbs (fq29.hip.h): 81 partial products per multiplication, not 100.
 //   4. k_reduce_marg / k_reduce_tail_quad (k_reduce_tail: the one-lane form, MsmTune::tail_scalar)
 //                    sum_m m*B_m per window by MARGINAL SUMS (m = LO*hi + lo: plain row and column sums, every lane busy,
 //                    then two short weighted sums); k_reduce1/2 (per-lane running sums + wavefront suffix scans) for windows
@@ -34,6 +35,7 @@
 #include <vector>
 #include "ctx.hpp"
 #include "ec.hip.h"
+#include "ec29.hip.h"
 #include "ec_quad.hip.h"
 #include "hostmath.hpp"
 #include "recode.hip.h"
@@ -489,6 +491,30 @@ __global__ void __launch_bounds__(256) k_acc_points_sized(const uint32_t *__rest
     e = e_next;
   }
   xyzz_store(cnt > ACC_CAP ? pieces + ((size_t)piece_base[fb] + it.y) * XYZZ_WORDS : buckets + (size_t)fb * XYZZ_WORDS, acc);
+}
+// The same kernel with the accumulator in 9 x 29-bit limbs (fq29.hip.h, ec29.hip.h; MsmTune::acc_fq29): 81 partial products per field
+// multiplication instead of 100.  Same items, entries, sign fold and first-entry start; the sum is converted once, at the store, into the
+// 40-word layout and the magnitudes that k_merge_heavy<true> and the bucket reduction read (every limb below 2^26).
+__global__ void __launch_bounds__(256) k_acc_points_sized29(const uint32_t *__restrict__ sorted, const uint32_t *__restrict__ start,
+                                                            const uint32_t *__restrict__ count, const uint2 *__restrict__ items,
+                                                            const uint32_t *__restrict__ ctr, const uint32_t *__restrict__ piece_base,
+                                                            const uint32_t *__restrict__ points, uint32_t *__restrict__ buckets,
+                                                            uint32_t *__restrict__ pieces) {
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= ctr[3]) return;
+  const uint2 it = items[g];
+  const uint32_t fb = it.x, cnt = count[fb], first = it.y * ACC_CAP, len = min(ACC_CAP, cnt - first);
+  const uint32_t *ent = sorted + start[fb] + first;
+  uint32_t e = ent[0];
+  xyzz29 acc = xyzz29_from_aff(aff29_cneg(aff29_load(points + (size_t)(e & 0x7FFFFFFFu) * 16), (e >> 31) & 1u));
+  e = len > 1 ? ent[1] : 0u;
+  for (uint32_t k = 1; k < len; k++) {
+    const uint32_t e_next = (k + 1 < len) ? ent[k + 1] : 0u;
+    aff29 P = aff29_cneg(aff29_load(points + (size_t)(e & 0x7FFFFFFFu) * 16), (e >> 31) & 1u);
+    xyzz29_madd(acc, P);
+    e = e_next;
+  }
+  xyzz_store(cnt > ACC_CAP ? pieces + ((size_t)piece_base[fb] + it.y) * XYZZ_WORDS : buckets + (size_t)fb * XYZZ_WORDS, xyzz29_to_xyzz(acc));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1030,6 +1056,7 @@ struct MsmPlan {
   int ntiles;
   int Q;                       // bucket ranges per window of the ranged scatter (k_scatter_ranges); 0 = k_scatter
   bool sized;                  // accumulate whole buckets in order of size (k_order, k_acc_points_sized) instead of slices of L entries
+  bool fq29;                   // sized, with the accumulator in 9 x 29-bit limbs (k_acc_points_sized29)
 };
 
 static MsmPlan make_plan(size_t n, size_t batch, int c, bool flat, const MsmTune &tune) {
@@ -1131,6 +1158,8 @@ static MsmPlan make_plan(size_t n, size_t batch, int c, bool flat, const MsmTune
   // and c = 16 the accumulation stage falls 1.113 -> 1.010 ms; at 2^16 and c = 13 it has 86 K items of 16 entries, a third of the chip's wave
   // slots on chains twice as long as the slices', and rises 0.186 -> 0.311 ms
   p.sized = batch == 1 && !flat && !tune.acc_lds && (tune.acc_sized > 0 || (tune.acc_sized < 0 && c == 16));
+  // on 9 x 29-bit limbs by default ("9 x 29-bit limbs"): accumulation 1.010 -> 0.892 ms at 2^20 terms, 8 interleaved pairs
+  p.fq29 = p.sized && tune.acc_fq29 != 0;
   return p;
 }
 
@@ -1279,6 +1308,7 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
     // 3. accumulate
     ctx->last_acc_lds = ctx->tune.acc_lds ? 1 : 0;
     ctx->last_acc_sized = p.sized ? 1 : 0;
+    ctx->last_acc_fq29 = p.fq29 ? 1 : 0;
     // the ordering pass has to precede the accumulation, so its time is booked with acc_points; acc_points + acc_records is the accumulation
     // on either route
     if (p.sized)
@@ -1286,8 +1316,8 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
                                                                           heavy_buckets, heavy_count);
     if (ctx->pre_acc) { auto f = ctx->pre_acc; ctx->pre_acc = nullptr; int rc_ = f(ctx->pre_acc_arg); if (rc_) return rc_; }
     if (p.sized) {
-      k_acc_points_sized<<<dim3((unsigned)((items_max + 255) / 256)), dim3(256), 0, st>>>(sorted, start, count, items, heavy_count, piece_base,
-                                                                                          (const uint32_t *)d_points, buckets, rec_pt);
+      (p.fq29 ? k_acc_points_sized29 : k_acc_points_sized)<<<dim3((unsigned)((items_max + 255) / 256)), dim3(256), 0, st>>>(
+          sorted, start, count, items, heavy_count, piece_base, (const uint32_t *)d_points, buckets, rec_pt);
       prof_mark(ctx, 3);
       k_merge_heavy<true><<<dim3(2048), dim3(64), 0, st>>>(start, count, 0, rec_pt, piece_base, buckets, heavy_items, heavy_slot, heavy_buckets, heavy_count, chunk_sums);
     } else {

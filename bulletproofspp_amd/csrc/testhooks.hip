@@ -3,6 +3,7 @@
 #include <vector>
 #include "ctx.hpp"
 #include "ec.hip.h"
+#include "ec29.hip.h"
 #include "ec_quad.hip.h"
 #include "modinv.hip.h"
 #include "fr26.hip.h"
@@ -167,6 +168,35 @@ __global__ void __launch_bounds__(64) k_test_point_chain(int op, const uint32_t 
   xyzz_store(o, r); xyzz_store(o + 40, s);
   aff_store(out + (size_t)i * 16, xyzz_to_aff(r));
 }
+// fq29.hip.h on raw limbs (n x 9 words each, the caller keeps to the magnitude contract).  op 0: a b, 1: a^2, 2: weak_pass(sub<3>(a, b)),
+// 3: from_fe of the canonical 8 x 32 value in a's first 8 words.  raw: the 9 result limbs, then the 10 limbs of fq29_to_fq26(result);
+// out: that value canonical, 8 words
+__global__ void __launch_bounds__(64) k_test_fq29(int op, const uint32_t *a, const uint32_t *b, uint32_t n, uint32_t *raw, uint32_t *out) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const fq29 A = fq29_load9(a + (size_t)i * 9), B = fq29_load9(b + (size_t)i * 9);
+  fq29 r;
+  if (op == 0) r = fq29_mul(A, B);
+  else if (op == 1) r = fq29_sqr(A);
+  else if (op == 2) r = fq29_weak_pass(fq29_sub<3>(A, B));
+  else { fe v; for (int k = 0; k < 8; k++) v.v[k] = A.n[k]; r = fq29_from_fe(v); }
+  const fq t = fq29_to_fq26(r);
+  fq29_store9(raw + (size_t)i * 19, r);
+  fq_store10(raw + (size_t)i * 19 + 9, t);
+  fe_store(out + (size_t)i * 8, fq_to_fe(t));
+}
+// one chain of k mixed additions per lane, as k_acc_points_sized29 walks an item: the first point is loaded into the accumulator, the others
+// are added with xyzz29_madd; flags[j] != 0 negates point j (the sign fold).  raw: the 40 stored words of the sum (xyzz29_to_xyzz)
+__global__ void __launch_bounds__(64) k_test_madd29_chain(const uint32_t *pts, const uint32_t *flags, uint32_t k, uint32_t n, uint32_t *out, uint32_t *raw) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t *p = pts + (size_t)i * k * 16, *f = flags + (size_t)i * k;
+  xyzz29 acc = xyzz29_from_aff(aff29_cneg(aff29_load(p), f[0] != 0));
+  for (uint32_t j = 1; j < k; j++) xyzz29_madd(acc, aff29_cneg(aff29_load(p + (size_t)j * 16), f[j] != 0));
+  const xyzz s = xyzz29_to_xyzz(acc);
+  xyzz_store(raw + (size_t)i * XYZZ_WORDS, s);
+  aff_store(out + (size_t)i * 16, xyzz_to_aff(s));
+}
 }  // namespace bppp
 
 using namespace bppp;
@@ -326,6 +356,43 @@ extern "C" int bppp_test_last_acc_sized(bppp_ctx *ctx, int *sized) {
   if (!ctx || !sized) return BPPP_ERR_ARG;
   *sized = ctx->last_acc_sized;
   return BPPP_OK;
+}
+
+extern "C" int bppp_test_last_acc_fq29(bppp_ctx *ctx, int *fq29) {
+  if (!ctx || !fq29) return BPPP_ERR_ARG;
+  *fq29 = ctx->last_acc_fq29;
+  return BPPP_OK;
+}
+
+extern "C" int bppp_test_fq29_op(bppp_ctx *ctx, int op, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *raw, uint32_t *out) {
+  if (!ctx || !a || !b || !raw || !out || op < 0 || op > 3 || n >= (1u << 24)) return BPPP_ERR_ARG;
+  if (n == 0) return BPPP_OK;
+  hipSetDevice(ctx->device);
+  uint32_t *d = nullptr;                       // a | b | raw | out
+  if (hipMalloc(&d, n * (9 + 9 + 19 + 8) * 4) != hipSuccess) return bppp::fail(ctx, BPPP_ERR_HIP, "test_fq29_op: hipMalloc");
+  uint32_t *d_b = d + n * 9, *d_raw = d_b + n * 9, *d_out = d_raw + n * 19;
+  hipStream_t st = ctx->stream;
+  bool ok = hipMemcpyAsync(d, a, n * 36, hipMemcpyHostToDevice, st) == hipSuccess && hipMemcpyAsync(d_b, b, n * 36, hipMemcpyHostToDevice, st) == hipSuccess;
+  if (ok) k_test_fq29<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st>>>(op, d, d_b, (uint32_t)n, d_raw, d_out);
+  ok = ok && hipMemcpyAsync(raw, d_raw, n * 19 * 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, st) == hipSuccess;
+  if (hipStreamSynchronize(st) != hipSuccess) ok = false;
+  hipFree(d);
+  return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_fq29_op: kernel or copy failed");
+}
+extern "C" int bppp_test_madd29_chain(bppp_ctx *ctx, const uint64_t *points, const uint32_t *flags, size_t k, size_t n, uint64_t *out, uint32_t *raw) {
+  if (!ctx || !points || !flags || !out || !raw || !k || k >= (1u << 16) || n >= (1u << 16)) return BPPP_ERR_ARG;
+  if (n == 0) return BPPP_OK;
+  hipSetDevice(ctx->device);
+  uint32_t *d = nullptr;                       // points | flags | out | raw
+  if (hipMalloc(&d, (n * k * 17 + n * (16 + XYZZ_WORDS)) * 4) != hipSuccess) return bppp::fail(ctx, BPPP_ERR_HIP, "test_madd29_chain: hipMalloc");
+  uint32_t *d_f = d + n * k * 16, *d_out = d_f + n * k, *d_raw = d_out + n * 16;
+  hipStream_t st = ctx->stream;
+  bool ok = hipMemcpyAsync(d, points, n * k * 64, hipMemcpyHostToDevice, st) == hipSuccess && hipMemcpyAsync(d_f, flags, n * k * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+  if (ok) k_test_madd29_chain<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st>>>(d, d_f, (uint32_t)k, (uint32_t)n, d_out, d_raw);
+  ok = ok && hipMemcpyAsync(out, d_out, n * 64, hipMemcpyDeviceToHost, st) == hipSuccess && hipMemcpyAsync(raw, d_raw, n * XYZZ_WORDS * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+  if (hipStreamSynchronize(st) != hipSuccess) ok = false;
+  hipFree(d);
+  return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_madd29_chain: kernel or copy failed");
 }
 
 extern "C" int bppp_test_last_windows(bppp_ctx *ctx, int *windows) {

@@ -55,6 +55,17 @@ int bppp_test_last_sort_ranges(bppp_ctx *ctx, int *q);
  * k_acc_points_sized; BPPP_ACC_SIZED, one MSM over arbitrary points only), 0 = slices of the sorted entries (k_acc_points, k_merge),
  * -1 = none yet. */
 int bppp_test_last_acc_sized(bppp_ctx *ctx, int *sized);
+/* 1 = the last MSM of the general pipeline on this context accumulated on 9 x 29-bit limbs (k_acc_points_sized29; BPPP_ACC_FQ29 on a sized
+ * plan), 0 = on 10 x 26, -1 = none yet. */
+int bppp_test_last_acc_fq29(bppp_ctx *ctx, int *fq29);
+/* csrc/fq29.hip.h on caller-built RAW limbs (n x 9 uint32 each, within the magnitude contract of the operation): op 0: a b (magnitudes with
+ * product <= 7), 1: a^2 (<= 2), 2: weak_pass(sub<3>(a, b)) (a, b <= 3), 3: fq29_from_fe of the canonical 8 x 32-bit value in the first 8 words
+ * of a.  raw: n x 19 uint32, the 9 limbs of the result and the 10 limbs of fq29_to_fq26(result); out: n x 8 uint32, that value canonical. */
+int bppp_test_fq29_op(bppp_ctx *ctx, int op, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *raw, uint32_t *out);
+/* n chains of k mixed additions (csrc/ec29.hip.h), one lane each, walked as k_acc_points_sized29 walks an item: the first point is loaded into
+ * the accumulator, the others are added with xyzz29_madd.  points: n x k x 8 uint64 affine ((0, 0) = infinity), flags: n x k uint32, not 0
+ * negates the point first.  out: n x 8 uint64 canonical affine sums; raw: n x 40 uint32, the sums as the kernel stores them. */
+int bppp_test_madd29_chain(bppp_ctx *ctx, const uint64_t *points, const uint32_t *flags, size_t k, size_t n, uint64_t *out, uint32_t *raw);
 /* The windows (digit rows per scalar) of the plan of the last MSM on this context, the small route included: 16 with 16-bit windows, where
  * the top window is stored negated instead of carrying into a 17th; 256 / c + 1 for a registered basis; -1 = none yet. */
 int bppp_test_last_windows(bppp_ctx *ctx, int *windows);
