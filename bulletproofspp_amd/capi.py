@@ -41,6 +41,8 @@ SYMBOLS = [
     "bppp_rp_tally_each", "bppp_rp_tally_each_device", "bppp_rp_tally_batch", "bppp_rp_tally_batch_device", "bppp_rp_tally_claims", "bppp_rp_tally_claims_device",
     "bppp_rp_excess_sign", "bppp_rp_excess_sign_device", "bppp_rp_excess_verify_each", "bppp_rp_excess_verify_each_device", "bppp_rp_excess_verify_batch",
     "bppp_rp_excess_verify_batch_device",
+    "bppp_rp_excess_keys", "bppp_rp_excess_keys_device", "bppp_rp_excess_verify_keys_each", "bppp_rp_excess_verify_keys_each_device", "bppp_rp_excess_verify_keys_batch",
+    "bppp_rp_excess_verify_keys_batch_device", "bppp_rp_excess_sums_each", "bppp_rp_excess_sums_each_device", "bppp_rp_excess_sums_batch", "bppp_rp_excess_sums_batch_device",
     "bppp_seed_candidate_x", "bppp_points_from_seed", "bppp_points_from_seed_device", "bppp_rp_create_seeded", "bppp_rp_create_binary_seeded",
 ]
 
@@ -187,6 +189,16 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_excess_verify_each_device.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp]
     lib.bppp_rp_excess_verify_batch.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, C.POINTER(i), vp, vp]
     lib.bppp_rp_excess_verify_batch_device.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, C.c_uint64, vp, C.POINTER(i), vp, vp]
+    lib.bppp_rp_excess_keys.argtypes = [vp, sz, vp, vp, vp]
+    lib.bppp_rp_excess_keys_device.argtypes = [vp, sz, vp, vp, vp]
+    lib.bppp_rp_excess_verify_keys_each.argtypes = [vp, sz, vp, vp, vp, vp]
+    lib.bppp_rp_excess_verify_keys_each_device.argtypes = [vp, sz, vp, vp, vp, vp]
+    lib.bppp_rp_excess_verify_keys_batch.argtypes = [vp, sz, vp, vp, vp, vp, C.POINTER(i), vp, vp]
+    lib.bppp_rp_excess_verify_keys_batch_device.argtypes = [vp, sz, vp, vp, vp, C.c_uint64, vp, C.POINTER(i), vp, vp]
+    lib.bppp_rp_excess_sums_each.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp]
+    lib.bppp_rp_excess_sums_each_device.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp]
+    lib.bppp_rp_excess_sums_batch.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, C.POINTER(i), vp, vp]
+    lib.bppp_rp_excess_sums_batch_device.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, C.c_uint64, vp, C.POINTER(i), vp, vp]
     lib.bppp_seed_candidate_x.argtypes = [C.c_char_p, sz, C.c_uint64, vp]
     lib.bppp_points_from_seed.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
     lib.bppp_points_from_seed_device.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
@@ -294,6 +306,9 @@ RP_OPEN_OK, RP_OPEN_MISMATCH, RP_OPEN_MALFORMED, RP_OPEN_NOT_CANONICAL = 0, 1, 2
 RP_EXCESS_OK, RP_EXCESS_NOT_CANONICAL, RP_EXCESS_ZERO, RP_EXCESS_NONCE = 0, 1, 2, 3
 RP_EXCESS_BAD_R, RP_EXCESS_NO_KEY = 4, 5
 RP_EXCESS_SIG_BYTES = 65
+# the stated keys (bppp_rp_excess_keys / _verify_keys_* / _sums_*): 33 bytes a key, and the verdict of one that does not lift
+RP_EXCESS_KEY_BYTES = 33
+RP_EXCESS_BAD_KEY = 6
 # BPPP_RP_BINDING_BYTES: one proof's transcript binding of the bppp_rp_*_bound* entry points
 RP_BINDING_BYTES = 32
 

@@ -5,6 +5,7 @@
 #include <string.h>
 #include <algorithm>
 #include <chrono>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -296,7 +297,8 @@ int rpp_negated_column_sums(bppp_rp *rp, uint64_t n, const uint32_t *prods, uint
 }  // namespace bppp
 namespace bppp {
 // ---- the stage the tally entry points (csrc/rptally.hip, which defines it) and the excess signatures (csrc/rpexcess.hip) share: the job's
-// checks, the pool decoded once, the plan of a pass and the segmented signed sums of its sums
+// checks, the pool decoded once, the plan of a pass and the segmented signed sums of its sums; and the two passes of a tally themselves, which
+// the sums against stated keys (csrc/rpexkeys.hip) run over a pool and a CSR that they extend
 namespace tally {
 using bppp_tally::Levels;
 // one call's arguments, all in HBM, and what the checks established
@@ -306,6 +308,8 @@ struct Job {
   const uint8_t *coms; const uint32_t *start, *entries, *amt, *ty, *bl;
   std::vector<uint32_t> h_start;               // sum_start on the host, after validation
   bool zero_claims = false;
+  size_t tail = 0;                             // points behind the decoded pool, filled by the caller (Ext::prepare); 0: a plain tally
+  const char *bl_name = "claim_blinds";       // what the caller's ABI calls the third claim array, for tally_checks' text
 };
 struct Work {
   uint32_t *pool, *bad, *any, *sums, *malformed, *in_sc, *flag, *rec, *status, *zz, *zinv, *xy, *zero, *part[2];
@@ -323,6 +327,22 @@ int decode_pool(const Job &J, const Work &W);
 int sum_launches(const Job &J, const Work &W, size_t t0, size_t ns, const Levels &L);
 // k_rp_tally_affine: n XYZZ points and the inverses of their ZZ ZZZ (zero: the all-zero point) -> affine
 int affine_launch(bppp_ctx *ctx, size_t n, const uint32_t *sums, const uint32_t *zinv, uint32_t *out);
+// What a caller adds to the two passes below; with nullptr they are the plain tally, launch for launch.  The job it hands in has passed tally_checks
+// over the caller's own CSR and then carries the EXTENDED h_start and nnz (the plan and the sizes come from them) and J.tail; start and entries still
+// name the caller's arrays.  prepare runs once per pass over the workspace, after decode_pool and on a copy of the job: it fills the tail of W.pool
+// and points the copy's start / entries at extended arrays of its own in W.extra (`extra` bytes).  judge runs in each_pass after k_rp_tally_compare
+// of sums [t0, t0 + ns) and may overrule W.status (and W.zz when zz is set).  rejects runs in batch_run after the last pass: what the combined point
+// cannot show.
+struct Ext {
+  size_t extra = 0;
+  std::function<int(Job &J, const Work &W)> prepare;
+  std::function<int(const Work &W, size_t t0, size_t ns, bool zz)> judge;
+  std::function<int(const Work &W, bool &reject)> rejects;
+};
+// every sum decided on its own: status [nsums] and, when not NULL, sums_xy [nsums][8], both on the host
+int each_pass(const Job &J, uint32_t *status, uint64_t *sums_xy, const Ext *ext = nullptr);
+// all sums by one weighted combination per pass; status (may be NULL) by one each_pass when rejected; *accept is 0 on entry
+int batch_run(const Job &J, uint64_t index_offset, const uint8_t seed[32], int *accept, uint32_t *status, uint64_t *combined_xy, const Ext *ext = nullptr);
 }  // namespace tally
 }  // namespace bppp
 int rp_ensure_comb(bppp_rp *rp);      // csrc/rpprove.hip

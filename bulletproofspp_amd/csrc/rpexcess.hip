@@ -13,6 +13,8 @@
 //   k_rp_excess_mulcheck   verifier: one QUAD per sum: c_t X_t by the walk of csrc/rpexcess.hip.h, then s_t B - c_t X_t against R_t, cross-multiplied
 //   k_rp_excess_weights    batch: rho_t, the product column - rho_t s_t and the two MSM terms of the sum
 // Every kernel is bounds-checked on its own index, reads the 65-byte signature rows bytewise and writes with ordinary vector stores.
+// The domains, the three-block hash and the challenge are in csrc/rpexcess_shared.hip.h: the stated keys (csrc/rpexkeys.hip) hash the same
+// messages and run k_rp_excess_sigs, k_rp_excess_mulcheck and k_rp_excess_weights through the launches at the end of the kernels here.
 #include <string.h>
 #include <algorithm>
 #include <string>
@@ -23,50 +25,12 @@
 #include "rpwords.hip.h"
 #include "rplift.hip.h"
 #include "rpexcess.hip.h"
+#include "rpexcess_shared.hip.h"
 #include "sha256.hip.h"
 
 namespace bppp {
 
 int batch_inverse_run(bppp_ctx *, const void *, size_t, int, void *);      // csrc/rounds.hip
-
-static constexpr uint32_t EX_SIG = BPPP_RP_EXCESS_SIG_BYTES, EX_MSG = 32;
-static constexpr uint32_t EX_EVAL = 0xFFFFFFFFu;       // a verdict still open: the equation decides
-struct ExDomain { uint32_t w[8]; };                    // a domain digest as the eight big-endian words it is hashed as
-
-BPPP_DI uint32_t ex_dom_byte(const ExDomain &d, uint32_t k) { return (d.w[k >> 2] >> (24 - 8 * (k & 3))) & 0xFFu; }
-// byte o (< 33) of an affine point as a signature and the messages hold it: put (x), then the sign byte (y > p - y)
-BPPP_DI uint32_t ex_pt_byte(const uint32_t *pt, uint32_t o) { return o < 32 ? enc_be_byte(pt, o) : enc_sign(pt); }
-// decode (SHA-256 (message)) mod n of a message of 120 .. 183 bytes (three blocks), byte k of it being at (k)
-template <class F> BPPP_DI fe ex_hash3(uint32_t nbytes, F at) {
-  uint32_t st[8], w[16];
-  sha256_init(st);
-#pragma unroll
-  for (uint32_t blk = 0; blk < 3; blk++) {
-#pragma unroll
-    for (uint32_t q = 0; q < 16; q++) {
-      uint32_t word = 0;
-#pragma unroll
-      for (uint32_t r = 0; r < 4; r++) {
-        const uint32_t k = 64 * blk + 4 * q + r;
-        word = (word << 8) | (k < nbytes ? (at(k) & 0xFFu) : k == nbytes ? 0x80u : 0u);
-      }
-      w[q] = word;
-    }
-    if (blk == 2) w[15] = nbytes * 8;
-    sha256_compress(st, w);
-  }
-  fe r; sha256_digest_to_limbs(st, r.v);
-  return wi_umod_n(r);
-}
-// c = decode (SHA-256 (Dc || the 33 bytes of R || put (X.x) || sign (X) || msg)) mod n: 130 bytes; rbyte (o): byte o of R as the signature holds it
-template <class F> BPPP_DI fe ex_challenge(const ExDomain &dc, F rbyte, const uint32_t *X, const uint8_t *msg) {
-  return ex_hash3(32 + 33 + 33 + EX_MSG, [&](uint32_t k) -> uint32_t {
-    if (k < 32) return ex_dom_byte(dc, k);
-    if (k < 65) return rbyte(k - 32);
-    if (k < 98) return ex_pt_byte(X, k - 65);
-    return msg[k - 98];
-  });
-}
 
 // ---- signer.  in_sc [2n][3][8]: row t the scalars of R_t = k_t B, row n + t those of X_t = e_t B, on base `slot` (typed 2: H1, binary 1: h0); a
 // refused sum gets zero scalars, so its two points are the infinity encoding
@@ -220,25 +184,37 @@ __global__ void __launch_bounds__(64) k_rp_excess_weights(uint32_t n, uint32_t s
 
 }  // namespace bppp
 
+namespace bppp {
+namespace excess {
+
+// the launches the stated keys share (csrc/rpexkeys.hip, declared in csrc/rpexcess_shared.hip.h): the grids of verify_stage and of the two passes below
+int sigs_launch(bppp_ctx *ctx, size_t n, uint32_t slot, const uint8_t *sigs, uint32_t *in_sc, uint32_t *R, uint32_t *bits) {
+  k_rp_excess_sigs<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream>>>((uint32_t)n, slot, sigs, in_sc, R, bits);
+  BPPP_HIP(ctx, hipGetLastError());
+  return BPPP_OK;
+}
+int mulcheck_launch(bppp_ctx *ctx, size_t n, const uint32_t *c, const uint32_t *X, const uint32_t *P, const uint32_t *R, const uint32_t *pre, uint32_t *status) {
+  k_rp_excess_mulcheck<<<dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, ctx->stream>>>((uint32_t)n, c, X, P, R, pre, status);
+  BPPP_HIP(ctx, hipGetLastError());
+  return BPPP_OK;
+}
+int weights_launch(bppp_ctx *ctx, size_t n, uint32_t slot, uint64_t j0, const uint8_t *seed, const uint8_t *sigs, const uint32_t *X, const uint8_t *msgs, const uint32_t *pre,
+                   const uint32_t *c, const uint32_t *in_sc, const uint32_t *R, uint32_t *prods, uint32_t *sc, uint32_t *pt, uint32_t *any) {
+  k_rp_excess_weights<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream>>>((uint32_t)n, slot, j0, seed, sigs, X, msgs, pre, c, in_sc, R, prods, sc, pt, any);
+  BPPP_HIP(ctx, hipGetLastError());
+  return BPPP_OK;
+}
+
+}  // namespace excess
+}  // namespace bppp
+
 using namespace bppp;
 using namespace bppp::tally;
+using namespace bppp::excess;
 
 namespace {
 
 constexpr size_t SIGN_CHUNK = (size_t)1 << 22;         // sums per pass of the signer over the workspace
-
-// SHA-256 (label || tag), once per call on the host
-ExDomain domain(const char *label, const std::string &tag) {
-  Sha256 h;
-  h.update(label, strlen(label));
-  h.update(tag.data(), tag.size());
-  ExDomain d;
-  h.finish(d.w);
-  return d;
-}
-ExDomain challenge_domain(const bppp_rp *rp) { return domain("bppp/excess/challenge/v1", rp->tag); }
-ExDomain nonce_domain(const bppp_rp *rp) { return domain("bppp/excess/nonce/v1", rp->tag); }
-uint32_t blind_slot(const bppp_rp *rp) { return rp->st.kind == 1 ? 1u : 2u; }     // B among [g | H0 | H1]: h0 of a binary handle, else H1
 
 const char *sign_status_text(uint32_t s) {
   return s == BPPP_RP_EXCESS_NOT_CANONICAL ? "the blinding sum is not canonical (>= n)"

@@ -1,0 +1,78 @@
+// rpexcess_shared.hip.h — what the two excess files share: the derived-key path (csrc/rpexcess.hip: the key X_t comes out of the pool) and
+// the stated-key path (csrc/rpexkeys.hip: the key is 33 bytes next to the signature).  The domains, the three-block hash and the challenge
+// are one definition, so that the 65 bytes bppp_rp_excess_sign writes verify on either path; the kernels both paths run stay in
+// csrc/rpexcess.hip and are reached through the launches declared at the end.
+#pragma once
+#include <string.h>
+#include <string>
+#include "ec.hip.h"
+#include "rp_internal.hpp"
+#include "rpprove_host.hpp"
+#include "rpwords.hip.h"
+#include "sha256.hip.h"
+
+namespace bppp {
+
+static constexpr uint32_t EX_SIG = BPPP_RP_EXCESS_SIG_BYTES, EX_MSG = 32, EX_KEY = BPPP_RP_EXCESS_KEY_BYTES;
+static constexpr uint32_t EX_EVAL = 0xFFFFFFFFu;       // a verdict still open: the equation decides
+struct ExDomain { uint32_t w[8]; };                    // a domain digest as the eight big-endian words it is hashed as
+
+BPPP_DI uint32_t ex_dom_byte(const ExDomain &d, uint32_t k) { return (d.w[k >> 2] >> (24 - 8 * (k & 3))) & 0xFFu; }
+// byte o (< 33) of an affine point as a signature, a key and the messages hold it: put (x), then the sign byte (y > p - y)
+BPPP_DI uint32_t ex_pt_byte(const uint32_t *pt, uint32_t o) { return o < 32 ? enc_be_byte(pt, o) : enc_sign(pt); }
+// decode (SHA-256 (message)) mod n of a message of 120 .. 183 bytes (three blocks), byte k of it being at (k)
+template <class F> BPPP_DI fe ex_hash3(uint32_t nbytes, F at) {
+  uint32_t st[8], w[16];
+  sha256_init(st);
+#pragma unroll
+  for (uint32_t blk = 0; blk < 3; blk++) {
+#pragma unroll
+    for (uint32_t q = 0; q < 16; q++) {
+      uint32_t word = 0;
+#pragma unroll
+      for (uint32_t r = 0; r < 4; r++) {
+        const uint32_t k = 64 * blk + 4 * q + r;
+        word = (word << 8) | (k < nbytes ? (at(k) & 0xFFu) : k == nbytes ? 0x80u : 0u);
+      }
+      w[q] = word;
+    }
+    if (blk == 2) w[15] = nbytes * 8;
+    sha256_compress(st, w);
+  }
+  fe r; sha256_digest_to_limbs(st, r.v);
+  return wi_umod_n(r);
+}
+// c = decode (SHA-256 (Dc || the 33 bytes of R || put (X.x) || sign (X) || msg)) mod n: 130 bytes; rbyte (o): byte o of R as the signature holds it
+template <class F> BPPP_DI fe ex_challenge(const ExDomain &dc, F rbyte, const uint32_t *X, const uint8_t *msg) {
+  return ex_hash3(32 + 33 + 33 + EX_MSG, [&](uint32_t k) -> uint32_t {
+    if (k < 32) return ex_dom_byte(dc, k);
+    if (k < 65) return rbyte(k - 32);
+    if (k < 98) return ex_pt_byte(X, k - 65);
+    return msg[k - 98];
+  });
+}
+
+namespace excess {
+
+// SHA-256 (label || tag), once per call on the host
+inline ExDomain domain(const char *label, const std::string &tag) {
+  Sha256 h;
+  h.update(label, strlen(label));
+  h.update(tag.data(), tag.size());
+  ExDomain d;
+  h.finish(d.w);
+  return d;
+}
+inline ExDomain challenge_domain(const bppp_rp *rp) { return domain("bppp/excess/challenge/v1", rp->tag); }
+inline ExDomain nonce_domain(const bppp_rp *rp) { return domain("bppp/excess/nonce/v1", rp->tag); }
+inline uint32_t blind_slot(const bppp_rp *rp) { return rp->st.kind == 1 ? 1u : 2u; }     // B among [g | H0 | H1]: h0 of a binary handle, else H1
+
+// the kernels of csrc/rpexcess.hip that serve the stated keys as they are, queued on the context's stream with the grids its own calls give them:
+// k_rp_excess_sigs (s canonical, R lifted), k_rp_excess_mulcheck (the equation, one quad a signature) and k_rp_excess_weights (the batch's terms)
+int sigs_launch(bppp_ctx *ctx, size_t n, uint32_t slot, const uint8_t *sigs, uint32_t *in_sc, uint32_t *R, uint32_t *bits);
+int mulcheck_launch(bppp_ctx *ctx, size_t n, const uint32_t *c, const uint32_t *X, const uint32_t *P, const uint32_t *R, const uint32_t *pre, uint32_t *status);
+int weights_launch(bppp_ctx *ctx, size_t n, uint32_t slot, uint64_t j0, const uint8_t *seed, const uint8_t *sigs, const uint32_t *X, const uint8_t *msgs, const uint32_t *pre,
+                   const uint32_t *c, const uint32_t *in_sc, const uint32_t *R, uint32_t *prods, uint32_t *sc, uint32_t *pt, uint32_t *any);
+
+}  // namespace excess
+}  // namespace bppp

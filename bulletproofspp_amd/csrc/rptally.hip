@@ -252,7 +252,7 @@ int tally_checks(Job &J, bool null_args, bool claims) {
   if (claims) {
     const bool binary = rp->st.kind == 1;
     const int given = (J.amt ? 1 : 0) + (J.bl ? 1 : 0) + ((!binary && J.ty) ? 1 : 0), all = binary ? 2 : 3;
-    if (given && given != all) return fail(ctx, BPPP_ERR_ARG, who + ": claim_amounts, claim_types and claim_blinds must be given together or all be NULL");
+    if (given && given != all) return fail(ctx, BPPP_ERR_ARG, who + ": claim_amounts, claim_types and " + J.bl_name + " must be given together or all be NULL");
     J.zero_claims = !given;
   }
   hipSetDevice(ctx->device);
@@ -287,13 +287,14 @@ Levels plan_levels(const Job &J, size_t t0, size_t t1) {
 }
 
 // ns: the sums of the largest chunk; each: the per-sum pass (ni items, np[2] partial points); batch: the weighted combination (ne entries a MSM);
-// extra: bytes behind everything else for the caller's own arrays (csrc/rpexcess.hip), so that the arrays above lie where they lay without them
+// extra: bytes behind everything else for the caller's own arrays (csrc/rpexcess.hip), so that the arrays above lie where they lay without them;
+// J.tail: points behind the decoded pool that the caller fills (csrc/rpexkeys.hip), none in a plain tally
 int carve(const Job &J, size_t ns, bool each, size_t ni, const size_t np[2], bool batch, size_t ne, Work &W, size_t extra) {
   bppp_rp *rp = J.rp;
   const size_t total = J.rows * rp->D.nr, R = std::max<size_t>(1, std::min<size_t>(J.rows, ((size_t)1 << 22) / rp->D.nr));
   for (int pass = 0; pass < 2; pass++) {
     Carver cv(pass ? rp->pwork : nullptr, rp->pwork_bytes);
-    W.pool = cv.take<uint32_t>(total * 16 + 16); W.bad = cv.take<uint32_t>(R); W.any = cv.take<uint32_t>(4);
+    W.pool = cv.take<uint32_t>((total + J.tail) * 16 + 16); W.bad = cv.take<uint32_t>(R); W.any = cv.take<uint32_t>(4);
     W.in_sc = cv.take<uint32_t>(ns * 24); W.flag = cv.take<uint32_t>(ns); W.zero = cv.take<uint32_t>(J.zero_claims ? ns * 8 : 0);
     W.sums = cv.take<uint32_t>(each ? ns * XYZZ_WORDS : 0); W.malformed = cv.take<uint32_t>(each ? ns : 0); W.rec = cv.take<uint32_t>(each ? ns * 16 : 0);
     W.status = cv.take<uint32_t>(each ? ns : 0); W.zz = cv.take<uint32_t>(each ? ns * 8 : 0); W.zinv = cv.take<uint32_t>(each ? ns * 8 : 0);
@@ -352,13 +353,11 @@ int affine_launch(bppp_ctx *ctx, size_t n, const uint32_t *sums, const uint32_t 
 }  // namespace tally
 }  // namespace bppp
 
-using namespace bppp;
-using namespace bppp::tally;
-
-namespace {
+namespace bppp {
+namespace tally {
 
 // sums [t0, t0 + ns): the claimed scalars in W.in_sc / W.flag, W.any[1] raised by a non-canonical one
-int claim_scalars(const Job &J, const Work &W, size_t t0, size_t ns) {
+static int claim_scalars(const Job &J, const Work &W, size_t t0, size_t ns) {
   bppp_ctx *ctx = J.rp->ctx;
   if (J.zero_claims) {
     BPPP_HIP(ctx, hipMemsetAsync(W.zero, 0, ns * 32, ctx->stream));
@@ -368,7 +367,11 @@ int claim_scalars(const Job &J, const Work &W, size_t t0, size_t ns) {
 }
 
 // every sum decided on its own: status [nsums] and, when not NULL, sums_xy [nsums][8], both on the host.  The job has passed tally_checks.
-int each_pass(const Job &J, uint32_t *status, uint64_t *sums_xy) {
+// ext (rp_internal.hpp): what the stated keys add; nullptr queues a plain tally's launches
+int each_pass(const Job &J0, uint32_t *status, uint64_t *sums_xy, const Ext *ext) {
+  Job Jx;
+  if (ext) Jx = J0;                             // prepare points its copy at the merged arrays
+  const Job &J = ext ? Jx : J0;
   bppp_rp *rp = J.rp;
   bppp_ctx *ctx = rp->ctx;
   hipStream_t st = ctx->stream;
@@ -383,13 +386,15 @@ int each_pass(const Job &J, uint32_t *status, uint64_t *sums_xy) {
     for (int k = 0; k < 2; k++) np[k] = std::max(np[k], plans[c].npart[k]);
   }
   Work W;
-  if ((rc = carve(J, ns_max, true, ni, np, false, 0, W)) || (rc = decode_pool(J, W))) return rc;
+  if ((rc = carve(J, ns_max, true, ni, np, false, 0, W, ext ? ext->extra : 0)) || (rc = decode_pool(J, W))) return rc;
+  if (ext && (rc = ext->prepare(Jx, W))) return rc;
   for (size_t c = 0; c + 1 < cb.size(); c++) {
     const size_t t0 = cb[c], ns = cb[c + 1] - t0;
     if ((rc = sum_launches(J, W, t0, ns, plans[c]))) return rc;
     if ((rc = claim_scalars(J, W, t0, ns)) || (rc = rpp_commit_inputs(rp, W.in_sc, ns, W.rec))) return rc;
     k_rp_tally_compare<<<dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st>>>((uint32_t)ns, W.sums, W.rec, W.flag, W.malformed, W.status, sums_xy ? W.zz : nullptr);
     BPPP_HIP(ctx, hipGetLastError());
+    if (ext && (rc = ext->judge(W, t0, ns, sums_xy != nullptr))) return rc;
     BPPP_HIP(ctx, hipMemcpyAsync(status + t0, W.status, ns * 4, hipMemcpyDeviceToHost, st));
     if (sums_xy) {
       if ((rc = batch_inverse_run(ctx, W.zz, ns, 0, W.zinv))) return rc;
@@ -401,35 +406,16 @@ int each_pass(const Job &J, uint32_t *status, uint64_t *sums_xy) {
   return BPPP_OK;
 }
 
-int fill(Job &J, bppp_rp *rp, const char *who, size_t rows, const void *coms, size_t nsums, const void *start, const void *entries, size_t nnz, const void *amt,
-         const void *ty, const void *bl) {
-  J.rp = rp; J.who = who; J.rows = rows; J.nsums = nsums; J.nnz = nnz;
-  J.coms = (const uint8_t *)coms; J.start = (const uint32_t *)start; J.entries = (const uint32_t *)entries;
-  J.amt = (const uint32_t *)amt; J.ty = rp->st.kind == 1 ? nullptr : (const uint32_t *)ty; J.bl = (const uint32_t *)bl;
-  return BPPP_OK;
-}
-
-int tally_each_device(bppp_rp *rp, size_t rows, const void *d_coms, size_t nsums, const void *d_start, const void *d_entries, size_t nnz, const void *d_amt, const void *d_ty,
-                      const void *d_bl, uint32_t *status, uint64_t *sums_xy) {
-  if (!rp) return BPPP_ERR_ARG;
-  if (ctx_closed(rp->ctx)) return BPPP_ERR_ARG;
-  if (!nsums) return BPPP_OK;
-  Job J;
-  fill(J, rp, "rp_tally_each", rows, d_coms, nsums, d_start, d_entries, nnz, d_amt, d_ty, d_bl);
-  int rc = tally_checks(J, (rows && !d_coms) || !status, true);
-  return rc ? rc : each_pass(J, status, sums_xy);
-}
-
-int tally_batch_device(bppp_rp *rp, size_t rows, const void *d_coms, size_t nsums, const void *d_start, const void *d_entries, size_t nnz, const void *d_amt, const void *d_ty,
-                       const void *d_bl, uint64_t index_offset, const uint8_t seed[32], int *accept, uint32_t *status, uint64_t *combined_xy) {
-  if (!rp || !accept) return BPPP_ERR_ARG;
+// all sums by one weighted combination per pass: *accept, status (NULL, or [nsums]: one exact pass when rejected) and combined_xy (NULL or [8]), on
+// the host.  The job has passed tally_checks and *accept is 0.  ext as for each_pass.
+int batch_run(const Job &J0, uint64_t index_offset, const uint8_t seed[32], int *accept, uint32_t *status, uint64_t *combined_xy, const Ext *ext) {
+  Job Jx;
+  if (ext) Jx = J0;
+  const Job &J = ext ? Jx : J0;
+  bppp_rp *rp = J.rp;
   bppp_ctx *ctx = rp->ctx;
-  if (ctx_closed(ctx)) return BPPP_ERR_ARG;
-  *accept = 0;
-  if (!nsums) { if (combined_xy) memset(combined_xy, 0, 64); *accept = 1; return BPPP_OK; }
-  Job J;
-  fill(J, rp, "rp_tally_batch", rows, d_coms, nsums, d_start, d_entries, nnz, d_amt, d_ty, d_bl);
-  int rc = tally_checks(J, (rows && !d_coms) || !seed, true); if (rc) return rc;
+  const size_t nsums = J.nsums, nnz = J.nnz;
+  int rc;
   if (combined_xy) memset(combined_xy, 0, 64);
   hipStream_t st = ctx->stream;
   const std::vector<size_t> cb = chunk_bounds(J);
@@ -437,7 +423,8 @@ int tally_batch_device(bppp_rp *rp, size_t rows, const void *d_coms, size_t nsum
   size_t ns_max = 0;
   for (size_t c = 0; c + 1 < cb.size(); c++) ns_max = std::max(ns_max, cb[c + 1] - cb[c]);
   Work W;
-  if ((rc = carve(J, ns_max, false, 0, no_parts, true, std::min(E, std::max<size_t>(1, nnz)), W)) || (rc = decode_pool(J, W))) return rc;
+  if ((rc = carve(J, ns_max, false, 0, no_parts, true, std::min(E, std::max<size_t>(1, nnz)), W, ext ? ext->extra : 0)) || (rc = decode_pool(J, W))) return rc;
+  if (ext && (rc = ext->prepare(Jx, W))) return rc;
   BPPP_HIP(ctx, hipMemcpyAsync(W.seed, seed, 32, hipMemcpyHostToDevice, st));
   BPPP_HIP(ctx, hipMemsetAsync(W.any, 0, 8, st));
   std::vector<uint64_t> parts;                  // one combined point per MSM
@@ -469,10 +456,52 @@ int tally_batch_device(bppp_rp *rp, size_t rows, const void *d_coms, size_t nsum
   uint64_t xy[8];
   if ((rc = bppp_sum_points(ctx, parts.data(), parts.size() / 8, xy))) return rc;
   if (combined_xy) memcpy(combined_xy, xy, 64);
-  *accept = (rp_point_is_inf(xy) && !any[0] && !any[1]) ? 1 : 0;
+  bool reject = false;
+  if (ext && (rc = ext->rejects(W, reject))) return rc;
+  *accept = (rp_point_is_inf(xy) && !any[0] && !any[1] && !reject) ? 1 : 0;
   if (!status) return BPPP_OK;
   if (*accept) { memset(status, 0, nsums * 4); return BPPP_OK; }
-  return each_pass(J, status, nullptr);         // one exact pass, whatever the number of bad sums
+  return each_pass(J0, status, nullptr, ext);   // one exact pass, whatever the number of bad sums
+}
+
+}  // namespace tally
+}  // namespace bppp
+
+using namespace bppp;
+using namespace bppp::tally;
+
+namespace {
+
+int fill(Job &J, bppp_rp *rp, const char *who, size_t rows, const void *coms, size_t nsums, const void *start, const void *entries, size_t nnz, const void *amt,
+         const void *ty, const void *bl) {
+  J.rp = rp; J.who = who; J.rows = rows; J.nsums = nsums; J.nnz = nnz;
+  J.coms = (const uint8_t *)coms; J.start = (const uint32_t *)start; J.entries = (const uint32_t *)entries;
+  J.amt = (const uint32_t *)amt; J.ty = rp->st.kind == 1 ? nullptr : (const uint32_t *)ty; J.bl = (const uint32_t *)bl;
+  return BPPP_OK;
+}
+
+int tally_each_device(bppp_rp *rp, size_t rows, const void *d_coms, size_t nsums, const void *d_start, const void *d_entries, size_t nnz, const void *d_amt, const void *d_ty,
+                      const void *d_bl, uint32_t *status, uint64_t *sums_xy) {
+  if (!rp) return BPPP_ERR_ARG;
+  if (ctx_closed(rp->ctx)) return BPPP_ERR_ARG;
+  if (!nsums) return BPPP_OK;
+  Job J;
+  fill(J, rp, "rp_tally_each", rows, d_coms, nsums, d_start, d_entries, nnz, d_amt, d_ty, d_bl);
+  int rc = tally_checks(J, (rows && !d_coms) || !status, true);
+  return rc ? rc : each_pass(J, status, sums_xy);
+}
+
+int tally_batch_device(bppp_rp *rp, size_t rows, const void *d_coms, size_t nsums, const void *d_start, const void *d_entries, size_t nnz, const void *d_amt, const void *d_ty,
+                       const void *d_bl, uint64_t index_offset, const uint8_t seed[32], int *accept, uint32_t *status, uint64_t *combined_xy) {
+  if (!rp || !accept) return BPPP_ERR_ARG;
+  bppp_ctx *ctx = rp->ctx;
+  if (ctx_closed(ctx)) return BPPP_ERR_ARG;
+  *accept = 0;
+  if (!nsums) { if (combined_xy) memset(combined_xy, 0, 64); *accept = 1; return BPPP_OK; }
+  Job J;
+  fill(J, rp, "rp_tally_batch", rows, d_coms, nsums, d_start, d_entries, nnz, d_amt, d_ty, d_bl);
+  int rc = tally_checks(J, (rows && !d_coms) || !seed, true); if (rc) return rc;
+  return batch_run(J, index_offset, seed, accept, status, combined_xy, nullptr);
 }
 
 int tally_claims_device(bppp_rp *rp, size_t rows, const void *d_amt, const void *d_ty, const void *d_bl, size_t nsums, const void *d_start, const void *d_entries, size_t nnz,

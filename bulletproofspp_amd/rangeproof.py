@@ -1370,6 +1370,123 @@ class NativeRangeProofs:
                                                                         p(d_msgs), p(d_sigs), index_offset, *a)
         return self._tally_batch(fn, nsums, seed, want_status, want_point)
 
+    # ---- excess keys: the excess stated as 33 bytes, for signatures checked with no pool and sums checked after cut-through
+    # (bppp_rp_excess_keys / _verify_keys_each / _verify_keys_batch / _sums_each / _sums_batch)
+    def excess_keys(self, blinds: Sequence[int], want_status: bool = False):
+        """bppp_rp_excess_keys: the 33-byte key X = e B of every blinding sum.  Returns the keys, or (keys, statuses) with want_status (a refused
+        sum has 33 zero bytes); without it a refused sum raises BpppError."""
+        import ctypes as C
+        import numpy as np
+        from .capi import scalars_to_array
+        n = len(blinds)
+        bl, ks = scalars_to_array(list(blinds) or [0]), np.zeros(max(n, 1) * EXCESS_KEY_BYTES, dtype=np.uint8)
+        st = self._excess_keys(self.gpu.lib.bppp_rp_excess_keys, n, C.c_void_p(bl.ctypes.data), C.c_void_p(ks.ctypes.data), want_status)
+        raw = ks.tobytes()
+        out = [raw[t * EXCESS_KEY_BYTES:(t + 1) * EXCESS_KEY_BYTES] for t in range(n)]
+        return (out, st) if want_status else out
+
+    def excess_keys_device(self, nsums: int, d_blinds: int, d_keys: int, want_status: bool = False):
+        """bppp_rp_excess_keys_device: excess_keys on buffers in HBM (d_keys receives [nsums][33] bytes); returns the statuses or None"""
+        import ctypes as C
+        return self._excess_keys(self.gpu.lib.bppp_rp_excess_keys_device, nsums, C.c_void_p(d_blinds), C.c_void_p(d_keys), want_status)
+
+    def _excess_keys(self, fn, n, pb, pk, want_status):
+        import ctypes as C
+        import numpy as np
+        status = np.zeros(max(n, 1), dtype=np.uint32)
+        self.gpu._check(fn(self.h, n, pb, pk, C.c_void_p(status.ctypes.data) if want_status else None), "bppp_rp_excess_keys")
+        return [int(v) for v in status[:n]] if want_status else None
+
+    def _excess_key_args(self, keys, msgs, sigs):
+        import ctypes as C
+        n = len(keys)
+        if len(msgs) != n or len(sigs) != n:
+            raise ValueError("one message and one signature per key are required")
+        keep = [self._excess_bytes(keys, EXCESS_KEY_BYTES, "keys"), self._excess_bytes(msgs, 32, "messages"), self._excess_bytes(sigs, EXCESS_SIG_BYTES, "signatures")]
+        return keep, n, (n,) + tuple(C.c_void_p(a.ctypes.data) for a in keep)
+
+    def excess_verify_keys_each(self, keys: Sequence[bytes], msgs: Sequence[bytes], sigs: Sequence[bytes]):
+        """bppp_rp_excess_verify_keys_each: does sigs[t] sign msgs[t] under the stated key keys[t]?  No pool is needed.  Returns one verdict per key
+        (capi.RP_OPEN_OK / _MISMATCH / _NOT_CANONICAL, RP_EXCESS_BAD_R, RP_EXCESS_BAD_KEY)."""
+        keep, n, args = self._excess_key_args(keys, msgs, sigs)
+        return self._excess_keys_each(self.gpu.lib.bppp_rp_excess_verify_keys_each, n, args)
+
+    def excess_verify_keys_each_device(self, nkeys: int, d_keys: int, d_msgs: int, d_sigs: int):
+        """bppp_rp_excess_verify_keys_each_device: excess_verify_keys_each on buffers in HBM"""
+        import ctypes as C
+        p = C.c_void_p
+        return self._excess_keys_each(self.gpu.lib.bppp_rp_excess_verify_keys_each_device, nkeys, (nkeys, p(d_keys), p(d_msgs), p(d_sigs)))
+
+    def _excess_keys_each(self, fn, n, args):
+        import ctypes as C
+        import numpy as np
+        status = np.zeros(max(n, 1), dtype=np.uint32)
+        self.gpu._check(fn(self.h, *args, C.c_void_p(status.ctypes.data)), "bppp_rp_excess_verify_keys_each")
+        return [int(v) for v in status[:n]]
+
+    def excess_verify_keys_batch(self, keys: Sequence[bytes], msgs: Sequence[bytes], sigs: Sequence[bytes], seed: Optional[bytes] = None, want_status: bool = False,
+                                 want_point: bool = False):
+        """bppp_rp_excess_verify_keys_batch: every signature under its stated key with one weighted combination (weights: excess_weight over the lifted
+        key).  Returns accept, or (accept, verdicts or None, combined point or None) when want_status / want_point is set."""
+        keep, n, args = self._excess_key_args(keys, msgs, sigs)
+        fn = lambda *a: self.gpu.lib.bppp_rp_excess_verify_keys_batch(self.h, *args, *a)
+        return self._tally_batch(fn, n, seed, want_status, want_point)
+
+    def excess_verify_keys_batch_device(self, nkeys: int, d_keys: int, d_msgs: int, d_sigs: int, seed: Optional[bytes] = None, index_offset: int = 0,
+                                        want_status: bool = False, want_point: bool = False):
+        """bppp_rp_excess_verify_keys_batch_device: excess_verify_keys_batch on buffers in HBM; this call holds keys [index_offset, index_offset + nkeys) of a
+        sharded job whose ranks all pass the same seed (their combined points add up to the one-call point)"""
+        import ctypes as C
+        p = C.c_void_p
+        fn = lambda *a: self.gpu.lib.bppp_rp_excess_verify_keys_batch_device(self.h, nkeys, p(d_keys), p(d_msgs), p(d_sigs), index_offset, *a)
+        return self._tally_batch(fn, nkeys, seed, want_status, want_point)
+
+    def _excess_sums_host_args(self, coms_files, sum_start, entries, claims, key_start, keys):
+        import ctypes as C
+        import numpy as np
+        ss, en, nsums, nnz = self._tally_csr(sum_start, entries)
+        if len(key_start) != nsums + 1:
+            raise ValueError("key_start holds nsums + 1 offsets")
+        amt, typ, off = self._tally_claim_arrays(claims, nsums)
+        keep = [self._coms_array(coms_files, len(coms_files)), ss, en, amt, typ, off, np.array(list(key_start), dtype=np.uint32), self._excess_bytes(keys, EXCESS_KEY_BYTES, "keys")]
+        vp = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+        cf, ss, en, amt, typ, off, ks, ky = keep
+        return keep, nsums, (len(coms_files), vp(cf), nsums, vp(ss), vp(en), nnz, vp(amt), vp(typ), vp(off), len(keys), vp(ks), vp(ky))
+
+    def excess_sums_each(self, coms_files: Sequence[bytes], sum_start, entries, claims, key_start, keys: Sequence[bytes], want_points: bool = False):
+        """bppp_rp_excess_sums_each: does sum t, less claims[t] = (amount, type, offset) ((amount, offset) on a binary handle; None: zero claims), equal
+        the sum of the stated keys keys[key_start[t]:key_start[t + 1]]?  Returns one verdict per sum (capi.RP_OPEN_* / RP_EXCESS_BAD_KEY), or (verdicts,
+        points) with want_points: S_t less its keys, None for the identity, a MALFORMED and a BAD_KEY sum."""
+        keep, nsums, args = self._excess_sums_host_args(coms_files, sum_start, entries, claims, key_start, keys)
+        return self._excess_each(self.gpu.lib.bppp_rp_excess_sums_each, nsums, args, want_points)
+
+    def excess_sums_each_device(self, rows: int, d_coms: int, nsums: int, d_sum_start: int, d_entries: int, nnz: int, d_amounts: int, d_types: int, d_offsets: int,
+                                nkeys: int, d_key_start: int, d_keys: int, want_points: bool = False):
+        """bppp_rp_excess_sums_each_device: excess_sums_each on buffers in HBM (0 for all three claim arrays: zero claims)"""
+        import ctypes as C
+        p = C.c_void_p
+        return self._excess_each(self.gpu.lib.bppp_rp_excess_sums_each_device, nsums,
+                                 (rows, p(d_coms), nsums, p(d_sum_start), p(d_entries), nnz, p(d_amounts), p(d_types), p(d_offsets), nkeys, p(d_key_start), p(d_keys)), want_points)
+
+    def excess_sums_batch(self, coms_files: Sequence[bytes], sum_start, entries, claims, key_start, keys: Sequence[bytes], seed: Optional[bytes] = None,
+                          want_status: bool = False, want_point: bool = False):
+        """bppp_rp_excess_sums_batch: every sum against its stated keys with one weighted combination (weights: tally_weight over (amount, type,
+        offset)).  Returns accept, or (accept, verdicts or None, combined point or None) when want_status / want_point is set."""
+        keep, nsums, args = self._excess_sums_host_args(coms_files, sum_start, entries, claims, key_start, keys)
+        fn = lambda *a: self.gpu.lib.bppp_rp_excess_sums_batch(self.h, *args, *a)
+        return self._tally_batch(fn, nsums, seed, want_status, want_point)
+
+    def excess_sums_batch_device(self, rows: int, d_coms: int, nsums: int, d_sum_start: int, d_entries: int, nnz: int, d_amounts: int, d_types: int, d_offsets: int,
+                                 nkeys: int, d_key_start: int, d_keys: int, seed: Optional[bytes] = None, index_offset: int = 0, want_status: bool = False,
+                                 want_point: bool = False):
+        """bppp_rp_excess_sums_batch_device: excess_sums_batch on buffers in HBM; this call holds sums [index_offset, index_offset + nsums) of a sharded job
+        whose ranks all pass the same seed (their combined points add up to the one-call point)"""
+        import ctypes as C
+        p = C.c_void_p
+        fn = lambda *a: self.gpu.lib.bppp_rp_excess_sums_batch_device(self.h, rows, p(d_coms), nsums, p(d_sum_start), p(d_entries), nnz, p(d_amounts), p(d_types), p(d_offsets),
+                                                                      nkeys, p(d_key_start), p(d_keys), index_offset, *a)
+        return self._tally_batch(fn, nsums, seed, want_status, want_point)
+
     def share_comb(self, donor: "NativeRangeProofs"):
         """bppp_rp_share_comb: prove over `donor`'s comb table from now on (built now if it has none).  Same context; the donor's basis
         must extend this handle's point by point.  The table lives until its last user is closed."""
@@ -1569,6 +1686,8 @@ def tally_claims_host(triples: Sequence[Tuple[int, int, int]], sum_start: Sequen
 FIELD_P = 2**256 - 2**32 - 977
 EXCESS_SIG_BYTES = 65
 EXCESS_OK, EXCESS_NOT_CANONICAL, EXCESS_ZERO, EXCESS_NONCE, EXCESS_BAD_R, EXCESS_NO_KEY = 0, 1, 2, 3, 4, 5
+EXCESS_KEY_BYTES = 33
+EXCESS_BAD_KEY = 6
 
 
 def _put(s: int) -> bytes:
@@ -1647,6 +1766,57 @@ def excess_verify_host(backend: "Backend", setup, S: Point, claim, msg: bytes, s
         return EXCESS_NO_KEY
     c = excess_challenge(tag, sig[:33], X, msg)
     return 0 if _commit_terms(backend, [(s, B), (-c, X)]) == (x, y) else 1
+
+
+# ---- the stated keys (bppp_rp_excess_keys / _verify_keys_* / _sums_*)
+def excess_key33(X: Tuple[int, int]) -> bytes:
+    """the 33 bytes of a key: put (x), then the sign byte (1 when y > p - y)"""
+    return _point33(X)
+
+
+def excess_lift33(b33: bytes) -> Optional[Tuple[int, int]]:
+    """the point 33 bytes name, as the library lifts a key and the R of a signature: x reduced mod p, the root of x^3 + 7 with the stated sign; None
+    when the sign byte is above 1 or x has no curve point"""
+    x = decode_field(b33[:32], FIELD_P)
+    y = pow((x * x * x + 7) % FIELD_P, (FIELD_P + 1) // 4, FIELD_P)
+    if b33[32] > 1 or (y * y - x * x * x - 7) % FIELD_P:
+        return None
+    return (x, y if (y > FIELD_P - y) == bool(b33[32]) else FIELD_P - y)
+
+
+def excess_verify_key_host(backend: "Backend", setup, key: bytes, msg: bytes, sig: bytes, tag: bytes = b"") -> int:
+    """Host restatement of bppp_rp_excess_verify_keys_each for one (key, message, signature): the first verdict that applies, in the header's order.
+    The challenge hashes the canonical bytes of the lifted key."""
+    _, _, B = _excess_bases(setup)
+    X = excess_lift33(key)
+    if X is None:
+        return EXCESS_BAD_KEY
+    s = sum(int.from_bytes(sig[33 + 8 * i:41 + 8 * i], "big") << (64 * i) for i in range(4))
+    if s >= N:
+        return 3
+    R = excess_lift33(sig[:33])
+    if R is None:
+        return EXCESS_BAD_R
+    c = excess_challenge(tag, sig[:33], X, msg)
+    return 0 if _commit_terms(backend, [(s, B), (-c, X)]) == R else 1
+
+
+def excess_sums_host(backend: "Backend", setup, S: Point, claim, keys: Sequence[bytes], malformed: bool = False):
+    """Host restatement of bppp_rp_excess_sums_each for one sum S (None: the identity; malformed: some referenced x has no curve point) with the
+    revealed claim (a, ty, o) ((a, o) on a binary setup) and the stated keys of its group: (verdict, S less the keys — None for the identity, a
+    malformed sum and one with a key that does not lift)"""
+    g, H0, B = _excess_bases(setup)
+    a, ty, o = claim if H0 is not None else (claim[0], 0, claim[-1])
+    if malformed:
+        return 2, None
+    Xs = [excess_lift33(k) for k in keys]
+    if None in Xs:
+        return EXCESS_BAD_KEY, None
+    rest = _commit_terms(backend, [(1, S)] + [(-1, X) for X in Xs])
+    if not 0 <= ty < N or not 0 <= o < N:
+        return 3, rest
+    want = _commit_terms(backend, [(a, g), (o, B)] + ([(ty, H0)] if H0 is not None else []))
+    return (0 if rest == want else 1), rest
 
 
 def _mixed_groups(files):

@@ -876,6 +876,93 @@ int bppp_rp_excess_verify_batch_device(bppp_rp *rp, size_t rows, const void *d_c
                                        size_t nnz, const void *d_claim_amounts, const void *d_claim_types, const void *d_msgs, const void *d_sigs,
                                        uint64_t index_offset, const uint8_t seed[32], int *accept, uint32_t *status, uint64_t *combined_xy);
 
+/* ---- excess keys: the excess stated as a public key, so that signatures and sums still check after cut-through ------------------------------
+ * The calls above derive X_t from the pool, so a signature can only be checked by someone who holds every input and output of its
+ * transaction.  Here the transaction PUBLISHES its excess as a key next to the signature.  Then (1) an archive node or a mempool checks (key,
+ * message, signature) triples with no commitment in hand, and (2) a block that has merged its transactions and dropped the outputs spent inside
+ * it (cut-through) is still checked as one sum: the remaining outputs minus the inputs, minus the fees, minus a revealed offset, equal the sum of
+ * the stated keys.  Domains, messages, put, decode, the sign byte and B are those of the excess signatures above; a signature made by
+ * bppp_rp_excess_sign verifies under the stated key X_t = e_t B, the same 65 bytes.
+ *
+ * KEY.  keys [n][BPPP_RP_EXCESS_KEY_BYTES = 33]: put (x), then one sign byte, 0 or 1 (y > p - y) — exactly how a signature holds R.  It is lifted
+ * by the decoder the pool and R take (x is reduced mod p; the root of x^3 + 7 with that sign).  EVERY HASH THAT NAMES THE KEY — the challenge c and
+ * the weight rho of verify_keys_batch — TAKES THE CANONICAL 33 BYTES OF THE LIFTED POINT (put of the reduced x, the sign of the chosen y), not
+ * the bytes as they were passed: that is what the derived-key calls hash, so both paths give one verdict.  Infinity has no encoding, so there is
+ * no NO_KEY verdict here.  BPPP_RP_EXCESS_BAD_KEY (6): the sign byte is above 1, or x has no curve point.
+ *
+ * bppp_rp_excess_keys{,_device}: the builder's side.  claim_blinds [nsums][4] as bppp_rp_excess_sign takes them; keys [nsums][33] receives
+ * X_t = e_t B, over the table the signer uses.  key_status (host, may be NULL, [nsums]): BPPP_RP_EXCESS_OK, BPPP_RP_EXCESS_NOT_CANONICAL (e >= n)
+ * or BPPP_RP_EXCESS_ZERO (e = 0); a refused row gets 33 zero bytes.  With key_status == NULL a refusal is BPPP_ERR_ARG and bppp_last_error names
+ * the lowest refused sum ("sum N: ..."), as bppp_rp_excess_sign does; the keys are then as they would be with key_status given.
+ *
+ * bppp_rp_excess_verify_keys_each{,_device}: keys, msgs [nkeys][32], sigs [nkeys][65]; status [nkeys] (host, required), the first that applies of
+ *   BPPP_RP_EXCESS_BAD_KEY (6)      the key's sign byte is above 1, or its x has no curve point
+ *   BPPP_RP_OPEN_NOT_CANONICAL (3)  s >= n
+ *   BPPP_RP_EXCESS_BAD_R (4)        the sign byte of R is not 0 or 1, or R.x has no curve point
+ *   BPPP_RP_OPEN_MISMATCH (1) or BPPP_RP_OPEN_OK (0), from  s B - c X = R  with
+ *   c = decode (SHA-256 (Dc || sig[0..33) || the canonical 33 bytes of X || msg)) mod n      — the CHALLENGE above, 130 bytes.
+ * No pool is decoded, no sum is formed and nothing is inverted: one lane lifts a key, four lanes share the walk of c X.
+ *
+ * bppp_rp_excess_verify_keys_batch{,_device}: all signatures by ONE weighted combination per pass of 2^20 keys,
+ *   combined = sum_t rho_t (s_t B - c_t X_t - R_t)        over the keys whose verdict the equation has to give,
+ *   rho_t = decode (SHA-256 (seed[32] || le64 (index_offset + t) || sig_t[65] || the canonical 33 bytes of X_t || msg_t)) mod n, 1 in place of 0
+ *                                                                                                                      — 170 bytes,
+ * as one MSM over 2 nkeys + 1 terms, exactly as bppp_rp_excess_verify_batch.  *accept = 1 iff no key has a verdict other than OK or MISMATCH and
+ * combined is the identity (a BAD_KEY contributes no term and still rejects).  status (may be NULL): all OK when accepted; on rejection exactly
+ * verify_keys_each's verdicts, from one such pass.  combined_xy (may be NULL): the combined point, infinity as all zeros.  seed, index_offset and
+ * shards adding up with bppp_sum_points are as in bppp_rp_tally_batch_device; the host call is the _device call with index_offset 0.
+ * nkeys == 0 is BPPP_OK (*accept = 1).
+ *
+ * bppp_rp_excess_sums_each{,_device}: the tally's job — POOL, SUMS, entries and claims exactly as for bppp_rp_tally_each — plus the keys of every
+ * sum: key_start [nsums + 1] (uint32, required, non-decreasing, key_start[0] = 0, key_start[nsums] = nkeys) and keys [nkeys][33]; the keys of sum
+ * t are the contiguous rows key_start[t] .. key_start[t + 1].  Sum t must satisfy
+ *   S_t - a_t g - ty_t H0 - o_t B - sum of the keys of group t = identity        (a binary handle: no H0 term, claim_types ignored)
+ * claim_offsets is the tally's claim_blinds under its protocol name: a REVEALED scalar o_t.  Amounts, types and offsets all NULL: zero claims.
+ * status [nsums] (host, required), the first that applies of
+ *   BPPP_RP_OPEN_MALFORMED (2)      an x in a referenced commitment has no curve point
+ *   BPPP_RP_EXCESS_BAD_KEY (6)      a key of the group has a sign byte above 1 or an x without a curve point
+ *   BPPP_RP_OPEN_NOT_CANONICAL (3)  the claimed type or offset is >= n
+ *   BPPP_RP_OPEN_MISMATCH (1) or BPPP_RP_OPEN_OK (0).
+ * sums_xy (host, may be NULL, [nsums][8]): S_t - sum of the keys of group t; zeros for infinity, for a MALFORMED sum and for a BAD_KEY sum.  A
+ * group may be empty: that sum is exactly a tally.  DUPLICATE KEYS ARE NOT REJECTED: a key that stands twice is subtracted twice, in one group or in
+ * two — whether a key may be used again is the caller's rule (a chain keeps its own set of seen kernels).  The keys are lifted behind the decoded
+ * pool and merged into the sums, so a sum's keys are split into pieces and summed in the same pass as its entries: thousands of keys in one sum cost
+ * what thousands of entries cost.
+ *
+ * bppp_rp_excess_sums_batch{,_device}: combined = sum_t rho_t (S_t - a_t g - ty_t H0 - o_t B - sum of the keys of group t) as one MSM over
+ * nnz + nkeys + 3 terms per pass, with rho_t exactly bppp_rp_tally_batch's weight over (seed, index_offset + t, a_t, ty_t, o_t): the keys, like the
+ * pool, are the checker's own inputs fixed before the seed is drawn.  accept (a BAD_KEY rejects), status on rejection, combined_xy, index_offset and
+ * shards are as in bppp_rp_tally_batch_device.
+ *
+ * Errors (BPPP_ERR_ARG, bppp_last_error names the offender): those of bppp_rp_tally_each, and rows * nranges + nkeys >= 2^31, nnz + nkeys >= 2^31,
+ * a key_start that is not non-decreasing from 0 to nkeys ("key_start[i] = ...").  key_start is validated as sum_start is: by a kernel whose verdict
+ * is read back before anything reads through the array — a bad array is an error code, never an out-of-bounds read, and no output buffer is written.
+ * nsums == 0 is BPPP_OK (sums_batch with *accept = 1) and nothing else is looked at.  The host variants upload, call the _device variant and
+ * download; status and point arrays, aux and seed are host memory. */
+#define BPPP_RP_EXCESS_KEY_BYTES 33
+#define BPPP_RP_EXCESS_BAD_KEY 6u
+int bppp_rp_excess_keys(bppp_rp *rp, size_t nsums, const uint64_t *claim_blinds, uint8_t *keys, uint32_t *key_status /* may be NULL */);
+int bppp_rp_excess_keys_device(bppp_rp *rp, size_t nsums, const void *d_claim_blinds, void *d_keys, uint32_t *key_status /* host, [nsums], may be NULL */);
+int bppp_rp_excess_verify_keys_each(bppp_rp *rp, size_t nkeys, const uint8_t *keys, const uint8_t *msgs, const uint8_t *sigs, uint32_t *status);
+int bppp_rp_excess_verify_keys_each_device(bppp_rp *rp, size_t nkeys, const void *d_keys, const void *d_msgs, const void *d_sigs,
+                                           uint32_t *status /* host, [nkeys], required */);
+int bppp_rp_excess_verify_keys_batch(bppp_rp *rp, size_t nkeys, const uint8_t *keys, const uint8_t *msgs, const uint8_t *sigs, const uint8_t seed[32], int *accept,
+                                     uint32_t *status /* may be NULL */, uint64_t *combined_xy /* may be NULL */);
+int bppp_rp_excess_verify_keys_batch_device(bppp_rp *rp, size_t nkeys, const void *d_keys, const void *d_msgs, const void *d_sigs, uint64_t index_offset,
+                                            const uint8_t seed[32], int *accept, uint32_t *status /* host, may be NULL */, uint64_t *combined_xy /* may be NULL */);
+int bppp_rp_excess_sums_each(bppp_rp *rp, size_t rows, const uint8_t *coms_files, size_t nsums, const uint32_t *sum_start, const uint32_t *entries, size_t nnz,
+                             const uint64_t *claim_amounts, const uint64_t *claim_types, const uint64_t *claim_offsets, size_t nkeys, const uint32_t *key_start,
+                             const uint8_t *keys, uint32_t *status, uint64_t *sums_xy /* may be NULL */);
+int bppp_rp_excess_sums_each_device(bppp_rp *rp, size_t rows, const void *d_coms_files, size_t nsums, const void *d_sum_start, const void *d_entries, size_t nnz,
+                                    const void *d_claim_amounts, const void *d_claim_types, const void *d_claim_offsets, size_t nkeys, const void *d_key_start,
+                                    const void *d_keys, uint32_t *status /* host, [nsums], required */, uint64_t *sums_xy /* host, [nsums][8], may be NULL */);
+int bppp_rp_excess_sums_batch(bppp_rp *rp, size_t rows, const uint8_t *coms_files, size_t nsums, const uint32_t *sum_start, const uint32_t *entries, size_t nnz,
+                              const uint64_t *claim_amounts, const uint64_t *claim_types, const uint64_t *claim_offsets, size_t nkeys, const uint32_t *key_start,
+                              const uint8_t *keys, const uint8_t seed[32], int *accept, uint32_t *status, uint64_t *combined_xy);
+int bppp_rp_excess_sums_batch_device(bppp_rp *rp, size_t rows, const void *d_coms_files, size_t nsums, const void *d_sum_start, const void *d_entries, size_t nnz,
+                                     const void *d_claim_amounts, const void *d_claim_types, const void *d_claim_offsets, size_t nkeys, const void *d_key_start,
+                                     const void *d_keys, uint64_t index_offset, const uint8_t seed[32], int *accept, uint32_t *status, uint64_t *combined_xy);
+
 /* ---- one comb table for the handles of a basis family --------------------------------------------------------------------------
  * Every setup's basis [g | H | G] is a prefix of the point stream its points came from (see bppp_rp_verify_mixed), and the comb table
  * is laid out tab[window][point][multiple]: the table of the longest basis of a stream contains the table of every shorter one (same
