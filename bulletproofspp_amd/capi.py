@@ -236,6 +236,7 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_rp_set_tally_short_max.argtypes = [vp, sz]
     lib.bppp_test_rp_set_tally_piece.argtypes = [vp, sz]
     lib.bppp_test_rp_set_tally_chunk.argtypes = [vp, sz]
+    lib.bppp_test_rp_set_flat_chunk.argtypes = [vp, sz]
     lib.bppp_test_rp_excess_mul.argtypes = [vp, sz, vp, vp, vp]
     lib.bppp_test_rp_witness_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.bppp_test_points_from_seed_chunked.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, sz, vp, C.POINTER(C.c_uint64)]

@@ -81,6 +81,7 @@ struct LapTimer {
 };
 
 int msm_run(bppp_ctx *, const void *, const void *, size_t, size_t, int, int, uint64_t *);
+int batch_inverse_run(bppp_ctx *, const void *, size_t, int, void *);      // csrc/rounds.hip
 // bppp_{nl,ip}_verify_batch_device with the validation of untrusted inputs optional (csrc/nlbatch.hip)
 int nl_verify_batch_run(bppp_ctx *, size_t, size_t, size_t, size_t, size_t, size_t, size_t, const void *, const void *, const void *, const void *, const void *, const void *,
                         const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, uint64_t *, bool);
@@ -191,6 +192,9 @@ struct bppp_rp {
   // the tally entry points (csrc/rptally.hip): the longest sum one lane walks alone, the entries of one workgroup's piece of a longer sum, and
   // the entries (and sums) of one pass over the workspace; test hooks lower them so that small jobs straddle them (include/bppp_test.h)
   size_t tally_short_max = 16, tally_piece = 4096, tally_chunk = (size_t)1 << 22;
+  // the items (commitments, sums, keys) of one pass over the workspace in every balance call that is not planned by the tally's chunk: commit, open,
+  // sign, keys and the two key verifiers (rpp_flat_chunk); a test hook lowers it so that a small job takes several passes
+  size_t flat_chunk = (size_t)1 << 22;
   // per-proof public amounts of the *_pub entry points (bppp_rp_public_count per proof): grow-only device copy of one call's canonical
   // scalars, [batch][public_count][8] words
   uint32_t *d_pub = nullptr; size_t d_pub_bytes = 0;
@@ -294,6 +298,19 @@ void rp_decode_coms(bppp_rp *rp, size_t nb, const uint8_t *d_coms, uint32_t *pts
 static constexpr unsigned RPP_REDUCE_BLOCKS = 1024;
 int rpp_claim_scalars(bppp_rp *rp, uint64_t n, const uint32_t *amounts, const uint32_t *types, const uint32_t *blinds, uint32_t *in_sc, uint32_t *flag, uint32_t *any);
 int rpp_negated_column_sums(bppp_rp *rp, uint64_t n, const uint32_t *prods, uint32_t *part, uint32_t *out);
+// ---- what the passes of the balance calls share (csrc/rpcommit.hip, rptally.hip, rpexcess.hip, rpexkeys.hip)
+// the items of one pass over the workspace; a caller whose items are heavier takes a fraction of it
+inline size_t rpp_flat_chunk(const bppp_rp *rp) { return rp->flat_chunk; }
+// the end of a builder: the statuses of its n items (on the host) go out as they are, or, without a status array, the first refusal is the call's
+// error  "<who>: <noun> <position>: <text (status)>"
+int rpp_report_refusals(bppp_ctx *ctx, const char *who, const char *noun, const uint32_t *h_status, size_t n, uint32_t *out_status, const char *(*text)(uint32_t));
+// the combined points of a batch check, one per MSM.  msm: one more MSM of n terms (msm_run: returns with the stream drained, also when it fails);
+// finish: their sum into combined_xy (may be NULL), *accept = the sum is the identity and the caller saw nothing that rejects
+struct BatchParts {
+  std::vector<uint64_t> xy;
+  int msm(bppp_ctx *ctx, const void *sc, const void *pt, size_t n);
+  int finish(bppp_ctx *ctx, bool reject, uint64_t *combined_xy, int *accept);
+};
 }  // namespace bppp
 namespace bppp {
 // ---- the stage the tally entry points (csrc/rptally.hip, which defines it) and the excess signatures (csrc/rpexcess.hip) share: the job's
@@ -318,9 +335,15 @@ struct Work {
   uint8_t *seed, *extra;
 };
 // claims: the three claim arrays of a tally are judged too (all given or all NULL)
+// the arguments of a call as it names them; the type array of a binary handle is dropped
+void fill(Job &J, bppp_rp *rp, const char *who, size_t rows, const void *coms, size_t nsums, const void *start, const void *entries, size_t nnz, const void *amt,
+          const void *ty, const void *bl);
 int tally_checks(Job &J, bool null_args, bool claims);
 std::vector<size_t> chunk_bounds(const Job &J);
 Levels plan_levels(const Job &J, size_t t0, size_t t1);
+// the passes of a job over the workspace (cb: their bounds), the levels of each and the largest of every size that carve takes
+struct Plan { std::vector<size_t> cb; std::vector<Levels> plans; size_t ns_max = 0, ni = 0, np[2] = {0, 0}; };
+Plan make_plan(const Job &J);
 int carve(const Job &J, size_t ns, bool each, size_t ni, const size_t np[2], bool batch, size_t ne, Work &W, size_t extra = 0);
 int decode_pool(const Job &J, const Work &W);
 // W.sums [ns][XYZZ_WORDS] and W.malformed [ns] of the sums [t0, t0 + ns), planned as L; zeroes W.any[0..1]

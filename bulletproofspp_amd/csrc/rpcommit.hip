@@ -23,6 +23,7 @@
 #include "ec.hip.h"
 #include "comb.hpp"
 #include "rp_internal.hpp"
+#include "rphostcall.hpp"
 #include "rpprove_host.hpp"
 #include "rpwords.hip.h"
 #include "sha256.hip.h"
@@ -236,15 +237,32 @@ int rpp_negated_column_sums(bppp_rp *rp, uint64_t n, const uint32_t *prods, uint
   return BPPP_OK;
 }
 
+int rpp_report_refusals(bppp_ctx *ctx, const char *who, const char *noun, const uint32_t *h_status, size_t n, uint32_t *out_status, const char *(*text)(uint32_t)) {
+  if (out_status) { memcpy(out_status, h_status, n * 4); return BPPP_OK; }
+  for (size_t i = 0; i < n; i++)
+    if (h_status[i]) return fail(ctx, BPPP_ERR_ARG, std::string(who) + ": " + noun + " " + std::to_string(i) + ": " + text(h_status[i]));
+  return BPPP_OK;
+}
+int BatchParts::msm(bppp_ctx *ctx, const void *sc, const void *pt, size_t n) {
+  xy.resize(xy.size() + 8);
+  const int rc = msm_run(ctx, sc, pt, n, 1, 0, 0, &xy[xy.size() - 8]);
+  if (rc) hipStreamSynchronize(ctx->stream);
+  return rc;
+}
+int BatchParts::finish(bppp_ctx *ctx, bool reject, uint64_t *combined_xy, int *accept) {
+  uint64_t sum[8];
+  const int rc = bppp_sum_points(ctx, xy.data(), xy.size() / 8, sum);
+  if (rc) return rc;
+  if (combined_xy) memcpy(combined_xy, sum, 64);
+  *accept = (rp_point_is_inf(sum) && !reject) ? 1 : 0;
+  return BPPP_OK;
+}
+
 }  // namespace bppp
 
 using namespace bppp;
 
 namespace {
-
-// commitments per pass over the workspace: a larger batch goes through in chunks of whole rows (~300 bytes of workspace a commitment)
-constexpr size_t CHUNK_COMS = (size_t)1 << 22;
-constexpr unsigned REDUCE_BLOCKS = 1024;       // partials of k_rp_open_reduce's first launch at most: its second is one workgroup over them
 
 const char *commit_status_text(uint32_t s) {
   return s == BPPP_RP_COMMIT_INFINITY ? "the commitment is the point at infinity (amount, type and blinding are all zero mod n)" : bppp_rps::wit_status_text(s);
@@ -263,18 +281,19 @@ int carve(bppp_rp *rp, size_t R, bool open, bool weights, Work &W) {
     W.any = cv.take<uint32_t>(2);
     W.dec = cv.take<uint32_t>(open ? (n + 3) * 16 : 0); W.bad = cv.take<uint32_t>(open ? R : 0); W.status = cv.take<uint32_t>(open ? n : 0);
     W.rho = cv.take<uint32_t>(weights ? (n + 3) * 8 : 0); W.prods = cv.take<uint32_t>(weights ? n * 24 : 0);
-    W.part = cv.take<uint32_t>(weights ? (size_t)REDUCE_BLOCKS * 24 : 0); W.seed = cv.take<uint8_t>(32);
+    W.part = cv.take<uint32_t>(weights ? (size_t)RPP_REDUCE_BLOCKS * 24 : 0); W.seed = cv.take<uint8_t>(32);
     if (!pass) { int rc = rpp_ensure_pwork(rp, cv.off); if (rc) return rc; }
   }
   return BPPP_OK;
 }
-size_t chunk_rows(const bppp_rp *rp, size_t batch) { return std::max<size_t>(1, std::min(batch, CHUNK_COMS / rp->D.nr)); }
+// rows per pass over the workspace: a larger batch goes through in chunks of whole rows (~300 bytes of workspace a commitment)
+size_t chunk_rows(const bppp_rp *rp, size_t batch) { return std::max<size_t>(1, std::min(batch, rpp_flat_chunk(rp) / rp->D.nr)); }
 
 // the checks every entry point makes on a non-empty batch
 int entry_checks(bppp_rp *rp, size_t batch, const char *who, bool bad_args) {
   bppp_ctx *ctx = rp->ctx;
   if (bad_args) return fail(ctx, BPPP_ERR_ARG, std::string(who) + ": null input");
-  if (!rp->D.nr || batch > (((size_t)1 << 31) - 1) / rp->D.nr) return fail(ctx, BPPP_ERR_ARG, std::string(who) + ": batch * nranges must be below 2^31");
+  if (!rp->D.nr || batch > RPP_LIM31 / rp->D.nr) return fail(ctx, BPPP_ERR_ARG, std::string(who) + ": batch * nranges must be below 2^31");
   hipSetDevice(ctx->device);
   return BPPP_OK;
 }
@@ -310,10 +329,7 @@ int commit_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *
     BPPP_HIP(ctx, hipMemcpyAsync(status.data() + o, W.row_status, rows * 4, hipMemcpyDeviceToHost, ctx->stream));
     BPPP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
-  if (commit_status) { memcpy(commit_status, status.data(), batch * 4); return BPPP_OK; }
-  for (size_t b = 0; b < batch; b++)
-    if (status[b]) return fail(ctx, BPPP_ERR_ARG, "rp_commit_batch: proof " + std::to_string(b) + ": " + commit_status_text(status[b]));
-  return BPPP_OK;
+  return rpp_report_refusals(ctx, "rp_commit_batch", "proof", status.data(), batch, commit_status, commit_status_text);
 }
 
 // decode + claim + commit of one chunk, in W.dec / W.rec / W.flag; W.any = (some x had no point, some claim was not canonical)
@@ -377,7 +393,7 @@ int open_batch_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const vo
   Work W;
   if ((rc = carve(rp, R, true, true, W))) return rc;
   BPPP_HIP(ctx, hipMemcpyAsync(W.seed, seed, 32, hipMemcpyHostToDevice, st));
-  std::vector<uint64_t> parts;                  // one combined point per chunk
+  BatchParts parts;                             // one combined point per chunk
   uint32_t any[2] = {0, 0};
   for (size_t o = 0; o < batch; o += R) {
     const size_t rows = std::min(R, batch - o);
@@ -385,47 +401,24 @@ int open_batch_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const vo
     if ((rc = open_chunk(rp, W, rows, o, d_coms, d_amounts, d_types, d_blinds, false))) return rc;
     k_rp_open_weights<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st>>>(n, (uint32_t)nr, (uint32_t)cb, binary, (index_offset + o) * nr, W.seed,
                                                                            (const uint8_t *)d_coms + o * cb, W.in_sc, W.rho, W.prods);
-    const unsigned G = (unsigned)std::min<uint64_t>((n + 255) / 256, REDUCE_BLOCKS);
-    k_rp_open_reduce<<<dim3(G), dim3(256), 0, st>>>(n, W.prods, W.part, 0u);
-    k_rp_open_reduce<<<dim3(1), dim3(256), 0, st>>>(G, W.part, W.rho + n * 8, 1u);       // - sum rho v, - sum rho ty, - sum rho bl: the scalars of g, H0, H1
     BPPP_HIP(ctx, hipGetLastError());
+    if ((rc = rpp_negated_column_sums(rp, n, W.prods, W.part, W.rho + n * 8))) return rc;   // - sum rho v, - sum rho ty, - sum rho bl: the scalars of g, H0, H1
     BPPP_HIP(ctx, hipMemcpyAsync(W.dec + n * 16, rp->d_basis, 3 * 64, hipMemcpyDeviceToDevice, st));   // [g | H0 | H1 ...]: the registered basis starts with them
     uint32_t chunk_any[2];
     BPPP_HIP(ctx, hipMemcpyAsync(chunk_any, W.any, 8, hipMemcpyDeviceToHost, st));
-    parts.resize(parts.size() + 8);
-    if ((rc = msm_run(ctx, W.rho, W.dec, n + 3, 1, 0, 0, &parts[parts.size() - 8]))) { hipStreamSynchronize(st); return rc; }   // returns with the stream drained
+    if ((rc = parts.msm(ctx, W.rho, W.dec, n + 3))) return rc;
     any[0] |= chunk_any[0]; any[1] |= chunk_any[1];
   }
-  uint64_t xy[8];
-  if ((rc = bppp_sum_points(ctx, parts.data(), parts.size() / 8, xy))) return rc;
-  if (combined_xy) memcpy(combined_xy, xy, 64);
-  *accept = (rp_point_is_inf(xy) && !any[0] && !any[1]) ? 1 : 0;
+  if ((rc = parts.finish(ctx, any[0] || any[1], combined_xy, accept))) return rc;
   if (!open_status) return BPPP_OK;
   if (*accept) { memset(open_status, 0, batch * nr * 4); return BPPP_OK; }
   return open_each_pass(rp, batch, d_coms, d_amounts, d_types, d_blinds, open_status);      // one exact pass, whatever the number of bad openings
 }
 
 // ---- host variants: upload, the _device variant, download
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() { if (p) hipFree(p); }
-  int up(bppp_ctx *ctx, const void *src, size_t bytes) {
-    BPPP_HIP(ctx, hipMalloc(&p, bytes ? bytes : 16));
-    if (src) BPPP_HIP(ctx, hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
-    return BPPP_OK;
-  }
-};
-// the three claimed arrays of a host call in HBM; types stays NULL where the caller passed none
-struct Claims {
-  DevBuf amt, ty, bl;
-  int up(bppp_rp *rp, size_t batch, const uint64_t *amounts, const uint64_t *types, const uint64_t *blinds) {
-    const size_t bytes = batch * rp->D.nr * 32;
-    int rc = amt.up(rp->ctx, amounts, bytes);
-    if (!rc) rc = bl.up(rp->ctx, blinds, bytes);
-    if (!rc && types) rc = ty.up(rp->ctx, types, bytes);
-    return rc;
-  }
-};
+// the claimed arrays of a host call are batch * nranges scalars each; types stays NULL where the caller passed none
+size_t claim_bytes(const bppp_rp *rp, size_t batch) { return batch * rp->D.nr * 32; }
+size_t files_bytes(const bppp_rp *rp, size_t batch) { return batch * (size_t)rp->D.coms_bytes; }
 
 }  // namespace
 
@@ -443,16 +436,11 @@ int bppp_rp_commit_batch(bppp_rp *rp, size_t batch, const uint64_t *amounts, con
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
   if (!batch) return BPPP_OK;
   int rc = entry_checks(rp, batch, "rp_commit_batch", !amounts || (!types && rp->st.kind != 1) || !blinds || !coms_files); if (rc) return rc;
-  Claims in;
-  DevBuf files;
-  const size_t bytes = batch * (size_t)rp->D.coms_bytes;
-  if ((rc = in.up(rp, batch, amounts, types, blinds)) || (rc = files.up(ctx, nullptr, bytes))) return rc;
-  rc = commit_device(rp, batch, in.amt.p, in.ty.p, in.bl.p, commit_status, files.p);
-  // a refusal without commit_status is the call's error, but the files are complete (refused rows zeroed): they go down either way
-  if (rc && rc != BPPP_ERR_ARG) return rc;
-  const std::string err = rc ? ctx->err : std::string();
-  BPPP_HIP(ctx, hipMemcpy(coms_files, files.p, bytes, hipMemcpyDeviceToHost));
-  return rc ? fail(ctx, rc, err) : BPPP_OK;
+  DevBuf amt, ty, bl, files;
+  const size_t cl = claim_bytes(rp, batch);
+  if ((rc = amt.up(ctx, amounts, cl)) || (rc = ty.up(ctx, types, cl)) || (rc = bl.up(ctx, blinds, cl)) || (rc = files.out(ctx, coms_files, files_bytes(rp, batch)))) return rc;
+  rc = commit_device(rp, batch, amt.p, ty.p, bl.p, commit_status, files.p);
+  return rpp_download_refused(ctx, rc, nullptr, coms_files, files.p, files_bytes(rp, batch));     // entry_checks has refused everything but a commitment
 }
 
 int bppp_rp_open_each_device(bppp_rp *rp, size_t batch, const void *d_coms_files, const void *d_amounts, const void *d_types, const void *d_blinds,
@@ -467,10 +455,10 @@ int bppp_rp_open_each(bppp_rp *rp, size_t batch, const uint8_t *coms_files, cons
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
   if (!batch) return BPPP_OK;
   int rc = entry_checks(rp, batch, "rp_open_each", !coms_files || !amounts || (!types && rp->st.kind != 1) || !blinds || !open_status); if (rc) return rc;
-  Claims in;
-  DevBuf files;
-  if ((rc = in.up(rp, batch, amounts, types, blinds)) || (rc = files.up(ctx, coms_files, batch * (size_t)rp->D.coms_bytes))) return rc;
-  return open_each_device(rp, batch, files.p, in.amt.p, in.ty.p, in.bl.p, open_status);
+  DevBuf amt, ty, bl, files;
+  const size_t cl = claim_bytes(rp, batch);
+  if ((rc = amt.up(ctx, amounts, cl)) || (rc = ty.up(ctx, types, cl)) || (rc = bl.up(ctx, blinds, cl)) || (rc = files.up(ctx, coms_files, files_bytes(rp, batch)))) return rc;
+  return open_each_device(rp, batch, files.p, amt.p, ty.p, bl.p, open_status);
 }
 
 int bppp_rp_open_batch_device(bppp_rp *rp, size_t batch, uint64_t index_offset, const void *d_coms_files, const void *d_amounts, const void *d_types,
@@ -487,10 +475,10 @@ int bppp_rp_open_batch(bppp_rp *rp, size_t batch, const uint8_t *coms_files, con
   if (combined_xy) memset(combined_xy, 0, 64);
   if (!batch) { *accept = 1; return BPPP_OK; }
   int rc = entry_checks(rp, batch, "rp_open_batch", !coms_files || !amounts || (!types && rp->st.kind != 1) || !blinds || !seed); if (rc) return rc;
-  Claims in;
-  DevBuf files;
-  if ((rc = in.up(rp, batch, amounts, types, blinds)) || (rc = files.up(ctx, coms_files, batch * (size_t)rp->D.coms_bytes))) return rc;
-  return open_batch_device(rp, batch, 0, files.p, in.amt.p, in.ty.p, in.bl.p, seed, accept, open_status, combined_xy);
+  DevBuf amt, ty, bl, files;
+  const size_t cl = claim_bytes(rp, batch);
+  if ((rc = amt.up(ctx, amounts, cl)) || (rc = ty.up(ctx, types, cl)) || (rc = bl.up(ctx, blinds, cl)) || (rc = files.up(ctx, coms_files, files_bytes(rp, batch)))) return rc;
+  return open_batch_device(rp, batch, 0, files.p, amt.p, ty.p, bl.p, seed, accept, open_status, combined_xy);
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@
 #include <vector>
 #include "ec.hip.h"
 #include "rp_internal.hpp"
+#include "rphostcall.hpp"
 #include "rpprove_host.hpp"
 #include "rpwords.hip.h"
 #include "rplift.hip.h"
@@ -29,8 +30,6 @@
 #include "sha256.hip.h"
 
 namespace bppp {
-
-int batch_inverse_run(bppp_ctx *, const void *, size_t, int, void *);      // csrc/rounds.hip
 
 // ---- signer.  in_sc [2n][3][8]: row t the scalars of R_t = k_t B, row n + t those of X_t = e_t B, on base `slot` (typed 2: H1, binary 1: h0); a
 // refused sum gets zero scalars, so its two points are the infinity encoding
@@ -198,11 +197,18 @@ int mulcheck_launch(bppp_ctx *ctx, size_t n, const uint32_t *c, const uint32_t *
   BPPP_HIP(ctx, hipGetLastError());
   return BPPP_OK;
 }
-int weights_launch(bppp_ctx *ctx, size_t n, uint32_t slot, uint64_t j0, const uint8_t *seed, const uint8_t *sigs, const uint32_t *X, const uint8_t *msgs, const uint32_t *pre,
-                   const uint32_t *c, const uint32_t *in_sc, const uint32_t *R, uint32_t *prods, uint32_t *sc, uint32_t *pt, uint32_t *any) {
-  k_rp_excess_weights<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream>>>((uint32_t)n, slot, j0, seed, sigs, X, msgs, pre, c, in_sc, R, prods, sc, pt, any);
+int batch_chunk(bppp_rp *rp, size_t n, uint64_t j0, const uint8_t *seed, const uint8_t *sigs, const uint32_t *X, const uint8_t *msgs, const uint32_t *pre, const uint32_t *c,
+                const uint32_t *sp, const uint32_t *R, uint32_t *prods, uint32_t *red, uint32_t *sc3, uint32_t *msm_sc, uint32_t *msm_pt, uint32_t *any, BatchParts &parts) {
+  bppp_ctx *ctx = rp->ctx;
+  hipStream_t st = ctx->stream;
+  const uint32_t slot = blind_slot(rp);
+  int rc;
+  k_rp_excess_weights<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st>>>((uint32_t)n, slot, j0, seed, sigs, X, msgs, pre, c, sp, R, prods, msm_sc, msm_pt, any);
   BPPP_HIP(ctx, hipGetLastError());
-  return BPPP_OK;
+  if ((rc = rpp_negated_column_sums(rp, n, prods, red, sc3))) return rc;                  // sum rho s: the scalar of B
+  BPPP_HIP(ctx, hipMemcpyAsync(msm_sc + 2 * n * 8, sc3, 32, hipMemcpyDeviceToDevice, st));
+  BPPP_HIP(ctx, hipMemcpyAsync(msm_pt + 2 * n * 16, rp->d_basis + 16 * slot, 64, hipMemcpyDeviceToDevice, st));   // [g | H0 | H1 ...]: the registered basis starts with them
+  return parts.msm(ctx, msm_sc, msm_pt, 2 * n + 1);
 }
 
 }  // namespace excess
@@ -213,8 +219,6 @@ using namespace bppp::tally;
 using namespace bppp::excess;
 
 namespace {
-
-constexpr size_t SIGN_CHUNK = (size_t)1 << 22;         // sums per pass of the signer over the workspace
 
 const char *sign_status_text(uint32_t s) {
   return s == BPPP_RP_EXCESS_NOT_CANONICAL ? "the blinding sum is not canonical (>= n)"
@@ -228,11 +232,11 @@ int sign_device(bppp_rp *rp, size_t nsums, const void *d_blinds, const void *d_m
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
   if (!nsums) return BPPP_OK;
   if (!d_blinds || !d_msgs || !aux || !d_sigs) return fail(ctx, BPPP_ERR_ARG, "rp_excess_sign: null input");
-  if (nsums > (((size_t)1 << 31) - 1)) return fail(ctx, BPPP_ERR_ARG, "rp_excess_sign: nsums must be below 2^31");
+  if (nsums > RPP_LIM31) return fail(ctx, BPPP_ERR_ARG, "rp_excess_sign: nsums must be below 2^31");
   hipSetDevice(ctx->device);
   int rc;
   if (!rp->comb && (rc = rpp_build_fixed_table(rp))) return rc;
-  const size_t C = std::min(nsums, SIGN_CHUNK);
+  const size_t C = std::min(nsums, rpp_flat_chunk(rp));         // sums per pass over the workspace
   uint32_t *in_sc = nullptr, *pts = nullptr, *nonce = nullptr, *status = nullptr;
   uint8_t *d_aux = nullptr;
   for (int pass = 0; pass < 2; pass++) {
@@ -261,10 +265,7 @@ int sign_device(bppp_rp *rp, size_t nsums, const void *d_blinds, const void *d_m
     if (excess_xy) BPPP_HIP(ctx, hipMemcpyAsync(excess_xy + o * 8, pts + n * 16, n * 64, hipMemcpyDeviceToHost, st));
     BPPP_HIP(ctx, hipStreamSynchronize(st));
   }
-  if (sign_status) { memcpy(sign_status, h_status.data(), nsums * 4); return BPPP_OK; }
-  for (size_t t = 0; t < nsums; t++)
-    if (h_status[t]) return fail(ctx, BPPP_ERR_ARG, "rp_excess_sign: sum " + std::to_string(t) + ": " + sign_status_text(h_status[t]));
-  return BPPP_OK;
+  return rpp_report_refusals(ctx, "rp_excess_sign", "sum", h_status.data(), nsums, sign_status, sign_status_text);
 }
 
 // the verifier's own arrays of one pass, carved behind the tally's (Work::extra)
@@ -282,9 +283,7 @@ struct ExJob { Job J; const uint8_t *msgs, *sigs; };
 int verify_checks(ExJob &E, bppp_rp *rp, const char *who, size_t rows, const void *coms, size_t nsums, const void *start, const void *entries, size_t nnz, const void *amt,
                   const void *ty, const void *msgs, const void *sigs, bool null_args) {
   Job &J = E.J;
-  J.rp = rp; J.who = who; J.rows = rows; J.nsums = nsums; J.nnz = nnz;
-  J.coms = (const uint8_t *)coms; J.start = (const uint32_t *)start; J.entries = (const uint32_t *)entries;
-  J.amt = (const uint32_t *)amt; J.ty = rp->st.kind == 1 ? nullptr : (const uint32_t *)ty; J.bl = nullptr;
+  fill(J, rp, who, rows, coms, nsums, start, entries, nnz, amt, ty, nullptr);
   E.msgs = (const uint8_t *)msgs; E.sigs = (const uint8_t *)sigs;
   int rc = tally_checks(J, null_args || (rows && !coms) || !msgs || !sigs, false); if (rc) return rc;
   if (rp->st.kind != 1 && (J.amt == nullptr) != (J.ty == nullptr))
@@ -305,26 +304,13 @@ int verify_stage(const ExJob &E, const Work &W, const ExWork &X, size_t t0, size
   BPPP_HIP(ctx, hipMemsetAsync(X.zero, 0, ns * 32, st));
   const uint32_t *amt = J.zero_claims ? X.zero : J.amt + t0 * 8, *ty = J.zero_claims ? X.zero : J.ty ? J.ty + t0 * 8 : nullptr;
   if ((rc = rpp_claim_scalars(rp, ns, amt, ty, X.zero, W.in_sc, W.flag, W.any + 1)) || (rc = rpp_commit_inputs(rp, W.in_sc, ns, W.rec))) return rc;
-  const dim3 g64((unsigned)((ns + 63) / 64)), g256((unsigned)((ns + 255) / 256));
-  k_rp_excess_sigs<<<g64, dim3(64), 0, st>>>((uint32_t)ns, blind_slot(rp), E.sigs + t0 * EX_SIG, X.sp, X.R, X.bits);
-  k_rp_excess_key<<<g256, dim3(256), 0, st>>>((uint32_t)ns, W.sums, W.rec, W.malformed, W.zz);
+  if ((rc = sigs_launch(ctx, ns, blind_slot(rp), E.sigs + t0 * EX_SIG, X.sp, X.R, X.bits))) return rc;
+  k_rp_excess_key<<<dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st>>>((uint32_t)ns, W.sums, W.rec, W.malformed, W.zz);
   BPPP_HIP(ctx, hipGetLastError());
   if ((rc = batch_inverse_run(ctx, W.zz, ns, 0, W.zinv)) || (rc = affine_launch(ctx, ns, W.sums, W.zinv, W.xy))) return rc;
-  k_rp_excess_challenge<<<g64, dim3(64), 0, st>>>((uint32_t)ns, dc, E.sigs + t0 * EX_SIG, W.xy, E.msgs + t0 * EX_MSG, W.malformed, W.flag, X.bits, X.c, X.pre);
+  k_rp_excess_challenge<<<dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, st>>>((uint32_t)ns, dc, E.sigs + t0 * EX_SIG, W.xy, E.msgs + t0 * EX_MSG, W.malformed, W.flag, X.bits, X.c, X.pre);
   BPPP_HIP(ctx, hipGetLastError());
   return BPPP_OK;
-}
-
-struct Plan { std::vector<size_t> cb; std::vector<Levels> plans; size_t ns_max = 0, ni = 0, np[2] = {0, 0}; };
-Plan make_plan(const Job &J) {
-  Plan P;
-  P.cb = chunk_bounds(J);
-  for (size_t c = 0; c + 1 < P.cb.size(); c++) {
-    P.plans.push_back(plan_levels(J, P.cb[c], P.cb[c + 1]));
-    P.ns_max = std::max(P.ns_max, P.cb[c + 1] - P.cb[c]); P.ni = std::max(P.ni, P.plans[c].nitems);
-    for (int k = 0; k < 2; k++) P.np[k] = std::max(P.np[k], P.plans[c].npart[k]);
-  }
-  return P;
 }
 
 // every sum decided on its own: status [nsums] and, when not NULL, excess_xy [nsums][8], both on the host.  The job has passed verify_checks.
@@ -347,10 +333,10 @@ int verify_each_pass(const ExJob &E, uint32_t *status, uint64_t *excess_xy) {
     const size_t t0 = P.cb[c], ns = P.cb[c + 1] - t0;
     if ((rc = verify_stage(E, W, X, t0, ns, P.plans[c], dc)) || (rc = rpp_commit_inputs(rp, X.sp, ns, X.P))) break;
     if (ev[0]) hipEventRecord(ev[0], st);
-    k_rp_excess_mulcheck<<<dim3((unsigned)((4 * ns + 63) / 64)), dim3(64), 0, st>>>((uint32_t)ns, X.c, W.xy, X.P, X.R, X.pre, W.status);
+    rc = mulcheck_launch(ctx, ns, X.c, W.xy, X.P, X.R, X.pre, W.status);
     if (ev[0]) hipEventRecord(ev[1], st);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(status + t0, W.status, ns * 4, hipMemcpyDeviceToHost, st);
+    if (rc) break;
+    hipError_t e = hipMemcpyAsync(status + t0, W.status, ns * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && excess_xy) e = hipMemcpyAsync(excess_xy + t0 * 8, W.xy, ns * 64, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { rc = fail(ctx, BPPP_ERR_HIP, std::string("rp_excess_verify_each: ") + hipGetErrorString(e)); break; }
@@ -393,63 +379,33 @@ int verify_batch_device(bppp_rp *rp, size_t rows, const void *d_coms, size_t nsu
   if ((rc = carve(J, P.ns_max, true, P.ni, P.np, true, 2 * P.ns_max, W, ex_carve(nullptr, P.ns_max, X))) || (rc = decode_pool(J, W))) return rc;
   ex_carve(W.extra, P.ns_max, X);
   const ExDomain dc = challenge_domain(rp);
-  const uint32_t slot = blind_slot(rp);
   BPPP_HIP(ctx, hipMemcpyAsync(W.seed, seed, 32, hipMemcpyHostToDevice, st));
   BPPP_HIP(ctx, hipMemsetAsync(X.any, 0, 16, st));
-  std::vector<uint64_t> parts;                  // one combined point per pass
+  BatchParts parts;                             // one combined point per pass
   for (size_t c = 0; c + 1 < P.cb.size(); c++) {
     const size_t t0 = P.cb[c], ns = P.cb[c + 1] - t0;
     if ((rc = verify_stage(E, W, X, t0, ns, P.plans[c], dc))) return rc;
-    k_rp_excess_weights<<<dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, st>>>((uint32_t)ns, slot, index_offset + t0, W.seed, E.sigs + t0 * EX_SIG, W.xy, E.msgs + t0 * EX_MSG, X.pre,
-                                                                              X.c, X.sp, X.R, W.prods, W.msm_sc, W.msm_pt, X.any);
-    BPPP_HIP(ctx, hipGetLastError());
-    if ((rc = rpp_negated_column_sums(rp, ns, W.prods, W.red, W.sc3))) return rc;        // sum rho s: the scalar of B
-    BPPP_HIP(ctx, hipMemcpyAsync(W.msm_sc + 2 * ns * 8, W.sc3, 32, hipMemcpyDeviceToDevice, st));
-    BPPP_HIP(ctx, hipMemcpyAsync(W.msm_pt + 2 * ns * 16, rp->d_basis + 16 * slot, 64, hipMemcpyDeviceToDevice, st));   // [g | H0 | H1 ...]: the registered basis starts with them
-    parts.resize(parts.size() + 8);
-    if ((rc = msm_run(ctx, W.msm_sc, W.msm_pt, 2 * ns + 1, 1, 0, 0, &parts[parts.size() - 8]))) { hipStreamSynchronize(st); return rc; }   // returns with the stream drained
+    if ((rc = batch_chunk(rp, ns, index_offset + t0, W.seed, E.sigs + t0 * EX_SIG, W.xy, E.msgs + t0 * EX_MSG, X.pre, X.c, X.sp, X.R, W.prods, W.red, W.sc3, W.msm_sc, W.msm_pt, X.any,
+                          parts))) return rc;
   }
   uint32_t any = 0;
   BPPP_HIP(ctx, hipMemcpy(&any, X.any, 4, hipMemcpyDeviceToHost));
-  uint64_t xy[8];
-  if ((rc = bppp_sum_points(ctx, parts.data(), parts.size() / 8, xy))) return rc;
-  if (combined_xy) memcpy(combined_xy, xy, 64);
-  *accept = (rp_point_is_inf(xy) && !any) ? 1 : 0;
+  if ((rc = parts.finish(ctx, any != 0, combined_xy, accept))) return rc;
   if (!status) return BPPP_OK;
   if (*accept) { memset(status, 0, nsums * 4); return BPPP_OK; }
   return verify_each_pass(E, status, nullptr);  // one exact pass, whatever the number of bad sums
 }
 
 // ---- host variants: upload, the _device variant, download
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() { if (p) hipFree(p); }
-  int up(bppp_ctx *ctx, const void *src, size_t bytes) {
-    if (!src) return BPPP_OK;                  // a NULL argument stays NULL: the _device variant judges it
-    BPPP_HIP(ctx, hipMalloc(&p, bytes ? bytes : 16));
-    if (bytes) BPPP_HIP(ctx, hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
-    return BPPP_OK;
-  }
-  int out(bppp_ctx *ctx, const void *want, size_t bytes) {
-    if (want) BPPP_HIP(ctx, hipMalloc(&p, bytes ? bytes : 16));
-    return BPPP_OK;
-  }
-};
-struct HostJob {
-  DevBuf coms, start, entries, a, ty, msgs, sigs;
+// the tally's arrays without a third claim, and the messages and signatures of the sums
+struct HostJob : HostCsr {
+  DevBuf msgs, sigs;
   int up(bppp_rp *rp, size_t rows, const void *h_coms, size_t nsums, const uint32_t *sum_start, const uint32_t *ent, size_t nnz, const uint64_t *ca, const uint64_t *cty,
          const uint8_t *m, const uint8_t *s) {
-    bppp_ctx *ctx = rp->ctx;
-    const size_t lim = ((size_t)1 << 31) - 1;
-    if (!rp->D.nr || rows > lim / rp->D.nr || nsums > lim || nnz > lim) return BPPP_OK;      // the _device variant refuses these sizes before it reads anything
-    hipSetDevice(ctx->device);
-    int rc = coms.up(ctx, h_coms, rows * rp->D.coms_bytes);
-    if (!rc) rc = start.up(ctx, sum_start, (nsums + 1) * 4);
-    if (!rc) rc = entries.up(ctx, ent, nnz * 4);
-    if (!rc) rc = a.up(ctx, ca, nsums * 32);
-    if (!rc) rc = ty.up(ctx, cty, nsums * 32);
-    if (!rc) rc = msgs.up(ctx, m, nsums * EX_MSG);
-    if (!rc) rc = sigs.up(ctx, s, nsums * EX_SIG);
+    if (!rpp_sizes_ok(rp, rows, nsums, nnz)) return BPPP_OK;
+    int rc = HostCsr::up(rp, rows, h_coms, rp->D.coms_bytes, nsums, sum_start, ent, nnz, ca, cty, nullptr, nsums * 32);
+    if (!rc) rc = msgs.up(rp->ctx, m, nsums * EX_MSG);
+    if (!rc) rc = sigs.up(rp->ctx, s, nsums * EX_SIG);
     return rc;
   }
 };
@@ -470,7 +426,7 @@ int bppp_rp_excess_sign(bppp_rp *rp, size_t nsums, const uint64_t *claim_blinds,
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
   if (!nsums) return BPPP_OK;
   DevBuf bl, m, s;
-  if (nsums <= (((size_t)1 << 31) - 1)) {
+  if (nsums <= RPP_LIM31) {
     hipSetDevice(ctx->device);
     int rc = bl.up(ctx, claim_blinds, nsums * 32);
     if (!rc) rc = m.up(ctx, msgs, nsums * EX_MSG);
@@ -478,11 +434,7 @@ int bppp_rp_excess_sign(bppp_rp *rp, size_t nsums, const uint64_t *claim_blinds,
     if (rc) return rc;
   }
   int rc = sign_device(rp, nsums, bl.p, m.p, aux, s.p, excess_xy, sign_status);
-  // a refusal without sign_status is the call's error, but the signatures are complete (refused rows zeroed): they go down either way
-  if (rc && !(rc == BPPP_ERR_ARG && s.p && ctx->err.compare(0, 20, "rp_excess_sign: sum ") == 0)) return rc;
-  const std::string err = rc ? ctx->err : std::string();
-  BPPP_HIP(ctx, hipMemcpy(sigs, s.p, nsums * EX_SIG, hipMemcpyDeviceToHost));
-  return rc ? fail(ctx, rc, err) : BPPP_OK;
+  return rpp_download_refused(ctx, rc, "rp_excess_sign: sum ", sigs, s.p, nsums * EX_SIG);
 }
 
 int bppp_rp_excess_verify_each_device(bppp_rp *rp, size_t rows, const void *d_coms_files, size_t nsums, const void *d_sum_start, const void *d_entries, size_t nnz,

@@ -68,11 +68,14 @@ inline ExDomain nonce_domain(const bppp_rp *rp) { return domain("bppp/excess/non
 inline uint32_t blind_slot(const bppp_rp *rp) { return rp->st.kind == 1 ? 1u : 2u; }     // B among [g | H0 | H1]: h0 of a binary handle, else H1
 
 // the kernels of csrc/rpexcess.hip that serve the stated keys as they are, queued on the context's stream with the grids its own calls give them:
-// k_rp_excess_sigs (s canonical, R lifted), k_rp_excess_mulcheck (the equation, one quad a signature) and k_rp_excess_weights (the batch's terms)
+// k_rp_excess_sigs (s canonical, R lifted), k_rp_excess_mulcheck (the equation, one quad a signature) and, inside batch_chunk, k_rp_excess_weights
 int sigs_launch(bppp_ctx *ctx, size_t n, uint32_t slot, const uint8_t *sigs, uint32_t *in_sc, uint32_t *R, uint32_t *bits);
 int mulcheck_launch(bppp_ctx *ctx, size_t n, const uint32_t *c, const uint32_t *X, const uint32_t *P, const uint32_t *R, const uint32_t *pre, uint32_t *status);
-int weights_launch(bppp_ctx *ctx, size_t n, uint32_t slot, uint64_t j0, const uint8_t *seed, const uint8_t *sigs, const uint32_t *X, const uint8_t *msgs, const uint32_t *pre,
-                   const uint32_t *c, const uint32_t *in_sc, const uint32_t *R, uint32_t *prods, uint32_t *sc, uint32_t *pt, uint32_t *any);
+// one pass of a signature batch over n signatures at job positions j0 ..: the weights and the two MSM terms of each (k_rp_excess_weights; X the keys, sp
+// the scalars of s B, as the stage before left them), sum rho s on B as term 2n, and the MSM into parts.  prods [n][24], red [RPP_REDUCE_BLOCKS * 24],
+// sc3 [24], msm_sc [2n + 1][8], msm_pt [2n + 1][16] are workspace; any[0] is raised by a signature whose verdict is already taken
+int batch_chunk(bppp_rp *rp, size_t n, uint64_t j0, const uint8_t *seed, const uint8_t *sigs, const uint32_t *X, const uint8_t *msgs, const uint32_t *pre, const uint32_t *c,
+                const uint32_t *sp, const uint32_t *R, uint32_t *prods, uint32_t *red, uint32_t *sc3, uint32_t *msm_sc, uint32_t *msm_pt, uint32_t *any, BatchParts &parts);
 
 }  // namespace excess
 }  // namespace bppp

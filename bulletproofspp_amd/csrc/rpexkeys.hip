@@ -25,6 +25,7 @@
 #include <vector>
 #include "ec.hip.h"
 #include "rp_internal.hpp"
+#include "rphostcall.hpp"
 #include "rpprove_host.hpp"
 #include "rpwords.hip.h"
 #include "rplift.hip.h"
@@ -149,8 +150,8 @@ using namespace bppp::excess;
 
 namespace {
 
-constexpr size_t KEYS_CHUNK = (size_t)1 << 20;         // keys per pass over the workspace
-constexpr size_t LIM31 = ((size_t)1 << 31) - 1;
+// keys per pass over the workspace: a quarter of the flat chunk
+size_t keys_chunk(const bppp_rp *rp, size_t n) { return std::min(n, std::max<size_t>(1, rpp_flat_chunk(rp) / 4)); }
 
 const char *key_status_text(uint32_t s) {
   return s == BPPP_RP_EXCESS_NOT_CANONICAL ? "the blinding sum is not canonical (>= n)"
@@ -164,11 +165,11 @@ int keys_device(bppp_rp *rp, size_t nsums, const void *d_blinds, void *d_keys, u
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
   if (!nsums) return BPPP_OK;
   if (!d_blinds || !d_keys) return fail(ctx, BPPP_ERR_ARG, "rp_excess_keys: null input");
-  if (nsums > LIM31) return fail(ctx, BPPP_ERR_ARG, "rp_excess_keys: nsums must be below 2^31");
+  if (nsums > RPP_LIM31) return fail(ctx, BPPP_ERR_ARG, "rp_excess_keys: nsums must be below 2^31");
   hipSetDevice(ctx->device);
   int rc;
   if (!rp->comb && (rc = rpp_build_fixed_table(rp))) return rc;
-  const size_t C = std::min(nsums, KEYS_CHUNK);
+  const size_t C = keys_chunk(rp, nsums);
   uint32_t *in_sc = nullptr, *pts = nullptr, *status = nullptr;
   for (int pass = 0; pass < 2; pass++) {
     Carver cv(pass ? rp->pwork : nullptr, rp->pwork_bytes);
@@ -189,10 +190,7 @@ int keys_device(bppp_rp *rp, size_t nsums, const void *d_blinds, void *d_keys, u
     BPPP_HIP(ctx, hipMemcpyAsync(h_status.data() + o, status, n * 4, hipMemcpyDeviceToHost, st));
     BPPP_HIP(ctx, hipStreamSynchronize(st));
   }
-  if (key_status) { memcpy(key_status, h_status.data(), nsums * 4); return BPPP_OK; }
-  for (size_t t = 0; t < nsums; t++)
-    if (h_status[t]) return fail(ctx, BPPP_ERR_ARG, "rp_excess_keys: sum " + std::to_string(t) + ": " + key_status_text(h_status[t]));
-  return BPPP_OK;
+  return rpp_report_refusals(ctx, "rp_excess_keys", "sum", h_status.data(), nsums, key_status, key_status_text);
 }
 
 // ---- signatures against stated keys: no pool, no sum stage, no inversion
@@ -201,7 +199,7 @@ struct KeyWork { uint32_t *sp, *P, *R, *X, *bits, *pre, *c, *status, *any, *prod
 
 int key_checks(KeyJob &K, bppp_rp *rp, const char *who, size_t nkeys, const void *keys, const void *msgs, const void *sigs, bool null_args) {
   bppp_ctx *ctx = rp->ctx;
-  if (nkeys > LIM31) return fail(ctx, BPPP_ERR_ARG, std::string(who) + ": nkeys must be below 2^31");
+  if (nkeys > RPP_LIM31) return fail(ctx, BPPP_ERR_ARG, std::string(who) + ": nkeys must be below 2^31");
   if (null_args || !keys || !msgs || !sigs) return fail(ctx, BPPP_ERR_ARG, std::string(who) + ": null input");
   K.rp = rp; K.nkeys = nkeys; K.keys = (const uint8_t *)keys; K.msgs = (const uint8_t *)msgs; K.sigs = (const uint8_t *)sigs;
   hipSetDevice(ctx->device);
@@ -235,7 +233,7 @@ int verify_keys_each_pass(const KeyJob &K, uint32_t *status) {
   hipStream_t st = ctx->stream;
   int rc;
   if (!rp->comb && (rc = rpp_build_fixed_table(rp))) return rc;
-  const size_t C = std::min(K.nkeys, KEYS_CHUNK);
+  const size_t C = keys_chunk(rp, K.nkeys);
   KeyWork W;
   if ((rc = key_carve(rp, C, false, W))) return rc;
   const ExDomain dc = challenge_domain(rp);
@@ -268,30 +266,22 @@ int verify_keys_batch_device(bppp_rp *rp, size_t nkeys, const void *d_keys, cons
   int rc = key_checks(K, rp, "rp_excess_verify_keys_batch", nkeys, d_keys, d_msgs, d_sigs, !seed); if (rc) return rc;
   if (combined_xy) memset(combined_xy, 0, 64);
   hipStream_t st = ctx->stream;
-  const size_t C = std::min(nkeys, KEYS_CHUNK);
+  const size_t C = keys_chunk(rp, nkeys);
   KeyWork W;
   if ((rc = key_carve(rp, C, true, W))) return rc;
   const ExDomain dc = challenge_domain(rp);
-  const uint32_t slot = blind_slot(rp);
   BPPP_HIP(ctx, hipMemcpyAsync(W.seed, seed, 32, hipMemcpyHostToDevice, st));
   BPPP_HIP(ctx, hipMemsetAsync(W.any, 0, 16, st));
-  std::vector<uint64_t> parts;                  // one combined point per pass
+  BatchParts parts;                             // one combined point per pass
   for (size_t o = 0; o < nkeys; o += C) {
     const size_t n = std::min(C, nkeys - o);
     if ((rc = key_stage(K, W, o, n, dc))) return rc;
-    if ((rc = weights_launch(ctx, n, slot, index_offset + o, W.seed, K.sigs + o * EX_SIG, W.X, K.msgs + o * EX_MSG, W.pre, W.c, W.sp, W.R, W.prods, W.msm_sc, W.msm_pt, W.any))) return rc;
-    if ((rc = rpp_negated_column_sums(rp, n, W.prods, W.red, W.sc3))) return rc;          // sum rho s: the scalar of B
-    BPPP_HIP(ctx, hipMemcpyAsync(W.msm_sc + 2 * n * 8, W.sc3, 32, hipMemcpyDeviceToDevice, st));
-    BPPP_HIP(ctx, hipMemcpyAsync(W.msm_pt + 2 * n * 16, rp->d_basis + 16 * slot, 64, hipMemcpyDeviceToDevice, st));   // [g | H0 | H1 ...]: the registered basis starts with them
-    parts.resize(parts.size() + 8);
-    if ((rc = msm_run(ctx, W.msm_sc, W.msm_pt, 2 * n + 1, 1, 0, 0, &parts[parts.size() - 8]))) { hipStreamSynchronize(st); return rc; }   // returns with the stream drained
+    if ((rc = batch_chunk(rp, n, index_offset + o, W.seed, K.sigs + o * EX_SIG, W.X, K.msgs + o * EX_MSG, W.pre, W.c, W.sp, W.R, W.prods, W.red, W.sc3, W.msm_sc, W.msm_pt, W.any,
+                          parts))) return rc;
   }
   uint32_t any = 0;
   BPPP_HIP(ctx, hipMemcpy(&any, W.any, 4, hipMemcpyDeviceToHost));
-  uint64_t xy[8];
-  if ((rc = bppp_sum_points(ctx, parts.data(), parts.size() / 8, xy))) return rc;
-  if (combined_xy) memcpy(combined_xy, xy, 64);
-  *accept = (rp_point_is_inf(xy) && !any) ? 1 : 0;
+  if ((rc = parts.finish(ctx, any != 0, combined_xy, accept))) return rc;
   if (!status) return BPPP_OK;
   if (*accept) { memset(status, 0, nkeys * 4); return BPPP_OK; }
   return verify_keys_each_pass(K, status);      // one exact pass, whatever the number of bad signatures
@@ -317,13 +307,11 @@ int sums_checks(SumsJob &S, bppp_rp *rp, const char *who, size_t rows, const voi
   bppp_ctx *ctx = rp->ctx;
   const std::string w = who;
   const size_t nr = rp->D.nr;
-  if (!nr || rows > LIM31 / nr || nkeys > LIM31 || rows * nr + nkeys > LIM31) return fail(ctx, BPPP_ERR_ARG, w + ": rows * nranges + nkeys must be below 2^31");
-  if (nnz > LIM31 || nnz + nkeys > LIM31) return fail(ctx, BPPP_ERR_ARG, w + ": nnz + nkeys must be below 2^31");
+  if (!nr || rows > RPP_LIM31 / nr || nkeys > RPP_LIM31 || rows * nr + nkeys > RPP_LIM31) return fail(ctx, BPPP_ERR_ARG, w + ": rows * nranges + nkeys must be below 2^31");
+  if (nnz > RPP_LIM31 || nnz + nkeys > RPP_LIM31) return fail(ctx, BPPP_ERR_ARG, w + ": nnz + nkeys must be below 2^31");
   Job &J = S.J;
-  J.rp = rp; J.who = who; J.rows = rows; J.nsums = nsums; J.nnz = nnz;
+  fill(J, rp, who, rows, coms, nsums, start, entries, nnz, amt, ty, off);
   J.bl_name = "claim_offsets";
-  J.coms = (const uint8_t *)coms; J.start = (const uint32_t *)start; J.entries = (const uint32_t *)entries;
-  J.amt = (const uint32_t *)amt; J.ty = rp->st.kind == 1 ? nullptr : (const uint32_t *)ty; J.bl = (const uint32_t *)off;
   S.nkeys = nkeys; S.nnz = nnz; S.keys = (const uint8_t *)keys; S.key_start = (const uint32_t *)key_start;
   int rc = tally_checks(J, null_args || (rows && !coms) || !key_start || (nkeys && !keys), true); if (rc) return rc;
   uint32_t *flag = (uint32_t *)rp->pwork, h = EXK_NONE;          // tally_checks made sure of 256 bytes
@@ -415,25 +403,11 @@ int sums_batch_device(bppp_rp *rp, size_t rows, const void *d_coms, size_t nsums
 }
 
 // ---- host variants: upload, the _device variant, download
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() { if (p) hipFree(p); }
-  int up(bppp_ctx *ctx, const void *src, size_t bytes) {
-    if (!src) return BPPP_OK;                  // a NULL argument stays NULL: the _device variant judges it
-    BPPP_HIP(ctx, hipMalloc(&p, bytes ? bytes : 16));
-    if (bytes) BPPP_HIP(ctx, hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
-    return BPPP_OK;
-  }
-  int out(bppp_ctx *ctx, const void *want, size_t bytes) {
-    if (want) BPPP_HIP(ctx, hipMalloc(&p, bytes ? bytes : 16));
-    return BPPP_OK;
-  }
-};
 struct HostKeys {
   DevBuf keys, msgs, sigs;
   int up(bppp_rp *rp, size_t nkeys, const uint8_t *k, const uint8_t *m, const uint8_t *s) {
     bppp_ctx *ctx = rp->ctx;
-    if (nkeys > LIM31) return BPPP_OK;         // the _device variant refuses this size before it reads anything
+    if (nkeys > RPP_LIM31) return BPPP_OK;     // the _device variant refuses this size before it reads anything
     hipSetDevice(ctx->device);
     int rc = keys.up(ctx, k, nkeys * EX_KEY);
     if (!rc) rc = msgs.up(ctx, m, nkeys * EX_MSG);
@@ -441,22 +415,15 @@ struct HostKeys {
     return rc;
   }
 };
-struct HostSums {
-  DevBuf coms, start, entries, a, ty, o, kstart, keys;
+// the tally's arrays (the third claim: the offsets) and the keys of the sums
+struct HostSums : HostCsr {
+  DevBuf kstart, keys;
   int up(bppp_rp *rp, size_t rows, const void *h_coms, size_t nsums, const uint32_t *sum_start, const uint32_t *ent, size_t nnz, const uint64_t *ca, const uint64_t *cty,
          const uint64_t *co, size_t nkeys, const uint32_t *key_start, const uint8_t *k) {
-    bppp_ctx *ctx = rp->ctx;
-    const size_t nr = rp->D.nr;
-    if (!nr || rows > LIM31 / nr || nsums > LIM31 || nnz > LIM31 || nkeys > LIM31 || rows * nr + nkeys > LIM31 || nnz + nkeys > LIM31) return BPPP_OK;      // refused below, unread
-    hipSetDevice(ctx->device);
-    int rc = coms.up(ctx, h_coms, rows * rp->D.coms_bytes);
-    if (!rc) rc = start.up(ctx, sum_start, (nsums + 1) * 4);
-    if (!rc) rc = entries.up(ctx, ent, nnz * 4);
-    if (!rc) rc = a.up(ctx, ca, nsums * 32);
-    if (!rc) rc = ty.up(ctx, cty, nsums * 32);
-    if (!rc) rc = o.up(ctx, co, nsums * 32);
-    if (!rc) rc = kstart.up(ctx, key_start, (nsums + 1) * 4);
-    if (!rc) rc = keys.up(ctx, k, nkeys * EX_KEY);
+    if (!rpp_sizes_ok(rp, rows, nsums, nnz, nkeys)) return BPPP_OK;
+    int rc = HostCsr::up(rp, rows, h_coms, rp->D.coms_bytes, nsums, sum_start, ent, nnz, ca, cty, co, nsums * 32);
+    if (!rc) rc = kstart.up(rp->ctx, key_start, (nsums + 1) * 4);
+    if (!rc) rc = keys.up(rp->ctx, k, nkeys * EX_KEY);
     return rc;
   }
 };
@@ -475,18 +442,14 @@ int bppp_rp_excess_keys(bppp_rp *rp, size_t nsums, const uint64_t *claim_blinds,
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
   if (!nsums) return BPPP_OK;
   DevBuf bl, k;
-  if (nsums <= LIM31) {
+  if (nsums <= RPP_LIM31) {
     hipSetDevice(ctx->device);
     int rc = bl.up(ctx, claim_blinds, nsums * 32);
     if (!rc) rc = k.out(ctx, keys, nsums * EX_KEY);
     if (rc) return rc;
   }
   int rc = keys_device(rp, nsums, bl.p, k.p, key_status);
-  // a refusal without key_status is the call's error, but the keys are complete (refused rows zeroed): they go down either way
-  if (rc && !(rc == BPPP_ERR_ARG && k.p && ctx->err.compare(0, 20, "rp_excess_keys: sum ") == 0)) return rc;
-  const std::string err = rc ? ctx->err : std::string();
-  BPPP_HIP(ctx, hipMemcpy(keys, k.p, nsums * EX_KEY, hipMemcpyDeviceToHost));
-  return rc ? fail(ctx, rc, err) : BPPP_OK;
+  return rpp_download_refused(ctx, rc, "rp_excess_keys: sum ", keys, k.p, nsums * EX_KEY);
 }
 
 int bppp_rp_excess_verify_keys_each_device(bppp_rp *rp, size_t nkeys, const void *d_keys, const void *d_msgs, const void *d_sigs, uint32_t *status) {
@@ -536,7 +499,7 @@ int bppp_rp_excess_sums_each(bppp_rp *rp, size_t rows, const uint8_t *coms_files
   HostSums H;
   int rc = H.up(rp, rows, coms_files, nsums, sum_start, entries, nnz, claim_amounts, claim_types, claim_offsets, nkeys, key_start, keys);
   if (rc) return rc;
-  return sums_each_device(rp, rows, H.coms.p, nsums, H.start.p, H.entries.p, nnz, H.a.p, H.ty.p, H.o.p, nkeys, H.kstart.p, H.keys.p, status, sums_xy);
+  return sums_each_device(rp, rows, H.coms.p, nsums, H.start.p, H.entries.p, nnz, H.a.p, H.ty.p, H.e.p, nkeys, H.kstart.p, H.keys.p, status, sums_xy);
 }
 
 int bppp_rp_excess_sums_batch_device(bppp_rp *rp, size_t rows, const void *d_coms_files, size_t nsums, const void *d_sum_start, const void *d_entries, size_t nnz,
@@ -557,7 +520,7 @@ int bppp_rp_excess_sums_batch(bppp_rp *rp, size_t rows, const uint8_t *coms_file
     int rc = H.up(rp, rows, coms_files, nsums, sum_start, entries, nnz, claim_amounts, claim_types, claim_offsets, nkeys, key_start, keys);
     if (rc) return rc;
   }
-  return sums_batch_device(rp, rows, H.coms.p, nsums, H.start.p, H.entries.p, nnz, H.a.p, H.ty.p, H.o.p, nkeys, H.kstart.p, H.keys.p, 0, seed, accept, status, combined_xy);
+  return sums_batch_device(rp, rows, H.coms.p, nsums, H.start.p, H.entries.p, nnz, H.a.p, H.ty.p, H.e.p, nkeys, H.kstart.p, H.keys.p, 0, seed, accept, status, combined_xy);
 }
 
 }  // extern "C"

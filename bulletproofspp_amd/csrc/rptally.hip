@@ -22,14 +22,13 @@
 #include <vector>
 #include "ec.hip.h"
 #include "rp_internal.hpp"
+#include "rphostcall.hpp"
 #include "rpprove_host.hpp"
 #include "rptally_plan.hpp"
 #include "rpwords.hip.h"
 #include "sha256.hip.h"
 
 namespace bppp {
-
-int batch_inverse_run(bppp_ctx *, const void *, size_t, int, void *);      // csrc/rounds.hip
 
 static constexpr uint32_t TALLY_LANES = 256;
 static constexpr uint32_t TALLY_FINAL = 0x80000000u;     // an item's destination: bit 31 = the sum itself, else a partial point
@@ -240,12 +239,19 @@ __global__ void __launch_bounds__(256) k_rp_tally_claims(uint32_t nsums, uint32_
 namespace bppp {
 namespace tally {
 
+void fill(Job &J, bppp_rp *rp, const char *who, size_t rows, const void *coms, size_t nsums, const void *start, const void *entries, size_t nnz, const void *amt,
+          const void *ty, const void *bl) {
+  J.rp = rp; J.who = who; J.rows = rows; J.nsums = nsums; J.nnz = nnz;
+  J.coms = (const uint8_t *)coms; J.start = (const uint32_t *)start; J.entries = (const uint32_t *)entries;
+  J.amt = (const uint32_t *)amt; J.ty = rp->st.kind == 1 ? nullptr : (const uint32_t *)ty; J.bl = (const uint32_t *)bl;
+}
+
 // the call-level checks of a non-empty job; then the CSR conditions by k_rp_tally_validate, its flag read back before anything gathers
 int tally_checks(Job &J, bool null_args, bool claims) {
   bppp_rp *rp = J.rp;
   bppp_ctx *ctx = rp->ctx;
   const std::string who = J.who;
-  const size_t nr = rp->D.nr, lim = ((size_t)1 << 31) - 1;
+  const size_t nr = rp->D.nr, lim = RPP_LIM31;
   if (!nr || J.rows > lim / nr) return fail(ctx, BPPP_ERR_ARG, who + ": rows * nranges must be below 2^31");
   if (J.nnz > lim || J.nsums > lim) return fail(ctx, BPPP_ERR_ARG, who + ": nnz and nsums must be below 2^31");
   if (null_args || !J.start || (J.nnz && !J.entries)) return fail(ctx, BPPP_ERR_ARG, who + ": null input");
@@ -284,6 +290,16 @@ static_assert(sizeof(bppp_tally::Item) == sizeof(uint4), "an item is the kernel'
 std::vector<size_t> chunk_bounds(const Job &J) { return bppp_tally::chunk_bounds(J.h_start.data(), J.nsums, J.rp->tally_chunk); }
 Levels plan_levels(const Job &J, size_t t0, size_t t1) {
   return bppp_tally::plan_levels(J.h_start.data(), t0, t1, (uint32_t)std::min<size_t>(J.rp->tally_short_max, 0xFFFFFFFFu), (uint32_t)std::min<size_t>(J.rp->tally_piece, 0x7FFFFFFFu));
+}
+Plan make_plan(const Job &J) {
+  Plan P;
+  P.cb = chunk_bounds(J);
+  for (size_t c = 0; c + 1 < P.cb.size(); c++) {
+    P.plans.push_back(plan_levels(J, P.cb[c], P.cb[c + 1]));
+    P.ns_max = std::max(P.ns_max, P.cb[c + 1] - P.cb[c]); P.ni = std::max(P.ni, P.plans[c].nitems);
+    for (int k = 0; k < 2; k++) P.np[k] = std::max(P.np[k], P.plans[c].npart[k]);
+  }
+  return P;
 }
 
 // ns: the sums of the largest chunk; each: the per-sum pass (ni items, np[2] partial points); batch: the weighted combination (ne entries a MSM);
@@ -377,20 +393,13 @@ int each_pass(const Job &J0, uint32_t *status, uint64_t *sums_xy, const Ext *ext
   hipStream_t st = ctx->stream;
   int rc;
   if (!rp->comb && (rc = rpp_build_fixed_table(rp))) return rc;
-  const std::vector<size_t> cb = chunk_bounds(J);
-  std::vector<Levels> plans;
-  size_t ns_max = 0, ni = 0, np[2] = {0, 0};
-  for (size_t c = 0; c + 1 < cb.size(); c++) {
-    plans.push_back(plan_levels(J, cb[c], cb[c + 1]));
-    ns_max = std::max(ns_max, cb[c + 1] - cb[c]); ni = std::max(ni, plans[c].nitems);
-    for (int k = 0; k < 2; k++) np[k] = std::max(np[k], plans[c].npart[k]);
-  }
+  const Plan P = make_plan(J);
   Work W;
-  if ((rc = carve(J, ns_max, true, ni, np, false, 0, W, ext ? ext->extra : 0)) || (rc = decode_pool(J, W))) return rc;
+  if ((rc = carve(J, P.ns_max, true, P.ni, P.np, false, 0, W, ext ? ext->extra : 0)) || (rc = decode_pool(J, W))) return rc;
   if (ext && (rc = ext->prepare(Jx, W))) return rc;
-  for (size_t c = 0; c + 1 < cb.size(); c++) {
-    const size_t t0 = cb[c], ns = cb[c + 1] - t0;
-    if ((rc = sum_launches(J, W, t0, ns, plans[c]))) return rc;
+  for (size_t c = 0; c + 1 < P.cb.size(); c++) {
+    const size_t t0 = P.cb[c], ns = P.cb[c + 1] - t0;
+    if ((rc = sum_launches(J, W, t0, ns, P.plans[c]))) return rc;
     if ((rc = claim_scalars(J, W, t0, ns)) || (rc = rpp_commit_inputs(rp, W.in_sc, ns, W.rec))) return rc;
     k_rp_tally_compare<<<dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st>>>((uint32_t)ns, W.sums, W.rec, W.flag, W.malformed, W.status, sums_xy ? W.zz : nullptr);
     BPPP_HIP(ctx, hipGetLastError());
@@ -427,7 +436,7 @@ int batch_run(const Job &J0, uint64_t index_offset, const uint8_t seed[32], int 
   if (ext && (rc = ext->prepare(Jx, W))) return rc;
   BPPP_HIP(ctx, hipMemcpyAsync(W.seed, seed, 32, hipMemcpyHostToDevice, st));
   BPPP_HIP(ctx, hipMemsetAsync(W.any, 0, 8, st));
-  std::vector<uint64_t> parts;                  // one combined point per MSM
+  BatchParts parts;                             // one combined point per MSM
   const bool binary = rp->st.kind == 1;
   for (size_t c = 0; c + 1 < cb.size(); c++) {
     const size_t t0 = cb[c], ns = cb[c + 1] - t0;
@@ -446,19 +455,15 @@ int batch_run(const Job &J0, uint64_t index_offset, const uint8_t seed[32], int 
       if (first) BPPP_HIP(ctx, hipMemcpyAsync(W.msm_sc + n * 8, W.sc3, 96, hipMemcpyDeviceToDevice, st));
       else BPPP_HIP(ctx, hipMemsetAsync(W.msm_sc + n * 8, 0, 96, st));
       BPPP_HIP(ctx, hipMemcpyAsync(W.msm_pt + n * 16, rp->d_basis, 3 * 64, hipMemcpyDeviceToDevice, st));   // [g | H0 | H1 ...]: the registered basis starts with them
-      parts.resize(parts.size() + 8);
-      if ((rc = msm_run(ctx, W.msm_sc, W.msm_pt, n + 3, 1, 0, 0, &parts[parts.size() - 8]))) { hipStreamSynchronize(st); return rc; }   // returns with the stream drained
+      if ((rc = parts.msm(ctx, W.msm_sc, W.msm_pt, n + 3))) return rc;
       e0 += n; first = false;
     } while (e0 < e1);
   }
   uint32_t any[2];
   BPPP_HIP(ctx, hipMemcpy(any, W.any, 8, hipMemcpyDeviceToHost));
-  uint64_t xy[8];
-  if ((rc = bppp_sum_points(ctx, parts.data(), parts.size() / 8, xy))) return rc;
-  if (combined_xy) memcpy(combined_xy, xy, 64);
   bool reject = false;
   if (ext && (rc = ext->rejects(W, reject))) return rc;
-  *accept = (rp_point_is_inf(xy) && !any[0] && !any[1] && !reject) ? 1 : 0;
+  if ((rc = parts.finish(ctx, any[0] || any[1] || reject, combined_xy, accept))) return rc;
   if (!status) return BPPP_OK;
   if (*accept) { memset(status, 0, nsums * 4); return BPPP_OK; }
   return each_pass(J0, status, nullptr, ext);   // one exact pass, whatever the number of bad sums
@@ -471,14 +476,6 @@ using namespace bppp;
 using namespace bppp::tally;
 
 namespace {
-
-int fill(Job &J, bppp_rp *rp, const char *who, size_t rows, const void *coms, size_t nsums, const void *start, const void *entries, size_t nnz, const void *amt,
-         const void *ty, const void *bl) {
-  J.rp = rp; J.who = who; J.rows = rows; J.nsums = nsums; J.nnz = nnz;
-  J.coms = (const uint8_t *)coms; J.start = (const uint32_t *)start; J.entries = (const uint32_t *)entries;
-  J.amt = (const uint32_t *)amt; J.ty = rp->st.kind == 1 ? nullptr : (const uint32_t *)ty; J.bl = (const uint32_t *)bl;
-  return BPPP_OK;
-}
 
 int tally_each_device(bppp_rp *rp, size_t rows, const void *d_coms, size_t nsums, const void *d_start, const void *d_entries, size_t nnz, const void *d_amt, const void *d_ty,
                       const void *d_bl, uint32_t *status, uint64_t *sums_xy) {
@@ -526,43 +523,6 @@ int tally_claims_device(bppp_rp *rp, size_t rows, const void *d_amt, const void 
   return BPPP_OK;
 }
 
-// ---- host variants: upload, the _device variant, download
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() { if (p) hipFree(p); }
-  int up(bppp_ctx *ctx, const void *src, size_t bytes) {
-    if (!src) return BPPP_OK;                  // a NULL argument stays NULL: the _device variant judges it
-    BPPP_HIP(ctx, hipMalloc(&p, bytes ? bytes : 16));
-    if (bytes) BPPP_HIP(ctx, hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
-    return BPPP_OK;
-  }
-  int out(bppp_ctx *ctx, const void *want, size_t bytes) {
-    if (want) BPPP_HIP(ctx, hipMalloc(&p, bytes ? bytes : 16));
-    return BPPP_OK;
-  }
-};
-// the pool, the CSR arrays and the three claim arrays of a host call in HBM
-struct HostJob {
-  DevBuf coms, start, entries, a, ty, e;
-  int up(bppp_rp *rp, size_t rows, const void *h_coms, size_t coms_row_bytes, size_t nsums, const uint32_t *sum_start, const uint32_t *ent, size_t nnz,
-         const uint64_t *ca, const uint64_t *cty, const uint64_t *ce, size_t claim_bytes) {
-    bppp_ctx *ctx = rp->ctx;
-    hipSetDevice(ctx->device);
-    int rc = coms.up(ctx, h_coms, rows * coms_row_bytes);
-    if (!rc) rc = start.up(ctx, sum_start, (nsums + 1) * 4);
-    if (!rc) rc = entries.up(ctx, ent, nnz * 4);
-    if (!rc) rc = a.up(ctx, ca, claim_bytes);
-    if (!rc) rc = ty.up(ctx, cty, claim_bytes);
-    if (!rc) rc = e.up(ctx, ce, claim_bytes);
-    return rc;
-  }
-};
-// the sizes a host variant multiplies before the _device variant has judged them
-bool sizes_ok(const bppp_rp *rp, size_t rows, size_t nsums, size_t nnz) {
-  const size_t lim = ((size_t)1 << 31) - 1;
-  return rp->D.nr && rows <= lim / rp->D.nr && nsums <= lim && nnz <= lim;
-}
-
 }  // namespace
 
 extern "C" {
@@ -577,8 +537,8 @@ int bppp_rp_tally_each(bppp_rp *rp, size_t rows, const uint8_t *coms_files, size
   if (!rp) return BPPP_ERR_ARG;
   if (ctx_closed(rp->ctx)) return BPPP_ERR_ARG;
   if (!nsums) return BPPP_OK;
-  HostJob H;
-  if (sizes_ok(rp, rows, nsums, nnz)) {
+  HostCsr H;
+  if (rpp_sizes_ok(rp, rows, nsums, nnz)) {
     int rc = H.up(rp, rows, coms_files, rp->D.coms_bytes, nsums, sum_start, entries, nnz, claim_amounts, claim_types, claim_blinds, nsums * 32);
     if (rc) return rc;
   }
@@ -598,8 +558,8 @@ int bppp_rp_tally_batch(bppp_rp *rp, size_t rows, const uint8_t *coms_files, siz
   if (!rp || !accept) return BPPP_ERR_ARG;
   if (ctx_closed(rp->ctx)) return BPPP_ERR_ARG;
   *accept = 0;
-  HostJob H;
-  if (nsums && sizes_ok(rp, rows, nsums, nnz)) {
+  HostCsr H;
+  if (nsums && rpp_sizes_ok(rp, rows, nsums, nnz)) {
     int rc = H.up(rp, rows, coms_files, rp->D.coms_bytes, nsums, sum_start, entries, nnz, claim_amounts, claim_types, claim_blinds, nsums * 32);
     if (rc) return rc;
   }
@@ -617,9 +577,9 @@ int bppp_rp_tally_claims(bppp_rp *rp, size_t rows, const uint64_t *amounts, cons
   bppp_ctx *ctx = rp->ctx;
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
   if (!nsums) return BPPP_OK;
-  HostJob H;
+  HostCsr H;
   DevBuf oa, oty, oe;
-  if (sizes_ok(rp, rows, nsums, nnz)) {
+  if (rpp_sizes_ok(rp, rows, nsums, nnz)) {
     int rc = H.up(rp, 0, nullptr, 0, nsums, sum_start, entries, nnz, amounts, types, blinds, rows * rp->D.nr * 32);
     if (!rc) rc = oa.out(ctx, claim_amounts, nsums * 32);
     if (!rc) rc = oty.out(ctx, claim_types, nsums * 32);

@@ -429,6 +429,11 @@ extern "C" int bppp_test_rp_set_tally_chunk(bppp_rp *rp, size_t entries) {
   rp->tally_chunk = entries ? entries : bppp_rp().tally_chunk;
   return BPPP_OK;
 }
+extern "C" int bppp_test_rp_set_flat_chunk(bppp_rp *rp, size_t items) {
+  if (!rp) return BPPP_ERR_ARG;
+  rp->flat_chunk = items ? items : bppp_rp().flat_chunk;
+  return BPPP_OK;
+}
 
 // one quad per instance; all four lanes hold the product, lane 0 of the quad inverts and stores
 namespace bppp {

@@ -84,6 +84,10 @@ int bppp_test_rp_set_each_chunk(bppp_rp *rp, size_t proofs);
 int bppp_test_rp_set_tally_short_max(bppp_rp *rp, size_t entries);
 int bppp_test_rp_set_tally_piece(bppp_rp *rp, size_t entries);
 int bppp_test_rp_set_tally_chunk(bppp_rp *rp, size_t entries);
+/* The items of one pass over the workspace in the balance calls that the tally's chunk does not plan (0 restores the default, 2^22):
+ * bppp_rp_commit_batch* and bppp_rp_open_* take  max (1, items / nranges)  rows a pass, bppp_rp_excess_sign*  items  sums, bppp_rp_excess_keys* and
+ * bppp_rp_excess_verify_keys_*  max (1, items / 4)  keys.  A test takes several passes with a handful of items. */
+int bppp_test_rp_set_flat_chunk(bppp_rp *rp, size_t items);
 /* The quad walk of k_rp_excess_mulcheck alone (csrc/rpexcess.hip.h): out_i = c_i X_i in affine form, infinity as all zeros, for n instances
  * of four lanes each.  d_scalars [n][4] words (walked as the 256-bit integers they are, reduced or not), d_points_xy and d_out_xy [n][8]
  * words, all in HBM.  The real entry points derive the challenge from a hash; here a test chooses it. */
