@@ -37,6 +37,7 @@
 #include "ec.hip.h"
 #include "ec29.hip.h"
 #include "ec_quad.hip.h"
+#include "hostcurve.hpp"
 #include "hostmath.hpp"
 #include "recode.hip.h"
 
@@ -1214,15 +1215,7 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
     BPPP_HIP(ctx, hipMemcpyAsync(ctx->pinned, winsum, bytes, hipMemcpyDeviceToHost, st));
     prof_mark(ctx, 6);
     BPPP_HIP(ctx, hipStreamSynchronize(st));
-    const uint32_t *ws = (const uint32_t *)ctx->pinned;
-    HJac r = hj_inf();
-    for (int w = W - 1; w >= 0; w--) {
-      const uint32_t *q = ws + (size_t)w * XYZZ_WORDS;
-      for (int k = 0; k < (w < acnt ? c : c - 1); k++) r = hj_dbl(r);
-      r = hj_add(r, hj_from_xyzz(from_limbs26(q), from_limbs26(q + 10), from_limbs26(q + 20), from_limbs26(q + 30)));
-    }
-    HAff a = hj_to_aff(r);
-    a.x.store(out_xy); a.y.store(out_xy + 4);
+    window_combine_host((const uint32_t *)ctx->pinned, W, c, acnt, false, 0, out_xy);
     BPPP_HIP(ctx, hipGetLastError());
     prof_collect(ctx, 7);
     return BPPP_OK;
@@ -1359,25 +1352,9 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
       prof_mark(ctx, 6);
       BPPP_HIP(ctx, hipStreamSynchronize(st));
       const uint32_t *ws = (const uint32_t *)ctx->pinned;
-      for (size_t b = 0; b < batch; b++) {
-        HJac r = hj_inf();
-        auto pt = [&](const uint32_t *q) { return hj_from_xyzz(from_limbs26(q), from_limbs26(q + 10), from_limbs26(q + 20), from_limbs26(q + 30)); };
-        for (int w = p.Wc - 1; w >= 0; w--) {
-          const int cw = (p.flat || w < p.acnt) ? c : c - 1;     // this window's width = the doublings that separate it from the one above
-          if (p.marg) {                               // window value = 2^a * W1 + W2: the doublings are split around W1
-            const uint32_t *q = ws + ((size_t)b * p.Wc + w) * 2 * XYZZ_WORDS;
-            for (int k = 0; k < cw - p.mg.a; k++) r = hj_dbl(r);
-            r = hj_add(r, pt(q));
-            for (int k = 0; k < p.mg.a; k++) r = hj_dbl(r);
-            r = hj_add(r, pt(q + XYZZ_WORDS));
-          } else {
-            for (int k = 0; k < cw; k++) r = hj_dbl(r);
-            r = hj_add(r, pt(ws + ((size_t)b * p.Wc + w) * XYZZ_WORDS));
-          }
-        }
-        HAff a = hj_to_aff(r);
-        a.x.store(out_xy + 8 * b); a.y.store(out_xy + 8 * b + 4);
-      }
+      // a flat table has one bucket set and windows of c bits throughout; the marginal reduction leaves (W1, W2) per window
+      for (size_t b = 0; b < batch; b++)
+        window_combine_host(ws + b * p.Wc * (p.marg ? 2 : 1) * XYZZ_WORDS, p.Wc, c, p.flat ? p.Wc : p.acnt, p.marg, p.marg ? p.mg.a : 0, out_xy + 8 * b);
     }
     BPPP_HIP(ctx, hipGetLastError());
     prof_collect(ctx, 7);
