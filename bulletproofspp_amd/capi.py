@@ -43,6 +43,8 @@ SYMBOLS = [
     "bppp_rp_excess_verify_batch_device",
     "bppp_rp_excess_keys", "bppp_rp_excess_keys_device", "bppp_rp_excess_verify_keys_each", "bppp_rp_excess_verify_keys_each_device", "bppp_rp_excess_verify_keys_batch",
     "bppp_rp_excess_verify_keys_batch_device", "bppp_rp_excess_sums_each", "bppp_rp_excess_sums_each_device", "bppp_rp_excess_sums_batch", "bppp_rp_excess_sums_batch_device",
+    "bppp_rp_excess_part_nonces", "bppp_rp_excess_part_nonces_device", "bppp_rp_excess_part_aggregate", "bppp_rp_excess_part_aggregate_device", "bppp_rp_excess_part_sign",
+    "bppp_rp_excess_part_sign_device", "bppp_rp_excess_part_verify", "bppp_rp_excess_part_verify_device", "bppp_rp_excess_part_combine", "bppp_rp_excess_part_combine_device",
     "bppp_seed_candidate_x", "bppp_points_from_seed", "bppp_points_from_seed_device", "bppp_rp_create_seeded", "bppp_rp_create_binary_seeded",
 ]
 
@@ -199,6 +201,16 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_excess_sums_each_device.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp]
     lib.bppp_rp_excess_sums_batch.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, C.POINTER(i), vp, vp]
     lib.bppp_rp_excess_sums_batch_device.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, C.c_uint64, vp, C.POINTER(i), vp, vp]
+    lib.bppp_rp_excess_part_nonces.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    lib.bppp_rp_excess_part_nonces_device.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    lib.bppp_rp_excess_part_aggregate.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp]
+    lib.bppp_rp_excess_part_aggregate_device.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp]
+    lib.bppp_rp_excess_part_sign.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    lib.bppp_rp_excess_part_sign_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    lib.bppp_rp_excess_part_verify.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+    lib.bppp_rp_excess_part_verify_device.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
+    lib.bppp_rp_excess_part_combine.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.bppp_rp_excess_part_combine_device.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.bppp_seed_candidate_x.argtypes = [C.c_char_p, sz, C.c_uint64, vp]
     lib.bppp_points_from_seed.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
     lib.bppp_points_from_seed_device.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
@@ -238,6 +250,7 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_rp_set_tally_chunk.argtypes = [vp, sz]
     lib.bppp_test_rp_set_flat_chunk.argtypes = [vp, sz]
     lib.bppp_test_rp_excess_mul.argtypes = [vp, sz, vp, vp, vp]
+    lib.bppp_test_rp_excess_mul2.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     lib.bppp_test_rp_witness_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.bppp_test_points_from_seed_chunked.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, sz, vp, C.POINTER(C.c_uint64)]
     lib.bppp_test_seed_lift_digests.argtypes = [vp, C.c_char_p, sz, vp, vp, vp]
@@ -310,6 +323,12 @@ RP_EXCESS_SIG_BYTES = 65
 # the stated keys (bppp_rp_excess_keys / _verify_keys_* / _sums_*): 33 bytes a key, and the verdict of one that does not lift
 RP_EXCESS_KEY_BYTES = 33
 RP_EXCESS_BAD_KEY = 6
+# the multi-party signer (bppp_rp_excess_part_*): 66 bytes a public nonce, 32 a partial response, and its two verdicts: a nonce sum that is
+# infinity, and (part_verify) a part whose sum has no aggregate because another part does not lift
+RP_EXCESS_PUBNONCE_BYTES = 66
+RP_EXCESS_PARTIAL_BYTES = 32
+RP_EXCESS_NONCE_INFINITY = 7
+RP_EXCESS_NO_AGGREGATE = 8
 # BPPP_RP_BINDING_BYTES: one proof's transcript binding of the bppp_rp_*_bound* entry points
 RP_BINDING_BYTES = 32
 

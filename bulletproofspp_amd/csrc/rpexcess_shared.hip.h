@@ -1,7 +1,8 @@
-// rpexcess_shared.hip.h — what the two excess files share: the derived-key path (csrc/rpexcess.hip: the key X_t comes out of the pool) and
-// the stated-key path (csrc/rpexkeys.hip: the key is 33 bytes next to the signature).  The domains, the three-block hash and the challenge
-// are one definition, so that the 65 bytes bppp_rp_excess_sign writes verify on either path; the kernels both paths run stay in
-// csrc/rpexcess.hip and are reached through the launches declared at the end.
+// rpexcess_shared.hip.h — what the excess files share: the derived-key path (csrc/rpexcess.hip: the key X_t comes out of the pool), the
+// stated-key path (csrc/rpexkeys.hip: the key is 33 bytes next to the signature) and the multi-party signer (csrc/rpexpart.hip: builders
+// who each know a part of the blinding sum).  The domains, the three-block hash, the challenge and the lift of 33 bytes are one definition,
+// so that the 65 bytes bppp_rp_excess_sign or bppp_rp_excess_part_combine writes verify on either path; the kernels both verifying paths
+// run stay in csrc/rpexcess.hip and are reached through the launches declared at the end.
 #pragma once
 #include <string.h>
 #include <string>
@@ -9,6 +10,7 @@
 #include "rp_internal.hpp"
 #include "rpprove_host.hpp"
 #include "rpwords.hip.h"
+#include "rplift.hip.h"
 #include "sha256.hip.h"
 
 namespace bppp {
@@ -20,6 +22,15 @@ struct ExDomain { uint32_t w[8]; };                    // a domain digest as the
 BPPP_DI uint32_t ex_dom_byte(const ExDomain &d, uint32_t k) { return (d.w[k >> 2] >> (24 - 8 * (k & 3))) & 0xFFu; }
 // byte o (< 33) of an affine point as a signature, a key and the messages hold it: put (x), then the sign byte (y > p - y)
 BPPP_DI uint32_t ex_pt_byte(const uint32_t *pt, uint32_t o) { return o < 32 ? enc_be_byte(pt, o) : enc_sign(pt); }
+// the 33 bytes of a key, or of any point held as a signature holds R -> the lifted point; false (and the infinity encoding) for a sign byte
+// above 1 or an x without a curve point
+BPPP_DI bool exk_lift(const uint8_t *key, aff &X) {
+  const uint32_t sign = key[32];
+  bool ok;
+  X = rp_lift_x(load_field_be<0>(key), sign == 1, ok);
+  if (sign > 1 || !ok) { X = aff_inf(); return false; }
+  return true;
+}
 // decode (SHA-256 (message)) mod n of a message of 120 .. 183 bytes (three blocks), byte k of it being at (k)
 template <class F> BPPP_DI fe ex_hash3(uint32_t nbytes, F at) {
   uint32_t st[8], w[16];

@@ -37,15 +37,6 @@ namespace bppp {
 static constexpr uint32_t EXK_NONE = 0xFFFFFFFFu;
 static constexpr uint32_t EXK_SUBTRACT = 0x80000000u;
 
-// the 33 bytes of a key -> the lifted point; false (and the infinity encoding) for a sign byte above 1 or an x without a curve point
-BPPP_DI bool exk_lift(const uint8_t *key, aff &X) {
-  const uint32_t sign = key[32];
-  bool ok;
-  X = rp_lift_x(load_field_be<0>(key), sign == 1, ok);
-  if (sign > 1 || !ok) { X = aff_inf(); return false; }
-  return true;
-}
-
 // ---- builder.  in_sc [n][3][8]: the scalars of X_t = e_t B on base `slot`, zero for a refused sum
 __global__ void __launch_bounds__(64) k_rp_exkeys_blinds(uint32_t n, uint32_t slot, const uint32_t *__restrict__ blinds, uint32_t *__restrict__ in_sc,
                                                          uint32_t *__restrict__ status) {

@@ -11,6 +11,7 @@
 #include "rpwitness.hip.h"
 #include "rpdecode.hip.h"
 #include "rpexcess.hip.h"
+#include "rpexpart.hip.h"
 #include "seedpoints.hip.h"
 #include "comb.hip.h"
 #include "rpp_transcript.hpp"
@@ -451,6 +452,26 @@ extern "C" int bppp_test_rp_excess_mul(bppp_rp *rp, size_t n, const void *d_scal
   k_test_excess_mul<<<dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, ctx->stream>>>((uint32_t)n, (const uint32_t *)d_scalars, (const uint32_t *)d_points_xy, (uint32_t *)d_out_xy);
   const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
   return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_rp_excess_mul: kernel failed");
+}
+
+// the joint walk of k_rp_expart_mulcheck alone: one quad per instance; lane 0 of the quad inverts and stores
+namespace bppp {
+__global__ void __launch_bounds__(64) k_test_excess_mul2(uint32_t n, const uint32_t *__restrict__ b, const uint32_t *__restrict__ P, const uint32_t *__restrict__ c,
+                                                         const uint32_t *__restrict__ Q, uint32_t *__restrict__ out) {
+  const uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) >> 2;
+  if (i >= n) return;
+  const xyzz r = excess_mul2_quad(fe_load(b + (size_t)i * 8), aff_load(P + (size_t)i * 16), fe_load(c + (size_t)i * 8), aff_load(Q + (size_t)i * 16));
+  if (quad_lane() == 0) aff_store(out + (size_t)i * 16, xyzz_to_aff(r));
+}
+}  // namespace bppp
+extern "C" int bppp_test_rp_excess_mul2(bppp_rp *rp, size_t n, const void *d_b, const void *d_P_xy, const void *d_c, const void *d_Q_xy, void *d_out_xy) {
+  if (!rp || !n || n >= (1u << 24) || !d_b || !d_P_xy || !d_c || !d_Q_xy || !d_out_xy) return BPPP_ERR_ARG;
+  bppp_ctx *ctx = rp->ctx;
+  hipSetDevice(ctx->device);
+  k_test_excess_mul2<<<dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, ctx->stream>>>((uint32_t)n, (const uint32_t *)d_b, (const uint32_t *)d_P_xy, (const uint32_t *)d_c,
+                                                                                       (const uint32_t *)d_Q_xy, (uint32_t *)d_out_xy);
+  const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
+  return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_rp_excess_mul2: kernel failed");
 }
 
 extern "C" int bppp_test_rp_witness_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds, const void *d_public_amounts,

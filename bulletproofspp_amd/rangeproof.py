@@ -1487,6 +1487,136 @@ class NativeRangeProofs:
                                                                       nkeys, p(d_key_start), p(d_keys), index_offset, *a)
         return self._tally_batch(fn, nsums, seed, want_status, want_point)
 
+    # ---- the multi-party signer: parties who each know a part of the blinding sum (bppp_rp_excess_part_nonces / _aggregate / _sign / _verify / _combine)
+    def _excess_part_rows(self, fn, name, n, args, out_specs, want_status, status_len=None):
+        """one builder call: args before the outputs; out_specs [(row bytes, rows, wanted)]; returns (outputs as row lists or None, statuses or None)"""
+        import ctypes as C
+        import numpy as np
+        bufs = [np.zeros(max(rows, 1) * width, dtype=np.uint8) if wanted else None for width, rows, wanted in out_specs]
+        status = np.zeros(max(status_len if status_len is not None else n, 1), dtype=np.uint32)
+        vp = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+        self.gpu._check(fn(self.h, *args, *[vp(b) for b in bufs], vp(status) if want_status else None), name)
+        outs = []
+        for (width, rows, wanted), b in zip(out_specs, bufs):
+            raw = b.tobytes() if wanted else None
+            outs.append([raw[t * width:(t + 1) * width] for t in range(rows)] if wanted else None)
+        return outs, ([int(v) for v in status[:status_len if status_len is not None else n]] if want_status else None)
+
+    def _excess_part_device(self, fn, name, args, n_status, want_status):
+        import ctypes as C
+        import numpy as np
+        status = np.zeros(max(n_status, 1), dtype=np.uint32)
+        self.gpu._check(fn(self.h, *args, C.c_void_p(status.ctypes.data) if want_status else None), name)
+        return [int(v) for v in status[:n_status]] if want_status else None
+
+    def excess_part_nonces(self, blinds: Sequence[int], msgs: Sequence[bytes], aux: bytes, want_status: bool = False):
+        """bppp_rp_excess_part_nonces: round 1 of one party for len(blinds) sessions.  Returns the 66-byte public nonces, or (nonces, statuses) with
+        want_status (a refused row has zero bytes); without it a refused row raises BpppError.  aux: 32 bytes of fresh randomness."""
+        import ctypes as C
+        import numpy as np
+        from .capi import scalars_to_array
+        n = len(blinds)
+        if len(msgs) != n or len(aux) != 32:
+            raise ValueError("one 32-byte message per session and 32 bytes of aux are required")
+        bl, mg, ax = scalars_to_array(list(blinds) or [0]), self._excess_bytes(msgs, 32, "messages"), np.frombuffer(aux, dtype=np.uint8)
+        vp = lambda a: C.c_void_p(a.ctypes.data)
+        (out,), st = self._excess_part_rows(self.gpu.lib.bppp_rp_excess_part_nonces, "bppp_rp_excess_part_nonces", n, (n, vp(bl), vp(mg), vp(ax)),
+                                            [(EXCESS_PUBNONCE_BYTES, n, True)], want_status)
+        return (out, st) if want_status else out
+
+    def excess_part_nonces_device(self, n: int, d_blinds: int, d_msgs: int, d_pubnonces: int, aux: bytes, want_status: bool = False):
+        """bppp_rp_excess_part_nonces_device: excess_part_nonces on buffers in HBM (d_pubnonces receives [n][66] bytes); returns the statuses or None"""
+        import ctypes as C
+        import numpy as np
+        p, ax = C.c_void_p, np.frombuffer(aux, dtype=np.uint8)
+        return self._excess_part_device(self.gpu.lib.bppp_rp_excess_part_nonces_device, "bppp_rp_excess_part_nonces", (n, p(d_blinds), p(d_msgs), p(ax.ctypes.data), p(d_pubnonces)),
+                                        n, want_status)
+
+    def _excess_part_groups(self, part_start, pubnonces, keys, partials=None, msgs=None):
+        import ctypes as C
+        import numpy as np
+        nsums, nparts = len(part_start) - 1, len(pubnonces)
+        if len(keys) != nparts or (partials is not None and len(partials) != nparts) or (msgs is not None and len(msgs) != nsums):
+            raise ValueError("one public nonce, one key and one partial per part and one message per sum are required")
+        keep = [np.array(list(part_start), dtype=np.uint32), self._excess_bytes(pubnonces, EXCESS_PUBNONCE_BYTES, "public nonces"), self._excess_bytes(keys, EXCESS_KEY_BYTES, "keys")]
+        if partials is not None:
+            keep += [self._excess_bytes(partials, EXCESS_PARTIAL_BYTES, "partials"), self._excess_bytes(msgs, 32, "messages")]
+        return keep, nsums, nparts, (nsums, nparts) + tuple(C.c_void_p(a.ctypes.data) for a in keep)
+
+    def excess_part_aggregate(self, part_start, pubnonces: Sequence[bytes], keys: Sequence[bytes], want_status: bool = False):
+        """bppp_rp_excess_part_aggregate: the coordinator's step; the parts of sum t are rows part_start[t] .. part_start[t + 1].  Returns (aggregated nonces
+        of 66 bytes, aggregated keys of 33 bytes), with the statuses as a third component with want_status; without it a refused sum raises BpppError."""
+        keep, nsums, nparts, args = self._excess_part_groups(part_start, pubnonces, keys)
+        (an, ak), st = self._excess_part_rows(self.gpu.lib.bppp_rp_excess_part_aggregate, "bppp_rp_excess_part_aggregate", nsums, args,
+                                              [(EXCESS_PUBNONCE_BYTES, nsums, True), (EXCESS_KEY_BYTES, nsums, True)], want_status)
+        return (an, ak, st) if want_status else (an, ak)
+
+    def excess_part_aggregate_device(self, nsums: int, nparts: int, d_part_start: int, d_pubnonces: int, d_keys: int, d_agg_nonces: int, d_agg_keys: int, want_status: bool = False):
+        """bppp_rp_excess_part_aggregate_device: excess_part_aggregate on buffers in HBM; returns the statuses or None"""
+        import ctypes as C
+        p = C.c_void_p
+        return self._excess_part_device(self.gpu.lib.bppp_rp_excess_part_aggregate_device, "bppp_rp_excess_part_aggregate",
+                                        (nsums, nparts, p(d_part_start), p(d_pubnonces), p(d_keys), p(d_agg_nonces), p(d_agg_keys)), nsums, want_status)
+
+    def excess_part_sign(self, blinds: Sequence[int], msgs: Sequence[bytes], aux: bytes, agg_nonces: Sequence[bytes], agg_keys: Sequence[bytes], want_status: bool = False):
+        """bppp_rp_excess_part_sign: round 2 of one party: the 32-byte partial responses, or (partials, statuses) with want_status.  aux is the aux of round 1;
+        never sign twice with one (blinding, message, aux) under different aggregates."""
+        import ctypes as C
+        import numpy as np
+        from .capi import scalars_to_array
+        n = len(blinds)
+        if len(msgs) != n or len(agg_nonces) != n or len(agg_keys) != n or len(aux) != 32:
+            raise ValueError("one message, one aggregated nonce and one aggregated key per session and 32 bytes of aux are required")
+        keep = [scalars_to_array(list(blinds) or [0]), self._excess_bytes(msgs, 32, "messages"), np.frombuffer(aux, dtype=np.uint8),
+                self._excess_bytes(agg_nonces, EXCESS_PUBNONCE_BYTES, "aggregated nonces"), self._excess_bytes(agg_keys, EXCESS_KEY_BYTES, "aggregated keys")]
+        (out,), st = self._excess_part_rows(self.gpu.lib.bppp_rp_excess_part_sign, "bppp_rp_excess_part_sign", n, (n,) + tuple(C.c_void_p(a.ctypes.data) for a in keep),
+                                            [(EXCESS_PARTIAL_BYTES, n, True)], want_status)
+        return (out, st) if want_status else out
+
+    def excess_part_sign_device(self, n: int, d_blinds: int, d_msgs: int, d_agg_nonces: int, d_agg_keys: int, d_partials: int, aux: bytes, want_status: bool = False):
+        """bppp_rp_excess_part_sign_device: excess_part_sign on buffers in HBM (d_partials receives [n][32] bytes); returns the statuses or None"""
+        import ctypes as C
+        import numpy as np
+        p, ax = C.c_void_p, np.frombuffer(aux, dtype=np.uint8)
+        return self._excess_part_device(self.gpu.lib.bppp_rp_excess_part_sign_device, "bppp_rp_excess_part_sign",
+                                        (n, p(d_blinds), p(d_msgs), p(ax.ctypes.data), p(d_agg_nonces), p(d_agg_keys), p(d_partials)), n, want_status)
+
+    def _excess_part_verify(self, fn, nsums, nparts, args):
+        import ctypes as C
+        import numpy as np
+        status, sst = np.zeros(max(nparts, 1), dtype=np.uint32), np.zeros(max(nsums, 1), dtype=np.uint32)
+        self.gpu._check(fn(self.h, *args, C.c_void_p(status.ctypes.data), C.c_void_p(sst.ctypes.data)), "bppp_rp_excess_part_verify")
+        return [int(v) for v in status[:nparts]], [int(v) for v in sst[:nsums]]
+
+    def excess_part_verify(self, part_start, pubnonces: Sequence[bytes], keys: Sequence[bytes], partials: Sequence[bytes], msgs: Sequence[bytes]):
+        """bppp_rp_excess_part_verify: who misbehaved: (one verdict per part, one verdict per sum)"""
+        keep, nsums, nparts, args = self._excess_part_groups(part_start, pubnonces, keys, partials, msgs)
+        return self._excess_part_verify(self.gpu.lib.bppp_rp_excess_part_verify, nsums, nparts, args)
+
+    def excess_part_verify_device(self, nsums: int, nparts: int, d_part_start: int, d_pubnonces: int, d_keys: int, d_partials: int, d_msgs: int):
+        """bppp_rp_excess_part_verify_device: excess_part_verify on buffers in HBM"""
+        import ctypes as C
+        p = C.c_void_p
+        return self._excess_part_verify(self.gpu.lib.bppp_rp_excess_part_verify_device, nsums, nparts,
+                                        (nsums, nparts, p(d_part_start), p(d_pubnonces), p(d_keys), p(d_partials), p(d_msgs)))
+
+    def excess_part_combine(self, part_start, pubnonces: Sequence[bytes], keys: Sequence[bytes], partials: Sequence[bytes], msgs: Sequence[bytes], want_status: bool = False,
+                            want_keys: bool = False):
+        """bppp_rp_excess_part_combine: the 65-byte signatures, or (signatures, statuses or None, aggregated keys or None) as asked; the partials are not
+        checked — verify the signature under the aggregated key, and ask excess_part_verify only when that fails"""
+        keep, nsums, nparts, args = self._excess_part_groups(part_start, pubnonces, keys, partials, msgs)
+        (sg, ak), st = self._excess_part_rows(self.gpu.lib.bppp_rp_excess_part_combine, "bppp_rp_excess_part_combine", nsums, args,
+                                              [(EXCESS_SIG_BYTES, nsums, True), (EXCESS_KEY_BYTES, nsums, want_keys)], want_status)
+        return (sg, st, ak) if (want_status or want_keys) else sg
+
+    def excess_part_combine_device(self, nsums: int, nparts: int, d_part_start: int, d_pubnonces: int, d_keys: int, d_partials: int, d_msgs: int, d_sigs: int, d_agg_keys: int = 0,
+                                   want_status: bool = False):
+        """bppp_rp_excess_part_combine_device: excess_part_combine on buffers in HBM (d_agg_keys 0: not wanted); returns the statuses or None"""
+        import ctypes as C
+        p = C.c_void_p
+        return self._excess_part_device(self.gpu.lib.bppp_rp_excess_part_combine_device, "bppp_rp_excess_part_combine",
+                                        (nsums, nparts, p(d_part_start), p(d_pubnonces), p(d_keys), p(d_partials), p(d_msgs), p(d_sigs), p(d_agg_keys or None)), nsums, want_status)
+
     def share_comb(self, donor: "NativeRangeProofs"):
         """bppp_rp_share_comb: prove over `donor`'s comb table from now on (built now if it has none).  Same context; the donor's basis
         must extend this handle's point by point.  The table lives until its last user is closed."""
@@ -1817,6 +1947,137 @@ def excess_sums_host(backend: "Backend", setup, S: Point, claim, keys: Sequence[
         return 3, rest
     want = _commit_terms(backend, [(a, g), (o, B)] + ([(ty, H0)] if H0 is not None else []))
     return (0 if rest == want else 1), rest
+
+
+# ---- the multi-party signer (bppp_rp_excess_part_*): builders who each know a part e_i of the blinding sum; include/bppp.h states every message
+EXCESS_PUBNONCE_BYTES = 66
+EXCESS_PARTIAL_BYTES = 32
+EXCESS_NONCE_INFINITY = 7
+EXCESS_NO_AGGREGATE = 8
+
+
+def _get256(b32: bytes) -> int:
+    """the 256-bit integer 32 bytes hold as put wrote them, not reduced"""
+    return sum(int.from_bytes(b32[8 * i:8 * i + 8], "big") << (64 * i) for i in range(4))
+
+
+def excess_part_nonce(tag: bytes, e: int, msg: bytes, aux: bytes, j: int) -> int:
+    """k_j = decode (SHA-256 (Dm || put (e) || msg || aux || byte j)) mod n for j = 1, 2, Dm = SHA-256 ("bppp/excess/partnonce/v1" || tag): 129 bytes"""
+    return decode_field(hashlib.sha256(hashlib.sha256(b"bppp/excess/partnonce/v1" + tag).digest() + _put(e) + msg + aux + bytes([j])).digest(), N)
+
+
+def excess_nonce_coef(tag: bytes, r1_33: bytes, r2_33: bytes, X: Tuple[int, int], msg: bytes) -> int:
+    """b = decode (SHA-256 (Db || the canonical 33 bytes of R1agg || of R2agg || of X || msg)) mod n, Db = SHA-256 ("bppp/excess/noncecoef/v1" || tag):
+    163 bytes"""
+    return decode_field(hashlib.sha256(hashlib.sha256(b"bppp/excess/noncecoef/v1" + tag).digest() + r1_33 + r2_33 + _point33(X) + msg).digest(), N)
+
+
+def _excess_part_status(e: int, tag: bytes, msg: bytes, aux: bytes):
+    """the signer's verdict on its blinding part and the two nonces (None where refused)"""
+    if not 0 <= e < N:
+        return EXCESS_NOT_CANONICAL, None
+    if e == 0:
+        return EXCESS_ZERO, None
+    ks = [excess_part_nonce(tag, e, msg, aux, j) for j in (1, 2)]
+    return (EXCESS_NONCE, None) if 0 in ks else (EXCESS_OK, ks)
+
+
+def excess_part_nonces_host(backend: "Backend", setup, e: int, msg: bytes, aux: bytes, tag: bytes = b""):
+    """Host restatement of bppp_rp_excess_part_nonces for one session: (status, the 66 bytes of (k_1 B, k_2 B)); a refused row has zero bytes"""
+    _, _, B = _excess_bases(setup)
+    status, ks = _excess_part_status(e, tag, msg, aux)
+    if status != EXCESS_OK:
+        return status, bytes(EXCESS_PUBNONCE_BYTES)
+    return status, b"".join(_point33(backend.commit([k], [B])) for k in ks)
+
+
+def _excess_part_group(backend: "Backend", pubnonces: Sequence[bytes], keys: Sequence[bytes]):
+    """the stage of bppp_rp_excess_part_aggregate for one sum: (verdict, R1agg, R2agg, X), the points None unless the verdict is OK"""
+    Xs = [excess_lift33(k) for k in keys]
+    if None in Xs:
+        return EXCESS_BAD_KEY, None, None, None
+    R1s, R2s = [excess_lift33(pn[:33]) for pn in pubnonces], [excess_lift33(pn[33:]) for pn in pubnonces]
+    if None in R1s or None in R2s:
+        return EXCESS_BAD_R, None, None, None
+    X, R1, R2 = (_commit_terms(backend, [(1, p) for p in ps]) for ps in (Xs, R1s, R2s))
+    if X is None:
+        return EXCESS_NO_KEY, None, None, None
+    if R1 is None or R2 is None:
+        return EXCESS_NONCE_INFINITY, None, None, None
+    return EXCESS_OK, R1, R2, X
+
+
+def _excess_part_session(backend: "Backend", tag: bytes, R1, R2, X, msg: bytes):
+    """(b, R, c) of a session; R None (and c None) when R1agg + b R2agg is infinity"""
+    b = excess_nonce_coef(tag, _point33(R1), _point33(R2), X, msg)
+    R = _commit_terms(backend, [(1, R1), (b, R2)])
+    return b, R, (excess_challenge(tag, _point33(R), X, msg) if R is not None else None)
+
+
+def excess_part_aggregate_host(backend: "Backend", setup, pubnonces: Sequence[bytes], keys: Sequence[bytes]):
+    """Host restatement of bppp_rp_excess_part_aggregate for one sum: (status, the 66 bytes of (R1agg, R2agg), the 33 bytes of X); zero bytes when refused"""
+    status, R1, R2, X = _excess_part_group(backend, pubnonces, keys)
+    if status != EXCESS_OK:
+        return status, bytes(EXCESS_PUBNONCE_BYTES), bytes(EXCESS_KEY_BYTES)
+    return status, _point33(R1) + _point33(R2), _point33(X)
+
+
+def excess_part_sign_host(backend: "Backend", setup, e: int, msg: bytes, aux: bytes, agg_nonce: bytes, agg_key: bytes, tag: bytes = b""):
+    """Host restatement of bppp_rp_excess_part_sign for one session: (status, put (k_1 + b k_2 + c e)); zero bytes when refused"""
+    refused = lambda st: (st, bytes(EXCESS_PARTIAL_BYTES))
+    status, ks = _excess_part_status(e, tag, msg, aux)
+    if status != EXCESS_OK:
+        return refused(status)
+    X, R1, R2 = excess_lift33(agg_key), excess_lift33(agg_nonce[:33]), excess_lift33(agg_nonce[33:])
+    if X is None:
+        return refused(EXCESS_BAD_KEY)
+    if R1 is None or R2 is None:
+        return refused(EXCESS_BAD_R)
+    b, R, c = _excess_part_session(backend, tag, R1, R2, X, msg)
+    if R is None:
+        return refused(EXCESS_NONCE_INFINITY)
+    return EXCESS_OK, _put((ks[0] + b * ks[1] + c * e) % N)
+
+
+def excess_part_verify_host(backend: "Backend", setup, pubnonces: Sequence[bytes], keys: Sequence[bytes], partials: Sequence[bytes], msg: bytes, tag: bytes = b""):
+    """Host restatement of bppp_rp_excess_part_verify for one sum: (the verdict of every part, the verdict of the sum), in the header's order"""
+    _, _, B = _excess_bases(setup)
+    sum_status, R1, R2, X = _excess_part_group(backend, pubnonces, keys)
+    b = c = None
+    if sum_status == EXCESS_OK:
+        b, R, c = _excess_part_session(backend, tag, R1, R2, X, msg)
+        if R is None:
+            sum_status = EXCESS_NONCE_INFINITY
+    out = []
+    for pn, key, part in zip(pubnonces, keys, partials):
+        Xi, R1i, R2i, s = excess_lift33(key), excess_lift33(pn[:33]), excess_lift33(pn[33:]), _get256(part)
+        if Xi is None:
+            out.append(EXCESS_BAD_KEY)
+        elif s >= N:
+            out.append(3)
+        elif R1i is None or R2i is None:
+            out.append(EXCESS_BAD_R)
+        elif sum_status in (EXCESS_BAD_KEY, EXCESS_BAD_R):
+            out.append(EXCESS_NO_AGGREGATE)                 # another part of the sum does not lift
+        elif sum_status != EXCESS_OK:
+            out.append(sum_status)
+        else:
+            out.append(0 if _commit_terms(backend, [(s, B), (-b, R2i), (-c, Xi)]) == R1i else 1)
+    return out, sum_status
+
+
+def excess_part_combine_host(backend: "Backend", setup, pubnonces: Sequence[bytes], keys: Sequence[bytes], partials: Sequence[bytes], msg: bytes, tag: bytes = b""):
+    """Host restatement of bppp_rp_excess_part_combine for one sum: (status, the 65 signature bytes, the 33 bytes of the aggregated key); zero bytes when
+    refused.  The partials are added mod n as they are: nothing checks them here."""
+    status, R1, R2, X = _excess_part_group(backend, pubnonces, keys)
+    R = None
+    if status == EXCESS_OK:
+        _, R, _ = _excess_part_session(backend, tag, R1, R2, X, msg)
+        if R is None:
+            status = EXCESS_NONCE_INFINITY
+    if status != EXCESS_OK:
+        return status, bytes(EXCESS_SIG_BYTES), bytes(EXCESS_KEY_BYTES)
+    return status, _point33(R) + _put(sum(_get256(p) for p in partials) % N), _point33(X)
 
 
 def _mixed_groups(files):

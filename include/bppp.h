@@ -963,6 +963,96 @@ int bppp_rp_excess_sums_batch_device(bppp_rp *rp, size_t rows, const void *d_com
                                      const void *d_claim_amounts, const void *d_claim_types, const void *d_claim_offsets, size_t nkeys, const void *d_key_start,
                                      const void *d_keys, uint64_t index_offset, const uint8_t seed[32], int *accept, uint32_t *status, uint64_t *combined_xy);
 
+/* ---- multi-party excess signatures: builders who each know a PART of the blinding sum sign together --------------------------------------------
+ * bppp_rp_excess_sign takes e_t whole.  In a transaction between a sender and a receiver nobody knows it whole: party i knows e_{t,i}, the blinding
+ * sum of its own inputs and outputs, and e_t = sum_i e_{t,i}.  The calls below let the parties produce the 65 bytes of the SIGNATURE above under the
+ * CHALLENGE above, so every verifier of this header accepts the result as it is.  Two rounds with two nonces a party, as in MuSig2: no commitment
+ * round is needed for sessions that run at the same time.  Keys add PLAINLY, with no key-aggregation coefficients: the aggregated key has to equal
+ * the excess of the commitments, X_t = sum_i X_{t,i} = S_t - a_t g - ty_t H0, and it is the sums check (bppp_rp_excess_sums_*, or the derived key of
+ * bppp_rp_excess_verify_*) that binds it to commitments whose range proofs prove knowledge of their blindings.  A stated-key signature ALONE
+ * (bppp_rp_excess_verify_keys_* without that check) does not protect against a cosigner who chooses its key as a difference X' - X_1.
+ * B, put, decode, the sign byte, the lift of 33 bytes, tag, Dc and the challenge are those of the two blocks above.  New domains, hashed once a call:
+ *   Dm = SHA-256 ("bppp/excess/partnonce/v1" || tag)        Db = SHA-256 ("bppp/excess/noncecoef/v1" || tag)
+ * Dm is not the single signer's Dn: a party that also signs alone with the same (e, msg, aux) never uses a nonce twice.
+ *   party nonces   k_j = decode (SHA-256 (Dm || put (e_i) || msg[32] || aux[32] || byte j)) mod n,  j = 1, 2                          — 129 bytes
+ *   public nonce   [BPPP_RP_EXCESS_PUBNONCE_BYTES = 66]: the 33 bytes of R1 = k_1 B, then the 33 bytes of R2 = k_2 B
+ *   aggregates     R1agg = sum_i R1_i,  R2agg = sum_i R2_i,  X = sum_i X_i;  X_i = e_i B as 33 bytes comes from bppp_rp_excess_keys
+ *   coefficient    b = decode (SHA-256 (Db || canon33 (R1agg) || canon33 (R2agg) || canon33 (X) || msg)) mod n                        — 163 bytes
+ *                  canon33: the canonical 33 bytes of the LIFTED point, the rule of every hash that names a key
+ *   session        R = R1agg + b R2agg,    c = the CHALLENGE over (canon33 (R), X, msg): the single signer's, byte for byte
+ *   partial        [BPPP_RP_EXCESS_PARTIAL_BYTES = 32]: put (s_i),  s_i = k_1 + b k_2 + c e_i mod n
+ *   signature      canon33 (R) || put (sum_i s_i mod n)
+ *   partial check  s_i B - b R2_i - c X_i = R1_i
+ * GROUPS.  part_start [nsums + 1] (uint32, non-decreasing, part_start[0] = 0, part_start[nsums] = nparts): the parts of sum t are the contiguous
+ * rows part_start[t] .. part_start[t + 1] of pubnonces [nparts][66], keys [nparts][33] and partials [nparts][32].  It is validated as key_start is:
+ * by a kernel whose verdict is read back before anything reads through the array.  A sum with no part is BPPP_ERR_ARG ("part_start: sum N has no part").
+ *
+ * 1. bppp_rp_excess_part_nonces{,_device}: round 1 for n sessions of ONE party: part_blinds [n][4], msgs [n][32], aux[32] -> pubnonces [n][66].
+ *    status (host, may be NULL, [n]): BPPP_RP_EXCESS_OK, _NOT_CANONICAL (e >= n), _ZERO (e = 0) or _NONCE (k_1 or k_2 is 0); a refused row is 66
+ *    zero bytes.  With status == NULL a refusal is BPPP_ERR_ARG and bppp_last_error names the lowest refused row ("part N: ..."); the output is then
+ *    as it would be with status given.  The secret nonces never leave the call: round 2 derives them again.
+ * 2. bppp_rp_excess_part_aggregate{,_device}: the coordinator's step; it needs no secret.  agg_nonces [nsums][66] = (R1agg, R2agg) and agg_keys
+ *    [nsums][33] = X.  status (host, may be NULL, [nsums]), the first that applies of
+ *      BPPP_RP_EXCESS_BAD_KEY (6)         a key of the group has a sign byte above 1 or an x without a curve point
+ *      BPPP_RP_EXCESS_BAD_R (4)           a nonce point of the group has
+ *      BPPP_RP_EXCESS_NO_KEY (5)          X is infinity
+ *      BPPP_RP_EXCESS_NONCE_INFINITY (7)  R1agg or R2agg is infinity
+ *      BPPP_RP_EXCESS_OK (0)
+ *    A refused sum gets zero bytes; with status == NULL a refusal is BPPP_ERR_ARG ("sum N: ...").
+ * 3. bppp_rp_excess_part_sign{,_device}: round 2 for n sessions of one party: partials [n][32].  It is STATELESS: k_1 and k_2 are derived again from
+ *    (e, msg, aux), the aggregates are lifted, and b, R, c and s_i follow.  status (host, may be NULL, [n]), the first that applies of the three
+ *    refusals of call 1, BPPP_RP_EXCESS_BAD_KEY (agg_keys does not lift), BPPP_RP_EXCESS_BAD_R (an aggregated nonce point does not),
+ *    BPPP_RP_EXCESS_NONCE_INFINITY (R is infinity), BPPP_RP_EXCESS_OK; refusals and a NULL status as in call 1.
+ *    TWO RULES THE CALLER MUST KEEP.  (a) aux is FRESH RANDOMNESS for every session.  (b) part_sign is NEVER called twice with one (e, msg, aux) under
+ *    different aggregates.  Either mistake yields two responses over the same nonces under different b or c, and they reveal e.  The library is not
+ *    hardened against side channels, here as everywhere.
+ * 4. bppp_rp_excess_part_verify{,_device}: who misbehaved.  It aggregates by the stage of call 2 itself, so a caller cannot hand it aggregates that
+ *    do not belong to the parts.  msgs [nsums][32].  status [nparts] (host, required), per part the first that applies of
+ *      BPPP_RP_EXCESS_BAD_KEY (6)         the part's key does not lift
+ *      BPPP_RP_OPEN_NOT_CANONICAL (3)     s_i >= n
+ *      BPPP_RP_EXCESS_BAD_R (4)           one of the part's nonce points does not lift
+ *      BPPP_RP_EXCESS_NO_AGGREGATE (8)    ANOTHER part of its sum has a key or a nonce point that does not lift: the sum has no aggregate and this
+ *                                         part no equation to be asked, until that part — the one that reads BAD_KEY or BAD_R — is replaced
+ *      the verdict of its sum, if that is not OK: BPPP_RP_EXCESS_NO_KEY (5) or BPPP_RP_EXCESS_NONCE_INFINITY (7; also: R is infinity)
+ *      BPPP_RP_OPEN_MISMATCH (1) or BPPP_RP_OPEN_OK (0), from the partial check.
+ *    sum_status (host, may be NULL, [nsums]): the verdict of each sum as call 2 gives it, NONCE_INFINITY also for R.
+ * 5. bppp_rp_excess_part_combine{,_device}: the final signatures sigs [nsums][65]; agg_keys (may be NULL) [nsums][33].  status (host, may be NULL,
+ *    [nsums]) as sum_status of call 4; a refused sum gets zero bytes, and with status == NULL a refusal is BPPP_ERR_ARG ("sum N: ...").  IT DOES NOT
+ *    CHECK THE PARTIALS (each is taken mod n): the caller checks the 65 bytes with bppp_rp_excess_verify_keys_each under the aggregated key, and
+ *    runs call 4 only when that fails.
+ *
+ * PASSES.  Calls 2, 4 and 5 cut their passes over the workspace at sum boundaries, 2^20 parts a pass; a single sum with more parts than one pass
+ * holds is BPPP_ERR_ARG, and bppp_last_error names the sum and the limit.  A group is added serially by four lanes: parties per transaction are few.
+ * Errors (BPPP_ERR_ARG): a NULL buffer, n, nsums or nparts >= 2^31, a part_start that is not non-decreasing from 0 to nparts ("part_start[i] =
+ * ..."), an empty or an over-long group; no output buffer is written then.  n == 0 or nsums == 0 is BPPP_OK and nothing else is looked at.  The host
+ * variants upload, call the _device variant and download; status arrays and aux are host memory. */
+#define BPPP_RP_EXCESS_PUBNONCE_BYTES 66
+#define BPPP_RP_EXCESS_PARTIAL_BYTES 32
+#define BPPP_RP_EXCESS_NONCE_INFINITY 7u
+#define BPPP_RP_EXCESS_NO_AGGREGATE 8u
+int bppp_rp_excess_part_nonces(bppp_rp *rp, size_t n, const uint64_t *part_blinds, const uint8_t *msgs, const uint8_t aux[32], uint8_t *pubnonces,
+                               uint32_t *status /* may be NULL */);
+int bppp_rp_excess_part_nonces_device(bppp_rp *rp, size_t n, const void *d_part_blinds, const void *d_msgs, const uint8_t aux[32], void *d_pubnonces,
+                                      uint32_t *status /* host, [n], may be NULL */);
+int bppp_rp_excess_part_aggregate(bppp_rp *rp, size_t nsums, size_t nparts, const uint32_t *part_start, const uint8_t *pubnonces, const uint8_t *keys,
+                                  uint8_t *agg_nonces, uint8_t *agg_keys, uint32_t *status /* may be NULL */);
+int bppp_rp_excess_part_aggregate_device(bppp_rp *rp, size_t nsums, size_t nparts, const void *d_part_start, const void *d_pubnonces, const void *d_keys,
+                                         void *d_agg_nonces, void *d_agg_keys, uint32_t *status /* host, [nsums], may be NULL */);
+int bppp_rp_excess_part_sign(bppp_rp *rp, size_t n, const uint64_t *part_blinds, const uint8_t *msgs, const uint8_t aux[32], const uint8_t *agg_nonces,
+                             const uint8_t *agg_keys, uint8_t *partials, uint32_t *status /* may be NULL */);
+int bppp_rp_excess_part_sign_device(bppp_rp *rp, size_t n, const void *d_part_blinds, const void *d_msgs, const uint8_t aux[32], const void *d_agg_nonces,
+                                    const void *d_agg_keys, void *d_partials, uint32_t *status /* host, [n], may be NULL */);
+int bppp_rp_excess_part_verify(bppp_rp *rp, size_t nsums, size_t nparts, const uint32_t *part_start, const uint8_t *pubnonces, const uint8_t *keys,
+                               const uint8_t *partials, const uint8_t *msgs, uint32_t *status, uint32_t *sum_status /* may be NULL */);
+int bppp_rp_excess_part_verify_device(bppp_rp *rp, size_t nsums, size_t nparts, const void *d_part_start, const void *d_pubnonces, const void *d_keys,
+                                      const void *d_partials, const void *d_msgs, uint32_t *status /* host, [nparts], required */,
+                                      uint32_t *sum_status /* host, [nsums], may be NULL */);
+int bppp_rp_excess_part_combine(bppp_rp *rp, size_t nsums, size_t nparts, const uint32_t *part_start, const uint8_t *pubnonces, const uint8_t *keys,
+                                const uint8_t *partials, const uint8_t *msgs, uint8_t *sigs, uint8_t *agg_keys /* may be NULL */, uint32_t *status /* may be NULL */);
+int bppp_rp_excess_part_combine_device(bppp_rp *rp, size_t nsums, size_t nparts, const void *d_part_start, const void *d_pubnonces, const void *d_keys,
+                                       const void *d_partials, const void *d_msgs, void *d_sigs, void *d_agg_keys /* may be NULL */,
+                                       uint32_t *status /* host, [nsums], may be NULL */);
+
 /* ---- one comb table for the handles of a basis family --------------------------------------------------------------------------
  * Every setup's basis [g | H | G] is a prefix of the point stream its points came from (see bppp_rp_verify_mixed), and the comb table
  * is laid out tab[window][point][multiple]: the table of the longest basis of a stream contains the table of every shorter one (same

@@ -86,12 +86,17 @@ int bppp_test_rp_set_tally_piece(bppp_rp *rp, size_t entries);
 int bppp_test_rp_set_tally_chunk(bppp_rp *rp, size_t entries);
 /* The items of one pass over the workspace in the balance calls that the tally's chunk does not plan (0 restores the default, 2^22):
  * bppp_rp_commit_batch* and bppp_rp_open_* take  max (1, items / nranges)  rows a pass, bppp_rp_excess_sign*  items  sums, bppp_rp_excess_keys* and
- * bppp_rp_excess_verify_keys_*  max (1, items / 4)  keys.  A test takes several passes with a handful of items. */
+ * bppp_rp_excess_verify_keys_*  max (1, items / 4)  keys, bppp_rp_excess_part_*  max (1, items / 4)  sessions or parts (whole groups: a group longer
+ * than that is an error).  A test takes several passes with a handful of items. */
 int bppp_test_rp_set_flat_chunk(bppp_rp *rp, size_t items);
 /* The quad walk of k_rp_excess_mulcheck alone (csrc/rpexcess.hip.h): out_i = c_i X_i in affine form, infinity as all zeros, for n instances
  * of four lanes each.  d_scalars [n][4] words (walked as the 256-bit integers they are, reduced or not), d_points_xy and d_out_xy [n][8]
  * words, all in HBM.  The real entry points derive the challenge from a hash; here a test chooses it. */
 int bppp_test_rp_excess_mul(bppp_rp *rp, size_t n, const void *d_scalars, const void *d_points_xy, void *d_out_xy);
+/* The joint walk of k_rp_expart_mulcheck alone (csrc/rpexpart.hip.h): out_i = b_i P_i + c_i Q_i in affine form, infinity as all zeros, for n
+ * instances of four lanes each.  d_b and d_c [n][4] words (walked as the 256-bit integers they are, reduced or not), d_P_xy, d_Q_xy and d_out_xy
+ * [n][8] words (infinity as all zeros), all in HBM.  P = Q, P = -Q and infinity in either place are ordinary input. */
+int bppp_test_rp_excess_mul2(bppp_rp *rp, size_t n, const void *d_b, const void *d_P_xy, const void *d_c, const void *d_Q_xy, void *d_out_xy);
 /* The witness kernel of bppp_rp_prove_batch_device alone (csrc/rpwitness.hip.h): inputs in HBM as that entry point takes them
  * (d_types ignored on a binary handle, d_public_amounts NULL or CANONICAL scalars [batch][public_count][4]); its arrays copied to the
  * host: in_sc [batch][nranges][3][4] words, status [batch] (0 = a witness; the arrays of a refused proof are unspecified) and, typed:
