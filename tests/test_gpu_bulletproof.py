@@ -122,9 +122,10 @@ def test_examples_64by64_shape(gpu, oracle_lib):
 
 
 def test_batch_verifier(gpu, oracle_lib):
-    """SURVEY.md 8(c) pins for the batch verifier: (ii) each valid proof's MSM is infinity, (iii) the random linear
-    combination is infinity iff all are valid, and (i) the combined result equals the oracle's sum_k rho_k * MSM(T_k)
-    when one proof is corrupted (a non-infinity point that depends on every per-proof scalar)."""
+    """SURVEY.md 8(c) pins for the batch verifier, as verdicts: (ii) each valid proof's MSM is infinity (on the oracle), (iii) the random
+    linear combination is accepted when all are valid and rejected when one proof is corrupted.  Pin (i) — the combined point equals
+    the oracle's sum_k rho_k * MSM(T_k), a non-infinity point that depends on every per-proof scalar — is checked in
+    tests/test_gpu_few_rounds.py::test_batch_point_equals_the_oracles_weighted_sum over shapes of 0, 1 and 2 rounds."""
     from bulletproofspp_amd.bulletproof import verifyBatch
     nl, ll, B = 12, 5, 7
     g, gs, hs, _, _, _, _ = _instance(nl, ll, 4242)
