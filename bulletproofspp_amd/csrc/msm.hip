@@ -89,14 +89,23 @@ __global__ void k_hist(const uint16_t *__restrict__ dig, uint32_t n, uint32_t st
   __syncthreads();
   uint32_t per = (((n + CH - 1) / CH) + 7u) & ~7u, lo = ch * per, hi = min(n, lo + per);
   const uint16_t *d = dig + (size_t)nbw * stride;
-  for (uint32_t j0 = lo + threadIdx.x * 8; j0 < hi; j0 += blockDim.x * 8) {
-    uint4 pk = *reinterpret_cast<const uint4 *>(d + j0);
+  // the digits of the next step are loaded before this step's are counted (a second register set, as marg_serial_sum's buckets): a lane
+  // has two loads in flight, not one.  Every load, the first and the ones ahead, is guarded by its own j < hi.
+  const uint32_t step = blockDim.x * 8;
+  uint32_t j0 = lo + threadIdx.x * 8;
+  uint4 pk = make_uint4(0u, 0u, 0u, 0u);
+  if (j0 < hi) pk = *reinterpret_cast<const uint4 *>(d + j0);
+  while (j0 < hi) {
+    const uint32_t jn = j0 + step;
+    uint4 pkn = pk;
+    if (jn < hi) pkn = *reinterpret_cast<const uint4 *>(d + jn);
     uint32_t w[4] = {pk.x, pk.y, pk.z, pk.w};
 #pragma unroll
     for (int k = 0; k < 8; k++) {
       int v = (int)((w[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu) - M;
       if (j0 + k < hi && v) atomicAdd(&lh[(v < 0 ? -v : v) - 1], 1u);
     }
+    pk = pkn; j0 = jn;
   }
   __syncthreads();
   uint32_t *out = blockhist + ((size_t)nbw * CH + ch) * M;
@@ -182,17 +191,38 @@ __global__ void k_scatter(const uint16_t *__restrict__ dig, const unsigned long 
   // flat_stride != 0: the windows of an instance share one bucket set and the entry indexes the table row of its window
   const uint32_t *st = start + (size_t)(flat_stride ? nbw / W : nbw) * M;
   const uint32_t idx_base = flat_stride ? (nbw % W) * flat_stride : 0u;
-  for (int t = threadIdx.x; t < M; t += blockDim.x) lh[t] = st[t] + bh[t];
+  // cursors: four pairs of loads are in flight before the first of them is added into LDS
+  for (int t0 = threadIdx.x; t0 < M; t0 += 4 * (int)blockDim.x) {
+    uint32_t a[4], b[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) { const int t = t0 + i * (int)blockDim.x; a[i] = t < M ? st[t] : 0u; b[i] = t < M ? bh[t] : 0u; }
+#pragma unroll
+    for (int i = 0; i < 4; i++) { const int t = t0 + i * (int)blockDim.x; if (t < M) lh[t] = a[i] + b[i]; }
+  }
   __syncthreads();
   uint32_t per = (((n + CH - 1) / CH) + 7u) & ~7u, lo = ch * per, hi = min(n, lo + per);
   const uint16_t *d = dig + (size_t)nbw * stride;
-  const uint32_t inst = nbw / W;
-  for (uint32_t j0 = lo + threadIdx.x * 8; j0 < hi; j0 += blockDim.x * 8) {
-    uint4 pk = *reinterpret_cast<const uint4 *>(d + j0);
+  const uint64_t inst0 = (uint64_t)(nbw / W) * n;
+  // the next step's digits and sign words are loaded before this step's entries are placed (k_hist); each load is guarded by its own j < hi
+  const uint32_t step = blockDim.x * 8;
+  uint32_t j0 = lo + threadIdx.x * 8;
+  uint4 pk = make_uint4(0u, 0u, 0u, 0u);
+  // sign bits of the 8 scalars: they may straddle two 64-bit words when inst*n is not a multiple of 8
+  unsigned long long m0 = 0ull, m1 = 0ull;
+  if (j0 < hi) {
+    pk = *reinterpret_cast<const uint4 *>(d + j0);
+    m0 = negmask[(inst0 + j0) >> 6]; m1 = negmask[(inst0 + j0 + 7) >> 6];
+  }
+  while (j0 < hi) {
+    const uint32_t jn = j0 + step;
+    uint4 pkn = pk;
+    unsigned long long m0n = m0, m1n = m1;
+    if (jn < hi) {
+      pkn = *reinterpret_cast<const uint4 *>(d + jn);
+      m0n = negmask[(inst0 + jn) >> 6]; m1n = negmask[(inst0 + jn + 7) >> 6];
+    }
     uint32_t w[4] = {pk.x, pk.y, pk.z, pk.w};
-    uint64_t flat0 = (uint64_t)inst * n + j0;
-    // sign bits of the 8 scalars: they may straddle two 64-bit words when inst*n is not a multiple of 8
-    unsigned long long m0 = negmask[flat0 >> 6], m1 = negmask[(flat0 + 7) >> 6];
+    const uint64_t flat0 = inst0 + j0;
 #pragma unroll
     for (int k = 0; k < 8; k++) {
       int v = (int)((w[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu) - M;
@@ -206,6 +236,7 @@ __global__ void k_scatter(const uint16_t *__restrict__ dig, const unsigned long 
         sorted[pos] = (sg << 31) | (idx_base + j0 + k);   // 4 bytes: the bucket is implied by start[] (position -> bucket), not stored
       }
     }
+    pk = pkn; m0 = m0n; m1 = m1n; j0 = jn;
   }
 }
 
@@ -217,34 +248,78 @@ __global__ void k_scatter(const uint16_t *__restrict__ dig, const unsigned long 
 // observed XCD affinity: an XCD works through its units one after another and the unit's slice of `sorted` (n * 4 / Q bytes) can stay in its
 // 4-MiB L2 until the lines are full.  That is placement for speed only — any dispatch order and any block -> XCD map give the same `sorted`
 // positions; no workgroup waits for another.  The digit row is re-read Q times (non-temporal: it should not push the output lines out).
+// ONE workgroup per CU (the launch asks for more than half of a CU's LDS, msm_run_ex): a unit's chunks then fill the XCD and one unit is live per
+// L2.  With two workgroups per CU (64 VGPRs allow it) two units are live, the lines leave the L2 half full (WRITE_SIZE 109 -> 215 MB at 2^20
+// terms) and the kernel is slower, loads ahead or not.  So the latency of a workgroup's chain is hidden inside the lane instead:
+// the digits and sign bytes of its first SCATTER_AHEAD steps are requested BEFORE the cursors, all cursor loads before the first LDS write, and
+// a step's registers are refilled with the step SCATTER_AHEAD further on as soon as its entries are placed.  The test j < hi that guarded the
+// single load per step now selects the ADDRESS: a lane whose step lies past the chunk's end reads the first 16 bytes of the row (and mask byte 0),
+// which every row has, and drops them.  A load under a branch would do, but its result then meets the other path's value in a register copy, and
+// the compiler waits for the load right there.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__global__ void k_scatter_ranges(const uint16_t *__restrict__ dig, const unsigned long long *__restrict__ negmask, uint32_t n, uint32_t stride,
-                                 int c, int CH, int Q, uint32_t U, int top, const uint32_t *__restrict__ blockhist,
-                                 const uint32_t *__restrict__ start, uint32_t *__restrict__ sorted) {
+static constexpr int SCATTER_AHEAD = 4;                     // 2^20 terms in 32 chunks of 1024 lanes: 4 steps, all in flight at once
+__global__ void __launch_bounds__(1024) k_scatter_ranges(const uint16_t *__restrict__ dig, const unsigned long long *__restrict__ negmask, uint32_t n,
+                                                         uint32_t stride, int c, int CH, int Q, uint32_t U, int top,
+                                                         const uint32_t *__restrict__ blockhist, const uint32_t *__restrict__ start,
+                                                         uint32_t *__restrict__ sorted) {
   extern __shared__ uint32_t lh[];
   const uint32_t M = 1u << (c - 1), Mq = M / (uint32_t)Q;
   const uint32_t s = blockIdx.x & 7u, k = blockIdx.x >> 3, u = (k / (uint32_t)CH) * 8u + s, ch = k % (uint32_t)CH;
   if (u >= U) return;                                       // the grid is padded to 8 slots x whole units
   const uint32_t nbw = u / (uint32_t)Q, r0 = (u % (uint32_t)Q) * Mq;
   const uint32_t flip = (int)nbw == top ? 1u : 0u;          // row `top` holds its digits negated (k_digits)
-  const uint32_t *bh = blockhist + ((size_t)nbw * CH + ch) * M + r0;
-  const uint32_t *st = start + (size_t)nbw * M + r0;
-  for (uint32_t t = threadIdx.x; t < Mq; t += blockDim.x) lh[t] = st[t] + bh[t];
-  __syncthreads();
   uint32_t per = (((n + CH - 1) / CH) + 7u) & ~7u, lo = ch * per, hi = min(n, lo + per);
   const uint16_t *d = dig + (size_t)nbw * stride;
-  for (uint32_t j0 = lo + threadIdx.x * 8; j0 < hi; j0 += blockDim.x * 8) {
-    u32x4 pk = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(d + j0));
-    uint32_t w[4] = {pk.x, pk.y, pk.z, pk.w};
-    const uint32_t sneg8 = (uint32_t)(negmask[j0 >> 6] >> (j0 & 63u));   // one instance, j0 a multiple of 8: the 8 sign bits share a word
+  // one instance and j a multiple of 8: the sign bits of a step's 8 scalars are ONE BYTE of negmask (bit j of the mask is bit j & 7 of
+  // byte j >> 3: the words are little-endian)
+  const uint8_t *sgn = reinterpret_cast<const uint8_t *>(negmask);
+  const uint32_t step = blockDim.x * 8;
+  uint32_t j0 = lo + threadIdx.x * 8;
+  u32x4 pk[SCATTER_AHEAD];
+  uint32_t sneg8[SCATTER_AHEAD];
 #pragma unroll
-    for (int e = 0; e < 8; e++) {
-      int v = (int)((w[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu) - (int)M;
-      uint32_t mb = (uint32_t)(v < 0 ? -v : v) - 1u - r0;   // v == 0: wraps past Mq
-      if (j0 + e < hi && v && mb < Mq) {
-        uint32_t sg = (v < 0 ? 1u : 0u) ^ ((sneg8 >> e) & 1u) ^ flip;
-        uint32_t pos = atomicAdd(&lh[mb], 1u);
-        sorted[pos] = (sg << 31) | (j0 + e);
+  for (int i = 0; i < SCATTER_AHEAD; i++) {
+    const uint32_t j = j0 + (uint32_t)i * step, ja = j < hi ? j : 0u;
+    pk[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(d + ja)); sneg8[i] = sgn[ja >> 3];
+  }
+  // cursors, four buckets per load (M = 2^15, Q <= 4 and the 16-byte aligned arrays: r0 and Mq are multiples of 4): all of a lane's loads
+  // (Mq / 4096 pairs, two at Q = 4) are in flight before the first sum is written to LDS
+  const uint4 *bh = reinterpret_cast<const uint4 *>(blockhist + ((size_t)nbw * CH + ch) * M + r0);
+  const uint4 *st = reinterpret_cast<const uint4 *>(start + (size_t)nbw * M + r0);
+  const uint32_t nq = Mq >> 2;
+  for (uint32_t t0 = threadIdx.x; t0 < nq; t0 += 4 * blockDim.x) {
+    uint4 a[4], b[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const uint32_t t = t0 + i * blockDim.x;
+      a[i] = b[i] = make_uint4(0u, 0u, 0u, 0u);
+      if (t < nq) { a[i] = st[t]; b[i] = bh[t]; }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const uint32_t t = t0 + i * blockDim.x;
+      if (t < nq) { lh[4 * t] = a[i].x + b[i].x; lh[4 * t + 1] = a[i].y + b[i].y; lh[4 * t + 2] = a[i].z + b[i].z; lh[4 * t + 3] = a[i].w + b[i].w; }
+    }
+  }
+  __syncthreads();
+  for (; j0 < hi; j0 += SCATTER_AHEAD * step) {
+#pragma unroll
+    for (int i = 0; i < SCATTER_AHEAD; i++) {
+      const uint32_t j = j0 + (uint32_t)i * step;
+      if (j < hi) {
+        const uint32_t w[4] = {pk[i].x, pk[i].y, pk[i].z, pk[i].w}, sn = sneg8[i];
+        const uint32_t jn = j + SCATTER_AHEAD * step, ja = jn < hi ? jn : 0u;
+        pk[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(d + ja)); sneg8[i] = sgn[ja >> 3];
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+          int v = (int)((w[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu) - (int)M;
+          uint32_t mb = (uint32_t)(v < 0 ? -v : v) - 1u - r0;   // v == 0: wraps past Mq
+          if (j + e < hi && v && mb < Mq) {
+            uint32_t sg = (v < 0 ? 1u : 0u) ^ ((sn >> e) & 1u) ^ flip;
+            uint32_t pos = atomicAdd(&lh[mb], 1u);
+            sorted[pos] = (sg << 31) | (j + e);
+          }
+        }
       }
     }
   }
@@ -1080,11 +1155,12 @@ static MsmPlan make_plan(size_t n, size_t batch, int c, bool flat, const MsmTune
   // the histogram of a wide window (>= 80 KB of LDS) leaves room for ONE k_hist / k_scatter workgroup per CU: a grid a few workgroups
   // over a whole number of rounds (17 windows x 16 chunks on 256 CUs) runs a nearly empty extra round — take the chunk count that fills
   // the rounds instead (15: sort stage 0.301 -> 0.277 ms at 2^20)
-  // ranged scatter (k_scatter_ranges): a (window, range) unit has as many chunks as an XCD has CUs (num_cus / 8: 32).  Two of its workgroups
-  // fit on a CU, so two units are live on an XCD: 2 MiB of `sorted` slices (n * 4 / Q bytes each for evenly spread digits) at 2^20 terms and
-  // Q = 4, half of the L2.  Measured there, sort stage: Q = 4 0.229 / 0.212 / 0.277 ms at 16 / 32 / 64 chunks, Q = 2 0.299 / 0.218 / 0.287
-  // (k_scatter, 15 chunks: 0.260).  A shorter input takes fewer chunks — more units are then live, still about 2 MiB of slices in all — but
-  // never fewer than the rule above gives.
+  // ranged scatter (k_scatter_ranges): a (window, range) unit has as many chunks as an XCD has CUs (num_cus / 8: 32) and ONE workgroup is
+  // resident per CU (the launch's LDS request), so one unit is live on an XCD: 1 MiB of `sorted` (n * 4 / Q bytes for evenly spread digits)
+  // at 2^20 terms and Q = 4, a quarter of the L2.  Two workgroups per CU, i.e. two live units, lose half of the merging and 0.01 ms (DESIGN.md
+  // 0.2).  Measured with the loads four steps ahead, sort stage: Q = 4 0.175 / 0.176 / 0.222 ms at 16 / 32 / 64 chunks, Q = 2 0.258 / 0.171 /
+  // 0.221 (k_scatter: 0.248 / 0.268 / 0.284).  A shorter input takes fewer chunks — more units are then live, still about 2 MiB of slices in
+  // all — but never fewer than the rule above gives.
   // k_hist, k_count_tiles and the blockhist layout use the same chunk count.
   p.Q = 0;
   if (batch == 1 && !flat && (size_t)p.M * 4 > 80 * 1024 && tune.num_cus >= 8 && (tune.sort_ranges == 2 || tune.sort_ranges == 4)) {
@@ -1292,8 +1368,10 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
     ctx->last_windows = p.W;
     if (p.Q) {
       const uint32_t U = (uint32_t)p.W * p.Q;                // units (window, range); 8 slots x ceil(U / 8) units x CH chunks
-      k_scatter_ranges<<<dim3(8u * ((U + 7) / 8) * p.CH), dim3(p.hist_threads), lds / p.Q, st>>>(dig, negmask, (uint32_t)n, stride, c, p.CH, p.Q, U,
-                                                                                                 p.top, blockhist, start, sorted);
+      // the cursors take lds / Q bytes; the request is for more than half of a CU's 160 KiB, so that ONE workgroup is resident per CU (k_scatter_ranges)
+      const size_t lds_one = std::max<size_t>(lds / p.Q, 84 * 1024);
+      k_scatter_ranges<<<dim3(8u * ((U + 7) / 8) * p.CH), dim3(p.hist_threads), lds_one, st>>>(dig, negmask, (uint32_t)n, stride, c, p.CH, p.Q, U,
+                                                                                               p.top, blockhist, start, sorted);
     } else
       k_scatter<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(dig, negmask, (uint32_t)n, stride, c, p.CH, p.W, blockhist, start, sorted,
                                                                                p.flat ? (uint32_t)table_stride : 0u, p.top);
