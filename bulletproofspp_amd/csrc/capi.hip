@@ -44,6 +44,7 @@ void MsmTune::from_env() {
   small_c = geti("BPPP_MSM_SMALL_C"); small_len = geti("BPPP_MSM_SMALL_LEN"); small_max = geti("BPPP_MSM_SMALL_MAX"); hist_ch = geti("BPPP_HIST_CH"); no_small = getenv("BPPP_MSM_NO_SMALL") != nullptr; if (getenv("BPPP_COMB_ROWS_MIN_MB")) comb_rows_min_bytes = (size_t)strtoull(getenv("BPPP_COMB_ROWS_MIN_MB"), nullptr, 10) << 20; no_balance = getenv("BPPP_MSM_NO_BALANCE") != nullptr;
   tail_scalar = getenv("BPPP_REDUCE_TAIL_SCALAR") != nullptr;     // k_reduce_tail (one lane per element) instead of k_reduce_tail_quad
   if (const char *e = getenv("BPPP_SORT_RANGES")) sort_ranges = atoi(e);   // 0 k_scatter, 2 / 4 k_scatter_ranges with that many bucket ranges per window
+  if (const char *e = getenv("BPPP_SCATTER_ONE_READ")) scatter_one_read = atoi(e) != 0;   // 0: k_scatter_ranges whatever the chunk length; else k_scatter_one_read where the plan allows it (the default)
   if (const char *e = getenv("BPPP_ACC_SIZED")) acc_sized = atoi(e) != 0;   // 1 / 0: k_acc_points_sized for every / no MSM over arbitrary points; unset: make_plan's default
   if (const char *e = getenv("BPPP_ACC_FQ29")) acc_fq29 = atoi(e) != 0;   // 1 / 0: k_acc_points_sized29 (9 x 29-bit limbs) for every / no sized accumulation
   if (const char *e = getenv("BPPP_ACC_LDS")) acc_lds = atoi(e) != 0;   // k_acc_points_lds (next point prefetched into LDS) instead of k_acc_points

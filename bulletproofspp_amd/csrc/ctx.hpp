@@ -10,7 +10,7 @@
 // Tuning overrides of the MSM plan (benchmarks/sweep_window.py and friends): the BPPP_* environment is read ONCE, when the context is
 // created; 0 / false = the library's heuristic.  No entry point reads the environment per call.
 struct MsmTune {
-  double gcost = 0; int cmin = 0, lw = 0, rg = 0, marg_s = 0, lacc = 0, window_batched = 0, comb_wpe = 0, small_c = 0, small_len = 0, small_max = 0, hist_ch = 0, num_cus = 0, sort_ranges = 4 /* bucket ranges per window of the ranged scatter, BPPP_SORT_RANGES: 0 = k_scatter */, acc_sized = -1 /* whole buckets by size (k_acc_points_sized), BPPP_ACC_SIZED: 1 = every one-MSM plan, 0 = none, -1 = the plans where it measured faster (make_plan) */, acc_fq29 = 1 /* the sized accumulation on 9 x 29-bit limbs (k_acc_points_sized29), BPPP_ACC_FQ29: not 0 = every sized plan (the default, by measurement: DESIGN.md 0.2), 0 = k_acc_points_sized on 10 x 26 */; bool reduce_old = false, no_small = false, no_balance = false, tail_scalar = false, acc_lds = false; size_t comb_rows_min_bytes = (size_t)4 << 30; int comb_rows_waves = 0;
+  double gcost = 0; int cmin = 0, lw = 0, rg = 0, marg_s = 0, lacc = 0, window_batched = 0, comb_wpe = 0, small_c = 0, small_len = 0, small_max = 0, hist_ch = 0, num_cus = 0, sort_ranges = 4 /* bucket ranges per window of the ranged scatter, BPPP_SORT_RANGES: 0 = k_scatter */, scatter_one_read = 1 /* the ranged scatter reads a chunk's digits once for all ranges (k_scatter_one_read), BPPP_SCATTER_ONE_READ: 0 = k_scatter_ranges always */, acc_sized = -1 /* whole buckets by size (k_acc_points_sized), BPPP_ACC_SIZED: 1 = every one-MSM plan, 0 = none, -1 = the plans where it measured faster (make_plan) */, acc_fq29 = 1 /* the sized accumulation on 9 x 29-bit limbs (k_acc_points_sized29), BPPP_ACC_FQ29: not 0 = every sized plan (the default, by measurement: DESIGN.md 0.2), 0 = k_acc_points_sized on 10 x 26 */; bool reduce_old = false, no_small = false, no_balance = false, tail_scalar = false, acc_lds = false; size_t comb_rows_min_bytes = (size_t)4 << 30; int comb_rows_waves = 0;
   void from_env();
 };
 
@@ -64,6 +64,7 @@ struct bppp_ctx {
   uint64_t last_mixed_terms = 0;     // terms of the last multi-setup MSM (bppp_test_last_mixed_msm_terms)
   int last_acc_lds = -1;             // accumulate kernel of the last general-pipeline MSM: 0 k_acc_points, 1 k_acc_points_lds (bppp_test_last_acc_kernel)
   int last_sort_ranges = -1;         // bucket ranges Q of the last general-pipeline MSM's scatter: 0 k_scatter, 2 / 4 k_scatter_ranges (bppp_test_last_sort_ranges)
+  int last_scatter_one_read = -1;    // 1: the last general-pipeline MSM's scatter was k_scatter_one_read, 0: any other (bppp_test_last_scatter_one_read)
   int last_acc_sized = -1;           // 1: the last general-pipeline MSM accumulated whole buckets by size (k_order, k_acc_points_sized), 0: slices (bppp_test_last_acc_sized)
   int last_acc_fq29 = -1;            // 1: the last general-pipeline MSM ran k_acc_points_sized29 (fq29 accumulator), 0: any other accumulate kernel (bppp_test_last_acc_fq29)
   int last_windows = -1;             // digit rows W per scalar of the last MSM's plan, either route (bppp_test_last_windows)

@@ -240,14 +240,16 @@ __global__ void k_scatter(const uint16_t *__restrict__ dig, const unsigned long 
   }
 }
 
-// The scatter of ONE MSM with wide windows (M * 4 > 80 KiB; make_plan, MsmPlan::Q), by bucket range.  k_scatter's stores are its whole cost:
+// The scatter of ONE MSM with wide windows (M * 4 > 80 KiB; make_plan, MsmPlan::Q), by bucket range, in the form for chunks of ANY length;
+// a plan whose chunks fit a lane's registers takes k_scatter_one_read below instead (MsmPlan::one_read).  k_scatter's stores are its whole cost:
 // a bucket's ~n / M entries (one 128-byte line at 2^20 terms) arrive from CH workgroups that sit on all 8 XCDs, so every 4-byte store leaves an
 // L2 as a request of its own.  Here a workgroup is (window w, range q of Q, chunk ch): it reads its chunk of the window's digit row as
 // k_scatter does, keeps only the cursors of the M / Q buckets of its range in LDS and places only their entries, at the positions k_scatter
 // would use (the order inside a (bucket, chunk) may differ).  The 1-D grid puts the chunks of one (w, q) unit on blocks b = s (mod 8), the
 // observed XCD affinity: an XCD works through its units one after another and the unit's slice of `sorted` (n * 4 / Q bytes) can stay in its
 // 4-MiB L2 until the lines are full.  That is placement for speed only — any dispatch order and any block -> XCD map give the same `sorted`
-// positions; no workgroup waits for another.  The digit row is re-read Q times (non-temporal: it should not push the output lines out).
+// positions; no workgroup waits for another.  The digit row is read Q times, once per range (non-temporal: it should not push the output lines
+// out): a quarter of this launch's traffic at Q = 4, which is what k_scatter_one_read saves where the chunk is short enough.
 // ONE workgroup per CU (the launch asks for more than half of a CU's LDS, msm_run_ex): a unit's chunks then fill the XCD and one unit is live per
 // L2.  With two workgroups per CU (64 VGPRs allow it) two units are live, the lines leave the L2 half full (WRITE_SIZE 109 -> 215 MB at 2^20
 // terms) and the kernel is slower, loads ahead or not.  So the latency of a workgroup's chain is hidden inside the lane instead:
@@ -322,6 +324,79 @@ __global__ void __launch_bounds__(1024) k_scatter_ranges(const uint16_t *__restr
         }
       }
     }
+  }
+}
+
+// The ranged scatter with a chunk's digits read ONCE (make_plan, MsmPlan::one_read: every chunk fits the SCATTER_AHEAD steps a lane holds in
+// registers).  A workgroup is (window w, chunk ch): it requests its digit packs and sign bytes as k_scatter_ranges does, before the cursors,
+// loads the cursors of all M buckets into LDS (M * 4 bytes, 128 KiB: one workgroup per CU, as k_scatter), and after ONE barrier places range 0,
+// then range 1, ... from the same registers, each pass taking only the entries whose bucket lies in its range.  The (window, range) -> XCD
+// placement of k_scatter_ranges is kept in time instead of in space: the 1-D grid puts the CH chunks of a window on blocks b = s (mod 8), so
+// an XCD works through its windows one after another, its workgroups walk the ranges together and the live slice of `sorted` per L2 is one
+// range of one window (n * 4 / Q bytes).  Placement for speed only: every entry lands where k_scatter puts it (the order inside a (bucket,
+// chunk) may differ), whatever the dispatch order; no workgroup waits for another.  The barrier after every pass is for speed too: it keeps
+// the 16 wavefronts of a workgroup, and with them the 32 workgroups of an XCD, on one range.  Without it they drift apart, all Q slices are
+// live at once and the lines leave the L2 a fraction full (WRITE_SIZE 66 -> 405 MB at 2^20 terms, sort stage 0.163 -> 0.183 ms).
+__global__ void __launch_bounds__(1024) k_scatter_one_read(const uint16_t *__restrict__ dig, const unsigned long long *__restrict__ negmask, uint32_t n,
+                                                           uint32_t stride, int c, int CH, int Q, uint32_t W, int top,
+                                                           const uint32_t *__restrict__ blockhist, const uint32_t *__restrict__ start,
+                                                           uint32_t *__restrict__ sorted) {
+  extern __shared__ uint32_t lh[];
+  const uint32_t M = 1u << (c - 1);
+  const uint32_t s = blockIdx.x & 7u, k = blockIdx.x >> 3, nbw = (k / (uint32_t)CH) * 8u + s, ch = k % (uint32_t)CH;
+  if (nbw >= W) return;                                     // the grid is padded to 8 slots x whole windows
+  const uint32_t flip = (int)nbw == top ? 1u : 0u;          // row `top` holds its digits negated (k_digits)
+  uint32_t per = (((n + CH - 1) / CH) + 7u) & ~7u, lo = ch * per, hi = min(n, lo + per);
+  const uint16_t *d = dig + (size_t)nbw * stride;
+  const uint8_t *sgn = reinterpret_cast<const uint8_t *>(negmask);   // one byte per step (k_scatter_ranges)
+  const uint32_t step = blockDim.x * 8, j0 = lo + threadIdx.x * 8;
+  u32x4 pk[SCATTER_AHEAD];
+  uint32_t sneg8[SCATTER_AHEAD];
+#pragma unroll
+  for (int i = 0; i < SCATTER_AHEAD; i++) {
+    const uint32_t j = j0 + (uint32_t)i * step, ja = j < hi ? j : 0u;   // past the chunk's end: the row's first 16 bytes, dropped below
+    pk[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(d + ja)); sneg8[i] = sgn[ja >> 3];
+  }
+  // cursors of the whole window, four buckets per load (M is a multiple of 4 and the arrays are 16-byte aligned), four pairs of loads per
+  // lane and round of the loop
+  const uint4 *bh = reinterpret_cast<const uint4 *>(blockhist + ((size_t)nbw * CH + ch) * M);
+  const uint4 *st = reinterpret_cast<const uint4 *>(start + (size_t)nbw * M);
+  const uint32_t nq = M >> 2;
+  for (uint32_t t0 = threadIdx.x; t0 < nq; t0 += 4 * blockDim.x) {
+    uint4 a[4], b[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const uint32_t t = t0 + i * blockDim.x;
+      a[i] = b[i] = make_uint4(0u, 0u, 0u, 0u);
+      if (t < nq) { a[i] = st[t]; b[i] = bh[t]; }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const uint32_t t = t0 + i * blockDim.x;
+      if (t < nq) { lh[4 * t] = a[i].x + b[i].x; lh[4 * t + 1] = a[i].y + b[i].y; lh[4 * t + 2] = a[i].z + b[i].z; lh[4 * t + 3] = a[i].w + b[i].w; }
+    }
+  }
+  __syncthreads();
+  const uint32_t Mq = M / (uint32_t)Q;
+  for (uint32_t r0 = 0; r0 < M; r0 += Mq) {
+#pragma unroll
+    for (int i = 0; i < SCATTER_AHEAD; i++) {
+      const uint32_t j = j0 + (uint32_t)i * step;
+      if (j < hi) {
+        const uint32_t w[4] = {pk[i].x, pk[i].y, pk[i].z, pk[i].w}, sn = sneg8[i];
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+          int v = (int)((w[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu) - (int)M;
+          uint32_t mb = (uint32_t)(v < 0 ? -v : v) - 1u;        // v == 0: wraps past every range
+          if (j + e < hi && v && mb - r0 < Mq) {
+            uint32_t sg = (v < 0 ? 1u : 0u) ^ ((sn >> e) & 1u) ^ flip;
+            uint32_t pos = atomicAdd(&lh[mb], 1u);
+            sorted[pos] = (sg << 31) | (j + e);
+          }
+        }
+      }
+    }
+    __syncthreads();                                        // the workgroup's wavefronts move to the next range together (see above)
   }
 }
 
@@ -1130,7 +1205,8 @@ struct MsmPlan {
   int RG;                      // k_reduce_groups lanes per window (0 = wave-per-window path)
   bool marg; MargGeom mg;      // marginal-sum reduction (M >= 256, not the grouped path)
   int ntiles;
-  int Q;                       // bucket ranges per window of the ranged scatter (k_scatter_ranges); 0 = k_scatter
+  int Q;                       // bucket ranges per window of the ranged scatter (k_scatter_ranges, k_scatter_one_read); 0 = k_scatter
+  bool one_read;               // ranged scatter from (window, chunk) workgroups that read their digits once (k_scatter_one_read)
   bool sized;                  // accumulate whole buckets in order of size (k_order, k_acc_points_sized) instead of slices of L entries
   bool fq29;                   // sized, with the accumulator in 9 x 29-bit limbs (k_acc_points_sized29)
 };
@@ -1155,12 +1231,13 @@ static MsmPlan make_plan(size_t n, size_t batch, int c, bool flat, const MsmTune
   // the histogram of a wide window (>= 80 KB of LDS) leaves room for ONE k_hist / k_scatter workgroup per CU: a grid a few workgroups
   // over a whole number of rounds (17 windows x 16 chunks on 256 CUs) runs a nearly empty extra round — take the chunk count that fills
   // the rounds instead (15: sort stage 0.301 -> 0.277 ms at 2^20)
-  // ranged scatter (k_scatter_ranges): a (window, range) unit has as many chunks as an XCD has CUs (num_cus / 8: 32) and ONE workgroup is
-  // resident per CU (the launch's LDS request), so one unit is live on an XCD: 1 MiB of `sorted` (n * 4 / Q bytes for evenly spread digits)
-  // at 2^20 terms and Q = 4, a quarter of the L2.  Two workgroups per CU, i.e. two live units, lose half of the merging and 0.01 ms (DESIGN.md
-  // 0.2).  Measured with the loads four steps ahead, sort stage: Q = 4 0.175 / 0.176 / 0.222 ms at 16 / 32 / 64 chunks, Q = 2 0.258 / 0.171 /
-  // 0.221 (k_scatter: 0.248 / 0.268 / 0.284).  A shorter input takes fewer chunks — more units are then live, still about 2 MiB of slices in
-  // all — but never fewer than the rule above gives.
+  // ranged scatter (k_scatter_ranges, k_scatter_one_read): a window is cut into as many chunks as an XCD has CUs (num_cus / 8: 32) and ONE
+  // workgroup is resident per CU (the launches' LDS requests), so that the workgroups of one (window, range) unit fill an XCD and ONE unit is
+  // live per L2: 1 MiB of `sorted` (n * 4 / Q bytes for evenly spread digits) at 2^20 terms and Q = 4, a quarter of the L2.  A second live
+  // unit — two workgroups per CU, or the wavefronts of k_scatter_one_read left to drift over the ranges — loses the merging.
+  // Measured with k_scatter_ranges, loads four steps ahead, sort stage: Q = 4 0.175 / 0.176 / 0.222 ms at 16 / 32 / 64 chunks, Q = 2 0.258 /
+  // 0.171 / 0.221 (k_scatter: 0.248 / 0.268 / 0.284); under k_scatter_one_read Q = 2 at 32 chunks is no faster than Q = 4.  A shorter
+  // input takes fewer chunks, of the same length, but never fewer than the rule above gives.
   // k_hist, k_count_tiles and the blockhist layout use the same chunk count.
   p.Q = 0;
   if (batch == 1 && !flat && (size_t)p.M * 4 > 80 * 1024 && tune.num_cus >= 8 && (tune.sort_ranges == 2 || tune.sort_ranges == 4)) {
@@ -1177,6 +1254,20 @@ static MsmPlan make_plan(size_t n, size_t batch, int c, bool flat, const MsmTune
     }
   }
   if (tune.hist_ch >= 1 && tune.hist_ch <= 64) p.CH = tune.hist_ch;
+  // one read of the digits (k_scatter_one_read): a lane holds SCATTER_AHEAD steps of 8 digits in registers, so the form is possible exactly
+  // when a chunk is no longer than that many steps of the workgroup — a rule in steps per lane, whatever n and the chunk count are.  With the
+  // chunk rule above that is every n up to 2^15 x (CUs of an XCD); a longer chunk keeps k_scatter_ranges, which refills its registers.
+  // Its W x CH workgroups run one per CU and each lasts Q range passes, so the form is taken only for grids that fill their rounds:
+  // - at least one whole round.  A smaller grid is a shorter MSM that often shares the chip with another stream's: two verifiers at once
+  //   (345 k terms each, 176 workgroups) ran 2.25 -> 2.34 ms per batch with the long workgroups, for 0.007 ms less sort stage when alone;
+  // - no last round for fewer than a quarter of the CUs, which costs a whole workgroup's time for little work where k_scatter_ranges'
+  //   workgroups of one pass each fill the CUs evenly — 17 chunks of 16 windows on 256 CUs (16 workgroups in the second round): sort stage
+  //   0.127 ms ranged, 0.134 read once; 20 chunks (64): 0.139 either way; 16 and 24 to 32 chunks are faster read once.
+  // Every other plan keeps k_scatter_ranges too.
+  const uint64_t chunk = ((((uint64_t)n + p.CH - 1) / p.CH) + 7u) & ~(uint64_t)7, lane_steps = (chunk + (uint64_t)p.hist_threads * 8 - 1) / ((uint64_t)p.hist_threads * 8);
+  const uint64_t wgs = (uint64_t)p.W * p.CH, cus = (uint64_t)std::max(tune.num_cus, 1), last_round = wgs % cus;
+  const bool full_rounds = wgs >= cus && !(last_round && 4 * last_round < cus);
+  p.one_read = p.Q && tune.scatter_one_read && lane_steps <= (uint64_t)SCATTER_AHEAD && full_rounds;
   // bucket reduce geometry: lanes per window T = M / Lw, at most 64 wavefronts per window
   if (p.M <= 64) { p.Lw = 1; p.WPW = 1; }
   else {
@@ -1351,6 +1442,7 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
       BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter_ranges, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter_one_read, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       ctx->sort_lds_set = lds;
     }
     prof_mark(ctx, 0);
@@ -1366,7 +1458,12 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
     k_scan_apply<<<dim3(p.ntiles), dim3(256), 0, st>>>(count, p.FB, tiles, start, size_hist);
     ctx->last_sort_ranges = p.Q;
     ctx->last_windows = p.W;
-    if (p.Q) {
+    ctx->last_scatter_one_read = p.one_read ? 1 : 0;
+    if (p.one_read) {
+      // 8 slots x ceil(W / 8) windows x CH chunks; the cursors of all M buckets take the whole request, which leaves ONE workgroup per CU
+      k_scatter_one_read<<<dim3(8u * (((uint32_t)p.W + 7) / 8) * p.CH), dim3(p.hist_threads), lds, st>>>(
+          dig, negmask, (uint32_t)n, stride, c, p.CH, p.Q, (uint32_t)p.W, p.top, blockhist, start, sorted);
+    } else if (p.Q) {
       const uint32_t U = (uint32_t)p.W * p.Q;                // units (window, range); 8 slots x ceil(U / 8) units x CH chunks
       // the cursors take lds / Q bytes; the request is for more than half of a CU's 160 KiB, so that ONE workgroup is resident per CU (k_scatter_ranges)
       const size_t lds_one = std::max<size_t>(lds / p.Q, 84 * 1024);

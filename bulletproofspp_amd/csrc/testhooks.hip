@@ -353,6 +353,12 @@ extern "C" int bppp_test_last_sort_ranges(bppp_ctx *ctx, int *q) {
   return BPPP_OK;
 }
 
+extern "C" int bppp_test_last_scatter_one_read(bppp_ctx *ctx, int *one_read) {
+  if (!ctx || !one_read) return BPPP_ERR_ARG;
+  *one_read = ctx->last_scatter_one_read;
+  return BPPP_OK;
+}
+
 extern "C" int bppp_test_last_acc_sized(bppp_ctx *ctx, int *sized) {
   if (!ctx || !sized) return BPPP_ERR_ARG;
   *sized = ctx->last_acc_sized;

@@ -51,6 +51,9 @@ int bppp_test_last_acc_kernel(bppp_ctx *ctx, int *lds);
 /* The scatter the last MSM of the general pipeline on this context launched: 0 = k_scatter, 2 or 4 = k_scatter_ranges with that many
  * bucket ranges per window (BPPP_SORT_RANGES; one MSM over arbitrary points with 16-bit windows only), -1 = none yet. */
 int bppp_test_last_sort_ranges(bppp_ctx *ctx, int *q);
+/* 1 = the ranged scatter of the last MSM of the general pipeline on this context read every chunk's digits once (k_scatter_one_read: no
+ * chunk longer than the steps a lane holds in registers, and BPPP_SCATTER_ONE_READ not 0), 0 = k_scatter_ranges or k_scatter, -1 = none yet. */
+int bppp_test_last_scatter_one_read(bppp_ctx *ctx, int *one_read);
 /* How the last MSM of the general pipeline on this context accumulated its buckets: 1 = whole buckets in order of size (k_order,
  * k_acc_points_sized; BPPP_ACC_SIZED, one MSM over arbitrary points only), 0 = slices of the sorted entries (k_acc_points, k_merge),
  * -1 = none yet. */
