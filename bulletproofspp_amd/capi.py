@@ -46,7 +46,22 @@ SYMBOLS = [
     "bppp_rp_excess_part_nonces", "bppp_rp_excess_part_nonces_device", "bppp_rp_excess_part_aggregate", "bppp_rp_excess_part_aggregate_device", "bppp_rp_excess_part_sign",
     "bppp_rp_excess_part_sign_device", "bppp_rp_excess_part_verify", "bppp_rp_excess_part_verify_device", "bppp_rp_excess_part_combine", "bppp_rp_excess_part_combine_device",
     "bppp_seed_candidate_x", "bppp_points_from_seed", "bppp_points_from_seed_device", "bppp_rp_create_seeded", "bppp_rp_create_binary_seeded",
+    "bppp_rp_verify_block", "bppp_rp_verify_block_device",
 ]
+
+
+class RpBlock(C.Structure):
+    """bppp_rp_block (include/bppp.h): host pointers for bppp_rp_verify_block, HBM pointers for bppp_rp_verify_block_device"""
+    _fields_ = [("rows", C.c_size_t), ("coms_files", C.c_void_p), ("nproofs", C.c_size_t), ("proof_files", C.c_void_p), ("bindings", C.c_void_p),
+                ("nsums", C.c_size_t), ("sum_start", C.c_void_p), ("entries", C.c_void_p), ("nnz", C.c_size_t),
+                ("claim_amounts", C.c_void_p), ("claim_types", C.c_void_p), ("claim_offsets", C.c_void_p),
+                ("nkeys", C.c_size_t), ("key_start", C.c_void_p), ("keys", C.c_void_p), ("msgs", C.c_void_p), ("sigs", C.c_void_p),
+                ("proof_offset", C.c_uint64), ("key_offset", C.c_uint64), ("sum_offset", C.c_uint64)]
+
+
+class RpBlockStatus(C.Structure):
+    """bppp_rp_block_status: three host arrays of uint32, each may be NULL"""
+    _fields_ = [("proof_status", C.c_void_p), ("key_status", C.c_void_p), ("sum_status", C.c_void_p)]
 
 
 class BpppError(RuntimeError):
@@ -211,6 +226,8 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_excess_part_verify_device.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp]
     lib.bppp_rp_excess_part_combine.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.bppp_rp_excess_part_combine_device.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.bppp_rp_verify_block.argtypes = [vp, C.POINTER(RpBlock), vp, C.POINTER(i), C.POINTER(RpBlockStatus), vp]
+    lib.bppp_rp_verify_block_device.argtypes = [vp, C.POINTER(RpBlock), vp, C.POINTER(i), C.POINTER(RpBlockStatus), vp]
     lib.bppp_seed_candidate_x.argtypes = [C.c_char_p, sz, C.c_uint64, vp]
     lib.bppp_points_from_seed.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
     lib.bppp_points_from_seed_device.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
@@ -245,6 +262,7 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_madd29_chain.argtypes = [vp, vp, vp, sz, sz, vp, vp]
     lib.bppp_test_last_windows.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_rp_last_verify_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.bppp_test_rp_last_block_counts.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
     lib.bppp_test_rp_set_each_chunk.argtypes = [vp, sz]
     lib.bppp_test_rp_set_tally_short_max.argtypes = [vp, sz]
     lib.bppp_test_rp_set_tally_piece.argtypes = [vp, sz]

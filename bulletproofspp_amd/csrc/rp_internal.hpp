@@ -188,6 +188,9 @@ struct bppp_rp {
   void *ework = nullptr; size_t ework_bytes = 0;
   size_t each_chunk = 0;
   uint64_t n_combined = 0, n_each = 0;
+  // what the last block call on this handle launched up to its verdict (csrc/rpblock.hip; bppp_test_rp_last_block_counts): MSMs, the terms of
+  // the one MSM, keys lifted and commitments square-rooted
+  uint64_t blk_msms = 0, blk_terms = 0, blk_key_lifts = 0, blk_coms = 0;
   int last_text_kernel = -1;         // transcript text kernel of the last verification on this handle: 0 k_rp_text, 1 k_rp_text_lds (bppp_test_rp_last_text_kernel)
   // the tally entry points (csrc/rptally.hip): the longest sum one lane walks alone, the entries of one workgroup's piece of a longer sum, and
   // the entries (and sums) of one pass over the workspace; test hooks lower them so that small jobs straddle them (include/bppp_test.h)
@@ -364,6 +367,13 @@ struct Ext {
 };
 // every sum decided on its own: status [nsums] and, when not NULL, sums_xy [nsums][8], both on the host
 int each_pass(const Job &J, uint32_t *status, uint64_t *sums_xy, const Ext *ext = nullptr);
+// the two steps of batch_run's pass that assemble its MSM, for a caller that runs the MSM itself (csrc/rpblock.hip).  batch_weights: the claimed
+// scalars of sums [t0, t0 + ns) (W.in_sc, W.flag; W.any[1] for a non-canonical one), their weights W.rho at job positions j0 .. under W.seed, and the
+// three negated column sums W.sc3 (the scalars of g, H0, H1).  batch_terms: entries [e0, e0 + n) of those sums -> n scalars and points; W.any[0] is
+// raised by an entry that gathers the infinity encoding.
+int claim_scalars(const Job &J, const Work &W, size_t t0, size_t ns);
+int batch_weights(const Job &J, const Work &W, size_t t0, size_t ns, uint64_t j0);
+int batch_terms(const Job &J, const Work &W, size_t t0, size_t ns, size_t e0, size_t n, uint32_t *sc, uint32_t *pt);
 // all sums by one weighted combination per pass; status (may be NULL) by one each_pass when rejected; *accept is 0 on entry
 int batch_run(const Job &J, uint64_t index_offset, const uint8_t seed[32], int *accept, uint32_t *status, uint64_t *combined_xy, const Ext *ext = nullptr);
 }  // namespace tally

@@ -197,15 +197,20 @@ int mulcheck_launch(bppp_ctx *ctx, size_t n, const uint32_t *c, const uint32_t *
   BPPP_HIP(ctx, hipGetLastError());
   return BPPP_OK;
 }
+int batch_assemble(bppp_rp *rp, size_t n, uint64_t j0, const uint8_t *seed, const uint8_t *sigs, const uint32_t *X, const uint8_t *msgs, const uint32_t *pre, const uint32_t *c,
+                   const uint32_t *sp, const uint32_t *R, uint32_t *prods, uint32_t *red, uint32_t *sc3, uint32_t *msm_sc, uint32_t *msm_pt, uint32_t *any) {
+  bppp_ctx *ctx = rp->ctx;
+  k_rp_excess_weights<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream>>>((uint32_t)n, blind_slot(rp), j0, seed, sigs, X, msgs, pre, c, sp, R, prods, msm_sc, msm_pt, any);
+  BPPP_HIP(ctx, hipGetLastError());
+  return rpp_negated_column_sums(rp, n, prods, red, sc3);                                 // sum rho s: the scalar of B
+}
 int batch_chunk(bppp_rp *rp, size_t n, uint64_t j0, const uint8_t *seed, const uint8_t *sigs, const uint32_t *X, const uint8_t *msgs, const uint32_t *pre, const uint32_t *c,
                 const uint32_t *sp, const uint32_t *R, uint32_t *prods, uint32_t *red, uint32_t *sc3, uint32_t *msm_sc, uint32_t *msm_pt, uint32_t *any, BatchParts &parts) {
   bppp_ctx *ctx = rp->ctx;
   hipStream_t st = ctx->stream;
   const uint32_t slot = blind_slot(rp);
   int rc;
-  k_rp_excess_weights<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st>>>((uint32_t)n, slot, j0, seed, sigs, X, msgs, pre, c, sp, R, prods, msm_sc, msm_pt, any);
-  BPPP_HIP(ctx, hipGetLastError());
-  if ((rc = rpp_negated_column_sums(rp, n, prods, red, sc3))) return rc;                  // sum rho s: the scalar of B
+  if ((rc = batch_assemble(rp, n, j0, seed, sigs, X, msgs, pre, c, sp, R, prods, red, sc3, msm_sc, msm_pt, any))) return rc;
   BPPP_HIP(ctx, hipMemcpyAsync(msm_sc + 2 * n * 8, sc3, 32, hipMemcpyDeviceToDevice, st));
   BPPP_HIP(ctx, hipMemcpyAsync(msm_pt + 2 * n * 16, rp->d_basis + 16 * slot, 64, hipMemcpyDeviceToDevice, st));   // [g | H0 | H1 ...]: the registered basis starts with them
   return parts.msm(ctx, msm_sc, msm_pt, 2 * n + 1);

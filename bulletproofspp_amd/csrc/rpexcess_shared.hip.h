@@ -88,5 +88,30 @@ int mulcheck_launch(bppp_ctx *ctx, size_t n, const uint32_t *c, const uint32_t *
 int batch_chunk(bppp_rp *rp, size_t n, uint64_t j0, const uint8_t *seed, const uint8_t *sigs, const uint32_t *X, const uint8_t *msgs, const uint32_t *pre, const uint32_t *c,
                 const uint32_t *sp, const uint32_t *R, uint32_t *prods, uint32_t *red, uint32_t *sc3, uint32_t *msm_sc, uint32_t *msm_pt, uint32_t *any, BatchParts &parts);
 
+// ... and its assembly alone: everything of batch_chunk but term 2n and the MSM, for a caller that runs the MSM itself (csrc/rpblock.hip)
+int batch_assemble(bppp_rp *rp, size_t n, uint64_t j0, const uint8_t *seed, const uint8_t *sigs, const uint32_t *X, const uint8_t *msgs, const uint32_t *pre, const uint32_t *c,
+                   const uint32_t *sp, const uint32_t *R, uint32_t *prods, uint32_t *red, uint32_t *sc3, uint32_t *msm_sc, uint32_t *msm_pt, uint32_t *any);
+
 }  // namespace excess
+
+// ---- what the stated keys (csrc/rpexkeys.hip, which defines it) lend to the block call (csrc/rpblock.hip): the jobs after their checks, the stage
+// of a signature up to the verdict that needs no equation, and the two exact passes that name the culprits of a rejected job
+namespace exkeys {
+struct KeyJob { bppp_rp *rp; size_t nkeys; const uint8_t *keys, *msgs, *sigs; };
+struct KeyWork { uint32_t *sp, *P, *R, *X, *bits, *pre, *c, *status, *any, *prods, *red, *sc3, *msm_sc, *msm_pt; uint8_t *seed; };
+struct SumsJob {
+  tally::Job J;                                 // after sums_checks: h_start and nnz merged, tail = nkeys; start and entries the caller's
+  size_t nkeys = 0, nnz = 0;                    // nnz: the caller's
+  const uint8_t *keys = nullptr; const uint32_t *key_start = nullptr;
+};
+// keys per pass over the workspace: a quarter of the flat chunk
+inline size_t keys_chunk(const bppp_rp *rp, size_t n) { return std::min(n, std::max<size_t>(1, rpp_flat_chunk(rp) / 4)); }
+int key_checks(KeyJob &K, bppp_rp *rp, const char *who, size_t nkeys, const void *keys, const void *msgs, const void *sigs, bool null_args);
+// keys [o, o + n) up to the verdict that needs no equation: W.X the lifted keys, W.R, W.c, W.pre and W.sp, the scalars of s B
+int key_stage(const KeyJob &K, const KeyWork &W, size_t o, size_t n, const ExDomain &dc);
+int verify_keys_each_pass(const KeyJob &K, uint32_t *status);
+int sums_checks(SumsJob &S, bppp_rp *rp, const char *who, size_t rows, const void *coms, size_t nsums, const void *start, const void *entries, size_t nnz, const void *amt,
+                const void *ty, const void *off, size_t nkeys, const void *key_start, const void *keys, bool null_args);
+tally::Ext sums_ext(const SumsJob &S);
+}  // namespace exkeys
 }  // namespace bppp

@@ -138,11 +138,9 @@ __global__ void __launch_bounds__(256) k_rp_exsums_judge(uint32_t n, const uint3
 using namespace bppp;
 using namespace bppp::tally;
 using namespace bppp::excess;
+using namespace bppp::exkeys;
 
 namespace {
-
-// keys per pass over the workspace: a quarter of the flat chunk
-size_t keys_chunk(const bppp_rp *rp, size_t n) { return std::min(n, std::max<size_t>(1, rpp_flat_chunk(rp) / 4)); }
 
 const char *key_status_text(uint32_t s) {
   return s == BPPP_RP_EXCESS_NOT_CANONICAL ? "the blinding sum is not canonical (>= n)"
@@ -184,18 +182,7 @@ int keys_device(bppp_rp *rp, size_t nsums, const void *d_blinds, void *d_keys, u
   return rpp_report_refusals(ctx, "rp_excess_keys", "sum", h_status.data(), nsums, key_status, key_status_text);
 }
 
-// ---- signatures against stated keys: no pool, no sum stage, no inversion
-struct KeyJob { bppp_rp *rp; size_t nkeys; const uint8_t *keys, *msgs, *sigs; };
-struct KeyWork { uint32_t *sp, *P, *R, *X, *bits, *pre, *c, *status, *any, *prods, *red, *sc3, *msm_sc, *msm_pt; uint8_t *seed; };
-
-int key_checks(KeyJob &K, bppp_rp *rp, const char *who, size_t nkeys, const void *keys, const void *msgs, const void *sigs, bool null_args) {
-  bppp_ctx *ctx = rp->ctx;
-  if (nkeys > RPP_LIM31) return fail(ctx, BPPP_ERR_ARG, std::string(who) + ": nkeys must be below 2^31");
-  if (null_args || !keys || !msgs || !sigs) return fail(ctx, BPPP_ERR_ARG, std::string(who) + ": null input");
-  K.rp = rp; K.nkeys = nkeys; K.keys = (const uint8_t *)keys; K.msgs = (const uint8_t *)msgs; K.sigs = (const uint8_t *)sigs;
-  hipSetDevice(ctx->device);
-  return BPPP_OK;
-}
+// the workspace of a pass of the signatures against stated keys (KeyWork: csrc/rpexcess_shared.hip.h)
 int key_carve(bppp_rp *rp, size_t C, bool batch, KeyWork &W) {
   for (int pass = 0; pass < 2; pass++) {
     Carver cv(pass ? rp->pwork : nullptr, rp->pwork_bytes);
@@ -205,6 +192,30 @@ int key_carve(bppp_rp *rp, size_t C, bool batch, KeyWork &W) {
     W.msm_sc = cv.take<uint32_t>(batch ? (2 * C + 1) * 8 : 0); W.msm_pt = cv.take<uint32_t>(batch ? (2 * C + 1) * 16 : 0); W.seed = cv.take<uint8_t>(32);
     if (!pass) { int rc = rpp_ensure_pwork(rp, cv.off); if (rc) return rc; }
   }
+  return BPPP_OK;
+}
+
+// what the sums against stated keys keep behind the tally's workspace (SumsJob: csrc/rpexcess_shared.hip.h)
+struct SumsExtra { uint32_t *m_start, *m_entries, *keybad, *any; };
+size_t sums_carve(uint8_t *base, const SumsJob &S, SumsExtra &X) {
+  Carver cv(base, 0);
+  X.m_start = cv.take<uint32_t>(S.J.nsums + 1); X.m_entries = cv.take<uint32_t>(S.nnz + S.nkeys); X.keybad = cv.take<uint32_t>(S.J.nsums); X.any = cv.take<uint32_t>(4);
+  return cv.off;
+}
+
+}  // namespace
+
+// ---- what the block call (csrc/rpblock.hip) shares with the entry points below, declared in csrc/rpexcess_shared.hip.h
+namespace bppp {
+namespace exkeys {
+
+// ---- signatures against stated keys: no pool, no sum stage, no inversion (KeyJob, KeyWork: csrc/rpexcess_shared.hip.h)
+int key_checks(KeyJob &K, bppp_rp *rp, const char *who, size_t nkeys, const void *keys, const void *msgs, const void *sigs, bool null_args) {
+  bppp_ctx *ctx = rp->ctx;
+  if (nkeys > RPP_LIM31) return fail(ctx, BPPP_ERR_ARG, std::string(who) + ": nkeys must be below 2^31");
+  if (null_args || !keys || !msgs || !sigs) return fail(ctx, BPPP_ERR_ARG, std::string(who) + ": null input");
+  K.rp = rp; K.nkeys = nkeys; K.keys = (const uint8_t *)keys; K.msgs = (const uint8_t *)msgs; K.sigs = (const uint8_t *)sigs;
+  hipSetDevice(ctx->device);
   return BPPP_OK;
 }
 // keys [o, o + n) up to the verdict that needs no equation: W.X the lifted keys, W.R, W.c, W.pre and W.sp, the scalars of s B
@@ -237,60 +248,8 @@ int verify_keys_each_pass(const KeyJob &K, uint32_t *status) {
   return BPPP_OK;
 }
 
-int verify_keys_each_device(bppp_rp *rp, size_t nkeys, const void *d_keys, const void *d_msgs, const void *d_sigs, uint32_t *status) {
-  if (!rp) return BPPP_ERR_ARG;
-  if (ctx_closed(rp->ctx)) return BPPP_ERR_ARG;
-  if (!nkeys) return BPPP_OK;
-  KeyJob K;
-  int rc = key_checks(K, rp, "rp_excess_verify_keys_each", nkeys, d_keys, d_msgs, d_sigs, !status);
-  return rc ? rc : verify_keys_each_pass(K, status);
-}
 
-int verify_keys_batch_device(bppp_rp *rp, size_t nkeys, const void *d_keys, const void *d_msgs, const void *d_sigs, uint64_t index_offset, const uint8_t seed[32], int *accept,
-                             uint32_t *status, uint64_t *combined_xy) {
-  if (!rp || !accept) return BPPP_ERR_ARG;
-  bppp_ctx *ctx = rp->ctx;
-  if (ctx_closed(ctx)) return BPPP_ERR_ARG;
-  *accept = 0;
-  if (!nkeys) { if (combined_xy) memset(combined_xy, 0, 64); *accept = 1; return BPPP_OK; }
-  KeyJob K;
-  int rc = key_checks(K, rp, "rp_excess_verify_keys_batch", nkeys, d_keys, d_msgs, d_sigs, !seed); if (rc) return rc;
-  if (combined_xy) memset(combined_xy, 0, 64);
-  hipStream_t st = ctx->stream;
-  const size_t C = keys_chunk(rp, nkeys);
-  KeyWork W;
-  if ((rc = key_carve(rp, C, true, W))) return rc;
-  const ExDomain dc = challenge_domain(rp);
-  BPPP_HIP(ctx, hipMemcpyAsync(W.seed, seed, 32, hipMemcpyHostToDevice, st));
-  BPPP_HIP(ctx, hipMemsetAsync(W.any, 0, 16, st));
-  BatchParts parts;                             // one combined point per pass
-  for (size_t o = 0; o < nkeys; o += C) {
-    const size_t n = std::min(C, nkeys - o);
-    if ((rc = key_stage(K, W, o, n, dc))) return rc;
-    if ((rc = batch_chunk(rp, n, index_offset + o, W.seed, K.sigs + o * EX_SIG, W.X, K.msgs + o * EX_MSG, W.pre, W.c, W.sp, W.R, W.prods, W.red, W.sc3, W.msm_sc, W.msm_pt, W.any,
-                          parts))) return rc;
-  }
-  uint32_t any = 0;
-  BPPP_HIP(ctx, hipMemcpy(&any, W.any, 4, hipMemcpyDeviceToHost));
-  if ((rc = parts.finish(ctx, any != 0, combined_xy, accept))) return rc;
-  if (!status) return BPPP_OK;
-  if (*accept) { memset(status, 0, nkeys * 4); return BPPP_OK; }
-  return verify_keys_each_pass(K, status);      // one exact pass, whatever the number of bad signatures
-}
-
-// ---- sums against stated keys: the tally's two passes over the pool with the keys behind it and the merged CSR
-struct SumsJob {
-  Job J;                                        // after sums_checks: h_start and nnz merged, tail = nkeys; start and entries the caller's
-  size_t nkeys = 0, nnz = 0;                    // nnz: the caller's
-  const uint8_t *keys = nullptr; const uint32_t *key_start = nullptr;
-};
-struct SumsExtra { uint32_t *m_start, *m_entries, *keybad, *any; };
-size_t sums_carve(uint8_t *base, const SumsJob &S, SumsExtra &X) {
-  Carver cv(base, 0);
-  X.m_start = cv.take<uint32_t>(S.J.nsums + 1); X.m_entries = cv.take<uint32_t>(S.nnz + S.nkeys); X.keybad = cv.take<uint32_t>(S.J.nsums); X.any = cv.take<uint32_t>(4);
-  return cv.off;
-}
-
+// ---- sums against stated keys: the tally's two passes over the pool with the keys behind it and the merged CSR (SumsJob: csrc/rpexcess_shared.hip.h)
 // the argument checks of both calls: the sizes before anything is read, the tally's own checks over the caller's CSR and claims, then key_start by a
 // kernel whose verdict is read back before anything reads through it
 int sums_checks(SumsJob &S, bppp_rp *rp, const char *who, size_t rows, const void *coms, size_t nsums, const void *start, const void *entries, size_t nnz, const void *amt,
@@ -367,6 +326,52 @@ Ext sums_ext(const SumsJob &S) {
     return BPPP_OK;
   };
   return E;
+}
+
+}  // namespace exkeys
+}  // namespace bppp
+
+namespace {
+
+int verify_keys_each_device(bppp_rp *rp, size_t nkeys, const void *d_keys, const void *d_msgs, const void *d_sigs, uint32_t *status) {
+  if (!rp) return BPPP_ERR_ARG;
+  if (ctx_closed(rp->ctx)) return BPPP_ERR_ARG;
+  if (!nkeys) return BPPP_OK;
+  KeyJob K;
+  int rc = key_checks(K, rp, "rp_excess_verify_keys_each", nkeys, d_keys, d_msgs, d_sigs, !status);
+  return rc ? rc : verify_keys_each_pass(K, status);
+}
+
+int verify_keys_batch_device(bppp_rp *rp, size_t nkeys, const void *d_keys, const void *d_msgs, const void *d_sigs, uint64_t index_offset, const uint8_t seed[32], int *accept,
+                             uint32_t *status, uint64_t *combined_xy) {
+  if (!rp || !accept) return BPPP_ERR_ARG;
+  bppp_ctx *ctx = rp->ctx;
+  if (ctx_closed(ctx)) return BPPP_ERR_ARG;
+  *accept = 0;
+  if (!nkeys) { if (combined_xy) memset(combined_xy, 0, 64); *accept = 1; return BPPP_OK; }
+  KeyJob K;
+  int rc = key_checks(K, rp, "rp_excess_verify_keys_batch", nkeys, d_keys, d_msgs, d_sigs, !seed); if (rc) return rc;
+  if (combined_xy) memset(combined_xy, 0, 64);
+  hipStream_t st = ctx->stream;
+  const size_t C = keys_chunk(rp, nkeys);
+  KeyWork W;
+  if ((rc = key_carve(rp, C, true, W))) return rc;
+  const ExDomain dc = challenge_domain(rp);
+  BPPP_HIP(ctx, hipMemcpyAsync(W.seed, seed, 32, hipMemcpyHostToDevice, st));
+  BPPP_HIP(ctx, hipMemsetAsync(W.any, 0, 16, st));
+  BatchParts parts;                             // one combined point per pass
+  for (size_t o = 0; o < nkeys; o += C) {
+    const size_t n = std::min(C, nkeys - o);
+    if ((rc = key_stage(K, W, o, n, dc))) return rc;
+    if ((rc = batch_chunk(rp, n, index_offset + o, W.seed, K.sigs + o * EX_SIG, W.X, K.msgs + o * EX_MSG, W.pre, W.c, W.sp, W.R, W.prods, W.red, W.sc3, W.msm_sc, W.msm_pt, W.any,
+                          parts))) return rc;
+  }
+  uint32_t any = 0;
+  BPPP_HIP(ctx, hipMemcpy(&any, W.any, 4, hipMemcpyDeviceToHost));
+  if ((rc = parts.finish(ctx, any != 0, combined_xy, accept))) return rc;
+  if (!status) return BPPP_OK;
+  if (*accept) { memset(status, 0, nkeys * 4); return BPPP_OK; }
+  return verify_keys_each_pass(K, status);      // one exact pass, whatever the number of bad signatures
 }
 
 int sums_each_device(bppp_rp *rp, size_t rows, const void *d_coms, size_t nsums, const void *d_start, const void *d_entries, size_t nnz, const void *d_amt, const void *d_ty,

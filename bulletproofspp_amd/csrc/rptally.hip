@@ -373,7 +373,7 @@ namespace bppp {
 namespace tally {
 
 // sums [t0, t0 + ns): the claimed scalars in W.in_sc / W.flag, W.any[1] raised by a non-canonical one
-static int claim_scalars(const Job &J, const Work &W, size_t t0, size_t ns) {
+int claim_scalars(const Job &J, const Work &W, size_t t0, size_t ns) {
   bppp_ctx *ctx = J.rp->ctx;
   if (J.zero_claims) {
     BPPP_HIP(ctx, hipMemsetAsync(W.zero, 0, ns * 32, ctx->stream));
@@ -415,6 +415,24 @@ int each_pass(const Job &J0, uint32_t *status, uint64_t *sums_xy, const Ext *ext
   return BPPP_OK;
 }
 
+// the assembly of a pass's MSM, apart from the MSM itself (rp_internal.hpp): batch_run below queues these, and so does the block call
+// (csrc/rpblock.hip) into its own buffers
+int batch_weights(const Job &J, const Work &W, size_t t0, size_t ns, uint64_t j0) {
+  bppp_rp *rp = J.rp;
+  bppp_ctx *ctx = rp->ctx;
+  int rc;
+  if ((rc = claim_scalars(J, W, t0, ns))) return rc;
+  k_rp_tally_weights<<<dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, ctx->stream>>>((uint32_t)ns, rp->st.kind == 1, j0, W.seed, W.in_sc, W.rho, W.prods);
+  BPPP_HIP(ctx, hipGetLastError());
+  return rpp_negated_column_sums(rp, ns, W.prods, W.red, W.sc3);        // - sum rho a, - sum rho ty, - sum rho e: the scalars of g, H0, H1
+}
+int batch_terms(const Job &J, const Work &W, size_t t0, size_t ns, size_t e0, size_t n, uint32_t *sc, uint32_t *pt) {
+  bppp_ctx *ctx = J.rp->ctx;
+  if (n) k_rp_tally_terms<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream>>>((uint32_t)n, (uint32_t)e0, J.start + t0, (uint32_t)ns, J.entries, W.pool, W.rho, sc, pt, W.any);
+  BPPP_HIP(ctx, hipGetLastError());
+  return BPPP_OK;
+}
+
 // all sums by one weighted combination per pass: *accept, status (NULL, or [nsums]: one exact pass when rejected) and combined_xy (NULL or [8]), on
 // the host.  The job has passed tally_checks and *accept is 0.  ext as for each_pass.
 int batch_run(const Job &J0, uint64_t index_offset, const uint8_t seed[32], int *accept, uint32_t *status, uint64_t *combined_xy, const Ext *ext) {
@@ -437,21 +455,16 @@ int batch_run(const Job &J0, uint64_t index_offset, const uint8_t seed[32], int 
   BPPP_HIP(ctx, hipMemcpyAsync(W.seed, seed, 32, hipMemcpyHostToDevice, st));
   BPPP_HIP(ctx, hipMemsetAsync(W.any, 0, 8, st));
   BatchParts parts;                             // one combined point per MSM
-  const bool binary = rp->st.kind == 1;
   for (size_t c = 0; c + 1 < cb.size(); c++) {
     const size_t t0 = cb[c], ns = cb[c + 1] - t0;
-    if ((rc = claim_scalars(J, W, t0, ns))) return rc;
-    k_rp_tally_weights<<<dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, st>>>((uint32_t)ns, binary, index_offset + t0, W.seed, W.in_sc, W.rho, W.prods);
-    BPPP_HIP(ctx, hipGetLastError());
-    if ((rc = rpp_negated_column_sums(rp, ns, W.prods, W.red, W.sc3))) return rc;        // - sum rho a, - sum rho ty, - sum rho e: the scalars of g, H0, H1
+    if ((rc = batch_weights(J, W, t0, ns, index_offset + t0))) return rc;
     // the entries of the chunk, at most E to a MSM (a chunk of more is one long sum); the three claim terms ride with the first
     size_t e0 = J.h_start[t0];
     const size_t e1 = J.h_start[t0 + ns];
     bool first = true;
     do {
       const size_t n = std::min(E, e1 - e0);
-      if (n) k_rp_tally_terms<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>((uint32_t)n, (uint32_t)e0, J.start + t0, (uint32_t)ns, J.entries, W.pool, W.rho, W.msm_sc, W.msm_pt, W.any);
-      BPPP_HIP(ctx, hipGetLastError());
+      if ((rc = batch_terms(J, W, t0, ns, e0, n, W.msm_sc, W.msm_pt))) return rc;
       if (first) BPPP_HIP(ctx, hipMemcpyAsync(W.msm_sc + n * 8, W.sc3, 96, hipMemcpyDeviceToDevice, st));
       else BPPP_HIP(ctx, hipMemsetAsync(W.msm_sc + n * 8, 0, 96, st));
       BPPP_HIP(ctx, hipMemcpyAsync(W.msm_pt + n * 16, rp->d_basis, 3 * 64, hipMemcpyDeviceToDevice, st));   // [g | H0 | H1 ...]: the registered basis starts with them

@@ -415,6 +415,12 @@ extern "C" int bppp_test_rp_last_verify_counts(bppp_rp *rp, uint64_t *combined_m
   return BPPP_OK;
 }
 
+extern "C" int bppp_test_rp_last_block_counts(bppp_rp *rp, uint64_t *msms, uint64_t *terms, uint64_t *key_lifts, uint64_t *coms_decoded) {
+  if (!rp || !msms || !terms || !key_lifts || !coms_decoded) return BPPP_ERR_ARG;
+  *msms = rp->blk_msms; *terms = rp->blk_terms; *key_lifts = rp->blk_key_lifts; *coms_decoded = rp->blk_coms;
+  return BPPP_OK;
+}
+
 extern "C" int bppp_test_rp_set_each_chunk(bppp_rp *rp, size_t proofs) {
   if (!rp || (proofs && proofs < 8)) return BPPP_ERR_ARG;
   rp->each_chunk = proofs;

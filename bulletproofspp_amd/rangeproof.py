@@ -1487,6 +1487,80 @@ class NativeRangeProofs:
                                                                       nkeys, p(d_key_start), p(d_keys), index_offset, *a)
         return self._tally_batch(fn, nsums, seed, want_status, want_point)
 
+    # ---- a block in one call: range proofs, key signatures and sums after cut-through as ONE MSM (bppp_rp_verify_block / _device)
+    def block_arrays(self, coms_files, proof_files, sum_start, entries, claims, key_start, keys, msgs, sigs, bindings):
+        """the block's arguments as [(field of capi.RpBlock, numpy array or None)] and its sizes as a dict of RpBlock's counts: what verify_block passes
+        from the host, and what a caller uploads once to fill an RpBlock with device pointers for verify_block_call(..., device=True)"""
+        import numpy as np
+        from .capi import bindings_array
+        rows, nproofs, nkeys = len(coms_files), len(proof_files), len(keys)
+        if any(len(p) != self.shape["proof_bytes"] for p in proof_files):
+            raise ValueError("proof files of proof_bytes each are required")
+        if len(msgs) != nkeys or len(sigs) != nkeys:
+            raise ValueError("one message and one signature per key are required")
+        ss, en, nsums, nnz = self._tally_csr(sum_start if sum_start is not None else [0], entries)
+        if len(key_start) != nsums + 1:
+            raise ValueError("key_start holds nsums + 1 offsets")
+        amt, typ, off = self._tally_claim_arrays(claims, nsums)
+        arrs = [("coms_files", self._coms_array(coms_files, rows)), ("proof_files", np.frombuffer(b"".join(proof_files) or b"\0", dtype=np.uint8)),
+                ("bindings", None if bindings is None else bindings_array(bindings, nproofs)), ("sum_start", ss), ("entries", en), ("claim_amounts", amt),
+                ("claim_types", typ), ("claim_offsets", off), ("key_start", np.array(list(key_start), dtype=np.uint32)),
+                ("keys", self._excess_bytes(keys, EXCESS_KEY_BYTES, "keys")), ("msgs", self._excess_bytes(msgs, 32, "messages")),
+                ("sigs", self._excess_bytes(sigs, EXCESS_SIG_BYTES, "signatures"))]
+        return arrs, dict(rows=rows, nproofs=nproofs, nsums=nsums, nnz=nnz, nkeys=nkeys)
+
+    def verify_block_call(self, blk, seed: Optional[bytes] = None, want_status: bool = False, want_point: bool = False, device: bool = False):
+        """bppp_rp_verify_block (device: bppp_rp_verify_block_device) on a filled capi.RpBlock.  Returns accept, or (accept, (proof, key, sum
+        statuses) or None, combined point or None) when want_status / want_point is set."""
+        import ctypes as C
+        import numpy as np
+        from .capi import RpBlockStatus, array_to_point
+        if seed is None:
+            seed = os.urandom(32)
+        if len(seed) != 32:
+            raise ValueError("a 32-byte seed is required")
+        acc, sd, xy = C.c_int(0), np.frombuffer(seed, dtype=np.uint8), np.zeros(8, dtype=np.uint64)
+        sts = [np.zeros(max(n, 1), dtype=np.uint32) for n in (blk.nproofs, blk.nkeys, blk.nsums)]
+        status = RpBlockStatus(*[a.ctypes.data for a in sts])
+        fn = self.gpu.lib.bppp_rp_verify_block_device if device else self.gpu.lib.bppp_rp_verify_block
+        rc = fn(self.h, C.byref(blk), C.c_void_p(sd.ctypes.data), C.byref(acc), C.byref(status) if want_status else None, C.c_void_p(xy.ctypes.data) if want_point else None)
+        self.gpu._check(rc, "bppp_rp_verify_block")
+        if not (want_status or want_point):
+            return bool(acc.value)
+        st = tuple([int(v) for v in a[:n]] for a, n in zip(sts, (blk.nproofs, blk.nkeys, blk.nsums))) if want_status else None
+        return bool(acc.value), st, (array_to_point(xy) if want_point else None)
+
+    def verify_block(self, coms_files: Sequence[bytes], proof_files: Sequence[bytes], sum_start, entries, claims, key_start, keys: Sequence[bytes], msgs: Sequence[bytes],
+                     sigs: Sequence[bytes], bindings=None, seed: Optional[bytes] = None, offsets=(0, 0, 0), want_status: bool = False, want_point: bool = False,
+                     _device: bool = False):
+        """bppp_rp_verify_block: a block in one call and one MSM.  coms_files: the pool, its first len(proof_files) rows the outputs that carry a proof
+        (bound to `bindings` as verify_batch binds them; None: unbound); sum_start / entries / claims / key_start / keys as excess_sums_batch takes them
+        (claims (amount, type, offset) per sum); msgs / sigs: one per key, as excess_verify_keys_batch takes them; offsets: the job positions of this
+        shard's (proofs, keys, sums).  The combined point is V + K + S of the three calls under block_seeds(seed).  Returns accept, or (accept,
+        (proof statuses, key statuses, sum statuses) or None, combined point or None) when want_status / want_point is set."""
+        from .capi import RpBlock
+        arrs, n = self.block_arrays(coms_files, proof_files, sum_start, entries, claims, key_start, keys, msgs, sigs, bindings)
+        blk = RpBlock(proof_offset=offsets[0], key_offset=offsets[1], sum_offset=offsets[2], **n)
+        dev = []
+        try:
+            for name, a in arrs:
+                if a is None:
+                    continue
+                if _device:
+                    dev.append(self.gpu.to_device(a))
+                    setattr(blk, name, dev[-1])
+                else:
+                    setattr(blk, name, a.ctypes.data)
+            return self.verify_block_call(blk, seed, want_status, want_point, device=_device)
+        finally:
+            for d in dev:
+                self.gpu.free(d)
+
+    def verify_block_device(self, *args, **kwargs):
+        """bppp_rp_verify_block_device: verify_block with every buffer uploaded first (a caller whose buffers already lie in HBM fills a capi.RpBlock
+        with the device pointers and calls verify_block_call(..., device=True))"""
+        return self.verify_block(*args, _device=True, **kwargs)
+
     # ---- the multi-party signer: parties who each know a part of the blinding sum (bppp_rp_excess_part_nonces / _aggregate / _sign / _verify / _combine)
     def _excess_part_rows(self, fn, name, n, args, out_specs, want_status, status_len=None):
         """one builder call: args before the outputs; out_specs [(row bytes, rows, wanted)]; returns (outputs as row lists or None, statuses or None)"""
@@ -1813,6 +1887,13 @@ def tally_claims_host(triples: Sequence[Tuple[int, int, int]], sum_start: Sequen
 
 
 # ----------------------------------------------------------------------------- excess signatures (bppp_rp_excess_*; include/bppp.h states every message)
+def block_seeds(seed: bytes) -> Tuple[bytes, bytes, bytes]:
+    """the part seeds of bppp_rp_verify_block: SHA-256 (b"bppp block" + seed + bytes([p])) for p = 0 (proofs), 1 (signatures), 2 (sums)"""
+    if len(seed) != 32:
+        raise ValueError("a 32-byte seed is required")
+    return tuple(hashlib.sha256(b"bppp block" + seed + bytes([p])).digest() for p in range(3))
+
+
 FIELD_P = 2**256 - 2**32 - 977
 EXCESS_SIG_BYTES = 65
 EXCESS_OK, EXCESS_NOT_CANONICAL, EXCESS_ZERO, EXCESS_NONCE, EXCESS_BAD_R, EXCESS_NO_KEY = 0, 1, 2, 3, 4, 5

@@ -1053,6 +1053,67 @@ int bppp_rp_excess_part_combine_device(bppp_rp *rp, size_t nsums, size_t nparts,
                                        const void *d_partials, const void *d_msgs, void *d_sigs, void *d_agg_keys /* may be NULL */,
                                        uint32_t *status /* host, [nsums], may be NULL */);
 
+/* ---- a block in one call: range proofs, key signatures and sums after cut-through as ONE MSM --------------------------------------------
+ * A node that receives a block checks the range proofs of its new outputs (bppp_rp_verify_bound), the kernel signatures against their
+ * stated keys (bppp_rp_excess_verify_keys_batch) and the balance after cut-through (bppp_rp_excess_sums_batch).  bppp_rp_verify_block runs the
+ * three as one weighted combination: one MSM of
+ *   T = 1 + llen + nlen + nproofs (ninit + 2k) + nnz + 2 nkeys
+ * terms  [ g | H | G | per-proof terms | entry terms | per key: X_k, R_k ]  instead of three MSMs of nkeys + 4 terms more.  Up to the verdict
+ * every key is lifted once and the commitments of the proven rows are square-rooted once; the status passes of a REJECTED block are the
+ * counterparts' own and lift what they need again (the keys once more for key_status and once more for sum_status).
+ *
+ * bppp_rp_block, all of one handle (typed-reciprocal or binary, either argument flavour):
+ *   POOL        rows, coms_files [rows][coms_bytes] as bppp_rp_tally_each takes them; rows [0, nproofs) are the outputs that carry a proof
+ *   PROOFS      nproofs <= rows, proof_files [nproofs][proof_bytes] (NULL allowed when nproofs == 0), bindings [nproofs][32] or NULL (an
+ *               unbound call) as bppp_rp_verify_bound takes them.  The proofs verify under the handle's own public amounts.
+ *   SUMS        nsums, sum_start, entries, nnz, claim_amounts, claim_types, claim_offsets, nkeys, key_start, keys [nkeys][33] exactly as
+ *               bppp_rp_excess_sums_batch takes them
+ *   SIGNATURES  msgs [nkeys][32], sigs [nkeys][65]: one per key, as bppp_rp_excess_verify_keys_batch takes them
+ *   OFFSETS     proof_offset, key_offset, sum_offset: the job positions of this shard's proofs, keys and sums (0 for a whole block)
+ * bppp_rp_verify_block takes host pointers in the struct, bppp_rp_verify_block_device HBM pointers; seed, accept, the status arrays and
+ * combined_xy are host memory in both.
+ *
+ * Part seeds: seed_p = SHA-256 ("bppp block" (10 bytes) || seed[32] || byte p), a message of 43 bytes, with p = 0 for the proofs, 1 for the
+ * signatures, 2 for the sums; derived on the host.  The three weight families of the counterpart calls hash messages of different layouts;
+ * under separate sub-seeds their independence needs no argument about message lengths.
+ * Combined point: combined = V + K + S, where V is the combined_xy of bppp_rp_verify_bound_device over rows [0, nproofs) with index_offset =
+ * proof_offset, public_amounts = NULL and seed_0; K that of bppp_rp_excess_verify_keys_batch_device with index_offset = key_offset and seed_1;
+ * S that of bppp_rp_excess_sums_batch_device with index_offset = sum_offset and seed_2.  Every weight, challenge and scalar is the counterpart's
+ * own formula; key k of sum t carries the ONE scalar  n - rho^K_k c_k - rho^S_t  (mod n)  on X_k.  The point is defined by the formula only when
+ * nothing is malformed or non-canonical, as the counterparts say.
+ * *accept = 1 iff every proof decodes, no referenced commitment is malformed, no key has a verdict other than OK or MISMATCH, no claim is
+ * non-canonical, and combined is the identity.
+ * Status (bppp_rp_block_status, host arrays, each may be NULL, as may the struct): proof_status [nproofs], key_status [nkeys], sum_status
+ * [nsums].  On acceptance every array given is filled with VALID / OK (zeros).  On rejection each array given receives exactly what the
+ * counterpart reports over the same inputs: proof_status by the handle's culprit search (bisection, or one per-proof pass under
+ * BPPP_RP_OPT_CULPRITS = 1), key_status by one pass of bppp_rp_excess_verify_keys_each, sum_status by one pass of bppp_rp_excess_sums_each.  A
+ * rejected combined point does not say which part failed, so all the arrays asked for are computed.
+ * Sharding: ranks pass the same seed, their own slices (rows and entries re-indexed per shard) and offsets; their points add up with
+ * bppp_sum_points to the one-call point.
+ * Empty parts: any part may be empty and its term of the formula is then the identity; with nsums == 0 the keys belong to no sum and only their
+ * signatures are checked.  All three empty returns BPPP_OK with *accept = 1 and looks at nothing else.
+ * BPPP_ERR_ARG (bppp_last_error names the offender; no output buffer is written on an error): the errors of the three counterparts, under the name
+ * rp_verify_block; nproofs > rows; the tag limit of the bound calls when bindings are given; rows * nranges + nkeys, nnz + nkeys or nsums at
+ * or above 2^31; nproofs >= 2^22; and a block that does not fit ONE pass of the handle's limits (nnz + nkeys or nsums above the tally's chunk,
+ * nkeys above a quarter of the flat chunk): the block call is one MSM by contract, the text names the limit and says "shard it", and the offsets
+ * are the route to larger jobs.  sum_start, entries and key_start are validated by kernels whose verdict is read back before anything reads
+ * through the arrays. */
+typedef struct bppp_rp_block {
+  size_t rows;    const void *coms_files;                 /* [rows][coms_bytes] */
+  size_t nproofs; const void *proof_files;                /* [nproofs][proof_bytes]; NULL ok when nproofs == 0 */
+  const void *bindings;                                   /* [nproofs][32] or NULL (unbound) */
+  size_t nsums; const void *sum_start, *entries; size_t nnz;
+  const void *claim_amounts, *claim_types, *claim_offsets;
+  size_t nkeys; const void *key_start, *keys;             /* [nsums + 1], [nkeys][33] */
+  const void *msgs, *sigs;                                /* [nkeys][32], [nkeys][65] */
+  uint64_t proof_offset, key_offset, sum_offset;
+} bppp_rp_block;
+typedef struct bppp_rp_block_status { uint32_t *proof_status, *key_status, *sum_status; } bppp_rp_block_status;  /* host; each may be NULL */
+int bppp_rp_verify_block(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t seed[32], int *accept, const bppp_rp_block_status *status /* may be NULL */,
+                         uint64_t *combined_xy /* may be NULL */);
+int bppp_rp_verify_block_device(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t seed[32], int *accept, const bppp_rp_block_status *status /* may be NULL */,
+                                uint64_t *combined_xy /* may be NULL */);
+
 /* ---- one comb table for the handles of a basis family --------------------------------------------------------------------------
  * Every setup's basis [g | H | G] is a prefix of the point stream its points came from (see bppp_rp_verify_mixed), and the comb table
  * is laid out tab[window][point][multiple]: the table of the longest basis of a stream contains the table of every shorter one (same

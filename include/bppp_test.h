@@ -76,6 +76,11 @@ int bppp_test_last_windows(bppp_ctx *ctx, int *windows);
  * bppp_rp_verify_mixed*): combined MSMs (the accept check and every bisection step) and per-proof passes.  A test sees the cost of a
  * culprit search without timing it. */
 int bppp_test_rp_last_verify_counts(bppp_rp *rp, uint64_t *combined_msms, uint64_t *each_passes);
+/* What the last bppp_rp_verify_block* on this handle launched up to its verdict (the status passes of a rejected block are not counted): MSMs, the
+ * terms of the one MSM, keys lifted (one lift per key: the signatures' stage serves the sums) and commitments square-rooted (rows * nranges: the
+ * proven rows are taken from the verifier's decoder).  All zero after an empty block; a call refused with an argument error leaves them, and the
+ * counts of bppp_test_rp_last_verify_counts, as they were. */
+int bppp_test_rp_last_block_counts(bppp_rp *rp, uint64_t *msms, uint64_t *terms, uint64_t *key_lifts, uint64_t *coms_decoded);
 /* Proofs per chunk of the per-proof pass on this handle (0 = from the row budget, the default): a test crosses a chunk boundary
  * with a small batch. */
 int bppp_test_rp_set_each_chunk(bppp_rp *rp, size_t proofs);
