@@ -253,7 +253,6 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_point_chain.argtypes = [vp, i, vp, vp, sz, vp, vp]
     lib.bppp_test_mulmod_rate.argtypes = [vp, i, C.POINTER(C.c_double)]
     lib.bppp_test_last_mixed_msm_terms.argtypes = [vp, C.POINTER(C.c_uint64)]
-    lib.bppp_test_last_acc_kernel.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_last_sort_ranges.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_last_scatter_one_read.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_last_acc_sized.argtypes = [vp, C.POINTER(C.c_int)]

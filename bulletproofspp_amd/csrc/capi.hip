@@ -36,18 +36,31 @@ void ctx_release(bppp_ctx *ctx) {
   delete ctx;
 }
 }  // namespace bppp
+// the three forms of a tuning variable: an integer if set, a switch that is on unless set to 0 (or the other way round), a flag if present
+static int env_int(const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; }
+static int env_switch(const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) != 0 : unset; }
+static bool env_flag(const char *name) { return getenv(name) != nullptr; }
 void MsmTune::from_env() {
-  auto geti = [](const char *n) { const char *e = getenv(n); return e ? atoi(e) : 0; };
   if (const char *e = getenv("BPPP_GCOST")) gcost = atof(e);
-  cmin = geti("BPPP_CMIN"); lw = geti("BPPP_LW"); rg = geti("BPPP_RG"); marg_s = geti("BPPP_MARG_S"); lacc = geti("BPPP_LACC");
-  window_batched = geti("BPPP_WINDOW_BATCHED"); comb_wpe = geti("BPPP_COMB_WPE"); comb_rows_waves = geti("BPPP_COMB_ROWS_WAVES"); reduce_old = getenv("BPPP_REDUCE_OLD") != nullptr;
-  small_c = geti("BPPP_MSM_SMALL_C"); small_len = geti("BPPP_MSM_SMALL_LEN"); small_max = geti("BPPP_MSM_SMALL_MAX"); hist_ch = geti("BPPP_HIST_CH"); no_small = getenv("BPPP_MSM_NO_SMALL") != nullptr; if (getenv("BPPP_COMB_ROWS_MIN_MB")) comb_rows_min_bytes = (size_t)strtoull(getenv("BPPP_COMB_ROWS_MIN_MB"), nullptr, 10) << 20; no_balance = getenv("BPPP_MSM_NO_BALANCE") != nullptr;
-  tail_scalar = getenv("BPPP_REDUCE_TAIL_SCALAR") != nullptr;     // k_reduce_tail (one lane per element) instead of k_reduce_tail_quad
-  if (const char *e = getenv("BPPP_SORT_RANGES")) sort_ranges = atoi(e);   // 0 k_scatter, 2 / 4 k_scatter_ranges with that many bucket ranges per window
-  if (const char *e = getenv("BPPP_SCATTER_ONE_READ")) scatter_one_read = atoi(e) != 0;   // 0: k_scatter_ranges whatever the chunk length; else k_scatter_one_read where the plan allows it (the default)
-  if (const char *e = getenv("BPPP_ACC_SIZED")) acc_sized = atoi(e) != 0;   // 1 / 0: k_acc_points_sized for every / no MSM over arbitrary points; unset: make_plan's default
-  if (const char *e = getenv("BPPP_ACC_FQ29")) acc_fq29 = atoi(e) != 0;   // 1 / 0: k_acc_points_sized29 (9 x 29-bit limbs) for every / no sized accumulation
-  if (const char *e = getenv("BPPP_ACC_LDS")) acc_lds = atoi(e) != 0;   // k_acc_points_lds (next point prefetched into LDS) instead of k_acc_points
+  cmin = env_int("BPPP_CMIN", 0);
+  lw = env_int("BPPP_LW", 0);
+  rg = env_int("BPPP_RG", 0);
+  marg_s = env_int("BPPP_MARG_S", 0);
+  lacc = env_int("BPPP_LACC", 0);
+  window_batched = env_int("BPPP_WINDOW_BATCHED", 0);
+  comb_wpe = env_int("BPPP_COMB_WPE", 0);
+  comb_rows_waves = env_int("BPPP_COMB_ROWS_WAVES", 0);
+  if (const char *e = getenv("BPPP_COMB_ROWS_MIN_MB")) comb_rows_min_bytes = (size_t)strtoull(e, nullptr, 10) << 20;
+  small_c = env_int("BPPP_MSM_SMALL_C", 0);
+  small_len = env_int("BPPP_MSM_SMALL_LEN", 0);
+  small_max = env_int("BPPP_MSM_SMALL_MAX", 0);
+  hist_ch = env_int("BPPP_HIST_CH", 0);
+  no_small = env_flag("BPPP_MSM_NO_SMALL");
+  no_balance = env_flag("BPPP_MSM_NO_BALANCE");
+  sort_ranges = env_int("BPPP_SORT_RANGES", sort_ranges);                      // 0 k_scatter, 2 / 4 k_scatter_ranges with that many bucket ranges per window
+  scatter_one_read = env_switch("BPPP_SCATTER_ONE_READ", scatter_one_read);   // 0: k_scatter_ranges whatever the chunk length; else k_scatter_one_read where the plan allows it (the default)
+  acc_sized = env_switch("BPPP_ACC_SIZED", acc_sized);                         // 1 / 0: k_acc_points_sized for every / no MSM over arbitrary points; unset: plan_accumulate's default
+  acc_fq29 = env_switch("BPPP_ACC_FQ29", acc_fq29);                            // 1 / 0: k_acc_points_sized29 (9 x 29-bit limbs) for every / no sized accumulation
 }
 namespace bppp {
 int ctx_aux(bppp_ctx *ctx) {

@@ -6,13 +6,7 @@
 #include <string>
 #include <vector>
 #include "../../include/bppp.h"
-
-// Tuning overrides of the MSM plan (benchmarks/sweep_window.py and friends): the BPPP_* environment is read ONCE, when the context is
-// created; 0 / false = the library's heuristic.  No entry point reads the environment per call.
-struct MsmTune {
-  double gcost = 0; int cmin = 0, lw = 0, rg = 0, marg_s = 0, lacc = 0, window_batched = 0, comb_wpe = 0, small_c = 0, small_len = 0, small_max = 0, hist_ch = 0, num_cus = 0, sort_ranges = 4 /* bucket ranges per window of the ranged scatter, BPPP_SORT_RANGES: 0 = k_scatter */, scatter_one_read = 1 /* the ranged scatter reads a chunk's digits once for all ranges (k_scatter_one_read), BPPP_SCATTER_ONE_READ: 0 = k_scatter_ranges always */, acc_sized = -1 /* whole buckets by size (k_acc_points_sized), BPPP_ACC_SIZED: 1 = every one-MSM plan, 0 = none, -1 = the plans where it measured faster (make_plan) */, acc_fq29 = 1 /* the sized accumulation on 9 x 29-bit limbs (k_acc_points_sized29), BPPP_ACC_FQ29: not 0 = every sized plan (the default, by measurement: DESIGN.md 0.2), 0 = k_acc_points_sized on 10 x 26 */; bool reduce_old = false, no_small = false, no_balance = false, tail_scalar = false, acc_lds = false; size_t comb_rows_min_bytes = (size_t)4 << 30; int comb_rows_waves = 0;
-  void from_env();
-};
+#include "msm_plan.hpp"   // MsmTune, Carver
 
 // What the last comb_msm launch on a context did (csrc/comb.hip.h; read by bppp_test_last_comb_msm): the kernel it took and how it split the work
 struct CombLast {
@@ -62,7 +56,6 @@ struct bppp_ctx {
   void *mix = nullptr;
   size_t mix_bytes = 0;
   uint64_t last_mixed_terms = 0;     // terms of the last multi-setup MSM (bppp_test_last_mixed_msm_terms)
-  int last_acc_lds = -1;             // accumulate kernel of the last general-pipeline MSM: 0 k_acc_points, 1 k_acc_points_lds (bppp_test_last_acc_kernel)
   int last_sort_ranges = -1;         // bucket ranges Q of the last general-pipeline MSM's scatter: 0 k_scatter, 2 / 4 k_scatter_ranges (bppp_test_last_sort_ranges)
   int last_scatter_one_read = -1;    // 1: the last general-pipeline MSM's scatter was k_scatter_one_read, 0: any other (bppp_test_last_scatter_one_read)
   int last_acc_sized = -1;           // 1: the last general-pipeline MSM accumulated whole buckets by size (k_order, k_acc_points_sized), 0: slices (bppp_test_last_acc_sized)
@@ -84,18 +77,6 @@ inline int fail(bppp_ctx *ctx, int code, const std::string &msg) {
     if (_e != hipSuccess)                                                                      \
       return bppp::fail(ctx, BPPP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
   } while (0)
-
-// bump allocator over the context workspace
-struct Carver {
-  char *base; size_t off = 0, cap;
-  Carver(void *b, size_t c) : base((char *)b), cap(c) {}
-  template <typename T> T *take(size_t count) {
-    size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
-    T *p = (T *)(base ? base + off : nullptr);
-    off += bytes;
-    return p;
-  }
-};
 
 void ctx_retain(bppp_ctx *ctx);
 void ctx_release(bppp_ctx *ctx);          // the last release tears the context down

@@ -23,12 +23,15 @@
 //                    of size so that the lanes of a wavefront run equally long: no boundary logic in the loop, no
 //                    partial sums unless the scalars are skewed.  k_acc_points_sized29 (MsmTune::acc_fq29, the default) is the same
 //                    kernel with the accumulator in 9 x 29-bit limbs (fq29.hip.h): 81 partial products per multiplication, not 100.
-//   4. k_reduce_marg / k_reduce_tail_quad (k_reduce_tail: the one-lane form, MsmTune::tail_scalar)
+//   4. k_reduce_marg / k_reduce_tail_quad
 //                    sum_m m*B_m per window by MARGINAL SUMS (m = LO*hi + lo: plain row and column sums, every lane busy,
 //                    then two short weighted sums); k_reduce1/2 (per-lane running sums + wavefront suffix scans) for windows
 //                    under 256 buckets, k_reduce_groups for thousands of small windows.
 //   5. window combine: Horner over <= 65 window sums — on the host for one MSM (a 256-doubling
 //                    dependency chain), in k_window_combine for batches.
+//
+// The plan of a call (window layout, chunk counts, kernel forms, reduction geometry) and the layout of its workspace are plain host code in
+// msm_plan.hpp; this file holds the kernels and, at the end, the stages that launch them.
 //
 // Integer / carry-chain work on the VALU; nothing here is a dense contraction, so no MFMA.
 #include <algorithm>
@@ -43,6 +46,8 @@
 
 namespace bppp {
 
+static_assert(MSM_XYZZ_WORDS == XYZZ_WORDS, "msm_plan.hpp sizes the workspace by the stored point of ec.hip.h");
+static_assert(sizeof(MsmPair) == sizeof(uint2) && sizeof(MsmQuad) == sizeof(uint4) && alignof(MsmQuad) == alignof(uint4), "the workspace's pairs and quadruples are the kernels' uint2 / uint4");
 
 // ------------------------------------------------------------------------------------------------
 // 1. digits
@@ -119,7 +124,6 @@ __global__ void k_hist(const uint16_t *__restrict__ dig, uint32_t n, uint32_t st
 // Those reads grow as ntiles^2 / 2 words: 9 K at 2^20 terms (136 tiles), 0.8 M at the largest batched shapes in use (~1300 tiles).  A plan
 // may reach 2^32 buckets only on paper — the bucket array alone is 160 B each, so 288 GB of HBM hold under 2^31 / 4096 = 2^19 tiles, and
 // anything near that is seconds of accumulation; at 2^27 buckets (21 GB, 32 K tiles) it is 2 GB of L2 reads, about a millisecond.
-static constexpr int SCAN_TILE = 4096;
 __global__ void __launch_bounds__(256) k_count_tiles(uint32_t *__restrict__ blockhist, int M, int CH, uint64_t FB, uint32_t *__restrict__ count,
                                                      uint32_t *__restrict__ tile_sums) {
   __shared__ uint32_t ws[4];
@@ -143,8 +147,7 @@ __global__ void __launch_bounds__(256) k_count_tiles(uint32_t *__restrict__ bloc
 // An ITEM of the sized accumulation (section 3'): a bucket of at most ACC_CAP entries, or a piece of ACC_CAP entries (the last one: the rest) of
 // a larger one.  size_hist (the sized route only, else null; zero at launch: k_digits) counts the items by size: the tile's histogram in LDS,
 // then one global atomic per non-empty bin.  Bin size - 1 is the word (size - 1) * ACC_LINE: a bin has a 128-byte line to itself, so that the
-// atomics of different bins do not queue on one line.
-static constexpr uint32_t ACC_CAP = 128, ACC_LINE = 32;
+// atomics of different bins do not queue on one line.  (SCAN_TILE, ACC_CAP, ACC_LINE: msm_plan.hpp)
 __global__ void __launch_bounds__(256) k_scan_apply(const uint32_t *__restrict__ in, uint64_t n, const uint32_t *__restrict__ tile_sums,
                                                     uint32_t *__restrict__ out, uint32_t *__restrict__ size_hist) {
   // the tile's offset, then a block-level exclusive scan of the tile (16 per thread); the last lane of the last tile writes the total out[n]
@@ -250,7 +253,7 @@ __global__ void k_scatter(const uint16_t *__restrict__ dig, const unsigned long 
 // 4-MiB L2 until the lines are full.  That is placement for speed only — any dispatch order and any block -> XCD map give the same `sorted`
 // positions; no workgroup waits for another.  The digit row is read Q times, once per range (non-temporal: it should not push the output lines
 // out): a quarter of this launch's traffic at Q = 4, which is what k_scatter_one_read saves where the chunk is short enough.
-// ONE workgroup per CU (the launch asks for more than half of a CU's LDS, msm_run_ex): a unit's chunks then fill the XCD and one unit is live per
+// ONE workgroup per CU (the launch asks for more than half of a CU's LDS, ranges_lds_bytes): a unit's chunks then fill the XCD and one unit is live per
 // L2.  With two workgroups per CU (64 VGPRs allow it) two units are live, the lines leave the L2 half full (WRITE_SIZE 109 -> 215 MB at 2^20
 // terms) and the kernel is slower, loads ahead or not.  So the latency of a workgroup's chain is hidden inside the lane instead:
 // the digits and sign bytes of its first SCATTER_AHEAD steps are requested BEFORE the cursors, all cursor loads before the first LDS write, and
@@ -259,7 +262,55 @@ __global__ void k_scatter(const uint16_t *__restrict__ dig, const unsigned long 
 // which every row has, and drops them.  A load under a branch would do, but its result then meets the other path's value in a register copy, and
 // the compiler waits for the load right there.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-static constexpr int SCATTER_AHEAD = 4;                     // 2^20 terms in 32 chunks of 1024 lanes: 4 steps, all in flight at once
+// The three steps that k_scatter_ranges and k_scatter_one_read share (SCATTER_AHEAD: msm_plan.hpp).
+// Prefetch: the digit packs and sign bytes of the lane's steps j0, j0 + step, ... of the row d; a step past the chunk's end reads the row's
+// first 16 bytes (and mask byte 0), dropped at the placement.
+BPPP_DI void scatter_prefetch(const uint16_t *__restrict__ d, const uint8_t *__restrict__ sgn, uint32_t j0, uint32_t step, uint32_t hi,
+                              u32x4 (&pk)[SCATTER_AHEAD], uint32_t (&sneg8)[SCATTER_AHEAD]) {
+#pragma unroll
+  for (int i = 0; i < SCATTER_AHEAD; i++) {
+    const uint32_t j = j0 + (uint32_t)i * step, ja = j < hi ? j : 0u;
+    pk[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(d + ja)); sneg8[i] = sgn[ja >> 3];
+  }
+}
+// Cursors of the buckets [r0, r0 + count) of a (window, chunk) into lh[0, count): bh_row and st_row are the chunk's histogram row and the
+// window's start row.  Four buckets per load (r0 and count are multiples of 4 and the arrays 16-byte aligned), four pairs of loads per lane
+// and round of the loop, all in flight before the first sum is written to LDS.
+BPPP_DI void scatter_load_cursors(const uint32_t *__restrict__ bh_row, const uint32_t *__restrict__ st_row, uint32_t r0, uint32_t count, uint32_t *lh) {
+  const uint4 *bh = reinterpret_cast<const uint4 *>(bh_row + r0);
+  const uint4 *st = reinterpret_cast<const uint4 *>(st_row + r0);
+  const uint32_t nq = count >> 2;
+  for (uint32_t t0 = threadIdx.x; t0 < nq; t0 += 4 * blockDim.x) {
+    uint4 a[4], b[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const uint32_t t = t0 + i * blockDim.x;
+      a[i] = b[i] = make_uint4(0u, 0u, 0u, 0u);
+      if (t < nq) { a[i] = st[t]; b[i] = bh[t]; }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const uint32_t t = t0 + i * blockDim.x;
+      if (t < nq) { lh[4 * t] = a[i].x + b[i].x; lh[4 * t + 1] = a[i].y + b[i].y; lh[4 * t + 2] = a[i].z + b[i].z; lh[4 * t + 3] = a[i].w + b[i].w; }
+    }
+  }
+}
+// Placement: the entries of the pack of step j (digits pkv, sign byte sn) whose bucket lies in [r0, r0 + Mq); lh[b - b0] is bucket b's cursor
+// (b0 = r0 where LDS holds the range alone, 0 where it holds the window).
+BPPP_DI void scatter_place(const u32x4 pkv, uint32_t sn, uint32_t j, uint32_t hi, uint32_t M, uint32_t r0, uint32_t Mq, uint32_t flip, uint32_t *lh, uint32_t b0,
+                           uint32_t *__restrict__ sorted) {
+  const uint32_t w[4] = {pkv.x, pkv.y, pkv.z, pkv.w};
+#pragma unroll
+  for (int e = 0; e < 8; e++) {
+    int v = (int)((w[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu) - (int)M;
+    uint32_t mb = (uint32_t)(v < 0 ? -v : v) - 1u;            // v == 0: wraps past every range
+    if (j + e < hi && v && mb - r0 < Mq) {
+      uint32_t sg = (v < 0 ? 1u : 0u) ^ ((sn >> e) & 1u) ^ flip;
+      uint32_t pos = atomicAdd(&lh[mb - b0], 1u);
+      sorted[pos] = (sg << 31) | (j + e);
+    }
+  }
+}
 __global__ void __launch_bounds__(1024) k_scatter_ranges(const uint16_t *__restrict__ dig, const unsigned long long *__restrict__ negmask, uint32_t n,
                                                          uint32_t stride, int c, int CH, int Q, uint32_t U, int top,
                                                          const uint32_t *__restrict__ blockhist, const uint32_t *__restrict__ start,
@@ -279,49 +330,21 @@ __global__ void __launch_bounds__(1024) k_scatter_ranges(const uint16_t *__restr
   uint32_t j0 = lo + threadIdx.x * 8;
   u32x4 pk[SCATTER_AHEAD];
   uint32_t sneg8[SCATTER_AHEAD];
-#pragma unroll
-  for (int i = 0; i < SCATTER_AHEAD; i++) {
-    const uint32_t j = j0 + (uint32_t)i * step, ja = j < hi ? j : 0u;
-    pk[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(d + ja)); sneg8[i] = sgn[ja >> 3];
-  }
-  // cursors, four buckets per load (M = 2^15, Q <= 4 and the 16-byte aligned arrays: r0 and Mq are multiples of 4): all of a lane's loads
-  // (Mq / 4096 pairs, two at Q = 4) are in flight before the first sum is written to LDS
-  const uint4 *bh = reinterpret_cast<const uint4 *>(blockhist + ((size_t)nbw * CH + ch) * M + r0);
-  const uint4 *st = reinterpret_cast<const uint4 *>(start + (size_t)nbw * M + r0);
-  const uint32_t nq = Mq >> 2;
-  for (uint32_t t0 = threadIdx.x; t0 < nq; t0 += 4 * blockDim.x) {
-    uint4 a[4], b[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const uint32_t t = t0 + i * blockDim.x;
-      a[i] = b[i] = make_uint4(0u, 0u, 0u, 0u);
-      if (t < nq) { a[i] = st[t]; b[i] = bh[t]; }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const uint32_t t = t0 + i * blockDim.x;
-      if (t < nq) { lh[4 * t] = a[i].x + b[i].x; lh[4 * t + 1] = a[i].y + b[i].y; lh[4 * t + 2] = a[i].z + b[i].z; lh[4 * t + 3] = a[i].w + b[i].w; }
-    }
-  }
+  scatter_prefetch(d, sgn, j0, step, hi, pk, sneg8);
+  // cursors of the range (M = 2^15, Q <= 4: r0 and Mq are multiples of 4): all of a lane's loads (Mq / 4096 pairs, two at Q = 4) are in
+  // flight before the first sum is written to LDS
+  scatter_load_cursors(blockhist + ((size_t)nbw * CH + ch) * M, start + (size_t)nbw * M, r0, Mq, lh);
   __syncthreads();
   for (; j0 < hi; j0 += SCATTER_AHEAD * step) {
 #pragma unroll
     for (int i = 0; i < SCATTER_AHEAD; i++) {
       const uint32_t j = j0 + (uint32_t)i * step;
       if (j < hi) {
-        const uint32_t w[4] = {pk[i].x, pk[i].y, pk[i].z, pk[i].w}, sn = sneg8[i];
+        const u32x4 pkv = pk[i];
+        const uint32_t sn = sneg8[i];
         const uint32_t jn = j + SCATTER_AHEAD * step, ja = jn < hi ? jn : 0u;
         pk[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(d + ja)); sneg8[i] = sgn[ja >> 3];
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-          int v = (int)((w[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu) - (int)M;
-          uint32_t mb = (uint32_t)(v < 0 ? -v : v) - 1u - r0;   // v == 0: wraps past Mq
-          if (j + e < hi && v && mb < Mq) {
-            uint32_t sg = (v < 0 ? 1u : 0u) ^ ((sn >> e) & 1u) ^ flip;
-            uint32_t pos = atomicAdd(&lh[mb], 1u);
-            sorted[pos] = (sg << 31) | (j + e);
-          }
-        }
+        scatter_place(pkv, sn, j, hi, M, r0, Mq, flip, lh, r0, sorted);
       }
     }
   }
@@ -352,49 +375,16 @@ __global__ void __launch_bounds__(1024) k_scatter_one_read(const uint16_t *__res
   const uint32_t step = blockDim.x * 8, j0 = lo + threadIdx.x * 8;
   u32x4 pk[SCATTER_AHEAD];
   uint32_t sneg8[SCATTER_AHEAD];
-#pragma unroll
-  for (int i = 0; i < SCATTER_AHEAD; i++) {
-    const uint32_t j = j0 + (uint32_t)i * step, ja = j < hi ? j : 0u;   // past the chunk's end: the row's first 16 bytes, dropped below
-    pk[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(d + ja)); sneg8[i] = sgn[ja >> 3];
-  }
-  // cursors of the whole window, four buckets per load (M is a multiple of 4 and the arrays are 16-byte aligned), four pairs of loads per
-  // lane and round of the loop
-  const uint4 *bh = reinterpret_cast<const uint4 *>(blockhist + ((size_t)nbw * CH + ch) * M);
-  const uint4 *st = reinterpret_cast<const uint4 *>(start + (size_t)nbw * M);
-  const uint32_t nq = M >> 2;
-  for (uint32_t t0 = threadIdx.x; t0 < nq; t0 += 4 * blockDim.x) {
-    uint4 a[4], b[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const uint32_t t = t0 + i * blockDim.x;
-      a[i] = b[i] = make_uint4(0u, 0u, 0u, 0u);
-      if (t < nq) { a[i] = st[t]; b[i] = bh[t]; }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const uint32_t t = t0 + i * blockDim.x;
-      if (t < nq) { lh[4 * t] = a[i].x + b[i].x; lh[4 * t + 1] = a[i].y + b[i].y; lh[4 * t + 2] = a[i].z + b[i].z; lh[4 * t + 3] = a[i].w + b[i].w; }
-    }
-  }
+  scatter_prefetch(d, sgn, j0, step, hi, pk, sneg8);
+  // cursors of the whole window (M is a multiple of 4)
+  scatter_load_cursors(blockhist + ((size_t)nbw * CH + ch) * M, start + (size_t)nbw * M, 0u, M, lh);
   __syncthreads();
   const uint32_t Mq = M / (uint32_t)Q;
   for (uint32_t r0 = 0; r0 < M; r0 += Mq) {
 #pragma unroll
     for (int i = 0; i < SCATTER_AHEAD; i++) {
       const uint32_t j = j0 + (uint32_t)i * step;
-      if (j < hi) {
-        const uint32_t w[4] = {pk[i].x, pk[i].y, pk[i].z, pk[i].w}, sn = sneg8[i];
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-          int v = (int)((w[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu) - (int)M;
-          uint32_t mb = (uint32_t)(v < 0 ? -v : v) - 1u;        // v == 0: wraps past every range
-          if (j + e < hi && v && mb - r0 < Mq) {
-            uint32_t sg = (v < 0 ? 1u : 0u) ^ ((sn >> e) & 1u) ^ flip;
-            uint32_t pos = atomicAdd(&lh[mb], 1u);
-            sorted[pos] = (sg << 31) | (j + e);
-          }
-        }
-      }
+      if (j < hi) scatter_place(pk[i], sneg8[i], j, hi, M, r0, Mq, flip, lh, 0u, sorted);
     }
     __syncthreads();                                        // the workgroup's wavefronts move to the next range together (see above)
   }
@@ -459,12 +449,17 @@ __global__ void __launch_bounds__(256) k_acc_points(const uint32_t *__restrict__
   else xyzz_store(buckets + (size_t)cur * XYZZ_WORDS, acc);
 }
 
-static constexpr int MERGE_SERIAL_MAX = 8;   // longer spans go to the wavefront-cooperative kernels
-static constexpr int HEAVY_CHUNK = 256;      // partial sums per wavefront in k_merge_heavy
-
 // partial t of a bucket whose first lane is g0: t = 0 is g0's tail slot, t >= 1 the head slot of lane g0+t
 BPPP_DI const uint32_t *partial_ptr(const uint32_t *rec_pt, uint64_t g0, uint64_t t) {
   return rec_pt + (t == 0 ? 2 * g0 + 1 : 2 * (g0 + t)) * XYZZ_WORDS;
+}
+// hand bucket fb with np partial sums to k_merge_heavy, HEAVY_CHUNK partials per wavefront: its (bucket, chunk) items are drawn from ctr[0]
+// and, when there are several, the bucket gets an entry of heavy_buckets (drawn from ctr[1]) on which the chunks draw their tickets
+BPPP_DI void heavy_register(uint32_t fb, uint32_t np, uint2 *heavy_items, uint32_t *heavy_slot, uint4 *heavy_buckets, uint32_t *ctr) {
+  const uint32_t nch = (np + HEAVY_CHUNK - 1) / HEAVY_CHUNK;
+  uint32_t base = atomicAdd(&ctr[0], nch), hb = 0;
+  if (nch > 1) { hb = atomicAdd(&ctr[1], 1u); heavy_buckets[hb] = make_uint4(fb, base, nch, 0u); }   // .w: the chunks' ticket
+  for (uint32_t j = 0; j < nch; j++) { heavy_items[base + j] = make_uint2(fb, j); heavy_slot[base + j] = hb; }
 }
 
 __global__ void __launch_bounds__(256) k_merge(const uint32_t *__restrict__ start, const uint32_t *__restrict__ count, uint64_t FB, int L,
@@ -482,11 +477,8 @@ __global__ void __launch_bounds__(256) k_merge(const uint32_t *__restrict__ star
   if (g0 == g1) return;                       // summed and stored by its lane
   uint32_t np = (uint32_t)(g1 - g0 + 1);      // number of partial sums
   if (np > MERGE_SERIAL_MAX + 1) {
-    // skewed scalars / a narrow top window: hand the bucket to wavefronts, HEAVY_CHUNK partials each
-    uint32_t nch = (np + HEAVY_CHUNK - 1) / HEAVY_CHUNK;
-    uint32_t base = atomicAdd(&heavy_count[0], nch), hb = 0;
-    if (nch > 1) { hb = atomicAdd(&heavy_count[1], 1u); heavy_buckets[hb] = make_uint4((uint32_t)fb, base, nch, 0u); }   // .w: the chunks' ticket
-    for (uint32_t j = 0; j < nch; j++) { heavy_items[base + j] = make_uint2((uint32_t)fb, j); heavy_slot[base + j] = hb; }
+    // skewed scalars / a narrow top window: hand the bucket to wavefronts
+    heavy_register((uint32_t)fb, np, heavy_items, heavy_slot, heavy_buckets, heavy_count);
     return;
   }
   xyzz acc = xyzz_load(partial_ptr(rec_pt, g0, 0));
@@ -612,60 +604,67 @@ __global__ void __launch_bounds__(256) k_order(const uint32_t *__restrict__ coun
     for (uint32_t j = 0; j < full; j++) items[off[ACC_CAP - 1] + lb[ACC_CAP - 1] + rf[k] + j] = make_uint2((uint32_t)fb, j);
     if (rem) items[off[rem - 1] + lb[rem - 1] + rr[k]] = make_uint2((uint32_t)fb, full);
     if (cnt[k] <= ACC_CAP) continue;
-    const uint32_t np = full + (rem ? 1u : 0u), nch = (np + HEAVY_CHUNK - 1) / HEAVY_CHUNK;
+    const uint32_t np = full + (rem ? 1u : 0u);
     piece_base[fb] = atomicAdd(&ctr[2], np);
-    uint32_t base = atomicAdd(&ctr[0], nch), hb = 0;
-    if (nch > 1) { hb = atomicAdd(&ctr[1], 1u); heavy_buckets[hb] = make_uint4((uint32_t)fb, base, nch, 0u); }   // .w: the chunks' ticket
-    for (uint32_t j = 0; j < nch; j++) { heavy_items[base + j] = make_uint2((uint32_t)fb, j); heavy_slot[base + j] = hb; }
+    heavy_register((uint32_t)fb, np, heavy_items, heavy_slot, heavy_buckets, ctr);
   }
 }
 
+// The point arithmetic of the sized accumulation: the entry's point with its sign folded in, the accumulator started from it, the mixed
+// addition, and the sum in the 40-word layout that k_merge_heavy<true> and the bucket reduction read.
+struct AccFq26 {                                   // 10 x 26-bit limbs (ec.hip.h)
+  typedef aff point; typedef xyzz sum;
+  static BPPP_DI aff load(const uint32_t *p) { return aff_load(p); }
+  static BPPP_DI aff cneg(const aff &P, bool neg) { return aff_cneg(P, neg); }
+  static BPPP_DI xyzz first(const aff &P) { return xyzz_from_aff(P); }
+  static BPPP_DI void madd(xyzz &acc, const aff &P) { xyzz_madd(acc, P); }
+  static BPPP_DI xyzz stored(const xyzz &acc) { return acc; }
+};
+// 9 x 29-bit limbs (fq29.hip.h, ec29.hip.h; MsmTune::acc_fq29): 81 partial products per field multiplication instead of 100.  The sum is
+// converted once, at the store (every limb below 2^26).
+struct AccFq29 {
+  typedef aff29 point; typedef xyzz29 sum;
+  static BPPP_DI aff29 load(const uint32_t *p) { return aff29_load(p); }
+  static BPPP_DI aff29 cneg(const aff29 &P, bool neg) { return aff29_cneg(P, neg); }
+  static BPPP_DI xyzz29 first(const aff29 &P) { return xyzz29_from_aff(P); }
+  static BPPP_DI void madd(xyzz29 &acc, const aff29 &P) { xyzz29_madd(acc, P); }
+  static BPPP_DI xyzz stored(const xyzz29 &acc) { return xyzz29_to_xyzz(acc); }
+};
 // one item per lane: the same 4-byte entries, sign fold and complete mixed addition as k_acc_points.  A lane whose item is shorter than the
 // wavefront's longest leaves the loop early (execution mask); a whole bucket goes to `buckets`, a piece to its slot of `pieces`.
+template <class A>
+BPPP_DI void acc_points_sized(const uint32_t *__restrict__ sorted, const uint32_t *__restrict__ start, const uint32_t *__restrict__ count,
+                              const uint2 *__restrict__ items, const uint32_t *__restrict__ ctr, const uint32_t *__restrict__ piece_base,
+                              const uint32_t *__restrict__ points, uint32_t *__restrict__ buckets, uint32_t *__restrict__ pieces) {
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= ctr[3]) return;
+  const uint2 it = items[g];
+  const uint32_t fb = it.x, cnt = count[fb], first = it.y * ACC_CAP, len = min(ACC_CAP, cnt - first);
+  const uint32_t *ent = sorted + start[fb] + first;
+  uint32_t e = ent[0];
+  typename A::sum acc = A::first(A::cneg(A::load(points + (size_t)(e & 0x7FFFFFFFu) * 16), (e >> 31) & 1u));
+  e = len > 1 ? ent[1] : 0u;
+  for (uint32_t k = 1; k < len; k++) {
+    const uint32_t e_next = (k + 1 < len) ? ent[k + 1] : 0u;
+    typename A::point P = A::cneg(A::load(points + (size_t)(e & 0x7FFFFFFFu) * 16), (e >> 31) & 1u);
+    A::madd(acc, P);
+    e = e_next;
+  }
+  xyzz_store(cnt > ACC_CAP ? pieces + ((size_t)piece_base[fb] + it.y) * XYZZ_WORDS : buckets + (size_t)fb * XYZZ_WORDS, A::stored(acc));
+}
 __global__ void __launch_bounds__(256) k_acc_points_sized(const uint32_t *__restrict__ sorted, const uint32_t *__restrict__ start,
                                                           const uint32_t *__restrict__ count, const uint2 *__restrict__ items,
                                                           const uint32_t *__restrict__ ctr, const uint32_t *__restrict__ piece_base,
                                                           const uint32_t *__restrict__ points, uint32_t *__restrict__ buckets,
                                                           uint32_t *__restrict__ pieces) {
-  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= ctr[3]) return;
-  const uint2 it = items[g];
-  const uint32_t fb = it.x, cnt = count[fb], first = it.y * ACC_CAP, len = min(ACC_CAP, cnt - first);
-  const uint32_t *ent = sorted + start[fb] + first;
-  uint32_t e = ent[0];
-  xyzz acc = xyzz_from_aff(aff_cneg(aff_load(points + (size_t)(e & 0x7FFFFFFFu) * 16), (e >> 31) & 1u));
-  e = len > 1 ? ent[1] : 0u;
-  for (uint32_t k = 1; k < len; k++) {
-    const uint32_t e_next = (k + 1 < len) ? ent[k + 1] : 0u;
-    aff P = aff_cneg(aff_load(points + (size_t)(e & 0x7FFFFFFFu) * 16), (e >> 31) & 1u);
-    xyzz_madd(acc, P);
-    e = e_next;
-  }
-  xyzz_store(cnt > ACC_CAP ? pieces + ((size_t)piece_base[fb] + it.y) * XYZZ_WORDS : buckets + (size_t)fb * XYZZ_WORDS, acc);
+  acc_points_sized<AccFq26>(sorted, start, count, items, ctr, piece_base, points, buckets, pieces);
 }
-// The same kernel with the accumulator in 9 x 29-bit limbs (fq29.hip.h, ec29.hip.h; MsmTune::acc_fq29): 81 partial products per field
-// multiplication instead of 100.  Same items, entries, sign fold and first-entry start; the sum is converted once, at the store, into the
-// 40-word layout and the magnitudes that k_merge_heavy<true> and the bucket reduction read (every limb below 2^26).
 __global__ void __launch_bounds__(256) k_acc_points_sized29(const uint32_t *__restrict__ sorted, const uint32_t *__restrict__ start,
                                                             const uint32_t *__restrict__ count, const uint2 *__restrict__ items,
                                                             const uint32_t *__restrict__ ctr, const uint32_t *__restrict__ piece_base,
                                                             const uint32_t *__restrict__ points, uint32_t *__restrict__ buckets,
                                                             uint32_t *__restrict__ pieces) {
-  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= ctr[3]) return;
-  const uint2 it = items[g];
-  const uint32_t fb = it.x, cnt = count[fb], first = it.y * ACC_CAP, len = min(ACC_CAP, cnt - first);
-  const uint32_t *ent = sorted + start[fb] + first;
-  uint32_t e = ent[0];
-  xyzz29 acc = xyzz29_from_aff(aff29_cneg(aff29_load(points + (size_t)(e & 0x7FFFFFFFu) * 16), (e >> 31) & 1u));
-  e = len > 1 ? ent[1] : 0u;
-  for (uint32_t k = 1; k < len; k++) {
-    const uint32_t e_next = (k + 1 < len) ? ent[k + 1] : 0u;
-    aff29 P = aff29_cneg(aff29_load(points + (size_t)(e & 0x7FFFFFFFu) * 16), (e >> 31) & 1u);
-    xyzz29_madd(acc, P);
-    e = e_next;
-  }
-  xyzz_store(cnt > ACC_CAP ? pieces + ((size_t)piece_base[fb] + it.y) * XYZZ_WORDS : buckets + (size_t)fb * XYZZ_WORDS, xyzz29_to_xyzz(acc));
+  acc_points_sized<AccFq29>(sorted, start, count, items, ctr, piece_base, points, buckets, pieces);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -734,12 +733,10 @@ __global__ void __launch_bounds__(64) k_reduce2(const uint32_t *__restrict__ red
 // R and C are PLAIN sums: k_reduce_marg gives every lane S consecutive (rows) or strided (columns) buckets — no scan, every
 // lane busy, one wavefront per SIMD — and finishes them with a short segmented tree.  With the SIMD to itself the wavefront adds with
 // xyzz_add_chain (ec.hip.h: the products of an addition issued in pairs, so that one fills the other's stall slots) and loads the
-// next bucket while it adds the current one; so do k_reduce_tail and the trees of k_merge_heavy.  The two weighted sums left are over HI and
-// LO (<= 256) elements: k_reduce_tail, one element per lane (suffix scan + tree, ~18 chained additions).  The factor LO is not
+// next bucket while it adds the current one; so do the trees of k_merge_heavy.  The two weighted sums left are over HI and
+// LO (<= 256) elements: k_reduce_tail_quad, on TR = HI / 16 row and TC = LO / 16 column blocks of 16 elements.  The factor LO is not
 // applied on the device at all: the window combine, which doubles c times per window anyway, takes (W1, W2) and does
-// r = (r * 2^(c-a) + W1) * 2^a + W2.
-// quad = 1: k_reduce_tail_quad, on TR = HI / 16 row and TC = LO / 16 column blocks of 16 elements (MsmTune::tail_scalar = 0)
-struct MargGeom { int a, LO, HI, PR, PC, SR, SC; uint32_t row_tiles, col_tiles; int quad, TR, TC; };
+// r = (r * 2^(c-a) + W1) * 2^a + W2.  (MargGeom: msm_plan.hpp)
 
 // the serial part of a lane: b[0] + b[stride] + ... (S terms).  Bucket k + 1 is loaded (ten 16-byte loads into a second set of registers)
 // before bucket k is added, so the wavefront — alone on its SIMD, nothing else to hide a load behind — waits for memory once, not S times.
@@ -787,39 +784,7 @@ __global__ void __launch_bounds__(64) k_reduce_marg(const uint32_t *__restrict__
   }
 }
 
-// one workgroup per (window, R | C) — blockIdx.y = 0: R, 1: C — of at most four wavefronts, one per SIMD of its CU: a dependent
-// chain of point additions runs at one wavefront's instruction rate, and two chains on one SIMD would each run at half of it.
-// Both kinds are launched with 64 * ceil(LO / 64) threads; the spare wavefronts of an R workgroup hold infinity.
-__global__ void __launch_bounds__(256) k_reduce_tail(const uint32_t *__restrict__ R, const uint32_t *__restrict__ C, MargGeom Gm, uint32_t *__restrict__ winsum2) {
-  __shared__ __attribute__((aligned(16))) uint32_t tot[4 * XYZZ_WORDS];
-  const uint32_t nbw = blockIdx.x, lane = threadIdx.x & 63, gw = threadIdx.x >> 6, gn = blockDim.x >> 6;
-  const bool isC = blockIdx.y != 0;
-  const uint32_t n = isC ? (uint32_t)Gm.LO : (uint32_t)Gm.HI, idx = gw * 64 + lane;
-  xyzz suf = xyzz_inf();
-  if (idx < n) suf = xyzz_load((isC ? C + ((size_t)nbw * Gm.LO + idx) * XYZZ_WORDS : R + ((size_t)nbw * Gm.HI + idx) * XYZZ_WORDS));
-  for (int d = 1; d < 64; d <<= 1) {             // inclusive suffix scan inside the wavefront
-    xyzz o = xyzz_shfl_down(suf, d);
-    if ((int)lane + d < 64) xyzz_add_chain(suf, o);
-  }
-  if (lane == 0) xyzz_store(tot + gw * XYZZ_WORDS, suf);
-  __syncthreads();
-  for (uint32_t w = gw + 1; w < gn; w++) { xyzz t = xyzz_load(tot + w * XYZZ_WORDS); xyzz_add_chain(suf, t); }     // later wavefronts of the group
-  // R: sum_hi hi * R_hi = sum_{hi >= 1} suffix(hi);   C: sum_lo (lo + 1) * C_lo = sum_{lo >= 0} suffix(lo)
-  xyzz v = (!isC && idx == 0) ? xyzz_inf() : suf;
-  for (int d = 32; d >= 1; d >>= 1) {
-    xyzz o = xyzz_shfl_down(v, d);
-    if ((int)lane + d < 64) xyzz_add_chain(v, o);
-  }
-  __syncthreads();
-  if (lane == 0) xyzz_store(tot + gw * XYZZ_WORDS, v);
-  __syncthreads();
-  if (lane == 0 && gw == 0) {
-    for (uint32_t w = 1; w < gn; w++) { xyzz t = xyzz_load(tot + w * XYZZ_WORDS); xyzz_add_chain(v, t); }
-    xyzz_store(winsum2 + ((size_t)nbw * 2 + (isC ? 1 : 0)) * XYZZ_WORDS, v);
-  }
-}
-
-// The same two weighted sums with one QUAD per element (ec_quad.hip.h): a quad addition is about a third of a lane addition's depth,
+// The two weighted sums with one QUAD per element (ec_quad.hip.h): a quad addition is about a third of a lane addition's depth,
 // and the extra lanes are free where the chip is idle.  A block of 16 elements is one single-wavefront workgroup (workgroups land
 // on separate CUs, so every wavefront has a SIMD of its own; 16 wavefronts of one workgroup would share four).  The R kind reads
 // its elements shifted by one, R'_k = R_{k+1}, so that both kinds are  W = sum_i (i + 1) E_i.  With i = 16 b + j:
@@ -943,10 +908,7 @@ __global__ void __launch_bounds__(64) k_window_combine(const uint32_t *__restric
 // entries in LDS, M = 2^(c-1) buckets with 256 / M lanes each (a shuffle tree joins them), and the running-sum reduction sum (m + 1) B_m
 // as a suffix scan + tree over M lanes.  c = 6: 43 windows, ~17 dependent point operations deep (0.13 ms).  k_msm_small_join adds the
 // slices of a window (one wavefront per window); the window sums go to the host's Horner combine like the general path's.
-static constexpr uint32_t MSM_SMALL_MAX = 4096;            // terms per slice (LDS: 6 bytes each)
-static constexpr size_t MSM_SMALL_DEFAULT_MAX = 8192;      // terms per MSM on this route unless BPPP_MSM_SMALL_MAX says otherwise: every (window, slice) workgroup
-                                                           // pays the ~17-operation reduction chain with most lanes idle, so the general pipeline wins from ~2^14 terms
-                                                           // (benchmarks/sweep_small_msm.py: 858 terms 0.36 -> 0.21 ms, 4096 0.38 -> 0.27, 8192 0.40 -> 0.33, 22016 0.45 -> 0.43, 65536 0.52 -> 0.78)
+// (MSM_SMALL_MAX terms per slice and the route's default length limit: msm_plan.hpp, MsmSmallPlan)
 __global__ void __launch_bounds__(256) k_msm_small(const uint32_t *__restrict__ scalars_all, const uint32_t *__restrict__ points_all, uint32_t n_all, uint32_t slice_len,
                                                    int c, int acnt, int top, RecodeK K, uint32_t *__restrict__ winsum) {
   // slice blockIdx.y of the terms: its own bucket set, its own partial window sum (k_msm_small_join adds the slices of a window)
@@ -1064,271 +1026,169 @@ __global__ void __launch_bounds__(64) k_msm_small_join(const uint32_t *__restric
   if (lane == 0) xyzz_store(winsum + (size_t)w * XYZZ_WORDS, acc);
 }
 
-// The same kernel with the point of entry p + 1 in flight while entry p is added (MsmTune::acc_lds).  The gather goes straight into LDS
-// (global_load_lds_dwordx4: per-lane source address, no VGPR destination, so the prefetch costs no occupancy): a wavefront owns two stages
-// of 4 KB laid out [piece][lane] — one instruction writes piece k of all 64 lanes contiguously, and every lane reads back only its own
-// 4 x 16 bytes, so there is no barrier.  Ordinary loads whose results are used while a direct-to-LDS load is outstanding would drain it
-// early, so everything entry p + 1 needs is read BEFORE its gather is issued: its bucket (start[] at a bucket boundary, the bisect over
-// empty buckets) and the entry after it (sorted[p + 2], first used after the next wait).  Same sums in the same order as k_acc_points.
-__global__ void __launch_bounds__(256) k_acc_points_lds(const uint32_t *__restrict__ sorted, const uint32_t *__restrict__ start, uint32_t FB,
-                                                        const uint32_t *__restrict__ points, uint32_t n, uint32_t WM, int shared_pts,
-                                                        int L, uint64_t G, uint32_t *__restrict__ buckets, uint32_t *__restrict__ rec_pt) {
-  __shared__ uint4 stage[4][2][4][64];                          // [wavefront][stage][piece][lane]
-  uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= G) return;
-  const uint32_t total = start[FB];
-  const uint64_t pos0 = g * (uint64_t)L;
-  if (pos0 >= total) return;
-  const uint32_t pos1 = (uint32_t)min((uint64_t)total, pos0 + L);
-  uint32_t lo = 0, hi = FB - 1;
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo + 1) / 2;
-    if (start[mid] <= (uint32_t)pos0) lo = mid; else hi = mid - 1;
-  }
-  uint32_t cur = lo, end = start[cur + 1];
-  const bool from_prev = start[cur] < (uint32_t)pos0;
-  bool first = true;
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const uint32_t div = shared_pts ? (uint32_t)shared_pts : 1u;
-  auto gather = [&](uint32_t st, uint32_t ent, uint32_t bucket) {
-    const uint32_t idx = ent & 0x7FFFFFFFu;
-    const size_t pidx = shared_pts == 1 ? (size_t)idx : (size_t)((bucket / WM) / div) * n + idx;
-    const uint32_t *src = points + pidx * 16;
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + 4 * k),
-                                       (__attribute__((address_space(3))) void *)&stage[wv][st][k][0], 16, 0, 0);
-  };
-  uint32_t e = sorted[pos0], e1 = (pos0 + 1 < pos1) ? sorted[pos0 + 1] : 0u, st = 0;
-  gather(0, e, cur);
-  xyzz acc = xyzz_inf();
-  for (uint32_t p = (uint32_t)pos0; p < pos1; p++) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the point of entry p has landed
-    uint32_t w[16];
-#pragma unroll
-    for (int k = 0; k < 4; k++) { const uint4 v = stage[wv][st][k][lane]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
-    // the bucket of entry p + 1
-    const bool more = p + 1 < pos1, boundary = more && p + 1 == end;
-    uint32_t ncur = cur, nend = end;
-    if (boundary) {
-      ncur = cur + 1; nend = start[ncur + 1];
-      if (nend <= p + 1) {                                      // empty buckets: bisect for the one that holds p + 1 (see k_acc_points)
-        uint32_t lo2 = ncur + 1, hi2 = FB - 1;
-        while (lo2 < hi2) {
-          const uint32_t mid = lo2 + (hi2 - lo2 + 1) / 2;
-          if (start[mid] <= p + 1) lo2 = mid; else hi2 = mid - 1;
-        }
-        ncur = lo2; nend = start[ncur + 1];
-      }
-    }
-    const uint32_t e2 = (p + 2 < pos1) ? sorted[p + 2] : 0u;
-    if (more) gather(st ^ 1u, e1, ncur);
-    fe fx, fy;
-#pragma unroll
-    for (int i = 0; i < 8; i++) { fx.v[i] = w[i]; fy.v[i] = w[8 + i]; }
-    aff P; P.x = fq_from_fe(fx); P.y = fq_from_fe(fy);
-    xyzz_madd(acc, aff_cneg(P, (e >> 31) & 1u));
-    if (boundary) {
-      // the run ends inside this lane: head partial if it came from the previous lane, else complete
-      if (first && from_prev) xyzz_store(rec_pt + (2 * g) * XYZZ_WORDS, acc);
-      else xyzz_store(buckets + (size_t)cur * XYZZ_WORDS, acc);
-      first = false; acc = xyzz_inf();
-      cur = ncur; end = nend;
-    }
-    e = e1; e1 = e2; st ^= 1u;
-  }
-  const bool hi_part = first && from_prev, ti = end > pos1;
-  if (hi_part) xyzz_store(rec_pt + (2 * g) * XYZZ_WORDS, acc);
-  else if (ti) xyzz_store(rec_pt + (2 * g + 1) * XYZZ_WORDS, acc);
-  else xyzz_store(buckets + (size_t)cur * XYZZ_WORDS, acc);
-}
-
 // ------------------------------------------------------------------------------------------------
-// host orchestration
-static int choose_window(size_t n, size_t batch, const MsmTune &tune) {
-  // Cost model in units of one mixed addition (~68 ps chip-wide, measured at 2^20; profiles/):
-  //   accumulate: one addition per (scalar, window that holds real bits): ceil(255/c) windows (+ half a window when
-  //               c divides 255: the top digit then wraps for half the scalars and a carry window appears — the only widths
-  //               that still have one, window_layout);
-  //   reduce:     ~10 per bucket (the wave-prefix bucket reduction is latency-bound; fitted at c = 13..16); ~3.5 per
-  //               bucket for a large batch of small MSMs, which goes through k_reduce_groups (throughput-bound);
-  //   heavy top:  when the top window has few real bits its buckets hold n / 2^r entries each and go through the
-  //               wave-cooperative merge tree: a flat ~1.5e6 (0.1 ms) once they span many lanes.
-  // One large MSM: the reduction is latency-bound and nearly flat in the bucket count (0.12 ms at c = 11 .. 0.26 ms at c = 16),
-  // so the model above overprices wide windows; thresholds read off the (n, c, L) table of benchmarks/sweep_window.py
-  // (profiles/r02_window_sweep.txt): c = 16 has 16 windows (17 when that table was read, window_layout) against 20 at c = 13 and no heavy top window.
-  // (re-read after the balanced windows of make_plan, which removed the heavy top window of every width that does not divide 256:
-  // 9000-12000 terms 0.47 ms at c = 8 against 0.33 at c = 11; 22 016 terms 0.376 at c = 12; 43 782 terms 0.423 at c = 13)
-  if (batch == 1 && n >= 4096) return n < 20000 ? 11 : n < 30000 ? 12 : n < 200000 ? 13 : 16;
-  const double gcost = tune.gcost > 0 ? tune.gcost : 3.5;               // tuning sweeps override both
-  const int cmin = tune.cmin ? std::max(2, tune.cmin) : 4;
-  double best = 1e300; int bc = 8;
-  for (int c = cmin; c <= 16; c++) {
-    int full = 254 / c, r = 255 - c * full, W = full + 1 + (r == c ? 1 : 0);   // r = real bits in the top window (1..c); W as window_layout's
-    double weff = full + 1 + (r == c ? 0.5 : 0.0);
-    const bool groups = c <= 9 && (double)batch * W >= 4096.0;
-    double cost = weff * (double)n + (groups ? gcost : 10.0) * W * (double)(1u << (c - 1));
-    double top_bucket = r == c ? n / 2.0 : (double)n / (double)(1u << (r < 20 ? r : 20));
-    if ((r == c || r < c - 1) && top_bucket > 1024.0) cost += 1.5e6;
-    if (cost < best) { best = cost; bc = c; }
-  }
-  return bc;
+// host orchestration: the plan and the workspace layout come from msm_plan.hpp; here the small route and the stages of the general pipeline,
+// one launcher each, in the order msm_run_ex calls them.  The prof_mark indices are the stage boundaries bench.py reads.
+
+// the one-shot hook that runs right before the first kernel that reads the points (ctx.hpp)
+static int run_pre_acc(bppp_ctx *ctx) {
+  if (!ctx->pre_acc) return BPPP_OK;
+  auto f = ctx->pre_acc; ctx->pre_acc = nullptr;
+  return f(ctx->pre_acc_arg);
 }
 
-// The windows of a scalar over arbitrary points.  A folded scalar has 255 bits (recode.hip.h) and the signed digits carry upwards, so the top
-// window holds d in [0, 2^r] for its r real bits.  r <= cw - 2: d + 2^(cw-1) fits the window's cw bits as every other digit does.
-// r = cw - 1: only d = 2^(cw-1) does not, and rather than a further window for that one carry the top window is left unbiased and stored
-// negated (top = its index; k_digits, k_msm_small) — its largest magnitude is then the bucket of -2^(cw-1) that every window has.
-// r = cw (uniform widths, c divides 255): half of the scalars carry, the window above stays.
-//   balanced (one MSM, c does not divide 256): ceil(256 / c) windows, the first acnt c bits wide, the others c - 1; r = cw - 1 always;
-//   uniform: ceil(255 / c) windows, r = cw - 1 exactly when c divides 256 (16 windows at c = 16, 32 at c = 8), + 1 when c divides 255.
-// A registered basis (flat plans, basis.hip, comb.hip) keeps 256 / c + 1 biased rows: its tables are laid out by them.
-struct WindowLayout { int W, acnt, top; };
-static WindowLayout window_layout(int c, bool balanced) {
-  WindowLayout l;
-  if (balanced) {
-    l.W = (256 + c - 1) / c; l.acnt = 256 - l.W * (c - 1); l.top = l.W - 1;
-  } else {
-    const int T = (255 + c - 1) / c, r = 255 - c * (T - 1);
-    l.W = T + (r == c ? 1 : 0); l.acnt = l.W; l.top = r == c - 1 ? l.W - 1 : -1;
-  }
-  return l;
+// ---- one small or mid-size MSM: k_msm_small over (window, slice of <= 4096 terms) workgroups, the slices of a window joined by one
+// wavefront each, then the host's Horner combine over the W window sums
+static int msm_small(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_t n, uint64_t *out_xy) {
+  using namespace bppp_host;
+  const MsmSmallPlan s = make_small_plan(n, ctx->tune);
+  Carver sizing(nullptr, 0);
+  carve_small(sizing, s);
+  int rc = ensure_workspace(ctx, sizing.off); if (rc) return rc;
+  Carver cv(ctx->ws, ctx->ws_bytes);
+  const MsmSmallWorkspace ws = carve_small(cv, s);
+  const size_t bytes = (size_t)s.W * XYZZ_WORDS * 4;
+  rc = ensure_pinned(ctx, bytes); if (rc) return rc;
+  hipStream_t st = ctx->stream;
+  ctx->last_windows = s.W;
+  for (int i = 0; i <= 2; i++) prof_mark(ctx, i);
+  rc = run_pre_acc(ctx); if (rc) return rc;
+  k_msm_small<<<dim3((unsigned)s.W, (unsigned)s.S), dim3(256), s.lds, st>>>((const uint32_t *)d_scalars, (const uint32_t *)d_points, (uint32_t)n, (uint32_t)s.len, s.c,
+                                                                         s.acnt, s.top, make_recode_k(s.c, s.W, s.acnt, s.top >= 0), s.S > 1 ? ws.partials : ws.winsum);
+  if (s.S > 1) k_msm_small_join<<<dim3((unsigned)s.W), dim3(64), 0, st>>>(ws.partials, (uint32_t)s.S, ws.winsum);
+  for (int i = 3; i <= 5; i++) prof_mark(ctx, i);
+  BPPP_HIP(ctx, hipMemcpyAsync(ctx->pinned, ws.winsum, bytes, hipMemcpyDeviceToHost, st));
+  prof_mark(ctx, 6);
+  BPPP_HIP(ctx, hipStreamSynchronize(st));
+  window_combine_host((const uint32_t *)ctx->pinned, s.W, s.c, s.acnt, false, 0, out_xy);
+  BPPP_HIP(ctx, hipGetLastError());
+  prof_collect(ctx, 7);
+  return BPPP_OK;
 }
 
-struct MsmPlan {
-  size_t n, batch; int c, W, acnt, M, CH, hist_threads, Lw, WPW;   // acnt: windows [0, acnt) are c bits wide, the others c - 1
-  int top;                     // the digit row stored negated (window_layout), -1: none
-  bool flat;                   // precomputed table 2^(c w) P_i: all windows of an instance share ONE bucket set
-  int Wc;                      // windows left for the window combine (1 when flat)
-  uint64_t NB, NS, FB, total_max;   // digit rows (batch * W), bucket sets (batch * W, or batch when flat), buckets, sorted entries
-  int L; uint64_t G;           // sorted entries per lane, number of lanes
-  int RG;                      // k_reduce_groups lanes per window (0 = wave-per-window path)
-  bool marg; MargGeom mg;      // marginal-sum reduction (M >= 256, not the grouped path)
-  int ntiles;
-  int Q;                       // bucket ranges per window of the ranged scatter (k_scatter_ranges, k_scatter_one_read); 0 = k_scatter
-  bool one_read;               // ranged scatter from (window, chunk) workgroups that read their digits once (k_scatter_one_read)
-  bool sized;                  // accumulate whole buckets in order of size (k_order, k_acc_points_sized) instead of slices of L entries
-  bool fq29;                   // sized, with the accumulator in 9 x 29-bit limbs (k_acc_points_sized29)
-};
+// ---- the general pipeline
+// the sort kernels' dynamic LDS above the 64 KiB a kernel gets unasked: set once per size, not per call
+static int msm_sort_lds(bppp_ctx *ctx, const MsmPlan &p) {
+  const size_t lds = sort_lds_bytes(p);
+  if (lds > 64 * 1024 && lds > ctx->sort_lds_set) {
+    BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter_ranges, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter_one_read, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ctx->sort_lds_set = lds;
+  }
+  return BPPP_OK;
+}
 
-static MsmPlan make_plan(size_t n, size_t batch, int c, bool flat, const MsmTune &tune) {
-  MsmPlan p;
-  p.n = n; p.batch = batch; p.c = c; p.W = 256 / c + 1; p.M = 1 << (c - 1);
-  p.acnt = p.W; p.top = -1;
-  // Balanced windows (one MSM over arbitrary points, c not a divisor of 256): with uniform widths the top window holds only
-  // 256 - c floor(256 / c) real bits, i.e. a few buckets with n / 2^r entries each — the "heavy" merges (0.05 ms at 2^16 terms, c = 13:
-  // 256 buckets of 256 entries).  Instead ceil(256 / c) windows of widths c (the low ones) and c - 1 share the 256 bits, so every
-  // window's buckets are evenly filled.
-  if (!flat) {
-    const WindowLayout l = window_layout(c, batch == 1 && c >= 3 && 256 % c != 0 && !tune.no_balance);
-    p.W = l.W; p.acnt = l.acnt; p.top = l.top;
-  }
-  p.flat = flat; p.Wc = flat ? 1 : p.W;
-  p.NB = (uint64_t)batch * p.W; p.NS = flat ? batch : p.NB; p.FB = p.NS * p.M; p.total_max = p.NB * n;
-  p.hist_threads = p.M >= 8192 ? 1024 : 256;
-  size_t per_block = (size_t)p.hist_threads * 64;
-  p.CH = (int)std::max<size_t>(1, std::min<size_t>(64, (n + per_block - 1) / per_block));
-  // the histogram of a wide window (>= 80 KB of LDS) leaves room for ONE k_hist / k_scatter workgroup per CU: a grid a few workgroups
-  // over a whole number of rounds (17 windows x 16 chunks on 256 CUs) runs a nearly empty extra round — take the chunk count that fills
-  // the rounds instead (15: sort stage 0.301 -> 0.277 ms at 2^20)
-  // ranged scatter (k_scatter_ranges, k_scatter_one_read): a window is cut into as many chunks as an XCD has CUs (num_cus / 8: 32) and ONE
-  // workgroup is resident per CU (the launches' LDS requests), so that the workgroups of one (window, range) unit fill an XCD and ONE unit is
-  // live per L2: 1 MiB of `sorted` (n * 4 / Q bytes for evenly spread digits) at 2^20 terms and Q = 4, a quarter of the L2.  A second live
-  // unit — two workgroups per CU, or the wavefronts of k_scatter_one_read left to drift over the ranges — loses the merging.
-  // Measured with k_scatter_ranges, loads four steps ahead, sort stage: Q = 4 0.175 / 0.176 / 0.222 ms at 16 / 32 / 64 chunks, Q = 2 0.258 /
-  // 0.171 / 0.221 (k_scatter: 0.248 / 0.268 / 0.284); under k_scatter_one_read Q = 2 at 32 chunks is no faster than Q = 4.  A shorter
-  // input takes fewer chunks, of the same length, but never fewer than the rule above gives.
-  // k_hist, k_count_tiles and the blockhist layout use the same chunk count.
-  p.Q = 0;
-  if (batch == 1 && !flat && (size_t)p.M * 4 > 80 * 1024 && tune.num_cus >= 8 && (tune.sort_ranges == 2 || tune.sort_ranges == 4)) {
-    p.Q = tune.sort_ranges;
-    const uint64_t cus = (uint64_t)tune.num_cus / 8, unit_bytes = (uint64_t)n * 4 / p.Q;
-    const uint64_t ch = (cus * unit_bytes + (1u << 20) - 1) >> 20;
-    p.CH = (int)std::min<uint64_t>(std::min<uint64_t>(cus, 64), std::max<uint64_t>((uint64_t)p.CH, ch));
-  } else if ((size_t)p.M * 4 > 80 * 1024 && tune.num_cus > 0) {
-    const double rounds = (double)p.NB * p.CH / tune.num_cus;
-    if (rounds >= 0.75) {
-      const uint64_t r = (uint64_t)(rounds + 0.5) ? (uint64_t)(rounds + 0.5) : 1;
-      const uint64_t ch = r * (uint64_t)tune.num_cus / p.NB;
-      if (ch >= 1 && ch <= 64 && 4 * ch >= 3 * (uint64_t)p.CH) p.CH = (int)ch;
-    }
-  }
-  if (tune.hist_ch >= 1 && tune.hist_ch <= 64) p.CH = tune.hist_ch;
-  // one read of the digits (k_scatter_one_read): a lane holds SCATTER_AHEAD steps of 8 digits in registers, so the form is possible exactly
-  // when a chunk is no longer than that many steps of the workgroup — a rule in steps per lane, whatever n and the chunk count are.  With the
-  // chunk rule above that is every n up to 2^15 x (CUs of an XCD); a longer chunk keeps k_scatter_ranges, which refills its registers.
-  // Its W x CH workgroups run one per CU and each lasts Q range passes, so the form is taken only for grids that fill their rounds:
-  // - at least one whole round.  A smaller grid is a shorter MSM that often shares the chip with another stream's: two verifiers at once
-  //   (345 k terms each, 176 workgroups) ran 2.25 -> 2.34 ms per batch with the long workgroups, for 0.007 ms less sort stage when alone;
-  // - no last round for fewer than a quarter of the CUs, which costs a whole workgroup's time for little work where k_scatter_ranges'
-  //   workgroups of one pass each fill the CUs evenly — 17 chunks of 16 windows on 256 CUs (16 workgroups in the second round): sort stage
-  //   0.127 ms ranged, 0.134 read once; 20 chunks (64): 0.139 either way; 16 and 24 to 32 chunks are faster read once.
-  // Every other plan keeps k_scatter_ranges too.
-  const uint64_t chunk = ((((uint64_t)n + p.CH - 1) / p.CH) + 7u) & ~(uint64_t)7, lane_steps = (chunk + (uint64_t)p.hist_threads * 8 - 1) / ((uint64_t)p.hist_threads * 8);
-  const uint64_t wgs = (uint64_t)p.W * p.CH, cus = (uint64_t)std::max(tune.num_cus, 1), last_round = wgs % cus;
-  const bool full_rounds = wgs >= cus && !(last_round && 4 * last_round < cus);
-  p.one_read = p.Q && tune.scatter_one_read && lane_steps <= (uint64_t)SCATTER_AHEAD && full_rounds;
-  // bucket reduce geometry: lanes per window T = M / Lw, at most 64 wavefronts per window
-  if (p.M <= 64) { p.Lw = 1; p.WPW = 1; }
-  else {
-    p.Lw = 1;
-    while (p.M / p.Lw > 64 * 64) p.Lw <<= 1;     // cap at 4096 lanes per window
-    if (p.M / p.Lw >= 1024 && p.Lw < 4) p.Lw = std::min(4, p.M / 1024);  // amortise the wave scan
-    if (p.Lw < 1) p.Lw = 1;
-    if (tune.lw) { const int v = tune.lw; if (v >= 1 && (v & (v - 1)) == 0 && p.M / v >= 64 && p.M / v <= 4096) p.Lw = v; }
-    p.WPW = p.M / p.Lw / 64;
-    if (p.WPW < 1) p.WPW = 1;
-  }
-  p.RG = 0;
-  if (p.M <= 256 && p.NS >= 4096) {                            // M is a power of two >= 2
-    // lanes per window: the serial part costs 2 additions per bucket, the in-group scan and tree ~3 log2(RG) more per lane, so
-    // keep >= 16 buckets per lane (RG = 8 on 8 buckets is 11 additions per bucket, RG = 1 is 2) unless the launch would
-    // then be under ~2 wavefronts per SIMD
-    const int cap = std::min(8, p.M);
-    p.RG = std::max(1, std::min(cap, p.M / 16));
-    while (p.RG < cap && p.NS * (uint64_t)p.RG < 131072) p.RG <<= 1;
-    if (tune.rg) { const int v = tune.rg; if (v >= 1 && v <= cap && (v & (v - 1)) == 0) p.RG = v; }
-  }
-  p.marg = !p.RG && p.M >= 256 && p.NS <= 65535 && !tune.reduce_old;
-  memset(&p.mg, 0, sizeof p.mg);
-  if (p.marg) {
-    MargGeom &g = p.mg;
-    g.a = (c - 1 + 1) / 2; g.LO = 1 << g.a; g.HI = p.M / g.LO;          // LO >= HI, both <= 256
-    // serial length S per lane: about one wavefront per SIMD over the whole launch (2 * FB bucket reads over ~64K lanes)
-    int S = 1;
-    while (S < 16 && (2.0 * (double)p.FB) / S > 98304.0) S <<= 1;
-    if (tune.marg_s) { const int v = tune.marg_s; if (v >= 1 && v <= 64 && (v & (v - 1)) == 0) S = v; }
-    g.SR = std::min(S, g.LO); g.SC = std::min(S, g.HI);
-    g.PR = g.LO / g.SR; g.PC = g.HI / g.SC;
-    while (g.PR > 64) { g.PR >>= 1; g.SR <<= 1; }                        // the segmented tree lives inside one wavefront
-    while (g.PC > 64) { g.PC >>= 1; g.SC <<= 1; }
-    g.row_tiles = (uint32_t)(((size_t)g.HI * g.PR + 63) / 64); g.col_tiles = (uint32_t)(((size_t)g.LO * g.PC + 63) / 64);
-    g.TR = g.HI / 16; g.TC = g.LO / 16; g.quad = !tune.tail_scalar && g.TR >= 1 && g.TC <= 16;     // HI, LO: powers of two in [16, 256]
-  }
-  // slice length: short enough to keep >= ~150K lanes (two to four wavefronts per SIMD), but at least a quarter of a bucket's
-  // expected entries, so that a bucket straddles few lanes and stays on the serial merge path (sweep_window.py table)
-  if (batch == 1 && !flat) {
-    const uint64_t occ = n / (uint64_t)p.M;
-    int lo = 8; while (lo < 64 && (uint64_t)(4 * lo) < occ) lo <<= 1;
-    p.L = 64; while (p.L > lo && p.total_max / (uint64_t)p.L < 150000) p.L >>= 1;
+// 1. digits; the first kernel of the call also zeroes its counters and the scan's tile sums
+static void msm_digits(bppp_ctx *ctx, const MsmPlan &p, const MsmWorkspace &ws, const void *d_scalars) {
+  const uint64_t total_sc = (uint64_t)p.batch * p.n;
+  k_digits<<<dim3((unsigned)((total_sc + 255) / 256)), dim3(256), 0, ctx->stream>>>((const uint32_t *)d_scalars, total_sc, (uint32_t)p.n, ws.stride, p.c, p.W, p.acnt, p.top,
+                                                                                     make_recode_k(p.c, p.W, p.acnt, p.top >= 0), ws.dig, ws.negmask, ws.heavy_count,
+                                                                                     (uint32_t)ws.nzero, ws.tiles, (uint32_t)p.ntiles);
+}
+
+// 2. sort
+static void msm_sort(bppp_ctx *ctx, const MsmPlan &p, const MsmWorkspace &ws, size_t table_stride) {
+  hipStream_t st = ctx->stream;
+  const size_t lds = sort_lds_bytes(p);
+  const uint32_t n = (uint32_t)p.n;
+  k_hist<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(ws.dig, n, ws.stride, p.c, p.CH, ws.blockhist);
+  // flat: the (window, chunk) histograms of an instance are W * CH chunks of ONE bucket set (same memory layout)
+  k_count_tiles<<<dim3((unsigned)((p.FB + 255) / 256)), dim3(256), 0, st>>>(ws.blockhist, p.M, p.flat ? p.W * p.CH : p.CH, p.FB, ws.count, ws.tiles);
+  k_scan_apply<<<dim3(p.ntiles), dim3(256), 0, st>>>(ws.count, p.FB, ws.tiles, ws.start, ws.size_hist);
+  ctx->last_sort_ranges = p.Q;
+  ctx->last_windows = p.W;
+  ctx->last_scatter_one_read = p.one_read ? 1 : 0;
+  if (p.one_read) {
+    // 8 slots x ceil(W / 8) windows x CH chunks; the cursors of all M buckets take the whole request, which leaves ONE workgroup per CU
+    k_scatter_one_read<<<dim3(ranged_grid(p)), dim3(p.hist_threads), lds, st>>>(ws.dig, ws.negmask, n, ws.stride, p.c, p.CH, p.Q, (uint32_t)p.W, p.top, ws.blockhist,
+                                                                                ws.start, ws.sorted);
+  } else if (p.Q) {
+    // units (window, range); 8 slots x ceil(U / 8) units x CH chunks
+    k_scatter_ranges<<<dim3(ranged_grid(p)), dim3(p.hist_threads), ranges_lds_bytes(p), st>>>(ws.dig, ws.negmask, n, ws.stride, p.c, p.CH, p.Q, ranges_units(p), p.top,
+                                                                                              ws.blockhist, ws.start, ws.sorted);
+  } else
+    k_scatter<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(ws.dig, ws.negmask, n, ws.stride, p.c, p.CH, p.W, ws.blockhist, ws.start, ws.sorted,
+                                                                             p.flat ? (uint32_t)table_stride : 0u, p.top);
+}
+
+// 3. accumulate: bucket sums from the sorted entries, then the buckets left in several partial sums
+static int msm_accumulate(bppp_ctx *ctx, const MsmPlan &p, const MsmWorkspace &ws, const void *d_points, int shared_points) {
+  hipStream_t st = ctx->stream;
+  uint2 *items = (uint2 *)ws.items, *heavy_items = (uint2 *)ws.heavy_items;
+  uint4 *heavy_buckets = (uint4 *)ws.heavy_buckets;
+  ctx->last_acc_sized = p.sized ? 1 : 0;
+  ctx->last_acc_fq29 = p.fq29 ? 1 : 0;
+  // the ordering pass has to precede the accumulation, so its time is booked with acc_points; acc_points + acc_records is the accumulation
+  // on either route
+  if (p.sized)
+    k_order<<<dim3(p.ntiles), dim3(256), 0, st>>>(ws.count, p.FB, ws.size_hist, ws.cursors, items, ws.piece_base, ws.buckets, heavy_items, ws.heavy_slot, heavy_buckets,
+                                                  ws.heavy_count);
+  int rc = run_pre_acc(ctx); if (rc) return rc;
+  if (p.sized) {
+    (p.fq29 ? k_acc_points_sized29 : k_acc_points_sized)<<<dim3((unsigned)((ws.items_max + 255) / 256)), dim3(256), 0, st>>>(
+        ws.sorted, ws.start, ws.count, items, ws.heavy_count, ws.piece_base, (const uint32_t *)d_points, ws.buckets, ws.rec_pt);
+    prof_mark(ctx, 3);
+    k_merge_heavy<true><<<dim3(2048), dim3(64), 0, st>>>(ws.start, ws.count, 0, ws.rec_pt, ws.piece_base, ws.buckets, heavy_items, ws.heavy_slot, heavy_buckets,
+                                                         ws.heavy_count, ws.chunk_sums);
   } else {
-    p.L = 4;
-    while (p.L < 64 && p.total_max / (uint64_t)(2 * p.L) >= 65536) p.L <<= 1;
+    k_acc_points<<<dim3((unsigned)((p.G + 255) / 256)), dim3(256), 0, st>>>(ws.sorted, ws.start, (uint32_t)p.FB, (const uint32_t *)d_points, (uint32_t)p.n,
+                                                                            (uint32_t)(p.Wc * p.M), shared_points, p.L, p.G, ws.buckets, ws.rec_pt);
+    prof_mark(ctx, 3);
+    k_merge<<<dim3((unsigned)((p.FB + 255) / 256)), dim3(256), 0, st>>>(ws.start, ws.count, p.FB, p.L, ws.rec_pt, ws.buckets, heavy_items, ws.heavy_slot, heavy_buckets,
+                                                                        ws.heavy_count);
+    k_merge_heavy<false><<<dim3(2048), dim3(64), 0, st>>>(ws.start, ws.count, p.L, ws.rec_pt, nullptr, ws.buckets, heavy_items, ws.heavy_slot, heavy_buckets,
+                                                          ws.heavy_count, ws.chunk_sums);
   }
-  // one bucket set for all windows: buckets hold W times more entries; a longer slice keeps a bucket within a few lanes (the
-  // serial merge path) while the launch still has two wavefronts per SIMD
-  // (L = 256 leaves one wavefront per SIMD and the gathers are no longer hidden: 1.39 ms against 1.15 ms at 2^20)
-  if (flat) while (p.L < 128 && (double)p.total_max / (double)p.FB > 4.0 * p.L && p.total_max / (uint64_t)(2 * p.L) >= 65536) p.L <<= 1;
-  if (tune.lacc >= 1 && tune.lacc <= 4096) p.L = tune.lacc;
-  p.G = (p.total_max + p.L - 1) / p.L; if (!p.G) p.G = 1;
-  p.ntiles = (int)((p.FB + SCAN_TILE - 1) / SCAN_TILE);
-  // sized accumulation: one MSM over arbitrary points.  The default is by measurement ("whole buckets by size"): at 2^20 terms
-  // and c = 16 the accumulation stage falls 1.113 -> 1.010 ms; at 2^16 and c = 13 it has 86 K items of 16 entries, a third of the chip's wave
-  // slots on chains twice as long as the slices', and rises 0.186 -> 0.311 ms
-  p.sized = batch == 1 && !flat && !tune.acc_lds && (tune.acc_sized > 0 || (tune.acc_sized < 0 && c == 16));
-  // on 9 x 29-bit limbs by default ("9 x 29-bit limbs"): accumulation 1.010 -> 0.892 ms at 2^20 terms, 8 interleaved pairs
-  p.fq29 = p.sized && tune.acc_fq29 != 0;
-  return p;
+  return BPPP_OK;
+}
+
+// 4. bucket reduce
+static void msm_reduce(bppp_ctx *ctx, const MsmPlan &p, const MsmWorkspace &ws) {
+  hipStream_t st = ctx->stream;
+  if (p.RG) {
+    k_reduce_groups<<<dim3((unsigned)((p.NS * p.RG + 63) / 64)), dim3(64), 0, st>>>(ws.buckets, p.M, p.RG, (uint32_t)p.NS, ws.winsum);
+  } else if (p.marg) {
+    uint32_t *Rm = ws.red, *Cm = ws.red + (size_t)p.NS * p.mg.HI * XYZZ_WORDS;
+    k_reduce_marg<<<dim3(p.mg.row_tiles + p.mg.col_tiles, (unsigned)p.NS), dim3(64), 0, st>>>(ws.buckets, p.M, p.mg, Rm, Cm);
+    k_reduce_tail_quad<<<dim3((unsigned)(p.mg.TR + p.mg.TC), (unsigned)p.NS), dim3(64), 0, st>>>(Rm, Cm, p.mg, ws.tail_part, ws.tail_cnt, ws.winsum);
+  } else {
+    k_reduce1<<<dim3((unsigned)p.NS, p.WPW), dim3(64), 0, st>>>(ws.buckets, p.M, p.Lw, p.WPW, ws.red);
+    k_reduce2<<<dim3((unsigned)p.NS), dim3(64), 0, st>>>(ws.red, p.Lw, p.WPW, ws.winsum);
+  }
+}
+
+// 5. window combine: left in HBM and not waited for (d_out_dev), on the device for a batch, on the host for up to four MSMs
+static int msm_finish(bppp_ctx *ctx, const MsmPlan &p, const MsmWorkspace &ws, uint64_t *out_xy, uint32_t *d_out_dev) {
+  using namespace bppp_host;
+  hipStream_t st = ctx->stream;
+  const size_t batch = p.batch;
+  const int a = p.marg ? p.mg.a : 0;
+  if (d_out_dev) {
+    k_window_combine<<<dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, st>>>(ws.winsum, p.Wc, p.c, a, (uint32_t)batch, d_out_dev);
+    BPPP_HIP(ctx, hipGetLastError());
+    return BPPP_OK;
+  }
+  if (batch > 4) {
+    k_window_combine<<<dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, st>>>(ws.winsum, p.Wc, p.c, a, (uint32_t)batch, ws.out_aff);
+    BPPP_HIP(ctx, hipMemcpyAsync(out_xy, ws.out_aff, batch * 64, hipMemcpyDeviceToHost, st));
+    prof_mark(ctx, 6);
+    BPPP_HIP(ctx, hipStreamSynchronize(st));
+  } else {
+    size_t bytes = (size_t)p.NS * (p.marg ? 2 : 1) * XYZZ_WORDS * 4;
+    int rc = ensure_pinned(ctx, bytes); if (rc) return rc;
+    BPPP_HIP(ctx, hipMemcpyAsync(ctx->pinned, ws.winsum, bytes, hipMemcpyDeviceToHost, st));
+    prof_mark(ctx, 6);
+    BPPP_HIP(ctx, hipStreamSynchronize(st));
+    const uint32_t *wsum = (const uint32_t *)ctx->pinned;
+    // a flat table has one bucket set and windows of c bits throughout; the marginal reduction leaves (W1, W2) per window
+    for (size_t b = 0; b < batch; b++)
+      window_combine_host(wsum + b * p.Wc * (p.marg ? 2 : 1) * XYZZ_WORDS, p.Wc, p.c, p.flat ? p.Wc : p.acnt, p.marg, a, out_xy + 8 * b);
+  }
+  BPPP_HIP(ctx, hipGetLastError());
+  prof_collect(ctx, 7);
+  return BPPP_OK;
 }
 
 int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_t n, size_t batch, int shared_points, int window_bits, uint64_t *out_xy,
@@ -1348,193 +1208,38 @@ int msm_batch_dev(bppp_ctx *ctx, const void *d_scalars, const void *d_points, si
 // all windows of an instance share one bucket set, so there is one bucket reduction per instance and no window combine
 int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_t n, size_t batch, int shared_points, int window_bits, uint64_t *out_xy,
                size_t table_stride, uint32_t *d_out_dev) {
-  using namespace bppp_host;
   if (!out_xy) return fail(ctx, BPPP_ERR_ARG, "msm: null output");
   if (n == 0 || batch == 0) { memset(out_xy, 0, 64 * (batch ? batch : 1)); return BPPP_OK; }
   if (!d_scalars || !d_points) return fail(ctx, BPPP_ERR_ARG, "msm: null input");
   if (n >= (1ull << 31)) return fail(ctx, BPPP_ERR_ARG, "msm: n must be < 2^31");
-  // ---- one small or mid-size MSM: k_msm_small over (window, slice of <= 4096 terms) workgroups, the slices of a window joined by one
-  // wavefront each, then the host's Horner combine over the W window sums
-  const size_t small_max = ctx->tune.small_max ? (size_t)ctx->tune.small_max : MSM_SMALL_DEFAULT_MAX;
-  if (batch == 1 && !table_stride && !window_bits && n <= small_max && !ctx->tune.no_small && !d_out_dev) {
-    const int c = ctx->tune.small_c >= 5 && ctx->tune.small_c <= 8 ? ctx->tune.small_c : 6, M = 1 << (c - 1);
-    const WindowLayout wl = window_layout(c, 256 % c != 0 && !ctx->tune.no_balance);
-    const int W = wl.W, acnt = wl.acnt;
-    size_t len = ctx->tune.small_len >= 64 && ctx->tune.small_len <= (int)MSM_SMALL_MAX ? (size_t)ctx->tune.small_len : (n <= 2048 ? 512 : 1024);
-    if (n <= len + len / 2) len = n;                                  // a second slice has to pay for the join launch
-    const size_t S = (n + len - 1) / len;
-    Carver cv0(nullptr, 0);
-    cv0.take<uint32_t>((size_t)W * S * XYZZ_WORDS); cv0.take<uint32_t>((size_t)W * XYZZ_WORDS);
-    int rc = ensure_workspace(ctx, cv0.off); if (rc) return rc;
-    Carver cv(ctx->ws, ctx->ws_bytes);
-    uint32_t *partials = cv.take<uint32_t>((size_t)W * S * XYZZ_WORDS), *winsum = cv.take<uint32_t>((size_t)W * XYZZ_WORDS);
-    const size_t bytes = (size_t)W * XYZZ_WORDS * 4;
-    rc = ensure_pinned(ctx, bytes); if (rc) return rc;
-    hipStream_t st = ctx->stream;
-    ctx->last_windows = W;
-    for (int i = 0; i <= 2; i++) prof_mark(ctx, i);
-    if (ctx->pre_acc) { auto f = ctx->pre_acc; ctx->pre_acc = nullptr; int rc_ = f(ctx->pre_acc_arg); if (rc_) return rc_; }
-    const size_t lds = (((size_t)(2 * M + 1) + len + (len + 1) / 2 + 3) & ~(size_t)3) * 4 + (size_t)(M + 4) * XYZZ_WORDS * 4;
-    k_msm_small<<<dim3((unsigned)W, (unsigned)S), dim3(256), lds, st>>>((const uint32_t *)d_scalars, (const uint32_t *)d_points, (uint32_t)n, (uint32_t)len, c,
-                                                                       acnt, wl.top, make_recode_k(c, W, acnt, wl.top >= 0), S > 1 ? partials : winsum);
-    if (S > 1) k_msm_small_join<<<dim3((unsigned)W), dim3(64), 0, st>>>(partials, (uint32_t)S, winsum);
-    for (int i = 3; i <= 5; i++) prof_mark(ctx, i);
-    BPPP_HIP(ctx, hipMemcpyAsync(ctx->pinned, winsum, bytes, hipMemcpyDeviceToHost, st));
-    prof_mark(ctx, 6);
-    BPPP_HIP(ctx, hipStreamSynchronize(st));
-    window_combine_host((const uint32_t *)ctx->pinned, W, c, acnt, false, 0, out_xy);
-    BPPP_HIP(ctx, hipGetLastError());
-    prof_collect(ctx, 7);
-    return BPPP_OK;
-  }
+  if (msm_small_route(n, batch, window_bits, table_stride, d_out_dev != nullptr, ctx->tune)) return msm_small(ctx, d_scalars, d_points, n, out_xy);
   int c = window_bits ? window_bits : choose_window(n, batch, ctx->tune);
   if (!window_bits && ctx->tune.window_batched) { const int v = ctx->tune.window_batched; if (batch > 4 && v >= 2 && v <= 16) c = v; }   // tuning sweeps
   if (c < 2 || c > 16) return fail(ctx, BPPP_ERR_ARG, "msm: window_bits must be in [2,16]");
   const bool flat = table_stride != 0;
   if (flat && (!window_bits || shared_points != 1 || n > table_stride || (uint64_t)(256 / c + 1) * table_stride >= (1ull << 31)))
     return fail(ctx, BPPP_ERR_ARG, "msm: bad precomputed-table arguments");
-  MsmPlan p = make_plan(n, batch, c, flat, ctx->tune);
+  const MsmPlan p = make_plan(n, batch, c, flat, ctx->tune);
   if (p.FB >= (1ull << 32) - 1 || p.total_max >= (1ull << 32) - 1)
     return fail(ctx, BPPP_ERR_ARG, "msm: batch*windows*buckets or batch*n*windows exceeds 2^32; split the batch");
+  // the workspace: laid out once over a null base for its size, once over the real one
+  Carver sizing(nullptr, 0);
+  carve(sizing, p, n, batch);
+  int rc = ensure_workspace(ctx, sizing.off); if (rc) return rc;
+  Carver cv(ctx->ws, ctx->ws_bytes);
+  const MsmWorkspace ws = carve(cv, p, n, batch);
+  rc = msm_sort_lds(ctx, p); if (rc) return rc;
 
-  // ---- carve the workspace
-  size_t need = 0;
-  for (int pass = 0; pass < 2; pass++) {
-    Carver cv(pass ? ctx->ws : nullptr, ctx->ws_bytes);
-    const uint32_t stride = (uint32_t)((n + 7) & ~(size_t)7);     // digit rows are 16-byte aligned
-    uint16_t *dig = cv.take<uint16_t>((size_t)p.NB * stride + 8);
-    unsigned long long *negmask = cv.take<unsigned long long>((batch * n + 63) / 64 + 1);
-    uint32_t *blockhist = cv.take<uint32_t>((size_t)p.NB * p.CH * p.M);
-    uint32_t *count = cv.take<uint32_t>(p.FB + 1);
-    uint32_t *start = cv.take<uint32_t>(p.FB + 1);
-    uint32_t *tiles = cv.take<uint32_t>(p.ntiles + 1);
-    uint32_t *sorted = cv.take<uint32_t>(p.total_max + 4);
-    uint32_t *buckets = cv.take<uint32_t>((size_t)p.FB * XYZZ_WORDS);
-    // sized: a bucket of several pieces has more than ACC_CAP entries and ceil(count / ACC_CAP) <= 2 count / ACC_CAP pieces, so there are at
-    // most total / ACC_CAP such buckets, 2 total / ACC_CAP piece sums (they take rec_pt's place) and total / ACC_CAP + 2 total / (ACC_CAP *
-    // HEAVY_CHUNK) (bucket, chunk) items; every non-empty bucket adds at most one item to the total / ACC_CAP full pieces
-    const size_t tcap = (size_t)(p.total_max / ACC_CAP);
-    const size_t items_max = std::min<size_t>((size_t)p.total_max, (size_t)p.FB + tcap);
-    uint32_t *rec_pt = cv.take<uint32_t>((p.sized ? 2 * tcap + 2 : (size_t)p.G * 2) * XYZZ_WORDS);
-    uint2 *items = cv.take<uint2>(p.sized ? items_max + 1 : 0);
-    uint32_t *piece_base = cv.take<uint32_t>(p.sized ? (size_t)p.FB : 0);
-    // heavy buckets span > 9 lanes: at most G/9 of them, and at most G/256 + G/9 (bucket, chunk) items
-    size_t hmax = p.sized ? tcap + 2 * tcap / HEAVY_CHUNK + 4 : (size_t)(p.G / 8 + 2);
-    uint2 *heavy_items = cv.take<uint2>(hmax);
-    uint4 *heavy_buckets = cv.take<uint4>(hmax);
-    uint32_t *chunk_sums = cv.take<uint32_t>(hmax * XYZZ_WORDS);
-    // counters and tickets, zeroed by k_digits (with the scan's tile sums): [0], [1] heavy items / buckets, [2], [3] the sized route's piece
-    // slots / items, [4..] k_reduce_tail_quad's tickets, then the sized route's size histogram and class cursors
-    const size_t ntail = p.marg ? 2 * (size_t)p.NS : 0, nzero = 4 + ntail + (p.sized ? 2 * ACC_CAP * ACC_LINE : 0);
-    uint32_t *heavy_count = cv.take<uint32_t>(nzero);
-    uint32_t *tail_cnt = heavy_count + 4;
-    uint32_t *size_hist = p.sized ? tail_cnt + ntail : nullptr, *cursors = p.sized ? size_hist + ACC_CAP * ACC_LINE : nullptr;
-    uint32_t *tail_part = cv.take<uint32_t>(p.marg && p.mg.quad ? (size_t)p.NS * 2 * 16 * 2 * XYZZ_WORDS : 0);
-    uint32_t *red = cv.take<uint32_t>(p.marg ? (size_t)p.NS * (p.mg.HI + p.mg.LO) * XYZZ_WORDS : (size_t)p.NS * p.WPW * 2 * XYZZ_WORDS);
-    uint32_t *winsum = cv.take<uint32_t>((size_t)p.NS * 2 * XYZZ_WORDS);
-    uint32_t *out_aff = cv.take<uint32_t>((size_t)batch * 16);
-    uint32_t *heavy_slot = cv.take<uint32_t>(hmax);     // per heavy item: its bucket's entry in heavy_buckets (the chunks' ticket)
-    if (!pass) { need = cv.off; int rc = ensure_workspace(ctx, need); if (rc) return rc; continue; }
-
-    hipStream_t st = ctx->stream;
-    const size_t lds = (size_t)p.M * 4;
-    if (lds > 64 * 1024 && lds > ctx->sort_lds_set) {
-      BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter_ranges, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_scatter_one_read, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      ctx->sort_lds_set = lds;
-    }
-    prof_mark(ctx, 0);
-    // 1. digits
-    uint64_t total_sc = (uint64_t)batch * n;
-    k_digits<<<dim3((unsigned)((total_sc + 255) / 256)), dim3(256), 0, st>>>((const uint32_t *)d_scalars, total_sc, (uint32_t)n, stride, c, p.W, p.acnt, p.top,
-                                                                            make_recode_k(c, p.W, p.acnt, p.top >= 0), dig, negmask, heavy_count, (uint32_t)nzero, tiles, (uint32_t)p.ntiles);
-    prof_mark(ctx, 1);
-    // 2. sort
-    k_hist<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(dig, (uint32_t)n, stride, c, p.CH, blockhist);
-    // flat: the (window, chunk) histograms of an instance are W * CH chunks of ONE bucket set (same memory layout)
-    k_count_tiles<<<dim3((unsigned)((p.FB + 255) / 256)), dim3(256), 0, st>>>(blockhist, p.M, p.flat ? p.W * p.CH : p.CH, p.FB, count, tiles);
-    k_scan_apply<<<dim3(p.ntiles), dim3(256), 0, st>>>(count, p.FB, tiles, start, size_hist);
-    ctx->last_sort_ranges = p.Q;
-    ctx->last_windows = p.W;
-    ctx->last_scatter_one_read = p.one_read ? 1 : 0;
-    if (p.one_read) {
-      // 8 slots x ceil(W / 8) windows x CH chunks; the cursors of all M buckets take the whole request, which leaves ONE workgroup per CU
-      k_scatter_one_read<<<dim3(8u * (((uint32_t)p.W + 7) / 8) * p.CH), dim3(p.hist_threads), lds, st>>>(
-          dig, negmask, (uint32_t)n, stride, c, p.CH, p.Q, (uint32_t)p.W, p.top, blockhist, start, sorted);
-    } else if (p.Q) {
-      const uint32_t U = (uint32_t)p.W * p.Q;                // units (window, range); 8 slots x ceil(U / 8) units x CH chunks
-      // the cursors take lds / Q bytes; the request is for more than half of a CU's 160 KiB, so that ONE workgroup is resident per CU (k_scatter_ranges)
-      const size_t lds_one = std::max<size_t>(lds / p.Q, 84 * 1024);
-      k_scatter_ranges<<<dim3(8u * ((U + 7) / 8) * p.CH), dim3(p.hist_threads), lds_one, st>>>(dig, negmask, (uint32_t)n, stride, c, p.CH, p.Q, U,
-                                                                                               p.top, blockhist, start, sorted);
-    } else
-      k_scatter<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(dig, negmask, (uint32_t)n, stride, c, p.CH, p.W, blockhist, start, sorted,
-                                                                               p.flat ? (uint32_t)table_stride : 0u, p.top);
-    prof_mark(ctx, 2);
-    // 3. accumulate
-    ctx->last_acc_lds = ctx->tune.acc_lds ? 1 : 0;
-    ctx->last_acc_sized = p.sized ? 1 : 0;
-    ctx->last_acc_fq29 = p.fq29 ? 1 : 0;
-    // the ordering pass has to precede the accumulation, so its time is booked with acc_points; acc_points + acc_records is the accumulation
-    // on either route
-    if (p.sized)
-      k_order<<<dim3(p.ntiles), dim3(256), 0, st>>>(count, p.FB, size_hist, cursors, items, piece_base, buckets, heavy_items, heavy_slot,
-                                                                          heavy_buckets, heavy_count);
-    if (ctx->pre_acc) { auto f = ctx->pre_acc; ctx->pre_acc = nullptr; int rc_ = f(ctx->pre_acc_arg); if (rc_) return rc_; }
-    if (p.sized) {
-      (p.fq29 ? k_acc_points_sized29 : k_acc_points_sized)<<<dim3((unsigned)((items_max + 255) / 256)), dim3(256), 0, st>>>(
-          sorted, start, count, items, heavy_count, piece_base, (const uint32_t *)d_points, buckets, rec_pt);
-      prof_mark(ctx, 3);
-      k_merge_heavy<true><<<dim3(2048), dim3(64), 0, st>>>(start, count, 0, rec_pt, piece_base, buckets, heavy_items, heavy_slot, heavy_buckets, heavy_count, chunk_sums);
-    } else {
-      (ctx->tune.acc_lds ? k_acc_points_lds : k_acc_points)<<<dim3((unsigned)((p.G + 255) / 256)), dim3(256), 0, st>>>(
-          sorted, start, (uint32_t)p.FB, (const uint32_t *)d_points, (uint32_t)n, (uint32_t)(p.Wc * p.M), shared_points, p.L, p.G, buckets, rec_pt);
-      prof_mark(ctx, 3);
-      k_merge<<<dim3((unsigned)((p.FB + 255) / 256)), dim3(256), 0, st>>>(start, count, p.FB, p.L, rec_pt, buckets, heavy_items, heavy_slot, heavy_buckets, heavy_count);
-      k_merge_heavy<false><<<dim3(2048), dim3(64), 0, st>>>(start, count, p.L, rec_pt, nullptr, buckets, heavy_items, heavy_slot, heavy_buckets, heavy_count, chunk_sums);
-    }
-    prof_mark(ctx, 4);
-    // 4. bucket reduce
-    if (p.RG) {
-      k_reduce_groups<<<dim3((unsigned)((p.NS * p.RG + 63) / 64)), dim3(64), 0, st>>>(buckets, p.M, p.RG, (uint32_t)p.NS, winsum);
-    } else if (p.marg) {
-      uint32_t *Rm = red, *Cm = red + (size_t)p.NS * p.mg.HI * XYZZ_WORDS;
-      k_reduce_marg<<<dim3(p.mg.row_tiles + p.mg.col_tiles, (unsigned)p.NS), dim3(64), 0, st>>>(buckets, p.M, p.mg, Rm, Cm);
-      if (p.mg.quad) k_reduce_tail_quad<<<dim3((unsigned)(p.mg.TR + p.mg.TC), (unsigned)p.NS), dim3(64), 0, st>>>(Rm, Cm, p.mg, tail_part, tail_cnt, winsum);
-      else k_reduce_tail<<<dim3((unsigned)p.NS, 2), dim3(64u * (unsigned)((p.mg.LO + 63) / 64)), 0, st>>>(Rm, Cm, p.mg, winsum);
-    } else {
-      k_reduce1<<<dim3((unsigned)p.NS, p.WPW), dim3(64), 0, st>>>(buckets, p.M, p.Lw, p.WPW, red);
-      k_reduce2<<<dim3((unsigned)p.NS), dim3(64), 0, st>>>(red, p.Lw, p.WPW, winsum);
-    }
-    prof_mark(ctx, 5);
-    // 5. window combine
-    if (d_out_dev) {
-      k_window_combine<<<dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, st>>>(winsum, p.Wc, c, p.marg ? p.mg.a : 0, (uint32_t)batch, d_out_dev);
-      BPPP_HIP(ctx, hipGetLastError());
-      return BPPP_OK;
-    }
-    if (batch > 4) {
-      k_window_combine<<<dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, st>>>(winsum, p.Wc, c, p.marg ? p.mg.a : 0, (uint32_t)batch, out_aff);
-      BPPP_HIP(ctx, hipMemcpyAsync(out_xy, out_aff, batch * 64, hipMemcpyDeviceToHost, st));
-      prof_mark(ctx, 6);
-      BPPP_HIP(ctx, hipStreamSynchronize(st));
-    } else {
-      size_t bytes = (size_t)p.NS * (p.marg ? 2 : 1) * XYZZ_WORDS * 4;
-      int rc = ensure_pinned(ctx, bytes); if (rc) return rc;
-      BPPP_HIP(ctx, hipMemcpyAsync(ctx->pinned, winsum, bytes, hipMemcpyDeviceToHost, st));
-      prof_mark(ctx, 6);
-      BPPP_HIP(ctx, hipStreamSynchronize(st));
-      const uint32_t *ws = (const uint32_t *)ctx->pinned;
-      // a flat table has one bucket set and windows of c bits throughout; the marginal reduction leaves (W1, W2) per window
-      for (size_t b = 0; b < batch; b++)
-        window_combine_host(ws + b * p.Wc * (p.marg ? 2 : 1) * XYZZ_WORDS, p.Wc, c, p.flat ? p.Wc : p.acnt, p.marg, p.marg ? p.mg.a : 0, out_xy + 8 * b);
-    }
-    BPPP_HIP(ctx, hipGetLastError());
-    prof_collect(ctx, 7);
-  }
-  return BPPP_OK;
+  prof_mark(ctx, 0);
+  msm_digits(ctx, p, ws, d_scalars);
+  prof_mark(ctx, 1);
+  msm_sort(ctx, p, ws, table_stride);
+  prof_mark(ctx, 2);
+  rc = msm_accumulate(ctx, p, ws, d_points, shared_points); if (rc) return rc;   // prof_mark 3 between the accumulation and the merges
+  prof_mark(ctx, 4);
+  msm_reduce(ctx, p, ws);
+  prof_mark(ctx, 5);
+  return msm_finish(ctx, p, ws, out_xy, d_out_dev);                              // prof_mark 6 after the copy is queued
 }
 
 }  // namespace bppp

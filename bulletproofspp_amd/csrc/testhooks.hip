@@ -341,12 +341,6 @@ extern "C" int bppp_test_last_mixed_msm_terms(bppp_ctx *ctx, uint64_t *terms) {
   return BPPP_OK;
 }
 
-extern "C" int bppp_test_last_acc_kernel(bppp_ctx *ctx, int *lds) {
-  if (!ctx || !lds) return BPPP_ERR_ARG;
-  *lds = ctx->last_acc_lds;
-  return BPPP_OK;
-}
-
 extern "C" int bppp_test_last_sort_ranges(bppp_ctx *ctx, int *q) {
   if (!ctx || !q) return BPPP_ERR_ARG;
   *q = ctx->last_sort_ranges;

@@ -45,9 +45,6 @@ int bppp_test_mulmod_rate(bppp_ctx *ctx, int iters, double *mulmods_per_sec);
 /* Terms of the one MSM the last bppp_rp_verify_mixed* call on this context ran (0 after an empty job): a test sees that the shared
  * bases of setups from one point stream were merged. */
 int bppp_test_last_mixed_msm_terms(bppp_ctx *ctx, uint64_t *terms);
-/* The accumulate kernel the last MSM of the general pipeline on this context launched: 0 = k_acc_points, 1 = k_acc_points_lds
- * (BPPP_ACC_LDS), -1 = none yet. */
-int bppp_test_last_acc_kernel(bppp_ctx *ctx, int *lds);
 /* The scatter the last MSM of the general pipeline on this context launched: 0 = k_scatter, 2 or 4 = k_scatter_ranges with that many
  * bucket ranges per window (BPPP_SORT_RANGES; one MSM over arbitrary points with 16-bit windows only), -1 = none yet. */
 int bppp_test_last_sort_ranges(bppp_ctx *ctx, int *q);

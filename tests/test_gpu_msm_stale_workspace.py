@@ -1,10 +1,9 @@
 """The general MSM pipeline no longer clears its bucket array between calls: an empty bucket is marked by k_merge, every other one is
 written before a reduction reads it.  These tests run a SPARSE call right after a DENSE one on the same context (same n, same window
 width, hence the same workspace layout), so that a bucket left over from the first call would show in the second; and they run
-k_acc_points_lds (BPPP_ACC_LDS, read when a context is created) beside k_acc_points on inputs that reach every branch of the kernel.
+k_acc_points (13-bit windows, batches) and the sized accumulation (16-bit windows) on inputs that reach every branch of the kernel.
 Every expected value comes from the oracle (oracle/pyoracle.py), never from the library."""
 import ctypes
-import os
 import random
 
 import numpy as np
@@ -116,55 +115,22 @@ def test_sparse_call_after_dense_call_registered_basis(gpu, oracle_lib, batch):
         basis.close()
 
 
-# ---- k_acc_points_lds beside k_acc_points
-@pytest.fixture(scope="module")
-def both_kernels():
-    """two contexts: BPPP_ACC_LDS=0 (k_acc_points) and BPPP_ACC_LDS=1 (k_acc_points_lds); the environment is read at creation"""
-    import bulletproofspp_amd as b
-    old = os.environ.get("BPPP_ACC_LDS")
-    ctxs = []
+# ---- the accumulate kernels on constructed inputs
+def _run(g, sc_arr, pt_arr, n, c):
+    ds, dp = g.to_device(sc_arr), g.to_device(pt_arr)
     try:
-        for v in ("0", "1"):
-            os.environ["BPPP_ACC_LDS"] = v
-            ctxs.append(b.Bppp(0))
+        return g.msm_device(ds, dp, n, window_bits=c)
     finally:
-        if old is None:
-            os.environ.pop("BPPP_ACC_LDS", None)
-        else:
-            os.environ["BPPP_ACC_LDS"] = old
-    yield ctxs
-    for c in ctxs:
-        c.close()
-
-
-def _assert_kernels(ctxs):
-    """the first context's last MSM ran k_acc_points, the second's k_acc_points_lds: the switch is wired, not merely set"""
-    from bulletproofspp_amd.capi import load_test_library
-    tl = load_test_library()
-    for want, g in enumerate(ctxs):
-        k = ctypes.c_int(-2)
-        assert tl.bppp_test_last_acc_kernel(g.h, ctypes.byref(k)) == 0 and k.value == want, (want, k.value)
-
-
-def _run_both(ctxs, sc_arr, pt_arr, n, c):
-    out = []
-    for g in ctxs:
-        ds, dp = g.to_device(sc_arr), g.to_device(pt_arr)
-        try:
-            out.append(g.msm_device(ds, dp, n, window_bits=c))
-        finally:
-            g.free(ds); g.free(dp)
-    _assert_kernels(ctxs)
-    return out
+        g.free(ds); g.free(dp)
 
 
 @pytest.mark.parametrize("c", [13, 16])
-def test_lds_kernel_edge_inputs(both_kernels, oracle_lib, big_points, c):
+def test_acc_kernel_edge_inputs(gpu, oracle_lib, big_points, c):
     """Infinity points, zero scalars, repeated and cancelling points inside a run, n not a multiple of 64.  One input in 64 is the point at
     infinity: slices are cut in SORTED order (a lane owns L consecutive sorted entries), so with ~5000 slices per call and a 1-in-64 density
     such entries fall on first and last slice positions by chance many times over, they are not placed there.  Zero scalars never reach
     the kernel (the sort drops zero digits); they shift every later entry's position.  The constructed boundary case is
-    test_lds_kernel_runs_that_end_on_slice_boundaries."""
+    test_acc_kernel_runs_that_end_on_slice_boundaries."""
     n = N_BIG
     rnd = random.Random(23)
     sc = [rnd.randrange(O.N) for _ in range(n)]
@@ -178,12 +144,11 @@ def test_lds_kernel_edge_inputs(both_kernels, oracle_lib, big_points, c):
         pts[i + 2, 4:] = int_to_limbs((O.P - limbs_to_int(pts[i, 4:])) % O.P)
         sc[i + 1] = sc[i + 2] = sc[i]
     sarr = scalars_to_array(sc)
-    got = _run_both(both_kernels, sarr, pts, n, c)
-    assert got[0] == got[1] == _oracle(oracle_lib, sarr, pts)
+    assert _run(gpu, sarr, pts, n, c) == _oracle(oracle_lib, sarr, pts)
 
 
 @pytest.mark.parametrize("c", [13, 16])
-def test_lds_kernel_runs_that_end_on_slice_boundaries(both_kernels, oracle_lib, big_points, c):
+def test_acc_kernel_runs_that_end_on_slice_boundaries(gpu, oracle_lib, big_points, c):
     """Scalars below 2^12 put every entry in window 0, bucket = the scalar: the sorted order is by scalar, then by input index.  Bucket m
     (m = 1, 2, ...) gets exactly 8 * m entries, so with L = 8 entries per lane at this size every run starts AND ends on a slice boundary
     (a multiple of every power of two <= 8), and infinity points sit first and last in their runs.  Whatever L the plan picks, run lengths
@@ -202,19 +167,17 @@ def test_lds_kernel_runs_that_end_on_slice_boundaries(both_kernels, oracle_lib, 
     n = len(sc)
     assert n > 8192
     sarr, parr = scalars_to_array(sc), np.ascontiguousarray(np.stack(pts))
-    got = _run_both(both_kernels, sarr, parr, n, c)
-    assert got[0] == got[1] == _oracle(oracle_lib, sarr, parr)
+    assert _run(gpu, sarr, parr, n, c) == _oracle(oracle_lib, sarr, parr)
 
 
 @pytest.mark.parametrize("c", [13, 16])
-def test_lds_kernel_one_bucket_holds_every_entry(both_kernels, big_points, big_cases, c):
+def test_acc_kernel_one_bucket_holds_every_entry(gpu, big_points, big_cases, c):
     sc, want = big_cases["all_equal"]
-    got = _run_both(both_kernels, sc, big_points, N_BIG, c)
-    assert got[0] == got[1] == want
+    assert _run(gpu, sc, big_points, N_BIG, c) == want
 
 
 @pytest.mark.parametrize("shared", [0, 1, 2])
-def test_lds_kernel_shared_points_modes(both_kernels, oracle_lib, shared):
+def test_acc_kernel_shared_points_modes(gpu, oracle_lib, shared):
     """shared_pts = 0 (a basis per instance), 1 (one basis), d = 2 (one basis per two consecutive instances)"""
     n, batch = 333, 6
     rnd = random.Random(24 + shared)
@@ -225,12 +188,9 @@ def test_lds_kernel_shared_points_modes(both_kernels, oracle_lib, shared):
     sc = [[rnd.randrange(O.N) if rnd.random() > 0.2 else 0 for _ in range(n)] for _ in range(batch)]
     sarr = np.concatenate([scalars_to_array(s) for s in sc])
     parr = np.concatenate([points_to_array(p) for p in bases])
-    outs = []
-    for g in both_kernels:
-        ds, dp = g.to_device(sarr), g.to_device(parr)
-        try:
-            outs.append(g.msm_batch_device(ds, dp, n, batch, shared_points=shared))
-        finally:
-            g.free(ds); g.free(dp)
-    _assert_kernels(both_kernels)
-    assert outs[0] == outs[1] == [oracle_lib.inner_product(list(zip(sc[b], bases[of(b)]))) for b in range(batch)]
+    ds, dp = gpu.to_device(sarr), gpu.to_device(parr)
+    try:
+        got = gpu.msm_batch_device(ds, dp, n, batch, shared_points=shared)
+    finally:
+        gpu.free(ds); gpu.free(dp)
+    assert got == [oracle_lib.inner_product(list(zip(sc[b], bases[of(b)]))) for b in range(batch)]
