@@ -89,8 +89,12 @@ inline bool make_range_data(uint32_t base, const U256 &lo, const U256 &hi, bool 
     // bn1 = 1 + w div (2 (b - 1)) - (b^n1 - 1) div (b - 1)
     U256 bn1 = u_sub(u_add(U256::one(), u_div64(w, 2 * (b - 1))), u_div64(u_sub(pw[n1], U256::one()), b - 1));
     bool ovf = false;
-    U256 first = u_sub(u_sub(w, u_mul64(bn1, b - 1, &ovf)), pw[n1]);
+    const U256 rest = u_add(pw[n1], u_mul64(bn1, b - 1, &ovf));      // b^n1 <= w / 2 here and bn1 (b - 1) <= w / 2 + b - 1: no carry out of 256 bits
     if (ovf) { err = "range arithmetic overflow"; return false; }
+    // 2 <= w < b (n1 = 0, bn1 = 1): the reference's leading coefficient w - b is NEGATIVE, the other one is 1 under a digit of radix b, so the
+    // digits bound value - min by b, not by w.  Compared before the subtraction, which would wrap to 2^256 - (b - w).  No other width gets here.
+    if (u_lt(w, rest)) { err = "range narrower than its digit base: the reference's coefficients do not bound it"; return false; }
+    U256 first = u_sub(w, rest);
     bs.push_back(first); bs.push_back(bn1);
   }
   for (int i = 1; i <= n1; i++) bs.push_back(pw[n1 - i]);

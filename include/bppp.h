@@ -334,6 +334,14 @@ int bppp_trrp_public_device(bppp_trrp *t, size_t batch, const void *d_challenges
  * CLI takes from getPoints (app/Main.hs:68-72, :260); at least 2 + lin_len + norm_len points (validated: on the curve).
  * `oracle_tag` (may be NULL = the reference's input) is prepended to every hashed message (domain separation for tests).
  *
+ * Schemas the reference's setup takes and this library refuses with BPPP_ERR_ARG and a message, from every bppp_rp_create*:
+ *   - an INLINE range with more reciprocal symbols than digits ((1 if it has a leading bit) + base - 1 > number of digits, e.g. base 16 over
+ *     [0, 100)): the reference's own norm vector is then longer than its basis ("... unsupported layout");
+ *   - a range of width 2 <= max - min < base, shared, inline or assumed: makeRangeData's leading coefficient max - min - base is negative there and
+ *     the other one is 1 under a digit of radix base, so a proof would bound value - min by base, not by max - min ("range narrower than its digit
+ *     base: the reference's coefficients do not bound it").  Use a base <= max - min (base 2 fits every width >= 2);
+ *   - a range of width 1 ("degenerate range: a digit coefficient is zero").
+ *
  * The Fiat-Shamir oracle of these entry points is the CLI's shaOracle (app/Main.hs:64-80) computed natively: challenge n =
  * decode (SHA-256 (tag <> show n <> show (length ps) <> foldMap (show x <> show y) ps)) over the WHOLE transcript, newest first
  * (src/ZKP.hs:96-101); `show` of a coordinate = its decimal integer (parity of that text with galois-field's Show instance is

@@ -4,7 +4,10 @@
 //     shapes of SURVEY.md App. B when the caller passes them;
 //   * a few hundred mutated ranges — min >= max, base 0 / 1 / 2 / 2^32 - 1, negative minima, the whole 256-bit width, zero ranges, hundreds of
 //     ranges — must be either accepted or refused with a message, never crash, overflow a buffer or hit undefined behaviour;
-//   * accepted ranges: the digits of the minimum, the maximum - 1 and random members recombine to the value (sum d_i coeff_i = value - min).
+//   * accepted ranges: the digits of the minimum, the maximum - 1 and random members recombine to the value (sum d_i coeff_i = value - min), and
+//     the largest value the digits can represent is the maximum - 1: sum (radix_i - 1) coeff_i = max - min - 1 as plain integers, no wrap-around;
+//   * a reciprocal range of width 2 .. base - 1 is refused with a message of its own: the reference's leading coefficient is negative there and
+//     its digits bound value - min by the base, not by the width.
 // stdin: lines  "<name> <typed> <flavour> <nlen> <llen> <rounds> <nranges> { <base> <min> <max> <shared> <output> <assumed> }*"  (decimal, min may be negative)
 #include <cstdio>
 #include <iostream>
@@ -39,6 +42,20 @@ static void check_digits(const RangeData &rd, const U256 &value_minus_min, bool 
   CHECK(bppp_host::cmp(acc, value_minus_min) == 0, "digits do not recombine (base %u)", rd.base);
 }
 
+// sum (radix_i - 1) coeff_i == max - min - 1 over the integers: every product and every partial sum must stay below 2^256
+static void check_top(const RangeData &rd, bool binary) {
+  if (rd.assumed && !binary) return;                   // an assumed reciprocal range keeps no coefficients
+  U256 acc = U256::zero();
+  bool wrapped = false;
+  for (size_t i = 0; i < rd.coeffs.size(); i++) {
+    const uint32_t radix = binary ? 2u : ((rd.has_bit && i == 0) ? 2u : rd.base);
+    const U256 term = u_mul64(rd.coeffs[i], radix - 1, &wrapped);
+    if (bppp_host::add_raw(acc, acc, term)) wrapped = true;
+  }
+  CHECK(!wrapped, "largest representable value wraps 2^256 (base %u)", rd.base);
+  CHECK(bppp_host::cmp(acc, u_sub(u_sub(rd.hi, rd.lo), U256::one())) == 0, "largest representable value is not max - min - 1 (base %u, %zu digits)", rd.base, rd.coeffs.size());
+}
+
 int main() {
   std::mt19937_64 g(2024);
   std::string line;
@@ -68,6 +85,7 @@ int main() {
       if (nlen) CHECK(st.nlen == nlen && st.llen == llen && st.rounds == rounds, "%s: shape (%zu, %zu, %zu), expected (%zu, %zu, %zu)", name.c_str(), st.nlen, st.llen, st.rounds, nlen, llen, rounds);
       for (const RangeData &rd : rds) {
         const U256 w = u_sub(rd.hi, rd.lo);
+        check_top(rd, false);
         check_digits(rd, U256::zero(), false); check_digits(rd, u_sub(w, U256::one()), false);
         for (int k = 0; k < 50; k++) { U256 v; for (int q = 0; q < 4; q++) v.w[q] = g(); while (!u_lt(v, w)) { for (int q = 3; q >= 0; q--) if (v.w[q]) { v.w[q] >>= 1; break; } } check_digits(rd, v, false); }
       }
@@ -78,6 +96,7 @@ int main() {
       if (name == "bin_test" && nlen) CHECK(sb.nlen == nlen && sb.rounds == rounds, "bin_test: shape (%zu, %zu), expected (%zu, %zu)", sb.nlen, sb.rounds, nlen, rounds);
       for (const RangeData &rd : brds) {
         const U256 w = u_sub(rd.hi, rd.lo);
+        check_top(rd, true);
         check_digits(rd, U256::zero(), true); check_digits(rd, u_sub(w, U256::one()), true);
         for (int k = 0; k < 50; k++) { U256 v; for (int q = 0; q < 4; q++) v.w[q] = g(); while (!u_lt(v, w)) { for (int q = 3; q >= 0; q--) if (v.w[q]) { v.w[q] >>= 1; break; } } check_digits(rd, v, true); }
       }
@@ -108,6 +127,7 @@ int main() {
       const bool shared = flags & 1, assumed = flags & 2;
       if (make_range_data(base, lo, hi, shared, true, assumed, rd, err)) {
         accepted++;
+        check_top(rd, false);
         const U256 w = u_sub(hi, lo);
         if (!assumed && rd.coeffs.size() < 300 && base <= 65536) { check_digits(rd, U256::zero(), false); check_digits(rd, u_sub(w, U256::one()), false); }
         Setup st; std::vector<RangeData> one(1 + it % 3, rd);
@@ -118,10 +138,30 @@ int main() {
     RangeData b; std::string e2;
     if (make_range_data_binary(lo, hi, true, it & 1, b, e2)) {
       accepted++;
+      check_top(b, true);
       if (!(it & 1)) { const U256 w = u_sub(hi, lo); check_digits(b, U256::zero(), true); check_digits(b, u_sub(w, U256::one()), true); }
       Setup sb; std::vector<RangeData> many(1 + it % 5, b);
       CHECK(make_setup_binary(it & 2, many, U256::from_u64(g()), it & 1, sb, e2) || !e2.empty(), "binary setup refused without a message");
     } else refused++;
+  }
+  // widths 2 .. base - 1: refused, shared or inline, assumed or not, whatever the minimum; base and base + 1 are the first widths accepted
+  const uint32_t narrow_bases[] = {3u, 4u, 5u, 7u, 10u, 16u, 255u, 257u, 65536u, 0xFFFFFFFFu};
+  for (uint32_t base : narrow_bases) {
+    const U256 los[] = {U256::zero(), U256::from_u64(10), u_sub(U256::zero(), U256::from_u64(20)), u_add(U256::from_u64(~0ull), U256::one())};
+    for (uint64_t w = 2; w < base; w = (w < 300 || w + 1 == base) ? w + 1 : std::min<uint64_t>(w + 1 + g() % (base / 64 + 1), base - 1))
+      for (int flags = 0; flags < 4; flags++) {
+        const U256 &lo = los[(w + flags) % 4];
+        RangeData rd; std::string err;
+        const bool ok = make_range_data(base, lo, u_add(lo, U256::from_u64(w)), flags & 1, true, flags & 2, rd, err);
+        CHECK(!ok && err.find("narrower than its digit base") != std::string::npos, "base %u width %llu not refused as narrow: %s", base, (unsigned long long)w, err.c_str());
+        refused += !ok;
+      }
+    for (uint64_t w = base; w <= (uint64_t)base + 1; w++) {
+      RangeData rd; std::string err;
+      const bool ok = make_range_data(base, los[1], u_add(los[1], U256::from_u64(w)), true, true, false, rd, err);
+      CHECK(ok, "base %u width %llu refused: %s", base, (unsigned long long)w, err.c_str());
+      if (ok) { accepted++; check_top(rd, false); check_digits(rd, U256::zero(), false); check_digits(rd, U256::from_u64(w - 1), false); }
+    }
   }
   { Setup st; std::string err; CHECK(!make_setup(false, std::vector<RangeData>(), std::vector<PublicVT>(), st, err, 0) && !err.empty(), "an empty range list set up"); }
   { Setup st; std::string err; CHECK(!make_setup_binary(true, std::vector<RangeData>(), U256::zero(), 0, st, err) && !err.empty(), "an empty binary range list set up"); }
