@@ -280,6 +280,7 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_comb_groups.argtypes = [vp, vp, sz, sz, sz, i, sz, vp]
     lib.bppp_test_comb_lanes.argtypes = [vp, vp, sz, sz, vp]
     lib.bppp_test_last_comb_msm.argtypes = [vp, C.POINTER(TestCombReport)]
+    lib.bppp_test_last_reduce.argtypes = [vp, C.POINTER(TestReduceReport)]
     lib.bppp_test_rp_last_text_kernel.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_rpp_transcript.argtypes = [vp, sz, vp, sz, vp, vp, vp]
     lib.bppp_test_rpp_draws.argtypes = [vp, C.c_char_p, sz, sz, sz, vp]
@@ -290,6 +291,12 @@ class TestCombReport(C.Structure):
     """bppp_test_comb_report (include/bppp_test.h): what the last comb_msm launch on a context did"""
     __test__ = False                      # not a pytest class
     _fields_ = [("route", C.c_int32), ("heavy_first", C.c_int32)] + [(n, C.c_uint32) for n in ("parts", "tparts", "wsplit", "chunks", "clen", "join_lanes")]
+
+
+class TestReduceReport(C.Structure):
+    """bppp_test_reduce_report (include/bppp_test.h): what the bucket reduction of the last MSM on a context launched"""
+    __test__ = False
+    _fields_ = [(n, C.c_int32) for n in ("route", "combine", "c", "W", "M", "RG", "Lw", "WPW", "a", "LO", "HI", "PR", "PC", "SR", "SC", "TR", "TC", "S")]
 
 
 class TestRppCall(C.Structure):

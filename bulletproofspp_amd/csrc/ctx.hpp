@@ -16,6 +16,16 @@ struct CombLast {
   uint32_t chunks = 0, clen = 0, join_lanes = 0;      // rows: partial sums per instance, terms of each, lanes per instance of k_comb_join_rows
 };
 
+// What the bucket reduction of the last MSM on a context launched (csrc/msm.hip: msm_reduce, msm_small, msm_finish; read by bppp_test_last_reduce)
+struct ReduceLast {
+  int route = -1;                    // -1 none yet, 0 the small route (k_msm_small's own tail, k_msm_small_join), 1 k_reduce_groups, 2 k_reduce_marg + k_reduce_tail_quad, 3 k_reduce1 + k_reduce2
+  int combine = -1;                  // 1: the windows were combined by k_window_combine, 0: on the host
+  int c = 0, W = 0, M = 0;           // window width, windows left for the combine (1 for a registered basis), buckets per window
+  int RG = 0, Lw = 0, WPW = 0;       // groups: lanes per window and buckets per lane; wavefront route: buckets per lane, wavefronts per window
+  int a = 0, LO = 0, HI = 0, PR = 0, PC = 0, SR = 0, SC = 0, TR = 0, TC = 0;   // marginal route: MargGeom (msm_plan.hpp)
+  int S = 0;                         // small route: slices
+};
+
 struct bppp_ctx {
   MsmTune tune;
   // Lifetime: the caller's handle holds one reference, every child handle (bppp_nl, bppp_nlb, bppp_ip, bppp_trrp, bppp_basis,
@@ -62,6 +72,7 @@ struct bppp_ctx {
   int last_acc_fq29 = -1;            // 1: the last general-pipeline MSM ran k_acc_points_sized29 (fq29 accumulator), 0: any other accumulate kernel (bppp_test_last_acc_fq29)
   int last_windows = -1;             // digit rows W per scalar of the last MSM's plan, either route (bppp_test_last_windows)
   CombLast last_comb;                // the last comb_msm launch (bppp_test_last_comb_msm)
+  ReduceLast last_reduce;            // the last MSM's bucket reduction and window combine (bppp_test_last_reduce)
   size_t sort_lds_set = 0;           // largest dynamic-LDS size set on the MSM's sort kernels (hipFuncSetAttribute once, not per call)
 };
 

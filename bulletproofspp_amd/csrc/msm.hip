@@ -1051,6 +1051,9 @@ static int msm_small(bppp_ctx *ctx, const void *d_scalars, const void *d_points,
   rc = ensure_pinned(ctx, bytes); if (rc) return rc;
   hipStream_t st = ctx->stream;
   ctx->last_windows = s.W;
+  ReduceLast &last = ctx->last_reduce;
+  last = ReduceLast();
+  last.route = 0; last.combine = 0; last.c = s.c; last.W = s.W; last.M = 1 << (s.c - 1); last.S = (int)s.S;
   for (int i = 0; i <= 2; i++) prof_mark(ctx, i);
   rc = run_pre_acc(ctx); if (rc) return rc;
   k_msm_small<<<dim3((unsigned)s.W, (unsigned)s.S), dim3(256), s.lds, st>>>((const uint32_t *)d_scalars, (const uint32_t *)d_points, (uint32_t)n, (uint32_t)s.len, s.c,
@@ -1147,6 +1150,14 @@ static int msm_accumulate(bppp_ctx *ctx, const MsmPlan &p, const MsmWorkspace &w
 // 4. bucket reduce
 static void msm_reduce(bppp_ctx *ctx, const MsmPlan &p, const MsmWorkspace &ws) {
   hipStream_t st = ctx->stream;
+  ReduceLast &last = ctx->last_reduce;
+  last = ReduceLast();
+  last.route = p.RG ? 1 : p.marg ? 2 : 3; last.c = p.c; last.W = p.Wc; last.M = p.M;
+  if (p.RG) { last.RG = p.RG; last.Lw = p.M / p.RG; }
+  else if (p.marg) {
+    last.a = p.mg.a; last.LO = p.mg.LO; last.HI = p.mg.HI; last.PR = p.mg.PR; last.PC = p.mg.PC; last.SR = p.mg.SR; last.SC = p.mg.SC;
+    last.TR = p.mg.TR; last.TC = p.mg.TC;
+  } else { last.Lw = p.Lw; last.WPW = p.WPW; }
   if (p.RG) {
     k_reduce_groups<<<dim3((unsigned)((p.NS * p.RG + 63) / 64)), dim3(64), 0, st>>>(ws.buckets, p.M, p.RG, (uint32_t)p.NS, ws.winsum);
   } else if (p.marg) {
@@ -1165,6 +1176,7 @@ static int msm_finish(bppp_ctx *ctx, const MsmPlan &p, const MsmWorkspace &ws, u
   hipStream_t st = ctx->stream;
   const size_t batch = p.batch;
   const int a = p.marg ? p.mg.a : 0;
+  ctx->last_reduce.combine = d_out_dev || batch > 4 ? 1 : 0;
   if (d_out_dev) {
     k_window_combine<<<dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, st>>>(ws.winsum, p.Wc, p.c, a, (uint32_t)batch, d_out_dev);
     BPPP_HIP(ctx, hipGetLastError());

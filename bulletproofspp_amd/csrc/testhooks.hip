@@ -648,6 +648,14 @@ extern "C" int bppp_test_last_comb_msm(bppp_ctx *ctx, bppp_test_comb_report *r) 
   return BPPP_OK;
 }
 
+extern "C" int bppp_test_last_reduce(bppp_ctx *ctx, bppp_test_reduce_report *r) {
+  if (!ctx || !r) return BPPP_ERR_ARG;
+  const ReduceLast &l = ctx->last_reduce;
+  r->route = l.route; r->combine = l.combine; r->c = l.c; r->W = l.W; r->M = l.M; r->RG = l.RG; r->Lw = l.Lw; r->WPW = l.WPW;
+  r->a = l.a; r->LO = l.LO; r->HI = l.HI; r->PR = l.PR; r->PC = l.PC; r->SR = l.SR; r->SC = l.SC; r->TR = l.TR; r->TC = l.TC; r->S = l.S;
+  return BPPP_OK;
+}
+
 extern "C" int bppp_test_rp_last_text_kernel(bppp_rp *rp, int *lds) {
   if (!rp || !lds) return BPPP_ERR_ARG;
   *lds = rp->last_text_kernel;

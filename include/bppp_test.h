@@ -153,6 +153,13 @@ int bppp_test_comb_lanes(bppp_test_comb *tab, const void *d_scalars, size_t nter
  * instance), 4 the same with the instances dispatched as pairs.  Fields of the other routes are 0. */
 typedef struct bppp_test_comb_report { int32_t route, heavy_first; uint32_t parts, tparts, wsplit, chunks, clen, join_lanes; } bppp_test_comb_report;
 int bppp_test_last_comb_msm(bppp_ctx *ctx, bppp_test_comb_report *report);
+/* What the bucket reduction of the last MSM on this context launched, the small route and the product's own calls included.  route: -1 none
+ * yet, 0 the small route (the tail of k_msm_small and, with S > 1 slices, k_msm_small_join), 1 k_reduce_groups (RG lanes per window, Lw buckets
+ * per lane), 2 k_reduce_marg + k_reduce_tail_quad (a .. TC: the MargGeom of csrc/msm_plan.hpp), 3 k_reduce1 + k_reduce2 (Lw buckets per lane, WPW
+ * wavefronts per window).  c: window bits, W: windows left for the combine (1 for a registered basis), M = 2^(c-1) buckets per window.  combine:
+ * 1 = the windows were combined in k_window_combine, 0 = on the host.  Fields of the other routes are 0. */
+typedef struct bppp_test_reduce_report { int32_t route, combine, c, W, M, RG, Lw, WPW, a, LO, HI, PR, PC, SR, SC, TR, TC, S; } bppp_test_reduce_report;
+int bppp_test_last_reduce(bppp_ctx *ctx, bppp_test_reduce_report *report);
 /* The transcript text kernel of the last verification on this handle (bppp_rp_verify_batch*, _each*, its share of _mixed*): 0 = k_rp_text,
  * 1 = k_rp_text_lds (while the text image of a proof fits 64 KiB of LDS: up to 272 transcript points), -1 = none yet. */
 int bppp_test_rp_last_text_kernel(bppp_rp *rp, int *lds);
