@@ -259,6 +259,9 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_last_acc_fq29.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_fq29_op.argtypes = [vp, i, vp, vp, sz, vp, vp]
     lib.bppp_test_madd29_chain.argtypes = [vp, vp, vp, sz, sz, vp, vp]
+    lib.bppp_test_madd26_chain.argtypes = [vp, vp, vp, sz, sz, vp, vp]
+    lib.bppp_test_last_msm_layout.argtypes = [vp, C.POINTER(TestMsmLayout)]
+    lib.bppp_test_last_msm_copy.argtypes = [vp, i, vp, sz]
     lib.bppp_test_last_windows.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_rp_last_verify_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.bppp_test_rp_last_block_counts.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
@@ -297,6 +300,17 @@ class TestReduceReport(C.Structure):
     """bppp_test_reduce_report (include/bppp_test.h): what the bucket reduction of the last MSM on a context launched"""
     __test__ = False
     _fields_ = [(n, C.c_int32) for n in ("route", "combine", "c", "W", "M", "RG", "Lw", "WPW", "a", "LO", "HI", "PR", "PC", "SR", "SC", "TR", "TC", "S")]
+
+
+class TestMsmLayout(C.Structure):
+    """bppp_test_msm_layout (include/bppp_test.h): the plan of the last general-pipeline MSM on a context"""
+    __test__ = False
+    _fields_ = [(n, C.c_int32) for n in ("c", "W", "acnt", "top", "M", "flat", "CH", "Q", "one_read", "sized", "fq29", "L", "shared_points", "reserved")] + \
+               [(n, C.c_uint32) for n in ("stride", "per")] + [(n, C.c_uint64) for n in ("batch", "n", "FB", "G", "total", "table_stride")]
+
+
+# bppp_test_last_msm_copy's arrays
+TEST_MSM_DIGITS, TEST_MSM_NEGMASK, TEST_MSM_COUNT, TEST_MSM_START, TEST_MSM_SORTED, TEST_MSM_BUCKETS_RAW, TEST_MSM_BUCKETS_AFF = range(7)
 
 
 class TestRppCall(C.Structure):

@@ -73,6 +73,12 @@ struct bppp_ctx {
   int last_windows = -1;             // digit rows W per scalar of the last MSM's plan, either route (bppp_test_last_windows)
   CombLast last_comb;                // the last comb_msm launch (bppp_test_last_comb_msm)
   ReduceLast last_reduce;            // the last MSM's bucket reduction and window combine (bppp_test_last_reduce)
+  // The last general-pipeline MSM (msm_run_ex; read by bppp_test_last_msm_layout / _copy, which carve the workspace again from the plan and read
+  // the stages back): valid until a call that lays `ws` out differently — the small route clears it, the tests read directly after their MSM
+  bool last_msm_valid = false;
+  bppp::MsmPlan last_msm_plan{};
+  size_t last_msm_n = 0, last_msm_batch = 0, last_msm_table_stride = 0;
+  int last_msm_shared_points = 0;
   size_t sort_lds_set = 0;           // largest dynamic-LDS size set on the MSM's sort kernels (hipFuncSetAttribute once, not per call)
 };
 

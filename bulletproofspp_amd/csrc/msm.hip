@@ -1051,6 +1051,7 @@ static int msm_small(bppp_ctx *ctx, const void *d_scalars, const void *d_points,
   rc = ensure_pinned(ctx, bytes); if (rc) return rc;
   hipStream_t st = ctx->stream;
   ctx->last_windows = s.W;
+  ctx->last_msm_valid = false;       // this route lays the workspace out its own way (carve_small)
   ReduceLast &last = ctx->last_reduce;
   last = ReduceLast();
   last.route = 0; last.combine = 0; last.c = s.c; last.W = s.W; last.M = 1 << (s.c - 1); last.S = (int)s.S;
@@ -1241,6 +1242,8 @@ int msm_run_ex(bppp_ctx *ctx, const void *d_scalars, const void *d_points, size_
   Carver cv(ctx->ws, ctx->ws_bytes);
   const MsmWorkspace ws = carve(cv, p, n, batch);
   rc = msm_sort_lds(ctx, p); if (rc) return rc;
+  ctx->last_msm_valid = true; ctx->last_msm_plan = p; ctx->last_msm_n = n; ctx->last_msm_batch = batch; ctx->last_msm_shared_points = shared_points;
+  ctx->last_msm_table_stride = table_stride;
 
   prof_mark(ctx, 0);
   msm_digits(ctx, p, ws, d_scalars);

@@ -198,6 +198,23 @@ __global__ void __launch_bounds__(64) k_test_madd29_chain(const uint32_t *pts, c
   xyzz_store(raw + (size_t)i * XYZZ_WORDS, s);
   aff_store(out + (size_t)i * 16, xyzz_to_aff(s));
 }
+// the same walk over 10 x 26-bit limbs, as k_acc_points_sized walks an item (and, from the second entry on, k_acc_points a run): xyzz_from_aff,
+// aff_cneg, xyzz_madd
+__global__ void __launch_bounds__(64) k_test_madd26_chain(const uint32_t *pts, const uint32_t *flags, uint32_t k, uint32_t n, uint32_t *out, uint32_t *raw) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t *p = pts + (size_t)i * k * 16, *f = flags + (size_t)i * k;
+  xyzz acc = xyzz_from_aff(aff_cneg(aff_load(p), f[0] != 0));
+  for (uint32_t j = 1; j < k; j++) xyzz_madd(acc, aff_cneg(aff_load(p + (size_t)j * 16), f[j] != 0));
+  xyzz_store(raw + (size_t)i * XYZZ_WORDS, acc);
+  aff_store(out + (size_t)i * 16, xyzz_to_aff(acc));
+}
+// the bucket array of an MSM as canonical affine points, infinity as (0, 0): one lane per bucket
+__global__ void __launch_bounds__(64) k_test_buckets_aff(const uint32_t *__restrict__ buckets, uint64_t FB, uint32_t *__restrict__ out) {
+  const uint64_t fb = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+  if (fb >= FB) return;
+  aff_store(out + fb * 16, xyzz_to_aff(xyzz_load(buckets + fb * XYZZ_WORDS)));
+}
 }  // namespace bppp
 
 using namespace bppp;
@@ -380,20 +397,85 @@ extern "C" int bppp_test_fq29_op(bppp_ctx *ctx, int op, const uint32_t *a, const
   hipFree(d);
   return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_fq29_op: kernel or copy failed");
 }
-extern "C" int bppp_test_madd29_chain(bppp_ctx *ctx, const uint64_t *points, const uint32_t *flags, size_t k, size_t n, uint64_t *out, uint32_t *raw) {
+static int madd_chain(bppp_ctx *ctx, bool fq29, const uint64_t *points, const uint32_t *flags, size_t k, size_t n, uint64_t *out, uint32_t *raw) {
   if (!ctx || !points || !flags || !out || !raw || !k || k >= (1u << 16) || n >= (1u << 16)) return BPPP_ERR_ARG;
   if (n == 0) return BPPP_OK;
   hipSetDevice(ctx->device);
   uint32_t *d = nullptr;                       // points | flags | out | raw
-  if (hipMalloc(&d, (n * k * 17 + n * (16 + XYZZ_WORDS)) * 4) != hipSuccess) return bppp::fail(ctx, BPPP_ERR_HIP, "test_madd29_chain: hipMalloc");
+  if (hipMalloc(&d, (n * k * 17 + n * (16 + XYZZ_WORDS)) * 4) != hipSuccess) return bppp::fail(ctx, BPPP_ERR_HIP, "test_madd_chain: hipMalloc");
   uint32_t *d_f = d + n * k * 16, *d_out = d_f + n * k, *d_raw = d_out + n * 16;
   hipStream_t st = ctx->stream;
   bool ok = hipMemcpyAsync(d, points, n * k * 64, hipMemcpyHostToDevice, st) == hipSuccess && hipMemcpyAsync(d_f, flags, n * k * 4, hipMemcpyHostToDevice, st) == hipSuccess;
-  if (ok) k_test_madd29_chain<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st>>>(d, d_f, (uint32_t)k, (uint32_t)n, d_out, d_raw);
+  if (ok && fq29) k_test_madd29_chain<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st>>>(d, d_f, (uint32_t)k, (uint32_t)n, d_out, d_raw);
+  else if (ok) k_test_madd26_chain<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st>>>(d, d_f, (uint32_t)k, (uint32_t)n, d_out, d_raw);
   ok = ok && hipMemcpyAsync(out, d_out, n * 64, hipMemcpyDeviceToHost, st) == hipSuccess && hipMemcpyAsync(raw, d_raw, n * XYZZ_WORDS * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
   if (hipStreamSynchronize(st) != hipSuccess) ok = false;
   hipFree(d);
-  return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_madd29_chain: kernel or copy failed");
+  return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_madd_chain: kernel or copy failed");
+}
+extern "C" int bppp_test_madd29_chain(bppp_ctx *ctx, const uint64_t *points, const uint32_t *flags, size_t k, size_t n, uint64_t *out, uint32_t *raw) {
+  return madd_chain(ctx, true, points, flags, k, n, out, raw);
+}
+extern "C" int bppp_test_madd26_chain(bppp_ctx *ctx, const uint64_t *points, const uint32_t *flags, size_t k, size_t n, uint64_t *out, uint32_t *raw) {
+  return madd_chain(ctx, false, points, flags, k, n, out, raw);
+}
+
+// ---- the stages of the last general-pipeline MSM on a context, read back from its workspace (ctx.hpp: last_msm_*)
+static bool last_msm_total(bppp_ctx *ctx, const MsmWorkspace &ws, uint64_t FB, uint32_t *total) {
+  return hipStreamSynchronize(ctx->stream) == hipSuccess && hipMemcpy(total, ws.start + FB, 4, hipMemcpyDeviceToHost) == hipSuccess;
+}
+extern "C" int bppp_test_last_msm_layout(bppp_ctx *ctx, bppp_test_msm_layout *r) {
+  if (!ctx || !r) return BPPP_ERR_ARG;
+  if (!ctx->last_msm_valid) return bppp::fail(ctx, BPPP_ERR_ARG, "test_last_msm_layout: no general-pipeline MSM has run on this context");
+  hipSetDevice(ctx->device);
+  const MsmPlan &p = ctx->last_msm_plan;
+  const size_t n = ctx->last_msm_n, batch = ctx->last_msm_batch;
+  Carver cv(ctx->ws, ctx->ws_bytes);
+  const MsmWorkspace ws = carve(cv, p, n, batch);
+  if (cv.off > ctx->ws_bytes) return bppp::fail(ctx, BPPP_ERR_ARG, "test_last_msm_layout: the workspace is smaller than the stored plan's layout");
+  uint32_t total = 0;
+  if (!last_msm_total(ctx, ws, p.FB, &total)) return bppp::fail(ctx, BPPP_ERR_HIP, "test_last_msm_layout: copy failed");
+  memset(r, 0, sizeof *r);
+  r->c = p.c; r->W = p.W; r->acnt = p.acnt; r->top = p.top; r->M = p.M; r->flat = p.flat ? 1 : 0; r->CH = p.CH; r->Q = p.Q; r->one_read = p.one_read ? 1 : 0;
+  r->sized = p.sized ? 1 : 0; r->fq29 = p.fq29 ? 1 : 0; r->L = p.L; r->shared_points = ctx->last_msm_shared_points;
+  r->stride = ws.stride;
+  r->per = ((((uint32_t)n + p.CH - 1) / p.CH) + 7u) & ~7u;      // the chunk length of k_hist and the three scatters
+  r->batch = batch; r->n = n; r->FB = p.FB; r->G = p.G; r->total = total; r->table_stride = ctx->last_msm_table_stride;
+  return BPPP_OK;
+}
+extern "C" int bppp_test_last_msm_copy(bppp_ctx *ctx, int what, void *out, size_t bytes) {
+  if (!ctx || !out) return BPPP_ERR_ARG;
+  if (!ctx->last_msm_valid) return bppp::fail(ctx, BPPP_ERR_ARG, "test_last_msm_copy: no general-pipeline MSM has run on this context");
+  hipSetDevice(ctx->device);
+  const MsmPlan &p = ctx->last_msm_plan;
+  const size_t n = ctx->last_msm_n, batch = ctx->last_msm_batch;
+  Carver cv(ctx->ws, ctx->ws_bytes);
+  const MsmWorkspace ws = carve(cv, p, n, batch);
+  if (cv.off > ctx->ws_bytes) return bppp::fail(ctx, BPPP_ERR_ARG, "test_last_msm_copy: the workspace is smaller than the stored plan's layout");
+  uint32_t total = 0;
+  if (!last_msm_total(ctx, ws, p.FB, &total)) return bppp::fail(ctx, BPPP_ERR_HIP, "test_last_msm_copy: copy failed");
+  const void *src = nullptr; size_t want = 0;
+  switch (what) {
+    case BPPP_TEST_MSM_DIGITS: src = ws.dig; want = (size_t)p.NB * ws.stride * 2; break;
+    case BPPP_TEST_MSM_NEGMASK: src = ws.negmask; want = ((batch * n + 63) / 64) * 8; break;
+    case BPPP_TEST_MSM_COUNT: src = ws.count; want = (size_t)p.FB * 4; break;
+    case BPPP_TEST_MSM_START: src = ws.start; want = ((size_t)p.FB + 1) * 4; break;
+    case BPPP_TEST_MSM_SORTED: src = ws.sorted; want = (size_t)total * 4; break;
+    case BPPP_TEST_MSM_BUCKETS_RAW: src = ws.buckets; want = (size_t)p.FB * XYZZ_WORDS * 4; break;
+    case BPPP_TEST_MSM_BUCKETS_AFF: want = (size_t)p.FB * 64; break;
+    default: return bppp::fail(ctx, BPPP_ERR_ARG, "test_last_msm_copy: unknown array");
+  }
+  if (bytes != want) return bppp::fail(ctx, BPPP_ERR_ARG, "test_last_msm_copy: the array has " + std::to_string(want) + " bytes, not " + std::to_string(bytes));
+  if (!want) return BPPP_OK;
+  uint32_t *d_aff = nullptr;
+  if (what == BPPP_TEST_MSM_BUCKETS_AFF) {
+    if (hipMalloc(&d_aff, want) != hipSuccess) return bppp::fail(ctx, BPPP_ERR_HIP, "test_last_msm_copy: hipMalloc");
+    k_test_buckets_aff<<<dim3((unsigned)((p.FB + 63) / 64)), dim3(64), 0, ctx->stream>>>(ws.buckets, p.FB, d_aff);
+    src = d_aff;
+  }
+  const bool ok = hipMemcpyAsync(out, src, want, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
+  hipFree(d_aff);
+  return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_last_msm_copy: kernel or copy failed");
 }
 
 extern "C" int bppp_test_last_windows(bppp_ctx *ctx, int *windows) {

@@ -66,6 +66,31 @@ int bppp_test_fq29_op(bppp_ctx *ctx, int op, const uint32_t *a, const uint32_t *
  * the accumulator, the others are added with xyzz29_madd.  points: n x k x 8 uint64 affine ((0, 0) = infinity), flags: n x k uint32, not 0
  * negates the point first.  out: n x 8 uint64 canonical affine sums; raw: n x 40 uint32, the sums as the kernel stores them. */
 int bppp_test_madd29_chain(bppp_ctx *ctx, const uint64_t *points, const uint32_t *flags, size_t k, size_t n, uint64_t *out, uint32_t *raw);
+/* The same chains over 10 x 26-bit limbs (csrc/ec.hip.h: xyzz_from_aff, aff_cneg, xyzz_madd), as k_acc_points_sized walks an item and k_acc_points a
+ * run; arguments and outputs as bppp_test_madd29_chain (raw: the accumulator as stored, lazily reduced). */
+int bppp_test_madd26_chain(bppp_ctx *ctx, const uint64_t *points, const uint32_t *flags, size_t k, size_t n, uint64_t *out, uint32_t *raw);
+/* The stages of the LAST general-pipeline MSM on this context (any entry point that reaches msm_run_ex past the small route), read back from the
+ * context's workspace, which is carved again from the plan the call stored: call these directly after the MSM, before anything else runs on the
+ * context.  BPPP_ERR_ARG when no such MSM has run (or the small route ran since).
+ * _layout: the plan (csrc/msm_plan.hpp) — c, W digit rows per scalar of which the first acnt are c bits wide, top (the row stored negated, -1 none),
+ * M buckets per window, flat (a registered basis: one bucket set per instance), CH chunks per digit row and their length per as k_hist and the
+ * scatters compute it, Q bucket ranges (0: k_scatter), one_read (k_scatter_one_read), sized / fq29 (the accumulation's form), L entries per lane and G
+ * lanes of k_acc_points, shared_points as the call gave it; stride: uint16 per digit row; FB buckets in all; total = start[FB], the sorted entries;
+ * table_stride: the rows' distance in a registered basis' table (0 otherwise).
+ * _copy: one array, `bytes` must be exactly its size —
+ *   DIGITS       [batch * W][stride] uint16, as stored (biased, the top row negated)
+ *   NEGMASK      ceil(batch * n / 64) uint64: bit i is the sign fold of scalar i
+ *   COUNT        [FB] uint32          START  [FB + 1] uint32          SORTED  [total] uint32: sign << 31 | point index
+ *   BUCKETS_RAW  [FB][40] uint32, the stored XYZZ sums         BUCKETS_AFF  [FB][16] uint32: xyzz_to_aff of each, infinity as (0, 0) */
+typedef struct bppp_test_msm_layout {
+  int32_t c, W, acnt, top, M, flat, CH, Q, one_read, sized, fq29, L, shared_points, reserved;
+  uint32_t stride, per;
+  uint64_t batch, n, FB, G, total, table_stride;
+} bppp_test_msm_layout;
+enum { BPPP_TEST_MSM_DIGITS = 0, BPPP_TEST_MSM_NEGMASK = 1, BPPP_TEST_MSM_COUNT = 2, BPPP_TEST_MSM_START = 3, BPPP_TEST_MSM_SORTED = 4,
+       BPPP_TEST_MSM_BUCKETS_RAW = 5, BPPP_TEST_MSM_BUCKETS_AFF = 6 };
+int bppp_test_last_msm_layout(bppp_ctx *ctx, bppp_test_msm_layout *report);
+int bppp_test_last_msm_copy(bppp_ctx *ctx, int what, void *out, size_t bytes);
 /* The windows (digit rows per scalar) of the plan of the last MSM on this context, the small route included: 16 with 16-bit windows, where
  * the top window is stored negated instead of carrying into a 17th; 256 / c + 1 for a registered basis; -1 = none yet. */
 int bppp_test_last_windows(bppp_ctx *ctx, int *windows);
