@@ -287,6 +287,8 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_rp_last_text_kernel.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_rpp_transcript.argtypes = [vp, sz, vp, sz, vp, vp, vp]
     lib.bppp_test_rpp_draws.argtypes = [vp, C.c_char_p, sz, sz, sz, vp]
+    lib.bppp_test_ctx_poison.argtypes = [vp, i, C.POINTER(C.c_uint64)]
+    lib.bppp_test_rp_poison.argtypes = [vp, i, C.POINTER(C.c_uint64)]
     return lib
 
 

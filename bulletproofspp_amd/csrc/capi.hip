@@ -70,12 +70,6 @@ int ctx_aux(bppp_ctx *ctx) {
   BPPP_HIP(ctx, hipEventCreateWithFlags(&ctx->aux_join, hipEventDisableTiming));
   return BPPP_OK;
 }
-void ctx_drain(bppp_ctx *ctx) {
-  if (ctx_closed(ctx)) return;
-  hipStreamSynchronize(ctx->stream);
-  if (ctx->aux_stream) hipStreamSynchronize(ctx->aux_stream);
-  (void)hipGetLastError();
-}
 int ensure_workspace(bppp_ctx *ctx, size_t bytes) {
   if (bytes <= ctx->ws_bytes) return BPPP_OK;
   BPPP_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -42,7 +42,9 @@ struct bppp_ctx {
   hipStream_t aux_stream = nullptr;
   hipEvent_t aux_fork = nullptr, aux_join = nullptr;
   std::string err;
-  // grow-only device workspace, carved per call (no hipMalloc on the steady-state path)
+  // grow-only device workspace, carved per call (no hipMalloc on the steady-state path).  The contract of ws, ws2, mix and pinned, and of the
+  // scratch buffers of a range-proof handle (csrc/rp_internal.hpp): no entry point reads a workspace word that the same call has not written;
+  // tests/test_gpu_poisoned_workspace.py holds it.
   void *ws = nullptr;
   size_t ws_bytes = 0;
   // second grow-only device buffer for callers that also run an MSM (which carves `ws`)
@@ -101,7 +103,12 @@ inline bool ctx_closed(const bppp_ctx *ctx) { return !ctx || ctx->closed.load();
 int ctx_aux(bppp_ctx *ctx);               // creates aux_stream and its two events if needed
 // nothing of a call is in flight once it has returned: both streams drained (the verifier's sliced uploads of host files run on the
 // second) and the runtime's last-error slot cleared; a no-op on a closed context
-void ctx_drain(bppp_ctx *ctx);
+inline void ctx_drain(bppp_ctx *ctx) {
+  if (ctx_closed(ctx)) return;
+  hipStreamSynchronize(ctx->stream);
+  if (ctx->aux_stream) hipStreamSynchronize(ctx->aux_stream);
+  (void)hipGetLastError();
+}
 int ensure_workspace(bppp_ctx *ctx, size_t bytes);
 int ensure_pinned(bppp_ctx *ctx, size_t bytes);
 int ensure_scratch(bppp_ctx *ctx, size_t bytes);

@@ -818,3 +818,71 @@ extern "C" int bppp_test_rpp_draws(bppp_ctx *ctx, const uint8_t *prefixes, size_
   hipFree(d);
   return rc;
 }
+
+// ---- poison: every scratch buffer of a context / a range-proof handle filled with one byte at its current capacity, so that the next call cannot
+// rest on what an earlier one left (include/bppp_test.h states which buffers are scratch and which are persistent)
+namespace {
+struct Poison {
+  bppp_ctx *ctx; int byte; uint64_t total = 0; bool ok = true;
+  void hbm(void *p, size_t n) {
+    if (!p || !n) return;
+    if (hipMemsetAsync(p, byte, n, ctx->stream) != hipSuccess) ok = false;
+    total += n;
+  }
+  void host(void *p, size_t n) {
+    if (!p || !n) return;
+    memset(p, byte, n);
+    total += n;
+  }
+  bool wait() { return hipStreamSynchronize(ctx->stream) == hipSuccess && ok; }
+};
+int ctx_poison(bppp_ctx *ctx, int byte, uint64_t *total) {
+  hipSetDevice(ctx->device);
+  ctx_drain(ctx);
+  Poison P{ctx, byte};
+  P.hbm(ctx->ws, ctx->ws_bytes);
+  P.hbm(ctx->ws2, ctx->ws2_bytes);
+  P.hbm(ctx->mix, ctx->mix_bytes);
+  P.host(ctx->pinned, ctx->pinned_bytes);
+  ctx->last_msm_valid = false;                   // the read-back hooks would copy poison
+  *total += P.total;
+  return P.wait() ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_ctx_poison: fill failed");
+}
+int rp_poison(bppp_rp *rp, int byte, uint64_t *total) {
+  bppp_ctx *ctx = rp->ctx;
+  hipSetDevice(ctx->device);
+  ctx_drain(ctx);
+  Poison P{ctx, byte};
+  P.hbm(rp->pwork, rp->pwork_bytes);
+  P.hbm(rp->awork, rp->awork_bytes);
+  P.hbm(rp->work, rp->work_bytes);
+  P.hbm(rp->stage, rp->stage_bytes);
+  P.hbm(rp->ework, rp->ework_bytes);
+  P.hbm(rp->d_pub, rp->d_pub_bytes);
+  P.hbm(rp->d_sel, rp->d_sel_bytes);
+  P.hbm(rp->d_bind, rp->d_bind_bytes);
+  P.hbm(rp->d_bhdr, rp->d_bhdr_bytes);
+  P.hbm(rp->d_comb_out, rp->comb_out_rows * 64);
+  P.host(rp->hpin, rp->hpin_bytes);
+  P.host(rp->hstage, rp->hstage_bytes);
+  P.host(rp->hflag, 64);
+  *total += P.total;
+  if (!P.wait()) return bppp::fail(ctx, BPPP_ERR_HIP, "test_rp_poison: fill failed");
+  if (rp->twin) {
+    if (int rc = rp_poison(rp->twin, byte, total)) return rc;
+    if (rp->twin_ctx && !ctx_closed(rp->twin_ctx)) return ctx_poison(rp->twin_ctx, byte, total);
+  }
+  return BPPP_OK;
+}
+}  // namespace
+
+extern "C" int bppp_test_ctx_poison(bppp_ctx *ctx, int byte, uint64_t *bytes_poisoned) {
+  if (!ctx || ctx_closed(ctx) || !bytes_poisoned || byte < 0 || byte > 255) return BPPP_ERR_ARG;
+  *bytes_poisoned = 0;
+  return ctx_poison(ctx, byte, bytes_poisoned);
+}
+extern "C" int bppp_test_rp_poison(bppp_rp *rp, int byte, uint64_t *bytes_poisoned) {
+  if (!rp || !rp->ctx || ctx_closed(rp->ctx) || !bytes_poisoned || byte < 0 || byte > 255) return BPPP_ERR_ARG;
+  *bytes_poisoned = 0;
+  return rp_poison(rp, byte, bytes_poisoned);
+}

@@ -201,6 +201,40 @@ int bppp_test_rpp_transcript(bppp_rp *rp, size_t batch, const bppp_test_rpp_call
 /* rpp_draws: out[b][c] = hashToScalar (prefix_b <> show c), c < nd; prefixes host [batch][prefix_len] (prefix_len 0: NULL will do), out host
  * [batch][nd][4] words. */
 int bppp_test_rpp_draws(bppp_ctx *ctx, const uint8_t *prefixes, size_t prefix_len, size_t batch, size_t nd, uint64_t *out);
+/* Poison: every SCRATCH buffer of a context, or of a range-proof handle, filled with `byte` (0 .. 255) at its current capacity, so that the next call
+ * cannot rest on what an earlier call left there (csrc/ctx.hpp: no entry point reads a workspace word that the same call has not written).  Both drain
+ * the context first (ctx_drain), fill HBM with hipMemsetAsync on the context's stream and wait for it, and fill pinned host memory with memset.
+ * bytes_poisoned: the bytes filled in all (0: nothing had been allocated yet).  A NULL handle or a closed context is BPPP_ERR_ARG.
+ * Scratch = rewritten by every call that uses it; persistent = filled at creation or first use and read by later calls (never poisoned).
+ * _ctx_ (members of bppp_ctx, csrc/ctx.hpp); it also drops last_msm_valid, so bppp_test_last_msm_layout / _copy refuse instead of copying poison:
+ *   ws           scratch     the MSM's workspace, carved per call (csrc/msm.hip), and the batch inversion's (csrc/rounds.hip)
+ *   ws2          scratch     what a caller that also runs an MSM assembles for it (csrc/nlbatch.hip, nl.hip, ip.hip, glv.hip, trrp.hip, seedpoints.hip, rpmixed.hip, rpblock.hip)
+ *   mix          scratch     one call's MSM input and shared scalars of the multi-setup verifier and the block call, the input commitments of one bppp_rp_prove_mixed (csrc/rpmixed.hip, rpblock.hip, rpshare.hip)
+ *   pinned       scratch     pinned host staging of small results and uploads (csrc/msm.hip, rounds.hip, ip.hip, capi.hip)
+ *   pre_acc, pre_acc_arg     not buffers: the one-shot upload hook of bppp_msm and its argument, set and cleared within one call (csrc/msm.hip)
+ * _rp_ (members of bppp_rp, csrc/rp_internal.hpp); with a twin handle (a split prove batch), the twin's buffers and the twin's own context as well, but
+ * NOT the handle's own context: the caller poisons both:
+ *   pwork        scratch     the provers' and the commit / open / tally / excess calls' workspace (csrc/rpprove.hip, rpprove_dev.hip, brpprove*.hip, rpcommit.hip, rptally.hip, rpexcess.hip, rpexkeys.hip, rpexpart.hip)
+ *   awork        scratch     the device-resident inner-product argument's workspace and final witness (csrc/rpprove_dev.hip hands it to ipb_prove_stream, csrc/ipb.hip)
+ *   hpin         scratch     pinned staging of the batch provers (csrc/rpprove.hip, brpprove.hip)
+ *   work         scratch     the verifier's per-proof arrays of one prepared batch (csrc/rp.hip: rp_verify_prepare)
+ *   stage        scratch     the host files of one verification, uploaded in slices (csrc/rp.hip: rp_stage_files)
+ *   ework        scratch     the per-proof verifier's rows (csrc/rpeach.hip)
+ *   hstage       scratch     pinned downloads and uploads of the host oracle of one verification (csrc/rp.hip)
+ *   hflag        scratch     64 pinned bytes; word 0 is copied from bad[batch] by every rp_verify_prepare (csrc/rp.hip) and read after the same call's MSM (csrc/rp.hip, rpmixed.hip, rpblock.hip)
+ *   d_pub        scratch     one call's canonical public amounts (csrc/rp.hip: rp_upload_public)
+ *   d_sel        scratch     the accepted / refused proofs of one status call (csrc/rpwitness.hip)
+ *   d_bind       scratch     one bound call's bindings (csrc/rpbind.hip)
+ *   d_bhdr       scratch     one bound call's per-proof headers (csrc/rpbind.hip: rp_bound_headers)
+ *   d_comb_out   scratch     comb_out_rows points: the first-round commitments of one call of the fold route, written by comb_msm and copied out in the same call (csrc/rpprove.hip)
+ *   d_basis, d_plan          persistent   the basis and the hash plan, uploaded by bppp_rp_create* (csrc/rp.hip)
+ *   d_fixed, commit_basis    persistent   the window table of (g, H0, H1) and the registered [g | H | G], built at first use (csrc/rpcommit.hip, rpprove.hip)
+ *   d_wit                    persistent   per-range data of the witness kernels, uploaded at the first device prove (csrc/rpwitness.hip)
+ *   tabs, btabs, comb        persistent   the setup's device tables and the comb table (csrc/trrp.hip, rp.hip, comb.hip)
+ *   ctx, twin, twin_ctx, pool             handles and the host oracle's workers, not buffers
+ *   pre_inputs               borrowed     the caller's precomputed input commitments while bppp_rp_prove_mixed runs (csrc/rpshare.hip) */
+int bppp_test_ctx_poison(bppp_ctx *ctx, int byte, uint64_t *bytes_poisoned);
+int bppp_test_rp_poison(bppp_rp *rp, int byte, uint64_t *bytes_poisoned);
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
