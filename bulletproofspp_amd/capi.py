@@ -47,6 +47,8 @@ SYMBOLS = [
     "bppp_rp_excess_part_sign_device", "bppp_rp_excess_part_verify", "bppp_rp_excess_part_verify_device", "bppp_rp_excess_part_combine", "bppp_rp_excess_part_combine_device",
     "bppp_seed_candidate_x", "bppp_points_from_seed", "bppp_points_from_seed_device", "bppp_rp_create_seeded", "bppp_rp_create_binary_seeded",
     "bppp_rp_verify_block", "bppp_rp_verify_block_device",
+    "bppp_rp_excess_halfagg", "bppp_rp_excess_halfagg_device", "bppp_rp_excess_halfagg_verify", "bppp_rp_excess_halfagg_verify_device",
+    "bppp_rp_verify_block_agg", "bppp_rp_verify_block_agg_device",
 ]
 
 
@@ -228,6 +230,12 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_excess_part_combine_device.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.bppp_rp_verify_block.argtypes = [vp, C.POINTER(RpBlock), vp, C.POINTER(i), C.POINTER(RpBlockStatus), vp]
     lib.bppp_rp_verify_block_device.argtypes = [vp, C.POINTER(RpBlock), vp, C.POINTER(i), C.POINTER(RpBlockStatus), vp]
+    lib.bppp_rp_excess_halfagg.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    lib.bppp_rp_excess_halfagg_device.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+    lib.bppp_rp_excess_halfagg_verify.argtypes = [vp, sz, vp, vp, vp, C.POINTER(i), vp, vp]
+    lib.bppp_rp_excess_halfagg_verify_device.argtypes = [vp, sz, vp, vp, vp, C.POINTER(i), vp, vp]
+    lib.bppp_rp_verify_block_agg.argtypes = [vp, C.POINTER(RpBlock), vp, vp, C.POINTER(i), C.POINTER(RpBlockStatus), vp]
+    lib.bppp_rp_verify_block_agg_device.argtypes = [vp, C.POINTER(RpBlock), vp, vp, C.POINTER(i), C.POINTER(RpBlockStatus), vp]
     lib.bppp_seed_candidate_x.argtypes = [C.c_char_p, sz, C.c_uint64, vp]
     lib.bppp_points_from_seed.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
     lib.bppp_points_from_seed_device.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]

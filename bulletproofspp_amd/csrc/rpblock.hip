@@ -14,6 +14,10 @@
 //                         g, H0, H1 and the signatures' sum rho s on B
 // All three are one lane per item, bounds-checked on their own index, gather form without atomics, and write with ordinary vector stores.
 // A rejected block names its culprits by the counterparts' own exact passes (rp_find_culprits, verify_keys_each_pass, tally::each_pass).
+// bppp_rp_verify_block_agg* is the same call with the half-aggregate of the signatures (csrc/rpexagg.hip) in their place:  K' = rho_A (s_agg B -
+// sum z_k (c_k X_k + R_k))  stands for K.  The hash tree, s_agg and rho_A come first; key_stage then runs over the R rows widened to signatures with
+// s = 0, k_rp_exagg_weights writes the key terms where k_rp_excess_weights does, and rho_A s_agg is the signatures' scalar on B.  The keys of a
+// rejected block get the aggregate's own verdict (exagg::verify_run).
 #include <string.h>
 #include <algorithm>
 #include <string>
@@ -23,6 +27,7 @@
 #include "rphostcall.hpp"
 #include "rpprove_host.hpp"
 #include "rpexcess_shared.hip.h"
+#include "rpexagg.hip.h"
 
 namespace bppp {
 
@@ -84,6 +89,7 @@ using namespace bppp;
 using namespace bppp::tally;
 using namespace bppp::excess;
 using namespace bppp::exkeys;
+using namespace bppp::exagg;
 
 namespace {
 
@@ -124,9 +130,10 @@ struct BlockWork {
   uint32_t *sc, *pts, *shared, *flags, *reject;
   KeyWork K;
   Work T;
+  AggWork A;                                      // bppp_rp_verify_block_agg alone
 };
 
-int block_carve(bppp_rp *rp, const bppp_rp_block &b, size_t Tn, bool zero_claims, BlockWork &W) {
+int block_carve(bppp_rp *rp, const bppp_rp_block &b, size_t Tn, bool zero_claims, bool with_agg, BlockWork &W) {
   bppp_ctx *ctx = rp->ctx;
   const size_t nr = rp->D.nr, total = b.rows * nr, ulen = 1 + rp->st.llen + rp->st.nlen, nk = b.nkeys, ns = b.nsums;
   for (int pass = 0; pass < 2; pass++) {
@@ -145,6 +152,8 @@ int block_carve(bppp_rp *rp, const bppp_rp_block &b, size_t Tn, bool zero_claims
     T.rho = cv.take<uint32_t>(ns * 8); T.prods = cv.take<uint32_t>(ns * 24); T.red = cv.take<uint32_t>((size_t)RPP_REDUCE_BLOCKS * 24); T.sc3 = cv.take<uint32_t>(24);
     T.seed = cv.take<uint8_t>(32);
     K.X = T.pool + total * 16;                    // the lifted keys: the tail of the pool, slot rows * nranges + k
+    W.A = AggWork{};
+    if (with_agg) agg_carve(cv, nk, nk, W.A);
     if (!pass && cv.off > ctx->mix_bytes) {
       BPPP_HIP(ctx, hipStreamSynchronize(ctx->stream));
       if (ctx->mix) BPPP_HIP(ctx, hipFree(ctx->mix));
@@ -157,7 +166,10 @@ int block_carve(bppp_rp *rp, const bppp_rp_block &b, size_t Tn, bool zero_claims
 }
 
 // every pointer of the block in HBM.  Checks first (no output is written before they have passed), then the one MSM, then the statuses.
-int block_device(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t seed[32], int *accept, const bppp_rp_block_status *status, uint64_t *combined_xy) {
+// with_agg: bppp_rp_verify_block_agg — the half-aggregate agg [33 nkeys + 32] (csrc/rpexagg.hip) stands where blk->sigs stands otherwise; without
+// it the call is bppp_rp_verify_block, launch for launch.
+int block_device(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t *agg, bool with_agg, const uint8_t seed[32], int *accept, const bppp_rp_block_status *status,
+                 uint64_t *combined_xy) {
   if (!rp || !blk || !accept) return BPPP_ERR_ARG;
   bppp_ctx *ctx = rp->ctx;
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
@@ -172,6 +184,7 @@ int block_device(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t seed[32], 
     return BPPP_OK;
   }
   int rc;
+  if (with_agg && (b.sigs || b.key_offset)) return fail(ctx, BPPP_ERR_ARG, "rp_verify_block_agg: blk->sigs must be NULL and blk->key_offset 0: the aggregate stands for the signatures of the whole job");
   if ((rc = block_sizes(rp, b))) return rc;
   if (!seed || (np && (!b.coms_files || !b.proof_files))) return fail(ctx, BPPP_ERR_ARG, std::string(WHO) + ": null input");
   hipSetDevice(ctx->device);
@@ -180,7 +193,7 @@ int block_device(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t seed[32], 
   KeyJob KJ{};
   if (ns && (rc = sums_checks(S, rp, WHO, b.rows, b.coms_files, ns, b.sum_start, b.entries, b.nnz, b.claim_amounts, b.claim_types, b.claim_offsets, nk, b.key_start, b.keys, false)))
     return rc;
-  if (nk && (rc = key_checks(KJ, rp, WHO, nk, b.keys, b.msgs, b.sigs, false))) return rc;
+  if (nk && (rc = key_checks(KJ, rp, WHO, nk, b.keys, b.msgs, with_agg ? (const void *)agg : b.sigs, false))) return rc;
   RpBindGuard guard{rp};
   if (np && (rc = rp_bind_begin(rp, b.bindings, true, np, WHO))) return rc;
   // ---- the checks have passed: from here on the call writes its outputs and the handle's counters
@@ -196,7 +209,7 @@ int block_device(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t seed[32], 
   const size_t nnz = ns ? b.nnz : 0;
   const size_t proof_off = ulen, entry_off = proof_off + np * per, key_off = entry_off + nnz, Tn = key_off + 2 * nk;
   BlockWork W;
-  if ((rc = block_carve(rp, b, Tn, ns && S.J.zero_claims, W))) return rc;
+  if ((rc = block_carve(rp, b, Tn, ns && S.J.zero_claims, with_agg && nk, W))) return rc;
   LapTimer timer(rp->opt.timing, "[rp_verify_block]");
   auto lap = [&](const char *what) { if (rp->opt.timing) { hipStreamSynchronize(st); timer.lap(what); } };
   BPPP_HIP(ctx, hipMemsetAsync(W.flags, 0, 16, st));
@@ -234,11 +247,18 @@ int block_device(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t seed[32], 
   if (nk) {
     const ExDomain dc = challenge_domain(rp);
     BPPP_HIP(ctx, hipMemcpyAsync(W.K.seed, seeds[1], 32, hipMemcpyHostToDevice, st));
+    if (with_agg) {                                     // the tree over the whole job, s_agg and rho_A; the R rows as signatures with s = 0 for the stage
+      KJ.sigs = W.A.sigx;
+      if ((rc = expand_launch(ctx, nk, agg, W.A.sigx)) || (rc = commit_tree(rp, nk, KJ.keys, KJ.msgs, agg, AGG_ROW, W.A)) || (rc = sagg_launch(ctx, agg + nk * AGG_ROW, W.A)) ||
+          (rc = rho_launch(ctx, W.K.seed, nk, agg + nk * AGG_ROW, W.A)))
+        return rc;
+    }
     if ((rc = key_stage(KJ, W.K, 0, nk, dc))) return rc;
     rp->blk_key_lifts += nk;
-    if ((rc = batch_assemble(rp, nk, b.key_offset, W.K.seed, KJ.sigs, W.K.X, KJ.msgs, W.K.pre, W.K.c, W.K.sp, W.K.R, W.K.prods, W.K.red, W.K.sc3, W.sc + key_off * 8,
-                             W.pts + key_off * 16, W.K.any)))
-      return rc;
+    if (with_agg) rc = weights_launch(rp, nk, 0, nk, W.A.root, W.A.rho, W.K.X, W.K.pre, W.K.c, W.K.sp, W.K.R, nullptr, W.sc + key_off * 8, W.pts + key_off * 16, W.K.any);
+    else rc = batch_assemble(rp, nk, b.key_offset, W.K.seed, KJ.sigs, W.K.X, KJ.msgs, W.K.pre, W.K.c, W.K.sp, W.K.R, W.K.prods, W.K.red, W.K.sc3, W.sc + key_off * 8,
+                             W.pts + key_off * 16, W.K.any);
+    if (rc) return rc;
     k_rp_block_key_terms<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st>>>((uint32_t)nk, (uint32_t)ns, ns ? S.key_start : nullptr, ns ? W.T.rho : nullptr, W.K.pre, W.K.X,
                                                                                  W.sc + key_off * 8, W.pts + key_off * 16, W.reject);
     BPPP_HIP(ctx, hipGetLastError());
@@ -246,7 +266,7 @@ int block_device(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t seed[32], 
   }
   // ---- the union basis and its scalars, then the one MSM
   k_rp_block_shared<<<dim3((unsigned)((ulen + 255) / 256)), dim3(256), 0, st>>>((uint32_t)ulen, (uint32_t)llen, (uint32_t)nlen, np ? W.shared : nullptr, ns ? W.T.sc3 : nullptr,
-                                                                              nk ? W.K.sc3 : nullptr, blind_slot(rp), W.sc);
+                                                                              !nk ? nullptr : with_agg ? W.A.rho + 8 : W.K.sc3, blind_slot(rp), W.sc);
   BPPP_HIP(ctx, hipGetLastError());
   BPPP_HIP(ctx, hipMemcpyAsync(W.pts, rp->d_basis, ulen * 64, hipMemcpyDeviceToDevice, st));
   uint64_t out_xy[8];
@@ -259,8 +279,10 @@ int block_device(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t seed[32], 
   BPPP_HIP(ctx, hipMemcpy(&reject, W.reject, 4, hipMemcpyDeviceToHost));
   BPPP_HIP(ctx, hipMemcpy(&kany, W.K.any, 4, hipMemcpyDeviceToHost));
   BPPP_HIP(ctx, hipMemcpy(tany, W.T.any, 8, hipMemcpyDeviceToHost));
+  uint32_t bad_s = 0;                                   // s_agg >= n
+  if (with_agg && nk) BPPP_HIP(ctx, hipMemcpy(&bad_s, W.A.flag, 4, hipMemcpyDeviceToHost));
   if (np && St.flavour && (rc = ip_verify_batch_flags(ctx, hflags))) return rc;
-  const bool bad = (np && rp->hflag[0] != 0) || reject || kany || tany[0] || tany[1];
+  const bool bad = (np && rp->hflag[0] != 0) || reject || kany || tany[0] || tany[1] || bad_s;
   if (combined_xy) memcpy(combined_xy, out_xy, 64);
   *accept = (rp_point_is_inf(out_xy) && !bad) ? 1 : 0;
   if (*accept) {
@@ -276,7 +298,10 @@ int block_device(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t seed[32], 
     for (size_t i = 0; i < np; i++) proof_status[i] = proof_status[i] ? BPPP_RP_MALFORMED : BPPP_RP_VALID;
     if ((rc = rp_find_culprits(rp, A, false, proof_status))) return rc;
   }
-  if (key_status && nk && (rc = verify_keys_each_pass(KJ, key_status))) return rc;
+  if (key_status && nk) {
+    int part = 0;                                       // the aggregate's own verdict: one equation for all open keys
+    if ((rc = with_agg ? verify_run(rp, nk, KJ.keys, KJ.msgs, agg, &part, key_status, nullptr) : verify_keys_each_pass(KJ, key_status))) return rc;
+  }
   if (sum_status && ns) {
     const Ext E = sums_ext(S);
     if ((rc = each_pass(S.J, sum_status, nullptr, &E))) return rc;
@@ -284,22 +309,47 @@ int block_device(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t seed[32], 
   return BPPP_OK;
 }
 
+int block_host(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t *agg, bool with_agg, const uint8_t seed[32], int *accept, const bppp_rp_block_status *status,
+               uint64_t *combined_xy);
+
 }  // namespace
 
 extern "C" {
 
 int bppp_rp_verify_block_device(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t seed[32], int *accept, const bppp_rp_block_status *status, uint64_t *combined_xy) {
-  const int rc = block_device(rp, blk, seed, accept, status, combined_xy);
+  const int rc = block_device(rp, blk, nullptr, false, seed, accept, status, combined_xy);
+  if (rc && rp && !ctx_closed(rp->ctx)) ctx_drain(rp->ctx);
+  return rc;
+}
+
+int bppp_rp_verify_block_agg_device(bppp_rp *rp, const bppp_rp_block *blk, const void *d_agg, const uint8_t seed[32], int *accept, const bppp_rp_block_status *status,
+                                    uint64_t *combined_xy) {
+  const int rc = block_device(rp, blk, (const uint8_t *)d_agg, true, seed, accept, status, combined_xy);
   if (rc && rp && !ctx_closed(rp->ctx)) ctx_drain(rp->ctx);
   return rc;
 }
 
 int bppp_rp_verify_block(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t seed[32], int *accept, const bppp_rp_block_status *status, uint64_t *combined_xy) {
+  return block_host(rp, blk, nullptr, false, seed, accept, status, combined_xy);
+}
+
+int bppp_rp_verify_block_agg(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t *agg, const uint8_t seed[32], int *accept, const bppp_rp_block_status *status,
+                             uint64_t *combined_xy) {
+  return block_host(rp, blk, agg, true, seed, accept, status, combined_xy);
+}
+
+}  // extern "C"
+
+namespace {
+
+// the host variants: every array of the struct (and the aggregate) uploaded, the _device body, the context drained
+int block_host(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t *agg, bool with_agg, const uint8_t seed[32], int *accept, const bppp_rp_block_status *status,
+               uint64_t *combined_xy) {
   if (!rp || !blk || !accept) return BPPP_ERR_ARG;
   bppp_ctx *ctx = rp->ctx;
   if (ctx_closed(ctx)) return BPPP_ERR_ARG;
   bppp_rp_block d = *blk;
-  DevBuf coms, proofs, bind, start, entries, a, ty, off, kstart, keys, msgs, sigs;
+  DevBuf coms, proofs, bind, start, entries, a, ty, off, kstart, keys, msgs, sigs, aggb;
   if (d.nproofs || d.nkeys || d.nsums) {
     int rc = block_sizes(rp, d);                         // before any size is multiplied
     if (rc) return rc;
@@ -317,14 +367,16 @@ int bppp_rp_verify_block(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t se
     if (!rc && sums) rc = kstart.up(ctx, d.key_start, (d.nsums + 1) * 4);
     if (!rc) rc = keys.up(ctx, d.keys, d.nkeys * EX_KEY);
     if (!rc) rc = msgs.up(ctx, d.msgs, d.nkeys * EX_MSG);
-    if (!rc) rc = sigs.up(ctx, d.sigs, d.nkeys * EX_SIG);
+    if (!rc && !with_agg) rc = sigs.up(ctx, d.sigs, d.nkeys * EX_SIG);
+    if (!rc && with_agg) rc = aggb.up(ctx, agg, BPPP_RP_EXCESS_AGG_BYTES(d.nkeys));
     if (rc) return rc;
     d.coms_files = coms.p; d.proof_files = proofs.p; d.bindings = bind.p; d.sum_start = start.p; d.entries = entries.p; d.claim_amounts = a.p; d.claim_types = ty.p;
-    d.claim_offsets = off.p; d.key_start = kstart.p; d.keys = keys.p; d.msgs = msgs.p; d.sigs = sigs.p;
+    d.claim_offsets = off.p; d.key_start = kstart.p; d.keys = keys.p; d.msgs = msgs.p;
+    if (!with_agg) d.sigs = sigs.p;                      // with the aggregate: as the caller left it, for the _device body to judge
   }
-  const int rc = block_device(rp, &d, seed, accept, status, combined_xy);
+  const int rc = block_device(rp, &d, (const uint8_t *)aggb.p, with_agg, seed, accept, status, combined_xy);
   ctx_drain(ctx);
   return rc;
 }
 
-}  // extern "C"
+}  // namespace

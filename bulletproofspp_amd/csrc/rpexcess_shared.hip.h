@@ -53,6 +53,30 @@ template <class F> BPPP_DI fe ex_hash3(uint32_t nbytes, F at) {
   fe r; sha256_digest_to_limbs(st, r.v);
   return wi_umod_n(r);
 }
+// its sibling for the half-aggregate's hash tree (csrc/rpexagg.hip): the RAW digest, as eight big-endian words, of a message of NB blocks
+// (64 NB - 72 <= nbytes <= 64 NB - 9: two blocks hold 56 .. 119 bytes, three 120 .. 183), byte k of it being at (k)
+template <uint32_t NB, class F> BPPP_DI void ex_digest(uint32_t nbytes, F at, uint32_t st[8]) {
+  uint32_t w[16];
+  sha256_init(st);
+#pragma unroll
+  for (uint32_t blk = 0; blk < NB; blk++) {
+#pragma unroll
+    for (uint32_t q = 0; q < 16; q++) {
+      uint32_t word = 0;
+#pragma unroll
+      for (uint32_t r = 0; r < 4; r++) {
+        const uint32_t k = 64 * blk + 4 * q + r;
+        word = (word << 8) | (k < nbytes ? (at(k) & 0xFFu) : k == nbytes ? 0x80u : 0u);
+      }
+      w[q] = word;
+    }
+    if (blk == NB - 1) w[15] = nbytes * 8;
+    sha256_compress(st, w);
+  }
+}
+// byte k of a digest held as big-endian words, and decode (digest) mod n
+BPPP_DI uint32_t ex_word_byte(const uint32_t *w, uint32_t k) { return (w[k >> 2] >> (24 - 8 * (k & 3))) & 0xFFu; }
+BPPP_DI fe ex_digest_scalar(const uint32_t st[8]) { fe r; sha256_digest_to_limbs(st, r.v); return wi_umod_n(r); }
 // c = decode (SHA-256 (Dc || the 33 bytes of R || put (X.x) || sign (X) || msg)) mod n: 130 bytes; rbyte (o): byte o of R as the signature holds it
 template <class F> BPPP_DI fe ex_challenge(const ExDomain &dc, F rbyte, const uint32_t *X, const uint8_t *msg) {
   return ex_hash3(32 + 33 + 33 + EX_MSG, [&](uint32_t k) -> uint32_t {

@@ -1509,9 +1509,10 @@ class NativeRangeProofs:
                 ("sigs", self._excess_bytes(sigs, EXCESS_SIG_BYTES, "signatures"))]
         return arrs, dict(rows=rows, nproofs=nproofs, nsums=nsums, nnz=nnz, nkeys=nkeys)
 
-    def verify_block_call(self, blk, seed: Optional[bytes] = None, want_status: bool = False, want_point: bool = False, device: bool = False):
+    def verify_block_call(self, blk, seed: Optional[bytes] = None, want_status: bool = False, want_point: bool = False, device: bool = False, agg: Optional[int] = None):
         """bppp_rp_verify_block (device: bppp_rp_verify_block_device) on a filled capi.RpBlock.  Returns accept, or (accept, (proof, key, sum
-        statuses) or None, combined point or None) when want_status / want_point is set."""
+        statuses) or None, combined point or None) when want_status / want_point is set.  agg: the address of a half-aggregate (host memory, or HBM
+        with device) — then the call is bppp_rp_verify_block_agg / _device, and blk.sigs and blk.key_offset stay zero."""
         import ctypes as C
         import numpy as np
         from .capi import RpBlockStatus, array_to_point
@@ -1522,8 +1523,12 @@ class NativeRangeProofs:
         acc, sd, xy = C.c_int(0), np.frombuffer(seed, dtype=np.uint8), np.zeros(8, dtype=np.uint64)
         sts = [np.zeros(max(n, 1), dtype=np.uint32) for n in (blk.nproofs, blk.nkeys, blk.nsums)]
         status = RpBlockStatus(*[a.ctypes.data for a in sts])
-        fn = self.gpu.lib.bppp_rp_verify_block_device if device else self.gpu.lib.bppp_rp_verify_block
-        rc = fn(self.h, C.byref(blk), C.c_void_p(sd.ctypes.data), C.byref(acc), C.byref(status) if want_status else None, C.c_void_p(xy.ctypes.data) if want_point else None)
+        lib = self.gpu.lib
+        if agg is None:
+            fn, head = (lib.bppp_rp_verify_block_device if device else lib.bppp_rp_verify_block), (self.h, C.byref(blk))
+        else:
+            fn, head = (lib.bppp_rp_verify_block_agg_device if device else lib.bppp_rp_verify_block_agg), (self.h, C.byref(blk), C.c_void_p(agg))
+        rc = fn(*head, C.c_void_p(sd.ctypes.data), C.byref(acc), C.byref(status) if want_status else None, C.c_void_p(xy.ctypes.data) if want_point else None)
         self.gpu._check(rc, "bppp_rp_verify_block")
         if not (want_status or want_point):
             return bool(acc.value)
@@ -1560,6 +1565,94 @@ class NativeRangeProofs:
         """bppp_rp_verify_block_device: verify_block with every buffer uploaded first (a caller whose buffers already lie in HBM fills a capi.RpBlock
         with the device pointers and calls verify_block_call(..., device=True))"""
         return self.verify_block(*args, _device=True, **kwargs)
+
+    # ---- half-aggregate excess signatures: 33 bytes a kernel and one scalar (bppp_rp_excess_halfagg / _halfagg_verify, bppp_rp_verify_block_agg)
+    def _excess_halfagg(self, fn, n, args, want_status):
+        import ctypes as C
+        import numpy as np
+        status = np.zeros(max(n, 1), dtype=np.uint32)
+        self.gpu._check(fn(self.h, *args, C.c_void_p(status.ctypes.data) if want_status else None), "bppp_rp_excess_halfagg")
+        return [int(v) for v in status[:n]] if want_status else None
+
+    def excess_halfagg(self, keys: Sequence[bytes], msgs: Sequence[bytes], sigs: Sequence[bytes], want_status: bool = False):
+        """bppp_rp_excess_halfagg: the half-aggregate of the signatures, EXCESS_AGG_BYTES (n) bytes (b"" for no key): the R rows, then put (sum z_i s_i)
+        with the coefficients of excess_halfagg_coef.  The equations are NOT evaluated: check the signatures first.  Returns the aggregate, or (aggregate,
+        statuses) with want_status (all zero bytes when a signature is refused); without it a refusal raises BpppError."""
+        import ctypes as C
+        import numpy as np
+        keep, n, args = self._excess_key_args(keys, msgs, sigs)
+        ag = np.zeros(EXCESS_AGG_BYTES(n), dtype=np.uint8)
+        st = self._excess_halfagg(self.gpu.lib.bppp_rp_excess_halfagg, n, args + (C.c_void_p(ag.ctypes.data),), want_status)
+        out = ag.tobytes() if n else b""
+        return (out, st) if want_status else out
+
+    def excess_halfagg_device(self, nkeys: int, d_keys: int, d_msgs: int, d_sigs: int, d_agg: int, want_status: bool = False):
+        """bppp_rp_excess_halfagg_device: excess_halfagg on buffers in HBM (d_agg receives EXCESS_AGG_BYTES (nkeys) bytes); returns the statuses or None"""
+        import ctypes as C
+        p = C.c_void_p
+        return self._excess_halfagg(self.gpu.lib.bppp_rp_excess_halfagg_device, nkeys, (nkeys, p(d_keys), p(d_msgs), p(d_sigs), p(d_agg)), want_status)
+
+    def _excess_halfagg_verify(self, fn, n, args, want_status, want_point):
+        import ctypes as C
+        import numpy as np
+        from .capi import array_to_point
+        acc, status, xy = C.c_int(0), np.zeros(max(n, 1), dtype=np.uint32), np.zeros(8, dtype=np.uint64)
+        rc = fn(self.h, *args, C.byref(acc), C.c_void_p(status.ctypes.data) if want_status else None, C.c_void_p(xy.ctypes.data) if want_point else None)
+        self.gpu._check(rc, "bppp_rp_excess_halfagg_verify")
+        if not (want_status or want_point):
+            return bool(acc.value)
+        return bool(acc.value), ([int(v) for v in status[:n]] if want_status else None), (array_to_point(xy) if want_point else None)
+
+    def excess_halfagg_verify(self, keys: Sequence[bytes], msgs: Sequence[bytes], agg: bytes, want_status: bool = False, want_point: bool = False):
+        """bppp_rp_excess_halfagg_verify: does the half-aggregate hold for these keys and messages?  One equation, one MSM a pass and no seed.  Returns accept,
+        or (accept, verdicts or None, the equation's left side or None) when want_status / want_point is set; the verdict of the equation is the same for
+        every key it is asked of: an aggregate cannot name a culprit."""
+        import ctypes as C
+        import numpy as np
+        n = len(keys)
+        if len(msgs) != n or len(agg) != (EXCESS_AGG_BYTES(n) if n else len(agg)):
+            raise ValueError("one message per key and an aggregate of 33 n + 32 bytes are required")
+        keep = [self._excess_bytes(keys, EXCESS_KEY_BYTES, "keys"), self._excess_bytes(msgs, 32, "messages"), np.frombuffer(agg or b"\0", dtype=np.uint8)]
+        return self._excess_halfagg_verify(self.gpu.lib.bppp_rp_excess_halfagg_verify, n, (n,) + tuple(C.c_void_p(a.ctypes.data) for a in keep), want_status, want_point)
+
+    def excess_halfagg_verify_device(self, nkeys: int, d_keys: int, d_msgs: int, d_agg: int, want_status: bool = False, want_point: bool = False):
+        """bppp_rp_excess_halfagg_verify_device: excess_halfagg_verify on buffers in HBM"""
+        import ctypes as C
+        p = C.c_void_p
+        return self._excess_halfagg_verify(self.gpu.lib.bppp_rp_excess_halfagg_verify_device, nkeys, (nkeys, p(d_keys), p(d_msgs), p(d_agg)), want_status, want_point)
+
+    def verify_block_agg(self, coms_files: Sequence[bytes], proof_files: Sequence[bytes], sum_start, entries, claims, key_start, keys: Sequence[bytes], msgs: Sequence[bytes],
+                         agg: bytes, bindings=None, seed: Optional[bytes] = None, offsets=(0, 0, 0), want_status: bool = False, want_point: bool = False,
+                         _device: bool = False):
+        """bppp_rp_verify_block_agg: verify_block with the half-aggregate of the kernel signatures (excess_halfagg) in their place: the combined point is
+        V + K' + S with K' = block_agg_weight (...) times the point of excess_halfagg_verify.  offsets: (proofs, keys, sums); the keys' must be 0, an
+        aggregate is not shardable.  Returns as verify_block does; on rejection the key statuses are those of excess_halfagg_verify."""
+        import numpy as np
+        from .capi import RpBlock
+        nkeys = len(keys)
+        if len(agg) != (EXCESS_AGG_BYTES(nkeys) if nkeys else len(agg)):
+            raise ValueError("an aggregate of 33 nkeys + 32 bytes is required")
+        arrs, n = self.block_arrays(coms_files, proof_files, sum_start, entries, claims, key_start, keys, msgs, [bytes(EXCESS_SIG_BYTES)] * nkeys, bindings)
+        arrs = [(name, a) for name, a in arrs if name != "sigs"] + [("agg", np.frombuffer(agg or b"\0", dtype=np.uint8))]
+        blk = RpBlock(proof_offset=offsets[0], key_offset=offsets[1], sum_offset=offsets[2], **n)
+        dev, at = [], {}
+        try:
+            for name, a in arrs:
+                if a is None:
+                    continue
+                if _device:
+                    dev.append(self.gpu.to_device(a))
+                at[name] = dev[-1] if _device else a.ctypes.data
+                if name != "agg":
+                    setattr(blk, name, at[name])
+            return self.verify_block_call(blk, seed, want_status, want_point, device=_device, agg=at["agg"])
+        finally:
+            for d in dev:
+                self.gpu.free(d)
+
+    def verify_block_agg_device(self, *args, **kwargs):
+        """bppp_rp_verify_block_agg_device: verify_block_agg with every buffer uploaded first"""
+        return self.verify_block_agg(*args, _device=True, **kwargs)
 
     # ---- the multi-party signer: parties who each know a part of the blinding sum (bppp_rp_excess_part_nonces / _aggregate / _sign / _verify / _combine)
     def _excess_part_rows(self, fn, name, n, args, out_specs, want_status, status_len=None):
@@ -2028,6 +2121,89 @@ def excess_sums_host(backend: "Backend", setup, S: Point, claim, keys: Sequence[
         return 3, rest
     want = _commit_terms(backend, [(a, g), (o, B)] + ([(ty, H0)] if H0 is not None else []))
     return (0 if rest == want else 1), rest
+
+
+# ---- half-aggregate excess signatures (bppp_rp_excess_halfagg / _halfagg_verify, bppp_rp_verify_block_agg); include/bppp.h states every message
+def EXCESS_AGG_BYTES(n: int) -> int:
+    """BPPP_RP_EXCESS_AGG_BYTES: n rows of 33 bytes and one scalar"""
+    return 33 * n + 32
+
+
+def _halfagg_domain(part: bytes, tag: bytes) -> bytes:
+    return hashlib.sha256(b"bppp/excess/halfagg/" + part + b"/v1" + tag).digest()
+
+
+def _s_of(b32: bytes) -> int:
+    return sum(int.from_bytes(b32[8 * i:8 * i + 8], "big") << (64 * i) for i in range(4))
+
+
+def excess_halfagg_leaf(tag: bytes, r33: bytes, key33: bytes, msg: bytes) -> bytes:
+    """leaf = SHA-256 (Dl || the 33 bytes of R as they stand || the canonical 33 bytes of the key: put (x mod p), the sign byte || msg): 130 bytes"""
+    return hashlib.sha256(_halfagg_domain(b"leaf", tag) + r33 + _put(decode_field(key33[:32], FIELD_P)) + key33[32:33] + msg).digest()
+
+
+def excess_halfagg_root(tag: bytes, leaves: Sequence[bytes]) -> bytes:
+    """the root over the leaves in job order: pairs hashed as SHA-256 (Dn || left || right), an odd last node moved up unchanged, until one is left"""
+    dn, level = _halfagg_domain(b"node", tag), list(leaves)
+    if not level:
+        raise ValueError("a tree needs a leaf")
+    while len(level) > 1:
+        level = [hashlib.sha256(dn + level[j] + level[j + 1]).digest() if j + 1 < len(level) else level[j] for j in range(0, len(level), 2)]
+    return level[0]
+
+
+def excess_halfagg_coef(tag: bytes, root: bytes, n: int, i: int) -> int:
+    """z_i = decode (SHA-256 (Dz || root || le64 (n) || le64 (i))) mod n, 1 for 0: 80 bytes"""
+    return decode_field(hashlib.sha256(_halfagg_domain(b"coef", tag) + root + n.to_bytes(8, "little") + i.to_bytes(8, "little")).digest(), N) or 1
+
+
+def _halfagg_coefs(tag: bytes, keys, msgs, rows) -> Tuple[bytes, List[int]]:
+    root = excess_halfagg_root(tag, [excess_halfagg_leaf(tag, r, k, m) for r, k, m in zip(rows, keys, msgs)])
+    return root, [excess_halfagg_coef(tag, root, len(keys), i) for i in range(len(keys))]
+
+
+def excess_halfagg_status(key: bytes, sig: bytes) -> int:
+    """the aggregator's verdict on one signature: BAD_KEY, NOT_CANONICAL (s >= n), BAD_R or OK; no equation"""
+    return EXCESS_BAD_KEY if excess_lift33(key) is None else 3 if _s_of(sig[33:]) >= N else EXCESS_BAD_R if excess_lift33(sig[:33]) is None else 0
+
+
+def excess_halfagg_host(tag: bytes, keys: Sequence[bytes], msgs: Sequence[bytes], sigs: Sequence[bytes]) -> bytes:
+    """Host restatement of bppp_rp_excess_halfagg: the aggregate bytes (b"" for no key; all zero when excess_halfagg_status refuses a signature)"""
+    n = len(keys)
+    if not n:
+        return b""
+    if any(excess_halfagg_status(k, s) for k, s in zip(keys, sigs)):
+        return bytes(EXCESS_AGG_BYTES(n))
+    rows = [s[:33] for s in sigs]
+    _, z = _halfagg_coefs(tag, keys, msgs, rows)
+    return b"".join(rows) + _put(sum(zi * _s_of(s[33:]) for zi, s in zip(z, sigs)) % N)
+
+
+def excess_halfagg_verify_host(backend: "Backend", setup, keys: Sequence[bytes], msgs: Sequence[bytes], agg: bytes, tag: bytes = b""):
+    """Host restatement of bppp_rp_excess_halfagg_verify: (accept, statuses, the left side  s_agg B - sum z_i (c_i X_i + R_i)  over the open keys, None
+    for the identity)"""
+    _, _, B = _excess_bases(setup)
+    n = len(keys)
+    if not n:
+        return True, [], None
+    rows, s_agg = [agg[33 * i:33 * i + 33] for i in range(n)], _s_of(agg[33 * n:])
+    _, z = _halfagg_coefs(tag, keys, msgs, rows)
+    Xs, Rs = [excess_lift33(k) for k in keys], [excess_lift33(r) for r in rows]
+    pre = [EXCESS_BAD_KEY if X is None else EXCESS_BAD_R if R is None else None for X, R in zip(Xs, Rs)]
+    terms = [(s_agg if s_agg < N else 0, B)]
+    for i in range(n):
+        if pre[i] is None:
+            terms += [(-z[i] * excess_challenge(tag, rows[i], Xs[i], msgs[i]), Xs[i]), (-z[i], Rs[i])]
+    point = _commit_terms(backend, terms)
+    open_verdict = 3 if s_agg >= N else 0 if point is None else 1
+    accept = all(p is None for p in pre) and s_agg < N and point is None
+    return accept, [open_verdict if p is None else p for p in pre], point
+
+
+def block_agg_weight(seed: bytes, nkeys: int, root: bytes, s32: bytes) -> int:
+    """rho_A of bppp_rp_verify_block_agg: decode (SHA-256 (seed_1 || le64 (nkeys) || root || the 32 bytes of s_agg)) mod n, 1 for 0: 104 bytes; seed:
+    block_seeds (seed)[1]"""
+    return decode_field(hashlib.sha256(seed + nkeys.to_bytes(8, "little") + root + s32).digest(), N) or 1
 
 
 # ---- the multi-party signer (bppp_rp_excess_part_*): builders who each know a part e_i of the blinding sum; include/bppp.h states every message

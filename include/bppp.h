@@ -1122,6 +1122,61 @@ int bppp_rp_verify_block(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t se
 int bppp_rp_verify_block_device(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t seed[32], int *accept, const bppp_rp_block_status *status /* may be NULL */,
                                 uint64_t *combined_xy /* may be NULL */);
 
+/* ---- half-aggregate excess signatures: 33 bytes a kernel and one scalar, checked as one MSM ------------------------------------------------
+ * After cut-through the kernels (a 33-byte key and a 65-byte signature each) are what a chain keeps for ever.  Non-interactive half-aggregation
+ * turns the n signatures (R_i, s_i) of a block into the n nonce points and ONE scalar: BPPP_RP_EXCESS_AGG_BYTES (n) = 33 n + 32 bytes instead
+ * of 65 n.  Anyone who holds the signatures can aggregate, with no secret and no interaction; the check is deterministic and takes no seed.
+ * put, decode, the sign byte, the lift of 33 bytes, B, tag and the challenge c_i are those of the excess signatures and the stated keys above.
+ * The canonical 33 bytes of a key are put (x mod p), then the sign byte as it stands: defined for every row, with no square root.
+ *   domains      Dl = SHA-256 ("bppp/excess/halfagg/leaf/v1" || tag), Dn = SHA-256 ("bppp/excess/halfagg/node/v1" || tag),
+ *                Dz = SHA-256 ("bppp/excess/halfagg/coef/v1" || tag), hashed once a call on the host
+ *   leaf         leaf_i = SHA-256 (Dl || the 33 bytes of R_i as the signature holds them || the canonical 33 bytes of X_i || msg_i)  — 130 bytes;
+ *                the raw digest, not reduced
+ *   tree         level 0: the n leaves in job order; level k has ceil (count_{k-1} / 2) nodes, node (k, j) = SHA-256 (Dn || node (k-1, 2j) ||
+ *                node (k-1, 2j+1)) — 96 bytes — when 2j + 1 < count_{k-1}, else node (k-1, 2j) unchanged; root: the node of the level of one
+ *                (n = 1: leaf_0)
+ *   coefficient  z_i = decode (SHA-256 (Dz || root || le64 (n) || le64 (i))) mod n, 1 in place of 0                                  — 80 bytes
+ *   aggregate    the n rows of 33 bytes of R_i, copied as they stand, then put (s_agg), s_agg = sum_i z_i s_i mod n
+ *   equation     s_agg B - sum_i z_i (c_i X_i + R_i) = identity: one MSM per pass over  n - z_i c_i  on X_i,  n - z_i  on R_i, and s_agg on B once
+ * The tree commits to every (R, X, msg) and to n before any z_i is fixed, so errors in several s_i cannot be chosen to cancel.
+ * THE AGGREGATE CANNOT NAME A CULPRIT: one equation speaks for all keys, and the s_i are gone.  Check the signatures before they are aggregated.
+ * INCREMENTAL AGGREGATION IS OUT OF SCOPE: one more signature changes the root and with it every z_i; aggregate a block once, from its signatures.
+ * THE AGGREGATE IS NOT SHARDABLE BY KEYS: every z_i depends on all of them, so the verifier takes no index offset.
+ *
+ * bppp_rp_excess_halfagg{,_device}: keys [nkeys][33], msgs [nkeys][32], sigs [nkeys][65] -> agg [33 nkeys + 32].  status (host, may be NULL,
+ * [nkeys]), per signature the first that applies of BPPP_RP_EXCESS_BAD_KEY (6), BPPP_RP_OPEN_NOT_CANONICAL (3: s >= n), BPPP_RP_EXCESS_BAD_R (4),
+ * BPPP_RP_OPEN_OK.  IT DOES NOT EVALUATE THE EQUATION of any signature: run bppp_rp_excess_verify_keys_batch over the same buffers first.  If any
+ * signature is refused agg is all zero bytes; with status == NULL a refusal is BPPP_ERR_ARG and bppp_last_error names the lowest refused key
+ * ("key N: ..."), as bppp_rp_excess_keys does for its sums.
+ *
+ * bppp_rp_excess_halfagg_verify{,_device}: *accept = 1 iff no key is BAD_KEY, no R row is BAD_R, s_agg < n and the combined point is the
+ * identity.  status (host, may be NULL, [nkeys]), per key the first that applies of 6, 4, 3 (for every key still open when s_agg >= n), otherwise
+ * the ONE verdict of the equation, BPPP_RP_OPEN_MISMATCH or BPPP_RP_OPEN_OK, for all open keys alike.  combined_xy (host, may be NULL): the left
+ * side of the equation over the open keys, infinity as zeros.
+ *
+ * bppp_rp_verify_block_agg{,_device}: bppp_rp_verify_block with the aggregate in place of the signatures.  blk->sigs must be NULL and
+ * blk->key_offset 0 (else BPPP_ERR_ARG); agg [33 nkeys + 32] lies where the struct's pointers lie (host / HBM).  combined = V + K' + S with V and S
+ * exactly as in bppp_rp_verify_block under seed_0 and seed_2, and
+ *   K' = rho_A (s_agg B - sum_k z_k (c_k X_k + R_k)),
+ *   rho_A = decode (SHA-256 (seed_1 || le64 (nkeys) || root || the 32 bytes of s_agg)) mod n, 1 in place of 0                        — 104 bytes.
+ * Key k of sum t carries the one scalar  n - rho_A z_k c_k - rho^S_t  on X_k, and every key is lifted once.  On rejection key_status is that of
+ * bppp_rp_excess_halfagg_verify; proof_status and sum_status are as in the block call, and so are the one-pass limits, errors and texts.
+ *
+ * nkeys == 0 is BPPP_OK (*accept = 1; the aggregator writes nothing) and nothing else is looked at.  BPPP_ERR_ARG: a NULL handle or buffer,
+ * nkeys >= 2^31.  The host variants upload, call the _device variant and download; status and point arrays are host memory. */
+#define BPPP_RP_EXCESS_AGG_BYTES(n) (33 * (size_t)(n) + 32)
+int bppp_rp_excess_halfagg(bppp_rp *rp, size_t nkeys, const uint8_t *keys, const uint8_t *msgs, const uint8_t *sigs, uint8_t *agg, uint32_t *status /* may be NULL */);
+int bppp_rp_excess_halfagg_device(bppp_rp *rp, size_t nkeys, const void *d_keys, const void *d_msgs, const void *d_sigs, void *d_agg,
+                                  uint32_t *status /* host, [nkeys], may be NULL */);
+int bppp_rp_excess_halfagg_verify(bppp_rp *rp, size_t nkeys, const uint8_t *keys, const uint8_t *msgs, const uint8_t *agg, int *accept,
+                                  uint32_t *status /* may be NULL */, uint64_t *combined_xy /* may be NULL */);
+int bppp_rp_excess_halfagg_verify_device(bppp_rp *rp, size_t nkeys, const void *d_keys, const void *d_msgs, const void *d_agg, int *accept,
+                                         uint32_t *status /* host, may be NULL */, uint64_t *combined_xy /* may be NULL */);
+int bppp_rp_verify_block_agg(bppp_rp *rp, const bppp_rp_block *blk, const uint8_t *agg, const uint8_t seed[32], int *accept,
+                             const bppp_rp_block_status *status /* may be NULL */, uint64_t *combined_xy /* may be NULL */);
+int bppp_rp_verify_block_agg_device(bppp_rp *rp, const bppp_rp_block *blk, const void *d_agg, const uint8_t seed[32], int *accept,
+                                    const bppp_rp_block_status *status /* may be NULL */, uint64_t *combined_xy /* may be NULL */);
+
 /* ---- one comb table for the handles of a basis family --------------------------------------------------------------------------
  * Every setup's basis [g | H | G] is a prefix of the point stream its points came from (see bppp_rp_verify_mixed), and the comb table
  * is laid out tab[window][point][multiple]: the table of the longest basis of a stream contains the table of every shorter one (same

@@ -209,12 +209,12 @@ int bppp_test_rpp_draws(bppp_ctx *ctx, const uint8_t *prefixes, size_t prefix_le
  * _ctx_ (members of bppp_ctx, csrc/ctx.hpp); it also drops last_msm_valid, so bppp_test_last_msm_layout / _copy refuse instead of copying poison:
  *   ws           scratch     the MSM's workspace, carved per call (csrc/msm.hip), and the batch inversion's (csrc/rounds.hip)
  *   ws2          scratch     what a caller that also runs an MSM assembles for it (csrc/nlbatch.hip, nl.hip, ip.hip, glv.hip, trrp.hip, seedpoints.hip, rpmixed.hip, rpblock.hip)
- *   mix          scratch     one call's MSM input and shared scalars of the multi-setup verifier and the block call, the input commitments of one bppp_rp_prove_mixed (csrc/rpmixed.hip, rpblock.hip, rpshare.hip)
+ *   mix          scratch     one call's MSM input and shared scalars of the multi-setup verifier and the block call, the input commitments of one bppp_rp_prove_mixed (csrc/rpmixed.hip, rpblock.hip — with the half-aggregate's tree in bppp_rp_verify_block_agg —, rpshare.hip)
  *   pinned       scratch     pinned host staging of small results and uploads (csrc/msm.hip, rounds.hip, ip.hip, capi.hip)
  *   pre_acc, pre_acc_arg     not buffers: the one-shot upload hook of bppp_msm and its argument, set and cleared within one call (csrc/msm.hip)
  * _rp_ (members of bppp_rp, csrc/rp_internal.hpp); with a twin handle (a split prove batch), the twin's buffers and the twin's own context as well, but
  * NOT the handle's own context: the caller poisons both:
- *   pwork        scratch     the provers' and the commit / open / tally / excess calls' workspace (csrc/rpprove.hip, rpprove_dev.hip, brpprove*.hip, rpcommit.hip, rptally.hip, rpexcess.hip, rpexkeys.hip, rpexpart.hip)
+ *   pwork        scratch     the provers' and the commit / open / tally / excess calls' workspace (csrc/rpprove.hip, rpprove_dev.hip, brpprove*.hip, rpcommit.hip, rptally.hip, rpexcess.hip, rpexkeys.hip, rpexpart.hip, rpexagg.hip: the half-aggregate's leaves and tree levels in front of a pass)
  *   awork        scratch     the device-resident inner-product argument's workspace and final witness (csrc/rpprove_dev.hip hands it to ipb_prove_stream, csrc/ipb.hip)
  *   hpin         scratch     pinned staging of the batch provers (csrc/rpprove.hip, brpprove.hip)
  *   work         scratch     the verifier's per-proof arrays of one prepared batch (csrc/rp.hip: rp_verify_prepare)
