@@ -12,6 +12,7 @@
 #include "rpdecode.hip.h"
 #include "rpexcess.hip.h"
 #include "rpexpart.hip.h"
+#include "rpseal.hip.h"
 #include "seedpoints.hip.h"
 #include "comb.hip.h"
 #include "rpp_transcript.hpp"
@@ -560,6 +561,43 @@ extern "C" int bppp_test_rp_excess_mul2(bppp_rp *rp, size_t n, const void *d_b, 
                                                                                        (const uint32_t *)d_Q_xy, (uint32_t *)d_out_xy);
   const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
   return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_rp_excess_mul2: kernel failed");
+}
+
+// the fixed-scalar walk of bppp_rp_scan alone: one lane per point, the recoded scalar a kernel argument; a second launch inverts and stores
+namespace bppp {
+__global__ void __launch_bounds__(64) k_test_scan_mul(uint32_t n, ScanWalk W, const uint32_t *__restrict__ pts, uint32_t *__restrict__ acc) {
+  __shared__ ScanTab tab[SCAN_TAB_WORDS];
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  xyzz_store(acc + (size_t)i * XYZZ_WORDS, scan_mul_lane(W, aff_load(pts + (size_t)i * 16), tab, threadIdx.x));
+}
+__global__ void __launch_bounds__(64) k_test_scan_affine(uint32_t n, const uint32_t *__restrict__ acc, uint32_t *__restrict__ out) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i < n) scan_affine_lane(acc + (size_t)i * XYZZ_WORDS, out + (size_t)i * 16);
+}
+}  // namespace bppp
+extern "C" int bppp_test_rp_scan_mul(bppp_rp *rp, size_t n, const uint64_t scalar[4], const void *d_points_xy, void *d_out_xy) {
+  if (!rp || !n || n >= (1u << 24) || !scalar || !d_points_xy || !d_out_xy) return BPPP_ERR_ARG;
+  bppp_ctx *ctx = rp->ctx;
+  ScanWalk W;
+  if (!scan_recode(scalar, W)) return bppp::fail(ctx, BPPP_ERR_ARG, "test_rp_scan_mul: the scalar's halves do not fit the walk");
+  hipSetDevice(ctx->device);
+  uint32_t *acc = nullptr;
+  BPPP_HIP(ctx, hipMalloc(&acc, n * XYZZ_WORDS * 4));
+  const dim3 grid((unsigned)((n + 63) / 64));
+  k_test_scan_mul<<<grid, dim3(64), 0, ctx->stream>>>((uint32_t)n, W, (const uint32_t *)d_points_xy, acc);
+  k_test_scan_affine<<<grid, dim3(64), 0, ctx->stream>>>((uint32_t)n, acc, (uint32_t *)d_out_xy);
+  const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess;
+  hipFree(acc);
+  return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_rp_scan_mul: kernel failed");
+}
+// the host recoding that walk is driven by: words [0, 9) the two-bit digits, word 9 their number, word 10 the signs of the halves.  Host only.
+extern "C" int bppp_test_rp_scan_recode(const uint64_t scalar[4], uint32_t out[11]) {
+  ScanWalk W;
+  if (!scalar || !out || !scan_recode(scalar, W)) return BPPP_ERR_ARG;
+  for (uint32_t k = 0; k < SCAN_DIGIT_WORDS; k++) out[k] = W.d[k];
+  out[SCAN_DIGIT_WORDS] = W.nbits; out[SCAN_DIGIT_WORDS + 1] = W.neg;
+  return BPPP_OK;
 }
 
 extern "C" int bppp_test_rp_witness_device(bppp_rp *rp, size_t batch, const void *d_amounts, const void *d_types, const void *d_blinds, const void *d_public_amounts,

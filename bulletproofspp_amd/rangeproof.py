@@ -1397,6 +1397,76 @@ class NativeRangeProofs:
         self.gpu._check(fn(self.h, n, pb, pk, C.c_void_p(status.ctypes.data) if want_status else None), "bppp_rp_excess_keys")
         return [int(v) for v in status[:n]] if want_status else None
 
+    # ---- sealed outputs: a one-sided receive and the view-key scan (bppp_rp_seal / bppp_rp_scan)
+    def seal(self, view_keys: Sequence[bytes], eph: Sequence[int], outputs, want_status: bool = False):
+        """bppp_rp_seal: row b is sealed to the 33-byte view key view_keys[b] under the ephemeral secret eph[b]; outputs[b] = one (amount, type) per
+        range (the type is ignored on a binary handle).  Returns (seals, blinds) — the seal's bytes and the blindings to commit or prove with, one
+        list per row — or (seals, blinds, statuses) with want_status (a refused row has zero bytes and zero blindings); without it a refused row
+        raises BpppError."""
+        import ctypes as C
+        import numpy as np
+        from .capi import array_to_scalars, scalars_to_array
+        B, nr, sb = len(outputs), len(self.st.rds), SEAL_BYTES(len(self.st.rds))
+        if len(view_keys) != B or len(eph) != B or any(len(k) != EXCESS_KEY_BYTES for k in view_keys) or any(len(row) != nr for row in outputs):
+            raise ValueError("one 33-byte view key, one ephemeral secret and one (amount, type) per range are required per row")
+        if B == 0:
+            return ([], [], []) if want_status else ([], [])
+        keys = np.frombuffer(b"".join(view_keys), dtype=np.uint8)
+        e, amt = scalars_to_array(list(eph)), scalars_to_array([v % 2**256 for row in outputs for v, _ in row])
+        typ = scalars_to_array([t for row in outputs for _, t in row])
+        seals, blinds, status = np.zeros(B * sb, dtype=np.uint8), np.zeros((B * nr, 4), dtype=np.uint64), np.zeros(B, dtype=np.uint32)
+        vp = lambda a: C.c_void_p(a.ctypes.data)
+        rc = self.gpu.lib.bppp_rp_seal(self.h, B, vp(keys), vp(e), vp(amt), vp(typ), vp(seals), vp(blinds), vp(status) if want_status else None)
+        self.gpu._check(rc, "bppp_rp_seal")
+        bl = array_to_scalars(blinds)
+        out = ([seals[b * sb:(b + 1) * sb].tobytes() for b in range(B)], [bl[b * nr:(b + 1) * nr] for b in range(B)])
+        return out + ([int(s) for s in status],) if want_status else out
+
+    def seal_device(self, batch: int, d_view_keys: int, d_eph: int, d_amounts: int, d_types: int, d_seals: int, d_blinds: int, want_status: bool = False):
+        """bppp_rp_seal_device: seal on buffers in HBM (device pointers; d_types is 0 on a binary handle); d_seals receives [batch][SEAL_BYTES] bytes and
+        d_blinds [batch][nranges][4] words.  Returns the verdicts (numpy uint32 [batch]) with want_status, else None (a refused row raises)."""
+        import ctypes as C
+        import numpy as np
+        status = np.zeros(max(batch, 1), dtype=np.uint32)
+        rc = self.gpu.lib.bppp_rp_seal_device(self.h, batch, C.c_void_p(d_view_keys), C.c_void_p(d_eph), C.c_void_p(d_amounts), C.c_void_p(d_types), C.c_void_p(d_seals),
+                                              C.c_void_p(d_blinds), C.c_void_p(status.ctypes.data) if want_status else None)
+        self.gpu._check(rc, "bppp_rp_seal_device")
+        return status[:batch] if want_status else None
+
+    def scan(self, view_secret: int, coms_files: Sequence[bytes], seals: Sequence[bytes]):
+        """bppp_rp_scan: the rows of (commitments file, seal) that belong to the view secret.  Returns (statuses, openings, nowned): capi.RP_SCAN_* per
+        row, and per row one (amount, type, blinding) per range — the amount as the scalar in [0, n) — all zeros unless the row is owned."""
+        import ctypes as C
+        import numpy as np
+        from .capi import array_to_scalars, int_to_limbs
+        rows, nr, sb = len(seals), len(self.st.rds), SEAL_BYTES(len(self.st.rds))
+        if any(len(s) != sb for s in seals):
+            raise ValueError("every seal has SEAL_BYTES (nranges) bytes")
+        a = int_to_limbs(view_secret % 2**256)
+        cf = self._coms_array(coms_files, rows)
+        sl = np.frombuffer(b"".join(seals) or b"\0", dtype=np.uint8)
+        status = np.zeros(max(rows, 1), dtype=np.uint32)
+        out = [np.zeros((max(rows, 1) * nr, 4), dtype=np.uint64) for _ in range(3)]
+        nowned = C.c_size_t(0)
+        vp = lambda x: C.c_void_p(x.ctypes.data)
+        rc = self.gpu.lib.bppp_rp_scan(self.h, vp(a), rows, vp(cf), vp(sl), vp(status), vp(out[0]), vp(out[1]), vp(out[2]), C.byref(nowned))
+        self.gpu._check(rc, "bppp_rp_scan")
+        v, t, bl = (array_to_scalars(o) for o in out)
+        return ([int(s) for s in status[:rows]], [[(v[b * nr + i], t[b * nr + i], bl[b * nr + i]) for i in range(nr)] for b in range(rows)], int(nowned.value))
+
+    def scan_device(self, view_secret: int, rows: int, d_coms: int, d_seals: int, d_amounts: int = 0, d_types: int = 0, d_blinds: int = 0):
+        """bppp_rp_scan_device: scan on buffers in HBM (device pointers; an output pointer of 0 is not written).  Returns (statuses as numpy uint32
+        [rows], nowned)."""
+        import ctypes as C
+        import numpy as np
+        from .capi import int_to_limbs
+        a = int_to_limbs(view_secret % 2**256)
+        status, nowned = np.zeros(max(rows, 1), dtype=np.uint32), C.c_size_t(0)
+        rc = self.gpu.lib.bppp_rp_scan_device(self.h, C.c_void_p(a.ctypes.data), rows, C.c_void_p(d_coms), C.c_void_p(d_seals), C.c_void_p(status.ctypes.data),
+                                              C.c_void_p(d_amounts), C.c_void_p(d_types), C.c_void_p(d_blinds), C.byref(nowned))
+        self.gpu._check(rc, "bppp_rp_scan_device")
+        return status[:rows], int(nowned.value)
+
     def _excess_key_args(self, keys, msgs, sigs):
         import ctypes as C
         n = len(keys)
@@ -2204,6 +2274,89 @@ def block_agg_weight(seed: bytes, nkeys: int, root: bytes, s32: bytes) -> int:
     """rho_A of bppp_rp_verify_block_agg: decode (SHA-256 (seed_1 || le64 (nkeys) || root || the 32 bytes of s_agg)) mod n, 1 for 0: 104 bytes; seed:
     block_seeds (seed)[1]"""
     return decode_field(hashlib.sha256(seed + nkeys.to_bytes(8, "little") + root + s32).digest(), N) or 1
+
+
+# ---- sealed outputs (bppp_rp_seal / bppp_rp_scan): a one-sided receive; include/bppp.h states every message
+SEAL_OK, SEAL_NOT_CANONICAL, SEAL_ZERO = 0, 1, 2
+SCAN_FOREIGN, SCAN_OWNED, SCAN_BAD_HINT, SCAN_TAG_ONLY = 0, 1, 2, 3
+
+
+def SEAL_BYTES(nranges: int) -> int:
+    """BPPP_RP_SEAL_BYTES: the hint R (33 bytes), the view tag, 64 memo bytes per range"""
+    return 34 + 64 * nranges
+
+
+def _seal_domain(part: bytes, tag: bytes) -> bytes:
+    return hashlib.sha256(b"bppp/seal/" + part + b"/v1" + tag).digest()
+
+
+def seal_shared(tag: bytes, P: Tuple[int, int], r33: bytes) -> bytes:
+    """ss = SHA-256 (Ds || put (P.x) || sign (P) || the 33 bytes of R as stored): 98 bytes"""
+    return hashlib.sha256(_seal_domain(b"shared", tag) + _point33(P) + r33).digest()
+
+
+def seal_view_tag(tag: bytes, ss: bytes) -> int:
+    return hashlib.sha256(_seal_domain(b"tag", tag) + ss).digest()[0]
+
+
+def seal_blind(tag: bytes, ss: bytes, i: int) -> int:
+    return decode_field(hashlib.sha256(_seal_domain(b"blind", tag) + ss + i.to_bytes(4, "little")).digest(), N)
+
+
+def seal_pad(tag: bytes, ss: bytes, i: int) -> bytes:
+    dm = _seal_domain(b"memo", tag)
+    return b"".join(hashlib.sha256(dm + ss + i.to_bytes(4, "little") + bytes([h])).digest() for h in (0, 1))
+
+
+def _xor(a: bytes, b: bytes) -> bytes:
+    return bytes(x ^ y for x, y in zip(a, b))
+
+
+def seal_host(backend: "Backend", setup, view_key: bytes, r: int, outputs: Sequence[Tuple[int, int]], tag: bytes = b""):
+    """Host restatement of bppp_rp_seal for one row: outputs = one (amount, type) per range (the type of a binary setup is ignored).  Returns
+    (status, the seal's bytes, the blindings); a refused row has zero bytes and zero blindings."""
+    _, H0, B = _excess_bases(setup)
+    nr = len(outputs)
+    types = [ty if H0 is not None else 0 for _, ty in outputs]
+    A = excess_lift33(view_key)
+    status = EXCESS_BAD_KEY if A is None else SEAL_NOT_CANONICAL if not 0 <= r < N or any(not 0 <= t < N for t in types) else SEAL_ZERO if r == 0 else SEAL_OK
+    if status != SEAL_OK:
+        return status, bytes(SEAL_BYTES(nr)), [0] * nr
+    r33 = _point33(backend.commit([r], [B]))
+    ss = seal_shared(tag, backend.commit([r], [A]), r33)
+    memos = [_xor(_put(v % N) + _put(t), seal_pad(tag, ss, i)) for i, ((v, _), t) in enumerate(zip(outputs, types))]
+    return status, r33 + bytes([seal_view_tag(tag, ss)]) + b"".join(memos), [seal_blind(tag, ss, i) for i in range(nr)]
+
+
+def _seal_decode_com(coms_file: bytes, nr: int, i: int) -> Optional[Tuple[int, int]]:
+    """commitment i of a commitments file (decodeCommitments, one point): None when its x has no curve point"""
+    ns = (nr + 7) // 8
+    return excess_lift33(coms_file[ns + 32 * i:ns + 32 * i + 32] + bytes([(coms_file[i >> 3] >> (i & 7)) & 1]))
+
+
+def scan_host(backend: "Backend", setup, a: int, coms_file: bytes, seal: bytes, tag: bytes = b""):
+    """Host restatement of bppp_rp_scan for one row under the view secret a (1 <= a < n): (verdict, [(amount, type, blinding)] per range); every
+    row that is not owned has zeros."""
+    g, H0, B = _excess_bases(setup)
+    nr = (len(seal) - 34) // 64
+    zeros = [(0, 0, 0)] * nr
+    R = excess_lift33(seal[:33])
+    if R is None:
+        return SCAN_BAD_HINT, zeros
+    ss = seal_shared(tag, backend.commit([a], [R]), seal[:33])
+    if seal_view_tag(tag, ss) != seal[33]:
+        return SCAN_FOREIGN, zeros
+    out = []
+    for i in range(nr):
+        m = _xor(seal[34 + 64 * i:98 + 64 * i], seal_pad(tag, ss, i))
+        v, ty, bl = _get256(m[:32]), _get256(m[32:]), seal_blind(tag, ss, i)
+        C = _seal_decode_com(coms_file, nr, i)
+        if v >= N or ty >= N or (H0 is None and ty) or C is None:          # a binary setup has no type base: a seal that carries a type names no commitment of it
+            return SCAN_TAG_ONLY, zeros
+        if C != _commit_terms(backend, [(v, g), (bl, B)] + ([(ty, H0)] if H0 is not None else [])):
+            return SCAN_TAG_ONLY, zeros
+        out.append((v, ty, bl))
+    return SCAN_OWNED, out
 
 
 # ---- the multi-party signer (bppp_rp_excess_part_*): builders who each know a part e_i of the blinding sum; include/bppp.h states every message

@@ -1177,6 +1177,73 @@ int bppp_rp_verify_block_agg(bppp_rp *rp, const bppp_rp_block *blk, const uint8_
 int bppp_rp_verify_block_agg_device(bppp_rp *rp, const bppp_rp_block *blk, const void *d_agg, const uint8_t seed[32], int *accept,
                                     const bppp_rp_block_status *status /* may be NULL */, uint64_t *combined_xy /* may be NULL */);
 
+/* ---- sealed outputs: a one-sided receive, and the view-key scan of an output set ---------------------------------------------------
+ * Every call above assumes that the owner of an output knows its amount, type and blinding.  A SEAL next to an output lets the holder of a view
+ * secret find the outputs that are its own in a set of outputs, with their openings, without having been online when they were made.
+ * put, decode, the sign byte and the 33-byte point format are those of the excess keys; tag = the handle's oracle tag bytes; B, g, H0 and the
+ * commitment C = v g + ty H0 + bl B are bppp_rp_commit_batch's (B = H1, or h0 of a binary handle, which has no H0); n = the group order.
+ *
+ * KEYS.  The view secret is a, 1 <= a < n; the view key is A = a B as 33 bytes: bppp_rp_excess_keys with claim_blinds = a writes it.
+ * DOMAINS, computed once per call on the host:
+ *   Ds = SHA-256 ("bppp/seal/shared/v1" || tag), Dt = SHA-256 ("bppp/seal/tag/v1" || tag), Db = SHA-256 ("bppp/seal/blind/v1" || tag),
+ *   Dm = SHA-256 ("bppp/seal/memo/v1" || tag).
+ * ROW, with the ephemeral secret r (1 <= r < n) and the recipient's key A:
+ *   R  = r B, the hint, stored as 33 bytes;  P = r A = a R, the shared point;
+ *   ss = SHA-256 (Ds || put (P.x) || sign (P) || the 33 bytes of R as stored)                                                      —  98 bytes
+ *   vt = the first byte of SHA-256 (Dt || ss), the view tag                                                                        —  64 bytes
+ * and per range i of the row:
+ *   bl_i   = decode (SHA-256 (Db || ss || le32 (i))) mod n                                                                         —  68 bytes
+ *   pad_i  = SHA-256 (Dm || ss || le32 (i) || 0x00) || SHA-256 (Dm || ss || le32 (i) || 0x01), 64 bytes                            —  69 bytes each
+ *   memo_i = (put (v_i mod n) || put (ty_i)) XOR pad_i, with ty_i = 0 on a binary handle.
+ * SEAL of a row:  R[33] || vt[1] || memo_0 .. memo_{nranges - 1}  =  BPPP_RP_SEAL_BYTES (nranges) = 34 + 64 nranges bytes.
+ *
+ * CAVEATS.  The sender knows the blindings, as in every non-interactive output of this kind: the receiver of a one-sided payment re-spends it
+ * into an output of its own.  The intended uses are restore-from-seed (the wallet seals to its own key with r derived from its seed) and such
+ * one-sided payments.  Script keys, a defence against a sender who re-spends, and rewinding the proof itself are not here.  There is no
+ * side-channel hardening, as everywhere in this library.
+ *
+ * bppp_rp_seal{,_device}: view_keys [batch][33], eph [batch][4] words (r), amounts and types [batch][nranges][4] words laid out and encoded as for
+ * bppp_rp_commit_batch (types may be NULL on a binary handle, which ignores it) -> seals [batch][BPPP_RP_SEAL_BYTES (nranges)] and blinds
+ * [batch][nranges][4] words: the caller then commits or proves with these blindings, and nothing else changes for the prover.
+ * seal_status (host, may be NULL, [batch]), the first that applies:
+ *   BPPP_RP_EXCESS_BAD_KEY (6)      the view key's sign byte is above 1, or its x has no curve point (bppp_rp_excess_verify_keys_each's rule)
+ *   BPPP_RP_SEAL_NOT_CANONICAL (1)  r or a type is >= n
+ *   BPPP_RP_SEAL_ZERO (2)           r = 0
+ *   BPPP_RP_SEAL_OK (0)
+ * A refused row gets zero bytes and zero blindings.  With seal_status == NULL a refusal is BPPP_ERR_ARG and bppp_last_error names the lowest such
+ * row ("rp_seal: row N: ..."), as bppp_rp_commit_batch does; the outputs are complete either way.
+ *
+ * bppp_rp_scan{,_device}: view_secret [4] words on the host, coms_files [rows][coms_bytes] as bppp_rp_open_each takes them and seals
+ * [rows][BPPP_RP_SEAL_BYTES (nranges)] -> scan_status (host, required, [rows]), per row the first that applies:
+ *   BPPP_RP_SCAN_BAD_HINT (2)  R's sign byte is not 0 or 1, or its x has no curve point (the rule of BPPP_RP_EXCESS_BAD_R)
+ *   BPPP_RP_SCAN_FOREIGN (0)   the view tag differs
+ *   BPPP_RP_SCAN_TAG_ONLY (3)  the tag matches (one foreign row in 256 does so by chance), but a decrypted amount or type is >= n (on a binary
+ *                              handle: the type is not 0, for its commitments have no type term), or a commitment of the row is malformed, or a
+ *                              commitment does not equal v' g + ty' H0 + bl_i B under bppp_rp_open_each's comparison
+ *   BPPP_RP_SCAN_OWNED (1)     every commitment of the row opens
+ * amounts, types, blinds (each may be NULL; [rows][nranges][4] words; HBM in the _device variant): an owned row receives v' (the scalar in [0, n):
+ * a negative amount reads as n - |v|), ty' and bl; every other row receives zeros.  *nowned (host, may be NULL): the number of owned rows.
+ * The rows go through in passes of bounded workspace (a R by a walk that takes the one scalar of the call as a kernel argument, one lane per row);
+ * a foreign row costs that walk and two hashes.  Rows are independent: a caller with several GPUs slices them.
+ * BPPP_ERR_ARG: a NULL handle or required buffer, a = 0 or a >= n, rows * nranges >= 2^31.  rows == 0 (or batch == 0) is BPPP_OK and nothing else
+ * is looked at, except that the scan still judges the view secret.  The host variants upload, call the _device variant and download. */
+#define BPPP_RP_SEAL_BYTES(nranges) (34 + 64 * (size_t)(nranges))
+#define BPPP_RP_SEAL_OK 0u
+#define BPPP_RP_SEAL_NOT_CANONICAL 1u
+#define BPPP_RP_SEAL_ZERO 2u
+#define BPPP_RP_SCAN_FOREIGN 0u
+#define BPPP_RP_SCAN_OWNED 1u
+#define BPPP_RP_SCAN_BAD_HINT 2u
+#define BPPP_RP_SCAN_TAG_ONLY 3u
+int bppp_rp_seal(bppp_rp *rp, size_t batch, const uint8_t *view_keys, const uint64_t *eph, const uint64_t *amounts, const uint64_t *types /* may be NULL: binary */,
+                 uint8_t *seals, uint64_t *blinds, uint32_t *seal_status /* may be NULL */);
+int bppp_rp_seal_device(bppp_rp *rp, size_t batch, const void *d_view_keys, const void *d_eph, const void *d_amounts, const void *d_types, void *d_seals,
+                        void *d_blinds, uint32_t *seal_status /* host, [batch], may be NULL */);
+int bppp_rp_scan(bppp_rp *rp, const uint64_t view_secret[4], size_t rows, const uint8_t *coms_files, const uint8_t *seals, uint32_t *scan_status,
+                 uint64_t *amounts /* may be NULL */, uint64_t *types /* may be NULL */, uint64_t *blinds /* may be NULL */, size_t *nowned /* may be NULL */);
+int bppp_rp_scan_device(bppp_rp *rp, const uint64_t view_secret[4], size_t rows, const void *d_coms_files, const void *d_seals, uint32_t *scan_status /* host, [rows] */,
+                        void *d_amounts /* may be NULL */, void *d_types /* may be NULL */, void *d_blinds /* may be NULL */, size_t *nowned /* may be NULL */);
+
 /* ---- one comb table for the handles of a basis family --------------------------------------------------------------------------
  * Every setup's basis [g | H | G] is a prefix of the point stream its points came from (see bppp_rp_verify_mixed), and the comb table
  * is laid out tab[window][point][multiple]: the table of the longest basis of a stream contains the table of every shorter one (same

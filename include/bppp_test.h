@@ -127,6 +127,14 @@ int bppp_test_rp_excess_mul(bppp_rp *rp, size_t n, const void *d_scalars, const 
  * instances of four lanes each.  d_b and d_c [n][4] words (walked as the 256-bit integers they are, reduced or not), d_P_xy, d_Q_xy and d_out_xy
  * [n][8] words (infinity as all zeros), all in HBM.  P = Q, P = -Q and infinity in either place are ordinary input. */
 int bppp_test_rp_excess_mul2(bppp_rp *rp, size_t n, const void *d_b, const void *d_P_xy, const void *d_c, const void *d_Q_xy, void *d_out_xy);
+/* The fixed-scalar walk of bppp_rp_scan alone (csrc/rpseal.hip.h): out_i = scalar P_i in affine form, infinity as all zeros, one lane per point and
+ * ONE scalar for all n of them.  scalar [4] words on the host (any 256-bit integer: reduced mod n, then split and recoded, before the launch),
+ * d_points_xy and d_out_xy [n][8] words in HBM (infinity as all zeros is ordinary input). */
+int bppp_test_rp_scan_mul(bppp_rp *rp, size_t n, const uint64_t scalar[4], const void *d_points_xy, void *d_out_xy);
+/* The recoding that walk is driven by, on the host alone (no GPU is touched): scalar mod n = a1 + a2 lambda; out[0 .. 8] hold the two-bit digits,
+ * digit i = bit i of |a1| + 2 * bit i of |a2| at bits 2 (i & 15) of word i >> 4; out[9] the number of digits, walked from the highest down;
+ * out[10] the signs (bit 0: a1 < 0, bit 1: a2 < 0). */
+int bppp_test_rp_scan_recode(const uint64_t scalar[4], uint32_t out[11]);
 /* The witness kernel of bppp_rp_prove_batch_device alone (csrc/rpwitness.hip.h): inputs in HBM as that entry point takes them
  * (d_types ignored on a binary handle, d_public_amounts NULL or CANONICAL scalars [batch][public_count][4]); its arrays copied to the
  * host: in_sc [batch][nranges][3][4] words, status [batch] (0 = a witness; the arrays of a refused proof are unspecified) and, typed:
