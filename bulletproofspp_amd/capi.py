@@ -50,6 +50,7 @@ SYMBOLS = [
     "bppp_rp_excess_halfagg", "bppp_rp_excess_halfagg_device", "bppp_rp_excess_halfagg_verify", "bppp_rp_excess_halfagg_verify_device",
     "bppp_rp_verify_block_agg", "bppp_rp_verify_block_agg_device",
     "bppp_rp_seal", "bppp_rp_seal_device", "bppp_rp_scan", "bppp_rp_scan_device",
+    "bppp_rp_scan_keys", "bppp_rp_scan_keys_device",
 ]
 
 
@@ -241,6 +242,8 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_seal_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp]
     lib.bppp_rp_scan.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]
     lib.bppp_rp_scan_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]
+    lib.bppp_rp_scan_keys.argtypes = [vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.POINTER(sz), C.POINTER(C.c_uint64)]
+    lib.bppp_rp_scan_keys_device.argtypes = [vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.POINTER(sz), C.POINTER(C.c_uint64)]
     lib.bppp_seed_candidate_x.argtypes =[C.c_char_p, sz, C.c_uint64, vp]
     lib.bppp_points_from_seed.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
     lib.bppp_points_from_seed_device.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
@@ -287,6 +290,9 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_rp_excess_mul2.argtypes = [vp, sz, vp, vp, vp, vp, vp]
     lib.bppp_test_rp_scan_mul.argtypes = [vp, sz, vp, vp, vp]
     lib.bppp_test_rp_scan_recode.argtypes = [vp, vp]
+    lib.bppp_test_rp_scan_keys_mul.argtypes = [vp, sz, vp, sz, vp, vp]
+    lib.bppp_test_rp_scan_keys_recode.argtypes = [vp, vp]
+    lib.bppp_test_rp_scan_keys_geometry.argtypes = [vp, sz, sz, vp]
     lib.bppp_test_rp_witness_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.bppp_test_points_from_seed_chunked.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, sz, vp, C.POINTER(C.c_uint64)]
     lib.bppp_test_seed_lift_digests.argtypes = [vp, C.c_char_p, sz, vp, vp, vp]
@@ -388,6 +394,7 @@ RP_EXCESS_NO_AGGREGATE = 8
 # sealed outputs (bppp_rp_seal / bppp_rp_scan): a seal's verdicts next to RP_EXCESS_BAD_KEY, a scanned row's verdicts, the bytes of a seal
 RP_SEAL_OK, RP_SEAL_NOT_CANONICAL, RP_SEAL_ZERO = 0, 1, 2
 RP_SCAN_FOREIGN, RP_SCAN_OWNED, RP_SCAN_BAD_HINT, RP_SCAN_TAG_ONLY = 0, 1, 2, 3
+RP_SCAN_MAX_KEYS = 1 << 20                                     # BPPP_RP_SCAN_MAX_KEYS: view secrets of one bppp_rp_scan_keys call
 
 
 def SEAL_BYTES(nranges: int) -> int:

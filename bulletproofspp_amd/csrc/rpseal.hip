@@ -32,36 +32,10 @@
 #include "rpexcess.hip.h"
 #include "rpexcess_shared.hip.h"
 #include "rpseal.hip.h"
+#include "rpsealhash.hip.h"
 #include "sha256.hip.h"
 
 namespace bppp {
-
-static constexpr uint32_t SEAL_HEAD = 34, SEAL_MEMO = 64;
-static constexpr uint32_t SCAN_OPEN = 0xFFFFFFFFu;      // a verdict still open
-struct SealDomains { ExDomain ds, dt, db, dm; };
-
-// ss = SHA-256 (Ds || put (P.x) || sign (P) || the 33 bytes of R as stored), as eight big-endian words; P: an affine point in memory
-template <class F> BPPP_DI void seal_shared(const ExDomain &ds, const uint32_t *P, F rbyte, uint32_t ss[8]) {
-  ex_digest<2>(98u, [&](uint32_t k) -> uint32_t { return k < 32 ? ex_dom_byte(ds, k) : k < 65 ? ex_pt_byte(P, k - 32) : rbyte(k - 65); }, ss);
-}
-BPPP_DI uint32_t seal_view_tag(const ExDomain &dt, const uint32_t ss[8]) {
-  uint32_t st[8];
-  ex_digest<2>(64u, [&](uint32_t k) -> uint32_t { return k < 32 ? ex_dom_byte(dt, k) : ex_word_byte(ss, k - 32); }, st);
-  return st[0] >> 24;
-}
-// byte k of  D || ss || le32 (i) [|| half]
-BPPP_DI uint32_t seal_range_byte(const ExDomain &d, const uint32_t ss[8], uint32_t i, uint32_t half, uint32_t k) {
-  return k < 32 ? ex_dom_byte(d, k) : k < 64 ? ex_word_byte(ss, k - 32) : k < 68 ? (i >> (8 * (k - 64))) & 0xFFu : half;
-}
-BPPP_DI fe seal_blind(const ExDomain &db, const uint32_t ss[8], uint32_t i) {
-  uint32_t st[8];
-  ex_digest<2>(68u, [&](uint32_t k) -> uint32_t { return seal_range_byte(db, ss, i, 0, k); }, st);
-  return ex_digest_scalar(st);
-}
-// pad_i as sixteen big-endian words
-BPPP_DI void seal_pad(const ExDomain &dm, const uint32_t ss[8], uint32_t i, uint32_t pad[16]) {
-  for (uint32_t h = 0; h < 2; h++) ex_digest<2>(69u, [&](uint32_t k) -> uint32_t { return seal_range_byte(dm, ss, i, h, k); }, pad + 8 * h);
-}
 
 // ---- seal
 __global__ void __launch_bounds__(64) k_rp_seal_check(uint32_t n, uint32_t nr, uint32_t binary, uint32_t slot, const uint8_t *__restrict__ keys,
@@ -204,11 +178,17 @@ __global__ void __launch_bounds__(64) k_rp_scan_judge(uint32_t n, uint32_t nr, u
 using namespace bppp;
 using namespace bppp::excess;
 
-namespace {
-
+namespace bppp {
 SealDomains seal_domains(const bppp_rp *rp) {
   return {domain("bppp/seal/shared/v1", rp->tag), domain("bppp/seal/tag/v1", rp->tag), domain("bppp/seal/blind/v1", rp->tag), domain("bppp/seal/memo/v1", rp->tag)};
 }
+void scan_lift_launch(bppp_rp *rp, uint32_t n, const uint8_t *d_seals, uint32_t *R, uint32_t *status) {
+  k_rp_scan_lift<<<dim3((n + 63) / 64), dim3(64), 0, rp->ctx->stream>>>(n, (uint32_t)BPPP_RP_SEAL_BYTES(rp->D.nr), d_seals, R, status);
+}
+}  // namespace bppp
+
+namespace {
+
 size_t seal_row_bytes(const bppp_rp *rp) { return BPPP_RP_SEAL_BYTES(rp->D.nr); }
 // rows per pass over the workspace, as the commit and open calls count them
 size_t pass_rows(const bppp_rp *rp, size_t rows) { return std::max<size_t>(1, std::min(rows, rpp_flat_chunk(rp) / rp->D.nr)); }

@@ -13,6 +13,7 @@
 #include "rpexcess.hip.h"
 #include "rpexpart.hip.h"
 #include "rpseal.hip.h"
+#include "rpscan_keys.hip.h"
 #include "seedpoints.hip.h"
 #include "comb.hip.h"
 #include "rpp_transcript.hpp"
@@ -597,6 +598,42 @@ extern "C" int bppp_test_rp_scan_recode(const uint64_t scalar[4], uint32_t out[1
   if (!scalar || !out || !scan_recode(scalar, W)) return BPPP_ERR_ARG;
   for (uint32_t k = 0; k < SCAN_DIGIT_WORDS; k++) out[k] = W.d[k];
   out[SCAN_DIGIT_WORDS] = W.nbits; out[SCAN_DIGIT_WORDS + 1] = W.neg;
+  return BPPP_OK;
+}
+
+// the multi-key walk of bppp_rp_scan_keys alone: the kernels of csrc/rpscan_keys.hip.h themselves — the table of every point once, then per tile of
+// keys one walk launch and one launch of the batched affine conversion, which writes the tile's rows of d_out_xy
+namespace {
+int scan_keys_mul_hook(bppp_rp *rp, size_t nkeys, const uint64_t *scalars, size_t n, const void *d_points_xy, void *d_out_xy) {
+  if (!rp || !nkeys || nkeys > BPPP_RP_SCAN_MAX_KEYS || !n || n >= (1u << 24) || !scalars || !d_points_xy || !d_out_xy) return BPPP_ERR_ARG;
+  bppp_ctx *ctx = rp->ctx;
+  std::vector<ScanKeyRec> recs(nkeys);
+  for (size_t k = 0; k < nkeys; k++)
+    if (!scan_keys_recode(scalars + 4 * k, recs[k])) return bppp::fail(ctx, BPPP_ERR_ARG, "test_rp_scan_keys_mul: the scalar's halves do not fit the walk");
+  const size_t kt = scan_keys_geometry(rpp_flat_chunk(rp), rp->D.nr, n, nkeys).kt;
+  hipSetDevice(ctx->device);
+  uint32_t *tab = nullptr, *acc = nullptr, *keys = nullptr;
+  bool ok = hipMalloc(&tab, (n + 63) / 64 * 64 * SCANK_TAB_WORDS * 4) == hipSuccess && hipMalloc(&acc, kt * n * XYZZ_WORDS * 4) == hipSuccess &&
+            hipMalloc(&keys, kt * sizeof(ScanKeyRec)) == hipSuccess;
+  ok = ok && scan_keys_mul_launch(ctx->stream, (uint32_t)n, recs.data(), nkeys, kt, (const uint32_t *)d_points_xy, tab, acc, keys, (uint32_t *)d_out_xy) == hipSuccess;
+  ok = ok && hipStreamSynchronize(ctx->stream) == hipSuccess;
+  hipFree(tab); hipFree(acc); hipFree(keys);
+  return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_rp_scan_keys_mul: kernel failed");
+}
+}  // namespace
+extern "C" int bppp_test_rp_scan_keys_mul(bppp_rp *rp, size_t nkeys, const uint64_t *scalars, size_t n, const void *d_points_xy, void *d_out_xy) {
+  return scan_keys_mul_hook(rp, nkeys, scalars, n, d_points_xy, d_out_xy);
+}
+extern "C" int bppp_test_rp_scan_keys_recode(const uint64_t scalar[4], uint32_t out[36]) {
+  ScanKeyRec W;
+  if (!scalar || !out || !scan_keys_recode(scalar, W)) return BPPP_ERR_ARG;
+  memcpy(out, &W, sizeof W);
+  return BPPP_OK;
+}
+extern "C" int bppp_test_rp_scan_keys_geometry(bppp_rp *rp, size_t rows, size_t nkeys, uint64_t out[3]) {
+  if (!rp || !out) return BPPP_ERR_ARG;
+  const ScanKeysGeom g = scan_keys_geometry(rpp_flat_chunk(rp), rp->D.nr, rows, nkeys);
+  out[0] = g.rows_pass; out[1] = g.kt; out[2] = g.open_chunk;
   return BPPP_OK;
 }
 

@@ -1467,6 +1467,69 @@ class NativeRangeProofs:
         self.gpu._check(rc, "bppp_rp_scan_device")
         return status[:rows], int(nowned.value)
 
+    # ---- the scan under many view secrets (bppp_rp_scan_keys)
+    def _scan_keys_hits(self, nhits: int, cap: int, hit_key, hit_row, v, t, bl):
+        nr, n = len(self.st.rds), min(nhits, cap)
+        return [(int(hit_key[h]), int(hit_row[h]), [(v[h * nr + i], t[h * nr + i], bl[h * nr + i]) for i in range(nr)]) for h in range(n)]
+
+    def scan_keys(self, view_secrets: Sequence[int], coms_files: Sequence[bytes], seals: Sequence[bytes]):
+        """bppp_rp_scan_keys: the rows of (commitments file, seal) under every secret of view_secrets in one call.  Returns (row_status, hits,
+        ntag_only): capi.RP_SCAN_* per row (BAD_HINT, else OWNED if some key owns it, else TAG_ONLY if some key's tag matched, else FOREIGN), the
+        hits as (key, row, opening) ordered by (row, key) with opening = one (amount, type, blinding) per range, and the number of (key, row) pairs
+        whose tag matched without the row opening.  Starts with cap = rows and calls once more with cap = nhits if that was too small."""
+        import ctypes as C
+        import numpy as np
+        from .capi import array_to_scalars, scalars_to_array
+        rows, nr, sb = len(seals), len(self.st.rds), SEAL_BYTES(len(self.st.rds))
+        if any(len(s) != sb for s in seals):
+            raise ValueError("every seal has SEAL_BYTES (nranges) bytes")
+        keys = scalars_to_array([a % 2**256 for a in view_secrets]) if len(view_secrets) else np.zeros((1, 4), dtype=np.uint64)
+        cf = self._coms_array(coms_files, rows)
+        sl = np.frombuffer(b"".join(seals) or b"\0", dtype=np.uint8)
+        status = np.zeros(max(rows, 1), dtype=np.uint32)
+        vp = lambda x: C.c_void_p(x.ctypes.data)
+        cap = rows
+        while True:
+            hk, hr = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint32)
+            out = [np.zeros((max(cap, 1) * nr, 4), dtype=np.uint64) for _ in range(3)]
+            nhits, ntag = C.c_size_t(0), C.c_uint64(0)
+            rc = self.gpu.lib.bppp_rp_scan_keys(self.h, len(view_secrets), vp(keys), rows, vp(cf), vp(sl), vp(status), cap, vp(hk), vp(hr), vp(out[0]), vp(out[1]), vp(out[2]),
+                                                C.byref(nhits), C.byref(ntag))
+            self.gpu._check(rc, "bppp_rp_scan_keys")
+            if nhits.value <= cap:
+                break
+            cap = nhits.value
+        hits = self._scan_keys_hits(nhits.value, cap, hk, hr, *(array_to_scalars(o) for o in out))
+        return [int(s) for s in status[:rows]], hits, int(ntag.value)
+
+    def scan_keys_device(self, view_secrets: Sequence[int], rows: int, d_coms: int, d_seals: int):
+        """bppp_rp_scan_keys_device: the same on files and seals in HBM (device pointers).  The hit list's openings are written to HBM buffers of this
+        call's own and downloaded, so the result is scan_keys': (row_status, hits, ntag_only).  Starts with cap = rows, once more with cap = nhits."""
+        import ctypes as C
+        import numpy as np
+        from .capi import array_to_scalars, scalars_to_array
+        nr, g = len(self.st.rds), self.gpu
+        keys = scalars_to_array([a % 2**256 for a in view_secrets]) if len(view_secrets) else np.zeros((1, 4), dtype=np.uint64)
+        status = np.zeros(max(rows, 1), dtype=np.uint32)
+        vp = lambda x: C.c_void_p(x.ctypes.data)
+        cap = rows
+        while True:
+            hk, hr = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint32)
+            nhits, ntag = C.c_size_t(0), C.c_uint64(0)
+            d_out = [g.alloc(max(cap, 1) * nr * 32) for _ in range(3)]
+            try:
+                rc = g.lib.bppp_rp_scan_keys_device(self.h, len(view_secrets), vp(keys), rows, C.c_void_p(d_coms), C.c_void_p(d_seals), vp(status), cap, vp(hk), vp(hr),
+                                                    C.c_void_p(d_out[0]), C.c_void_p(d_out[1]), C.c_void_p(d_out[2]), C.byref(nhits), C.byref(ntag))
+                g._check(rc, "bppp_rp_scan_keys_device")
+                out = [array_to_scalars(g.download(d, (max(cap, 1) * nr, 4), np.uint64)) for d in d_out] if nhits.value <= cap else None
+            finally:
+                for d in d_out:
+                    g.free(d)
+            if out is not None:
+                break
+            cap = nhits.value
+        return [int(s) for s in status[:rows]], self._scan_keys_hits(nhits.value, cap, hk, hr, *out), int(ntag.value)
+
     def _excess_key_args(self, keys, msgs, sigs):
         import ctypes as C
         n = len(keys)
@@ -2357,6 +2420,25 @@ def scan_host(backend: "Backend", setup, a: int, coms_file: bytes, seal: bytes, 
             return SCAN_TAG_ONLY, zeros
         out.append((v, ty, bl))
     return SCAN_OWNED, out
+
+
+SCAN_MAX_KEYS = 1 << 20
+
+
+def scan_keys_host(backend: "Backend", setup, secrets: Sequence[int], files: Sequence[bytes], seals: Sequence[bytes], tag: bytes = b""):
+    """Host restatement of bppp_rp_scan_keys: the literal K x rows loop over scan_host.  Returns (row_status, hits, ntag_only) — hits as (key, row,
+    opening) ordered by (row, key); a row is BAD_HINT, else OWNED if some key owns it, else TAG_ONLY if some key's tag matched, else FOREIGN."""
+    row_status, hits, ntag = [], [], 0
+    for i, (f, s) in enumerate(zip(files, seals)):
+        verdicts = []
+        for k, a in enumerate(secrets):
+            verdict, opening = scan_host(backend, setup, a, f, s, tag)
+            verdicts.append(verdict)
+            if verdict == SCAN_OWNED:
+                hits.append((k, i, opening))
+            ntag += verdict == SCAN_TAG_ONLY
+        row_status.append(next((v for v in (SCAN_BAD_HINT, SCAN_OWNED, SCAN_TAG_ONLY) if v in verdicts), SCAN_FOREIGN))
+    return row_status, hits, ntag
 
 
 # ---- the multi-party signer (bppp_rp_excess_part_*): builders who each know a part e_i of the blinding sum; include/bppp.h states every message

@@ -1244,6 +1244,41 @@ int bppp_rp_scan(bppp_rp *rp, const uint64_t view_secret[4], size_t rows, const 
 int bppp_rp_scan_device(bppp_rp *rp, const uint64_t view_secret[4], size_t rows, const void *d_coms_files, const void *d_seals, uint32_t *scan_status /* host, [rows] */,
                         void *d_amounts /* may be NULL */, void *d_types /* may be NULL */, void *d_blinds /* may be NULL */, size_t *nowned /* may be NULL */);
 
+/* ---- the scan under MANY view secrets ------------------------------------------------------------------------------------------------
+ * A scanning service holds the view secrets of its K accounts and tests every new output against each of them; a wallet restoring several accounts
+ * from one seed does the same.  bppp_rp_scan_keys{,_device} gives the verdicts of K scans in one pass over the output set and returns the owned
+ * (key, row) pairs as a compact hit list.  Wire formats, domains, hashes and status values are those above; no new bytes are defined.
+ *
+ * THE SPECIFICATION: for every key index k and row i, bppp_rp_scan_keys reports exactly what bppp_rp_scan with view_secrets[k] reports for row i.
+ *
+ * view_secrets [nkeys][4] words on the host, 1 <= nkeys <= BPPP_RP_SCAN_MAX_KEYS; coms_files and seals [rows][...] as bppp_rp_scan takes them.
+ * HITS.  A hit is a pair (k, i) that bppp_rp_scan under view_secrets[k] calls BPPP_RP_SCAN_OWNED for row i.  *nhits (host, required) is the number
+ * of ALL hits of the call, whatever cap is.  Hits are ordered by (row, key) ascending, and the first min (*nhits, cap) of them are written:
+ * hit_row[h], hit_key[h] (host, [cap]; may be NULL iff cap == 0) and the opening of row hit_row[h] under key hit_key[h] at slot h of amounts, types
+ * and blinds (each may be NULL; [cap][nranges][4] words; HBM in the _device variant) — the values bppp_rp_scan writes for that row.  Slots from
+ * *nhits up to cap receive zeros.  A caller that finds *nhits > cap calls again with a larger cap: that case is BPPP_OK, not an error.  Equal
+ * secrets in the list are allowed, and each is reported.
+ * row_status (host, [rows], may be NULL), the first that applies: BPPP_RP_SCAN_BAD_HINT (key-independent, by the rule of bppp_rp_scan);
+ * BPPP_RP_SCAN_OWNED: some key owns the row; BPPP_RP_SCAN_TAG_ONLY: some key's tag matched, but no key owns the row; BPPP_RP_SCAN_FOREIGN.
+ * *ntag_only (host, may be NULL): the number of pairs (k, i) that bppp_rp_scan would call BPPP_RP_SCAN_TAG_ONLY (about nkeys * rows / 256 occur
+ * by chance); they are counted, never listed.
+ * BPPP_ERR_ARG: a NULL handle or required buffer, nkeys == 0, nkeys > BPPP_RP_SCAN_MAX_KEYS, a secret that is 0 or >= n (bppp_last_error names the
+ * lowest such index: "rp_scan_keys: key N: ..."), rows * nranges >= 2^31.  With rows == 0 the call still judges the secrets and then returns BPPP_OK
+ * with *nhits = 0.  The host variant uploads, calls the _device variant and downloads.
+ * The rows go through in passes and the keys in tiles within a pass (rows outer, keys inner), so a pass's seals are lifted once for all keys; one
+ * launch walks a tile's keys over every row of the pass, one inversion a row serves the tile, and no buffer is sized by the 1 / 256 expectation:
+ * a job whose every pair is owned is answered like any other.  The recoded secrets are wiped, on the host and in HBM, before the call returns;
+ * there is no side-channel hardening, as everywhere in this library.  Rows and keys are independent: a caller with several GPUs slices either. */
+#define BPPP_RP_SCAN_MAX_KEYS ((size_t)1 << 20)
+int bppp_rp_scan_keys(bppp_rp *rp, size_t nkeys, const uint64_t *view_secrets /* host, [nkeys][4] */, size_t rows, const uint8_t *coms_files, const uint8_t *seals,
+                      uint32_t *row_status /* host, [rows], may be NULL */, size_t cap, uint32_t *hit_key, uint32_t *hit_row /* host, [cap]; may be NULL iff cap == 0 */,
+                      uint64_t *amounts, uint64_t *types, uint64_t *blinds /* each may be NULL; [cap][nranges][4] words */, size_t *nhits /* required */,
+                      uint64_t *ntag_only /* may be NULL */);
+int bppp_rp_scan_keys_device(bppp_rp *rp, size_t nkeys, const uint64_t *view_secrets /* host, [nkeys][4] */, size_t rows, const void *d_coms_files, const void *d_seals,
+                             uint32_t *row_status /* host, [rows], may be NULL */, size_t cap, uint32_t *hit_key, uint32_t *hit_row /* host, [cap] */,
+                             void *d_amounts, void *d_types, void *d_blinds /* HBM, each may be NULL; [cap][nranges][4] words */, size_t *nhits /* host, required */,
+                             uint64_t *ntag_only /* host, may be NULL */);
+
 /* ---- one comb table for the handles of a basis family --------------------------------------------------------------------------
  * Every setup's basis [g | H | G] is a prefix of the point stream its points came from (see bppp_rp_verify_mixed), and the comb table
  * is laid out tab[window][point][multiple]: the table of the longest basis of a stream contains the table of every shorter one (same

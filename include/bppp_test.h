@@ -135,6 +135,20 @@ int bppp_test_rp_scan_mul(bppp_rp *rp, size_t n, const uint64_t scalar[4], const
  * digit i = bit i of |a1| + 2 * bit i of |a2| at bits 2 (i & 15) of word i >> 4; out[9] the number of digits, walked from the highest down;
  * out[10] the signs (bit 0: a1 < 0, bit 1: a2 < 0). */
 int bppp_test_rp_scan_recode(const uint64_t scalar[4], uint32_t out[11]);
+/* The multi-key walk of bppp_rp_scan_keys alone (csrc/rpscan_keys.hip.h): the per-row table, the walk of a tile of keys in one launch and the
+ * batched affine conversion, without the hashes.  out[k][i] = scalars[k] P_i in affine form, infinity as all zeros.  scalars [nkeys][4] words on
+ * the host (any 256-bit integers: reduced mod n, split and recoded before the launch); d_points_xy [n][8] words and d_out_xy [nkeys][n][8] words
+ * in HBM (a point at infinity, all zeros, is ordinary input).  The keys go through in the tiles bppp_test_rp_scan_keys_geometry reports for
+ * (rows = n, nkeys). */
+int bppp_test_rp_scan_keys_mul(bppp_rp *rp, size_t nkeys, const uint64_t *scalars, size_t n, const void *d_points_xy, void *d_out_xy);
+/* The recoding that walk is driven by, on the host alone: the 36 words of a key record (csrc/rpscan_keys_plan.hpp).  scalar mod n = a1 + a2 lambda,
+ * each half as a width-4 signed sliding window with the half's sign folded in; position i is the byte at bits 8 (i & 3) of out[i >> 2], low nibble
+ * the digit of a1, high nibble of a2; a nibble is 0 for the digit 0, else (|digit| + 1) / 2 in its low three bits and 8 for a negative digit;
+ * out[33] the number of positions, walked from the highest down; out[34 .. 35] zero. */
+int bppp_test_rp_scan_keys_recode(const uint64_t scalar[4], uint32_t out[36]);
+/* The geometry bppp_rp_scan_keys would choose on this handle for (rows, nkeys): out[0] rows per pass, out[1] keys per tile (KT), out[2] survivors
+ * per open chunk.  Host only. */
+int bppp_test_rp_scan_keys_geometry(bppp_rp *rp, size_t rows, size_t nkeys, uint64_t out[3]);
 /* The witness kernel of bppp_rp_prove_batch_device alone (csrc/rpwitness.hip.h): inputs in HBM as that entry point takes them
  * (d_types ignored on a binary handle, d_public_amounts NULL or CANONICAL scalars [batch][public_count][4]); its arrays copied to the
  * host: in_sc [batch][nranges][3][4] words, status [batch] (0 = a witness; the arrays of a refused proof are unspecified) and, typed:
