@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Bit-exact Python model of csrc/fq29.hip.h and of the mixed addition of csrc/ec29.hip.h (Fq in 9 x 29-bit limbs, lazy magnitudes), with
+"""Bit-exact Python model of csrc/fq29.hip.h and of the mixed additions (complete, and exception-free with one fold for Y3) of csrc/ec29.hip.h (Fq in 9 x 29-bit limbs, lazy magnitudes), with
 assertions that every intermediate fits the 32 / 64-bit register it lives in on the GPU:  python benchmarks/fe29_model.py
 One branch is modelled by value only: the P = Q doubling, which the device runs on 10 x 26 limbs (xyzz_dbl_aff of ec.hip.h) and hands back
 normalised; xyzz_dbl_aff here returns the same canonical limbs from plain integers.
@@ -128,6 +128,21 @@ def sqr(a, bound=False):
             acc = u64(acc + a2[i] * a[k - i]); i += 1
         if k % 2 == 0:
             acc = u64(acc + a[k // 2] * a[k // 2])
+        return acc
+    return _product(col, bound)
+
+
+def mul_add2(a, b, c, d, bound=False):
+    """a b + c d in one pair of chains: both products' terms go into each column, one fold and one tail.  mag(a) mag(b) + mag(c) mag(d) <= 7
+    in, tight out: column 7 then holds 16 products of at most 7 * 8 * B29^2 together, what mul's 8 hold at 1 * 7 (the assertions decide)"""
+    for x in list(a) + list(b) + list(c) + list(d):
+        u32(x)
+
+    def col(k, acc):
+        for i in range(max(0, k - 8), min(8, k) + 1):
+            acc = u64(acc + a[i] * b[k - i])
+        for i in range(max(0, k - 8), min(8, k) + 1):
+            acc = u64(acc + c[i] * d[k - i])
         return acc
     return _product(col, bound)
 
@@ -265,6 +280,60 @@ def xyzz_madd(acc, q, bound=False):
     return out
 
 
+def _y3(Rw, Q, X3, Y, PPP, KY, bound):
+    """Y3 = R (Q - X3) - Y PPP as ONE reduced sum of two products (mul_add2): Q - X3 (1 + 6 = 7) takes a weak pass so that the pair stays
+    inside 1 * 1 + (KY + 1) * 1 <= 7; tight out"""
+    T = sub(Q, X3, 5, bound)
+    assert mag_ok(T, 7)
+    return mul_add2(Rw, weak_pass(T, bound), neg(Y, KY, bound), PPP, bound)
+
+
+def xyzz_madd_fast(acc, q, bound=False):
+    """acc += q for acc and q finite and q != +-acc: madd-2008-s with no test at all.  On any other input the limbs stay inside the same
+    bounds (they depend on the magnitudes alone) and ZZ3 = ZZ Pd^2 = 0 (mod p) from then on: the caller tests ZZ once per item"""
+    X, Y, ZZ, ZZZ = acc
+    assert mag_ok(X, 5) and mag_ok(Y, 3) and mag_ok(ZZ, 1) and mag_ok(ZZZ, 1) and mag_ok(q[0], 1) and mag_ok(q[1], 2)
+    U2 = mul(q[0], ZZ, bound); S2 = mul(q[1], ZZZ, bound)
+    Pw = weak_pass(sub(U2, X, 5, bound), bound); Rw = weak_pass(sub(S2, Y, 3, bound), bound)        # 7 -> 1, 5 -> 1
+    PP = sqr(Pw, bound); PPP = mul(Pw, PP, bound); Q = mul(X, PP, bound)                            # 5 * 1
+    X3 = sub(sqr(Rw, bound), add(PPP, mul_int(Q, 2, bound), bound), 3, bound)                       # 1 + 4 = 5
+    Y3 = _y3(Rw, Q, X3, Y, PPP, 3, bound)                                                           # 1 * 1 + 4 * 1 = 5 -> 1
+    out = [X3, Y3, mul(ZZ, PP, bound), mul(ZZZ, PPP, bound)]
+    assert mag_ok(out[0], 5) and mag_ok(out[1], 1) and mag_ok(out[2], 1) and mag_ok(out[3], 1)
+    return out
+
+
+def xyzz_from_two(p, q, bound=False):
+    """p + q for two finite affine points of different x (mmadd-2008-s, 4 M + 2 S), y magnitudes <= 2; x1 = x2 gives ZZ = 0 (mod p)"""
+    assert mag_ok(p[0], 1) and mag_ok(p[1], 2) and mag_ok(q[0], 1) and mag_ok(q[1], 2)
+    Pw = weak_pass(sub(q[0], p[0], 1, bound), bound); Rw = weak_pass(sub(q[1], p[1], 2, bound), bound)    # 3 -> 1, 5 -> 1
+    PP = sqr(Pw, bound); PPP = mul(Pw, PP, bound); Q = mul(p[0], PP, bound)
+    X3 = sub(sqr(Rw, bound), add(PPP, mul_int(Q, 2, bound), bound), 3, bound)                       # 1 + 4 = 5
+    Y3 = _y3(Rw, Q, X3, p[1], PPP, 2, bound)                                                        # 1 * 1 + 3 * 1 = 4 -> 1
+    out = [X3, Y3, PP, PPP]
+    assert mag_ok(out[0], 5) and mag_ok(out[1], 1) and mag_ok(out[2], 1) and mag_ok(out[3], 1)
+    return out
+
+
+def item_fast(points, bound=False, two=True):
+    """one item of k_acc_points_sized29_fast: entries (0, 0) skipped, the sum started from the first two finite ones through from_two (two=False:
+    from the first alone), the rest through madd_fast, one zero test of ZZ at the end; a flagged item is redone with the complete addition"""
+    fin = [q for q in points if not (is_zero_limbs(q[0]) and is_zero_limbs(q[1]))]
+    if not fin:
+        return xyzz_inf()
+    if two and len(fin) > 1:
+        acc, rest = xyzz_from_two(fin[0], fin[1], bound), fin[2:]
+    else:
+        acc, rest = xyzz_from_aff(fin[0]), fin[1:]
+    for q in rest:
+        acc = xyzz_madd_fast(acc, q, bound)
+    if normalizes_to_zero(acc[2]):
+        acc = xyzz_inf()
+        for q in points:
+            acc = xyzz_madd(acc, q)
+    return acc
+
+
 def xyzz_affine(acc):
     """canonical affine integers of an accumulator, None for infinity"""
     X, Y, ZZ, ZZZ = (val(c) % P for c in acc)
@@ -319,10 +388,25 @@ def check_bounds():
     xyzz_madd(acc, q, bound=True)
     d = xyzz_dbl_aff(q, bound=True)
     assert mag_ok(d[0], 5) and mag_ok(d[1], 3) and mag_ok(d[2], 1) and mag_ok(d[3], 1)
+    for ma, mb, mc, md in MUL_ADD2_WORST:
+        assert ma * mb + mc * md == 7
+        mul_add2(mag_limbs(ma), mag_limbs(mb), mag_limbs(mc), mag_limbs(md), bound=True)
+        mul_add2(mag_limbs(ma), mag_limbs(mb), mag_limbs(mc), mag_limbs(md))
+    xyzz_madd_fast(acc, q, bound=True)
+    xyzz_from_two(q, q, bound=True)
+
+
+MUL_ADD2_WORST = [(1, 1, 1, 6), (1, 3, 4, 1), (1, 1, 3, 2), (2, 2, 1, 3), (1, 6, 1, 1), (7, 1, 0, 0), (1, 4, 3, 1), (5, 1, 1, 2)]
 
 
 def forbidden_pairs_trip():
     """mul(1, 8) and mul(2, 4) reach 2^64 in column 7: the overflow assertion must fire"""
+    try:
+        mul_add2(mag_limbs(1), mag_limbs(4), mag_limbs(4), mag_limbs(1))
+    except Overflow:
+        pass
+    else:
+        raise AssertionError("mul_add2 at 1 * 4 + 4 * 1 did not trip the overflow assertion")
     for ma, mb in [(1, 8), (2, 4)]:
         a, b = mag_limbs(ma), mag_limbs(mb)
         if mb == 8:
@@ -377,6 +461,36 @@ def main():
             acc = xyzz_madd(acc, q)
             ref = ec_add(ref, pt)
             assert xyzz_affine(acc) == ref
+    # mul_add2 by value, inside and at its contract
+    for it in range(3000):
+        ma, mb, mc, md = rnd.choice(MUL_ADD2_WORST + [(1, 1, 4, 1), (1, 1, 3, 1), (1, 1, 1, 1)])
+        a, b, c, d = rand_mag(rnd, ma), rand_mag(rnd, mb), rand_mag(rnd, mc), rand_mag(rnd, md)
+        if it % 5 == 0:
+            a, b, c, d = mag_limbs(ma), mag_limbs(mb), mag_limbs(mc), mag_limbs(md)
+        assert val(mul_add2(a, b, c, d)) % P == (val(a) * val(b) + val(c) * val(d)) % P
+    # the fast item against integers: ordinary items limb for limb the group element of the complete chain, exceptions at every position redone
+    for it in range(60):
+        pts = [rand_point(rnd) for _ in range(6)]
+        m = lambda pt: (pt[0], P - pt[1])
+        chain = [[pts[0]], pts[:2], pts[:3], pts, [pts[0], pts[0]], [pts[0], m(pts[0])], [pts[0], pts[1], pts[1]], [pts[0], pts[1], m(pts[1]), pts[2]],
+                 [pts[0], m(pts[0]), pts[1], pts[2]], pts[:5] + [pts[4]], pts[:5] + [m(pts[4])], [None, pts[0], None, pts[1], pts[2], None], [None, None],
+                 [pts[0], None, m(pts[0])], [pts[0], pts[0], pts[1], m(pts[1]), pts[2]]][it % 15]
+        item, ref = [], None
+        for pt in chain:
+            q = [from_int(0), from_int(0)] if pt is None else [from_int(pt[0]), from_int(pt[1])]
+            if pt is not None and rnd.random() < 0.5:
+                q[1] = neg(from_int(P - pt[1]), 1)
+            item.append(q)
+            ref = ec_add(ref, pt)
+        assert xyzz_affine(item_fast(item)) == ref and xyzz_affine(item_fast(item, two=False)) == ref
+    # a lane gone wrong (ZZ = 0 mod p after P = +-Q) keeps ZZ = 0 and every bound to the end of its item
+    p0, rest = rand_point(rnd), [rand_point(rnd) for _ in range(8)]
+    for second in (p0, (p0[0], P - p0[1])):
+        acc = xyzz_madd_fast(xyzz_from_aff([from_int(p0[0]), from_int(p0[1])]), [from_int(second[0]), from_int(second[1])])
+        for pt in rest:
+            assert normalizes_to_zero(acc[2])
+            acc = xyzz_madd_fast(acc, [from_int(pt[0]), from_int(pt[1])])
+        assert normalizes_to_zero(acc[2])
     print("fe29 model OK")
 
 

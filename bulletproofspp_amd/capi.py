@@ -276,6 +276,7 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_fq29_op.argtypes = [vp, i, vp, vp, sz, vp, vp]
     lib.bppp_test_madd29_chain.argtypes = [vp, vp, vp, sz, sz, vp, vp]
     lib.bppp_test_madd26_chain.argtypes = [vp, vp, vp, sz, sz, vp, vp]
+    lib.bppp_test_ec29_fast_op.argtypes = [vp, i, vp, sz, vp]
     lib.bppp_test_last_msm_layout.argtypes = [vp, C.POINTER(TestMsmLayout)]
     lib.bppp_test_last_msm_copy.argtypes = [vp, i, vp, sz]
     lib.bppp_test_last_windows.argtypes = [vp, C.POINTER(C.c_int)]
@@ -328,7 +329,7 @@ class TestReduceReport(C.Structure):
 class TestMsmLayout(C.Structure):
     """bppp_test_msm_layout (include/bppp_test.h): the plan of the last general-pipeline MSM on a context"""
     __test__ = False
-    _fields_ = [(n, C.c_int32) for n in ("c", "W", "acnt", "top", "M", "flat", "CH", "Q", "one_read", "sized", "fq29", "L", "shared_points", "reserved")] + \
+    _fields_ = [(n, C.c_int32) for n in ("c", "W", "acnt", "top", "M", "flat", "CH", "Q", "one_read", "sized", "fq29", "L", "shared_points", "acc_fast")] + \
                [(n, C.c_uint32) for n in ("stride", "per")] + [(n, C.c_uint64) for n in ("batch", "n", "FB", "G", "total", "table_stride")]
 
 

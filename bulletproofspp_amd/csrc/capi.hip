@@ -61,6 +61,7 @@ void MsmTune::from_env() {
   scatter_one_read = env_switch("BPPP_SCATTER_ONE_READ", scatter_one_read);   // 0: k_scatter_ranges whatever the chunk length; else k_scatter_one_read where the plan allows it (the default)
   acc_sized = env_switch("BPPP_ACC_SIZED", acc_sized);                         // 1 / 0: k_acc_points_sized for every / no MSM over arbitrary points; unset: plan_accumulate's default
   acc_fq29 = env_switch("BPPP_ACC_FQ29", acc_fq29);                            // 1 / 0: k_acc_points_sized29 (9 x 29-bit limbs) for every / no sized accumulation
+  acc_fast = env_switch("BPPP_ACC_FAST", acc_fast);                            // 1 / 0: k_acc_points_sized29_fast / k_acc_points_sized29 for every fq29 accumulation
 }
 namespace bppp {
 int ctx_aux(bppp_ctx *ctx) {

@@ -11,6 +11,7 @@
 //   mul(a, b)   mag(a) * mag(b) <= 7, tight out.  Column 7 has 8 full products: 8 * 7 * 2^58 = 0.875 * 2^64; the rest covers the carry-in
 //               (< 2^36), the two fold terms (< 2^45) and the slack.  mag 1 * 8 and 2 * 4 reach 2^64: forbidden.
 //   sqr(a)      mag(a) <= 2 (the doubled limbs make column 7 8 * m^2 * 2^58), tight out.
+//   mul_add2(a, b, c, d) = a b + c d under one fold and one tail: mag(a) * mag(b) + mag(c) * mag(d) <= 7, tight out (column 7: 16 products).
 //   add         adds magnitudes;  sub<K>(a, b): mag(b) <= K, result mag(a) + K + 1;  neg<K>: K + 1;  mul_int(a, k): k * mag(a).
 //   weak_pass   any magnitude <= 7 in, tight out, value < 2^256 + 2^236.
 // Only the sized accumulation uses this type: points come in as canonical 8 x 32 words and sums leave as fq26 limbs (fq29_to_fq26).
@@ -70,6 +71,37 @@ BPPP_DI fq29 fq29_mul(const fq29 &a, const fq29 &b) {
     r.n[k] = (uint32_t)c & FQ29_M29; c >>= 29;
   }
   fq29_mul_tail(r, c, t8, u8, u[7]);
+  return r;
+}
+
+// a b + c d under one reduction: both products' terms go into each column of the same two chains, so the pair pays one fold and one tail
+// (19 products and 17 carry cuts less than two multiplications).  mag(a) * mag(b) + mag(c) * mag(d) <= 7, tight out: column 7 holds 16
+// products that together stay below what mul's 8 reach at 1 * 7 (fe29_model.py, mul_add2).
+BPPP_DI fq29 fq29_mul_add2(const fq29 &a, const fq29 &b, const fq29 &c, const fq29 &e) {
+  const uint32_t R0 = fq_sreg(FQ29_R0), R1 = fq_sreg(FQ29_R1);
+  uint64_t d = 0;
+#pragma unroll
+  for (int i = 0; i <= 8; i++) { d = fq_madc(a.n[i], b.n[8 - i], d); d = fq_madc(c.n[i], e.n[8 - i], d); }
+  const uint32_t t8 = (uint32_t)d & FQ29_M29; d >>= 29;
+  uint32_t u[8];
+#pragma unroll
+  for (int k = 9; k <= 16; k++) {
+#pragma unroll
+    for (int i = k - 8; i <= 8; i++) { d = fq_madc(a.n[i], b.n[k - i], d); d = fq_madc(c.n[i], e.n[k - i], d); }
+    u[k - 9] = (uint32_t)d & FQ29_M29; d >>= 29;
+  }
+  const uint64_t u8 = d;                           // leftover carry, < 2^36
+  fq29 r;
+  uint64_t s = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+#pragma unroll
+    for (int i = 0; i <= k; i++) { s = fq_madc(a.n[i], b.n[k - i], s); s = fq_madc(c.n[i], e.n[k - i], s); }
+    s = fq_madc(u[k], R0, s);
+    if (k) s = fq_madc(u[k - 1], R1, s);
+    r.n[k] = (uint32_t)s & FQ29_M29; s >>= 29;
+  }
+  fq29_mul_tail(r, s, t8, u8, u[7]);
   return r;
 }
 

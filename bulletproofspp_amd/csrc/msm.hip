@@ -23,6 +23,8 @@
 //                    of size so that the lanes of a wavefront run equally long: no boundary logic in the loop, no
 //                    partial sums unless the scalars are skewed.  k_acc_points_sized29 (MsmTune::acc_fq29, the default) is the same
 //                    kernel with the accumulator in 9 x 29-bit limbs (fq29.hip.h): 81 partial products per multiplication, not 100.
+//                    k_acc_points_sized29_fast (MsmTune::acc_fast, the default) is that kernel on an addition that tests nothing, with one
+//                    zero test of ZZ per item and the redo of a flagged item by the complete loop.
 //   4. k_reduce_marg / k_reduce_tail_quad
 //                    sum_m m*B_m per window by MARGINAL SUMS (m = LO*hi + lo: plain row and column sums, every lane busy,
 //                    then two short weighted sums); k_reduce1/2 (per-lane running sums + wavefront suffix scans) for windows
@@ -667,6 +669,61 @@ __global__ void __launch_bounds__(256) k_acc_points_sized29(const uint32_t *__re
   acc_points_sized<AccFq29>(sorted, start, count, items, ctr, piece_base, points, buckets, pieces);
 }
 
+// k_acc_points_sized29 without the exception tests of the mixed addition (MsmTune::acc_fast; DESIGN.md 0.2, "exception-free mixed addition").
+// An item starts as affine + affine (xyzz29_from_two) and goes on with xyzz29_madd_fast; neither tests anything; P = Q or P = -Q against the running sum leaves ZZ = 0 (mod p) to the end of
+// the item (ec29.hip.h), so one zero test of ZZ per item finds every such item, and its lane redoes it from the first entry with the complete
+// loop, after the fast one.  Input points at infinity (0, 0) are skipped before they reach the formula; the sum starts from the first finite
+// entry, and an item with no finite entry stores infinity.
+BPPP_DI void acc_item_complete29(const uint32_t *__restrict__ ent, uint32_t len, const uint32_t *__restrict__ points, uint32_t *__restrict__ dst) {
+  uint32_t e = ent[0];
+  xyzz29 acc = xyzz29_from_aff(aff29_cneg(aff29_load(points + (size_t)(e & 0x7FFFFFFFu) * 16), (e >> 31) & 1u));
+  for (uint32_t k = 1; k < len; k++) {
+    e = ent[k];
+    xyzz29_madd(acc, aff29_cneg(aff29_load(points + (size_t)(e & 0x7FFFFFFFu) * 16), (e >> 31) & 1u));
+  }
+  xyzz_store(dst, xyzz29_to_xyzz(acc));
+}
+// the next finite point of ent[k .. len) with its sign folded in, k left behind it; false when there is none
+BPPP_DI bool acc_next_finite(const uint32_t *__restrict__ ent, uint32_t &k, uint32_t len, const uint32_t *__restrict__ points, aff29 &P) {
+  bool finite = false;
+  while (k < len && !finite) {
+    const uint32_t e = ent[k++];
+    P = aff29_load_finite(points + (size_t)(e & 0x7FFFFFFFu) * 16, (e >> 31) & 1u, finite);
+  }
+  return finite;
+}
+// The redo is inline, after the fast loop, and not a __noinline__ function: as a callee its 184 VGPRs became the kernel's and left two
+// wavefronts per SIMD.  The fast loop itself does not carry the complete addition (no spill; profiles/r15_acc_fast_isa_histogram.txt); the
+// attribute keeps four wavefronts per SIMD as in k_acc_points_sized29, where the compiler left to itself takes over 128 VGPRs and three.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
+k_acc_points_sized29_fast(const uint32_t *__restrict__ sorted, const uint32_t *__restrict__ start, const uint32_t *__restrict__ count,
+                          const uint2 *__restrict__ items, const uint32_t *__restrict__ ctr, const uint32_t *__restrict__ piece_base,
+                          const uint32_t *__restrict__ points, uint32_t *__restrict__ buckets, uint32_t *__restrict__ pieces) {
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= ctr[3]) return;
+  const uint2 it = items[g];
+  const uint32_t fb = it.x, cnt = count[fb], first = it.y * ACC_CAP, len = min(ACC_CAP, cnt - first);
+  const uint32_t *ent = sorted + start[fb] + first;
+  uint32_t *dst = cnt > ACC_CAP ? pieces + ((size_t)piece_base[fb] + it.y) * XYZZ_WORDS : buckets + (size_t)fb * XYZZ_WORDS;
+  uint32_t k = 0;
+  aff29 P;
+  if (!acc_next_finite(ent, k, len, points, P)) { xyzz_store(dst, xyzz29_to_xyzz(xyzz29_inf())); return; }
+  xyzz29 acc;
+  acc.X = P.x; acc.Y = P.y; acc.ZZ = fq29_zero(); acc.ZZ.n[0] = 1u; acc.ZZZ = acc.ZZ;
+  aff29 P1;
+  if (acc_next_finite(ent, k, len, points, P1)) acc = xyzz29_from_two(P, P1);      // two or more finite entries: affine + affine, 4 M + 2 S
+  uint32_t e = k < len ? ent[k] : 0u;
+  for (; k < len; k++) {
+    const uint32_t e_next = (k + 1 < len) ? ent[k + 1] : 0u;
+    bool finite;
+    P = aff29_load_finite(points + (size_t)(e & 0x7FFFFFFFu) * 16, (e >> 31) & 1u, finite);
+    if (finite) xyzz29_madd_fast(acc, P);
+    e = e_next;
+  }
+  if (fq29_normalizes_to_zero(acc.ZZ)) { acc_item_complete29(ent, len, points, dst); return; }
+  xyzz_store(dst, xyzz29_to_xyzz(acc));
+}
+
 // ------------------------------------------------------------------------------------------------
 // 4. bucket reduction: per window  sum_{m=1..M} m * B_m
 // One wavefront handles 64*Lw consecutive buckets: lane l takes buckets [ (wave*64+l)*Lw, +Lw ).
@@ -1131,7 +1188,7 @@ static int msm_accumulate(bppp_ctx *ctx, const MsmPlan &p, const MsmWorkspace &w
                                                   ws.heavy_count);
   int rc = run_pre_acc(ctx); if (rc) return rc;
   if (p.sized) {
-    (p.fq29 ? k_acc_points_sized29 : k_acc_points_sized)<<<dim3((unsigned)((ws.items_max + 255) / 256)), dim3(256), 0, st>>>(
+    (p.acc_fast ? k_acc_points_sized29_fast : p.fq29 ? k_acc_points_sized29 : k_acc_points_sized)<<<dim3((unsigned)((ws.items_max + 255) / 256)), dim3(256), 0, st>>>(
         ws.sorted, ws.start, ws.count, items, ws.heavy_count, ws.piece_base, (const uint32_t *)d_points, ws.buckets, ws.rec_pt);
     prof_mark(ctx, 3);
     k_merge_heavy<true><<<dim3(2048), dim3(64), 0, st>>>(ws.start, ws.count, 0, ws.rec_pt, ws.piece_base, ws.buckets, heavy_items, ws.heavy_slot, heavy_buckets,

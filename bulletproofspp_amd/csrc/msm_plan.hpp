@@ -27,6 +27,7 @@ struct MsmTune {
   int scatter_one_read = 1;        // the ranged scatter reads a chunk's digits once for all ranges (k_scatter_one_read), BPPP_SCATTER_ONE_READ: 0 = k_scatter_ranges always
   int acc_sized = -1;              // whole buckets by size (k_acc_points_sized), BPPP_ACC_SIZED: 1 = every one-MSM plan, 0 = none, -1 = the plans where it measured faster (plan_accumulate)
   int acc_fq29 = 1;                // the sized accumulation on 9 x 29-bit limbs (k_acc_points_sized29), BPPP_ACC_FQ29: not 0 = every sized plan (the default, by measurement: DESIGN.md 0.2), 0 = k_acc_points_sized on 10 x 26
+  int acc_fast = 1;                // the fq29 accumulation on exception-free additions with one ZZ test per item, flagged items redone (k_acc_points_sized29_fast), BPPP_ACC_FAST: 0 = k_acc_points_sized29's complete addition in every step
   bool no_small = false;           // BPPP_MSM_NO_SMALL: the general pipeline for every length
   bool no_balance = false;         // BPPP_MSM_NO_BALANCE: uniform window widths
   size_t comb_rows_min_bytes = (size_t)4 << 30;   // BPPP_COMB_ROWS_MIN_MB (csrc/comb.hip.h)
@@ -165,6 +166,7 @@ struct MsmPlan {
   bool one_read;               // ranged scatter from (window, chunk) workgroups that read their digits once (k_scatter_one_read)
   bool sized;                  // accumulate whole buckets in order of size (k_order, k_acc_points_sized) instead of slices of L entries
   bool fq29;                   // sized, with the accumulator in 9 x 29-bit limbs (k_acc_points_sized29)
+  bool acc_fast;               // fq29, with the exception-free additions and one test per item (k_acc_points_sized29_fast)
 };
 
 // windows: n, batch, c, flat, W, acnt, top, M, Wc and the counts that follow from them
@@ -299,6 +301,7 @@ inline void plan_accumulate(MsmPlan &p, const MsmTune &tune) {
   p.sized = batch == 1 && !p.flat && (tune.acc_sized > 0 || (tune.acc_sized < 0 && p.c == 16));
   // on 9 x 29-bit limbs by default ("9 x 29-bit limbs"): accumulation 1.010 -> 0.892 ms at 2^20 terms, 8 interleaved pairs
   p.fq29 = p.sized && tune.acc_fq29 != 0;
+  p.acc_fast = p.fq29 && tune.acc_fast != 0;
 }
 
 inline MsmPlan make_plan(size_t n, size_t batch, int c, bool flat, const MsmTune &tune) {

@@ -200,6 +200,26 @@ __global__ void __launch_bounds__(64) k_test_madd29_chain(const uint32_t *pts, c
   xyzz_store(raw + (size_t)i * XYZZ_WORDS, s);
   aff_store(out + (size_t)i * 16, xyzz_to_aff(s));
 }
+// fq29_mul_add2, xyzz29_madd_fast and xyzz29_from_two on raw limbs.  op 0: mul_add2 of 4 elements, 1: madd_fast of X Y ZZ ZZZ x y, 2: from_two of
+// x1 y1 x2 y2; raw: 36 words per element,
+// the result's limbs (op 0: the first 9)
+__global__ void __launch_bounds__(64) k_test_ec29_fast(int op, const uint32_t *in, uint32_t n, uint32_t *raw) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t *p = in + (size_t)i * (op == 1 ? 54 : 36);
+  uint32_t *o = raw + (size_t)i * 36;
+  xyzz29 r = xyzz29_inf();
+  if (op == 0) r.X = fq29_mul_add2(fq29_load9(p), fq29_load9(p + 9), fq29_load9(p + 18), fq29_load9(p + 27));
+  else if (op == 1) {
+    r.X = fq29_load9(p); r.Y = fq29_load9(p + 9); r.ZZ = fq29_load9(p + 18); r.ZZZ = fq29_load9(p + 27);
+    aff29 q; q.x = fq29_load9(p + 36); q.y = fq29_load9(p + 45);
+    xyzz29_madd_fast(r, q);
+  } else {
+    aff29 a, b; a.x = fq29_load9(p); a.y = fq29_load9(p + 9); b.x = fq29_load9(p + 18); b.y = fq29_load9(p + 27);
+    r = xyzz29_from_two(a, b);
+  }
+  fq29_store9(o, r.X); fq29_store9(o + 9, r.Y); fq29_store9(o + 18, r.ZZ); fq29_store9(o + 27, r.ZZZ);
+}
 // the same walk over 10 x 26-bit limbs, as k_acc_points_sized walks an item (and, from the second entry on, k_acc_points a run): xyzz_from_aff,
 // aff_cneg, xyzz_madd
 __global__ void __launch_bounds__(64) k_test_madd26_chain(const uint32_t *pts, const uint32_t *flags, uint32_t k, uint32_t n, uint32_t *out, uint32_t *raw) {
@@ -399,6 +419,21 @@ extern "C" int bppp_test_fq29_op(bppp_ctx *ctx, int op, const uint32_t *a, const
   hipFree(d);
   return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_fq29_op: kernel or copy failed");
 }
+extern "C" int bppp_test_ec29_fast_op(bppp_ctx *ctx, int op, const uint32_t *in, size_t n, uint32_t *raw) {
+  if (!ctx || !in || !raw || op < 0 || op > 2 || n >= (1u << 24)) return BPPP_ERR_ARG;
+  if (n == 0) return BPPP_OK;
+  hipSetDevice(ctx->device);
+  const size_t win = n * (op == 1 ? 54 : 36), wout = n * 36;
+  uint32_t *d = nullptr;                       // in | raw
+  if (hipMalloc(&d, (win + wout) * 4) != hipSuccess) return bppp::fail(ctx, BPPP_ERR_HIP, "test_ec29_fast_op: hipMalloc");
+  hipStream_t st = ctx->stream;
+  bool ok = hipMemcpyAsync(d, in, win * 4, hipMemcpyHostToDevice, st) == hipSuccess;
+  if (ok) k_test_ec29_fast<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st>>>(op, d, (uint32_t)n, d + win);
+  ok = ok && hipMemcpyAsync(raw, d + win, wout * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+  if (hipStreamSynchronize(st) != hipSuccess) ok = false;
+  hipFree(d);
+  return ok ? BPPP_OK : bppp::fail(ctx, BPPP_ERR_HIP, "test_ec29_fast_op: kernel or copy failed");
+}
 static int madd_chain(bppp_ctx *ctx, bool fq29, const uint64_t *points, const uint32_t *flags, size_t k, size_t n, uint64_t *out, uint32_t *raw) {
   if (!ctx || !points || !flags || !out || !raw || !k || k >= (1u << 16) || n >= (1u << 16)) return BPPP_ERR_ARG;
   if (n == 0) return BPPP_OK;
@@ -439,7 +474,7 @@ extern "C" int bppp_test_last_msm_layout(bppp_ctx *ctx, bppp_test_msm_layout *r)
   if (!last_msm_total(ctx, ws, p.FB, &total)) return bppp::fail(ctx, BPPP_ERR_HIP, "test_last_msm_layout: copy failed");
   memset(r, 0, sizeof *r);
   r->c = p.c; r->W = p.W; r->acnt = p.acnt; r->top = p.top; r->M = p.M; r->flat = p.flat ? 1 : 0; r->CH = p.CH; r->Q = p.Q; r->one_read = p.one_read ? 1 : 0;
-  r->sized = p.sized ? 1 : 0; r->fq29 = p.fq29 ? 1 : 0; r->L = p.L; r->shared_points = ctx->last_msm_shared_points;
+  r->sized = p.sized ? 1 : 0; r->fq29 = p.fq29 ? 1 : 0; r->acc_fast = p.acc_fast ? 1 : 0; r->L = p.L; r->shared_points = ctx->last_msm_shared_points;
   r->stride = ws.stride;
   r->per = ((((uint32_t)n + p.CH - 1) / p.CH) + 7u) & ~7u;      // the chunk length of k_hist and the three scatters
   r->batch = batch; r->n = n; r->FB = p.FB; r->G = p.G; r->total = total; r->table_stride = ctx->last_msm_table_stride;

@@ -66,6 +66,11 @@ int bppp_test_fq29_op(bppp_ctx *ctx, int op, const uint32_t *a, const uint32_t *
  * the accumulator, the others are added with xyzz29_madd.  points: n x k x 8 uint64 affine ((0, 0) = infinity), flags: n x k uint32, not 0
  * negates the point first.  out: n x 8 uint64 canonical affine sums; raw: n x 40 uint32, the sums as the kernel stores them. */
 int bppp_test_madd29_chain(bppp_ctx *ctx, const uint64_t *points, const uint32_t *flags, size_t k, size_t n, uint64_t *out, uint32_t *raw);
+/* fq29_mul_add2 (csrc/fq29.hip.h), xyzz29_madd_fast and xyzz29_from_two (csrc/ec29.hip.h), the routines of k_acc_points_sized29_fast, on caller-built RAW limbs
+ * (uint32, 9 per field element, within each routine's magnitudes).  op 0: fq29_mul_add2(a, b, c, d), in: n x 4 elements, raw: n x 36 with the
+ * result in the first 9 words;  op 1: xyzz29_madd_fast(acc, q), in: n x 6 elements X Y ZZ ZZZ x y, raw: n x 36, the limbs of X Y ZZ ZZZ;
+ * op 2: xyzz29_from_two((x1, y1), (x2, y2)), in: n x 4 elements, raw as op 1. */
+int bppp_test_ec29_fast_op(bppp_ctx *ctx, int op, const uint32_t *in, size_t n, uint32_t *raw);
 /* The same chains over 10 x 26-bit limbs (csrc/ec.hip.h: xyzz_from_aff, aff_cneg, xyzz_madd), as k_acc_points_sized walks an item and k_acc_points a
  * run; arguments and outputs as bppp_test_madd29_chain (raw: the accumulator as stored, lazily reduced). */
 int bppp_test_madd26_chain(bppp_ctx *ctx, const uint64_t *points, const uint32_t *flags, size_t k, size_t n, uint64_t *out, uint32_t *raw);
@@ -74,7 +79,7 @@ int bppp_test_madd26_chain(bppp_ctx *ctx, const uint64_t *points, const uint32_t
  * context.  BPPP_ERR_ARG when no such MSM has run (or the small route ran since).
  * _layout: the plan (csrc/msm_plan.hpp) — c, W digit rows per scalar of which the first acnt are c bits wide, top (the row stored negated, -1 none),
  * M buckets per window, flat (a registered basis: one bucket set per instance), CH chunks per digit row and their length per as k_hist and the
- * scatters compute it, Q bucket ranges (0: k_scatter), one_read (k_scatter_one_read), sized / fq29 (the accumulation's form), L entries per lane and G
+ * scatters compute it, Q bucket ranges (0: k_scatter), one_read (k_scatter_one_read), sized / fq29 / acc_fast (the accumulation's form; acc_fast: k_acc_points_sized29_fast), L entries per lane and G
  * lanes of k_acc_points, shared_points as the call gave it; stride: uint16 per digit row; FB buckets in all; total = start[FB], the sorted entries;
  * table_stride: the rows' distance in a registered basis' table (0 otherwise).
  * _copy: one array, `bytes` must be exactly its size —
@@ -83,7 +88,7 @@ int bppp_test_madd26_chain(bppp_ctx *ctx, const uint64_t *points, const uint32_t
  *   COUNT        [FB] uint32          START  [FB + 1] uint32          SORTED  [total] uint32: sign << 31 | point index
  *   BUCKETS_RAW  [FB][40] uint32, the stored XYZZ sums         BUCKETS_AFF  [FB][16] uint32: xyzz_to_aff of each, infinity as (0, 0) */
 typedef struct bppp_test_msm_layout {
-  int32_t c, W, acnt, top, M, flat, CH, Q, one_read, sized, fq29, L, shared_points, reserved;
+  int32_t c, W, acnt, top, M, flat, CH, Q, one_read, sized, fq29, L, shared_points, acc_fast;
   uint32_t stride, per;
   uint64_t batch, n, FB, G, total, table_stride;
 } bppp_test_msm_layout;
