@@ -51,6 +51,7 @@ SYMBOLS = [
     "bppp_rp_verify_block_agg", "bppp_rp_verify_block_agg_device",
     "bppp_rp_seal", "bppp_rp_seal_device", "bppp_rp_scan", "bppp_rp_scan_device",
     "bppp_rp_scan_keys", "bppp_rp_scan_keys_device",
+    "bppp_rp_cut_through", "bppp_rp_cut_through_device",
 ]
 
 
@@ -61,6 +62,11 @@ class RpBlock(C.Structure):
                 ("claim_amounts", C.c_void_p), ("claim_types", C.c_void_p), ("claim_offsets", C.c_void_p),
                 ("nkeys", C.c_size_t), ("key_start", C.c_void_p), ("keys", C.c_void_p), ("msgs", C.c_void_p), ("sigs", C.c_void_p),
                 ("proof_offset", C.c_uint64), ("key_offset", C.c_uint64), ("sum_offset", C.c_uint64)]
+
+
+class RpCutCounts(C.Structure):
+    """bppp_rp_cut_counts: what bppp_rp_cut_through left — rows of the new pool, how many of them are new outputs, surviving entries, entries cut, entries kept again"""
+    _fields_ = [(n, C.c_size_t) for n in ("new_rows", "out_rows", "new_nnz", "ncut", "nagain")]
 
 
 class RpBlockStatus(C.Structure):
@@ -244,6 +250,8 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_scan_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]
     lib.bppp_rp_scan_keys.argtypes = [vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.POINTER(sz), C.POINTER(C.c_uint64)]
     lib.bppp_rp_scan_keys_device.argtypes = [vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.POINTER(sz), C.POINTER(C.c_uint64)]
+    lib.bppp_rp_cut_through.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(RpCutCounts)]
+    lib.bppp_rp_cut_through_device.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(RpCutCounts)]
     lib.bppp_seed_candidate_x.argtypes =[C.c_char_p, sz, C.c_uint64, vp]
     lib.bppp_points_from_seed.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
     lib.bppp_points_from_seed_device.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
@@ -311,6 +319,8 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_rpp_draws.argtypes = [vp, C.c_char_p, sz, sz, sz, vp]
     lib.bppp_test_ctx_poison.argtypes = [vp, i, C.POINTER(C.c_uint64)]
     lib.bppp_test_rp_poison.argtypes = [vp, i, C.POINTER(C.c_uint64)]
+    lib.bppp_test_rp_cut_through_force.argtypes = [vp, i, vp, i]
+    lib.bppp_test_rp_cut_through_last.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 3
     return lib
 
 
@@ -395,6 +405,8 @@ RP_EXCESS_NO_AGGREGATE = 8
 # sealed outputs (bppp_rp_seal / bppp_rp_scan): a seal's verdicts next to RP_EXCESS_BAD_KEY, a scanned row's verdicts, the bytes of a seal
 RP_SEAL_OK, RP_SEAL_NOT_CANONICAL, RP_SEAL_ZERO = 0, 1, 2
 RP_SCAN_FOREIGN, RP_SCAN_OWNED, RP_SCAN_BAD_HINT, RP_SCAN_TAG_ONLY = 0, 1, 2, 3
+# BPPP_RP_CUT_*: an entry's verdict from bppp_rp_cut_through
+RP_CUT_KEPT, RP_CUT_SPENT, RP_CUT_KEPT_AGAIN = 0, 1, 2
 RP_SCAN_MAX_KEYS = 1 << 20                                     # BPPP_RP_SCAN_MAX_KEYS: view secrets of one bppp_rp_scan_keys call
 
 

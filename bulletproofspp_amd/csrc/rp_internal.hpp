@@ -198,6 +198,13 @@ struct bppp_rp {
   // the items (commitments, sums, keys) of one pass over the workspace in every balance call that is not planned by the tally's chunk: commit, open,
   // sign, keys and the two key verifiers (rpp_flat_chunk); a test hook lowers it so that a small job takes several passes
   size_t flat_chunk = (size_t)1 << 22;
+  // cut-through (csrc/rpcut.hip).  What the test hooks pin (bppp_test_rp_cut_through_force): cut_same_hash makes every routing hash equal, cut_salt_pinned
+  // takes cut_salt in place of fresh randomness, cut_table_bits (0: at least 2 nnz slots) asks for 2^bits slots, lifted to the smallest power of two that
+  // holds every entry.  And what the last call on this handle ran (bppp_test_rp_cut_through_last): table slots, groups (distinct identities), sort passes
+  bool cut_same_hash = false, cut_salt_pinned = false;
+  uint8_t cut_salt[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int cut_table_bits = 0;
+  uint64_t cut_slots = 0, cut_groups = 0, cut_passes = 0;
   // per-proof public amounts of the *_pub entry points (bppp_rp_public_count per proof): grow-only device copy of one call's canonical
   // scalars, [batch][public_count][8] words
   uint32_t *d_pub = nullptr; size_t d_pub_bytes = 0;

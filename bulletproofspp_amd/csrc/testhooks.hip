@@ -560,6 +560,19 @@ extern "C" int bppp_test_rp_set_flat_chunk(bppp_rp *rp, size_t items) {
   rp->flat_chunk = items ? items : bppp_rp().flat_chunk;
   return BPPP_OK;
 }
+extern "C" int bppp_test_rp_cut_through_force(bppp_rp *rp, int mode, const uint8_t *salt, int table_bits) {
+  if (!rp || mode < 0 || mode > 1 || table_bits < 0 || table_bits > 32) return BPPP_ERR_ARG;
+  rp->cut_same_hash = mode == 1;
+  rp->cut_salt_pinned = salt != nullptr;
+  if (salt) memcpy(rp->cut_salt, salt, 16); else memset(rp->cut_salt, 0, 16);
+  rp->cut_table_bits = table_bits;
+  return BPPP_OK;
+}
+extern "C" int bppp_test_rp_cut_through_last(bppp_rp *rp, uint64_t *slots, uint64_t *groups, uint64_t *passes) {
+  if (!rp || !slots || !groups || !passes) return BPPP_ERR_ARG;
+  *slots = rp->cut_slots; *groups = rp->cut_groups; *passes = rp->cut_passes;
+  return BPPP_OK;
+}
 
 // one quad per instance; all four lanes hold the product, lane 0 of the quad inverts and stores
 namespace bppp {

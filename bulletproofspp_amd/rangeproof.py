@@ -1620,6 +1620,71 @@ class NativeRangeProofs:
                                                                       nkeys, p(d_key_start), p(d_keys), index_offset, *a)
         return self._tally_batch(fn, nsums, seed, want_status, want_point)
 
+    # ---- cut-through: the transactions' job -> the block's pool, one sum and claim (bppp_rp_cut_through / _device)
+    def _cut_claims(self, words):
+        """block_claims [3][4] -> the claim as verify_block takes it: (amount, type, offset) mod N ((amount, offset) on a binary handle)"""
+        from .capi import array_to_scalars
+        a, ty, o = array_to_scalars(words)
+        return self._tally_claims_shape([((a - 2**256 if a >= 2**255 else a) % N, ty, o)])[0]
+
+    def _cut_call(self, fn, name, rows, pc, nsums, ps, pe, nnz, pa, pt, po, p_new_coms, p_new_entries, have_claims):
+        import ctypes as C
+        import numpy as np
+        from .capi import RpCutCounts
+        status, row_map = np.zeros(max(nnz, 1), dtype=np.uint32), np.zeros(max(rows, 1), dtype=np.uint32)
+        bc, cnt = np.zeros((3, 4), dtype=np.uint64), RpCutCounts()
+        vp = lambda a: C.c_void_p(a.ctypes.data)
+        self.gpu._check(fn(self.h, rows, pc, nsums, ps, pe, nnz, pa, pt, po, vp(status), vp(row_map), p_new_coms, p_new_entries, vp(bc) if have_claims else None,
+                           C.byref(cnt)), name)
+        counts = {n: int(getattr(cnt, n)) for n, _ in RpCutCounts._fields_}
+        empty = nsums == 0 or nnz == 0
+        return CutThrough(None, None, [int(v) for v in row_map[:counts["new_rows"]]], counts["out_rows"], [] if empty else [int(v) for v in status[:nnz]],
+                          self._cut_claims(bc) if have_claims else None, counts)
+
+    def cut_through(self, coms_files: Sequence[bytes], sum_start, entries, claims=None) -> "CutThrough":
+        """bppp_rp_cut_through: the job of T transactions (the pool, one sum per transaction, claims (amount, type, offset) per sum or None) merged
+        into a block — outputs created and spent inside the set are dropped with their spends.  Returns a CutThrough: the new pool, the one sum's
+        entries, row_map, out_rows, one capi.RP_CUT_* per entry, the summed claim and the counts (cut_through_host restates every rule)."""
+        import ctypes as C
+        import numpy as np
+        ss, en, nsums, nnz = self._tally_csr(sum_start, entries)
+        amt, typ, off = self._tally_claim_arrays(claims, nsums)
+        rows, cb = len(coms_files), self.shape["coms_bytes"]
+        cf = self._coms_array(coms_files, rows)
+        nc, ne = np.zeros(max(rows * cb, 1), dtype=np.uint8), np.zeros(max(nnz, 1), dtype=np.uint32)
+        vp = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+        r = self._cut_call(self.gpu.lib.bppp_rp_cut_through, "bppp_rp_cut_through", rows, vp(cf), nsums, vp(ss), vp(en), nnz, vp(amt), vp(typ), vp(off), vp(nc), vp(ne),
+                           claims is not None)
+        r.coms_files = [nc[k * cb:(k + 1) * cb].tobytes() for k in range(r.counts["new_rows"])]
+        r.entries = [int(v) for v in ne[:r.counts["new_nnz"]]]
+        return r
+
+    def cut_through_device(self, rows: int, d_coms: int, nsums: int, d_sum_start: int, d_entries: int, nnz: int, d_amounts: int, d_types: int, d_offsets: int,
+                           d_new_coms: int, d_new_entries: int) -> "CutThrough":
+        """bppp_rp_cut_through_device: cut_through on buffers in HBM (0 for all three claim arrays: no claims; d_new_coms may be 0).  The new pool and
+        the one sum's entries are written to d_new_coms [rows][coms_bytes] and d_new_entries [nnz]: the CutThrough returned has None for both and
+        counts["new_rows"] / counts["new_nnz"] say how much of them is filled."""
+        import ctypes as C
+        p = C.c_void_p
+        return self._cut_call(self.gpu.lib.bppp_rp_cut_through_device, "bppp_rp_cut_through_device", rows, p(d_coms), nsums, p(d_sum_start), p(d_entries), nnz,
+                              p(d_amounts), p(d_types), p(d_offsets), p(d_new_coms), p(d_new_entries), bool(d_amounts or d_offsets))
+
+    def assemble_block(self, coms_files: Sequence[bytes], sum_start, entries, claims, keys: Sequence[bytes], msgs: Sequence[bytes], sigs: Sequence[bytes],
+                       proof_files: Optional[Sequence[bytes]] = None, bindings=None):
+        """The transactions' job -> the arguments of verify_block, through one cut_through: thin host glue.  proof_files (and bindings): None, or one
+        per ROW of the old pool (None for a row without a proof, e.g. the copy of a spent output); what belongs to a row is gathered with row_map, and
+        every new output (the rows in front of the new pool) must carry a proof.  The keys, messages and signatures of all transactions stand in one
+        group.  Returns (kwargs, cut): verify_block(**kwargs) checks the block; cut is the CutThrough."""
+        cut = self.cut_through(coms_files, sum_start, entries, claims)
+        outs = cut.row_map[:cut.out_rows]
+        proofs = [] if proof_files is None else [proof_files[r] for r in outs]
+        if any(p is None for p in proofs):
+            raise ValueError("every surviving output needs its proof file")
+        binds = None if bindings is None or proof_files is None else [bindings[r] for r in outs]
+        kwargs = dict(coms_files=cut.coms_files, proof_files=proofs, sum_start=[0, len(cut.entries)], entries=cut.entries,
+                      claims=None if cut.claims is None else [cut.claims], key_start=[0, len(keys)], keys=list(keys), msgs=list(msgs), sigs=list(sigs), bindings=binds)
+        return kwargs, cut
+
     # ---- a block in one call: range proofs, key signatures and sums after cut-through as ONE MSM (bppp_rp_verify_block / _device)
     def block_arrays(self, coms_files, proof_files, sum_start, entries, claims, key_start, keys, msgs, sigs, bindings):
         """the block's arguments as [(field of capi.RpBlock, numpy array or None)] and its sizes as a dict of RpBlock's counts: what verify_block passes
@@ -2110,6 +2175,71 @@ def tally_claims_host(triples: Sequence[Tuple[int, int, int]], sum_start: Sequen
                 acc[k] += sign * triples[e & (TALLY_SUBTRACT - 1)][k]
         out.append(tuple(v % N for v in acc))
     return out
+
+
+# ----------------------------------------------------------------------------- cut-through (bppp_rp_cut_through; include/bppp.h states every rule)
+CUT_KEPT, CUT_SPENT, CUT_KEPT_AGAIN = 0, 1, 2
+
+
+@dataclass
+class CutThrough:
+    """what bppp_rp_cut_through returns: the new pool, the surviving entries re-based to it (the block's one sum), row_map[k] = the old index of new
+    row k, out_rows = how many of the new rows are new outputs (they stand in front), one CUT_* per entry of the job, the summed claim (None without
+    claims) and the counts of bppp_rp_cut_counts as a dict"""
+    coms_files: List[bytes]
+    entries: List[int]
+    row_map: List[int]
+    out_rows: int
+    entry_status: List[int]
+    claims: Optional[tuple]
+    counts: Dict[str, int]
+
+
+def cut_identity(nranges: int, coms_file: bytes, i: int) -> Tuple[int, int]:
+    """the identity of commitment i of a commitments file: (x mod p, bit i of the sign bytes) — the 33 bytes put (x mod p) || sign as a pair"""
+    o = (nranges + 7) // 8 + 32 * i
+    return decode_field(coms_file[o:o + 32], FIELD_P), (coms_file[i >> 3] >> (i & 7)) & 1
+
+
+def cut_through_host(nranges: int, coms_files: Sequence[bytes], sum_start: Sequence[int], entries: Sequence[int], claims=None) -> CutThrough:
+    """Host restatement of bppp_rp_cut_through with dictionaries and lists: no GPU, no backend, no curve.  claims: None, or one (amount, type, offset)
+    per sum ((amount, offset) for a binary handle) — amounts any integers, types and offsets below N (ValueError otherwise, the call's BPPP_ERR_ARG)."""
+    nsums, nnz, rows = len(sum_start) - 1, len(entries), len(coms_files)
+    zero = dict(new_rows=0, out_rows=0, new_nnz=0, ncut=0, nagain=0)
+    width = len(claims[0]) if claims else 3
+    if nsums <= 0 or nnz == 0:
+        return CutThrough([], [], [], 0, [], None if claims is None else (0,) * width, zero)
+    if list(sum_start) != sorted(sum_start) or sum_start[0] != 0 or sum_start[-1] != nnz:
+        raise ValueError("sum_start is not non-decreasing from 0 to nnz")
+    if any((e & (TALLY_SUBTRACT - 1)) >= rows * nranges for e in entries):
+        raise ValueError("an entry's index is not below rows * nranges")
+    block = None
+    if claims is not None:
+        if len(claims) != nsums:
+            raise ValueError("one claim per sum is required")
+        for t, c in enumerate(claims):
+            if any(not 0 <= v < N for v in c[1:]):
+                raise ValueError(f"sum {t}: a claimed type or offset is not canonical (>= n)")
+        block = tuple(sum(c[k] for c in claims) % N for k in range(width))
+    ident = [cut_identity(nranges, coms_files[(e & (TALLY_SUBTRACT - 1)) // nranges], (e & (TALLY_SUBTRACT - 1)) % nranges) for e in entries]
+    count: Dict[tuple, List[int]] = {}
+    for e, idt in zip(entries, ident):
+        count.setdefault(idt, [0, 0])[e >> 31] += 1
+    seen: Dict[tuple, List[int]] = {}
+    status = []
+    for e, idt in zip(entries, ident):
+        rank = seen.setdefault(idt, [0, 0])
+        m = min(count[idt])
+        status.append(CUT_SPENT if rank[e >> 31] < m else CUT_KEPT if rank[e >> 31] == m else CUT_KEPT_AGAIN)
+        rank[e >> 31] += 1
+    kept = [e for e, s in zip(entries, status) if s != CUT_SPENT]
+    outs = sorted({(e & (TALLY_SUBTRACT - 1)) // nranges for e in kept if not e & TALLY_SUBTRACT})
+    rest = sorted({(e & (TALLY_SUBTRACT - 1)) // nranges for e in kept} - set(outs))
+    row_map = outs + rest
+    new_of = {r: k for k, r in enumerate(row_map)}
+    new_entries = [(e & TALLY_SUBTRACT) | (new_of[(e & (TALLY_SUBTRACT - 1)) // nranges] * nranges + (e & (TALLY_SUBTRACT - 1)) % nranges) for e in kept]
+    counts = dict(new_rows=len(row_map), out_rows=len(outs), new_nnz=len(kept), ncut=status.count(CUT_SPENT), nagain=status.count(CUT_KEPT_AGAIN))
+    return CutThrough([bytes(coms_files[r]) for r in row_map], new_entries, row_map, len(outs), status, block, counts)
 
 
 # ----------------------------------------------------------------------------- excess signatures (bppp_rp_excess_*; include/bppp.h states every message)

@@ -1279,6 +1279,72 @@ int bppp_rp_scan_keys_device(bppp_rp *rp, size_t nkeys, const uint64_t *view_sec
                              void *d_amounts, void *d_types, void *d_blinds /* HBM, each may be NULL; [cap][nranges][4] words */, size_t *nhits /* host, required */,
                              uint64_t *ntag_only /* host, may be NULL */);
 
+/* ---- cut-through: the transactions of a block merged into its one sum -----------------------------------------------------------------------------
+ * The block calls above (bppp_rp_excess_sums_*, bppp_rp_verify_block*, bppp_rp_excess_halfagg*) take a block "after cut-through".  This is the step:
+ * a miner, a mempool or an aggregator holds T transactions as they arrived, and an output that one of them creates and another spends need not reach
+ * the chain.  bppp_rp_cut_through turns the job of the T transactions into the pool, the one sum and the claim of the block.
+ *
+ * INPUT: the tally's job exactly as bppp_rp_excess_sums_each takes it, one sum per transaction — POOL (rows, coms_files [rows][coms_bytes]), SUMS
+ * (nsums, sum_start [nsums + 1], entries [nnz] with bit 31 = subtracted = an input, nnz) and the claims claim_amounts, claim_types, claim_offsets
+ * [nsums][4] (all three may be NULL; a binary handle's types do not count).  Keys, messages, signatures, proofs, bindings and seals are not inputs: a
+ * block's keys are the transactions' keys, concatenated, in one group (key_start = {0, nkeys}), and whatever belongs to a row is gathered by the caller
+ * with row_map.
+ *
+ * IDENTITY.  Entry e references the commitment with flat index j = r * nranges + i.  The identity of that commitment is 33 bytes: put (x mod p) of
+ * commitment i of row r, and bit i of the row's sign bytes.  Two entries reference the same commitment iff these 33 bytes are equal.  So a
+ * non-canonical x matches its reduction (x and x + p); unused bits of the sign bytes take no part; two different rows of equal content match (the
+ * normal case: transaction 2 brings its own copy of the output it spends); and one flat index used with both signs matches itself.  No square root is
+ * taken and nothing is judged for lying on the curve: what survives is judged by the block calls, and what is cut adds and subtracts the same term.
+ *
+ * WHAT IS CUT.  For every identity let P be its added entries and M its subtracted entries, both in job order (position in `entries`), and
+ * m = min (|P|, |M|).  The first m of P and the first m of M are cut; every other entry survives.  This is a multiset rule over the whole job: an
+ * output added and subtracted inside one transaction is cut, and the order of the transactions does not matter to the sum — whether a spend may
+ * come before its output is the caller's rule.
+ *
+ * OUTPUTS.
+ *   entry_status [nnz] (host, may be NULL)  BPPP_RP_CUT_KEPT (0); BPPP_RP_CUT_SPENT (1): the entry is cut; BPPP_RP_CUT_KEPT_AGAIN (2): it survives and
+ *                an EARLIER surviving entry has the same identity — necessarily with the same sign, so 2 marks a duplicate output or a double spend
+ *                inside the set.  Both are reported, never refused: the caller's rule, as for duplicate keys above.
+ *   row_map [rows] (host, may be NULL)  row_map[k] is the old index of new row k.  A row survives iff a surviving entry references one of its
+ *                commitments.  The surviving rows come in two groups, each in ascending old index: first the rows referenced by at least one surviving
+ *                ADDED entry — the block's new outputs, the rows [0, nproofs) that bppp_rp_verify_block wants in front —, then the other survivors.
+ *   new_coms_files [rows][coms_bytes] (may be NULL; HBM in the _device variant)  the surviving rows, copied byte for byte: the first new_rows rows
+ *                are written.  A row of several ranges that is only partly spent stays whole: its proof still speaks for the rest.
+ *   new_entries [nnz] (required; HBM in the _device variant)  the surviving entries in job order, in the first new_nnz slots: the sign kept, the
+ *                index re-based to the new pool.  The block's sum_start is {0, new_nnz}.
+ *   block_claims [3][4] (host; NULL iff the three claim arrays are NULL)  the sums mod n of the amounts, the types and the offsets, in this order
+ *                (zeros for the types of a binary handle).  The amount is written as bppp_rp_tally_claims writes it: a below 2^255, else a - n in
+ *                two's complement.  A type or an offset >= n is BPPP_ERR_ARG naming the lowest such sum.
+ *   counts (host, required)  new_rows, out_rows (the first group), new_nnz, ncut (entries cut, twice the pairs), nagain (entries with status 2).
+ * The call is deterministic: the same job gives the same bytes in every output, on every run.
+ *
+ * HOW.  The job is matched in ONE pass — matching is global and cannot be chunked as the tally chunks its sums.  Entries meet through a hash table of
+ * at least 2 nnz 32-bit slots.  The hash only routes: whether two identities are equal is decided by comparing all 33 bytes.  The hash (SipHash-2-4) is
+ * keyed with 16 fresh random bytes per call, so the author of a block cannot steer entries into one chain, and no output depends on the key.  Entries
+ * of one identity cost one comparison each, however many they are.  Job order within an identity comes from a stable counting sort of the positions,
+ * not from the order in which lanes arrive.  The workspace is the handle's, O (nnz + rows): at most 112 bytes an entry and 28 bytes a row.
+ *
+ * Errors and empties are the tally's: the BPPP_ERR_ARG cases and texts of bppp_rp_tally_each under the name rp_cut_through (NULL buffers with a
+ * non-empty job — new_entries and counts are required, block_claims must be given exactly when the claims are; rows * nranges, nnz or nsums >= 2^31;
+ * "sum_start[i] = ..."; "entries[i]: index ..."; only some of the claim arrays NULL).  The CSR arrays are validated by a kernel whose verdict is read
+ * back before anything reads through them, and no output is written on an error.  nsums == 0 or nnz == 0 is BPPP_OK with all counts zero (and a
+ * zeroed block_claims where one is given); nothing else is looked at.  Workspace that cannot be allocated is BPPP_ERR_HIP.  The host variant uploads,
+ * calls the _device variant and downloads; d_* buffers are in HBM, 16-byte aligned. */
+#define BPPP_RP_CUT_KEPT 0u
+#define BPPP_RP_CUT_SPENT 1u
+#define BPPP_RP_CUT_KEPT_AGAIN 2u
+typedef struct bppp_rp_cut_counts {
+  size_t new_rows, out_rows, new_nnz, ncut, nagain;
+} bppp_rp_cut_counts;
+int bppp_rp_cut_through(bppp_rp *rp, size_t rows, const uint8_t *coms_files, size_t nsums, const uint32_t *sum_start, const uint32_t *entries, size_t nnz,
+                        const uint64_t *claim_amounts, const uint64_t *claim_types, const uint64_t *claim_offsets, uint32_t *entry_status /* may be NULL */,
+                        uint32_t *row_map /* may be NULL */, uint8_t *new_coms_files /* may be NULL */, uint32_t *new_entries, uint64_t *block_claims,
+                        bppp_rp_cut_counts *counts);
+int bppp_rp_cut_through_device(bppp_rp *rp, size_t rows, const void *d_coms_files, size_t nsums, const void *d_sum_start, const void *d_entries, size_t nnz,
+                               const void *d_claim_amounts, const void *d_claim_types, const void *d_claim_offsets, uint32_t *entry_status /* host, [nnz], may be NULL */,
+                               uint32_t *row_map /* host, [rows], may be NULL */, void *d_new_coms_files /* HBM, may be NULL */, void *d_new_entries /* HBM, [nnz] */,
+                               uint64_t *block_claims /* host, [3][4] */, bppp_rp_cut_counts *counts /* host, required */);
+
 /* ---- one comb table for the handles of a basis family --------------------------------------------------------------------------
  * Every setup's basis [g | H | G] is a prefix of the point stream its points came from (see bppp_rp_verify_mixed), and the comb table
  * is laid out tab[window][point][multiple]: the table of the longest basis of a stream contains the table of every shorter one (same

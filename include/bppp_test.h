@@ -124,6 +124,15 @@ int bppp_test_rp_set_tally_chunk(bppp_rp *rp, size_t entries);
  * bppp_rp_excess_verify_keys_*  max (1, items / 4)  keys, bppp_rp_excess_part_*  max (1, items / 4)  sessions or parts (whole groups: a group longer
  * than that is an error).  A test takes several passes with a handful of items. */
 int bppp_test_rp_set_flat_chunk(bppp_rp *rp, size_t items);
+/* Cut-through on this handle (bppp_rp_cut_through*, csrc/rpcut.hip).  _force pins what a call otherwise draws or sizes itself, until it is called
+ * again: mode 0 = the keyed hash, 1 = every routing hash equal, so every entry probes ONE chain of the table and every comparison of two different
+ * identities is made; salt NULL = 16 fresh random bytes per call (the product's behaviour), else these 16 bytes are the key; table_bits 0 = at least
+ * 2 nnz slots, else 2^table_bits slots, lifted to the smallest legal table (the power of two that holds nnz entries) where that is larger — 1 asks for
+ * that smallest table.  (0, NULL, 0) restores the product's behaviour.  No output of the call may depend on any of the three.
+ * _last reports what the last successful non-empty call on the handle ran: the table's slots, the groups (distinct identities among the entries)
+ * and the passes of the counting sort (8 bits of 2 * groups - 1 each). */
+int bppp_test_rp_cut_through_force(bppp_rp *rp, int mode, const uint8_t *salt /* NULL or [16] */, int table_bits);
+int bppp_test_rp_cut_through_last(bppp_rp *rp, uint64_t *slots, uint64_t *groups, uint64_t *passes);
 /* The quad walk of k_rp_excess_mulcheck alone (csrc/rpexcess.hip.h): out_i = c_i X_i in affine form, infinity as all zeros, for n instances
  * of four lanes each.  d_scalars [n][4] words (walked as the 256-bit integers they are, reduced or not), d_points_xy and d_out_xy [n][8]
  * words, all in HBM.  The real entry points derive the challenge from a hash; here a test chooses it. */
@@ -241,7 +250,7 @@ int bppp_test_rpp_draws(bppp_ctx *ctx, const uint8_t *prefixes, size_t prefix_le
  *   pre_acc, pre_acc_arg     not buffers: the one-shot upload hook of bppp_msm and its argument, set and cleared within one call (csrc/msm.hip)
  * _rp_ (members of bppp_rp, csrc/rp_internal.hpp); with a twin handle (a split prove batch), the twin's buffers and the twin's own context as well, but
  * NOT the handle's own context: the caller poisons both:
- *   pwork        scratch     the provers' and the commit / open / tally / excess calls' workspace (csrc/rpprove.hip, rpprove_dev.hip, brpprove*.hip, rpcommit.hip, rptally.hip, rpexcess.hip, rpexkeys.hip, rpexpart.hip, rpexagg.hip: the half-aggregate's leaves and tree levels in front of a pass)
+ *   pwork        scratch     the provers' and the commit / open / tally / excess calls' workspace (csrc/rpprove.hip, rpprove_dev.hip, brpprove*.hip, rpcommit.hip, rptally.hip, rpexcess.hip, rpexkeys.hip, rpexpart.hip, rpexagg.hip: the half-aggregate's leaves and tree levels in front of a pass; rpcut.hip: cut-through's identities, table and sort)
  *   awork        scratch     the device-resident inner-product argument's workspace and final witness (csrc/rpprove_dev.hip hands it to ipb_prove_stream, csrc/ipb.hip)
  *   hpin         scratch     pinned staging of the batch provers (csrc/rpprove.hip, brpprove.hip)
  *   work         scratch     the verifier's per-proof arrays of one prepared batch (csrc/rp.hip: rp_verify_prepare)
