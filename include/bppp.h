@@ -15,7 +15,11 @@
  *                magnitude (< 2^130; rationalReducedScalarLength = 129, Commitment.hs:286)
  *
  * Buffers named d_* are DEVICE pointers (HBM-resident, 16-byte aligned); everything else is host
- * memory.  All calls are synchronous with respect to the caller on return (outputs are valid),
+ * memory.  A device buffer is exactly as long as its description says ([count][bytes a record],
+ * nothing rounded up to 16 bytes or to an allocation's granularity) and needs no alignment above
+ * 16 bytes, so buffers may be packed into one arena: no entry point writes behind the stated end
+ * of an output or into a buffer declared const (tests/test_gpu_guarded_outputs.py).
+ * All calls are synchronous with respect to the caller on return (outputs are valid),
  * matching a Haskell `foreign import ccall safe`.  A context is bound to one GPU and one HIP
  * stream and is not thread-safe; use one context per thread/GPU.
  *

@@ -68,10 +68,10 @@ def handles(gpu, oracle_lib):
 
 
 class _Dev:
-    """the claimed arrays (and files) of one call in HBM"""
+    """the claimed arrays (and files) of one call in HBM; alloc: another allocator than the handle's context (tests/guard_arena.py)"""
 
-    def __init__(self, nat, inputs, coms_files=None):
-        self.nat, self.gpu, self.B = nat, nat.gpu, len(inputs)
+    def __init__(self, nat, inputs, coms_files=None, alloc=None):
+        self.nat, self.gpu, self.B = nat, alloc or nat.gpu, len(inputs)
         self.binary = isinstance(nat, BRP.NativeBinaryRangeProofs)
         amt, typ, bld = nat._claim_arrays(inputs)
         self.cb = nat.shape["coms_bytes"]

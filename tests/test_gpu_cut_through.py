@@ -65,17 +65,18 @@ def _force(nat, mode=0, salt=None, bits=0):
     assert capi.load_test_library().bppp_test_rp_cut_through_force(nat.h, mode, buf, bits) == 0
 
 
-def _run(nat, j, device):
+def _run(nat, j, device, alloc=None):
+    """alloc: another allocator than the handle's context (tests/guard_arena.py); the two outputs then have their documented capacities to the byte"""
     cl = _claims(nat, j)
     if not device:
         return nat.cut_through(j["rows"], j["sum_start"], j["entries"], cl)
-    g, cb = nat.gpu, nat.shape["coms_bytes"]
+    g, cb, least = alloc or nat.gpu, nat.shape["coms_bytes"], 0 if alloc else 16
     rows, nnz = len(j["rows"]), len(j["entries"])
     ss, en, nsums, _ = nat._tally_csr(j["sum_start"], j["entries"])
     amt, typ, off = nat._tally_claim_arrays(cl, nsums)
     d = [g.to_device(np.frombuffer(b"".join(j["rows"]) or b"\0", dtype=np.uint8)), g.to_device(ss), g.to_device(en)]
     d += [g.to_device(a) if cl is not None and not (a is typ and _binary(nat)) else 0 for a in (amt, typ, off)]
-    d += [g.alloc(max(rows * cb, 16)), g.alloc(max(nnz * 4, 16))]
+    d += [g.alloc(max(rows * cb, least)), g.alloc(max(nnz * 4, least))]
     try:
         r = nat.cut_through_device(rows, d[0], nsums, d[1], d[2], nnz, d[3], d[4], d[5], d[6], d[7])
         nr_, nn = r.counts["new_rows"], r.counts["new_nnz"]

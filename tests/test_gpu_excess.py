@@ -101,10 +101,11 @@ def _host_verdicts(be, st, flat, ss, en, public, msgs, sigs, broken=()):
 
 
 class _Dev:
-    """pool, CSR arrays, public claims, messages and signatures of one call in HBM"""
+    """pool, CSR arrays, public claims, messages and signatures of one call in HBM; alloc: another allocator than the handle's context
+    (tests/guard_arena.py)"""
 
-    def __init__(self, nat, files, sum_start, entries, public, msgs, sigs):
-        g = self.gpu = nat.gpu
+    def __init__(self, nat, files, sum_start, entries, public, msgs, sigs, alloc=None):
+        g = self.gpu = alloc or nat.gpu
         self.rows, self.nsums, self.nnz = len(files), len(sum_start) - 1, len(entries)
         ss, en, _, _ = nat._tally_csr(sum_start, entries)
         amt, typ = nat._excess_claim_arrays(public, self.nsums)

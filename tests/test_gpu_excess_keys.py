@@ -310,10 +310,10 @@ def _native_claims(name, claims):
     return claims if claims is None or name != "bin_test" else [(a, o) for a, _, o in claims]
 
 
-def _sums_dev(nat, files, ss, en, claims, key_start, keys):
+def _sums_dev(nat, files, ss, en, claims, key_start, keys, alloc=None):
     ssa, ena, nsums, nnz = nat._tally_csr(ss, en)
     amt, typ, off = nat._tally_claim_arrays(claims, nsums)
-    dev = _Dev(nat.gpu, cf=_bytes(files), ss=ssa, en=ena, amt=amt, typ=typ if nat.st.__class__.__name__ == "SetupTRRP" else None, off=off,
+    dev = _Dev(alloc or nat.gpu, cf=_bytes(files), ss=ssa, en=ena, amt=amt, typ=typ if nat.st.__class__.__name__ == "SetupTRRP" else None, off=off,
                ks=np.array(key_start, dtype=np.uint32), ky=_bytes(keys))
     return dev, lambda d: (len(files), d["cf"], nsums, d["ss"], d["en"], nnz, d["amt"], d["typ"], d["off"], len(keys), d["ks"], d["ky"])
 

@@ -640,6 +640,10 @@ class Balance:
         comb = [RP.excess_part_combine_host(be, st, pn[ps[t]:ps[t + 1]], pk[ps[t]:ps[t + 1]], partials[ps[t]:ps[t + 1]], msgs[t]) for t in range(nsums)]
         c["part combine"] = lambda nat: (lambda: nat.excess_part_combine(ps, pn, pk, partials, msgs, want_status=True, want_keys=True)), ([x[1] for x in comb], [x[0] for x in comb], [x[2] for x in comb])
         self.calls, self.parts = c, {"part nonces", "part aggregate", "part sign", "part verify", "part combine"}
+        # the job's honest values, for callers that build calls of their own (tests/test_gpu_guarded_outputs.py)
+        self.v = types.SimpleNamespace(inputs=inputs, files=files, sum_start=ss, entries=en, claims=wcl, blinds=es, msgs=msgs, sigs=sigs, excess_points=Xs, keys=keys,
+                                       part_start=ps, part_blinds=pe, part_msgs=pm, part_nonces=pn, part_keys=pk, agg_nonces=an, agg_keys=ak, partials=partials,
+                                       combined=comb)
 
 
 _BALANCE = {}

@@ -89,10 +89,11 @@ def _prefixes(n, tag=b""):
 
 
 class _DeviceCall:
-    """the arrays of one prove call, on the host and uploaded: `amt`, `typ`, `bld` may be edited before `upload`"""
+    """the arrays of one prove call, on the host and uploaded: `amt`, `typ`, `bld` may be edited before `upload`.  alloc: another allocator than the
+    handle's context (tests/guard_arena.py); the two file buffers then have coms_bytes and proof_bytes a proof and not a byte more"""
 
-    def __init__(self, nat, inputs, prefixes, public_amounts=None):
-        self.nat, self.gpu, self.B = nat, nat.gpu, len(inputs)
+    def __init__(self, nat, inputs, prefixes, public_amounts=None, alloc=None):
+        self.nat, self.gpu, self.B, self.slack = nat, alloc or nat.gpu, len(inputs), 0 if alloc else 16
         self.amt, self.typ, self.bld, self.pre, self.plen, self.cf, self.pf = nat._prove_arrays(nat._prove_rows(inputs), prefixes)
         self.amt, self.typ, self.bld = self.amt.copy(), self.typ.copy(), self.bld.copy()
         self.pub = None if public_amounts is None else nat._public_words(public_amounts, self.B)
@@ -102,7 +103,7 @@ class _DeviceCall:
     def __enter__(self):
         g = self.gpu
         self.d = {"amt": g.to_device(self.amt), "typ": g.to_device(self.typ), "bld": g.to_device(self.bld), "pre": g.to_device(self.pre),
-                  "cf": g.alloc(self.cf.nbytes + 16), "pf": g.alloc(self.pf.nbytes + 16), "pub": g.to_device(self.pub) if self.pub is not None else 0}
+                  "cf": g.alloc(self.cf.nbytes + self.slack), "pf": g.alloc(self.pf.nbytes + self.slack), "pub": g.to_device(self.pub) if self.pub is not None else 0}
         return self
 
     def __exit__(self, *exc):

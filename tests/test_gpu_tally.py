@@ -91,10 +91,10 @@ def _claim_point(ec, st, claim):
 
 
 class _Dev:
-    """pool, CSR arrays and claims of one call in HBM"""
+    """pool, CSR arrays and claims of one call in HBM; alloc: another allocator than the handle's context (tests/guard_arena.py)"""
 
-    def __init__(self, nat, files, sum_start, entries, claims=None):
-        g = self.gpu = nat.gpu
+    def __init__(self, nat, files, sum_start, entries, claims=None, alloc=None):
+        g = self.gpu = alloc or nat.gpu
         self.rows, self.nsums, self.nnz = len(files), len(sum_start) - 1, len(entries)
         ss, en, _, _ = nat._tally_csr(sum_start, entries)
         amt, typ, bld = nat._tally_claim_arrays(claims, self.nsums)
