@@ -315,6 +315,10 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_last_comb_msm.argtypes = [vp, C.POINTER(TestCombReport)]
     lib.bppp_test_last_reduce.argtypes = [vp, C.POINTER(TestReduceReport)]
     lib.bppp_test_rp_last_text_kernel.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.bppp_test_rp_lds_plan.argtypes = [i, sz, sz, sz, sz, C.POINTER(TestRpLdsPlan)]
+    lib.bppp_test_rp_last_prove.argtypes = [vp, C.POINTER(TestRpProveReport)]
+    lib.bppp_test_trrp_last_public.argtypes = [vp, C.POINTER(TestRpPublicReport)]
+    lib.bppp_test_rp_last_public.argtypes = [vp, C.POINTER(TestRpPublicReport)]
     lib.bppp_test_rpp_transcript.argtypes = [vp, sz, vp, sz, vp, vp, vp]
     lib.bppp_test_rpp_draws.argtypes = [vp, C.c_char_p, sz, sz, sz, vp]
     lib.bppp_test_ctx_poison.argtypes = [vp, i, C.POINTER(C.c_uint64)]
@@ -328,6 +332,30 @@ class TestCombReport(C.Structure):
     """bppp_test_comb_report (include/bppp_test.h): what the last comb_msm launch on a context did"""
     __test__ = False                      # not a pytest class
     _fields_ = [("route", C.c_int32), ("heavy_first", C.c_int32)] + [(n, C.c_uint32) for n in ("parts", "tparts", "wsplit", "chunks", "clen", "join_lanes")]
+
+
+class TestRpLdsPlan(C.Structure):
+    """bppp_test_rp_lds_plan_report (include/bppp_test.h): the planned dynamic LDS of one of the size-dependent typed-reciprocal kernels"""
+    __test__ = False
+    _fields_ = [("lds_bytes", C.c_uint64)] + [(n, C.c_uint32) for n in ("table", "lanes", "fits", "split")]
+
+
+class TestRpProveReport(C.Structure):
+    """bppp_test_rp_prove_report: what the last typed-reciprocal prove on a handle ran"""
+    __test__ = False
+    _fields_ = [("route", C.c_int32), ("table", C.c_uint32), ("lds2_bytes", C.c_uint64), ("lds3_bytes", C.c_uint64)]
+
+
+class TestRpPublicReport(C.Structure):
+    """bppp_test_rp_public_report: what the last bppp_trrp_public_device on a setup's tables launched"""
+    __test__ = False
+    _fields_ = [("route", C.c_int32), ("lanes", C.c_int32), ("lds_bytes", C.c_uint64)]
+
+
+# bppp_test_rp_lds_plan's kernels, the routes of bppp_test_rp_last_prove and of bppp_test_*_last_public
+TEST_RP_K_PUBLIC, TEST_RP_K_PHASE2, TEST_RP_K_PHASE3 = 0, 2, 3
+TEST_RP_PROVE_DEVICE_ALGEBRA, TEST_RP_PROVE_HOST_ALGEBRA = 1, 2
+TEST_RP_PUBLIC_ONE_KERNEL, TEST_RP_PUBLIC_THREE_KERNELS = 1, 2
 
 
 class TestReduceReport(C.Structure):

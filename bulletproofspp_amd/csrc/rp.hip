@@ -33,6 +33,7 @@
 #include "rp_internal.hpp"
 #include "rpdecode.hip.h"
 #include "brp.hpp"
+#include "trrp.hpp"
 #include "rphash.hip.h"
 #include "fr26.hip.h"
 
@@ -334,6 +335,38 @@ namespace {
 
 std::string dec_str(uint64_t v) { return std::to_string(v); }
 
+// The limits of the device tables (csrc/trrp.hpp), checked on the host setup before anything is built and told in the caller's terms: the base map
+// x^(3 + 2 slot) has TRRP_MAX_SLOTS entries, one per distinct digit base (a leading bit is a digit of base 2), and the reciprocal symbols — as
+// rp_build_tables numbers them: the distinct values among the digits 1 .. b - 1 of every shared base and of every inline range, and the public
+// amounts' types — are at most TRRP_MAX_SYMS.  bppp_rp_shape_of asks the same function (it knows no public amounts: their types count at creation)
+bool rp_setup_limits(const bppp_rps::Setup &st, std::string &err) {
+  // every prover route, the host algebra that serves what the device algebra does not included, indexes ranges below 2^16
+  if (st.rds.size() > TRRP_MAX_RANGES) { err = dec_str(st.rds.size()) + " ranges: at most " + dec_str(TRRP_MAX_RANGES); return false; }
+  if (st.sorted_bases.size() > (size_t)TRRP_MAX_SLOTS) {
+    err = dec_str(st.sorted_bases.size()) + " distinct digit bases (a leading bit counts as base 2): at most " + dec_str(TRRP_MAX_SLOTS);
+    return false;
+  }
+  uint64_t top = 1;                                     // the small symbols are 1 .. top - 1
+  for (const bppp_rps::RangeData &rd : st.rds) if (!rd.assumed && !rd.shared) top = std::max<uint64_t>(top, rd.base);
+  for (uint32_t b : st.m_bases) top = std::max<uint64_t>(top, b);
+  std::vector<U256> types;
+  size_t nsyms = (size_t)(top - 1);
+  bool cut = false;                                     // stopped counting past the limit (a million public amounts are not compared pairwise)
+  for (const bppp_rps::PublicVT &pv : st.pubs) {
+    if (nsyms > TRRP_MAX_SYMS) { cut = true; break; }
+    const U256 &t = pv.type;
+    if (!(t.w[1] | t.w[2] | t.w[3]) && t.w[0] >= 1 && t.w[0] < top) continue;      // a type that equals a digit shares its symbol
+    if (std::find(types.begin(), types.end(), t) != types.end()) continue;
+    types.push_back(t); nsyms++;
+  }
+  if (nsyms > TRRP_MAX_SYMS) {
+    err = dec_str(nsyms) + (cut ? " or more" : "") + " reciprocal symbols (the digits 1 .. " + dec_str(top - 1) +
+          " of the widest live digit base" + (st.pubs.empty() ? "" : " and the distinct public types") + "): at most " + dec_str(TRRP_MAX_SYMS);
+    return false;
+  }
+  return true;
+}
+
 int rp_build_tables(bppp_rp *rp) {
   const bppp_rps::Setup &st = rp->st;
   std::vector<uint32_t> kind, rng, slot, psym, cs_slot, cs_sym, pub_out, pub_sym, assumed;
@@ -525,7 +558,7 @@ static int rp_create_common(bppp_ctx *ctx, int flavour, int has_types, const bpp
   rp->ctx = ctx; ctx_retain(ctx);
   rp->opt.from_env();
   auto fill = [&]() -> int {
-    if (!bppp_rps::make_setup(has_types != 0, rds, pv, rp->st, err, flavour)) return fail(ctx, BPPP_ERR_ARG, "rp_create: " + err);
+    if (!bppp_rps::make_setup(has_types != 0, rds, pv, rp->st, err, flavour) || !rp_setup_limits(rp->st, err)) return fail(ctx, BPPP_ERR_ARG, "rp_create: " + err);
     const bppp_rps::Setup &st = rp->st;
     // points = h : g : hs (linLen) ++ gs (nrmLen)   (TypedReciprocal.hs:334, :348-349); h is not used by the proof
     std::vector<uint64_t> seed_points;
@@ -583,7 +616,7 @@ int bppp_rp_shape_of(int flavour, int has_types, const bppp_rp_range *ranges, si
       return BPPP_ERR_ARG;
   }
   bppp_rps::Setup st;
-  if (!bppp_rps::make_setup(has_types != 0, rds, std::vector<bppp_rps::PublicVT>(), st, err, flavour)) return BPPP_ERR_ARG;
+  if (!bppp_rps::make_setup(has_types != 0, rds, std::vector<bppp_rps::PublicVT>(), st, err, flavour) || !rp_setup_limits(st, err)) return BPPP_ERR_ARG;
   const size_t nr = nranges, k = st.rounds, npp = 4 + 2 * k;
   out->nranges = nr; out->norm_len = st.nlen; out->lin_len = st.llen; out->rounds = k; out->final_norm = st.fn; out->final_lin = st.fl;
   out->coms_bytes = (nr + 7) / 8 + 32 * nr;
@@ -663,7 +696,7 @@ static int rp_create_binary_common(bppp_ctx *ctx, int flavour, int conserve, con
   *out = nullptr;
   if (!ranges || !nranges || !net_public || (!seeded && !points_xy)) return fail(ctx, BPPP_ERR_ARG, "rp_create_binary: null argument");
   if (flavour != 0 && flavour != 1) return fail(ctx, BPPP_ERR_ARG, "rp_create_binary: flavour must be 0 (norm-linear argument) or 1 (inner-product argument)");
-  if (nranges > 1024) return fail(ctx, BPPP_ERR_ARG, "rp_create_binary: at most 1024 ranges");
+  if (nranges > 1024) return fail(ctx, BPPP_ERR_ARG, "rp_create_binary: " + std::to_string(nranges) + " ranges: at most 1024 ranges");
   std::vector<bppp_rps::RangeData> rds(nranges);
   std::string err;
   for (size_t i = 0; i < nranges; i++) {

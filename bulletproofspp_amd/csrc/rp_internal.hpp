@@ -191,6 +191,9 @@ struct bppp_rp {
   // what the last block call on this handle launched up to its verdict (csrc/rpblock.hip; bppp_test_rp_last_block_counts): MSMs, the terms of
   // the one MSM, keys lifted and commitments square-rooted
   uint64_t blk_msms = 0, blk_terms = 0, blk_key_lifts = 0, blk_coms = 0;
+  // what the last typed-reciprocal prove on this handle ran (bppp_test_rp_last_prove): 0 nothing yet, 1 the device algebra (k_rpp_phase2 / k_rpp_phase3
+  // with last_lds2 / last_lds3 bytes of dynamic LDS, csrc/rpprove_dev.hip), 2 the host-algebra route (prove_batch_host, csrc/rpprove.hip)
+  int last_prove_route = 0; size_t last_lds2 = 0, last_lds3 = 0;
   int last_text_kernel = -1;         // transcript text kernel of the last verification on this handle: 0 k_rp_text, 1 k_rp_text_lds (bppp_test_rp_last_text_kernel)
   // the tally entry points (csrc/rptally.hip): the longest sum one lane walks alone, the entries of one workgroup's piece of a longer sum, and
   // the entries (and sums) of one pass over the workspace; test hooks lower them so that small jobs straddle them (include/bppp_test.h)

@@ -438,12 +438,11 @@ extern "C" int bppp_rp_prove_batch(bppp_rp *rp, size_t batch, const uint64_t *am
   return bppp_rp_prove_batch_pub(rp, batch, amounts, types, blinds, nullptr, rand_prefix, prefix_len, coms_files, proof_files);
 }
 
-// shapes the device algebra does not serve: it looks digits up in a per-proof table of reciprocals held in LDS (256 entries, up to 2048 for wider digit
-// bases); bases beyond that take the host-algebra path (prove_batch_one)
+// shapes the device algebra does not serve: it looks digits up in a per-proof table of reciprocals held in LDS (16 entries, up to 1024 for wider digit
+// bases) beside one entry per range.  A setup whose phase kernels would not fit a workgroup's LDS (the planning functions of csrc/rpprove_dev.hpp, which
+// size the launches too), and a wide table with many ranges, take the host-algebra path (prove_batch_one): the same bytes
 static bool lds_gate(const Setup &st) {
-  uint32_t max_base = 0;
-  for (const RangeData &rd : st.rds) max_base = std::max(max_base, rd.base);
-  return max_base > 2048 || (max_base > 256 && st.rds.size() > 256);
+  return !rpp_phases_fit_lds(st) || (rpp_maxb(st) > 256 && st.rds.size() > 256);
 }
 // bppp_rp_prove_batch_device: does this call run as one stream of kernels over the handle's comb table (csrc/rpprove_dev.hip, csrc/brpprove_dev.hip)?
 // Otherwise its inputs come down and the host-buffer routes below serve it.
@@ -675,6 +674,7 @@ static int prove_batch_host(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
   const Setup &st = rp->st;
   const size_t B = batch, nr = st.rds.size(), nlen = st.nlen, llen = st.llen, k = st.rounds, T = 1 + llen + nlen, npub = rp_public_count(rp);
   if (nr >= (1u << 16)) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: too many ranges");
+  rp->last_prove_route = 2; rp->last_lds2 = rp->last_lds3 = 0;
   { int rc = rpp_build_fixed_table(rp); if (rc) return rc; }
   // the basis of commitRPW is fixed per setup: registered once with its fixed-base table (one bucket set for all windows)
   if (!rp->commit_basis) { int rc = bppp_basis_create_device(ctx, rp->d_basis, T, 0, 4096, &rp->commit_basis); if (rc) return rc; }

@@ -426,8 +426,7 @@ static PDims rpp_dims(const bppp_rp *rp) {
   const bppp_rps::Setup &S = rp->st;
   PDims D; D.nlen = (uint32_t)S.nlen; D.llen = (uint32_t)S.llen; D.nr = (uint32_t)S.rds.size(); D.T = (uint32_t)(1 + S.llen + S.nlen); D.has_types = S.has_types ? 1u : 0u;
   D.nd = (uint32_t)(14 + (S.llen - 5) + S.nlen);
-  D.maxb = 16;
-  for (const bppp_rps::RangeData &rd : S.rds) while (D.maxb < rd.base && D.maxb < 2048) D.maxb <<= 1;       // bases above 2048 take the host-algebra route (csrc/rpprove.hip)
+  D.maxb = rpp_maxb(S);
   return D;
 }
 
@@ -497,6 +496,11 @@ int rpp_prove_body(bppp_rp *rp, size_t B, const RppWork &W, size_t prefix_len, c
   // every oracle call reads its points where they lie, and the headers of all 3 + k oracle calls go up here
   const bool stream_mode = rp->comb != nullptr && !rp->opt.fold_points;
   if (dev && !stream_mode) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch_device: no device stream on this route");
+  // the phase kernels' dynamic LDS, planned by the functions the route gate asks (csrc/rpprove_dev.hpp, lds_gate of csrc/rpprove.hip): a setup
+  // beyond a workgroup's LDS never gets here
+  const size_t lds2 = rpp_phase2_lds_bytes(D.maxb, nr), lds3 = rpp_phase3_lds_bytes(nr);
+  if (lds2 > LDS_MAX_BYTES || lds3 > LDS_MAX_BYTES) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: too many ranges for the device prover");
+  rp->last_prove_route = 1; rp->last_lds2 = lds2; rp->last_lds3 = lds3;
   const size_t cscratch_bytes = std::max(comb_rows_scratch_bytes(B), comb_scratch_bytes(2 * B));
   // A handful of proofs: the oracle moves to the host.  One GPU lane walks the ~160 SHA-256 blocks of a 64by64 transcript in ~0.6 ms
   // (11 times per proof); a host core needs ~50 us, which pays for the round trip of the new points and the challenges as long as
@@ -514,10 +518,8 @@ int rpp_prove_body(bppp_rp *rp, size_t B, const RppWork &W, size_t prefix_len, c
   int rc = rpp_commit_inputs(rp, in_sc, B * nr, in_pt); if (rc) return rc;
   if (host) BPPP_HIP(ctx, hipMemcpyAsync(out.input_coms, in_pt, B * nr * 64, hipMemcpyDeviceToHost, st));
   if (stream_mode) {
-    const size_t lds2 = (2 * (INV_DIG + D.maxb + nr) + 128 + TRRP_MAX_SLOTS) * 32, lds3 = ((size_t)6 * 64 + nr + TRRP_MAX_SLOTS + 4) * 32;
-    if (lds2 > 160 * 1024) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: too many ranges for the device prover");
-    if (lds2 > 64 * 1024) BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_rpp_phase2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-    if (lds3 > 64 * 1024) BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_rpp_phase3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
+    if (lds2 > LDS_DEFAULT_BYTES) BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_rpp_phase2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+    if (lds3 > LDS_DEFAULT_BYTES) BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_rpp_phase3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
     auto comb = [&](const uint32_t *rows, size_t n, uint32_t *dst, int hint) -> int {
       int r_ = comb_msm(rp->comb, rows, n, dst, st, hint, T, cscratch, cscratch_bytes);
       return r_ ? fail(ctx, r_, bppp_last_error(rp->comb->ctx)) : BPPP_OK;
@@ -574,17 +576,13 @@ int rpp_prove_body(bppp_rp *rp, size_t B, const RppWork &W, size_t prefix_len, c
     }
     rc = oracle(pts.data(), 0); if (rc) return rc;
   }
-  const size_t m2 = INV_DIG + D.maxb + nr;
-  const size_t lds2 = (2 * m2 + 128 + TRRP_MAX_SLOTS) * 32;
-  if (lds2 > 160 * 1024) return fail(ctx, BPPP_ERR_ARG, "rp_prove_batch: too many ranges for the device prover");
-  if (lds2 > 64 * 1024) BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_rpp_phase2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+  if (lds2 > LDS_DEFAULT_BYTES) BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_rpp_phase2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
   k_rpp_phase2<<<dim3((unsigned)B), dim3(64), lds2, st>>>(D, TD, tb->pos_kind, tb->pos_range, tb->pos_slot, tb->pos_sym, tb->syms, in_sc, dig, rnd, ch, row_r, ccbuf, invtab);
   BPPP_HIP(ctx, hipGetLastError());
   rc = rpp_commit_rows(rp, row_r, B, out.c_r); if (rc) return rc;
   // ---- (q, x', r1) <- oracle [rCom]
   rc = oracle(out.c_r, 1); if (rc) return rc;
-  const size_t lds3 = ((size_t)6 * 64 + nr + TRRP_MAX_SLOTS + 4) * 32;
-  if (lds3 > 64 * 1024) BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_rpp_phase3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
+  if (lds3 > LDS_DEFAULT_BYTES) BPPP_HIP(ctx, hipFuncSetAttribute((const void *)k_rpp_phase3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
   k_rpp_phase3<<<dim3((unsigned)B), dim3(64), lds3, st>>>(D, TD, tb->pos_kind, tb->pos_range, tb->pos_slot, tb->pos_coeff, tb->range_assumed, tb->syms, tb->cs_slot, tb->cs_sym,
                                                           in_sc, dig, mul, rnd, ch, rows_dm_m, row_r, ccbuf, invtab, row_bl, aux);
   BPPP_HIP(ctx, hipGetLastError());

@@ -6,11 +6,35 @@
 #include <vector>
 #include <stdint.h>
 #include "rp_internal.hpp"
+#include "trrp.hpp"
 
 namespace bppp {
 
 struct PDims { uint32_t nlen, llen, nr, T, nd, has_types, maxb; };     // T = 1 + llen + nlen (one commitment row), nd = random scalars per proof,
-// maxb = entries of the per-proof reciprocal table 1 / (e + s), s < maxb: the power of two at or above the setup's widest digit base (16 .. 2048)
+// maxb = entries of the per-proof reciprocal table 1 / (e + s), s < maxb: the power of two at or above the setup's widest digit base (16 .. 1024)
+
+// The widest digit base a proof of this setup has digits of, rounded up to the table classes 16, 32, ..., 1024.  An assumed range has no digits
+// and no symbols, whatever its base says; a live base is at most 1023 (a shared base b costs b - 1 of the TRRP_MAX_SYMS symbols, an inline one as
+// many digits: bppp_rp_create refuses anything wider)
+inline uint32_t rpp_table_class(uint32_t widest_base) {        // the power of two at or above the base, 16 at the least (a base fits 32 bits: no overflow below 2^31)
+  uint32_t t = 16;
+  while (t < widest_base && t < (1u << 31)) t <<= 1;
+  return t;
+}
+inline uint32_t rpp_maxb(const bppp_rps::Setup &S) {
+  uint32_t widest = 0;
+  for (const bppp_rps::RangeData &rd : S.rds) if (!rd.assumed) widest = std::max(widest, rd.base);
+  return rpp_table_class(widest);
+}
+// dynamic LDS of the two phase kernels (csrc/rpprove_dev.hip), one workgroup per proof, in field elements of 32 bytes.  Phase 2: the values and
+// the prefix products of the batch inversion (e, r0, the maxb reciprocals, one entry per range), two scan rows of 64, the base map.  Phase 3: six
+// reduction rows of 64, x^(2(j+1)) per range, the base map, four inverses
+inline size_t rpp_phase2_lds_bytes(size_t maxb, size_t nr) { return (2 * (2 + maxb + nr) + 128 + (size_t)TRRP_MAX_SLOTS) * 32; }
+inline size_t rpp_phase3_lds_bytes(size_t nr) { return ((size_t)6 * 64 + nr + (size_t)TRRP_MAX_SLOTS + 4) * 32; }
+// does the device algebra serve this setup?  (csrc/rpprove.hip: what does not fit takes the host-algebra route, same bytes out)
+inline bool rpp_phases_fit_lds(const bppp_rps::Setup &S) {
+  return rpp_phase2_lds_bytes(rpp_maxb(S), S.rds.size()) <= LDS_MAX_BYTES && rpp_phase3_lds_bytes(S.rds.size()) <= LDS_MAX_BYTES;
+}
 
 struct RppHostInputs {
   size_t batch;

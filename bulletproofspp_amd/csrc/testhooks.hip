@@ -17,6 +17,8 @@
 #include "seedpoints.hip.h"
 #include "comb.hip.h"
 #include "rpp_transcript.hpp"
+#include "rpprove_dev.hpp"
+#include "trrp.hpp"
 
 namespace bppp {
 template <int MOD> BPPP_DI fe apply_op(int op, const fe &a, const fe &b) {
@@ -865,6 +867,37 @@ extern "C" int bppp_test_rp_last_text_kernel(bppp_rp *rp, int *lds) {
   if (!rp || !lds) return BPPP_ERR_ARG;
   *lds = rp->last_text_kernel;
   return BPPP_OK;
+}
+
+// ---- the size classes of the range-proof layer: the launches' own planning functions (csrc/rpprove_dev.hpp, csrc/trrp.hpp), and what last ran
+extern "C" int bppp_test_rp_lds_plan(int kernel, size_t max_base, size_t nranges, size_t nsyms, size_t batch, bppp_test_rp_lds_plan_report *r) {
+  if (!r || nranges >= (1u << 24) || nsyms >= (1u << 24) || max_base >= (1u << 24)) return BPPP_ERR_ARG;
+  memset(r, 0, sizeof *r);
+  if (kernel == BPPP_TEST_RP_K_PHASE2 || kernel == BPPP_TEST_RP_K_PHASE3) {
+    const uint32_t maxb = rpp_table_class((uint32_t)max_base);      // the function rpp_maxb rounds with
+    r->table = maxb; r->lanes = 64;
+    r->lds_bytes = kernel == BPPP_TEST_RP_K_PHASE2 ? rpp_phase2_lds_bytes(maxb, nranges) : rpp_phase3_lds_bytes(nranges);
+    r->fits = r->lds_bytes <= LDS_MAX_BYTES;
+    return BPPP_OK;
+  }
+  if (kernel != BPPP_TEST_RP_K_PUBLIC || !batch) return BPPP_ERR_ARG;
+  const TrrpPublicPlan p = trrp_public_plan(nsyms, nranges, batch);
+  r->lanes = (uint32_t)p.G; r->lds_bytes = p.lds; r->fits = p.lds <= LDS_MAX_BYTES; r->split = p.split ? 1u : 0u;
+  return BPPP_OK;
+}
+extern "C" int bppp_test_rp_last_prove(bppp_rp *rp, bppp_test_rp_prove_report *r) {
+  if (!rp || !r) return BPPP_ERR_ARG;
+  r->route = rp->last_prove_route; r->table = rp->st.kind == 0 ? rpp_maxb(rp->st) : 0; r->lds2_bytes = rp->last_lds2; r->lds3_bytes = rp->last_lds3;
+  return BPPP_OK;
+}
+extern "C" int bppp_test_trrp_last_public(bppp_trrp *t, bppp_test_rp_public_report *r) {
+  if (!t || !r) return BPPP_ERR_ARG;
+  r->route = t->last_route; r->lanes = t->last_lanes; r->lds_bytes = t->last_lds;
+  return BPPP_OK;
+}
+extern "C" int bppp_test_rp_last_public(bppp_rp *rp, bppp_test_rp_public_report *r) {
+  if (!rp || !r || !rp->tabs) return BPPP_ERR_ARG;
+  return bppp_test_trrp_last_public(rp->tabs, r);
 }
 
 // ---- the provers' transcript and randomness (csrc/rpp_transcript.hip) alone.  That file and csrc/rpbind.hip are linked into this library as they

@@ -424,7 +424,7 @@ int bppp_trrp_create(bppp_ctx *ctx, int flavour, int has_types, size_t nlen, siz
                      size_t nsyms, const uint64_t *syms, const uint32_t *cs_slot, const uint32_t *cs_sym, size_t npub, const uint32_t *pub_is_out,
                      const uint64_t *pub_amount, const uint32_t *pub_sym, bppp_trrp **out) {
   if (!ctx || !out || ctx_closed(ctx)) return BPPP_ERR_ARG;
-  if (!nlen || llen < 6 || !nranges || nlen >= (1u << 24) || llen >= (1u << 24) || nranges >= (1u << 20) || nsyms + 2 > 1024 || npub >= (1u << 20) ||
+  if (!nlen || llen < 6 || !nranges || nlen >= (1u << 24) || llen >= (1u << 24) || nranges >= (1u << 20) || nsyms > TRRP_MAX_SYMS || npub >= (1u << 20) ||
       !pos_kind || !pos_range || !pos_slot || !pos_sym || !pos_coeff || !range_min || !range_assumed || (nsyms && !syms) || (llen > 6 && (!cs_slot || !cs_sym)) ||
       (npub && (!pub_is_out || !pub_amount || !pub_sym)))
     return fail(ctx, BPPP_ERR_ARG, "trrp_create: bad arguments (at most 1022 distinct reciprocal symbols)");
@@ -471,10 +471,14 @@ int bppp::trrp_public_run(bppp_trrp *o, size_t batch, const void *d_challenges, 
   if (!batch) return BPPP_OK;
   if (!d_challenges || !d_q || !d_sp || !d_pub_norm || !d_pub_lin_c || !d_init_scalars || batch >= (1u << 24)) return fail(ctx, BPPP_ERR_ARG, "trrp_public: bad arguments");
   hipSetDevice(ctx->device);
-  // batches that fill the chip: the three-kernel split (small live sets, the per-proof start-up once); its record lives in the context's scratch
+  // batches that fill the chip, and setups beyond one workgroup's LDS: the three-kernel split (small live sets, the per-proof start-up once); its
+  // record lives in the context's scratch
   static const int force_split = [] { const char *e = getenv("BPPP_TRRP_SPLIT"); return e ? atoi(e) : -1; }();
-  const bool split = force_split >= 0 ? force_split != 0 : batch > 1024;
-  if (split) {
+  static const int forced_g = [] { const char *e = getenv("BPPP_TRRP_G"); const int v = e ? atoi(e) : 0; return (v == 16 || v == 32 || v == 64) ? v : 0; }();
+  // one function plans the launch (csrc/trrp.hpp): a setup whose one-kernel LDS does not fit a workgroup takes the three kernels at every batch size
+  const TrrpPublicPlan plan = trrp_public_plan(o->D.nsyms, o->D.nr, batch, forced_g, force_split);
+  if (plan.split) {
+    o->last_route = 2; o->last_lanes = 0; o->last_lds = 0;
     const TrrpRec R = trrp_rec(o->D);
     int rc = ensure_scratch(ctx, (size_t)batch * R.words * 4 + 256); if (rc) return rc;
     uint32_t *rec = (uint32_t *)ctx->ws2;
@@ -497,12 +501,9 @@ int bppp::trrp_public_run(bppp_trrp *o, size_t batch, const void *d_challenges, 
   // lanes per proof: 32 (two proofs per wavefront) unless the LDS of the proofs of a wavefront would not fit a workgroup; a batch that
   // cannot give every SIMD a wavefront anyway (<= 1024 proofs) takes a whole wavefront per proof: the kernel is then one proof's
   // dependency chain, which 64 lanes walk in fewer steps
-  static const int forced_g = [] { const char *e = getenv("BPPP_TRRP_G"); const int v = e ? atoi(e) : 0; return (v == 16 || v == 32 || v == 64) ? v : 0; }();
-  int G = forced_g ? forced_g : (batch <= 1024 ? 64 : 32);
-  auto words = [&](int g) { return ((size_t)(2 + o->D.nsyms) + 2 * (size_t)g + o->D.nr + 3 * TRRP_MAX_SLOTS) * 10; };      // fr26: ten words per element
-  while (G < 64 && words(G) * 4 * (64 / G) > 64 * 1024) G <<= 1;
-  const size_t wpp = words(G), lds = wpp * 4 * (64 / G);
-  if (lds > 160 * 1024) return fail(ctx, BPPP_ERR_ARG, "trrp_public: too many ranges for one workgroup's LDS");
+  const int G = plan.G;
+  const size_t wpp = plan.words_per_proof, lds = plan.lds;
+  o->last_route = 1; o->last_lanes = G; o->last_lds = lds;
   const unsigned grid = (unsigned)((batch + 64 / G - 1) / (64 / G));
 #define TRRP_LAUNCH(GG, PP, AMT)                                                                                                               \
   k_trrp_public<GG, PP><<<dim3(grid), dim3(64), lds, ctx->stream>>>(o->D, (uint32_t)batch, (uint32_t)wpp, o->pos_kind, o->pos_range, o->pos_slot, o->pos_sym, \
@@ -511,7 +512,7 @@ int bppp::trrp_public_run(bppp_trrp *o, size_t batch, const void *d_challenges, 
                                                                    (uint32_t *)d_pub_norm, (uint32_t *)d_pub_lin_c, (uint32_t *)d_init_scalars)
 #define TRRP_LAUNCH_G(GG) do { if (d_pub_amounts) TRRP_LAUNCH(GG, true, (const uint32_t *)d_pub_amounts); else TRRP_LAUNCH(GG, false, o->pub_amount); } while (0)
   if (G == 64) {
-    if (lds > 64 * 1024)
+    if (lds > LDS_DEFAULT_BYTES)
       BPPP_HIP(ctx, hipFuncSetAttribute(d_pub_amounts ? (const void *)k_trrp_public<64, true> : (const void *)k_trrp_public<64, false>,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     TRRP_LAUNCH_G(64);

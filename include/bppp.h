@@ -345,6 +345,19 @@ int bppp_trrp_public_device(bppp_trrp *t, size_t batch, const void *d_challenges
  *     the other one is 1 under a digit of radix base, so a proof would bound value - min by base, not by max - min ("range narrower than its digit
  *     base: the reference's coefficients do not bound it").  Use a base <= max - min (base 2 fits every width >= 2);
  *   - a range of width 1 ("degenerate range: a digit coefficient is zero").
+ * Size limits, checked at creation before anything is built (BPPP_ERR_ARG and a message that names the count and the limit); a setup that
+ * bppp_rp_create accepts never fails later for its size:
+ *   - at most 65535 ranges ("65536 ranges: at most 65535"): every prover route, the host algebra included, indexes ranges below 2^16;
+ *   - at most 16 distinct digit bases among the ranges that are not assumed, a leading bit counting as base 2 ("17 distinct digit bases
+ *     (a leading bit counts as base 2): at most 16");
+ *   - at most 1022 reciprocal symbols: the digits 1 .. b - 1 of the widest shared or inline base b and the distinct public types that are not
+ *     such a digit ("1023 reciprocal symbols (...): at most 1022").  So a shared digit base is at most 1023 — and smaller by the number of
+ *     distinct public types; an inline base is bounded by its digits long before (base - 1 of them);
+ *   - bppp_rp_create_binary: at most 1024 ranges ("1025 ranges: at most 1024 ranges").
+ * bppp_rp_shape_of refuses the same ranges (it knows no public amounts: their types count at creation only).
+ * Beyond 2470 ranges of small bases (less with a wider base: the phase kernels' LDS, csrc/rpprove_dev.hpp) a prove takes the HOST_ALGEBRA route
+ * by itself, same bytes; beyond 3917 ranges and symbols together a verification computes its public scalars in three kernels over HBM instead
+ * of one over LDS, at every batch size (csrc/trrp.hpp), same results.
  *
  * The Fiat-Shamir oracle of these entry points is the CLI's shaOracle (app/Main.hs:64-80) computed natively: challenge n =
  * decode (SHA-256 (tag <> show n <> show (length ps) <> foldMap (show x <> show y) ps)) over the WHOLE transcript, newest first
@@ -563,7 +576,8 @@ int bppp_rp_prove_batch_pub(bppp_rp *rp, size_t batch, const uint64_t *amounts, 
  * two output buffers hold, byte for byte, what bppp_rp_prove_batch_pub writes for the same inputs on the same handle, and the call
  * does the same bookkeeping (the comb table is built at the same point, the options, a shared table and the two half-batches of a
  * large batch apply as they do there; d_public_amounts is read back and checked on the host as the verifier's _pub_device calls do).
- * With the handle's comb table in place (and neither HOST_ALGEBRA nor FOLD_POINTS set, no digit base above 2048) nothing of a proof
+ * With the handle's comb table in place (neither HOST_ALGEBRA nor FOLD_POINTS set, and a setup the device algebra serves: its phase kernels fit a
+ * workgroup's LDS — 2470 ranges of small bases —, and a digit base above 256 meets at most 256 ranges) nothing of a proof
  * crosses to the host but one status word per proof: a kernel checks the witness (canonical types and blindings, balance, ranges) and
  * extracts digits and multiplicities, the prover's stream of kernels runs on its output, a kernel encodes the files.  Internal
  * thresholds stay (at most HOST_ORACLE_MAX proofs still hash their transcripts on the host cores).  Every other route is the SLOW PATH

@@ -224,6 +224,30 @@ int bppp_test_last_reduce(bppp_ctx *ctx, bppp_test_reduce_report *report);
 /* The transcript text kernel of the last verification on this handle (bppp_rp_verify_batch*, _each*, its share of _mixed*): 0 = k_rp_text,
  * 1 = k_rp_text_lds (while the text image of a proof fits 64 KiB of LDS: up to 272 transcript points), -1 = none yet. */
 int bppp_test_rp_last_text_kernel(bppp_rp *rp, int *lds);
+/* The size classes of the typed-reciprocal kernels whose dynamic LDS grows with the setup.  bppp_test_rp_lds_plan asks the host functions that
+ * size the launches and gate the routes (csrc/rpprove_dev.hpp, csrc/trrp.hpp); it takes dimensions, needs no context and launches nothing.
+ *   kernel  BPPP_TEST_RP_K_PHASE2 / _PHASE3: the provers' k_rpp_phase2 / k_rpp_phase3 for a setup of `nranges` ranges whose widest live digit base
+ *           is max_base (nsyms, batch unused).  table: the entries of the per-proof reciprocal table, the power of two at or above max_base
+ *           (16 .. 1024); lanes 64; fits: lds_bytes <= 160 KiB — where either phase does not fit, a prove takes the host-algebra route.
+ *           BPPP_TEST_RP_K_PUBLIC: bppp_trrp_public_device on `batch` proofs of a setup of nranges ranges and nsyms reciprocal symbols (max_base
+ *           unused).  lanes per proof and lds_bytes of k_trrp_public; split: 1 = the call runs k_trrp_pre / k_trrp_pos / k_trrp_lin instead
+ *           (batch > 1024, or fits = 0).
+ * Above 64 KiB a launch asks for its LDS with hipFuncSetAttribute.
+ * bppp_test_rp_last_prove: the last typed-reciprocal prove on the handle.  route 0 = none yet, 1 = the device algebra (lds2_bytes / lds3_bytes: the
+ * dynamic LDS its phase kernels were launched with), 2 = the host-algebra route (both 0); table as above, for the handle's setup.  The report is
+ * written on the handle that proves: a batch of SPLIT_MIN proofs or more runs as two halves, the second on the handle's twin, so after such a call
+ * the report describes the first half only (same setup, same route and LDS); a batch run on the twin alone does not exist.  The reports say what
+ * was planned and launched, not whether hipFuncSetAttribute was called: a launch above 64 KiB has been seen to run without it.
+ * bppp_test_trrp_last_public / bppp_test_rp_last_public: the last bppp_trrp_public_device on these tables, resp. the last run of the same kernels
+ * inside a verification or a prove on the handle.  route 0 = none yet, 1 = k_trrp_public (lanes per proof, lds_bytes), 2 = the three kernels. */
+enum { BPPP_TEST_RP_K_PUBLIC = 0, BPPP_TEST_RP_K_PHASE2 = 2, BPPP_TEST_RP_K_PHASE3 = 3 };
+typedef struct bppp_test_rp_lds_plan_report { uint64_t lds_bytes; uint32_t table, lanes, fits, split; } bppp_test_rp_lds_plan_report;
+typedef struct bppp_test_rp_prove_report { int32_t route; uint32_t table; uint64_t lds2_bytes, lds3_bytes; } bppp_test_rp_prove_report;
+typedef struct bppp_test_rp_public_report { int32_t route, lanes; uint64_t lds_bytes; } bppp_test_rp_public_report;
+int bppp_test_rp_lds_plan(int kernel, size_t max_base, size_t nranges, size_t nsyms, size_t batch, bppp_test_rp_lds_plan_report *report);
+int bppp_test_rp_last_prove(bppp_rp *rp, bppp_test_rp_prove_report *report);
+int bppp_test_trrp_last_public(bppp_trrp *tabs, bppp_test_rp_public_report *report);
+int bppp_test_rp_last_public(bppp_rp *rp, bppp_test_rp_public_report *report);
 /* The provers' transcript (RppTranscript of csrc/rpp_transcript.hip) alone, in device mode whatever the batch size: begin with the `ncalls` oracle
  * calls given, no argument rounds, then call 0, 1, ... in turn.  Call c puts calls[c].points new points in front of every proof's text and draws
  * calls[c].count (1 .. 3) challenges, into slots first_slot .. of ch (first_slot + count <= 7) or, first_slot = 7 and count = 1, into es.

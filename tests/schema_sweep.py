@@ -266,10 +266,24 @@ def range_data(s):
     return rds
 
 
-def host_setup(backend, s):
+def basis_points_needed(s, rds):
+    """the points `setup` takes for this schema, by its own arithmetic (TypedReciprocal.hs:332-359: h, g, linLen, nrmLen; Binary.hs:147-148: h, g,
+    h0, h1, nrmLen): a norm position per coefficient of every range and one per range under types; six linear positions and base - 1 per
+    distinct shared base of the live ranges, 2 among them when a live shared range has a leading bit"""
     if s.binary:
-        return BRP.setup(backend, points(), s.cons, range_data(s), s.net_public, s.flavour)
-    return RP.setup(backend, points(), s.cons, list(s.pubs), range_data(s), s.flavour)
+        return 4 + sum(len(rd.base_coeffs) for rd in rds)
+    live = [rd for rd in rds if not rd.is_assumed]
+    m_bases = {rd.base for rd in live if rd.is_shared} | ({2} if any(rd.has_bit and rd.is_shared for rd in live) else set())
+    return 2 + 6 + sum(b - 1 for b in m_bases) + sum(len(rd.base_coeffs) + (1 if s.cons else 0) for rd in rds)
+
+
+def host_setup(backend, s):
+    rds = range_data(s)
+    need = basis_points_needed(s, rds)
+    pts = points() if need <= len(points()) else size_points(need)      # every member of the sweep fits points(); the size edges may not
+    if s.binary:
+        return BRP.setup(backend, pts, s.cons, rds, s.net_public, s.flavour)
+    return RP.setup(backend, pts, s.cons, list(s.pubs), rds, s.flavour)
 
 
 def _fits(s):
@@ -323,7 +337,186 @@ def edge_setups():
 
 
 def by_name(name):
-    return next(s for s in sweep() + edge_setups() if s.name == name)
+    s = next((s for s in sweep() + edge_setups() if s.name == name), None)
+    return s if s is not None else next(s for s in size_edges() if s.name == name)
+
+
+# ----------------------------------------------------------------------------- the setup size classes of the native layer
+# Setups that sit on the edges where the native range-proof layer changes its path with the SIZE of a setup (tests/test_size_classes_host.py
+# pins what they cover, tests/test_gpu_size_classes.py runs them): the 16 slots of the base map, the reciprocal-symbol limit, the classes of
+# the prover's reciprocal table, the 64 KiB and 160 KiB edges of the dynamic LDS of k_rpp_phase2, k_rpp_phase3 and k_trrp_public, the
+# prover's wide-table clause and the binary range limit.  The range counts at the LDS edges are not written down here: they are found by
+# bisection on bppp_test_rp_lds_plan, the functions that size the launches themselves, and `size_expect()` says which class every member
+# was built for — a test that finds it elsewhere fails and says that the shape must be picked again.
+MAX_SLOTS, MAX_SYMS, MAX_BINARY_RANGES, MAX_RANGES = 16, 1022, 1024, 65535
+LDS_DEFAULT, LDS_MAX = 64 * 1024, 160 * 1024
+K_PUBLIC, K_PHASE2, K_PHASE3 = 0, 2, 3
+WIDE_TYPE = 2**200
+_SIZE = {}
+_SIZE_POINTS = []
+_TLIB = []
+
+
+def lds_plan(kernel, max_base=0, nranges=0, nsyms=0, batch=1):
+    """bppp_test_rp_lds_plan: the planned dynamic LDS of one launch (no GPU, no context)"""
+    import ctypes as C
+    from bulletproofspp_amd import capi
+    if not _TLIB:
+        _TLIB.append(capi.load_test_library())
+    r = capi.TestRpLdsPlan()
+    assert _TLIB[0].bppp_test_rp_lds_plan(kernel, max_base, nranges, nsyms, batch, C.byref(r)) == 0
+    return r
+
+
+def first_count(pred, hi=1 << 20):
+    """the least n in [1, hi] with pred(n), for a monotone pred: bisection"""
+    lo = 1
+    assert pred(hi)
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if pred(mid):
+            hi = mid
+        else:
+            lo = mid + 1
+    return lo
+
+
+def lds_edges():
+    """the range counts at which a setup of inline base-2 ranges (table class 16, one reciprocal symbol) changes class"""
+    if "edges" not in _SIZE:
+        p2 = lambda n: lds_plan(K_PHASE2, 2, n).lds_bytes
+        p3 = lambda n: lds_plan(K_PHASE3, 2, n).lds_bytes
+        pub = lambda n: lds_plan(K_PUBLIC, 0, n, 1, 1).lds_bytes
+        _SIZE["edges"] = dict(
+            phase2_64k=first_count(lambda n: p2(n) > LDS_DEFAULT), phase3_64k=first_count(lambda n: p3(n) > LDS_DEFAULT),
+            public_64k=first_count(lambda n: pub(n) > LDS_DEFAULT), phase2_max=first_count(lambda n: p2(n) > LDS_MAX) - 1,
+            public_max=first_count(lambda n: pub(n) > LDS_MAX) - 1)
+    return dict(_SIZE["edges"])
+
+
+def size_points(n):
+    """the first n points of the size-edge basis (a prefix of one stream: a longer request extends it)"""
+    if len(_SIZE_POINTS) < n:
+        _SIZE_POINTS[:] = O.hash_points(b"schema sweep size edges", next((m for m in (1200, 4200) if m >= n), n))
+    return _SIZE_POINTS[:n]
+
+
+def _untyped(name, ranges, flavour="NL"):
+    rnd = random.Random("%s size %s" % (SEED, name))
+    rows = _rows_of(ranges, False)
+    return Schema(name, False, ranges, False, [], 0, flavour, _witnesses(rnd, rows, 0, False))
+
+
+def _typed(name, ranges, kind, ty, more_pubs=()):
+    """typed with public amounts: the ranges' own type balanced as the sweep balances it, `more_pubs` (pairs that cancel) in front"""
+    rnd = random.Random("%s size %s" % (SEED, name))
+    rows = _rows_of(ranges, False)
+    pubs, net = _publics(rnd, rows, kind, ty)
+    wits = _witnesses(rnd, rows, net, True)
+    assert wits is not None
+    return Schema(name, False, ranges, True, list(more_pubs) + pubs, ty, "NL", wits)
+
+
+def _bases16():
+    """bases 2 .. 17, no leading bit anywhere (every width a power of its base): inline 2, 3 and 14 (1, 2 and 13 digits), the rest shared with
+    one digit — slot 12 (base 14) inline, slots 13 .. 15 (15, 16, 17) shared"""
+    out = []
+    for b in range(2, 18):
+        inline = b in (2, 3, 14)
+        out.append((b, 0, b ** (b - 1) if inline else b, not inline, b % 2 == 1, False))
+    return out
+
+
+def _many(n):
+    return [(2, 0, 2, False, i % 2 == 1, False) for i in range(n)]
+
+
+def _generate_size_edges():
+    if "list" in _SIZE:
+        return
+    out, exp = [], {}
+
+    def put(s, **e):
+        out.append(s)
+        exp[s.name] = dict(dict(refused=None, binary=False), **e)
+
+    e = lds_edges()
+    # a, b: the base map's slots
+    a = _bases16()
+    for s in (_untyped("size-a-bases16-untyped-NL", a), _typed("size-a-bases16-typed-NL", a, 2, TYPES[0]), _untyped("size-a-bases16-untyped-IP", a, "IP")):
+        put(s, slots=16, table=32, nsyms=16 + (len({t for _, t, _ in s.pubs} - set(range(1, 17)))), prove="device", lds2="default", lds3="default", public="default")
+    put(_untyped("size-b-bases17-untyped-NL", a + [(18, 0, 18, True, False, False)]), slots=17, nsyms=17,
+        refused=["17 distinct digit bases", "at most 16"])
+    # c: the classes of the prover's reciprocal table, one shared one-digit range (its top digit base - 1 reads the table's last live entry)
+    for b, table in ((16, 16), (17, 32), (256, 256), (257, 512), (512, 512), (513, 1024), (1023, 1024)):
+        put(_untyped("size-c-base%d-shared" % b, [(b, 0, b, True, True, False), (4, 0, 4, True, False, False)]), slots=2, table=table, nsyms=b - 1, prove="device",
+            lds2="above" if table == 1024 else "default", lds3="default", public="default")      # 1024 reciprocals alone pass 64 KiB in phase 2
+    # an ASSUMED range has no digits and no symbols: its base, however wide, neither widens the table nor takes a slot or the host algebra
+    put(_typed("size-c-base4-beside-assumed-base2000", [(4, 0, 4, True, False, False), (2000, 0, 2000, True, True, True)], 1, TYPES[0]), slots=1, table=16,
+        nsyms=4, prove="device", lds2="default", lds3="default", public="default")
+    # d: the reciprocal-symbol limit
+    put(_untyped("size-d-base1024-shared", [(1024, 0, 1024, True, True, False), (4, 0, 4, True, False, False)]), slots=2, nsyms=1023,
+        refused=["1023 reciprocal symbols", "at most 1022"])
+    d = [(1000, 0, 1000, True, False, False), (4, 0, 4, True, True, True)]          # the assumed range takes what the public amounts leave
+    for extra, name in ((MAX_SYMS - 999 - 1, "size-d-base1000-typed-at-the-limit"), (MAX_SYMS - 999, "size-d-base1000-typed-one-over")):
+        pairs = [(io, WIDE_TYPE + 7 * k, 1000 + k) for k in range(1, extra + 1) for io in (False, True)]
+        s = _typed(name, d, 1, WIDE_TYPE, pairs)
+        n = 999 + len({t for _, t, _ in s.pubs})
+        if n <= MAX_SYMS:
+            put(s, slots=1, table=1024, nsyms=n, prove="device", lds2="above", lds3="default", public="default")
+        else:
+            put(s, slots=1, nsyms=n, refused=["%d" % n, "reciprocal symbols", "at most 1022"])
+    # e: a wide table (base above 256) with 256 and with 257 ranges: the prover's second clause
+    for n, route in ((256, "device"), (257, "host")):
+        put(_untyped("size-e-base257-%dranges" % n, [(257, 0, 257, True, i % 2 == 1, False) for i in range(n)]), slots=1, table=512, nsyms=256, prove=route,
+            lds2="default", lds3="default", public="default")
+    # f: many small ranges around the 64 KiB edges
+    big = max(e["phase2_64k"], e["phase3_64k"], e["public_64k"]) + 50
+    n3 = e["phase3_64k"]
+    assert max(e["phase2_64k"], e["public_64k"]) <= n3 - 1 and big <= e["phase2_max"]      # else: pick these shapes again
+    put(_untyped("size-f-%dranges-below-phase3-64k" % (n3 - 1), _many(n3 - 1)), slots=1, table=16, nsyms=1, prove="device", lds2="above", lds3="default", public="above")
+    put(_untyped("size-f-%dranges-above-phase3-64k" % n3, _many(n3)), slots=1, table=16, nsyms=1, prove="device", lds2="above", lds3="above", public="above")
+    put(_untyped("size-f-%dranges-above-all-64k" % big, _many(big)), slots=1, table=16, nsyms=1, prove="device", lds2="above", lds3="above", public="above")
+    put(_typed("size-f-%dranges-above-all-64k-typed" % big, _many(big), 1, TYPES[0]), slots=1, table=16, nsyms=2, prove="device", lds2="above", lds3="above",
+        public="above")
+    # g: the last range count the device algebra serves, and the first it does not
+    g = e["phase2_max"]
+    put(_untyped("size-g-%dranges-prover-limit" % g, _many(g)), slots=1, table=16, nsyms=1, prove="device", lds2="above", lds3="above", public="above")
+    put(_untyped("size-g-%dranges-past-prover-limit" % (g + 1), _many(g + 1)), slots=1, table=16, nsyms=1, prove="host", lds2="over", lds3="above", public="above")
+    # h: the last nsyms + nr the one-kernel verifier serves, and the first it does not
+    h = e["public_max"]
+    assert h > g + 1
+    put(_untyped("size-h-%dranges-verifier-limit" % h, _many(h)), slots=1, table=16, nsyms=1, prove="host", lds2="over", lds3="above", public="above")
+    put(_untyped("size-h-%dranges-past-verifier-limit" % (h + 1), _many(h + 1)), slots=1, table=16, nsyms=1, prove="host", lds2="over", lds3="above", public="three")
+    # i: the binary range limit
+    for n in (MAX_BINARY_RANGES, MAX_BINARY_RANGES + 1):
+        rnd = random.Random("%s size binary %d" % (SEED, n))
+        ranges = [(0, 2, i % 2 == 1, False) for i in range(n)]
+        rows = _rows_of(ranges, True)
+        pubs, net = _publics(rnd, rows, 0, 0)
+        put(Schema("size-i-binary-%dranges" % n, True, ranges, True, pubs, 0, "NL", _witnesses(rnd, rows, net, True)), binary=True,
+            refused=None if n <= MAX_BINARY_RANGES else ["%d ranges" % n, "at most 1024 ranges"])
+    assert len({s.name for s in out}) == len(out) and all(s.wits is not None and len(s.wits) == 3 for s in out)
+    _SIZE.update(list=out, expect=exp)
+
+
+def size_edges():
+    """the setups at the native layer's size-class edges (not part of sweep()); the same list on every machine"""
+    _generate_size_edges()
+    return list(_SIZE["list"])
+
+
+def size_expect(name):
+    """what a size-edge member was built for:
+      refused   None, or the pieces of bppp_rp_create's message
+      slots     distinct digit bases (the base map's slots in use)
+      table     the class of the prover's reciprocal table (16 .. 1024)
+      nsyms     reciprocal symbols
+      prove     the route a default prove takes: "device" algebra or "host" algebra
+      lds2/3    the dynamic LDS of k_rpp_phase2 / k_rpp_phase3: "default" (<= 64 KiB), "above" (64 KiB .. 160 KiB), "over" (does not fit)
+      public    k_trrp_public for a batch of at most 1024 proofs: "default", "above", or "three" (the three-kernel route instead)"""
+    _generate_size_edges()
+    return dict(_SIZE["expect"][name])
 
 
 # ----------------------------------------------------------------------------- proofs (seeded as tests/test_few_rounds_host.py::inputs_of)

@@ -40,14 +40,17 @@ REFUSALS = {"value outside its range": RP_WIT_OUT_OF_RANGE, "amounts of some typ
 
 # ----------------------------------------------------------------------------- one setup: host side once, a native handle per test
 class Case:
-    def __init__(self, ec, name):
+    def __init__(self, ec, name, proved=(0, 1, 2)):
+        """proved: the witness rows the host proves (all three in the sweep; a setup of thousands of ranges proves one)"""
         self.s = s = SW.by_name(name)
         self.mod = BRP if s.binary else RP
         self.nrp = 2 if s.binary else 4
         self.st = SW.host_setup(PointBackend(ec), s)
         self.inputs = [SW.inputs_of(s, w, j) for j, w in enumerate(s.wits)]
-        self.prefixes = [SW.prefix_of(j) for j in range(3)]
-        self.proofs = [SW.host_prove(self.st, s, j) for j in range(3)]
+        self.proved = list(proved)
+        self.p_inputs = [self.inputs[j] for j in self.proved]
+        self.prefixes = [SW.prefix_of(j) for j in self.proved]
+        self.proofs = [SW.host_prove(self.st, s, j) for j in self.proved]
         self.files = [E.encode_proof(self.nrp, p) for p in self.proofs]
 
     def native(self, gpu):
@@ -91,10 +94,10 @@ def _host_status(c, st1, row):
     return RP_WIT_OK
 
 
-def _refused_rows(c):
-    """[(what, row, host setup of that row, the hook's public argument, moved)]: every live range at min - 1 and at max — the balance kept
-    through the public amount or an assumed range where the setup has one (`moved`), so that the range check is what refuses — and one
-    unbalanced row"""
+def _refused_rows(c, only=None):
+    """[(what, row, host setup of that row, the hook's public argument, moved)]: every live range (of the ranges `only`, if given) at min - 1 and
+    at max — the balance kept through the public amount or an assumed range where the setup has one (`moved`), so that the range check is what
+    refuses — and one unbalanced row"""
     s, st = c.s, c.st
     base = c.inputs[2]
     rows_of = SW._rows_of(s.ranges, s.binary)
@@ -107,7 +110,7 @@ def _refused_rows(c):
         return row
 
     for i, (sg, lo, hi1, asm) in enumerate(rows_of):
-        if asm:
+        if asm or (only is not None and i not in only):
             continue
         for what, v in (("range %d at min - 1" % i, lo - 1), ("range %d at max" % i, hi1 + 1)):
             delta = sg * (v - base[i][0])                          # what the signed sum of the amounts gains
@@ -130,55 +133,69 @@ def _refused_rows(c):
     return out
 
 
+def check_witness_kernel(c, nat, refused=None):
+    """the witness kernels on the three rows of the case and on `refused` (default: every live range at min - 1 and at max, and an unbalanced row)"""
+    s, st = c.s, c.st
+    refused = _refused_rows(c) if refused is None else refused
+    rows = c.inputs + [r for _, r, _, _, _ in refused]
+    sts = [st] * 3 + [st1 for _, _, st1, _, _ in refused]
+    own = st.net_public if s.binary else [v % N for _, _, v in s.pubs]
+    pubs = None
+    if s.binary or any(p is not None for _, _, _, p, _ in refused):
+        pubs = [own] * 3 + [own if p is None else p for _, _, _, p, _ in refused]
+    want = [_host_status(c, st1, row) for st1, row in zip(sts, rows)]
+    assert want[:3] == [RP_WIT_OK] * 3
+    for (what, _, _, _, moved), w in zip(refused, want[3:]):
+        if moved is None:                                      # the unbalanced row
+            assert w == (RP_WIT_BIN_UNBALANCED if s.binary else RP_WIT_UNBALANCED), what
+        else:                                                  # a range check, unless nothing could keep the balance
+            assert w == (RP_WIT_OUT_OF_RANGE if moved else RP_WIT_UNBALANCED), what
+    sc, dig, mul, mss, status = _witness_device(nat, rows, pubs)
+    assert status == want, [w for w, _, _, _, _ in refused]
+    for b in range(3):
+        if s.binary:
+            assert sc[b] == [(v % N, bl % N, 0) for v, bl in rows[b]], b
+            assert dig[b] == [int(d) for d in BRP.witness(st, rows[b])[1]], b
+        else:
+            assert (sc[b], dig[b], mul[b], mss[b]) == _witness_host(st, rows[b]), b
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_setup_and_witness_kernel(gpu, oracle_lib, name):
     c = _case(oracle_lib, name)
-    s, st = c.s, c.st
     nat = c.native(gpu)
     try:
-        refused = _refused_rows(c)
-        rows = c.inputs + [r for _, r, _, _, _ in refused]
-        sts = [st] * 3 + [st1 for _, _, st1, _, _ in refused]
-        own = st.net_public if s.binary else [v % N for _, _, v in s.pubs]
-        pubs = None
-        if s.binary or any(p is not None for _, _, _, p, _ in refused):
-            pubs = [own] * 3 + [own if p is None else p for _, _, _, p, _ in refused]
-        want = [_host_status(c, st1, row) for st1, row in zip(sts, rows)]
-        assert want[:3] == [RP_WIT_OK] * 3
-        for (what, _, _, _, moved), w in zip(refused, want[3:]):
-            if moved is None:                                      # the unbalanced row
-                assert w == (RP_WIT_BIN_UNBALANCED if s.binary else RP_WIT_UNBALANCED), what
-            else:                                                  # a range check, unless nothing could keep the balance
-                assert w == (RP_WIT_OUT_OF_RANGE if moved else RP_WIT_UNBALANCED), what
-        sc, dig, mul, mss, status = _witness_device(nat, rows, pubs)
-        assert status == want, [w for w, _, _, _, _ in refused]
-        for b in range(3):
-            if s.binary:
-                assert sc[b] == [(v % N, bl % N, 0) for v, bl in rows[b]], b
-                assert dig[b] == [int(d) for d in BRP.witness(st, rows[b])[1]], b
-            else:
-                assert (sc[b], dig[b], mul[b], mss[b]) == _witness_host(st, rows[b]), b
+        check_witness_kernel(c, nat)
     finally:
         nat.close()
 
 
 # ----------------------------------------------------------------------------- 3. the prover's bytes on four routes
+def check_prover_bytes(c, nat, after=lambda route: None):
+    """the four prover routes write the host protocol's bytes; `after(route)` is called behind each prove ("default", "comb device hash",
+    "comb host hash", "host algebra")"""
+    want = c.files
+    assert nat.prove_batch(c.p_inputs, c.prefixes) == want
+    after("default")
+    nat.set_option("comb_min", 1); nat.set_option("comb_bits", 7)
+    for host_oracle_max in (0, 2**64 - 1):                     # a comb table of the basis; hashing on the device, then on the host cores
+        nat.set_option("host_oracle_max", host_oracle_max)
+        assert nat.prove_batch(c.p_inputs, c.prefixes) == want, host_oracle_max
+        after("comb host hash" if host_oracle_max else "comb device hash")
+    nat.set_option("host_algebra", 1)
+    assert nat.prove_batch(c.p_inputs, c.prefixes) == want
+    after("host algebra")
+    nat.set_option("host_algebra", 0)
+    ok, status, _ = nat.verify_batch([cf for cf, _ in want], [pf for _, pf in want], SEED, want_status=True)
+    assert ok and status == [VALID] * len(want)
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_prover_writes_the_host_protocols_bytes(gpu, oracle_lib, name):
     c = _case(oracle_lib, name)
     nat = c.native(gpu)
     try:
-        want = c.files
-        assert nat.prove_batch(c.inputs, c.prefixes) == want
-        nat.set_option("comb_min", 1); nat.set_option("comb_bits", 7)
-        for host_oracle_max in (0, 2**64 - 1):                     # a comb table of the basis; hashing on the device, then on the host cores
-            nat.set_option("host_oracle_max", host_oracle_max)
-            assert nat.prove_batch(c.inputs, c.prefixes) == want, host_oracle_max
-        nat.set_option("host_algebra", 1)
-        assert nat.prove_batch(c.inputs, c.prefixes) == want
-        nat.set_option("host_algebra", 0)
-        ok, status, _ = nat.verify_batch([cf for cf, _ in want], [pf for _, pf in want], SEED, want_status=True)
-        assert ok and status == [VALID] * 3
+        check_prover_bytes(c, nat)
     finally:
         nat.close()
 
@@ -201,17 +218,22 @@ def _check_public_rows(st, coms, chs, got):
         assert g_["init_scalars"] == [by_point[p_] for p_ in coms]
 
 
+def check_public_scalars(c, tabs, name):
+    """bppp_trrp_public_device on the real challenges of the case's first proof, two random rows and the edge rows [1 .. 7], [N - 1] * 7"""
+    st, proof = c.st, c.proofs[0]
+    rnd = random.Random("schema sweep challenges " + name)
+    real, es = RP.verifier_challenges(st, proof, RP.sha256_oracle())
+    assert es == RP.verify_inputs(st, proof, RP.sha256_oracle())["es"]
+    chs = [real] + [[rnd.randrange(N) for _ in range(7)] for _ in range(2)] + [[1, 2, 3, 4, 5, 6, 7], [N - 1] * 7]
+    _check_public_rows(st, proof.coms, chs, tabs.public(chs))
+
+
 @pytest.mark.parametrize("name", RECIPROCAL)
 def test_device_derived_verifier_scalars_equal_the_host_derivation(gpu, oracle_lib, name):
     c = _case(oracle_lib, name)
-    st, proof = c.st, c.proofs[0]
-    tabs = RP.DeviceVerifierTables(gpu, st)
+    tabs = RP.DeviceVerifierTables(gpu, c.st)
     try:
-        rnd = random.Random("schema sweep challenges " + name)
-        real, es = RP.verifier_challenges(st, proof, RP.sha256_oracle())
-        assert es == RP.verify_inputs(st, proof, RP.sha256_oracle())["es"]
-        chs = [real] + [[rnd.randrange(N) for _ in range(7)] for _ in range(2)] + [[1, 2, 3, 4, 5, 6, 7], [N - 1] * 7]
-        _check_public_rows(st, proof.coms, chs, tabs.public(chs))
+        check_public_scalars(c, tabs, name)
     finally:
         tabs.close()
 
@@ -244,40 +266,46 @@ def test_public_scalars_three_kernel_route_equals_the_single_kernel(gpu, oracle_
 
 
 # ----------------------------------------------------------------------------- 5. verdicts and points
+def check_verdicts_and_points(gpu, oracle_lib, c, nat, pick=lambda L, ms: ms):
+    """the honest first proof of the case and its single-field mutations (`pick` may choose among them) through verify_batch, verify_each and
+    the combined point, against the host verifier over the CPU oracle"""
+    st, mod, nrp = c.st, c.mod, c.nrp
+    L = Layout(nat.shape, nrp)
+    lift = Lift(oracle_lib)
+    cf, pf = c.files[0]
+    ms = pick(L, _mutants(L, cf, pf))
+    files = [("honest", cf, pf)] + ms
+    want_ok, want_pts = [], []
+    for _, c_, p_ in files:                                    # the host protocol verifier over the CPU oracle, and the point it commits
+        coms = E.decode_commitments(L.nr, c_, lift.many)
+        proof = E.decode_proof(nrp, st.rounds, st.final_lens, coms[0], p_, lift.many)
+        assert proof is not None                               # every mutation keeps the files well-formed
+        want_ok.append(bool(mod.verify(st, proof, RP.sha256_oracle())))
+        want_pts.append(st.backend.last)
+    assert want_ok == [True] + [False] * len(ms)
+    assert [e is None for e in want_pts] == want_ok
+    coms_f, prfs = [c_ for _, c_, _ in files], [p_ for _, _, p_ in files]
+    lead = nat.shape["challenges_per_proof"] - nat.shape["rounds"]
+    for host_oracle_max in (None, 0):                          # the handle's default, then hashing on the device
+        if host_oracle_max is not None:
+            nat.set_option("host_oracle_max", host_oracle_max)
+        ok, status, _ = nat.verify_batch(coms_f, prfs, SEED, want_status=True)
+        assert not ok and status == [VALID] + [INVALID] * len(ms), host_oracle_max
+        each, pts = nat.verify_each(coms_f, prfs, want_points=True)
+        assert each == status and pts == want_pts, host_oracle_max
+        ok2, st2, chs, comb = _batch_full(gpu, nat, coms_f, prfs)
+        assert (ok2, st2) == (ok, status)
+        rhos = [_rho(nat, SEED, b, chs[b][lead - 1], chs[b][lead] if nat.shape["rounds"] else 0, prfs[b]) for b in range(len(files))]
+        assert comb == oracle_lib.inner_product([(r, e) for r, e in zip(rhos, want_pts) if e is not None]), host_oracle_max
+        assert nat.verify_batch(coms_f[:1], prfs[:1], SEED) and nat.verify_each(coms_f[:1], prfs[:1], want_points=True) == ([VALID], [None])
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_verdicts_and_points_on_single_field_mutations(gpu, oracle_lib, name):
     c = _case(oracle_lib, name)
-    st, mod, nrp = c.st, c.mod, c.nrp
     nat = c.native(gpu)
     try:
-        L = Layout(nat.shape, nrp)
-        lift = Lift(oracle_lib)
-        cf, pf = c.files[0]
-        ms = _mutants(L, cf, pf)
-        files = [("honest", cf, pf)] + ms
-        want_ok, want_pts = [], []
-        for _, c_, p_ in files:                                    # the host protocol verifier over the CPU oracle, and the point it commits
-            coms = E.decode_commitments(L.nr, c_, lift.many)
-            proof = E.decode_proof(nrp, st.rounds, st.final_lens, coms[0], p_, lift.many)
-            assert proof is not None                               # every mutation keeps the files well-formed
-            want_ok.append(bool(mod.verify(st, proof, RP.sha256_oracle())))
-            want_pts.append(st.backend.last)
-        assert want_ok == [True] + [False] * len(ms)
-        assert [e is None for e in want_pts] == want_ok
-        coms_f, prfs = [c_ for _, c_, _ in files], [p_ for _, _, p_ in files]
-        lead = nat.shape["challenges_per_proof"] - nat.shape["rounds"]
-        for host_oracle_max in (None, 0):                          # the handle's default, then hashing on the device
-            if host_oracle_max is not None:
-                nat.set_option("host_oracle_max", host_oracle_max)
-            ok, status, _ = nat.verify_batch(coms_f, prfs, SEED, want_status=True)
-            assert not ok and status == [VALID] + [INVALID] * len(ms), host_oracle_max
-            each, pts = nat.verify_each(coms_f, prfs, want_points=True)
-            assert each == status and pts == want_pts, host_oracle_max
-            ok2, st2, chs, comb = _batch_full(gpu, nat, coms_f, prfs)
-            assert (ok2, st2) == (ok, status)
-            rhos = [_rho(nat, SEED, b, chs[b][lead - 1], chs[b][lead] if nat.shape["rounds"] else 0, prfs[b]) for b in range(len(files))]
-            assert comb == oracle_lib.inner_product([(r, e) for r, e in zip(rhos, want_pts) if e is not None]), host_oracle_max
-            assert nat.verify_batch(coms_f[:1], prfs[:1], SEED) and nat.verify_each(coms_f[:1], prfs[:1], want_points=True) == ([VALID], [None])
+        check_verdicts_and_points(gpu, oracle_lib, c, nat)
     finally:
         nat.close()
 
