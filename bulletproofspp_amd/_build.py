@@ -14,7 +14,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib")
-HIP_SOURCES = ["msm.hip", "basis.hip", "comb.hip", "fold.hip", "rounds.hip", "nl.hip", "nlb.hip", "nlbatch.hip", "ip.hip", "trrp.hip", "rp.hip", "rpmixed.hip", "rpshare.hip", "rpeach.hip", "rpbind.hip", "rpcommit.hip", "rptally.hip", "rpexcess.hip", "rpexkeys.hip", "rpexpart.hip", "rpexagg.hip", "rpseal.hip", "rpscan_keys.hip", "rpcut.hip", "rpblock.hip", "rpprove.hip", "rpprove_dev.hip", "rpwitness.hip", "rpp_transcript.hip", "ipb.hip", "ipb_host.hip", "brpprove.hip", "brpprove_dev.hip", "glv.hip", "seedpoints.hip", "capi.hip"]
+HIP_SOURCES = ["msm.hip", "basis.hip", "comb.hip", "fold.hip", "rounds.hip", "nl.hip", "nlb.hip", "nlbatch.hip", "ip.hip", "trrp.hip", "rp.hip", "rpmixed.hip", "rpshare.hip", "rpeach.hip", "rpbind.hip", "rpcommit.hip", "rptally.hip", "rpexcess.hip", "rpexkeys.hip", "rpexpart.hip", "rpexagg.hip", "rpseal.hip", "rpscan_keys.hip", "rpcut.hip", "rpset.hip", "rpblock.hip", "rpprove.hip", "rpprove_dev.hip", "rpwitness.hip", "rpp_transcript.hip", "ipb.hip", "ipb_host.hip", "brpprove.hip", "brpprove_dev.hip", "glv.hip", "seedpoints.hip", "capi.hip"]
 TEST_SOURCES = ["testhooks.hip"]
 # product objects linked into the test library a second time: the hooks that drive RppTranscript and rpp_draws (csrc/rpp_transcript.hip, with the
 # bound headers of csrc/rpbind.hip) need the code itself, and the product library exports nothing but its C ABI

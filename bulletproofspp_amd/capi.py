@@ -52,6 +52,8 @@ SYMBOLS = [
     "bppp_rp_seal", "bppp_rp_seal_device", "bppp_rp_scan", "bppp_rp_scan_device",
     "bppp_rp_scan_keys", "bppp_rp_scan_keys_device",
     "bppp_rp_cut_through", "bppp_rp_cut_through_device",
+    "bppp_rp_set_create", "bppp_rp_set_restore", "bppp_rp_set_destroy", "bppp_rp_set_append", "bppp_rp_set_info", "bppp_rp_set_root", "bppp_rp_set_peaks",
+    "bppp_rp_set_path_bytes", "bppp_rp_set_paths", "bppp_rp_set_verify_paths",
 ]
 
 
@@ -252,6 +254,18 @@ def load_library() -> C.CDLL:
     lib.bppp_rp_scan_keys_device.argtypes = [vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, C.POINTER(sz), C.POINTER(C.c_uint64)]
     lib.bppp_rp_cut_through.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(RpCutCounts)]
     lib.bppp_rp_cut_through_device.argtypes = [vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(RpCutCounts)]
+    lib.bppp_rp_set_create.argtypes = [vp, sz, i, C.POINTER(vp)]
+    lib.bppp_rp_set_restore.argtypes = [vp, sz, C.c_uint64, vp, C.POINTER(vp)]
+    lib.bppp_rp_set_destroy.argtypes = [vp]
+    lib.bppp_rp_set_destroy.restype = None
+    lib.bppp_rp_set_append.argtypes = [vp, sz, vp]
+    lib.bppp_rp_set_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+    lib.bppp_rp_set_root.argtypes = [vp, vp]
+    lib.bppp_rp_set_peaks.argtypes = [vp, vp]
+    lib.bppp_rp_set_path_bytes.argtypes = [C.c_uint64]
+    lib.bppp_rp_set_path_bytes.restype = sz
+    lib.bppp_rp_set_paths.argtypes = [vp, sz, vp, vp]
+    lib.bppp_rp_set_verify_paths.argtypes = [vp, sz, C.c_uint64, vp, sz, vp, vp, vp, vp, C.POINTER(C.c_int)]
     lib.bppp_seed_candidate_x.argtypes =[C.c_char_p, sz, C.c_uint64, vp]
     lib.bppp_points_from_seed.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
     lib.bppp_points_from_seed_device.argtypes = [vp, C.c_char_p, sz, C.c_uint64, sz, vp, C.POINTER(C.c_uint64)]
@@ -435,6 +449,9 @@ RP_SEAL_OK, RP_SEAL_NOT_CANONICAL, RP_SEAL_ZERO = 0, 1, 2
 RP_SCAN_FOREIGN, RP_SCAN_OWNED, RP_SCAN_BAD_HINT, RP_SCAN_TAG_ONLY = 0, 1, 2, 3
 # BPPP_RP_CUT_*: an entry's verdict from bppp_rp_cut_through
 RP_CUT_KEPT, RP_CUT_SPENT, RP_CUT_KEPT_AGAIN = 0, 1, 2
+# BPPP_RP_SET_*: a membership path's verdict from bppp_rp_set_verify_paths; the longest row of a set
+RP_SET_OK, RP_SET_MISMATCH, RP_SET_BAD_INDEX, RP_SET_BAD_PADDING = 0, 1, 2, 3
+RP_SET_MAX_ROW_BYTES = 8192
 RP_SCAN_MAX_KEYS = 1 << 20                                     # BPPP_RP_SCAN_MAX_KEYS: view secrets of one bppp_rp_scan_keys call
 
 

@@ -1530,6 +1530,35 @@ class NativeRangeProofs:
             cap = nhits.value
         return [int(s) for s in status[:rows]], self._scan_keys_hits(nhits.value, cap, hk, hr, *out), int(ntag.value)
 
+    def commitment_set(self, row_bytes: int, keep_nodes: bool = True) -> "CommitmentSet":
+        """bppp_rp_set_create: an empty set commitment over rows of row_bytes bytes on this handle (CommitmentSet below)"""
+        return CommitmentSet(self, row_bytes, keep_nodes)
+
+    @staticmethod
+    def set_path_bytes(n: int) -> int:
+        """bppp_rp_set_path_bytes, asked of the library"""
+        from .capi import load_library
+        return int(load_library().bppp_rp_set_path_bytes(int(n)))
+
+    def set_verify_paths(self, row_bytes: int, n: int, root: bytes, idx: Sequence[int], rows: Sequence[bytes], paths: Sequence[bytes], want_status: bool = False):
+        """bppp_rp_set_verify_paths: is rows[q] leaf idx[q] of the set of n rows with this root, by paths[q]?  Stateless.  Returns accept, or
+        (accept, [SET_OK / SET_MISMATCH / SET_BAD_INDEX / SET_BAD_PADDING per query]) with want_status"""
+        import ctypes as C
+        import numpy as np
+        nq, pb = len(idx), set_path_bytes(n)
+        if len(rows) != nq or len(paths) != nq or any(len(r) != row_bytes for r in rows) or any(len(p) != pb for p in paths) or len(root) != 32:
+            raise ValueError("one row of row_bytes bytes and one path of 32 bit_length (n) bytes per index, and a root of 32 bytes")
+        ix = np.array([int(i) % 2**64 for i in idx] or [0], dtype=np.uint64)
+        rw = np.frombuffer(b"".join(rows) or b"\0", dtype=np.uint8)
+        pt = np.frombuffer(b"".join(paths) or b"\0", dtype=np.uint8)
+        rt = np.frombuffer(bytes(root), dtype=np.uint8)
+        st = np.zeros(max(nq, 1), dtype=np.uint32)
+        accept = C.c_int(-1)
+        vp = lambda x: C.c_void_p(x.ctypes.data)
+        rc = self.gpu.lib.bppp_rp_set_verify_paths(self.h, row_bytes, n, vp(rt), nq, vp(ix), vp(rw), vp(pt) if pb else None, vp(st) if want_status else None, C.byref(accept))
+        self.gpu._check(rc, "bppp_rp_set_verify_paths")
+        return (bool(accept.value), [int(v) for v in st[:nq]]) if want_status else bool(accept.value)
+
     def _excess_key_args(self, keys, msgs, sigs):
         import ctypes as C
         n = len(keys)
@@ -2849,3 +2878,205 @@ def basis_points(seed: bytes, count: int) -> List[Point]:
             continue
         out.append((x, p - y if y & 1 else y))
     return out
+
+
+# ---- set commitments (bppp_rp_set_*): an append-only Merkle mountain range over opaque rows; include/bppp.h states every message.  The functions
+# below restate it with hashlib, and CommitmentSet wraps the device-resident set
+SET_OK, SET_MISMATCH, SET_BAD_INDEX, SET_BAD_PADDING = 0, 1, 2, 3
+SET_MAX_ROW_BYTES = 8192
+
+
+def _set_domain(part: bytes, tag: bytes) -> bytes:
+    return hashlib.sha256(b"bppp/set/" + part + b"/v1" + tag).digest()
+
+
+def set_path_bytes(n: int) -> int:
+    """bppp_rp_set_path_bytes: 32 bit_length (n)"""
+    return 32 * int(n).bit_length()
+
+
+def set_leaf_host(tag: bytes, row: bytes) -> bytes:
+    """leaf = SHA-256 (Dl || row)"""
+    return hashlib.sha256(_set_domain(b"leaf", tag) + row).digest()
+
+
+def _set_peak_levels(n: int) -> List[int]:
+    """the levels of P_0 .. P_{m-1}: the set bits of n from the highest down"""
+    return [k for k in range(n.bit_length() - 1, -1, -1) if (n >> k) & 1]
+
+
+def set_peaks_host(tag: bytes, rows: Sequence[bytes], start: Optional[Tuple[int, Sequence[bytes]]] = None) -> List[bytes]:
+    """The peaks P_0 .. P_{m-1} after `rows` were appended to an empty set, or to the state start = (n, its peaks): a stack of (level, node) whose two
+    topmost nodes merge into SHA-256 (Dn || left || right) whenever their levels are equal"""
+    dl, dn = _set_domain(b"leaf", tag), _set_domain(b"node", tag)
+    n0, peaks0 = start if start is not None else (0, [])
+    stack = list(zip(_set_peak_levels(n0), peaks0))
+    if len(stack) != bin(n0).count("1"):
+        raise ValueError("a state of n rows has popcount (n) peaks")
+    for row in rows:
+        stack.append((0, hashlib.sha256(dl + row).digest()))
+        while len(stack) > 1 and stack[-1][0] == stack[-2][0]:
+            (k, right), (_, left) = stack.pop(), stack.pop()
+            stack.append((k + 1, hashlib.sha256(dn + left + right).digest()))
+    return [h for _, h in stack]
+
+
+def _set_bag(tag: bytes, peaks: Sequence[bytes]) -> bytes:
+    if not peaks:
+        return bytes(32)
+    db, acc = _set_domain(b"bag", tag), peaks[-1]
+    for p in reversed(peaks[:-1]):
+        acc = hashlib.sha256(db + p + acc).digest()
+    return acc
+
+
+def set_root_host(tag: bytes, row_bytes: int, n: int, peaks: Sequence[bytes]) -> bytes:
+    """root = SHA-256 (Dr || le64 (n) || le32 (row_bytes) || bag), bag = P_{m-1} folded leftwards by SHA-256 (Db || P_i || acc); zeros for n = 0"""
+    return hashlib.sha256(_set_domain(b"root", tag) + n.to_bytes(8, "little") + row_bytes.to_bytes(4, "little") + _set_bag(tag, peaks)).digest()
+
+
+def set_levels_host(tag: bytes, rows: Sequence[bytes]) -> List[List[bytes]]:
+    """every node of the set of `rows`: levels[k][j] = node (k, j) for j < n >> k"""
+    dn = _set_domain(b"node", tag)
+    levels = [[set_leaf_host(tag, r) for r in rows]]
+    while len(levels[-1]) > 1:
+        lo = levels[-1]
+        levels.append([hashlib.sha256(dn + lo[2 * j] + lo[2 * j + 1]).digest() for j in range(len(lo) // 2)])
+    return levels
+
+
+def _set_locate(n: int, i: int) -> Tuple[int, int, int]:
+    """(h, p, m) of leaf i < n: its peak P_p of height h among the m peaks"""
+    start = 0
+    for p, k in enumerate(_set_peak_levels(n)):
+        if i < start + (1 << k):
+            return k, p, bin(n).count("1")
+        start += 1 << k
+    raise ValueError("i is not below n")
+
+
+def set_path_host(tag: bytes, rows: Sequence[bytes], i: int, levels: Optional[List[List[bytes]]] = None) -> bytes:
+    """The path of leaf i among the rows: the h siblings inside its peak bottom-up, the bag of the peaks to the right as one hash (if any), the peaks
+    to the left nearest first, zero bytes up to 32 bit_length (n).  levels: set_levels_host (tag, rows), to share among calls"""
+    n = len(rows)
+    levels = levels if levels is not None else set_levels_host(tag, rows)
+    h, p, m = _set_locate(n, i)
+    peaks = [levels[k][(n >> k) - 1] for k in _set_peak_levels(n)]
+    out = [levels[s][(i >> s) ^ 1] for s in range(h)]
+    if p < m - 1:
+        out.append(_set_bag(tag, peaks[p + 1:]))
+    out += peaks[:p][::-1]
+    assert len(out) <= n.bit_length()
+    return b"".join(out).ljust(set_path_bytes(n), b"\0")
+
+
+def set_verify_path_host(tag: bytes, row_bytes: int, n: int, root: bytes, i: int, row: bytes, path: bytes) -> int:
+    """Host restatement of one query of bppp_rp_set_verify_paths; the first verdict that applies: SET_BAD_INDEX, SET_BAD_PADDING, SET_MISMATCH, SET_OK"""
+    if len(row) != row_bytes or len(path) != set_path_bytes(n):
+        raise ValueError("a row has row_bytes bytes and a path 32 bit_length (n)")
+    if not 0 <= i < n:
+        return SET_BAD_INDEX
+    h, p, m = _set_locate(n, i)
+    used = h + (1 if p < m - 1 else 0) + p
+    if any(path[32 * used:]):
+        return SET_BAD_PADDING
+    dn, db = _set_domain(b"node", tag), _set_domain(b"bag", tag)
+    acc, hs = set_leaf_host(tag, row), [path[32 * s:32 * s + 32] for s in range(used)]
+    for s in range(h):
+        acc = hashlib.sha256(dn + hs[s] + acc).digest() if (i >> s) & 1 else hashlib.sha256(dn + acc + hs[s]).digest()
+    if p < m - 1:
+        acc = hashlib.sha256(db + acc + hs[h]).digest()
+    for left in hs[used - p:]:
+        acc = hashlib.sha256(db + left + acc).digest()
+    got = hashlib.sha256(_set_domain(b"root", tag) + n.to_bytes(8, "little") + row_bytes.to_bytes(4, "little") + acc).digest()
+    return SET_OK if got == root else SET_MISMATCH
+
+
+class CommitmentSet:
+    """A device-resident set commitment on a range-proof handle (bppp_rp_set_create / _restore): append rows, read the root, the peaks and membership
+    paths.  keep_nodes=False keeps the peaks alone and serves no paths.  Close it before its handle."""
+
+    def __init__(self, nat: "NativeRangeProofs", row_bytes: int, keep_nodes: bool = True, _handle=None):
+        import ctypes as C
+        self.nat, self.row_bytes, self.keep_nodes, self.h = nat, int(row_bytes), bool(keep_nodes), None
+        if _handle is None:
+            _handle = C.c_void_p()
+            nat.gpu._check(nat.gpu.lib.bppp_rp_set_create(nat.h, self.row_bytes, 1 if keep_nodes else 0, C.byref(_handle)), "bppp_rp_set_create")
+        self.h = _handle
+
+    @classmethod
+    def restore(cls, nat: "NativeRangeProofs", row_bytes: int, n: int, peaks: Sequence[bytes]) -> "CommitmentSet":
+        """bppp_rp_set_restore: a frontier-only set of n rows that continues from the peaks another set exported"""
+        import ctypes as C
+        import numpy as np
+        if len(peaks) != bin(n).count("1") or any(len(p) != 32 for p in peaks):
+            raise ValueError("a state of n rows has popcount (n) peaks of 32 bytes")
+        pk = np.frombuffer(b"".join(peaks) or b"\0", dtype=np.uint8)
+        hnd = C.c_void_p()
+        nat.gpu._check(nat.gpu.lib.bppp_rp_set_restore(nat.h, int(row_bytes), int(n), C.c_void_p(pk.ctypes.data), C.byref(hnd)), "bppp_rp_set_restore")
+        return cls(nat, row_bytes, False, _handle=hnd)
+
+    def _live(self):
+        if not self.h or not self.nat.h:
+            raise ValueError("the set or its handle is closed")
+        return self.nat.gpu
+
+    def close(self):
+        if self.h:
+            self.nat.gpu.lib.bppp_rp_set_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def append(self, rows) -> None:
+        """bppp_rp_set_append: rows as a sequence of row_bytes-long byte strings, or as their concatenation"""
+        import ctypes as C
+        import numpy as np
+        g = self._live()
+        blob = bytes(rows) if isinstance(rows, (bytes, bytearray, memoryview)) else b"".join(rows)
+        if len(blob) % self.row_bytes or (not isinstance(rows, (bytes, bytearray, memoryview)) and any(len(r) != self.row_bytes for r in rows)):
+            raise ValueError("every row has row_bytes bytes")
+        arr = np.frombuffer(blob or b"\0", dtype=np.uint8)
+        g._check(g.lib.bppp_rp_set_append(self.h, len(blob) // self.row_bytes, C.c_void_p(arr.ctypes.data)), "bppp_rp_set_append")
+
+    def info(self) -> dict:
+        """bppp_rp_set_info: n, row_bytes, npeaks, store_bytes"""
+        import ctypes as C
+        g = self._live()
+        n, rb, npk, sb = C.c_uint64(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        g._check(g.lib.bppp_rp_set_info(self.h, C.byref(n), C.byref(rb), C.byref(npk), C.byref(sb)), "bppp_rp_set_info")
+        return {"n": int(n.value), "row_bytes": int(rb.value), "npeaks": int(npk.value), "store_bytes": int(sb.value)}
+
+    def root(self) -> bytes:
+        """bppp_rp_set_root"""
+        import ctypes as C
+        g = self._live()
+        buf = (C.c_uint8 * 32)()
+        g._check(g.lib.bppp_rp_set_root(self.h, C.cast(buf, C.c_void_p)), "bppp_rp_set_root")
+        return bytes(buf)
+
+    def peaks(self) -> List[bytes]:
+        """bppp_rp_set_peaks: P_0 .. P_{m-1}"""
+        import ctypes as C
+        g = self._live()
+        m = self.info()["npeaks"]
+        buf = (C.c_uint8 * max(32 * m, 1))()
+        g._check(g.lib.bppp_rp_set_peaks(self.h, C.cast(buf, C.c_void_p)), "bppp_rp_set_peaks")
+        out = bytes(buf)
+        return [out[32 * p:32 * p + 32] for p in range(m)]
+
+    def paths(self, idx: Sequence[int]) -> List[bytes]:
+        """bppp_rp_set_paths: the paths of the leaves idx against the rows there are now"""
+        import ctypes as C
+        import numpy as np
+        g = self._live()
+        pb, nq = set_path_bytes(self.info()["n"]), len(idx)
+        ix = np.array(list(idx) or [0], dtype=np.uint64)
+        buf = np.empty(max(nq * pb, 1), dtype=np.uint8)
+        g._check(g.lib.bppp_rp_set_paths(self.h, nq, C.c_void_p(ix.ctypes.data), C.c_void_p(buf.ctypes.data)), "bppp_rp_set_paths")
+        out = buf.tobytes()
+        return [out[pb * q:pb * q + pb] for q in range(nq)]

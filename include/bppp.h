@@ -1363,6 +1363,73 @@ int bppp_rp_cut_through_device(bppp_rp *rp, size_t rows, const void *d_coms_file
                                uint32_t *row_map /* host, [rows], may be NULL */, void *d_new_coms_files /* HBM, may be NULL */, void *d_new_entries /* HBM, [nnz] */,
                                uint64_t *block_claims /* host, [3][4] */, bppp_rp_cut_counts *counts /* host, required */);
 
+/* ---- set commitments: an append-only Merkle mountain range, its root and membership paths ----------------------------------------------------------
+ * What a block header commits to: "the output set after this block" or "the kernels of this block" as 32 bytes, a proof that a row is in that set,
+ * and the check of such proofs by someone who holds the 32 bytes alone.  Rows are opaque byte strings of one length per set, row_bytes in
+ * 1 .. BPPP_RP_SET_MAX_ROW_BYTES: a commitments file of any setup, a 33-byte key, a seal.  H = SHA-256.  The four domains are
+ * D* = SHA-256 (label || the handle's oracle_tag) for the labels "bppp/set/leaf/v1" (Dl), "bppp/set/node/v1" (Dn), "bppp/set/bag/v1" (Db) and
+ * "bppp/set/root/v1" (Dr): sets of handles with different tags have unrelated roots.
+ *
+ *   leaf_i       = H (Dl || row_i)
+ *   node (0, j)  = leaf_j;  node (k, j) = H (Dn || node (k - 1, 2j) || node (k - 1, 2j + 1)), 96 bytes; it covers the leaves [j 2^k, (j + 1) 2^k) and
+ *                  exists once (j + 1) 2^k <= n
+ *   PEAKS of n rows: for every set bit k of n, from the highest down, P = node (k, (n with its bits <= k cleared) >> k): P_0 .. P_{m-1}, m = popcount (n)
+ *   BAG          acc = P_{m-1};  for i = m - 2 .. 0: acc = H (Db || P_i || acc);  32 zero bytes for n = 0
+ *   ROOT         = H (Dr || le64 (n) || le32 (row_bytes) || acc), 76 bytes
+ *   PATH of leaf i among n >= 1 rows: exactly bit_length (n) hashes of 32 bytes (bppp_rp_set_path_bytes), in this order:
+ *                  1. the h siblings of the leaf inside its peak P_p of height h, bottom-up (sibling s is node (s, (i >> s) ^ 1));
+ *                  2. if p < m - 1, the bag of P_{p+1} .. P_{m-1} as ONE hash;
+ *                  3. P_{p-1}, .., P_0, the nearest first;
+ *                  4. zero bytes up to the length (h + p + 1 <= bit_length (n) always).
+ *                The verifier hashes upwards: the leaf with its siblings (the path's hash on the left where bit s of i is set), then
+ *                acc = H (Db || acc || the right bag), then acc = H (Db || P || acc) for each peak to the left, then the root's message.
+ * None of this depends on how the rows were split into appends.
+ *
+ * THE SET is the device-resident thing; every buffer below is on the host.
+ * bppp_rp_set_create: an empty set on rp's context.  keep_nodes = 1 stores every node in HBM — one grow-only array per level, 32 bytes a node, 64 bytes
+ *   a row in the limit (an array that must grow at least doubles, so up to twice that is allocated; while an append grows the arrays the old ones
+ *   stay alive beside the new ones, transiently up to three times that) — and can serve paths; n < 2^31 rows, subject to HBM.  keep_nodes = 0 stores the peaks alone (2 KB) and can append, give its root and its peaks; n < 2^63.  The set uses rp's workspace for
+ *   scratch and its tag for the domains, so it is destroyed BEFORE rp, and like rp it serves one call at a time.
+ * bppp_rp_set_restore: a frontier-only set of n rows that continues from exported state, peaks [popcount (n)][32] as bppp_rp_set_peaks wrote them
+ *   (may be NULL iff n = 0).  The peaks are taken as they are: a caller who restores checks the root against one it trusts.
+ * bppp_rp_set_append: rows [nrows][row_bytes] behind the rows there are.  nrows = 0 is BPPP_OK and touches nothing; nrows < 2^31 a call.  A refused
+ *   call (BPPP_ERR_ARG, or workspace or level arrays that cannot be allocated, BPPP_ERR_HIP) leaves the set as it was: the arrays grow all or
+ *   nothing, and the set can be used and appended to afterwards.  One launch hashes the leaves (one lane a
+ *   row, ceil ((32 + row_bytes + 9) / 64) compressions), then one launch per EIGHT levels that have a new node builds the nodes above them through
+ *   LDS, whichever n the append starts from: at most 1 + ceil (bit_length (n + nrows) / 8) launches, one more on a frontier-only set.
+ * bppp_rp_set_info: rows, row_bytes, popcount (n) and the bytes of HBM the store (or the frontier) holds; any out pointer may be NULL.
+ * bppp_rp_set_root: the 32 bytes of the root of the rows there are.  bppp_rp_set_peaks: peaks [popcount (n)][32], P_0 first; nothing for n = 0.
+ * bppp_rp_set_path_bytes: 32 bit_length (n); host only, no handle.
+ * bppp_rp_set_paths: paths [nq][bppp_rp_set_path_bytes (n)] of the leaves idx [nq], against the set's current n.  BPPP_ERR_ARG on a frontier-only
+ *   set, and for any idx >= n: bppp_last_error names the first such index and nothing is written.  nq < 2^31.
+ * bppp_rp_set_verify_paths: stateless — what a light client or a validator holding only a header runs.  Query q: is rows [q][row_bytes] leaf
+ *   idx [q] of the set of n rows with this root, by paths [q][bppp_rp_set_path_bytes (n)]?  status [nq] (may be NULL), the first that applies:
+ *     BPPP_RP_SET_BAD_INDEX (2)    idx >= n
+ *     BPPP_RP_SET_BAD_PADDING (3)  a non-zero byte behind the hashes the path uses
+ *     BPPP_RP_SET_MISMATCH (1)     the root computed from the row and the path differs
+ *     BPPP_RP_SET_OK (0)
+ *   *accept = 1 iff every query is OK (nq = 0: 1).  One lane a query, about 2 bit_length (n) compressions and the leaf's.  n < 2^63, nq < 2^31.
+ * Errors: BPPP_ERR_ARG for a NULL handle, set or required buffer, a closed context, row_bytes outside 1 .. 8192 ("row_bytes = .. is outside"),
+ * keep_nodes other than 0 or 1, a size at or above its limit ("a full store holds fewer than 2^31", "a set holds fewer than 2^63", "is 2^31 or more").
+ * bppp_last_error of the handle's context gives the text. */
+#define BPPP_RP_SET_OK 0u
+#define BPPP_RP_SET_MISMATCH 1u
+#define BPPP_RP_SET_BAD_INDEX 2u
+#define BPPP_RP_SET_BAD_PADDING 3u
+#define BPPP_RP_SET_MAX_ROW_BYTES 8192
+typedef struct bppp_rp_set bppp_rp_set;
+int bppp_rp_set_create(bppp_rp *rp, size_t row_bytes, int keep_nodes, bppp_rp_set **set);
+int bppp_rp_set_restore(bppp_rp *rp, size_t row_bytes, uint64_t n, const uint8_t *peaks /* [popcount (n)][32] */, bppp_rp_set **set);
+void bppp_rp_set_destroy(bppp_rp_set *set);
+int bppp_rp_set_append(bppp_rp_set *set, size_t nrows, const uint8_t *rows /* [nrows][row_bytes] */);
+int bppp_rp_set_info(const bppp_rp_set *set, uint64_t *n, size_t *row_bytes, size_t *npeaks, size_t *store_bytes);
+int bppp_rp_set_root(bppp_rp_set *set, uint8_t root[32]);
+int bppp_rp_set_peaks(bppp_rp_set *set, uint8_t *peaks /* [popcount (n)][32] */);
+size_t bppp_rp_set_path_bytes(uint64_t n);
+int bppp_rp_set_paths(bppp_rp_set *set, size_t nq, const uint64_t *idx /* [nq] */, uint8_t *paths /* [nq][32 bit_length (n)] */);
+int bppp_rp_set_verify_paths(bppp_rp *rp, size_t row_bytes, uint64_t n, const uint8_t root[32], size_t nq, const uint64_t *idx, const uint8_t *rows, const uint8_t *paths,
+                             uint32_t *status /* [nq], may be NULL */, int *accept);
+
 /* ---- one comb table for the handles of a basis family --------------------------------------------------------------------------
  * Every setup's basis [g | H | G] is a prefix of the point stream its points came from (see bppp_rp_verify_mixed), and the comb table
  * is laid out tab[window][point][multiple]: the table of the longest basis of a stream contains the table of every shorter one (same
