@@ -457,7 +457,12 @@ int bppp_trrp_create(bppp_ctx *ctx, int flavour, int has_types, size_t nlen, siz
 
 int bppp_trrp_public_device(bppp_trrp *o, size_t batch, const void *d_challenges, void *d_q, void *d_sp, void *d_pub_norm, void *d_pub_lin_c,
                             void *d_init_scalars) {
-  return bppp::trrp_public_run(o, batch, d_challenges, d_q, d_sp, d_pub_norm, d_pub_lin_c, d_init_scalars, nullptr);
+  // synchronous on return like every other entry point (the verifiers inside the library queue trrp_public_run itself and drain at their own tail)
+  const int rc = bppp::trrp_public_run(o, batch, d_challenges, d_q, d_sp, d_pub_norm, d_pub_lin_c, d_init_scalars, nullptr);
+  if (!o || ctx_closed(o->ctx)) return rc;
+  if (rc) { ctx_drain(o->ctx); return rc; }
+  BPPP_HIP(o->ctx, hipStreamSynchronize(o->ctx->stream));
+  return BPPP_OK;
 }
 
 }  // extern "C"

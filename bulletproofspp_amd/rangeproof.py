@@ -797,7 +797,7 @@ class DeviceVerifierTables:
             pass
 
     def public_device(self, batch: int, d_challenges: int, d_q: int, d_sp: int, d_pub_norm: int, d_pub_lin_c: int, d_init_scalars: int):
-        """device pointers in, device arrays out (see include/bppp.h); asynchronous on the context's stream"""
+        """device pointers in, device arrays out (see include/bppp.h); the arrays are complete on return"""
         from .capi import _ptr
         self.gpu._check(self.gpu.lib.bppp_trrp_public_device(self.h, batch, _ptr(d_challenges), _ptr(d_q), _ptr(d_sp), _ptr(d_pub_norm), _ptr(d_pub_lin_c),
                                                              _ptr(d_init_scalars)), "bppp_trrp_public_device")

@@ -66,7 +66,14 @@ typedef struct bppp_ctx bppp_ctx;
 int bppp_ctx_create(int device, bppp_ctx **out);
 void bppp_ctx_destroy(bppp_ctx *ctx);
 /* run all work of this context on an existing hipStream_t (e.g. torch's current stream);
- * NULL = the context's own stream. */
+ * NULL = the context's own stream.  The call returns after the stream bound before has drained.
+ * With a caller's stream bound, the d_* inputs of a call may be produced by work the caller enqueued
+ * earlier on that stream and need not be complete when the library is entered: whatever reads them,
+ * kernels and copies alike, is ordered behind that work.  On return nothing of the call is in flight
+ * on any stream - the bound one, the null stream or the context's second stream - for refusals and
+ * failing return codes too, so outputs may be read from any stream at once.
+ * tests/test_gpu_stream_order.py holds both for every device entry point: inputs delivered late on
+ * a busy bound stream, outputs read off-stream on return. */
 int bppp_ctx_set_stream(bppp_ctx *ctx, void *hip_stream);
 const char *bppp_last_error(const bppp_ctx *ctx);
 const char *bppp_version(void);
@@ -311,8 +318,8 @@ int bppp_msm_glv_device(bppp_ctx *ctx, const void *d_scalars, const void *d_poin
  * bppp_trrp_public_device: d_challenges is [batch][7][4] = (e, x, r0, q, x', r1, t) per proof; outputs, all in HBM:
  *   d_q [batch][4], d_sp [batch][4], d_pub_norm [batch][nlen][4], d_pub_lin_c [batch][llen][4] and
  *   d_init_scalars [batch][4 + nranges][4] in the proof's commitment order blCom, rCom, dmCom, mCom, nComs...
- * — exactly the arrays bppp_nl_verify_batch_device reads (its pub_lin_x is all zero for these proofs).  Asynchronous on the
- * context's stream. */
+ * — exactly the arrays bppp_nl_verify_batch_device reads (its pub_lin_x is all zero for these proofs).  Synchronous on return
+ * like every other call: the five arrays are complete in HBM (it used to return with its kernels queued). */
 typedef struct bppp_trrp bppp_trrp;
 int bppp_trrp_create(bppp_ctx *ctx, int flavour, int has_types, size_t nlen, size_t llen, size_t nranges, const uint32_t *pos_kind,
                      const uint32_t *pos_range, const uint32_t *pos_slot, const uint32_t *pos_sym, const uint64_t *pos_coeff,
