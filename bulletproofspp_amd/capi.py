@@ -293,6 +293,7 @@ def load_test_library() -> C.CDLL:
     lib.bppp_test_last_mixed_msm_terms.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.bppp_test_last_sort_ranges.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_last_scatter_one_read.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.bppp_test_last_hist16.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_last_acc_sized.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_last_acc_fq29.argtypes = [vp, C.POINTER(C.c_int)]
     lib.bppp_test_fq29_op.argtypes = [vp, i, vp, vp, sz, vp, vp]

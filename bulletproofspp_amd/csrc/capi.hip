@@ -59,6 +59,7 @@ void MsmTune::from_env() {
   no_balance = env_flag("BPPP_MSM_NO_BALANCE");
   sort_ranges = env_int("BPPP_SORT_RANGES", sort_ranges);                      // 0 k_scatter, 2 / 4 k_scatter_ranges with that many bucket ranges per window
   scatter_one_read = env_switch("BPPP_SCATTER_ONE_READ", scatter_one_read);   // 0: k_scatter_ranges whatever the chunk length; else k_scatter_one_read where the plan allows it (the default)
+  hist16 = env_switch("BPPP_HIST16", hist16);                                  // 0: 32-bit per-chunk counts and prefixes always; else 16-bit ones where the plan allows it (MsmPlan::hist16, the default)
   acc_sized = env_switch("BPPP_ACC_SIZED", acc_sized);                         // 1 / 0: k_acc_points_sized for every / no MSM over arbitrary points; unset: plan_accumulate's default
   acc_fq29 = env_switch("BPPP_ACC_FQ29", acc_fq29);                            // 1 / 0: k_acc_points_sized29 (9 x 29-bit limbs) for every / no sized accumulation
   acc_fast = env_switch("BPPP_ACC_FAST", acc_fast);                            // 1 / 0: k_acc_points_sized29_fast / k_acc_points_sized29 for every fq29 accumulation

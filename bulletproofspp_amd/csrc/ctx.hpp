@@ -70,6 +70,7 @@ struct bppp_ctx {
   uint64_t last_mixed_terms = 0;     // terms of the last multi-setup MSM (bppp_test_last_mixed_msm_terms)
   int last_sort_ranges = -1;         // bucket ranges Q of the last general-pipeline MSM's scatter: 0 k_scatter, 2 / 4 k_scatter_ranges (bppp_test_last_sort_ranges)
   int last_scatter_one_read = -1;    // 1: the last general-pipeline MSM's scatter was k_scatter_one_read, 0: any other (bppp_test_last_scatter_one_read)
+  int last_hist16 = -1;              // 1: the last general-pipeline MSM's sort kept 16-bit per-chunk counts and prefixes (MsmPlan::hist16), 0: 32-bit words (bppp_test_last_hist16)
   int last_acc_sized = -1;           // 1: the last general-pipeline MSM accumulated whole buckets by size (k_order, k_acc_points_sized), 0: slices (bppp_test_last_acc_sized)
   int last_acc_fq29 = -1;            // 1: the last general-pipeline MSM ran k_acc_points_sized29 or k_acc_points_sized29_fast (fq29 accumulator), 0: any other accumulate kernel (bppp_test_last_acc_fq29)
   int last_windows = -1;             // digit rows W per scalar of the last MSM's plan, either route (bppp_test_last_windows)

@@ -88,7 +88,9 @@ __global__ void __launch_bounds__(256) k_digits(const uint32_t *__restrict__ sca
 // Both sort kernels read 8 consecutive u16 digits per lane with ONE 16-byte load (n is padded to a multiple of 8 in the
 // digit buffer's row stride), so each lane has 8 independent LDS atomics / stores in flight instead of a dependent
 // load -> atomic -> store chain per entry (the scattered stores are latency-, not bandwidth-bound).
-__global__ void k_hist(const uint16_t *__restrict__ dig, uint32_t n, uint32_t stride, int c, int CH, uint32_t *__restrict__ blockhist) {
+// h16 (MsmPlan::hist16: a ranged scatter's plan, no chunk longer than 65535 terms, so no count above that): the counts leave as 16-bit values,
+// eight per lane in one 16-byte store, in the same [row][chunk][bucket] order — half the bytes, in the front half of the allocation.
+__global__ void k_hist(const uint16_t *__restrict__ dig, uint32_t n, uint32_t stride, int c, int CH, uint32_t *__restrict__ blockhist, int h16) {
   extern __shared__ uint32_t lh[];
   const int M = 1 << (c - 1);
   const uint32_t nbw = blockIdx.x, ch = blockIdx.y;
@@ -115,6 +117,15 @@ __global__ void k_hist(const uint16_t *__restrict__ dig, uint32_t n, uint32_t st
     pk = pkn; j0 = jn;
   }
   __syncthreads();
+  if (h16) {                                                // M is 2^15 (a ranged scatter's plan): rows of 64 KiB, 16-byte aligned
+    uint4 *out16 = reinterpret_cast<uint4 *>(reinterpret_cast<uint16_t *>(blockhist) + ((size_t)nbw * CH + ch) * M);
+    const uint4 *l4 = reinterpret_cast<const uint4 *>(lh);
+    for (int t = threadIdx.x; t < M / 8; t += blockDim.x) {
+      const uint4 a = l4[2 * t], b = l4[2 * t + 1];
+      out16[t] = make_uint4(a.x | (a.y << 16), a.z | (a.w << 16), b.x | (b.y << 16), b.z | (b.w << 16));
+    }
+    return;
+  }
   uint32_t *out = blockhist + ((size_t)nbw * CH + ch) * M;
   for (int t = threadIdx.x; t < M; t += blockDim.x) out[t] = lh[t];
 }
@@ -145,6 +156,39 @@ __global__ void __launch_bounds__(256) k_count_tiles(uint32_t *__restrict__ bloc
   if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(tile_sums + blockIdx.x / (SCAN_TILE / 256), ws[0] + ws[1] + ws[2] + ws[3]);
+}
+// k_count_tiles on the 16-bit counts of k_hist (MsmPlan::hist16).  A lane takes TWO neighbouring buckets, one 32-bit word per chunk, so a
+// wavefront's requests stay 256 bytes wide, and a workgroup 512 buckets; M and FB are even, so both buckets lie in one window.  The exclusive
+// prefix goes back in place modulo 2^16: exact for a bucket of fewer than 65536 entries, and the scatters rebuild the prefixes of a larger one
+// from the wraps of its stored sequence (scatter_load_cursors16).  count[] and the tile sums are 32-bit, as k_count_tiles'.  The loads of
+// eight chunks are requested before the first prefix is stored (a load after a store to the same array would wait for it).
+__global__ void __launch_bounds__(256) k_count_tiles16(uint32_t *__restrict__ blockhist, int M, int CH, uint64_t FB, uint32_t *__restrict__ count,
+                                                       uint32_t *__restrict__ tile_sums) {
+  __shared__ uint32_t ws[4];
+  const uint64_t fb = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 2;
+  uint32_t s0 = 0, s1 = 0;
+  if (fb < FB) {
+    const uint64_t nbw = fb / M, mb = fb % M;
+    uint32_t *p = blockhist + ((size_t)nbw * CH * M + mb) / 2;        // the word that holds the two counts of chunk 0
+    const size_t row = (size_t)M / 2;                                 // words per chunk row
+    for (int ch0 = 0; ch0 < CH; ch0 += 8) {
+      uint32_t t[8];
+#pragma unroll
+      for (int k = 0; k < 8; k++) t[k] = ch0 + k < CH ? p[(size_t)(ch0 + k) * row] : 0u;
+#pragma unroll
+      for (int k = 0; k < 8; k++)
+        if (ch0 + k < CH) {
+          p[(size_t)(ch0 + k) * row] = (s0 & 0xFFFFu) | (s1 << 16);
+          s0 += t[k] & 0xFFFFu; s1 += t[k] >> 16;
+        }
+    }
+    *reinterpret_cast<uint2 *>(count + fb) = make_uint2(s0, s1);
+  }
+  uint32_t s = s0 + s1;
+  for (int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d, 64);
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(tile_sums + blockIdx.x / (SCAN_TILE / 512), ws[0] + ws[1] + ws[2] + ws[3]);
 }
 // An ITEM of the sized accumulation (section 3'): a bucket of at most ACC_CAP entries, or a piece of ACC_CAP entries (the last one: the rest) of
 // a larger one.  size_hist (the sized route only, else null; zero at launch: k_digits) counts the items by size: the tile's histogram in LDS,
@@ -297,6 +341,48 @@ BPPP_DI void scatter_load_cursors(const uint32_t *__restrict__ bh_row, const uin
     }
   }
 }
+// The cursors from the 16-bit prefixes of k_count_tiles16 (MsmPlan::hist16).  bh_row is the row of chunk ch of the window's CH rows of M values,
+// so chunk k's is bh_row - (ch - k) * M.  Eight buckets per 16-byte load of prefixes (r0 and count are multiples of 8), beside two loads of their
+// starts and the one start after them; a cursor is start[b] + the stored prefix.  A bucket of 65536 entries or more (start[b + 1] - start[b]) has
+// prefixes that wrapped.  Every chunk adds fewer than 65536 entries to it, so a stored prefix is below the one of the chunk before exactly when
+// it wrapped once more: the lane walks the bucket's stored values of chunks 1 .. ch (chunk 0 stores 0) and adds 65536 per decrease.  With
+// evenly spread digits no bucket is that large; n equal scalars have one per window.
+BPPP_DI uint32_t scatter_wraps(const uint16_t *__restrict__ at, uint32_t ch, uint32_t M) {
+  const uint16_t *p = at - (size_t)ch * M;
+  uint32_t wraps = 0, prev = 0;
+  for (uint32_t k = 1; k <= ch; k++) { const uint32_t v = p[(size_t)k * M]; wraps += v < prev ? 1u : 0u; prev = v; }
+  return wraps;
+}
+BPPP_DI void scatter_load_cursors16(const uint16_t *__restrict__ bh_row, uint32_t ch, uint32_t M, const uint32_t *__restrict__ st_row, uint32_t r0, uint32_t count,
+                                    uint32_t *lh) {
+  const uint4 *bh = reinterpret_cast<const uint4 *>(bh_row + r0);
+  const uint4 *st = reinterpret_cast<const uint4 *>(st_row + r0);
+  uint4 *lh4 = reinterpret_cast<uint4 *>(lh);
+  const uint32_t no = count >> 3;
+  for (uint32_t t0 = threadIdx.x; t0 < no; t0 += 4 * blockDim.x) {
+    uint4 a0[4], a1[4], b[4];
+    uint32_t a2[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const uint32_t t = t0 + i * blockDim.x;
+      a0[i] = a1[i] = b[i] = make_uint4(0u, 0u, 0u, 0u); a2[i] = 0u;
+      if (t < no) { a0[i] = st[2 * t]; a1[i] = st[2 * t + 1]; a2[i] = st_row[r0 + 8 * t + 8]; b[i] = bh[t]; }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const uint32_t t = t0 + i * blockDim.x;
+      if (t < no) {
+        const uint32_t s[9] = {a0[i].x, a0[i].y, a0[i].z, a0[i].w, a1[i].x, a1[i].y, a1[i].z, a1[i].w, a2[i]};
+        uint32_t pre[8] = {b[i].x & 0xFFFFu, b[i].x >> 16, b[i].y & 0xFFFFu, b[i].y >> 16, b[i].z & 0xFFFFu, b[i].z >> 16, b[i].w & 0xFFFFu, b[i].w >> 16};
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+          if (s[k + 1] - s[k] >= 65536u) pre[k] += scatter_wraps(bh_row + r0 + 8 * t + k, ch, M) << 16;
+        lh4[2 * t] = make_uint4(s[0] + pre[0], s[1] + pre[1], s[2] + pre[2], s[3] + pre[3]);
+        lh4[2 * t + 1] = make_uint4(s[4] + pre[4], s[5] + pre[5], s[6] + pre[6], s[7] + pre[7]);
+      }
+    }
+  }
+}
 // Placement: the entries of the pack of step j (digits pkv, sign byte sn) whose bucket lies in [r0, r0 + Mq); lh[b - b0] is bucket b's cursor
 // (b0 = r0 where LDS holds the range alone, 0 where it holds the window).
 BPPP_DI void scatter_place(const u32x4 pkv, uint32_t sn, uint32_t j, uint32_t hi, uint32_t M, uint32_t r0, uint32_t Mq, uint32_t flip, uint32_t *lh, uint32_t b0,
@@ -316,7 +402,7 @@ BPPP_DI void scatter_place(const u32x4 pkv, uint32_t sn, uint32_t j, uint32_t hi
 __global__ void __launch_bounds__(1024) k_scatter_ranges(const uint16_t *__restrict__ dig, const unsigned long long *__restrict__ negmask, uint32_t n,
                                                          uint32_t stride, int c, int CH, int Q, uint32_t U, int top,
                                                          const uint32_t *__restrict__ blockhist, const uint32_t *__restrict__ start,
-                                                         uint32_t *__restrict__ sorted) {
+                                                         uint32_t *__restrict__ sorted, int h16) {
   extern __shared__ uint32_t lh[];
   const uint32_t M = 1u << (c - 1), Mq = M / (uint32_t)Q;
   const uint32_t s = blockIdx.x & 7u, k = blockIdx.x >> 3, u = (k / (uint32_t)CH) * 8u + s, ch = k % (uint32_t)CH;
@@ -334,8 +420,9 @@ __global__ void __launch_bounds__(1024) k_scatter_ranges(const uint16_t *__restr
   uint32_t sneg8[SCATTER_AHEAD];
   scatter_prefetch(d, sgn, j0, step, hi, pk, sneg8);
   // cursors of the range (M = 2^15, Q <= 4: r0 and Mq are multiples of 4): all of a lane's loads (Mq / 4096 pairs, two at Q = 4) are in
-  // flight before the first sum is written to LDS
-  scatter_load_cursors(blockhist + ((size_t)nbw * CH + ch) * M, start + (size_t)nbw * M, r0, Mq, lh);
+  // flight before the first sum is written to LDS; h16 (MsmPlan::hist16): from 16-bit prefixes, eight buckets per load
+  if (h16) scatter_load_cursors16(reinterpret_cast<const uint16_t *>(blockhist) + ((size_t)nbw * CH + ch) * M, ch, M, start + (size_t)nbw * M, r0, Mq, lh);
+  else scatter_load_cursors(blockhist + ((size_t)nbw * CH + ch) * M, start + (size_t)nbw * M, r0, Mq, lh);
   __syncthreads();
   for (; j0 < hi; j0 += SCATTER_AHEAD * step) {
 #pragma unroll
@@ -365,7 +452,7 @@ __global__ void __launch_bounds__(1024) k_scatter_ranges(const uint16_t *__restr
 __global__ void __launch_bounds__(1024) k_scatter_one_read(const uint16_t *__restrict__ dig, const unsigned long long *__restrict__ negmask, uint32_t n,
                                                            uint32_t stride, int c, int CH, int Q, uint32_t W, int top,
                                                            const uint32_t *__restrict__ blockhist, const uint32_t *__restrict__ start,
-                                                           uint32_t *__restrict__ sorted) {
+                                                           uint32_t *__restrict__ sorted, int h16) {
   extern __shared__ uint32_t lh[];
   const uint32_t M = 1u << (c - 1);
   const uint32_t s = blockIdx.x & 7u, k = blockIdx.x >> 3, nbw = (k / (uint32_t)CH) * 8u + s, ch = k % (uint32_t)CH;
@@ -378,8 +465,9 @@ __global__ void __launch_bounds__(1024) k_scatter_one_read(const uint16_t *__res
   u32x4 pk[SCATTER_AHEAD];
   uint32_t sneg8[SCATTER_AHEAD];
   scatter_prefetch(d, sgn, j0, step, hi, pk, sneg8);
-  // cursors of the whole window (M is a multiple of 4)
-  scatter_load_cursors(blockhist + ((size_t)nbw * CH + ch) * M, start + (size_t)nbw * M, 0u, M, lh);
+  // cursors of the whole window (M is a multiple of 8), from 32-bit or (h16, MsmPlan::hist16) 16-bit prefixes
+  if (h16) scatter_load_cursors16(reinterpret_cast<const uint16_t *>(blockhist) + ((size_t)nbw * CH + ch) * M, ch, M, start + (size_t)nbw * M, 0u, M, lh);
+  else scatter_load_cursors(blockhist + ((size_t)nbw * CH + ch) * M, start + (size_t)nbw * M, 0u, M, lh);
   __syncthreads();
   const uint32_t Mq = M / (uint32_t)Q;
   for (uint32_t r0 = 0; r0 < M; r0 += Mq) {
@@ -1154,21 +1242,24 @@ static void msm_sort(bppp_ctx *ctx, const MsmPlan &p, const MsmWorkspace &ws, si
   hipStream_t st = ctx->stream;
   const size_t lds = sort_lds_bytes(p);
   const uint32_t n = (uint32_t)p.n;
-  k_hist<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(ws.dig, n, ws.stride, p.c, p.CH, ws.blockhist);
+  const int h16 = p.hist16 ? 1 : 0;                          // 16-bit counts and prefixes in the front half of blockhist (a ranged scatter's plan only)
+  k_hist<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(ws.dig, n, ws.stride, p.c, p.CH, ws.blockhist, h16);
   // flat: the (window, chunk) histograms of an instance are W * CH chunks of ONE bucket set (same memory layout)
-  k_count_tiles<<<dim3((unsigned)((p.FB + 255) / 256)), dim3(256), 0, st>>>(ws.blockhist, p.M, p.flat ? p.W * p.CH : p.CH, p.FB, ws.count, ws.tiles);
+  if (h16) k_count_tiles16<<<dim3((unsigned)((p.FB / 2 + 255) / 256)), dim3(256), 0, st>>>(ws.blockhist, p.M, p.CH, p.FB, ws.count, ws.tiles);
+  else k_count_tiles<<<dim3((unsigned)((p.FB + 255) / 256)), dim3(256), 0, st>>>(ws.blockhist, p.M, p.flat ? p.W * p.CH : p.CH, p.FB, ws.count, ws.tiles);
   k_scan_apply<<<dim3(p.ntiles), dim3(256), 0, st>>>(ws.count, p.FB, ws.tiles, ws.start, ws.size_hist);
   ctx->last_sort_ranges = p.Q;
   ctx->last_windows = p.W;
   ctx->last_scatter_one_read = p.one_read ? 1 : 0;
+  ctx->last_hist16 = h16;
   if (p.one_read) {
     // 8 slots x ceil(W / 8) windows x CH chunks; the cursors of all M buckets take the whole request, which leaves ONE workgroup per CU
     k_scatter_one_read<<<dim3(ranged_grid(p)), dim3(p.hist_threads), lds, st>>>(ws.dig, ws.negmask, n, ws.stride, p.c, p.CH, p.Q, (uint32_t)p.W, p.top, ws.blockhist,
-                                                                                ws.start, ws.sorted);
+                                                                                ws.start, ws.sorted, h16);
   } else if (p.Q) {
     // units (window, range); 8 slots x ceil(U / 8) units x CH chunks
     k_scatter_ranges<<<dim3(ranged_grid(p)), dim3(p.hist_threads), ranges_lds_bytes(p), st>>>(ws.dig, ws.negmask, n, ws.stride, p.c, p.CH, p.Q, ranges_units(p), p.top,
-                                                                                              ws.blockhist, ws.start, ws.sorted);
+                                                                                              ws.blockhist, ws.start, ws.sorted, h16);
   } else
     k_scatter<<<dim3((unsigned)p.NB, p.CH), dim3(p.hist_threads), lds, st>>>(ws.dig, ws.negmask, n, ws.stride, p.c, p.CH, p.W, ws.blockhist, ws.start, ws.sorted,
                                                                              p.flat ? (uint32_t)table_stride : 0u, p.top);

@@ -24,6 +24,7 @@ struct MsmTune {
   int hist_ch = 0;                 // BPPP_HIST_CH: chunks per digit row of the sort, 1..64
   int num_cus = 0;                 // the device's compute units (bppp_ctx_create), not from the environment
   int sort_ranges = 4;             // bucket ranges per window of the ranged scatter, BPPP_SORT_RANGES: 0 = k_scatter
+  int hist16 = 1;                  // per-chunk counts and cursors of a ranged scatter's sort as 16-bit values (MsmPlan::hist16), BPPP_HIST16: 0 = 32-bit words always
   int scatter_one_read = 1;        // the ranged scatter reads a chunk's digits once for all ranges (k_scatter_one_read), BPPP_SCATTER_ONE_READ: 0 = k_scatter_ranges always
   int acc_sized = -1;              // whole buckets by size (k_acc_points_sized), BPPP_ACC_SIZED: 1 = every one-MSM plan, 0 = none, -1 = the plans where it measured faster (plan_accumulate)
   int acc_fq29 = 1;                // the sized accumulation on 9 x 29-bit limbs (k_acc_points_sized29), BPPP_ACC_FQ29: not 0 = every sized plan (the default, by measurement: DESIGN.md 0.2), 0 = k_acc_points_sized on 10 x 26
@@ -164,6 +165,7 @@ struct MsmPlan {
   int ntiles;
   int Q;                       // bucket ranges per window of the ranged scatter (k_scatter_ranges, k_scatter_one_read); 0 = k_scatter
   bool one_read;               // ranged scatter from (window, chunk) workgroups that read their digits once (k_scatter_one_read)
+  bool hist16;                 // blockhist holds 16-bit counts, then 16-bit prefixes modulo 2^16 (k_hist, k_count_tiles16, the ranged scatters), in the front half of its allocation
   bool sized;                  // accumulate whole buckets in order of size (k_order, k_acc_points_sized) instead of slices of L entries
   bool fq29;                   // sized, with the accumulator in 9 x 29-bit limbs (k_acc_points_sized29)
   bool acc_fast;               // fq29, with the exception-free additions and one test per item (k_acc_points_sized29_fast)
@@ -231,6 +233,11 @@ inline void plan_sort(MsmPlan &p, const MsmTune &tune) {
   const uint64_t wgs = (uint64_t)p.W * p.CH, cus = (uint64_t)std::max(tune.num_cus, 1), last_round = wgs % cus;
   const bool full_rounds = wgs >= cus && !(last_round && 4 * last_round < cus);
   p.one_read = p.Q && tune.scatter_one_read && lane_steps <= (uint64_t)SCATTER_AHEAD && full_rounds;
+  // 16-bit per-chunk histograms under a ranged scatter: a chunk's count of a bucket is at most the chunk's length, and a bucket's prefix over
+  // the chunks is kept modulo 2^16 — exact for every bucket of fewer than 65536 entries; the scatters rebuild a larger ("wide") bucket's prefix
+  // from the wraps in its stored sequence (scatter_load_cursors16, msm.hip).  Half the bytes of k_hist's output, of k_count_tiles' pass in place
+  // and of the scatters' cursor loads.  The arrays take the front half of the blockhist allocation: carve() is the same either way.
+  p.hist16 = p.Q && chunk <= 65535 && tune.hist16 != 0;
 }
 
 // bucket reduction: k_reduce1/2 (Lw, WPW), k_reduce_groups (RG) or the marginal sums (marg, mg)

@@ -394,6 +394,12 @@ extern "C" int bppp_test_last_scatter_one_read(bppp_ctx *ctx, int *one_read) {
   return BPPP_OK;
 }
 
+extern "C" int bppp_test_last_hist16(bppp_ctx *ctx, int *hist16) {
+  if (!ctx || !hist16) return BPPP_ERR_ARG;
+  *hist16 = ctx->last_hist16;
+  return BPPP_OK;
+}
+
 extern "C" int bppp_test_last_acc_sized(bppp_ctx *ctx, int *sized) {
   if (!ctx || !sized) return BPPP_ERR_ARG;
   *sized = ctx->last_acc_sized;

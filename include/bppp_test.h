@@ -51,6 +51,9 @@ int bppp_test_last_sort_ranges(bppp_ctx *ctx, int *q);
 /* 1 = the ranged scatter of the last MSM of the general pipeline on this context read every chunk's digits once (k_scatter_one_read: no
  * chunk longer than the steps a lane holds in registers, and BPPP_SCATTER_ONE_READ not 0), 0 = k_scatter_ranges or k_scatter, -1 = none yet. */
 int bppp_test_last_scatter_one_read(bppp_ctx *ctx, int *one_read);
+/* 1 = the sort of the last MSM of the general pipeline on this context kept its per-chunk counts and prefixes as 16-bit values (a ranged
+ * scatter, no chunk longer than 65535 terms, and BPPP_HIST16 not 0), 0 = as 32-bit words, -1 = none yet. */
+int bppp_test_last_hist16(bppp_ctx *ctx, int *hist16);
 /* How the last MSM of the general pipeline on this context accumulated its buckets: 1 = whole buckets in order of size (k_order,
  * k_acc_points_sized; BPPP_ACC_SIZED, one MSM over arbitrary points only), 0 = slices of the sorted entries (k_acc_points, k_merge),
  * -1 = none yet. */
